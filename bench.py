@@ -57,7 +57,38 @@ def parse():
     ap.add_argument('--c5-batch', type=int, default=131072, help='GLOBAL batch of the c5_strong leg (N > 1); tests shrink it')
     ap.add_argument('--force-dist', action='store_true',
                     help='debug: take the process-group / all-reduce path even with one rank (RCCL smoke test on a 1-GPU box)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the headline train() call computed in its last step as DIR/<name>.npy '
+                         '(rank 0; at most 64 MB in all, per-trajectory arrays on a fixed seeded sample of rows when larger)')
     return ap.parse_args()
+
+
+DUMP_BUDGET_BYTES = 64_000_000
+
+
+def dump_outputs(ac, steps, path):
+    """The results of the timed actor_critic.train() call, as a caller of it sees them: the parameters after its last update
+    (theta, w), the mean reward of each timed update, and the last episode's rollout (final states, state trajectory, reward,
+    TD error, score of the policy).  Per-trajectory arrays keep the same rows of the shard: all of them when they fit the
+    budget, else a sorted sample drawn with a fixed seed (the same rows for the same arguments)."""
+    import numpy as np
+    import torch
+    torch.cuda.synchronize()
+    bufs = next(b for k, b in ac._train_bufs.items() if k[0] == 'train')
+    rb = bufs['rollout']
+    fixed = {'theta': np.ravel(np.asarray(ac.theta, dtype=np.float64)),
+             'w': np.ravel(ac.w).astype(np.float64),
+             'episode_reward': bufs['ep_reward'][:steps].cpu().numpy().astype(np.float64)}
+    per_traj = {'pi_last': ac._last_pi, 'pi_traj': rb['pi_traj'], 'reward': rb['reward'], 'delta': rb['delta'], 'g': rb['g']}
+    B = rb['pi_traj'].shape[0]
+    row_bytes = sum(t[0].numel() * t.element_size() for t in per_traj.values())
+    n = min(B, (DUMP_BUDGET_BYTES - 4096 - sum(a.nbytes for a in fixed.values())) // row_bytes)   # (4096: .npy headers)
+    if n < B:
+        idx = torch.as_tensor(np.sort(np.random.RandomState(0).choice(B, n, replace=False)), device=rb['pi_traj'].device)
+        per_traj = {k: t.index_select(0, idx) for k, t in per_traj.items()}
+    os.makedirs(path, exist_ok=True)
+    for name, a in list(fixed.items()) + [(k, t.cpu().numpy()) for k, t in per_traj.items()]:
+        np.save(os.path.join(path, name + '.npy'), a)
 
 
 def cpu_baseline(d, budget_s):
@@ -308,6 +339,8 @@ def main():
     B = args.batch // world if args.scaling == 'strong' else args.batch
     elapsed, theta_end, ac = training_leg(d, T, B, args.steps, args.warmup)
     value = world * B * T * args.steps / elapsed
+    if args.dump_outputs and rank == 0:
+        dump_outputs(ac, args.steps, args.dump_outputs)
     del ac
     other = None
     c5 = None

@@ -8,10 +8,20 @@ import os
 
 import numpy as np
 import pytest
+from threadpoolctl import threadpool_limits
 
 from oracle import mfg_oracle as O
 
 G = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden')
+
+
+@pytest.fixture(autouse=True)
+def _one_blas_thread():
+    """OpenBLAS splits a long dot product (V = phi . w has 33153 terms at d = 256) over its threads, and the partial sums
+    round differently for each thread count; the stored vectors were computed on one thread, so the bit-exact comparisons
+    run on one thread too, whatever the host's thread settings."""
+    with threadpool_limits(limits=1, user_api='blas'):
+        yield
 
 
 def load(name):
