@@ -104,7 +104,11 @@ __device__ __forceinline__ bool mt_accept(const GammaState& g, float x, float u,
   const float t = g.c * x;
   const float eps = t * (3.0f + t * (3.0f + t));  // v - 1, formed without cancellation
   const float x2 = x * x;
-  v = 1.0f + eps;
+  // v itself: 1 + eps cancels as t -> -1 (v = (1 + t)^3 -> 0; at 1 + t = 0.03 the sum keeps ~9 bits of v, below 1 + t = 4e-3
+  // none), which the accepted variate d v and the test ln(v) - eps inherit.  For t in [-1, -1/2] 1 + t is exact (Sterbenz),
+  // so the cube keeps v to a few ulp.  Only the cold path gets here with t < -1/2 (shapes below ~16: c |x| > 1/2).
+  const float tp = 1.0f + t;
+  v = t < -0.5f ? tp * tp * tp : 1.0f + eps;
   bool acc = u < 1.0f - 0.0331f * x2 * x2;
   if (!acc) {
     // log(v) - eps: series for small eps (large shapes), direct otherwise

@@ -2542,8 +2542,16 @@ static int status_error(unsigned bits) {
 // enqueueing leaves its peers' all-reduces without a partner (the private communicator has no watchdog).
 static thread_local bool g_status_check_deferred = false;
 
+// traj_offset + B <= 2^48: the id space of the Philox counter (MFG_TRAJ_ID_LIMIT, include/mfg_hip.h)
+static bool traj_ids_ok(uint64_t traj_offset, int64_t B) {
+  return traj_offset <= MFG_TRAJ_ID_LIMIT && (uint64_t)(B > 0 ? B : 0) <= MFG_TRAJ_ID_LIMIT - traj_offset;
+}
+
 static int launch_core(const CoreArgs& a_in, bool sample, bool td, int precision, hipStream_t st) {
   CoreArgs a = a_in;
+  if (!traj_ids_ok(a.traj_offset, a.B))
+    return fail(MFG_EINVAL, "trajectory ids traj_offset + B = %llu + %lld exceed 2^48 (MFG_TRAJ_ID_LIMIT)",
+                (unsigned long long)a.traj_offset, (long long)a.B);
   {
     const StatusWord sw = status_word();
     if (!sw.host) return fail(MFG_ELAUNCH, "%s", "status word allocation failed");
@@ -2778,6 +2786,7 @@ int mfg_draw_start(const float* mat_pi0, int64_t num_start, int64_t B, int d, ui
   REQUIRE(num_start > 0 && num_start <= 0x7FFFFFFF, "empty / oversized start-state table");
   REQUIRE(idx || pi0, "nothing to write");
   REQUIRE(!pi0 || mat_pi0, "null start-state table");
+  REQUIRE(traj_ids_ok(traj_offset, B), "trajectory ids traj_offset + B exceed 2^48 (MFG_TRAJ_ID_LIMIT)");
   hipLaunchKernelGGL(k_draw_start, dim3(grid_for(pi0 ? B * d : B, 256, 8)), dim3(256), 0, S(stream), mat_pi0, num_start, B, d,
                      seed, step, traj_offset, idx, pi0);
   return check_launch("draw_start");

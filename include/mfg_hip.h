@@ -47,6 +47,11 @@ enum {
 
 #define MFG_MAX_D 512
 
+/* Global trajectory ids traj_offset + b live in [0, 2^48): the Philox counter keeps 48 bits of the id (low 32 in c2, high 16
+ * in c3 below the draw block), so an id past 2^48 would draw another trajectory's actions.  Every entry point that takes a
+ * traj_offset fails with MFG_EINVAL when traj_offset + B > MFG_TRAJ_ID_LIMIT. */
+#define MFG_TRAJ_ID_LIMIT (1ull << 48)
+
 /* reward_kind for mfg_step_given_P / mfg_rollout */
 enum {
   MFG_REWARD_MFG_AC2 = 0,   /* sum_i pi_i sum_j P_ij^2 (pi_j - pi_i)   mfg_ac2.py:257-287 */

@@ -35,6 +35,11 @@ def O():
     return mfg_oracle
 
 
+def SR():
+    from oracle import sampler_ref
+    return sampler_ref
+
+
 def start_states(B, d, dev, seed=0):
     g = torch.Generator(device=dev)
     g.manual_seed(seed)
@@ -106,6 +111,8 @@ def test_fullsize_subsample_against_oracle(dev):
     assert np.max(np.abs(got_d - dl) / np.maximum(np.abs(dl), 1e-2)) < 1e-5
     got_g = out['g'][sel].cpu().numpy()
     assert np.max(np.abs(got_g - gg) / np.maximum(np.abs(gg), 1.0)) < 1e-5
+    # the actions themselves, element by element, against the sampler's restatement at the device's state of every step
+    SR().compare_rollout(P, out['pi_traj'][sel].cpu().numpy(), THETA, SHIFT, SCALE, 11, 0, sel.cpu().numpy().astype(np.uint64))
 
 
 def test_fullsize_split_invariance(dev):
@@ -234,6 +241,9 @@ def test_config_full_T_large_d(dev, d, B, T, nsub):
     assert np.max(np.abs(got_d - odl) / np.maximum(np.abs(odl), 1e-2)) < 1e-5
     got_g = sub['g'].cpu().numpy()
     assert np.max(np.abs(got_g - ogg) / np.maximum(np.abs(ogg), 1.0)) < 1e-5
+    # the slice's actions, element by element, against the sampler's restatement (k_core_large<2> / <4> keying)
+    SR().compare_rollout(P, sub['pi_traj'].cpu().numpy(), THETA, SHIFT, SCALE, 23, 0,
+                         np.arange(lo, lo + nsub, dtype=np.uint64))
 
 
 def _forward_with_masks(RO, params, pi, P, m3, m4):
@@ -286,9 +296,11 @@ def test_config_C4_irl_train_with_reward_net_in_the_loop(dev, mode, precision, t
     sc, sa = O().lr_scales(1, False)
     Gw_acc = np.zeros_like(w); Gt_acc = 0.0
     disc = 1.0
+    amb_c4 = 0                                                      # near ties of the element-wise action check
     for t in range(15):
         th = torch.tensor([theta], dtype=torch.float64, device=dev)
         P = o.sample_dirichlet(torch.as_tensor(pi, device=dev), th, 0.0, 1e4, seed=13, step=t, precision=precision).cpu().numpy()
+        amb_c4 += SR().compare(P, pi, theta, 0.0, 1e4, 13, t, 0, precision, max_ambiguous=1.0)['ambiguous']
         pn = O().transition(P, pi).astype(np.float32)
         drop = None
         if 'dropout' in reg and mode == 'step':
@@ -312,6 +324,7 @@ def test_config_C4_irl_train_with_reward_net_in_the_loop(dev, mode, precision, t
     if mode == 'rollout':
         w = w + 0.1 * sc * Gw_acc / (15 * B)
         theta = theta + 0.001 * sa * Gt_acc / (15 * B)
+    assert amb_c4 <= 2e-5 * 15 * B * d * d
     # fp32 reward kernel vs fp64 restatement: rewards agree to ~1e-6 absolute, so the updates agree to ~1e-9
     assert abs(float(np.ravel(ac.theta)[0]) - theta) < tol
     assert np.max(np.abs(ac.w[:, 0] - w)) < tol

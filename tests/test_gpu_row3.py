@@ -92,6 +92,10 @@ def test_row3_kernel_vs_the_oracle_directly(dev):
                       w=torch.as_tensor(w, device=dev), gamma=gamma, seed=99, first_step=5, traj_offset=1000, td=True, write_P=True)
     P = out['P'].cpu().numpy()
     assert np.max(np.abs(P.astype(np.float64).sum(-1) - 1)) < 5e-7
+    # the row3 kernel's actions, element by element, against the sampler's restatement (every step, from the odd step 5)
+    from oracle import sampler_ref
+    sampler_ref.compare_rollout(P, out['pi_traj'].cpu().numpy(), theta, shift, scale, 99, 5,
+                                np.arange(1000, 1000 + B, dtype=np.uint64))
     traj = O.batched_rollout_given_P(pi0, P, w, theta, shift, gamma=gamma)[0]
     assert np.allclose(out['pi_traj'].cpu().numpy(), traj, rtol=3e-7, atol=1e-12)
     pt = out['pi_traj'].cpu().numpy().astype(np.float64)
