@@ -5,5 +5,14 @@ Hot path: hand-written HIP kernels behind the C ABI of include/mfg_hip.h (csrc/)
 """
 from . import _lib  # noqa: F401
 
-__all__ = ['_lib']
+__all__ = ['_lib', 'population', 'ActorCriticPopulation']
+
+
+def __getattr__(name):
+    # the population module (K independent learners in the launches of one) imports torch: loaded on first use
+    if name in ('population', 'ActorCriticPopulation'):
+        import importlib
+        population = importlib.import_module(__name__ + '.population')
+        return population if name == 'population' else population.ActorCriticPopulation
+    raise AttributeError('module %r has no attribute %r' % (__name__, name))
 __version__ = '0.1.0'

@@ -17,6 +17,7 @@ MFG_MAX_D = 512
 REWARD_MFG_AC2, REWARD_SYNTHETIC, REWARD_EXTERNAL = 0, 1, 2
 ROLLOUT_WRITE_P, ROLLOUT_TD, ROLLOUT_DISCOUNT_POW, ROLLOUT_F64, TRAIN_APPLY = 1, 2, 4, 8, 16
 PRECISION_F64, PRECISION_MIXED = 0, 1
+POP_MAX_K = 65535                # MFG_POP_MAX_K: learners of one population call
 STATUS_MIXED_RANGE = 1
 ECOMM = -6                      # MFG_ECOMM: the call aborted its RCCL communicator, the handle is dead
 RN_TRAIN_MAX_TRAJ = 64          # MFG_RN_TRAIN_MAX_TRAJ
@@ -87,6 +88,10 @@ SIGNATURES = {
                                           _i32, _u64, _u32, _u64, _i32, _p, _p, _p, _p, _p, _p, _p, _sz, _p]),
     'mfg_train_episodes': (_i32, [_p, _i64, _p, _p, _i64, _i32, _i32, _i64, _i64, _i32, _p, _f64, _f64, _p, _f64, _i32, _u64, _u32,
                                   _u64, _i32, _f64, _f64, _p, _p, _p, _p, _p, _p, _sz, _p]),
+    'mfg_train_episodes_pop': (_i32, [_p, _i64, _p, _p, _i64, _i32, _i32, _i32, _i64, _i64, _i32, _p, _p, _p, _p, _f64, _i32, _p,
+                                      _u32, _u64, _i32, _p, _p, _p, _p, _p, _p, _p, _p, _sz, _p]),
+    'mfg_train_rollouts_pop': (_i32, [_p, _i64, _i64, _i32, _i32, _i32, _i64, _i64, _i32, _p, _p, _p, _p, _f64, _i32, _p, _u32, _u64,
+                                      _i32, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _sz, _p]),
     'mfg_dist_available': (_i32, []),
     'mfg_dist_unique_id': (_i32, [_p]),
     'mfg_dist_init': (_i32, [_p, _i32, _i32, C.POINTER(C.c_void_p)]),

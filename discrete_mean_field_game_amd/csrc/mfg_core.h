@@ -135,6 +135,20 @@ __device__ __forceinline__ int64_t core_src_row(const CoreArgs& a, int64_t b) {
   return a.start_idx ? start_row(a.start_idx[b], a.num_start) : b;
 }
 
+// the start-state draw of k_draw_start (mfg_kernels.hip) and its population form (mfg_population.hip): idx[b] and / or the rows
+__device__ __forceinline__ void draw_start_body(const float* __restrict__ mat, int64_t num_start, int64_t B, int d, uint64_t seed,
+                                                uint32_t step, uint64_t traj_offset, int32_t* __restrict__ idx_out,
+                                                float* __restrict__ out) {
+  const int64_t n = out ? B * d : B;
+  for (int64_t e = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; e < n; e += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t b = out ? e / d : e;
+    const int j = out ? (int)(e - b * d) : 0;
+    const int64_t row = start_draw_row(seed, step, traj_offset + (uint64_t)b, num_start);
+    if (idx_out && j == 0) idx_out[b] = (int32_t)row;
+    if (out) out[e] = mat[row * d + j];
+  }
+}
+
 __device__ __forceinline__ double reward_term(int kind, double pii, double pj, double p) {
   // contribution of element (i,j) BEFORE the factor pi_i (kind 0) / -0.5 pi_i (kind 1)
   return kind == MFG_REWARD_MFG_AC2 ? (pj - pii) * p * p : p * p;
@@ -474,7 +488,7 @@ template <bool SAMPLE, bool TD, bool FAST, int D, bool SUMS = false, int STEP = 
 #ifndef MFG_CORE_SMALL_WAVES_F64
 #define MFG_CORE_SMALL_WAVES_F64 3  // strict precision: 227 registers wanted; at 168 the third wave still pays (5.95 -> 5.80 ms at the bench shape)
 #endif
-__global__ __launch_bounds__(BLOCK, SUMS ? 2 : (FAST ? MFG_CORE_SMALL_WAVES : MFG_CORE_SMALL_WAVES_F64)) void k_core_small(CoreArgs a) {
+__device__ __forceinline__ void core_small_body(const CoreArgs& a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   MFG_STAMP0(8)
   MFG_STAMPB(0)
@@ -1179,6 +1193,8 @@ __global__ __launch_bounds__(BLOCK, SUMS ? 2 : (FAST ? MFG_CORE_SMALL_WAVES : MF
     MFG_STAMPB(1)
   }
 }
+template <bool SAMPLE, bool TD, bool FAST, int D, bool SUMS = false, int STEP = 0>
+__global__ __launch_bounds__(BLOCK, SUMS ? 2 : (FAST ? MFG_CORE_SMALL_WAVES : MFG_CORE_SMALL_WAVES_F64)) void k_core_small(CoreArgs a) { core_small_body<SAMPLE, TD, FAST, D, SUMS, STEP>(a); }
 
 inline size_t core_small_lds(int d, bool want_v, bool sample) {
   const int G = WAVE / d, TB = WAVES * G, dp = d | 1;

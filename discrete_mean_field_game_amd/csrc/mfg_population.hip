@@ -1,0 +1,176 @@
+// Population forms of the kernels of a training episode at d <= 64 (mfg_population.h): the start draw, the packed core kernel
+// (plain and SUMS), the gradient kernels and the row reduction with its update.  Each wrapper rebases the argument block to
+// learner k and runs the body of the single kernel (core_small_body, grad_*_body, reduce_partials_body, draw_start_body).
+#include <atomic>
+
+#include "mfg_core.h"
+#define MFG_GRAD_BODIES_ONLY
+#include "mfg_grad.h"
+#include "mfg_population.h"
+
+namespace mfg {
+
+template <class P>
+__device__ __forceinline__ P* pop_at(P* p, int64_t stride, int k) {
+  return p ? p + stride * k : p;
+}
+__device__ __forceinline__ double* pop_ws(double* p, const PopArgs& q, int k) {
+  return p ? reinterpret_cast<double*>(reinterpret_cast<char*>(p) + q.s_ws * k) : p;
+}
+
+// ---- packed core kernel: sampling, transition, reward, value, TD error, score (and the SUMS rows) of learner blockIdx.y ----
+template <bool FAST, int D, bool SUMS>
+__global__ __launch_bounds__(BLOCK, SUMS ? 2 : (FAST ? MFG_CORE_SMALL_WAVES : MFG_CORE_SMALL_WAVES_F64)) void k_core_small_pop(
+    CoreArgs a, PopArgs p) {
+  const int k = blockIdx.y;
+  CoreArgs b = a;
+  b.pi0 = pop_at(a.pi0, p.s_pi0, k);
+  b.theta = a.theta + k;
+  b.w = pop_at(a.w, p.F, k);
+  b.shift = p.shift[k];
+  b.alpha_scale = p.alpha_scale[k];
+  b.seed = p.seed[k];
+  b.pi_traj = pop_at(a.pi_traj, p.s_traj, k);
+  b.pi_next_out = pop_at(a.pi_next_out, p.s_state, k);
+  b.reward_out = pop_at(a.reward_out, p.s_n, k);
+  b.delta = pop_at(a.delta, p.s_n, k);
+  b.g = pop_at(a.g, p.s_n, k);
+  b.part_rows = pop_ws(a.part_rows, p, k);
+  core_small_body<true, true, FAST, D, SUMS, 0>(b);
+}
+
+template <bool FAST, int D, bool SUMS>
+static void go_pop(const CoreArgs& a, const PopArgs& p, int num_cus, size_t lds, hipStream_t st) {
+  // occupancy of this instantiation at this LDS size, cached per device (as launch_core_small does for the single kernel)
+  static std::atomic<size_t> cached_lds[64];
+  static std::atomic<int> cached_bpc[64];
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
+  if (cached_lds[dev].load() != lds + 1) {
+    int n = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_core_small_pop<FAST, D, SUMS>, BLOCK, lds) != hipSuccess || n < 1) n = 1;
+    cached_bpc[dev].store(n);
+    cached_lds[dev].store(lds + 1);
+  }
+  const int TB = WAVES * (WAVE / a.d);
+  const int grid = core_grid(a.B, TB, cached_bpc[dev].load() * (a.T == 1 ? 2 : MFG_CORE_OVERSUBSCRIBE), num_cus);
+  hipLaunchKernelGGL((k_core_small_pop<FAST, D, SUMS>), dim3((unsigned)grid, (unsigned)p.K), dim3(BLOCK), lds, st, a, p);
+}
+
+template <int D>
+static void dispatch_pop(const CoreArgs& a, const PopArgs& p, bool fast, int num_cus, size_t lds, hipStream_t st) {
+  if constexpr (D > 0) {
+    if (a.part_rows) {
+      if (fast) go_pop<true, D, true>(a, p, num_cus, lds, st);
+      else go_pop<false, D, true>(a, p, num_cus, lds, st);
+      return;
+    }
+  }
+  if (fast) go_pop<true, D, false>(a, p, num_cus, lds, st);
+  else go_pop<false, D, false>(a, p, num_cus, lds, st);
+}
+
+// Always the packed lane mapping: k_core_row3 is for batches that under-fill the machine, a population fills it (both
+// mappings give the same bits).  Training launches only (sampling + TD).
+int launch_core_small_pop(const CoreArgs& a, const PopArgs& p, bool fast, int num_cus, hipStream_t st) {
+  const int d = a.d;
+  if (d > WAVE) return MFG_EUNSUPPORTED;
+  const size_t lds = core_small_lds(d, a.w != nullptr, true);
+  if (d == 21) dispatch_pop<21>(a, p, fast, num_cus, lds, st);
+  else if (d == 15) dispatch_pop<15>(a, p, fast, num_cus, lds, st);
+  else if (!a.part_rows) dispatch_pop<0>(a, p, fast, num_cus, lds, st);
+  else return MFG_EUNSUPPORTED;  // (SUMS rows: compile-time d only, core_sums_rows)
+  return MFG_OK;
+}
+
+// ---- start-state draw (a9) of learner blockIdx.y ----
+__global__ void k_draw_start_pop(const float* __restrict__ mat, int64_t num_start, int64_t B, int d, uint32_t step,
+                                 uint64_t traj_offset, float* __restrict__ out, PopArgs p) {
+  const int k = blockIdx.y;
+  draw_start_body(mat, num_start, B, d, p.seed[k], step, traj_offset, nullptr, out + p.s_state * k);
+}
+
+void launch_draw_start_pop(int grid, const float* mat, int64_t num_start, int64_t B, int d, uint32_t step, uint64_t traj_offset,
+                           float* out, const PopArgs& p, hipStream_t st) {
+  hipLaunchKernelGGL(k_draw_start_pop, dim3((unsigned)grid, (unsigned)p.K), dim3(256), 0, st, mat, num_start, B, d, step,
+                     traj_offset, out, p);
+}
+
+// ---- batch sums of the update (+ the fused finish and update of the small-d kernel) ----
+__device__ __forceinline__ void pop_rebase_grad(GradArgs& a, const PopArgs& p, int k) {
+  a.pi += p.s_gpi * k;
+  a.delta += p.s_n * k;
+  a.g += p.s_n * k;
+  a.reward = pop_at(a.reward, p.s_n, k);
+  a.partial = pop_ws(a.partial, p, k);
+  if (a.counter) a.counter = reinterpret_cast<unsigned*>(reinterpret_cast<char*>(a.counter) + p.s_ws * k);
+  a.G = pop_at(a.G, p.F + 3, k);
+  a.w = pop_at(a.w, p.F, k);
+  a.theta = pop_at(a.theta, 1, k);
+  a.reward_acc = pop_at(a.reward_acc, p.s_acc, k);
+  a.lr_c = p.lr_c[k] * p.sc;
+  a.lr_a = p.lr_a[k] * p.sa;
+}
+
+template <int D>
+__global__ __launch_bounds__(BLOCK) void k_grad_mfma_small_pop(GradArgs a, PopArgs p) {
+  GradArgs b = a;
+  pop_rebase_grad(b, p, blockIdx.y);
+  grad_mfma_small_body<D, false>(b);
+}
+
+__global__ __launch_bounds__(BLOCK) void k_grad_partial_pop(GradArgs a, PopArgs p) {
+  GradArgs b = a;
+  pop_rebase_grad(b, p, blockIdx.z);
+  grad_partial_body(b);
+}
+
+template <int NPF>
+__global__ __launch_bounds__(BLOCK) void k_grad_mfma_pop(GradArgs a, int tpw, PopArgs p) {
+  GradArgs b = a;
+  pop_rebase_grad(b, p, blockIdx.z);
+  grad_mfma_body<NPF>(b, tpw);
+}
+
+__global__ __launch_bounds__(RP_SLICES* RP_OUT) void k_reduce_partials_pop(const double* __restrict__ partial, int64_t nsb,
+                                                                          int64_t FO, double* __restrict__ G, ReduceApply ap,
+                                                                          PopArgs p) {
+  const int k = blockIdx.y;
+  ReduceApply q = ap;
+  if (q.on) {
+    q.w = pop_at(ap.w, p.F, k);
+    q.theta = pop_at(ap.theta, 1, k);
+    q.reward_acc = pop_at(ap.reward_acc, p.s_acc, k);
+    q.lr_c = p.lr_c[k] * p.sc;
+    q.lr_a = p.lr_a[k] * p.sa;
+  }
+  reduce_partials_body(reinterpret_cast<const double*>(reinterpret_cast<const char*>(partial) + p.s_ws * k), nsb, FO, 0,
+                       G + FO * k, q);
+}
+
+void launch_grad_mfma_small_pop(int D, unsigned blocks, const GradArgs& a, const PopArgs& p, hipStream_t st) {
+  const dim3 grid(blocks, (unsigned)p.K);
+  if (D == 21) hipLaunchKernelGGL((k_grad_mfma_small_pop<21>), grid, dim3(BLOCK), 0, st, a, p);
+  else if (D == 15) hipLaunchKernelGGL((k_grad_mfma_small_pop<15>), grid, dim3(BLOCK), 0, st, a, p);
+  else hipLaunchKernelGGL((k_grad_mfma_small_pop<0>), grid, dim3(BLOCK), 0, st, a, p);
+}
+
+void launch_grad_partial_pop(unsigned nsb, unsigned nob, size_t lds, const GradArgs& a, const PopArgs& p, hipStream_t st) {
+  hipLaunchKernelGGL(k_grad_partial_pop, dim3(nsb, nob, (unsigned)p.K), dim3(BLOCK), lds, st, a, p);
+}
+
+void launch_grad_mfma_pop(int npf, unsigned nsb, unsigned ny, size_t lds, const GradArgs& a, int tpw, const PopArgs& p,
+                          hipStream_t st) {
+  const dim3 grid(nsb, ny, (unsigned)p.K);
+  switch (npf) {
+    case 2: hipLaunchKernelGGL((k_grad_mfma_pop<2>), grid, dim3(BLOCK), lds, st, a, tpw, p); break;
+    default: hipLaunchKernelGGL((k_grad_mfma_pop<0>), grid, dim3(BLOCK), lds, st, a, tpw, p); break;
+  }
+}
+
+void launch_reduce_partials_pop(unsigned nob, const double* partial, int64_t nsb, int64_t FO, double* G, const ReduceApply& ap,
+                                const PopArgs& p, hipStream_t st) {
+  hipLaunchKernelGGL(k_reduce_partials_pop, dim3(nob, (unsigned)p.K), dim3(RP_SLICES * RP_OUT), 0, st, partial, nsb, FO, G, ap, p);
+}
+
+}  // namespace mfg

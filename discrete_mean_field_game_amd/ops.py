@@ -463,6 +463,86 @@ def train_episodes(mat_pi0, pi, T, episodes, first_episode, constant, theta, shi
     return pi
 
 
+def _chk_pop(K, name, t, dtype):
+    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == dtype and t.is_contiguous() and t.numel() == K):
+        raise ValueError('%s: expected a contiguous %s device tensor of %d entries (one per learner)' % (name, dtype, K))
+
+
+def _chk_pop_shapes(K, B, d, T, episodes, theta, w, G, ws, bufs, reward_acc, mat_pi0):
+    """Shapes of the learner-major arrays of a population call: an undersized one would be written past its end."""
+    F = num_features(d)
+    want = dict(theta=(theta, (K,)), w=(w, (K, F)), G=(G, (K, F + 3)))
+    for key, t in bufs.items():
+        if t is None:
+            continue
+        shape = {'pi': (K, B, d), 'scratch': (K, B, d), 'pi_traj': (K, B, T + 1, d), 'pi_last': (K, B, d)}.get(key)
+        if shape is None:
+            shape = (K, B) if 'scratch' in bufs else (K, B, T)
+        want[key] = (t, shape)
+    if reward_acc is not None:
+        if not isinstance(reward_acc, torch.Tensor):
+            raise ValueError('reward_acc: expected a [K, episodes] fp64 device tensor or None')
+        want['reward_acc'] = (reward_acc, (K, max(int(episodes), 0)))
+    for name, (t, shape) in want.items():
+        if tuple(t.shape) != shape or not t.is_contiguous() or not t.is_cuda:
+            raise ValueError('%s: expected a contiguous device tensor of shape %s, got %s' % (name, shape, tuple(t.shape)))
+    if mat_pi0.dim() != 2 or mat_pi0.shape[1] != d:
+        raise ValueError('mat_pi0: expected [num_start, %d]' % d)
+    if ws.dim() != 2 or ws.shape[0] != K or not ws.is_contiguous() or ws.dtype != torch.float64:
+        raise ValueError('ws: expected a contiguous fp64 [K, slice] workspace')
+
+
+def train_episodes_pop(mat_pi0, pi, T, episodes, first_episode, constant, theta, shifts, alpha_scales, w, gamma, lr_critic,
+                       lr_actor, seeds, G, ws, bufs, reward_kind=L.REWARD_MFG_AC2, first_step=0, traj_offset=0, reward_acc=None,
+                       precision='mixed'):
+    """train_episodes for a population of K independent learners in the launches of one (mfg_train_episodes_pop): `pi`
+    [K,Bk,d], theta [K], w [K,F], G [K,F+3], ws [K, slice] fp64 (one learner's slice per row); shifts, alpha_scales,
+    lr_critic, lr_actor fp64 and seeds int64 (read as uint64) device arrays [K]; bufs = dict(scratch [K,Bk,d] f32,
+    reward [K,Bk] f32, delta / g [K,Bk] f64); reward_acc [K,episodes] fp64 or None."""
+    _chk_f32(mat_pi0, 'mat_pi0'); _chk_f32(pi, 'pi'); _chk_f64(theta, 'theta'); _chk_f64(w, 'w'); _chk_f64(G, 'G')
+    K, B, d = pi.shape
+    bufs = dict(bufs, pi=pi)
+    for name, t in (('shifts', shifts), ('alpha_scales', alpha_scales), ('lr_critic', lr_critic), ('lr_actor', lr_actor)):
+        _chk_pop(K, name, t, torch.float64)
+    _chk_pop(K, 'seeds', seeds, torch.int64)
+    _chk_pop_shapes(K, B, d, T, episodes, theta, w, G, ws, bufs, reward_acc, mat_pi0)
+    L.check(L.lib().mfg_train_episodes_pop(mat_pi0.data_ptr(), mat_pi0.shape[0], pi.data_ptr(), bufs['scratch'].data_ptr(), B, K,
+                                           d, int(T), int(episodes), int(first_episode), int(bool(constant)), theta.data_ptr(),
+                                           shifts.data_ptr(), alpha_scales.data_ptr(), w.data_ptr(), float(gamma),
+                                           int(reward_kind), seeds.data_ptr(), int(first_step), int(traj_offset),
+                                           L.PRECISIONS[precision], lr_critic.data_ptr(), lr_actor.data_ptr(),
+                                           bufs['reward'].data_ptr(), bufs['delta'].data_ptr(), bufs['g'].data_ptr(),
+                                           G.data_ptr(), _ptr(reward_acc), ws.data_ptr(), ws.shape[1] * ws.element_size(),
+                                           _stream()), 'mfg_train_episodes_pop')
+    return pi
+
+
+def train_rollouts_pop(mat_pi0, T, episodes, first_episode, constant, theta, shifts, alpha_scales, w, gamma, G, ws, bufs,
+                       lr_critic, lr_actor, seeds, reward_kind=L.REWARD_MFG_AC2, first_step=0, traj_offset=0, discount_pow=False,
+                       reward_acc=None, precision='mixed'):
+    """train_rollouts for a population of K independent learners (mfg_train_rollouts_pop): bufs = dict(pi_traj
+    [K,Bk,T+1,d] f32, pi_last [K,Bk,d] f32 (optional), reward [K,Bk,T] f32, delta / g [K,Bk,T] f64); the other arrays as
+    for train_episodes_pop."""
+    _chk_f32(mat_pi0, 'mat_pi0'); _chk_f64(theta, 'theta'); _chk_f64(w, 'w'); _chk_f64(G, 'G')
+    K, B, d = bufs['pi_traj'].shape[0], bufs['pi_traj'].shape[1], mat_pi0.shape[1]
+    for name, t in (('shifts', shifts), ('alpha_scales', alpha_scales), ('lr_critic', lr_critic), ('lr_actor', lr_actor)):
+        _chk_pop(K, name, t, torch.float64)
+    _chk_pop(K, 'seeds', seeds, torch.int64)
+    _chk_pop_shapes(K, B, d, T, episodes, theta, w, G, ws, bufs, reward_acc, mat_pi0)
+    flags = L.ROLLOUT_DISCOUNT_POW if discount_pow else 0
+    if L.PRECISIONS[precision] == L.PRECISION_F64:
+        flags |= L.ROLLOUT_F64
+    L.check(L.lib().mfg_train_rollouts_pop(mat_pi0.data_ptr(), mat_pi0.shape[0], B, K, d, int(T), int(episodes),
+                                           int(first_episode), int(bool(constant)), theta.data_ptr(), shifts.data_ptr(),
+                                           alpha_scales.data_ptr(), w.data_ptr(), float(gamma), int(reward_kind),
+                                           seeds.data_ptr(), int(first_step), int(traj_offset), flags, lr_critic.data_ptr(),
+                                           lr_actor.data_ptr(), bufs['pi_traj'].data_ptr(), _ptr(bufs.get('pi_last')),
+                                           bufs['reward'].data_ptr(), bufs['delta'].data_ptr(), bufs['g'].data_ptr(),
+                                           G.data_ptr(), _ptr(reward_acc), ws.data_ptr(), ws.shape[1] * ws.element_size(),
+                                           _stream()), 'mfg_train_rollouts_pop')
+    return bufs
+
+
 def reward_net_struct(net, dropout=None):
     """mfg_reward_net_t for a networks.RewardNet (device pointers of its parameters; keep the module alive while in use)."""
     if dropout is None:

@@ -1,0 +1,220 @@
+"""A population of K independent actor-critic learners trained in the launches of one (mfg_train_episodes_pop /
+mfg_train_rollouts_pop, include/mfg_hip.h).
+
+The reference trains such learners one after another: mfg_ac2.gridsearch sweeps theta, shift and alpha (mfg_ac2.py:673-689),
+and every result is a choice among several seeds and learning rates.  ActorCriticPopulation holds K learners, each with its own
+theta, critic weights w, shift, alpha_scale, learning rates, Philox seed and `batch` trajectories, and trains them in lock-step:
+learner k ends with exactly (bit for bit) what `actor_critic(theta_k, shift_k, alpha_k, d, batch=batch, seed=seed_k)` with
+the same w gives after the same train() calls.
+
+Start states are drawn on the device, as actor_critic does for batch > 1 (hence batch >= 2 here).  Single GPU, d <= 64,
+in-kernel rewards ('mfg_ac2', 'synthetic'); IRL and several GPUs are out of scope.
+
+The instance owns one ops.Context: its sticky mixed-range status word (include/mfg_hip.h, mfg_status) is shared by the K
+learners, so ONE learner whose policy leaves the fp32 range of mixed-precision sampling stops the population's next launch
+(train() raises MfgError; clear_status() resets it; precision='f64' has no such range).
+"""
+from __future__ import annotations
+
+import functools
+import os
+
+import numpy as np
+import torch
+
+from . import _lib as L
+from . import ops
+from .mfg_ac2 import EPISODE_STEPS, actor_critic
+
+REWARDS = {'mfg_ac2': L.REWARD_MFG_AC2, 'synthetic': L.REWARD_SYNTHETIC}
+
+
+def broadcast(name, value, K, dtype=np.float64):
+    """`value` (a scalar or K values) as a NumPy array [K] of `dtype`."""
+    a = np.asarray(value, dtype=dtype)
+    if a.ndim == 0:
+        return np.full(K, a, dtype=dtype)
+    a = a.reshape(-1)
+    if a.shape[0] != K:
+        raise ValueError('%s: expected a scalar or %d values (one per learner), got %d' % (name, K, a.shape[0]))
+    return a.copy()
+
+
+def check_args(K, d, batch, update_every, reward, precision, episode_steps):
+    """Validation of the constructor's arguments (no GPU needed)."""
+    if K < 1 or K > L.POP_MAX_K:
+        raise ValueError('population size %d outside [1, %d]' % (K, L.POP_MAX_K))
+    if not 1 <= d <= 64:
+        raise ValueError('d=%d: populations cover d <= 64 (one wave per trajectory already fills the machine beyond)' % d)
+    if batch < 2:
+        raise ValueError('batch=%d: a population draws its start states on the device, which actor_critic does from batch 2 '
+                         'on' % batch)
+    if update_every not in ('step', 'rollout'):
+        raise ValueError("update_every must be 'step' or 'rollout'")
+    if reward not in REWARDS:
+        raise ValueError("reward must be 'mfg_ac2' or 'synthetic' (in-kernel rewards; IRL is not supported)")
+    if precision not in ('mixed', 'f64'):
+        raise ValueError("precision must be 'mixed' or 'f64'")
+    if episode_steps < 1:
+        raise ValueError('episode_steps must be >= 1')
+
+
+def _with_ctx(method):
+    """Run a method with the instance's own context bound (as actor_critic's public methods do)."""
+    @functools.wraps(method)
+    def bound(self, *args, **kwargs):
+        prev = self._ctx.bind_scoped()
+        try:
+            return method(self, *args, **kwargs)
+        finally:
+            self._ctx.restore(prev)
+    return bound
+
+
+class ActorCriticPopulation:
+
+    def __init__(self, thetas, shifts=0.16, alpha_scales=12000, d=21, *, batch, seeds=None, w0=None, pi0=None,
+                 path_to_dir=None, update_every='step', reward='mfg_ac2', precision='mixed', episode_steps=EPISODE_STEPS,
+                 device=None, verbose=0):
+        th = np.asarray(thetas, dtype=np.float64).reshape(-1)
+        K = th.shape[0]
+        check_args(K, int(d), int(batch), update_every, reward, precision, int(episode_steps))
+        if not torch.cuda.is_available():
+            raise L.MfgError('ActorCriticPopulation needs a ROCm GPU: the HIP hot path has no CPU fallback')
+        L.lib()
+        ops.init()
+        self.device = torch.device(device) if device is not None else torch.device('cuda', torch.cuda.current_device())
+        self._ctx = ops.Context(self.device)
+        self.d, self.batch, self.episode_steps = int(d), int(batch), int(episode_steps)
+        self.update_every, self.reward, self.precision, self.verbose = update_every, reward, precision, verbose
+        self.reward_kind = REWARDS[reward]
+        F = ops.num_features(self.d)
+        self.shifts = broadcast('shifts', shifts, K)
+        self.alpha_scales = broadcast('alpha_scales', alpha_scales, K)
+        self.seeds = broadcast('seeds', np.arange(K) if seeds is None else seeds, K, np.uint64)
+        dev = self.device
+        self._theta = torch.as_tensor(th.copy(), device=dev)
+        # critic weights first, start states second: actor_critic's np.random consumption order, learner by learner
+        if w0 is None:
+            w = np.stack([np.asarray(actor_critic.init_w(None, self.d), dtype=np.float64).reshape(-1) for _ in range(K)])
+        else:
+            w = np.asarray(w0, dtype=np.float64)
+            w = np.broadcast_to(w.reshape(1, -1), (K, F)) if w.size == F else w.reshape(K, F)
+        self._w = torch.as_tensor(np.ascontiguousarray(w), device=dev)
+        # the start-state table, resolved as actor_critic resolves it, shared by all learners
+        if pi0 is not None:
+            table = np.array(pi0, dtype=np.float64)[:, 0:self.d]
+        else:
+            if path_to_dir is None:
+                path_to_dir = os.getcwd() + '/train_normalized_round2'
+            if os.path.isdir(path_to_dir):
+                holder = type('_Table', (), {})()
+                holder.d = self.d
+                actor_critic.init_pi0(holder, path_to_dir=path_to_dir)
+                table = holder.mat_pi0
+            else:
+                rs = np.random.RandomState(0)   # actor_critic's synthetic table: Dirichlet(1) rows via '%.3e' text
+                m = rs.dirichlet(np.ones(self.d), size=64)
+                table = np.array([[float('%.3e' % v) for v in row] for row in m])
+        self.mat_pi0 = table
+        self._mat_pi0_dev = torch.as_tensor(np.ascontiguousarray(table, dtype=np.float32), device=dev)
+        self._seeds_dev = torch.as_tensor(self.seeds.view(np.int64), device=dev)
+        self._shifts_dev = torch.as_tensor(self.shifts, device=dev)
+        self._alphas_dev = torch.as_tensor(self.alpha_scales, device=dev)
+        self._rng_step = 0  # Philox step counter, shared by the learners (they advance in lock-step)
+        self._bufs = None
+
+    # ------------------------------------------------------------------ state
+    @property
+    def K(self):
+        return int(self._theta.shape[0])
+
+    @property
+    def thetas(self):
+        return self._theta.cpu().numpy().copy()
+
+    @property
+    def w(self):
+        return self._w.cpu().numpy().copy()
+
+    def _buffers(self):
+        K, B, d, T = self.K, self.batch, self.d, self.episode_steps
+        if self._bufs is None:
+            dev, F = self.device, ops.num_features(d)
+            # one learner's workspace slice: what actor_critic allocates for B T samples, rounded up to 256 bytes
+            sb = (max(int(L.lib().mfg_workspace_bytes(B * T, d)), 8) + 255) // 256 * 256
+            b = {'G': torch.zeros(K, F + 3, dtype=torch.float64, device=dev),
+                 'ws': torch.zeros(K, sb // 8, dtype=torch.float64, device=dev)}
+            if self.update_every == 'step':
+                b['pi'] = torch.empty(K, B, d, dtype=torch.float32, device=dev)
+                b['run'] = {'scratch': torch.empty(K, B, d, dtype=torch.float32, device=dev),
+                            'reward': torch.empty(K, B, dtype=torch.float32, device=dev),
+                            'delta': torch.empty(K, B, dtype=torch.float64, device=dev),
+                            'g': torch.empty(K, B, dtype=torch.float64, device=dev)}
+            else:
+                b['run'] = {'pi_traj': torch.empty(K, B, T + 1, d, dtype=torch.float32, device=dev),
+                            'pi_last': torch.empty(K, B, d, dtype=torch.float32, device=dev),
+                            'reward': torch.empty(K, B, T, dtype=torch.float32, device=dev),
+                            'delta': torch.empty(K, B, T, dtype=torch.float64, device=dev),
+                            'g': torch.empty(K, B, T, dtype=torch.float64, device=dev)}
+            self._bufs = b
+        return self._bufs
+
+    # ------------------------------------------------------------------ training
+    @_with_ctx
+    def train(self, num_episodes, gamma=1, constant=0, lr_critic=0.1, lr_actor=0.001, *, first_episode=0):
+        """`num_episodes` episodes of every learner (mfg_ac2.py:448-539; update per env step or per episode as chosen at
+        construction).  lr_critic / lr_actor: scalars or [K].  Returns a NumPy array [K, num_episodes] of what
+        actor_critic.train books per episode (step mode: the sum of the T updates' mean rewards; rollout mode: the one
+        update's mean reward).  The Philox step counter carries over to the next call."""
+        K, T = self.K, self.episode_steps
+        num_episodes = int(num_episodes)
+        if num_episodes < 0:
+            raise ValueError('num_episodes < 0')
+        lrc = torch.as_tensor(broadcast('lr_critic', lr_critic, K), device=self.device)
+        lra = torch.as_tensor(broadcast('lr_actor', lr_actor, K), device=self.device)
+        acc = torch.zeros(K, max(num_episodes, 1), dtype=torch.float64, device=self.device)
+        if num_episodes == 0:
+            return np.zeros((K, 0))
+        b = self._buffers()
+        if self.update_every == 'step':
+            ops.train_episodes_pop(self._mat_pi0_dev, b['pi'], T, num_episodes, first_episode, constant == 1, self._theta,
+                                   self._shifts_dev, self._alphas_dev, self._w, gamma, lrc, lra, self._seeds_dev, b['G'],
+                                   b['ws'], b['run'], reward_kind=self.reward_kind, first_step=self._rng_step,
+                                   reward_acc=acc, precision=self.precision)
+        else:
+            ops.train_rollouts_pop(self._mat_pi0_dev, T, num_episodes, first_episode, constant == 1, self._theta,
+                                   self._shifts_dev, self._alphas_dev, self._w, gamma, b['G'], b['ws'], b['run'], lrc, lra,
+                                   self._seeds_dev, reward_kind=self.reward_kind, first_step=self._rng_step,
+                                   reward_acc=acc, precision=self.precision)
+        self._rng_step += num_episodes * T
+        out = acc.cpu().numpy()
+        if self.precision == 'mixed' and self._ctx.status(synchronize=True):
+            raise L.MfgError('a mixed-precision sampling launch of this population ran with |theta| (1/2 + |shift|) > 86 '
+                             '(or theta not finite): its outputs are NaN; use precision=\'f64\', then clear_status()')
+        return out
+
+    def status(self, synchronize=True) -> int:
+        """Bits of this population's status word (0 = healthy), shared by its K learners."""
+        return self._ctx.status(synchronize)
+
+    def clear_status(self):
+        self._ctx.clear_status()
+
+    def learner(self, k):
+        """An actor_critic holding learner k's parameters, table and Philox position (for evaluate / generate_trajectory
+        / further single training).  Its construction leaves the global np.random stream as it was."""
+        if not 0 <= k < self.K:
+            raise IndexError('learner %d of %d' % (k, self.K))
+        state = np.random.get_state()
+        try:
+            ac = actor_critic(float(self.thetas[k]), float(self.shifts[k]), float(self.alpha_scales[k]), self.d,
+                              pi0=self.mat_pi0, batch=self.batch, seed=int(self.seeds[k]), update_every=self.update_every,
+                              reward=self.reward, precision=self.precision, device=self.device, verbose=self.verbose,
+                              episode_steps=self.episode_steps)
+        finally:
+            np.random.set_state(state)
+        ac.w = self.w[k]
+        ac.theta = np.array([self.thetas[k]]) if self._rng_step else float(self.thetas[k])
+        ac._rng_step = self._rng_step
+        return ac

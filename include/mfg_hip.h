@@ -405,6 +405,38 @@ int mfg_train_episodes(const float* mat_pi0, int64_t num_start, float* pi_io, fl
                        int precision, double lr_critic, double lr_actor, float* reward, double* delta, double* g, double* G,
                        double* reward_acc, void* workspace, size_t workspace_bytes, mfg_stream_t stream);
 
+/* Populations: K independent learners trained in lock-step, every launch of an episode serving all K (single GPU,
+ * d <= 64, in-kernel reward).  Learner k of a population call gives, bit for bit in every output, what the single-learner
+ * call (mfg_train_episodes / mfg_train_rollouts) gives with B = Bk, the same traj_offset and workspace_bytes, and learner
+ * k's seed, theta, w, shift, alpha_scale and learning rates -- the reference's independent trainings (mfg_ac2.py:448-539,
+ * one per grid point / seed / learning rate of mfg_ac2.gridsearch, mfg_ac2.py:673-689) in the launches of one.
+ *   B = Bk trajectories per learner; per-learner scalars are device arrays [K]: seed (uint64), shift, alpha_scale,
+ *   lr_critic, lr_actor (learner k's rates in episode e: lr_critic[k] x, lr_actor[k] x the schedule of mfg_train_rollouts).
+ *   Learner-major arrays: theta [K], w [K,F], G [K,F+3], reward_acc [K,episodes] (may be NULL); step mode pi_io /
+ *   pi_scratch [K,Bk,d], reward / delta / g [K,Bk]; rollout mode pi_traj [K,Bk,T+1,d], pi_last [K,Bk,d] (may be NULL),
+ *   reward / delta / g [K,Bk,T].  mat_pi0 [num_start,d] is shared.
+ *   workspace_bytes: ONE learner's slice, a multiple of 256 (the buffer holds K slices back to back).
+ * Checked before anything is launched: 1 <= K <= MFG_POP_MAX_K, no null pointer, d <= 64 (MFG_EUNSUPPORTED beyond: one wave
+ * per trajectory fills the machine there), an in-kernel reward_kind, the Philox step counter does not wrap (MFG_EINVAL);
+ * the slice holds the update's partial rows (MFG_EWORKSPACE).  The sticky mixed-range status word (mfg_status) is per
+ * device / context: one learner whose policy left the fp32 range blocks the population's next mixed-precision launch. */
+#define MFG_POP_MAX_K 65535
+/* step mode (update_every = 'step', mfg_ac2.py:478-526): mfg_train_episodes for K learners */
+int mfg_train_episodes_pop(const float* mat_pi0, int64_t num_start, float* pi_io, float* pi_scratch, int64_t B, int K, int d, int T,
+                           int64_t episodes, int64_t first_episode, int constant, double* theta, const double* shift,
+                           const double* alpha_scale, double* w, double gamma, int reward_kind, const uint64_t* seed,
+                           uint32_t first_step, uint64_t traj_offset, int precision, const double* lr_critic,
+                           const double* lr_actor, float* reward, double* delta, double* g, double* G, double* reward_acc,
+                           void* workspace, size_t workspace_bytes, mfg_stream_t stream);
+/* rollout mode (one update per episode, mfg_ac2.py:460-526): mfg_train_rollouts for K learners (flags: MFG_ROLLOUT_F64 /
+ * MFG_ROLLOUT_DISCOUNT_POW) */
+int mfg_train_rollouts_pop(const float* mat_pi0, int64_t num_start, int64_t B, int K, int d, int T, int64_t episodes,
+                           int64_t first_episode, int constant, double* theta, const double* shift, const double* alpha_scale,
+                           double* w, double gamma, int reward_kind, const uint64_t* seed, uint32_t first_step,
+                           uint64_t traj_offset, int flags, const double* lr_critic, const double* lr_actor, float* pi_traj,
+                           float* pi_last, float* reward, double* delta, double* g, double* G, double* reward_acc,
+                           void* workspace, size_t workspace_bytes, mfg_stream_t stream);
+
 /* Weights of the reward network of networks.py:46-81 as device pointers (layouts as for mfg_reward_net_forward). */
 typedef struct mfg_reward_net {
   int k1, f2, k2, n3, n4;
