@@ -5,14 +5,18 @@ Hot path: hand-written HIP kernels behind the C ABI of include/mfg_hip.h (csrc/)
 """
 from . import _lib  # noqa: F401
 
-__all__ = ['_lib', 'population', 'ActorCriticPopulation']
+__all__ = ['_lib', 'population', 'ActorCriticPopulation', 'irl_population', 'AC_IRLPopulation']
 
 
 def __getattr__(name):
-    # the population module (K independent learners in the launches of one) imports torch: loaded on first use
+    # the population modules (K independent learners in the launches of one) import torch: loaded on first use
     if name in ('population', 'ActorCriticPopulation'):
         import importlib
         population = importlib.import_module(__name__ + '.population')
         return population if name == 'population' else population.ActorCriticPopulation
+    if name in ('irl_population', 'AC_IRLPopulation'):
+        import importlib
+        irl_population = importlib.import_module(__name__ + '.irl_population')
+        return irl_population if name == 'irl_population' else irl_population.AC_IRLPopulation
     raise AttributeError('module %r has no attribute %r' % (__name__, name))
 __version__ = '0.1.0'

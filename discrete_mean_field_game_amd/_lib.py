@@ -133,6 +133,14 @@ SIGNATURES['mfg_train_rollout_irl'] = (_i32, [_p, _i64, _p, _i64, _i32, _i32, _p
                                               _f64, C.POINTER(RewardNetStruct), _u64, _u64, _p, _p, _p, _p, _p, _p, _p, _p, _p, _sz,
                                               _p])
 
+SIGNATURES['mfg_train_episodes_irl_pop'] = (_i32, [_p, _i64, _p, _p, _i64, _i32, _i32, _i32, _i64, _i64, _i32, _p, _p, _p, _p, _f64,
+                                                   _p, _u32, _u64, _i32, _p, _p, C.POINTER(RewardNetStruct), _i32, _p, _u64, _p,
+                                                   _p, _p, _p, _p, _p, _p, _sz, _p])
+
+SIGNATURES['mfg_train_rollouts_irl_pop'] = (_i32, [_p, _i64, _i64, _i32, _i32, _i32, _i64, _i64, _i32, _p, _p, _p, _p, _f64, _p,
+                                                   _u32, _u64, _i32, _p, _p, C.POINTER(RewardNetStruct), _i32, _p, _u64, _p, _p,
+                                                   _p, _p, _p, _p, _p, _p, _p, _sz, _p])
+
 _lib = None
 
 

@@ -93,6 +93,30 @@ struct CoreArgs {
 // blocks behind the sampling blocks of a STEP launch: a wave per column of the FO-entry rows
 __host__ __device__ constexpr int core_step_red_blocks(int FO) { return (FO + WAVES - 1) / WAVES; }
 
+// The row reduction + update that closes an IRL episode of per-step updates (k_reduce_rows_apply and its population form): a
+// wave per column k of the [nrows][FO] rows, rows_column_sum -- G, w, theta (theta_in -> theta_out), the return.
+__device__ __forceinline__ void reduce_rows_apply_body(const double* __restrict__ rows, int nrows, int64_t FO, double* __restrict__ G,
+                                                       double lr_c, double lr_a, double count, double* __restrict__ w,
+                                                       const double* theta_in, double* theta_out, double* __restrict__ reward_acc) {
+  const int lane = threadIdx.x & (WAVE - 1), wv = threadIdx.x / WAVE;
+  const int64_t k = (int64_t)blockIdx.x * WAVES + wv, F = FO - 3;
+  if (k >= FO) return;
+  double old_val = 0.0;
+  if (lane == 0) {
+    if (k < F) old_val = w[k];
+    else if (k == F) old_val = *theta_in;
+    else if (k == F + 1 && reward_acc) old_val = *reward_acc;
+  }
+  const double gk = rows_column_sum(rows, nrows, FO, k, lane);
+  if (lane == 0) {
+    const double inv = 1.0 / count;
+    G[k] = gk;
+    if (k < F) w[k] = updated_param(old_val, lr_c, gk, inv);
+    else if (k == F) *theta_out = updated_param(old_val, lr_a, gk, inv);
+    else if (k == F + 1 && reward_acc) *reward_acc = old_val + gk * inv;
+  }
+}
+
 int set_error(int code, const char* msg);  // records mfg_last_error() (defined in mfg_kernels.hip)
 
 // IRL env step: reward network + the batch sums of the TD update over the same samples in one launch

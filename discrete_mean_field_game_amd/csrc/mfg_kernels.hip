@@ -23,6 +23,7 @@
 
 #include "../../include/mfg_hip.h"
 #include "mfg_core.h"
+#include "mfg_irl_population.h"
 #include "mfg_population.h"
 
 using namespace mfg;
@@ -1585,23 +1586,7 @@ __global__ __launch_bounds__(BLOCK) void k_reduce_rows_apply(const double* __res
                                                             double lr_c, double lr_a, double count, double* __restrict__ w,
                                                             const double* theta_in, double* theta_out,
                                                             double* __restrict__ reward_acc) {
-  const int lane = threadIdx.x & (WAVE - 1), wv = threadIdx.x / WAVE;
-  const int64_t k = (int64_t)blockIdx.x * WAVES + wv, F = FO - 3;
-  if (k >= FO) return;
-  double old_val = 0.0;
-  if (lane == 0) {
-    if (k < F) old_val = w[k];
-    else if (k == F) old_val = *theta_in;
-    else if (k == F + 1 && reward_acc) old_val = *reward_acc;
-  }
-  const double gk = rows_column_sum(rows, nrows, FO, k, lane);
-  if (lane == 0) {
-    const double inv = 1.0 / count;
-    G[k] = gk;
-    if (k < F) w[k] = updated_param(old_val, lr_c, gk, inv);
-    else if (k == F) *theta_out = updated_param(old_val, lr_a, gk, inv);
-    else if (k == F + 1 && reward_acc) *reward_acc = old_val + gk * inv;
-  }
+  reduce_rows_apply_body(rows, nrows, FO, G, lr_c, lr_a, count, w, theta_in, theta_out, reward_acc);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1909,8 +1894,10 @@ static bool traj_ids_ok(uint64_t traj_offset, int64_t B) {
   return traj_offset <= MFG_TRAJ_ID_LIMIT && (uint64_t)(B > 0 ? B : 0) <= MFG_TRAJ_ID_LIMIT - traj_offset;
 }
 
-// pop != NULL: the population form (mfg_population.h; training launches at d <= 64, packed lane mapping)
-static int launch_core(const CoreArgs& a_in, bool sample, bool td, int precision, hipStream_t st, const PopArgs* pop = nullptr) {
+// pop != NULL: the population form (mfg_population.h; training launches at d <= 64, packed lane mapping); ipop != NULL: the IRL
+// population form (mfg_irl_population.h; d = 21 / 15)
+static int launch_core(const CoreArgs& a_in, bool sample, bool td, int precision, hipStream_t st, const PopArgs* pop = nullptr,
+                       const IrlCorePop* ipop = nullptr) {
   CoreArgs a = a_in;
   if (!traj_ids_ok(a.traj_offset, a.B))
     return fail(MFG_EINVAL, "trajectory ids traj_offset + B = %llu + %lld exceed 2^48 (MFG_TRAJ_ID_LIMIT)",
@@ -1937,7 +1924,8 @@ static int launch_core(const CoreArgs& a_in, bool sample, bool td, int precision
     if (!a.htab) return fail(MFG_ELAUNCH, "%s", "h(z) table initialisation failed");
   }
   int rc;
-  if (pop) rc = (sample && td) ? launch_core_small_pop(a, *pop, precision == MFG_PRECISION_MIXED, num_cus(), st) : MFG_EUNSUPPORTED;
+  if (ipop) rc = (sample && td) ? launch_core_irl_pop(a, *ipop, precision == MFG_PRECISION_MIXED, num_cus(), st) : MFG_EUNSUPPORTED;
+  else if (pop) rc = (sample && td) ? launch_core_small_pop(a, *pop, precision == MFG_PRECISION_MIXED, num_cus(), st) : MFG_EUNSUPPORTED;
   else if (a.d <= WAVE) rc = launch_core_small(a, sample, td, precision == MFG_PRECISION_MIXED, num_cus(), st);
   else if (precision == MFG_PRECISION_MIXED) rc = launch_core_large_mixed(a, sample, td, num_cus(), st);
   else rc = launch_core_large_f64(a, sample, td, num_cus(), st);
@@ -3136,6 +3124,223 @@ int mfg_train_rollouts_pop(const float* mat_pi0, int64_t num_start, int64_t B, i
     if (rc != MFG_OK) return rc;
   }
   return MFG_OK;
+}
+
+// ---- IRL populations (mfg_irl_population.h): K forward learners of AC_IRL.train in the launches of one ----------------------
+#define CHECK_IRL_POP()                                                                                                  \
+  REQUIRE(K >= 1 && K <= MFG_POP_MAX_K, "population size K outside [1, MFG_POP_MAX_K]");                               \
+  CHECK_BD();                                                                                                            \
+  REQUIRE(T >= 1, "T < 1");                                                                                              \
+  REQUIRE(B * (int64_t)T <= 0x7FFFFFFF, "B * T too large");                                                             \
+  REQUIRE(mat_pi0 && num_start > 0 && num_start <= 0x7FFFFFFF, "null / empty / oversized start-state table");            \
+  REQUIRE(theta && shift && alpha_scale && w && seed && lr_critic && lr_actor && net && rn_seed && P && reward && delta && \
+              g && G && workspace,                                                                                       \
+          "null pointer");                                                                                               \
+  REQUIRE(net->keep_prob > 0.0f && net->keep_prob <= 1.0f, "reward net: keep_prob must be in (0,1]");                    \
+  REQUIRE(workspace_bytes % 256 == 0, "population: workspace_bytes (one learner's slice) must be a multiple of 256");     \
+  REQUIRE(episodes >= 0 && first_episode >= 0, "bad episode range");                                                     \
+  REQUIRE((uint64_t)first_step + (uint64_t)episodes * (uint64_t)T <= 0xFFFFFFFFull, "Philox step counter would wrap");    \
+  REQUIRE(traj_ids_ok(traj_offset, B), "trajectory ids traj_offset + B exceed 2^48 (MFG_TRAJ_ID_LIMIT)");               \
+  if (!reward_net_pop_ready(d, net, per_learner_net, K))                                                                 \
+    return fail(MFG_EUNSUPPORTED, "IRL population: d=%d, k1=%d, f2=%d, k2=%d, n_fc3=%d, n_fc4=%d: not the matrix-core "      \
+                "reward network (d = 21 / 15, 5 / 2 / 3, n_fc3 <= 16, 8-byte aligned fc3_w of every learner)",           \
+                d, net->k1, net->f2, net->k2, net->n3, net->n4)
+
+static IrlCorePop irl_core_pop(int K, int64_t B, int d, int T, int64_t episodes, const uint64_t* seed, const double* shift,
+                               const double* alpha_scale, const double* lr_critic, const double* lr_actor, size_t workspace_bytes) {
+  IrlCorePop p{};
+  p.K = K;
+  p.s_state = B * d;
+  p.s_theta_b = sizeof(double);
+  p.F = mfg_num_features(d);
+  p.s_traj = B * (T + 1) * d;
+  p.s_acc = episodes;
+  p.s_ws = (int64_t)workspace_bytes;
+  p.seed = seed;
+  p.shift = shift;
+  p.alpha_scale = alpha_scale;
+  p.lr_c = lr_critic;
+  p.lr_a = lr_actor;
+  return p;
+}
+
+static uint64_t rn_key_ctr(uint64_t call) { return call * 0x9E3779B97F4A7C15ull; }
+
+int mfg_train_episodes_irl_pop(const float* mat_pi0, int64_t num_start, float* pi_out, float* pi_scratch, int64_t B, int K, int d,
+                               int T, int64_t episodes, int64_t first_episode, int constant, double* theta, const double* shift,
+                               const double* alpha_scale, double* w, double gamma, const uint64_t* seed, uint32_t first_step,
+                               uint64_t traj_offset, int precision, const double* lr_critic, const double* lr_actor,
+                               const mfg_reward_net_t* net, int per_learner_net, const uint64_t* rn_seed, uint64_t rn_call0,
+                               float* P, float* reward, double* delta, double* g, double* G, double* reward_acc, void* workspace,
+                               size_t workspace_bytes, mfg_stream_t stream) {
+  REQUIRE(pi_out && pi_scratch, "null pointer");
+  CHECK_IRL_POP();
+  CHECK_PRECISION();
+  // one learner's slice: control block (two theta slots at bytes 16 / 24) | column F of the rows [max_rows] | rows [max_rows][FO]
+  const int64_t FO = mfg_num_features(d) + 3;
+  const int64_t max_rows = (B + 15) / 16 < 256 ? (B + 15) / 16 : 256;
+  const size_t need = MFG_WS_CONTROL_BYTES + (size_t)max_rows * (FO + 1) * 8;
+  if (workspace_bytes < need)
+    return fail(MFG_EWORKSPACE, "IRL population workspace: need %lld bytes per learner, have %lld", (long long)need,
+                (long long)workspace_bytes);
+  hipStream_t st = S(stream);
+  IrlCorePop p = irl_core_pop(K, B, d, 1, episodes, seed, shift, alpha_scale, lr_critic, lr_actor, workspace_bytes);
+  p.s_n = B;
+  p.s_P = B * d * d;
+  RnPop rp{};
+  rp.K = K;
+  rp.per_learner_net = per_learner_net ? 1 : 0;
+  rp.s_state = rp.s_next = B * d;
+  rp.s_action = B * d * d;
+  rp.s_n = B;
+  rp.s_w = FO - 3;
+  rp.s_ws = (int64_t)workspace_bytes;
+  rp.rn_seed = rn_seed;
+  double* rows_buf = reinterpret_cast<double*>((char*)workspace + MFG_WS_CONTROL_BYTES) + max_rows;
+  double* th_slot = reinterpret_cast<double*>((char*)workspace + 16);  // two slots: theta after odd / even steps
+  for (int64_t e = 0; e < episodes; ++e) {
+    const uint32_t step0 = first_step + (uint32_t)(e * T);
+    lr_schedule(first_episode + e, constant, &p.sc, &p.sa);
+    double* acc = reward_acc ? reward_acc + e : nullptr;
+    // the buffers alternate so that the LAST step writes pi_out (as mfg_train_episode_irl_draw does)
+    float* cur = (T & 1) ? pi_scratch : pi_out;
+    float* nxt = (T & 1) ? pi_out : pi_scratch;
+    const double* th_in = theta;
+    int64_t s_th_in = sizeof(double);
+    double discount = 1.0;
+    int nrows = 0;
+    for (int s = 0; s < T; ++s) {
+      CoreArgs a{};
+      a.pi0 = cur;
+      p.s_pi0 = B * d;
+      if (s == 0) {  // the first step kernel draws the start states and leaves them in `cur` for the network
+        a.pi0 = mat_pi0;
+        a.num_start = num_start;
+        a.start_draw = 1;
+        a.pi_start_out = cur;
+        a.step_nrows = -1;
+        p.s_pi0 = 0;
+      }
+      a.theta = th_in;
+      p.s_theta_b = s_th_in;
+      a.gamma = discount;
+      a.B = B;
+      a.d = d;
+      a.T = 1;
+      a.reward_kind = MFG_REWARD_EXTERNAL;
+      a.first_step = step0 + (uint32_t)s;
+      a.traj_offset = traj_offset;
+      a.pi_next_out = nxt;
+      a.g = g;
+      a.P_out = P;
+      if (s > 0) {
+        a.step_G = G;
+        a.w_out = w;
+        a.pend_reward_acc = acc;
+        a.step_rows = rows_buf;
+        a.step_nrows = nrows;
+        a.theta_out = th_slot + (s & 1);
+      }
+      int rc = launch_core(a, true, true, precision, st, nullptr, &p);
+      if (rc != MFG_OK) return rc;
+      if (s > 0) {
+        th_in = th_slot + (s & 1);
+        s_th_in = (int64_t)workspace_bytes;
+      }
+      rp.key_ctr = rn_key_ctr(rn_call0 + (uint64_t)(e * T + s) + 1ull);
+      RnSums sm{};
+      sm.g = g;
+      sm.delta_out = delta;
+      sm.part_rows = rows_buf;
+      sm.max_rows = max_rows;
+      sm.td_w = w;
+      sm.state_next = nxt;
+      sm.td_gamma = discount;
+      sm.col_f = rows_buf - max_rows;
+      int rows = 0;
+      rc = reward_net_forward_pop(cur, P, B, d, net, traj_offset, reward, &sm, &rows, rp, st, 0);
+      if (rc != MFG_OK) return rc;
+      if (rows != (int)max_rows) return fail(MFG_ELAUNCH, "%s", "train_episodes_irl_pop: the reward-network launch left no partial rows");
+      nrows = rows;
+      discount *= gamma;
+      float* t = cur;
+      cur = nxt;
+      nxt = t;
+    }
+    launch_reduce_rows_apply_pop(rows_buf, nrows, FO, G, (double)B, w, th_in, s_th_in, theta, acc, p, st);
+    const int rc = check_launch("train_episodes_irl_pop");
+    if (rc != MFG_OK) return rc;
+  }
+  return MFG_OK;
+}
+
+int mfg_train_rollouts_irl_pop(const float* mat_pi0, int64_t num_start, int64_t B, int K, int d, int T, int64_t episodes,
+                               int64_t first_episode, int constant, double* theta, const double* shift, const double* alpha_scale,
+                               double* w, double gamma, const uint64_t* seed, uint32_t first_step, uint64_t traj_offset, int flags,
+                               const double* lr_critic, const double* lr_actor, const mfg_reward_net_t* net, int per_learner_net,
+                               const uint64_t* rn_seed, uint64_t rn_call0, float* pi_traj, float* pi_last, float* P, float* reward,
+                               double* delta, double* g, double* G, double* reward_acc, void* workspace, size_t workspace_bytes,
+                               mfg_stream_t stream) {
+  REQUIRE(pi_traj, "null pointer");
+  CHECK_IRL_POP();
+  const size_t need = pop_workspace_need(d, B * T, false);
+  if (workspace_bytes < need)
+    return fail(MFG_EWORKSPACE, "IRL population workspace: need %lld bytes per learner, have %lld", (long long)need,
+                (long long)workspace_bytes);
+  hipStream_t st = S(stream);
+  IrlCorePop p = irl_core_pop(K, B, d, T, episodes, seed, shift, alpha_scale, lr_critic, lr_actor, workspace_bytes);
+  p.s_pi0 = 0;  // (the shared start-state table: the rows are drawn in the kernel)
+  p.s_n = B * T;
+  p.s_P = B * T * d * d;
+  PopArgs q = pop_args(K, B, d, T, episodes, seed, shift, alpha_scale, lr_critic, lr_actor, workspace_bytes);
+  q.s_gpi = q.s_traj;
+  q.s_n = B * T;
+  RnPop rp{};
+  rp.K = K;
+  rp.per_learner_net = per_learner_net ? 1 : 0;
+  rp.s_state = B * (T + 1) * d;
+  rp.s_action = B * T * d * d;
+  rp.s_n = B * T;
+  rp.s_ws = (int64_t)workspace_bytes;
+  rp.rn_seed = rn_seed;
+  const int precision = (flags & MFG_ROLLOUT_F64) ? MFG_PRECISION_F64 : MFG_PRECISION_MIXED;
+  for (int64_t e = 0; e < episodes; ++e) {
+    lr_schedule(first_episode + e, constant, &p.sc, &p.sa);
+    q.sc = p.sc;
+    q.sa = p.sa;
+    CoreArgs a{};
+    a.pi0 = mat_pi0;
+    a.start_draw = 1;
+    a.num_start = num_start;
+    a.theta = theta;
+    a.w = w;
+    a.gamma = gamma;
+    a.B = B;
+    a.d = d;
+    a.T = T;
+    a.reward_kind = MFG_REWARD_EXTERNAL;  // delta = discount V(pi') - V(pi); the reward joins it in the gradient kernel
+    a.discount_pow = (flags & MFG_ROLLOUT_DISCOUNT_POW) ? 1 : 0;
+    a.first_step = first_step + (uint32_t)(e * T);
+    a.traj_offset = traj_offset;
+    a.pi_traj = pi_traj;
+    a.pi_next_out = pi_last;
+    a.delta = delta;
+    a.g = g;
+    a.P_out = P;
+    int rc = launch_core(a, true, true, precision, st, nullptr, &p);
+    if (rc != MFG_OK) return rc;
+    // ONE reward-network pass over each learner's Bk T transitions, states read in place from pi_traj
+    rp.key_ctr = rn_key_ctr(rn_call0 + (uint64_t)e + 1ull);
+    rc = reward_net_forward_pop(pi_traj, P, B * (int64_t)T, d, net, traj_offset * (uint64_t)T, reward, nullptr, nullptr, rp, st, T);
+    if (rc != MFG_OK) return rc;
+    const ApplyArgs ap{0.0, 0.0, w, theta, reward_acc ? reward_acc + e : nullptr};
+    bool applied = false;
+    rc = launch_grad(pi_traj, (int64_t)(T + 1) * d, delta, g, reward, B * T, T, d, G, 0, workspace, workspace_bytes, st, &ap,
+                     &applied, true, &q);
+    if (rc != MFG_OK) return rc;
+    if (!applied) return fail(MFG_ELAUNCH, "%s", "IRL population: update not applied");  // (not reached: d <= 64)
+  }
+  return check_launch("train_rollouts_irl_pop");
 }
 
 int mfg_train_rollout_irl(const float* mat_pi0, int64_t num_start, const int32_t* idx, int64_t B, int d, int T, double* theta,

@@ -15,6 +15,7 @@
 
 #include "../../include/mfg_hip.h"
 #include "mfg_core.h"
+#include "mfg_irl_population.h"
 #include "mfg_rn_common.h"
 
 namespace mfg {
@@ -663,8 +664,9 @@ __device__ unsigned long long rn_stamps[2 * RM_WAVES * 16];
 #define RN_STAMP(i)
 #endif
 
+// (the body of k_reward_net_mfma; its population form k_reward_net_mfma_pop runs it for the learner of blockIdx.y)
 template <int D, int RUN, int RPR, int P1, bool SUMS>
-__global__ __launch_bounds__(RM_BLOCK) void k_reward_net_mfma(RewardNetArgs a) {
+__device__ __forceinline__ void reward_net_mfma_body(RewardNetArgs a) {
   using Gm = MfmaGeom<D, RUN, RPR, P1>;
   constexpr int K1 = Gm::K1, K2 = Gm::K2, F2 = Gm::F2, H1 = Gm::H1, H2 = Gm::H2, DD = Gm::DD, PP = Gm::PP;
   constexpr int KK = Gm::K, NSTEP = Gm::NSTEP, KW = Gm::KW, PITCH = Gm::PITCH;
@@ -1135,6 +1137,44 @@ __global__ __launch_bounds__(RM_BLOCK) void k_reward_net_mfma(RewardNetArgs a) {
   RN_STAMP(11)
 }
 
+template <int D, int RUN, int RPR, int P1, bool SUMS>
+__global__ __launch_bounds__(RM_BLOCK) void k_reward_net_mfma(RewardNetArgs a) {
+  reward_net_mfma_body<D, RUN, RPR, P1, SUMS>(a);
+}
+
+// population form (mfg_irl_population.h): learner blockIdx.y -- its weights, key, states, actions, outputs and workspace rows
+template <int D, int RUN, int RPR, int P1, bool SUMS>
+__global__ __launch_bounds__(RM_BLOCK) void k_reward_net_mfma_pop(RewardNetArgs a, RnPop p) {
+  const int k = blockIdx.y;
+  RewardNetArgs b = a;
+  if (p.per_learner_net) {
+    const int64_t n3 = a.n3, n4 = a.n4;
+    b.c1w += (int64_t)MfmaGeom<D, RUN, RPR, P1>::K1 * MfmaGeom<D, RUN, RPR, P1>::K1 * k;
+    b.c1b += k;
+    b.c2w += (int64_t)MfmaGeom<D, RUN, RPR, P1>::F2 * MfmaGeom<D, RUN, RPR, P1>::K2 * MfmaGeom<D, RUN, RPR, P1>::K2 * k;
+    b.c2b += (int64_t)MfmaGeom<D, RUN, RPR, P1>::F2 * k;
+    b.w3 += n3 * MfmaGeom<D, RUN, RPR, P1>::K * k;
+    b.b3 += n3 * k;
+    b.w4 += n4 * (n3 + D) * k;
+    b.b4 += n4 * k;
+    b.wo += n4 * k;
+    b.bo += k;
+  }
+  b.seed = p.rn_seed[k] ^ p.key_ctr;
+  b.state += p.s_state * k;
+  b.action += p.s_action * k;
+  b.reward += p.s_n * k;
+  if constexpr (SUMS) {
+    b.gsc += p.s_n * k;
+    b.delta_out += p.s_n * k;
+    b.td_w += p.s_w * k;
+    b.state_next += p.s_next * k;
+    b.part_rows = reinterpret_cast<double*>(reinterpret_cast<char*>(a.part_rows) + p.s_ws * k);
+    b.col_f = reinterpret_cast<double*>(reinterpret_cast<char*>(a.col_f) + p.s_ws * k);
+  }
+  reward_net_mfma_body<D, RUN, RPR, P1, SUMS>(b);
+}
+
 // dynamic LDS above 64 KB needs the attribute, which applies to the CURRENT device: once per device, result kept -- a device
 // where it failed takes the run-mapped kernels
 template <int D, int RUN, int RPR, int P1>
@@ -1285,6 +1325,78 @@ int reward_net_forward_sums(const float* state, const float* action, int64_t B, 
   else { RN_LAUNCH(16) }
 #undef RN_LAUNCH
   return hipGetLastError() == hipSuccess ? MFG_OK : set_error(MFG_ELAUNCH, "reward_net: launch failed");
+}
+
+// ---- populations (mfg_irl_population.h) ----
+template <int D, int RUN, int RPR, int P1>
+static bool mfma_lds_attribute_pop() {
+  static std::mutex attr_mu;
+  static signed char attr_state[64] = {0};
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return false;
+  std::lock_guard<std::mutex> lock(attr_mu);
+  if (attr_state[dev] == 0) {
+    const hipError_t e1 = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_reward_net_mfma_pop<D, RUN, RPR, P1, true>),
+                                              hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024);
+    const hipError_t e2 = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_reward_net_mfma_pop<D, RUN, RPR, P1, false>),
+                                              hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024);
+    attr_state[dev] = (e1 == hipSuccess && e2 == hipSuccess) ? 1 : -1;
+    (void)hipGetLastError();
+  }
+  return attr_state[dev] > 0;
+}
+
+bool reward_net_pop_ready(int d, const mfg_reward_net_t* net, int per_learner_net, int K) {
+  if (!net || K < 1 || net->n3 < 1 || net->n4 < 1 || net->n4 > RN_MAXN) return false;
+  if (!net->conv1_w || !net->conv1_b || !net->conv2_w || !net->conv2_b || !net->fc3_w || !net->fc3_b || !net->fc4_w ||
+      !net->fc4_b || !net->out_w || !net->out_b)
+    return false;
+  const int64_t n_w3 = (int64_t)net->n3 * net->f2 * d * d;
+  for (int k = 0; k < (per_learner_net ? K : 1); ++k)
+    if (!mfma_shape_ok(d, net->k1, net->f2, net->k2, net->n3, net->fc3_w + n_w3 * k)) return false;
+  return d == 21 ? mfma_lds_attribute_pop<21, 7, 3, MFG_RM_P21>() : mfma_lds_attribute_pop<15, 5, 3, MFG_RM_P15>();
+}
+
+template <int D, int RUN, int RPR, int P1>
+static void launch_reward_net_mfma_pop(const RewardNetArgs& a, bool sums, const RnPop& p, int* rows_out, hipStream_t st) {
+  using Gm = MfmaGeom<D, RUN, RPR, P1>;
+  int64_t grid = (a.B + RM_WAVES - 1) / RM_WAVES;  // (the single launch's grid for one learner)
+  if (grid > 256) grid = 256;
+  const size_t lds = Gm::lds_floats(a.n3, a.n4, sums) * 4;
+  const dim3 g((unsigned)grid, (unsigned)p.K);
+  if (sums) hipLaunchKernelGGL((k_reward_net_mfma_pop<D, RUN, RPR, P1, true>), g, dim3(RM_BLOCK), lds, st, a, p);
+  else hipLaunchKernelGGL((k_reward_net_mfma_pop<D, RUN, RPR, P1, false>), g, dim3(RM_BLOCK), lds, st, a, p);
+  if (rows_out) *rows_out = sums ? (int)grid : 0;
+}
+
+int reward_net_forward_pop(const float* state, const float* action, int64_t B, int d, const mfg_reward_net_t* net,
+                           uint64_t sample_offset, float* reward, const RnSums* sums, int* rows_out, const RnPop& p, hipStream_t st,
+                           int state_T) {
+  if (rows_out) *rows_out = 0;
+  if (B < 1 || !state || !action || !reward || !reward_net_pop_ready(d, net, p.per_learner_net, p.K))
+    return set_error(MFG_EUNSUPPORTED, "reward_net population: not the matrix-core geometry");
+  if (!(net->keep_prob > 0.0f && net->keep_prob <= 1.0f)) return set_error(MFG_EINVAL, "reward_net: keep_prob must be in (0,1]");
+  RewardNetArgs a{state, action, B, d, net->k1, net->f2, net->k2, net->n3, net->n4, net->conv1_w, net->conv1_b, net->conv2_w,
+                  net->conv2_b, net->fc3_w, net->fc3_b, net->fc4_w, net->fc4_b, net->out_w, net->out_b, net->keep_prob, 0,
+                  sample_offset, reward, 0, nullptr, nullptr, nullptr, nullptr};
+  a.state_T = state_T;
+  const bool want = sums != nullptr;
+  if (want) {
+    int64_t grid = (B + RM_WAVES - 1) / RM_WAVES;
+    if (grid > 256) grid = 256;
+    if (!(sums->td_w && sums->state_next && sums->col_f && sums->g && sums->delta_out && sums->part_rows) || grid > sums->max_rows)
+      return set_error(MFG_EWORKSPACE, "reward_net population: no room for the partial rows");
+    a.gsc = sums->g;
+    a.delta_out = sums->delta_out;
+    a.part_rows = sums->part_rows;
+    a.td_w = sums->td_w;
+    a.state_next = sums->state_next;
+    a.td_gamma = sums->td_gamma;
+    a.col_f = sums->col_f;
+  }
+  if (d == 21) launch_reward_net_mfma_pop<21, 7, 3, MFG_RM_P21>(a, want, p, rows_out, st);
+  else launch_reward_net_mfma_pop<15, 5, 3, MFG_RM_P15>(a, want, p, rows_out, st);
+  return hipGetLastError() == hipSuccess ? MFG_OK : set_error(MFG_ELAUNCH, "reward_net population: launch failed");
 }
 }  // namespace mfg
 

@@ -609,6 +609,112 @@ def train_rollout_irl(mat_pi0, idx, T, theta, shift, alpha_scale, w, gamma, lr_c
     return bufs
 
 
+IRL_POP_D = (15, 21)     # the matrix-core reward-network kernel's sizes (mfg_train_*_irl_pop)
+IRL_POP_MAX_FC3 = 16
+
+
+def irl_pop_net_geometry(nets):
+    """(d, n_fc3, n_fc4, keep_prob) shared by the networks.RewardNet modules `nets`; ValueError where they differ or where the
+    matrix-core reward-network kernel does not serve them (d = 15 / 21, k1 = 5, f2 = 2, k2 = 3, n_fc3 <= 16, n_fc4 <= 32)."""
+    if not nets:
+        raise ValueError('no reward network')
+    def geom(n):
+        return (n.d, n.conv1.out_channels, n.conv1.kernel_size[0], n.conv2.out_channels, n.conv2.kernel_size[0],
+                n.fc3.out_features, n.fc4.out_features)
+    def keep(n):
+        return float(n.keep_prob) if (n.use_dropout and (n.dropout_always or n.training)) else 1.0
+    g0, k0 = geom(nets[0]), keep(nets[0])
+    for n in nets[1:]:
+        if geom(n) != g0:
+            raise ValueError('reward networks of one population must share their geometry: %s vs %s' % (geom(n), g0))
+        if keep(n) != k0:
+            raise ValueError('reward networks of one population must share their dropout setting: keep %g vs %g' % (keep(n), k0))
+    d, f1, k1, f2, k2, n3, n4 = g0
+    if d not in IRL_POP_D or f1 != 1 or k1 != 5 or f2 != 2 or k2 != 3 or not 1 <= n3 <= IRL_POP_MAX_FC3 or not 1 <= n4 <= 32:
+        raise ValueError('reward network d=%d, f1=%d, k1=%d, f2=%d, k2=%d, n_fc3=%d, n_fc4=%d: IRL populations need the '
+                         'matrix-core kernel (d = 15 / 21, 1 / 5 / 2 / 3, n_fc3 <= %d, n_fc4 <= 32)'
+                         % (d, f1, k1, f2, k2, n3, n4, IRL_POP_MAX_FC3))
+    return d, n3, n4, k0
+
+
+def irl_pop_workspace_slice(B, d, T):
+    """Bytes of ONE learner's workspace slice for both IRL population flows: what the single-learner IRL calls get for B T
+    samples (ops.workspace), rounded up to 256."""
+    return (max(int(L.lib().mfg_workspace_bytes(B * T, d)), 8) + 255) // 256 * 256
+
+
+def _chk_irl_pop(K, B, d, T, episodes, theta, w, G, ws, bufs, reward_acc, mat_pi0, per_learner, shifts, alpha_scales,
+                 lr_critic, lr_actor, seeds, rn_seeds, net_struct):
+    if not 1 <= K <= L.POP_MAX_K:
+        raise ValueError('population size %d outside [1, %d]' % (K, L.POP_MAX_K))
+    for name, t in (('shifts', shifts), ('alpha_scales', alpha_scales), ('lr_critic', lr_critic), ('lr_actor', lr_actor)):
+        _chk_pop(K, name, t, torch.float64)
+    _chk_pop(K, 'seeds', seeds, torch.int64)
+    _chk_pop(K, 'rn_seeds', rn_seeds, torch.int64)
+    _chk_pop_shapes(K, B, d, T, episodes, theta, w, G, ws, bufs, reward_acc, mat_pi0)
+    if d not in IRL_POP_D:
+        raise ValueError('d=%d: IRL populations cover d = 15 / 21 (the matrix-core reward-network kernel)' % d)
+    if net_struct.n3 > IRL_POP_MAX_FC3:
+        raise ValueError('n_fc3=%d > %d: outside the matrix-core reward-network kernel' % (net_struct.n3, IRL_POP_MAX_FC3))
+
+
+def train_episodes_irl_pop(mat_pi0, pi, T, episodes, first_episode, constant, theta, shifts, alpha_scales, w, gamma, lr_critic,
+                           lr_actor, seeds, net_struct, per_learner_net, rn_seeds, rn_call0, G, ws, bufs, first_step=0,
+                           traj_offset=0, reward_acc=None, precision='mixed'):
+    """AC_IRL.train's step mode for K independent learners (mfg_train_episodes_irl_pop): `pi` [K,Bk,d] (output: the final
+    states), theta [K], w [K,F], G [K,F+3], ws [K, slice] fp64; shifts, alpha_scales, lr_critic, lr_actor fp64 and seeds,
+    rn_seeds int64 (read as uint64) device arrays [K]; net_struct = reward_net_struct(...) of the shared network or of the
+    stacked parameters (per_learner_net); bufs = dict(scratch [K,Bk,d] f32, P [K,Bk,d,d] f32, reward [K,Bk] f32, delta / g
+    [K,Bk] f64); reward_acc [K,episodes] fp64 or None.  The episode numbers of the schedule start at first_episode."""
+    import ctypes as C
+    _chk_f32(mat_pi0, 'mat_pi0'); _chk_f32(pi, 'pi'); _chk_f64(theta, 'theta'); _chk_f64(w, 'w'); _chk_f64(G, 'G')
+    if pi.dim() != 3:
+        raise ValueError('pi: expected [K, Bk, d]')
+    K, B, d = pi.shape
+    P = bufs['P']
+    _chk_irl_pop(K, B, d, T, episodes, theta, w, G, ws, dict(bufs, pi=pi, P=None), reward_acc, mat_pi0, per_learner_net,
+                 shifts, alpha_scales, lr_critic, lr_actor, seeds, rn_seeds, net_struct)
+    if tuple(P.shape) != (K, B, d, d) or not P.is_contiguous() or not P.is_cuda or P.dtype != torch.float32:
+        raise ValueError('P: expected a contiguous f32 device tensor [%d, %d, %d, %d]' % (K, B, d, d))
+    L.check(L.lib().mfg_train_episodes_irl_pop(
+        mat_pi0.data_ptr(), mat_pi0.shape[0], pi.data_ptr(), bufs['scratch'].data_ptr(), B, K, d, int(T), int(episodes),
+        int(first_episode), int(bool(constant)), theta.data_ptr(), shifts.data_ptr(), alpha_scales.data_ptr(), w.data_ptr(),
+        float(gamma), seeds.data_ptr(), int(first_step), int(traj_offset), L.PRECISIONS[precision], lr_critic.data_ptr(),
+        lr_actor.data_ptr(), C.byref(net_struct), int(bool(per_learner_net)), rn_seeds.data_ptr(), int(rn_call0), P.data_ptr(),
+        bufs['reward'].data_ptr(), bufs['delta'].data_ptr(), bufs['g'].data_ptr(), G.data_ptr(), _ptr(reward_acc),
+        ws.data_ptr(), ws.shape[1] * ws.element_size(), _stream()), 'mfg_train_episodes_irl_pop')
+    return pi
+
+
+def train_rollouts_irl_pop(mat_pi0, T, episodes, first_episode, constant, theta, shifts, alpha_scales, w, gamma, lr_critic,
+                           lr_actor, seeds, net_struct, per_learner_net, rn_seeds, rn_call0, G, ws, bufs, first_step=0,
+                           traj_offset=0, discount_pow=True, reward_acc=None, precision='mixed'):
+    """AC_IRL.train's rollout mode for K independent learners (mfg_train_rollouts_irl_pop): bufs = dict(pi_traj
+    [K,Bk,T+1,d] f32, pi_last [K,Bk,d] f32 (optional), P [K,Bk,T,d,d] f32, reward [K,Bk,T] f32, delta / g [K,Bk,T] f64);
+    the other arrays as for train_episodes_irl_pop."""
+    import ctypes as C
+    _chk_f32(mat_pi0, 'mat_pi0'); _chk_f64(theta, 'theta'); _chk_f64(w, 'w'); _chk_f64(G, 'G')
+    if bufs['pi_traj'].dim() != 4:
+        raise ValueError('pi_traj: expected [K, Bk, T+1, d]')
+    K, B, d = bufs['pi_traj'].shape[0], bufs['pi_traj'].shape[1], mat_pi0.shape[1]
+    P = bufs['P']
+    _chk_irl_pop(K, B, d, T, episodes, theta, w, G, ws, dict(bufs, P=None), reward_acc, mat_pi0, per_learner_net, shifts,
+                 alpha_scales, lr_critic, lr_actor, seeds, rn_seeds, net_struct)
+    if tuple(P.shape) != (K, B, T, d, d) or not P.is_contiguous() or not P.is_cuda or P.dtype != torch.float32:
+        raise ValueError('P: expected a contiguous f32 device tensor [%d, %d, %d, %d, %d]' % (K, B, T, d, d))
+    flags = L.ROLLOUT_DISCOUNT_POW if discount_pow else 0
+    if L.PRECISIONS[precision] == L.PRECISION_F64:
+        flags |= L.ROLLOUT_F64
+    L.check(L.lib().mfg_train_rollouts_irl_pop(
+        mat_pi0.data_ptr(), mat_pi0.shape[0], B, K, d, int(T), int(episodes), int(first_episode), int(bool(constant)),
+        theta.data_ptr(), shifts.data_ptr(), alpha_scales.data_ptr(), w.data_ptr(), float(gamma), seeds.data_ptr(),
+        int(first_step), int(traj_offset), flags, lr_critic.data_ptr(), lr_actor.data_ptr(), C.byref(net_struct),
+        int(bool(per_learner_net)), rn_seeds.data_ptr(), int(rn_call0), bufs['pi_traj'].data_ptr(), _ptr(bufs.get('pi_last')),
+        P.data_ptr(), bufs['reward'].data_ptr(), bufs['delta'].data_ptr(), bufs['g'].data_ptr(), G.data_ptr(),
+        _ptr(reward_acc), ws.data_ptr(), ws.shape[1] * ws.element_size(), _stream()), 'mfg_train_rollouts_irl_pop')
+    return bufs
+
+
 def episode_buffers(B, d, device):
     return {'scratch': torch.empty(B, d, dtype=torch.float32, device=device),
             'reward': torch.empty(B, dtype=torch.float32, device=device),

@@ -59,6 +59,23 @@ def check_args(K, d, batch, update_every, reward, precision, episode_steps):
         raise ValueError('episode_steps must be >= 1')
 
 
+def resolve_start_table(d, pi0=None, path_to_dir=None):
+    """The start-state table [num_start, d] (fp64) as actor_critic resolves it: `pi0`, else the reference's directory, else
+    actor_critic's synthetic table."""
+    if pi0 is not None:
+        return np.array(pi0, dtype=np.float64)[:, 0:d]
+    if path_to_dir is None:
+        path_to_dir = os.getcwd() + '/train_normalized_round2'
+    if os.path.isdir(path_to_dir):
+        holder = type('_Table', (), {})()
+        holder.d = d
+        actor_critic.init_pi0(holder, path_to_dir=path_to_dir)
+        return holder.mat_pi0
+    rs = np.random.RandomState(0)   # actor_critic's synthetic table: Dirichlet(1) rows via '%.3e' text
+    m = rs.dirichlet(np.ones(d), size=64)
+    return np.array([[float('%.3e' % v) for v in row] for row in m])
+
+
 def _with_ctx(method):
     """Run a method with the instance's own context bound (as actor_critic's public methods do)."""
     @functools.wraps(method)
@@ -102,20 +119,7 @@ class ActorCriticPopulation:
             w = np.broadcast_to(w.reshape(1, -1), (K, F)) if w.size == F else w.reshape(K, F)
         self._w = torch.as_tensor(np.ascontiguousarray(w), device=dev)
         # the start-state table, resolved as actor_critic resolves it, shared by all learners
-        if pi0 is not None:
-            table = np.array(pi0, dtype=np.float64)[:, 0:self.d]
-        else:
-            if path_to_dir is None:
-                path_to_dir = os.getcwd() + '/train_normalized_round2'
-            if os.path.isdir(path_to_dir):
-                holder = type('_Table', (), {})()
-                holder.d = self.d
-                actor_critic.init_pi0(holder, path_to_dir=path_to_dir)
-                table = holder.mat_pi0
-            else:
-                rs = np.random.RandomState(0)   # actor_critic's synthetic table: Dirichlet(1) rows via '%.3e' text
-                m = rs.dirichlet(np.ones(self.d), size=64)
-                table = np.array([[float('%.3e' % v) for v in row] for row in m])
+        table = resolve_start_table(self.d, pi0, path_to_dir)
         self.mat_pi0 = table
         self._mat_pi0_dev = torch.as_tensor(np.ascontiguousarray(table, dtype=np.float32), device=dev)
         self._seeds_dev = torch.as_tensor(self.seeds.view(np.int64), device=dev)

@@ -491,6 +491,47 @@ int mfg_train_rollout_irl(const float* mat_pi0, int64_t num_start, const int32_t
                           double* delta, double* g, double* G, double* reward_acc, void* workspace, size_t workspace_bytes,
                           mfg_stream_t stream);
 
+/* IRL populations: K independent forward learners of AC_IRL.train (ac_irl.py:634-732, stop_criteria = -1 as in outerloop)
+ * trained in lock-step on ONE GPU, every launch of an episode serving all K.  Learner k of a population call gives, bit for bit
+ * (theta, w, G, reward_acc, final states and the last step's P / reward / delta / g), what the single-learner path gives with
+ * B = Bk, the same traj_offset and learner k's seed, theta, w, shift, alpha_scale, learning rates and reward network:
+ *   step mode     `episodes` calls of mfg_train_episode_irl_draw (first_step + e T, lr x lr_schedule(first_episode + e),
+ *                 reward_acc + e, rn_seed[k], rn_call0 + e T, rn_sample_offset = traj_offset);
+ *   rollout mode  `episodes` calls of mfg_train_rollout_irl with idx = NULL and MFG_TRAIN_APPLY (first_step + e T, the same
+ *                 rates, rn_key = rn_seed[k] ^ ((rn_call0 + e + 1) 0x9E3779B97F4A7C15), rn_sample_offset = traj_offset T).
+ * Learning rates in episode e: lr_critic[k] x, lr_actor[k] x the schedule of mfg_train_rollouts at episode number
+ * first_episode + e (AC_IRL.train numbers its episodes from 1: pass first_episode + 1 to reproduce it).
+ * Dropout keys: rn_seed is a device array [K] (AC_IRL passes its seed + 0x5EED); rn_call0 the count of reward calls made before,
+ * shared (the learners move in lock-step).  Step mode, episode e, env step s:  rn_seed[k] ^ ((rn_call0 + e T + s + 1) x
+ * 0x9E3779B97F4A7C15);  rollout mode, episode e:  rn_seed[k] ^ ((rn_call0 + e + 1) x 0x9E3779B97F4A7C15)  (mod 2^64).
+ * Reward networks: `net` (host struct).  per_learner_net = 0: every learner reads the same tensors; 1: every pointer is the
+ * base of a stacked tensor, learner k's tensor t at base_t + k numel_t (numel_t from the geometry: k1^2, 1, f2 k2^2, f2,
+ * n3 f2 d^2, n3, n4 (n3 + d), n4, n4, 1).  Geometry and keep_prob are shared.
+ * Per-learner scalars and learner-major arrays as for mfg_train_episodes_pop / mfg_train_rollouts_pop, plus P: step mode
+ * pi_out / pi_scratch [K,Bk,d], P [K,Bk,d,d], reward / delta / g [K,Bk]; rollout mode pi_traj [K,Bk,T+1,d], pi_last [K,Bk,d]
+ * (may be NULL), P [K,Bk,T,d,d], reward / delta / g [K,Bk,T].  reward_acc [K,episodes] (may be NULL; step mode: += every
+ * step's mean reward, rollout mode: += the mean over the Bk T transitions).  Start states are drawn on the device from mat_pi0.
+ * Checked before anything is launched: MFG_EINVAL for K outside [1, MFG_POP_MAX_K], a null pointer, keep_prob outside (0,1],
+ * a Philox step counter that would wrap; MFG_EUNSUPPORTED where the matrix-core reward-network kernel does not serve
+ * (d = 21 / 15, k1 = 5, f2 = 2, k2 = 3, n_fc3 <= 16, n_fc4 <= 32, every learner's fc3_w 8-byte aligned); MFG_EWORKSPACE when
+ * one learner's slice (workspace_bytes, a multiple of 256) cannot hold the control block and the partial rows of the update:
+ * 64 + min(ceil(Bk / 16), 256) (F + 4) 8 bytes in step mode, those of the gradient kernels over Bk T samples in rollout mode. */
+int mfg_train_episodes_irl_pop(const float* mat_pi0, int64_t num_start, float* pi_out, float* pi_scratch, int64_t B, int K, int d,
+                               int T, int64_t episodes, int64_t first_episode, int constant, double* theta, const double* shift,
+                               const double* alpha_scale, double* w, double gamma, const uint64_t* seed, uint32_t first_step,
+                               uint64_t traj_offset, int precision, const double* lr_critic, const double* lr_actor,
+                               const mfg_reward_net_t* net_host, int per_learner_net, const uint64_t* rn_seed, uint64_t rn_call0,
+                               float* P, float* reward, double* delta, double* g, double* G, double* reward_acc, void* workspace,
+                               size_t workspace_bytes, mfg_stream_t stream);
+/* rollout mode; flags: MFG_ROLLOUT_DISCOUNT_POW | MFG_ROLLOUT_F64 */
+int mfg_train_rollouts_irl_pop(const float* mat_pi0, int64_t num_start, int64_t B, int K, int d, int T, int64_t episodes,
+                               int64_t first_episode, int constant, double* theta, const double* shift, const double* alpha_scale,
+                               double* w, double gamma, const uint64_t* seed, uint32_t first_step, uint64_t traj_offset, int flags,
+                               const double* lr_critic, const double* lr_actor, const mfg_reward_net_t* net_host,
+                               int per_learner_net, const uint64_t* rn_seed, uint64_t rn_call0, float* pi_traj, float* pi_last,
+                               float* P, float* reward, double* delta, double* g, double* G, double* reward_acc, void* workspace,
+                               size_t workspace_bytes, mfg_stream_t stream);
+
 /* f1 (optional importance weights, ac_irl.py:270-289 calc_pdf_action, :324-379 calc_z): log-density of the
  * product-Dirichlet policy for N (state, action) pairs under K policies theta_k (device array):
  *   out[n*K + k] = sum_i log Dirichlet(P_n[i,:] ; a_i),  a_ij = max(alpha_floor, alpha_scale * softplus(theta_k x_ij)).
