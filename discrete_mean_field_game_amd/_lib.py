@@ -141,6 +141,25 @@ SIGNATURES['mfg_train_rollouts_irl_pop'] = (_i32, [_p, _i64, _i64, _i32, _i32, _
                                                    _u32, _u64, _i32, _p, _p, C.POINTER(RewardNetStruct), _i32, _p, _u64, _p, _p,
                                                    _p, _p, _p, _p, _p, _p, _p, _sz, _p])
 
+# per-learner reward-call counters (device array [K]) and the learner stride of one flat parameter row per learner
+SIGNATURES['mfg_train_episodes_irl_pop_calls'] = (_i32, SIGNATURES['mfg_train_episodes_irl_pop'][1][:23] + [_i32, _i64, _p, _p]
+                                                  + SIGNATURES['mfg_train_episodes_irl_pop'][1][26:])
+SIGNATURES['mfg_train_rollouts_irl_pop_calls'] = (_i32, SIGNATURES['mfg_train_rollouts_irl_pop'][1][:21] + [_i32, _i64, _p, _p]
+                                                  + SIGNATURES['mfg_train_rollouts_irl_pop'][1][24:])
+SIGNATURES['mfg_reward_net_forward_pop'] = (_i32, [_p, _p, _i64, _i64, _i64, _i32, C.POINTER(RewardNetStruct), _i32, _i64, _i32, _p,
+                                                   _p, _i32, _u64, _p, _p, _sz, _p])
+
+
+class RnTrainPlan(C.Structure):
+    """mfg_rn_train_plan_t of include/mfg_hip.h: one update_reward of one learner of mfg_reward_net_train_steps_pop."""
+    _fields_ = [('learner', C.c_int32), ('lr_t', C.c_float), ('key', C.c_uint64), ('lr', C.c_double), ('adam_step', C.c_int64),
+                ('demo_rows', C.c_int32 * RN_TRAIN_MAX_TRAJ), ('gen_rows', C.c_int32 * RN_TRAIN_MAX_TRAJ)]
+
+
+SIGNATURES['mfg_reward_net_train_steps_pop'] = (_i32, [_p, _p, _p, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _p, _p, _i64, _p,
+                                                       _p, _i64, _p, _p, _sz, _i32, _i32, _i32, _i32, _i32, _i32, C.c_float,
+                                                       _i32, _f64, _f64, _f64, _p, _p, _sz, _p])
+
 _lib = None
 
 

@@ -30,8 +30,11 @@ struct IrlCorePop {
   double sc, sa;      // the episode's learning-rate multipliers (lr_schedule)
 };
 
-// the reward network's per-learner strides: states / actions / outputs, the learner's key rn_seed[k] ^ key_ctr, and its weights
-// (per_learner_net: learner k's tensor t at base_t + k numel_t, numel_t from the geometry; 0: shared)
+// the reward network's per-learner strides: states / actions / outputs, the learner's key, and its weights (per_learner_net:
+// learner k's tensor t at base_t + k numel_t, numel_t from the geometry, or at base_t + k s_net when s_net > 0; 0: shared).
+// Key of learner k: key[slot] when given, else rn_seed[k] ^ ((call_base[k] + call_j) 0x9E3779B97F4A7C15) when call_base is
+// given (per-learner reward-call counters), else rn_seed[k] ^ key_ctr.  Grid rows: n_y slots, slot -> learner[slot] when
+// learner is given (0 / NULL: K rows, slot = learner).
 struct RnPop {
   int K;
   int per_learner_net;
@@ -39,6 +42,12 @@ struct RnPop {
   int64_t s_ws;                                  // bytes (part_rows, col_f: in the learner's workspace slice)
   const uint64_t* rn_seed;
   uint64_t key_ctr;
+  int64_t s_net;                                 // elements between two learners' weights (0: numel_t per tensor)
+  const uint64_t* call_base;                     // [K] device (NULL: the shared key_ctr)
+  uint64_t call_j;
+  const uint64_t* key;                           // [n_y] device, by slot (NULL: from rn_seed)
+  const int32_t* learner;                        // [n_y] device (NULL: slot = learner)
+  int n_y;
 };
 
 int launch_core_irl_pop(const CoreArgs& a, const IrlCorePop& p, bool fast, int num_cus, hipStream_t st);
@@ -47,7 +56,8 @@ void launch_reduce_rows_apply_pop(const double* rows, int nrows, int64_t FO, dou
                                   const IrlCorePop& p, hipStream_t st);
 
 // true: K learners' networks of this geometry (fc3_w of every learner 8-byte aligned) run the matrix-core kernel
-bool reward_net_pop_ready(int d, const mfg_reward_net_t* net, int per_learner_net, int K);
+// (net_stride > 0: learner k's tensors at base + k net_stride; 0: the numel_t strides)
+bool reward_net_pop_ready(int d, const mfg_reward_net_t* net, int per_learner_net, int K, int64_t net_stride = 0);
 // the population form of reward_net_forward_sums for the matrix-core kernel (reward_net_pop_ready said yes); sums: the SUMS
 // variant with the TD error (*rows_out = partial rows per learner), NULL: the plain forward
 int reward_net_forward_pop(const float* state, const float* action, int64_t B, int d, const mfg_reward_net_t* net,

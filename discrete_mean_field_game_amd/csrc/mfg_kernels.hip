@@ -3141,7 +3141,7 @@ int mfg_train_rollouts_pop(const float* mat_pi0, int64_t num_start, int64_t B, i
   REQUIRE(episodes >= 0 && first_episode >= 0, "bad episode range");                                                     \
   REQUIRE((uint64_t)first_step + (uint64_t)episodes * (uint64_t)T <= 0xFFFFFFFFull, "Philox step counter would wrap");    \
   REQUIRE(traj_ids_ok(traj_offset, B), "trajectory ids traj_offset + B exceed 2^48 (MFG_TRAJ_ID_LIMIT)");               \
-  if (!reward_net_pop_ready(d, net, per_learner_net, K))                                                                 \
+  if (!reward_net_pop_ready(d, net, per_learner_net, K, net_stride))                                                               \
     return fail(MFG_EUNSUPPORTED, "IRL population: d=%d, k1=%d, f2=%d, k2=%d, n_fc3=%d, n_fc4=%d: not the matrix-core "      \
                 "reward network (d = 21 / 15, 5 / 2 / 3, n_fc3 <= 16, 8-byte aligned fc3_w of every learner)",           \
                 d, net->k1, net->f2, net->k2, net->n3, net->n4)
@@ -3166,14 +3166,17 @@ static IrlCorePop irl_core_pop(int K, int64_t B, int d, int T, int64_t episodes,
 
 static uint64_t rn_key_ctr(uint64_t call) { return call * 0x9E3779B97F4A7C15ull; }
 
-int mfg_train_episodes_irl_pop(const float* mat_pi0, int64_t num_start, float* pi_out, float* pi_scratch, int64_t B, int K, int d,
-                               int T, int64_t episodes, int64_t first_episode, int constant, double* theta, const double* shift,
-                               const double* alpha_scale, double* w, double gamma, const uint64_t* seed, uint32_t first_step,
-                               uint64_t traj_offset, int precision, const double* lr_critic, const double* lr_actor,
-                               const mfg_reward_net_t* net, int per_learner_net, const uint64_t* rn_seed, uint64_t rn_call0,
-                               float* P, float* reward, double* delta, double* g, double* G, double* reward_acc, void* workspace,
-                               size_t workspace_bytes, mfg_stream_t stream) {
+// (rn_call0_k: the per-learner reward-call counters [K] of mfg_train_episodes_irl_pop_calls, NULL: the shared rn_call0;
+//  net_stride: elements between two learners' weights, 0: the numel strides of the stacked tensors)
+static int train_episodes_irl_pop(const float* mat_pi0, int64_t num_start, float* pi_out, float* pi_scratch, int64_t B, int K, int d,
+                                  int T, int64_t episodes, int64_t first_episode, int constant, double* theta, const double* shift,
+                                  const double* alpha_scale, double* w, double gamma, const uint64_t* seed, uint32_t first_step,
+                                  uint64_t traj_offset, int precision, const double* lr_critic, const double* lr_actor,
+                                  const mfg_reward_net_t* net, int per_learner_net, int64_t net_stride, const uint64_t* rn_seed,
+                                  uint64_t rn_call0, const uint64_t* rn_call0_k, float* P, float* reward, double* delta, double* g,
+                                  double* G, double* reward_acc, void* workspace, size_t workspace_bytes, mfg_stream_t stream) {
   REQUIRE(pi_out && pi_scratch, "null pointer");
+  REQUIRE(net_stride >= 0, "net_stride < 0");
   CHECK_IRL_POP();
   CHECK_PRECISION();
   // one learner's slice: control block (two theta slots at bytes 16 / 24) | column F of the rows [max_rows] | rows [max_rows][FO]
@@ -3196,6 +3199,8 @@ int mfg_train_episodes_irl_pop(const float* mat_pi0, int64_t num_start, float* p
   rp.s_w = FO - 3;
   rp.s_ws = (int64_t)workspace_bytes;
   rp.rn_seed = rn_seed;
+  rp.call_base = rn_call0_k;
+  rp.s_net = per_learner_net ? net_stride : 0;
   double* rows_buf = reinterpret_cast<double*>((char*)workspace + MFG_WS_CONTROL_BYTES) + max_rows;
   double* th_slot = reinterpret_cast<double*>((char*)workspace + 16);  // two slots: theta after odd / even steps
   for (int64_t e = 0; e < episodes; ++e) {
@@ -3248,6 +3253,7 @@ int mfg_train_episodes_irl_pop(const float* mat_pi0, int64_t num_start, float* p
         s_th_in = (int64_t)workspace_bytes;
       }
       rp.key_ctr = rn_key_ctr(rn_call0 + (uint64_t)(e * T + s) + 1ull);
+      rp.call_j = (uint64_t)(e * T + s) + 1ull;
       RnSums sm{};
       sm.g = g;
       sm.delta_out = delta;
@@ -3274,14 +3280,15 @@ int mfg_train_episodes_irl_pop(const float* mat_pi0, int64_t num_start, float* p
   return MFG_OK;
 }
 
-int mfg_train_rollouts_irl_pop(const float* mat_pi0, int64_t num_start, int64_t B, int K, int d, int T, int64_t episodes,
-                               int64_t first_episode, int constant, double* theta, const double* shift, const double* alpha_scale,
-                               double* w, double gamma, const uint64_t* seed, uint32_t first_step, uint64_t traj_offset, int flags,
-                               const double* lr_critic, const double* lr_actor, const mfg_reward_net_t* net, int per_learner_net,
-                               const uint64_t* rn_seed, uint64_t rn_call0, float* pi_traj, float* pi_last, float* P, float* reward,
-                               double* delta, double* g, double* G, double* reward_acc, void* workspace, size_t workspace_bytes,
-                               mfg_stream_t stream) {
+static int train_rollouts_irl_pop(const float* mat_pi0, int64_t num_start, int64_t B, int K, int d, int T, int64_t episodes,
+                                  int64_t first_episode, int constant, double* theta, const double* shift, const double* alpha_scale,
+                                  double* w, double gamma, const uint64_t* seed, uint32_t first_step, uint64_t traj_offset, int flags,
+                                  const double* lr_critic, const double* lr_actor, const mfg_reward_net_t* net, int per_learner_net,
+                                  int64_t net_stride, const uint64_t* rn_seed, uint64_t rn_call0, const uint64_t* rn_call0_k,
+                                  float* pi_traj, float* pi_last, float* P, float* reward, double* delta, double* g, double* G,
+                                  double* reward_acc, void* workspace, size_t workspace_bytes, mfg_stream_t stream) {
   REQUIRE(pi_traj, "null pointer");
+  REQUIRE(net_stride >= 0, "net_stride < 0");
   CHECK_IRL_POP();
   const size_t need = pop_workspace_need(d, B * T, false);
   if (workspace_bytes < need)
@@ -3303,6 +3310,8 @@ int mfg_train_rollouts_irl_pop(const float* mat_pi0, int64_t num_start, int64_t 
   rp.s_n = B * T;
   rp.s_ws = (int64_t)workspace_bytes;
   rp.rn_seed = rn_seed;
+  rp.call_base = rn_call0_k;
+  rp.s_net = per_learner_net ? net_stride : 0;
   const int precision = (flags & MFG_ROLLOUT_F64) ? MFG_PRECISION_F64 : MFG_PRECISION_MIXED;
   for (int64_t e = 0; e < episodes; ++e) {
     lr_schedule(first_episode + e, constant, &p.sc, &p.sa);
@@ -3331,6 +3340,7 @@ int mfg_train_rollouts_irl_pop(const float* mat_pi0, int64_t num_start, int64_t 
     if (rc != MFG_OK) return rc;
     // ONE reward-network pass over each learner's Bk T transitions, states read in place from pi_traj
     rp.key_ctr = rn_key_ctr(rn_call0 + (uint64_t)e + 1ull);
+    rp.call_j = (uint64_t)e + 1ull;
     rc = reward_net_forward_pop(pi_traj, P, B * (int64_t)T, d, net, traj_offset * (uint64_t)T, reward, nullptr, nullptr, rp, st, T);
     if (rc != MFG_OK) return rc;
     const ApplyArgs ap{0.0, 0.0, w, theta, reward_acc ? reward_acc + e : nullptr};
@@ -3341,6 +3351,62 @@ int mfg_train_rollouts_irl_pop(const float* mat_pi0, int64_t num_start, int64_t 
     if (!applied) return fail(MFG_ELAUNCH, "%s", "IRL population: update not applied");  // (not reached: d <= 64)
   }
   return check_launch("train_rollouts_irl_pop");
+}
+
+int mfg_train_episodes_irl_pop(const float* mat_pi0, int64_t num_start, float* pi_out, float* pi_scratch, int64_t B, int K, int d,
+                               int T, int64_t episodes, int64_t first_episode, int constant, double* theta, const double* shift,
+                               const double* alpha_scale, double* w, double gamma, const uint64_t* seed, uint32_t first_step,
+                               uint64_t traj_offset, int precision, const double* lr_critic, const double* lr_actor,
+                               const mfg_reward_net_t* net, int per_learner_net, const uint64_t* rn_seed, uint64_t rn_call0,
+                               float* P, float* reward, double* delta, double* g, double* G, double* reward_acc, void* workspace,
+                               size_t workspace_bytes, mfg_stream_t stream) {
+  return train_episodes_irl_pop(mat_pi0, num_start, pi_out, pi_scratch, B, K, d, T, episodes, first_episode, constant, theta, shift,
+                                alpha_scale, w, gamma, seed, first_step, traj_offset, precision, lr_critic, lr_actor, net,
+                                per_learner_net, 0, rn_seed, rn_call0, nullptr, P, reward, delta, g, G, reward_acc, workspace,
+                                workspace_bytes, stream);
+}
+
+int mfg_train_episodes_irl_pop_calls(const float* mat_pi0, int64_t num_start, float* pi_out, float* pi_scratch, int64_t B, int K,
+                                     int d, int T, int64_t episodes, int64_t first_episode, int constant, double* theta,
+                                     const double* shift, const double* alpha_scale, double* w, double gamma, const uint64_t* seed,
+                                     uint32_t first_step, uint64_t traj_offset, int precision, const double* lr_critic,
+                                     const double* lr_actor, const mfg_reward_net_t* net, int per_learner_net, int64_t net_stride,
+                                     const uint64_t* rn_seed, const uint64_t* rn_call0, float* P, float* reward, double* delta,
+                                     double* g, double* G, double* reward_acc, void* workspace, size_t workspace_bytes,
+                                     mfg_stream_t stream) {
+  REQUIRE(rn_call0, "null pointer");
+  return train_episodes_irl_pop(mat_pi0, num_start, pi_out, pi_scratch, B, K, d, T, episodes, first_episode, constant, theta, shift,
+                                alpha_scale, w, gamma, seed, first_step, traj_offset, precision, lr_critic, lr_actor, net,
+                                per_learner_net, net_stride, rn_seed, 0, rn_call0, P, reward, delta, g, G, reward_acc, workspace,
+                                workspace_bytes, stream);
+}
+
+int mfg_train_rollouts_irl_pop(const float* mat_pi0, int64_t num_start, int64_t B, int K, int d, int T, int64_t episodes,
+                               int64_t first_episode, int constant, double* theta, const double* shift, const double* alpha_scale,
+                               double* w, double gamma, const uint64_t* seed, uint32_t first_step, uint64_t traj_offset, int flags,
+                               const double* lr_critic, const double* lr_actor, const mfg_reward_net_t* net, int per_learner_net,
+                               const uint64_t* rn_seed, uint64_t rn_call0, float* pi_traj, float* pi_last, float* P, float* reward,
+                               double* delta, double* g, double* G, double* reward_acc, void* workspace, size_t workspace_bytes,
+                               mfg_stream_t stream) {
+  return train_rollouts_irl_pop(mat_pi0, num_start, B, K, d, T, episodes, first_episode, constant, theta, shift, alpha_scale, w,
+                                gamma, seed, first_step, traj_offset, flags, lr_critic, lr_actor, net, per_learner_net, 0, rn_seed,
+                                rn_call0, nullptr, pi_traj, pi_last, P, reward, delta, g, G, reward_acc, workspace,
+                                workspace_bytes, stream);
+}
+
+int mfg_train_rollouts_irl_pop_calls(const float* mat_pi0, int64_t num_start, int64_t B, int K, int d, int T, int64_t episodes,
+                                     int64_t first_episode, int constant, double* theta, const double* shift,
+                                     const double* alpha_scale, double* w, double gamma, const uint64_t* seed, uint32_t first_step,
+                                     uint64_t traj_offset, int flags, const double* lr_critic, const double* lr_actor,
+                                     const mfg_reward_net_t* net, int per_learner_net, int64_t net_stride, const uint64_t* rn_seed,
+                                     const uint64_t* rn_call0, float* pi_traj, float* pi_last, float* P, float* reward,
+                                     double* delta, double* g, double* G, double* reward_acc, void* workspace,
+                                     size_t workspace_bytes, mfg_stream_t stream) {
+  REQUIRE(rn_call0, "null pointer");
+  return train_rollouts_irl_pop(mat_pi0, num_start, B, K, d, T, episodes, first_episode, constant, theta, shift, alpha_scale, w,
+                                gamma, seed, first_step, traj_offset, flags, lr_critic, lr_actor, net, per_learner_net, net_stride,
+                                rn_seed, 0, rn_call0, pi_traj, pi_last, P, reward, delta, g, G, reward_acc, workspace,
+                                workspace_bytes, stream);
 }
 
 int mfg_train_rollout_irl(const float* mat_pi0, int64_t num_start, const int32_t* idx, int64_t B, int d, int T, double* theta,

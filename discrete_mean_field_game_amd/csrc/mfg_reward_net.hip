@@ -12,6 +12,8 @@
 #include <stdint.h>
 
 #include <mutex>
+#include <string.h>
+#include <vector>
 
 #include "../../include/mfg_hip.h"
 #include "mfg_core.h"
@@ -1145,9 +1147,13 @@ __global__ __launch_bounds__(RM_BLOCK) void k_reward_net_mfma(RewardNetArgs a) {
 // population form (mfg_irl_population.h): learner blockIdx.y -- its weights, key, states, actions, outputs and workspace rows
 template <int D, int RUN, int RPR, int P1, bool SUMS>
 __global__ __launch_bounds__(RM_BLOCK) void k_reward_net_mfma_pop(RewardNetArgs a, RnPop p) {
-  const int k = blockIdx.y;
+  const int slot = blockIdx.y;
+  const int k = p.learner ? p.learner[slot] : slot;
   RewardNetArgs b = a;
-  if (p.per_learner_net) {
+  if (p.per_learner_net && p.s_net > 0) {
+    const int64_t o = p.s_net * k;
+    b.c1w += o; b.c1b += o; b.c2w += o; b.c2b += o; b.w3 += o; b.b3 += o; b.w4 += o; b.b4 += o; b.wo += o; b.bo += o;
+  } else if (p.per_learner_net) {
     const int64_t n3 = a.n3, n4 = a.n4;
     b.c1w += (int64_t)MfmaGeom<D, RUN, RPR, P1>::K1 * MfmaGeom<D, RUN, RPR, P1>::K1 * k;
     b.c1b += k;
@@ -1160,7 +1166,8 @@ __global__ __launch_bounds__(RM_BLOCK) void k_reward_net_mfma_pop(RewardNetArgs 
     b.wo += n4 * k;
     b.bo += k;
   }
-  b.seed = p.rn_seed[k] ^ p.key_ctr;
+  b.seed = p.key ? p.key[slot]
+                 : p.rn_seed[k] ^ (p.call_base ? (p.call_base[k] + p.call_j) * 0x9E3779B97F4A7C15ull : p.key_ctr);
   b.state += p.s_state * k;
   b.action += p.s_action * k;
   b.reward += p.s_n * k;
@@ -1346,14 +1353,14 @@ static bool mfma_lds_attribute_pop() {
   return attr_state[dev] > 0;
 }
 
-bool reward_net_pop_ready(int d, const mfg_reward_net_t* net, int per_learner_net, int K) {
+bool reward_net_pop_ready(int d, const mfg_reward_net_t* net, int per_learner_net, int K, int64_t net_stride) {
   if (!net || K < 1 || net->n3 < 1 || net->n4 < 1 || net->n4 > RN_MAXN) return false;
   if (!net->conv1_w || !net->conv1_b || !net->conv2_w || !net->conv2_b || !net->fc3_w || !net->fc3_b || !net->fc4_w ||
       !net->fc4_b || !net->out_w || !net->out_b)
     return false;
   const int64_t n_w3 = (int64_t)net->n3 * net->f2 * d * d;
   for (int k = 0; k < (per_learner_net ? K : 1); ++k)
-    if (!mfma_shape_ok(d, net->k1, net->f2, net->k2, net->n3, net->fc3_w + n_w3 * k)) return false;
+    if (!mfma_shape_ok(d, net->k1, net->f2, net->k2, net->n3, net->fc3_w + (net_stride > 0 ? net_stride : n_w3) * k)) return false;
   return d == 21 ? mfma_lds_attribute_pop<21, 7, 3, MFG_RM_P21>() : mfma_lds_attribute_pop<15, 5, 3, MFG_RM_P15>();
 }
 
@@ -1363,7 +1370,7 @@ static void launch_reward_net_mfma_pop(const RewardNetArgs& a, bool sums, const 
   int64_t grid = (a.B + RM_WAVES - 1) / RM_WAVES;  // (the single launch's grid for one learner)
   if (grid > 256) grid = 256;
   const size_t lds = Gm::lds_floats(a.n3, a.n4, sums) * 4;
-  const dim3 g((unsigned)grid, (unsigned)p.K);
+  const dim3 g((unsigned)grid, (unsigned)(p.n_y > 0 ? p.n_y : p.K));
   if (sums) hipLaunchKernelGGL((k_reward_net_mfma_pop<D, RUN, RPR, P1, true>), g, dim3(RM_BLOCK), lds, st, a, p);
   else hipLaunchKernelGGL((k_reward_net_mfma_pop<D, RUN, RPR, P1, false>), g, dim3(RM_BLOCK), lds, st, a, p);
   if (rows_out) *rows_out = sums ? (int)grid : 0;
@@ -1373,7 +1380,7 @@ int reward_net_forward_pop(const float* state, const float* action, int64_t B, i
                            uint64_t sample_offset, float* reward, const RnSums* sums, int* rows_out, const RnPop& p, hipStream_t st,
                            int state_T) {
   if (rows_out) *rows_out = 0;
-  if (B < 1 || !state || !action || !reward || !reward_net_pop_ready(d, net, p.per_learner_net, p.K))
+  if (B < 1 || !state || !action || !reward || !reward_net_pop_ready(d, net, p.per_learner_net, p.K, p.s_net))
     return set_error(MFG_EUNSUPPORTED, "reward_net population: not the matrix-core geometry");
   if (!(net->keep_prob > 0.0f && net->keep_prob <= 1.0f)) return set_error(MFG_EINVAL, "reward_net: keep_prob must be in (0,1]");
   RewardNetArgs a{state, action, B, d, net->k1, net->f2, net->k2, net->n3, net->n4, net->conv1_w, net->conv1_b, net->conv2_w,
@@ -1407,6 +1414,46 @@ extern "C" int mfg_reward_net_forward(const float* state, const float* action, i
                                       uint64_t seed, uint64_t sample_offset, float* reward, mfg_stream_t stream) {
   return mfg::reward_net_forward_sums(state, action, B, d, k1, f2, k2, n3, n4, conv1_w, conv1_b, conv2_w, conv2_b, fc3_w, fc3_b,
                                       fc4_w, fc4_b, out_w, out_b, keep_prob, seed, sample_offset, reward, nullptr, nullptr, stream, 0);
+}
+
+extern "C" int mfg_reward_net_forward_pop(const float* state, const float* action, int64_t s_state, int64_t s_action, int64_t N,
+                                          int d, const mfg_reward_net_t* net, int per_learner_net, int64_t net_stride, int K,
+                                          const int32_t* learners_host, const uint64_t* keys_host, int n, uint64_t sample_offset,
+                                          float* reward, void* scratch, size_t scratch_bytes, mfg_stream_t stream) {
+  if (!state || !action || !net || !reward || !learners_host || !keys_host || !scratch || K < 1 || K > MFG_POP_MAX_K || n < 0 ||
+      n > K || N < 0 || s_state < 0 || s_action < 0 || net_stride < 0 || (s_state && s_state < N * d) ||
+      (s_action && s_action < N * d * d))
+    return set_error(MFG_EINVAL, "reward_net_forward_pop: null pointer / bad count / overlapping learner inputs");
+  if (!(net->keep_prob > 0.0f && net->keep_prob <= 1.0f)) return set_error(MFG_EINVAL, "reward_net_forward_pop: keep_prob must be in (0,1]");
+  std::vector<char> seen((size_t)K, 0);
+  for (int s = 0; s < n; ++s) {
+    if (learners_host[s] < 0 || learners_host[s] >= K) return set_error(MFG_EINVAL, "reward_net_forward_pop: learner id out of range");
+    if (seen[(size_t)learners_host[s]]) return set_error(MFG_EINVAL, "reward_net_forward_pop: a learner twice in the list");
+    seen[(size_t)learners_host[s]] = 1;
+  }
+  if (!reward_net_pop_ready(d, net, per_learner_net, K, per_learner_net ? net_stride : 0))
+    return set_error(MFG_EUNSUPPORTED, "reward_net_forward_pop: not the matrix-core reward network (d = 21 / 15, 5 / 2 / 3, "
+                                       "n_fc3 <= 16, 8-byte aligned fc3_w of every learner)");
+  if (scratch_bytes < (size_t)n * 16) return set_error(MFG_EWORKSPACE, "reward_net_forward_pop: scratch holds fewer than 16 n bytes");
+  if (n == 0 || N == 0) return MFG_OK;
+  // keys [n] uint64 | learners [n] int32, uploaded once; the host copy dies with this frame, so the stream is drained first
+  std::vector<unsigned char> up((size_t)n * 12);
+  memcpy(up.data(), keys_host, (size_t)n * 8);
+  memcpy(up.data() + (size_t)n * 8, learners_host, (size_t)n * 4);
+  hipStream_t st = (hipStream_t)stream;
+  if (hipMemcpyAsync(scratch, up.data(), up.size(), hipMemcpyHostToDevice, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
+    return set_error(MFG_ELAUNCH, "reward_net_forward_pop: key upload failed");
+  RnPop rp{};
+  rp.K = K;
+  rp.per_learner_net = per_learner_net ? 1 : 0;
+  rp.s_state = s_state;
+  rp.s_action = s_action;
+  rp.s_n = N;
+  rp.s_net = per_learner_net ? net_stride : 0;
+  rp.key = (const uint64_t*)scratch;
+  rp.learner = (const int32_t*)((const char*)scratch + (size_t)n * 8);
+  rp.n_y = n;
+  return reward_net_forward_pop(state, action, N, d, net, sample_offset, reward, nullptr, nullptr, rp, st, 0);
 }
 
 #ifdef MFG_RN_STAMPS

@@ -28,6 +28,8 @@
 #include <math.h>
 #include <stdint.h>
 
+#include <vector>
+
 #include "../../include/mfg_hip.h"
 #include "mfg_core.h"
 #include "mfg_rn_common.h"
@@ -65,7 +67,7 @@ __host__ __device__ inline RtLayout rt_layout(int d, int k1, int f2, int k2, int
 // index of parameter p (outside fc3_w) in a sample's small Jacobian row
 __device__ __forceinline__ int rt_small(const RtLayout& L, int p) { return p < L.o_w3 ? p : p - (L.o_b3 - L.o_w3); }
 
-struct RtArgs {
+struct RtNet {
   const float* params;
   int d, k1, f2, k2, n3, n4;
   const float *demo_state, *demo_action, *gen_state, *gen_action;
@@ -74,19 +76,29 @@ struct RtArgs {
   int l1l2;
   uint64_t seed;
   float *r, *a2, *dz3, *js, *reg;  // workspace: [N], [N][a2], [N][n3], [N][ns], [1]
+};
+struct RtArgs : RtNet {
   int32_t rows[2 * RT_MAX_TRAJ];   // store rows of the batch: demonstrations, then generated
+};
+// population form (mfg_reward_net_train_steps_pop): slot blockIdx.y serves learner plan[slot].learner
+struct RtPop {
+  const mfg_rn_train_plan_t* plan;  // [n_active] entries of this update (device)
+  int64_t s_params;                 // elements between two learners' params / adam_m / adam_v
+  int64_t s_gen_state, s_gen_action;  // elements between two learners' generated stores
+  int64_t s_ws;                     // floats between two slots' workspace slices
 };
 
 // ---------------------------------------------------------------------------------------------------------------------
 // launch 1: one block per transition
 // ---------------------------------------------------------------------------------------------------------------------
-__device__ void rn_train_reg_block(const struct RtArgs& a, const RtLayout& L);
+__device__ void rn_train_reg_block(const struct RtNet& a, const RtLayout& L);
 
 // K1 / K2 / F2 > 0: compile-time conv geometry (the reference's 5 / 3 / 2: taps unroll, weights come as scalar loads,
 // the weight-gradient accumulators stay in registers); 0 = run-time geometry, tap by tap (any odd k <= 7, f2 <= 2).
 // QA: fc3 inputs per thread (4 covers f2 d^2 <= 1024, i.e. d <= 22 with two filters; 8 everything up to d = 32)
+// (the body of k_rn_train_sample; `row` = the store row of this block's trajectory, its population form passes the plan's)
 template <int K1, int K2, int F2, int QA>
-__global__ __launch_bounds__(RT_BLOCK) void k_rn_train_sample(RtArgs a) {
+__device__ __forceinline__ void rn_train_sample_body(const RtNet& a, int32_t row) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   __shared__ float red[RT_WAVES][64];
   __shared__ float s_h3[RT_MAXN], s_h4[RT_MAXN], s_dz3[RT_MAXN], s_dz4[RT_MAXN], s_state[32], s_dzo;
@@ -103,7 +115,7 @@ __global__ __launch_bounds__(RT_BLOCK) void k_rn_train_sample(RtArgs a) {
   // which transition: trajectory j of the batch, step t
   const int j = n / a.steps, t = n - j * a.steps;
   const bool demo = j < a.n_demo;
-  const int64_t tr = (int64_t)a.rows[demo ? j : RT_MAX_TRAJ + (j - a.n_demo)] * a.steps + t;
+  const int64_t tr = (int64_t)row * a.steps + t;
   const float* state = (demo ? a.demo_state : a.gen_state) + tr * d;
   const float* act = (demo ? a.demo_action : a.gen_action) + tr * dd;
   const float* P = a.params;
@@ -435,7 +447,7 @@ __global__ __launch_bounds__(RT_BLOCK) void k_rn_train_sample(RtArgs a) {
 }
 
 // the regulariser's value l1_l2(fc3_w) + l1_l2(fc4_w) (weights are read-only in launch 1): its own block, next to the samples
-__device__ void rn_train_reg_block(const RtArgs& a, const RtLayout& L) {
+__device__ void rn_train_reg_block(const RtNet& a, const RtLayout& L) {
   __shared__ float redr[RT_WAVES];
   const int tid = threadIdx.x, lane = tid & (WAVE - 1), wv = tid / WAVE;
   const float* P = a.params;
@@ -448,6 +460,37 @@ __device__ void rn_train_reg_block(const RtArgs& a, const RtLayout& L) {
   if (lane == 0) redr[wv] = s;
   __syncthreads();
   if (tid == 0) a.reg[0] = redr[0] + redr[1] + redr[2] + redr[3];
+}
+
+template <int K1, int K2, int F2, int QA>
+__global__ __launch_bounds__(RT_BLOCK) void k_rn_train_sample(RtArgs a) {
+  const int n = blockIdx.x, N = (a.n_demo + a.n_gen) * a.steps;
+  int32_t row = 0;
+  if (n < N) {
+    const int j = n / a.steps;
+    row = a.rows[j < a.n_demo ? j : RT_MAX_TRAJ + (j - a.n_demo)];
+  }
+  rn_train_sample_body<K1, K2, F2, QA>(a, row);
+}
+
+template <int K1, int K2, int F2, int QA>
+__global__ __launch_bounds__(RT_BLOCK) void k_rn_train_sample_pop(RtNet a, RtPop p) {
+  const mfg_rn_train_plan_t& e = p.plan[blockIdx.y];
+  const int k = e.learner;
+  RtNet b = a;
+  b.params = a.params + p.s_params * k;
+  b.gen_state = a.gen_state ? a.gen_state + p.s_gen_state * k : a.gen_state;
+  b.gen_action = a.gen_action ? a.gen_action + p.s_gen_action * k : a.gen_action;
+  b.seed = e.key;
+  const int64_t o = p.s_ws * blockIdx.y;
+  b.reg = a.reg + o; b.r = a.r + o; b.dz3 = a.dz3 + o; b.js = a.js + o; b.a2 = a.a2 + o;
+  const int n = blockIdx.x, N = (a.n_demo + a.n_gen) * a.steps;
+  int32_t row = 0;
+  if (n < N) {
+    const int j = n / a.steps;
+    row = j < a.n_demo ? e.demo_rows[j] : e.gen_rows[j - a.n_demo];
+  }
+  rn_train_sample_body<K1, K2, F2, QA>(b, row);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -477,7 +520,7 @@ __device__ __forceinline__ float adam_param(float p, float g, float& m, float& v
 // slice order (fixed association: bit-reproducible).  The first version ran one thread per parameter over all 150 samples
 // with a load and an integer division per iteration: 30 us, all of it L2 latency.
 constexpr int RT_CP = WAVE, RT_CU = 38, RT_DZ = 8;  // RT_CU: one round covers 4 x 38 = 152 samples (the reference batch is 150; a second round of reads cost 4 us)
-__global__ __launch_bounds__(RT_BLOCK) void k_rn_train_combine(RtCombineArgs a) {
+__device__ __forceinline__ void rn_train_combine_body(const RtCombineArgs& a) {
   __shared__ float s_c[2 * RT_MAX_TRAJ];  // dL/dr per trajectory: demonstrations, then generated
   __shared__ float s_S[RT_MAX_TRAJ];
   __shared__ float s_stat[2];
@@ -611,6 +654,23 @@ __global__ __launch_bounds__(RT_BLOCK) void k_rn_train_combine(RtCombineArgs a) 
   }
 }
 
+__global__ __launch_bounds__(RT_BLOCK) void k_rn_train_combine(RtCombineArgs a) { rn_train_combine_body(a); }
+
+// population form: slot blockIdx.y updates learner plan[slot].learner with the plan's lr_t; stats [K][4]
+__global__ __launch_bounds__(RT_BLOCK) void k_rn_train_combine_pop(RtCombineArgs a, RtPop p) {
+  const mfg_rn_train_plan_t& e = p.plan[blockIdx.y];
+  const int k = e.learner;
+  RtCombineArgs b = a;
+  b.params = a.params + p.s_params * k;
+  b.m = a.m + p.s_params * k;
+  b.v = a.v + p.s_params * k;
+  b.stats = a.stats + 4 * k;
+  const int64_t o = p.s_ws * blockIdx.y;
+  b.r = a.r + o; b.a2 = a.a2 + o; b.dz3 = a.dz3 + o; b.js = a.js + o; b.reg = a.reg + o;
+  b.lr_t = e.lr_t;
+  rn_train_combine_body(b);
+}
+
 __global__ __launch_bounds__(RT_BLOCK) void k_rn_adam(float* params, float* m, float* v, const float* grad, int64_t n, float lr_t,
                                                       float b1, float b2, float eps) {
   const int64_t p = (int64_t)blockIdx.x * RT_BLOCK + threadIdx.x;
@@ -734,6 +794,100 @@ int mfg_reward_net_adam(float* params, float* adam_m, float* adam_v, const float
   hipLaunchKernelGGL(k_rn_adam, dim3((unsigned)((n + RT_BLOCK - 1) / RT_BLOCK)), dim3(RT_BLOCK), 0, (hipStream_t)stream, params, adam_m,
                      adam_v, grad, n, adam_lr_t(lr, beta1, beta2, adam_step), (float)beta1, (float)beta2, (float)eps);
   return hipGetLastError() == hipSuccess ? MFG_OK : set_error(MFG_ELAUNCH, "reward_net_adam: launch failed");
+}
+
+int mfg_reward_net_train_steps_pop(float* params, float* adam_m, float* adam_v, int64_t param_stride, int K, int d, int k1, int f2,
+                                   int k2, int n3, int n4, const float* demo_state, const float* demo_action, int64_t demo_capacity,
+                                   const float* gen_state, const float* gen_action, int64_t gen_capacity,
+                                   mfg_rn_train_plan_t* plan_host, void* plan_dev, size_t plan_dev_bytes, int n_updates,
+                                   int n_active, int n_demo, int n_gen, int steps, int demo_divisor, float keep_prob, int l1l2,
+                                   double beta1, double beta2, double eps, float* stats, void* workspace, size_t workspace_bytes,
+                                   mfg_stream_t stream) {
+  if (!params || !adam_m || !adam_v || !stats || !workspace || !plan_host || !plan_dev || K < 1 || n_updates < 0 ||
+      n_active < 0 || n_active > K || n_demo < 0 || n_gen < 0 || steps < 1 || demo_divisor < 1 ||
+      (n_demo && (!demo_state || !demo_action || demo_capacity < 1)) || (n_gen && (!gen_state || !gen_action || gen_capacity < 1)))
+    return set_error(MFG_EINVAL, "reward_net_train_steps_pop: null pointer / bad count");
+  if (!(keep_prob > 0.0f && keep_prob <= 1.0f)) return set_error(MFG_EINVAL, "reward_net_train_steps_pop: keep_prob must be in (0,1]");
+  if (!((d == 15 || d == 21) && k1 == 5 && f2 == 2 && k2 == 3 && n3 >= 1 && n3 <= 16 && n4 >= 1 && n4 <= RT_MAXN))
+    return set_error(MFG_EUNSUPPORTED, "reward_net_train_steps_pop: the population geometry is d = 15 / 21, k1 = 5, f2 = 2, k2 = 3, "
+                                       "n_fc3 <= 16, n_fc4 <= 32");
+  const RtLayout L = rt_layout(d, k1, f2, k2, n3, n4);
+  if (param_stride < L.np) return set_error(MFG_EINVAL, "reward_net_train_steps_pop: param_stride < the parameter count");
+  if (n_demo > RT_MAX_TRAJ || n_gen > RT_MAX_TRAJ)
+    return set_error(MFG_EUNSUPPORTED, "reward_net_train_steps_pop: at most MFG_RN_TRAIN_MAX_TRAJ trajectories per batch half");
+  const int64_t N = (int64_t)(n_demo + n_gen) * steps;
+  if (N == 0) return set_error(MFG_EINVAL, "reward_net_train_steps_pop: empty batch");
+  if (N > 8 * RT_BLOCK || (size_t)N * (size_t)(1 + n3) * sizeof(float) > 60 * 1024)
+    return set_error(MFG_EUNSUPPORTED, "reward_net_train_steps_pop: batch too large ((n_demo + n_gen) * steps <= 2048 and * (1 + n_fc3) * 4 B <= 60 KB)");
+  // one slot's slice: the single step's workspace rounded up to 256 bytes
+  const size_t slice = (mfg_reward_net_train_workspace_bytes(d, k1, f2, k2, n3, n4, N) + 255) / 256 * 256;
+  const int64_t n_plan = (int64_t)n_updates * n_active;
+  if (workspace_bytes < slice * (size_t)n_active)
+    return set_error(MFG_EWORKSPACE, "reward_net_train_steps_pop: workspace too small (n_active slices of the single step's, rounded up to 256 B)");
+  // everything is checked before the first launch: learners, rows, Adam steps (lr_t is written into plan_host on the way)
+  mfg_rn_train_plan_t* plan = plan_host;
+  std::vector<int64_t> seen((size_t)K, -1);
+  for (int64_t u = 0; u < n_updates; ++u)
+    for (int s = 0; s < n_active; ++s) {
+      mfg_rn_train_plan_t& e = plan[(size_t)(u * n_active + s)];
+      if (e.learner < 0 || e.learner >= K) return set_error(MFG_EINVAL, "reward_net_train_steps_pop: learner id out of range");
+      if (seen[(size_t)e.learner] == u) return set_error(MFG_EINVAL, "reward_net_train_steps_pop: a learner twice in one update");
+      seen[(size_t)e.learner] = u;
+      if (e.adam_step < 1) return set_error(MFG_EINVAL, "reward_net_train_steps_pop: Adam step < 1");
+      for (int j = 0; j < n_demo; ++j)
+        if (e.demo_rows[j] < 0 || e.demo_rows[j] >= demo_capacity)
+          return set_error(MFG_EINVAL, "reward_net_train_steps_pop: demonstration row negative / beyond the store");
+      for (int j = 0; j < n_gen; ++j)
+        if (e.gen_rows[j] < 0 || e.gen_rows[j] >= gen_capacity)
+          return set_error(MFG_EINVAL, "reward_net_train_steps_pop: generated row negative / beyond the store");
+      e.lr_t = adam_lr_t(e.lr, beta1, beta2, e.adam_step);
+    }
+  if (plan_dev_bytes < (size_t)n_plan * sizeof(mfg_rn_train_plan_t))
+    return set_error(MFG_EWORKSPACE, "reward_net_train_steps_pop: plan_dev holds fewer than n_updates * n_active entries");
+  if (n_plan == 0) return MFG_OK;
+  hipStream_t st = (hipStream_t)stream;
+  // ONE upload of the plan per call; the caller may reuse plan_host on return, so the stream is drained before the launches
+  if (hipMemcpyAsync(plan_dev, plan, (size_t)n_plan * sizeof(mfg_rn_train_plan_t), hipMemcpyHostToDevice, st) != hipSuccess ||
+      hipStreamSynchronize(st) != hipSuccess)
+    return set_error(MFG_ELAUNCH, "reward_net_train_steps_pop: plan upload failed");
+  RtNet a{};
+  a.params = params;
+  a.d = d; a.k1 = k1; a.f2 = f2; a.k2 = k2; a.n3 = n3; a.n4 = n4;
+  a.demo_state = demo_state; a.demo_action = demo_action; a.gen_state = gen_state; a.gen_action = gen_action;
+  a.steps = steps; a.n_demo = n_demo; a.n_gen = n_gen;
+  a.keep_prob = keep_prob;
+  a.l1l2 = l1l2 ? 1 : 0;
+  float* ws = (float*)workspace;
+  a.reg = ws;
+  a.r = ws + 4;
+  a.dz3 = a.r + N;
+  a.js = a.dz3 + N * n3;
+  a.a2 = a.js + N * L.ns;
+  RtCombineArgs c{};
+  c.params = params; c.m = adam_m; c.v = adam_v; c.grad = nullptr; c.stats = stats;
+  c.r = a.r; c.a2 = a.a2; c.dz3 = a.dz3; c.js = a.js; c.reg = a.reg;
+  c.d = d; c.k1 = k1; c.f2 = f2; c.k2 = k2; c.n3 = n3; c.n4 = n4;
+  c.steps = steps; c.n_demo = n_demo; c.n_gen = n_gen;
+  c.demo_scale = 1.0f / (float)demo_divisor;
+  c.l1l2 = a.l1l2;
+  c.apply = 1;
+  c.beta1 = (float)beta1; c.beta2 = (float)beta2; c.eps = (float)eps;
+  RtPop p{};
+  p.s_params = param_stride;
+  p.s_gen_state = gen_capacity * steps * d;
+  p.s_gen_action = gen_capacity * steps * d * d;
+  p.s_ws = (int64_t)(slice / sizeof(float));
+  const int h1 = k1 / 2, h2 = k2 / 2, W1 = d + 2 * h1, W2 = d + 2 * h2;
+  const size_t lds = (size_t)(W1 * W1 + W2 * W2 + L.a2 + f2 * W2 * W2 + L.ns) * sizeof(float);
+  const dim3 g1((unsigned)N + 1, (unsigned)n_active), g2((unsigned)((L.np + RT_CP - 1) / RT_CP), (unsigned)n_active);
+  const mfg_rn_train_plan_t* pd = (const mfg_rn_train_plan_t*)plan_dev;
+  for (int64_t u = 0; u < n_updates; ++u) {
+    p.plan = pd + u * n_active;
+    if (L.a2 <= 4 * RT_BLOCK) hipLaunchKernelGGL((k_rn_train_sample_pop<5, 3, 2, 4>), g1, dim3(RT_BLOCK), lds, st, a, p);
+    else hipLaunchKernelGGL((k_rn_train_sample_pop<5, 3, 2, 8>), g1, dim3(RT_BLOCK), lds, st, a, p);
+    hipLaunchKernelGGL(k_rn_train_combine_pop, g2, dim3(RT_BLOCK), (size_t)N * (1 + n3) * sizeof(float), st, c, p);
+  }
+  return hipGetLastError() == hipSuccess ? MFG_OK : set_error(MFG_ELAUNCH, "reward_net_train_steps_pop: launch failed");
 }
 
 }  // extern "C"

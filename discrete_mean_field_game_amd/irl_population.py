@@ -9,13 +9,24 @@ all), and trains them in lock-step: after the same train() calls learner k holds
 `train(E, stop_criteria=-1)`.
 
 Scope: one GPU, start states drawn on the device (batch >= 2), Philox sampling, the matrix-core reward-network kernel's
-geometry (d = 15 / 21, n_fc3 <= 16), no early stop.  Training the reward networks stays with AC_IRL.
+geometry (d = 15 / 21, n_fc3 <= 16), no early stop in train().
+
+With per-learner networks and `demonstrations`, the population also runs the reward half of the IRL loop: update_reward,
+reward_iteration and outerloop give learner k exactly what AC_IRL's methods give with learner k's settings, its lr_reward
+and the module `random` stream seeded with host_seeds[k] (each learner draws its batches from its own random.Random; the
+module stream is never touched).  Early stopping in reward_iteration is decided per learner, so the reward-call, reward-train,
+Adam-step and reward-update counters are per-learner arrays; the Philox step and the D_samp trajectory counter stay shared.
+The reward updates of all learners run in the two launches per update of mfg_reward_net_train_steps_pop, each
+reward_iteration check is one population forward (mfg_reward_net_forward_pop) over the demonstrations and one over the
+learners' D_samp, plus one host read.  D_samp is generated as AC_IRL._generate_device does, one draw + one rollout launch per
+learner.  Out of scope: CSV / checkpoint files, a population state_dict, multi-GPU, calc_z and eval-set overrides.
 
 The instance owns one ops.Context; its sticky status word is shared by the K learners (as for ActorCriticPopulation).
 """
 from __future__ import annotations
 
 import copy
+import random
 
 import numpy as np
 import torch
@@ -26,12 +37,51 @@ from .ac_irl import AC_IRL
 from .mfg_ac2 import EPISODE_STEPS, actor_critic
 from .networks import RewardNet
 from .population import _with_ctx, broadcast, resolve_start_table
+from .reward_learning import RewardTrainer, StackedTrajectoryStore, TrajectoryStore
 
 # the tensors of mfg_reward_net_t, in the order of the struct, and the module parameter each one comes from
 NET_TENSORS = (('conv1_w', 'conv1.weight'), ('conv1_b', 'conv1.bias'), ('conv2_w', 'conv2.weight'), ('conv2_b', 'conv2.bias'),
                ('fc3_w', 'fc3.weight'), ('fc3_b', 'fc3.bias'), ('fc4_w', 'fc4.weight'), ('fc4_b', 'fc4.bias'),
                ('out_w', 'out.weight'), ('out_b', 'out.bias'))
 RN_SEED_OFFSET = 0x5EED      # AC_IRL's dropout key: (seed + 0x5EED) ^ (call x 0x9E3779B97F4A7C15), ac_irl.py reward()
+RT_SEED_OFFSET = 0x7EA1      # ... and that of the training batches: (seed + 0x7EA1) ^ (train call x ...), AC_IRL.update_reward
+KEY_MUL, MASK64 = 0x9E3779B97F4A7C15, 0xFFFFFFFFFFFFFFFF
+NUM_DEMO_SAMPLES = NUM_GEN_SAMPLES = 5     # AC_IRL.num_demo_samples / num_gen_samples
+PARAM_ALIGN = 64             # floats: one learner's flat parameter row is padded to this (keeps every fc3_w 8-byte aligned)
+
+
+def batch_fits(n_demo, n_gen, n_fc3, steps=EPISODE_STEPS):
+    """True when an update_reward batch is inside mfg_reward_net_train_step's limits (AC_IRL.update_reward's `fits`)."""
+    n_tr = (n_demo + n_gen) * steps
+    return (n_tr <= 2048 and n_tr * (1 + n_fc3) * 4 <= 60 * 1024 and n_demo <= L.RN_TRAIN_MAX_TRAJ
+            and n_gen <= L.RN_TRAIN_MAX_TRAJ)
+
+
+def check_demonstrations(demonstrations, d):
+    """The demonstrations as float32 arrays (states [n, 15, d], actions [n, 15, d, d]); ValueError when missing or ragged."""
+    if demonstrations is None or len(demonstrations) == 0:
+        raise ValueError('the reward half of the IRL loop needs demonstrations (a list of trajectories of %d (state, action) '
+                         'pairs)' % EPISODE_STEPS)
+    for tr in demonstrations:
+        if len(tr) != EPISODE_STEPS:
+            raise ValueError('ragged demonstrations: every trajectory needs %d (state, action) pairs, got %d'
+                             % (EPISODE_STEPS, len(tr)))
+    s = np.array([[np.asarray(p[0], dtype=np.float32)[:d] for p in tr] for tr in demonstrations], dtype=np.float32)
+    a = np.array([[np.asarray(p[1], dtype=np.float32)[:d, :d] for p in tr] for tr in demonstrations], dtype=np.float32)
+    if s.shape[2] != d or a.shape[2:] != (d, d):
+        raise ValueError('demonstrations: states of %d entries / actions of %d x %d expected' % (d, d, d))
+    return s, a
+
+
+def draw_batches(rng, nd_all, ng_all, n_updates, n_demo=NUM_DEMO_SAMPLES, n_gen=NUM_GEN_SAMPLES):
+    """The logical trajectory indices of `n_updates` update_reward calls drawn from random.Random `rng`: AC_IRL.update_reward's
+    random.sample calls on index ranges (demonstrations, then generated, per update)."""
+    out = []
+    for _ in range(n_updates):
+        di = rng.sample(range(nd_all), n_demo) if nd_all >= n_demo else list(range(nd_all))
+        gi = rng.sample(range(ng_all), n_gen) if ng_all >= n_gen else list(range(ng_all))
+        out.append((di, gi))
+    return out
 
 
 def check_args(K, d, batch, update_every, precision, reward_nets):
@@ -61,10 +111,15 @@ def check_args(K, d, batch, update_every, precision, reward_nets):
 class AC_IRLPopulation:
 
     def __init__(self, thetas, shifts=0.0, alpha_scales=1e4, d=15, *, batch, reward_nets, seeds=None, w0=None, pi0=None,
-                 path_to_dir=None, update_every='step', precision='mixed', device=None, verbose=0):
+                 path_to_dir=None, update_every='step', precision='mixed', device=None, verbose=0, demonstrations=None,
+                 lr_reward=1e-4, num_policies=10, host_seeds=None):
         th = np.asarray(thetas, dtype=np.float64).reshape(-1)
         K = th.shape[0]
         nets = check_args(K, int(d), int(batch), update_every, precision, reward_nets)
+        lr_reward = broadcast('lr_reward', lr_reward, K)
+        if int(num_policies) < 1:
+            raise ValueError('num_policies < 1')
+        demo_np = check_demonstrations(demonstrations, int(d)) if demonstrations is not None else None
         if not torch.cuda.is_available():
             raise L.MfgError('AC_IRLPopulation needs a ROCm GPU: the HIP hot path has no CPU fallback')
         L.lib()
@@ -91,14 +146,34 @@ class AC_IRLPopulation:
         self._rn_seeds_dev = torch.as_tensor((self.seeds + np.uint64(RN_SEED_OFFSET)).view(np.int64), device=dev)
         self._shifts_dev = torch.as_tensor(self.shifts, device=dev)
         self._alphas_dev = torch.as_tensor(self.alpha_scales, device=dev)
-        # the networks: owned copies, one stacked fp32 tensor per parameter ([1, ...] when shared)
+        # the networks: owned copies, one stacked fp32 tensor per parameter ([1, ...] when shared); per-learner networks live
+        # in one flat buffer [K, ld] (the reward trainer's parameter layout, rows padded to PARAM_ALIGN floats) and the
+        # stacked tensors are views into it
         self._templates = [copy.deepcopy(n).to('cpu') for n in nets]
         self.per_learner_net = len(nets) > 1
         self._net_params = {}
+        self._flat = None
+        self._net_stride = 0
+        n0 = nets[0]
+        self._rn_dims = (n0.d, n0.conv1.kernel_size[0], n0.conv2.out_channels, n0.conv2.kernel_size[0], n0.fc3.out_features,
+                         n0.fc4.out_features)
         with torch.no_grad():
-            for field, pname in NET_TENSORS:
-                ts = [n.get_parameter(pname).detach().to(device=dev, dtype=torch.float32) for n in nets]
-                self._net_params[field] = torch.stack(ts).contiguous()
+            if self.per_learner_net:
+                import ctypes as C
+                offs = (C.c_int64 * 11)()
+                L.check(L.lib().mfg_reward_net_param_offsets(*self._rn_dims, offs), 'mfg_reward_net_param_offsets')
+                npar = int(offs[10])
+                self._net_stride = (npar + PARAM_ALIGN - 1) // PARAM_ALIGN * PARAM_ALIGN
+                self._flat = torch.zeros(K, self._net_stride, dtype=torch.float32, device=dev)
+                for i, (field, pname) in enumerate(NET_TENSORS):
+                    shape = tuple(n0.get_parameter(pname).shape)
+                    view = self._flat[:, int(offs[i]):int(offs[i + 1])].view(K, *shape)
+                    view.copy_(torch.stack([n.get_parameter(pname).detach().to(device=dev, dtype=torch.float32) for n in nets]))
+                    self._net_params[field] = view
+            else:
+                for field, pname in NET_TENSORS:
+                    ts = [n.get_parameter(pname).detach().to(device=dev, dtype=torch.float32) for n in nets]
+                    self._net_params[field] = torch.stack(ts).contiguous()
         _, _, _, keep = ops.irl_pop_net_geometry(nets)
         st = L.RewardNetStruct()
         st.k1, st.f2, st.k2 = nets[0].conv1.kernel_size[0], nets[0].conv2.out_channels, nets[0].conv2.kernel_size[0]
@@ -108,10 +183,39 @@ class AC_IRLPopulation:
         st.keep_prob = keep
         self._net_struct = st
         self._rng_step = 0       # Philox step counter, shared by the learners (they advance in lock-step)
-        self._reward_calls = 0   # AC_IRL's reward-call counter (dropout keys), shared likewise
+        # AC_IRL's reward-call counters (dropout keys), one per learner: reward_iteration's checks stop per learner
+        self._calls_k = np.zeros(K, dtype=np.int64)
         self._bufs = None
+        # the reward half of the IRL loop (AC_IRL.update_reward / reward_iteration / outerloop)
+        self.lr_reward = lr_reward
+        self.num_policies = int(num_policies)
+        self.host_seeds = broadcast('host_seeds', self.seeds.astype(np.int64) if host_seeds is None else host_seeds, K, np.int64)
+        self._random = [random.Random(int(h)) for h in self.host_seeds]
+        self.theta_initial = th.copy()
+        self.list_policies = [[float(t)] * self.num_policies for t in th]
+        self.reward_update_count = np.zeros(K, dtype=np.int64)
+        self._reward_train_calls = np.zeros(K, dtype=np.int64)
+        self._adam_step = np.zeros(K, dtype=np.int64)
+        self._gen_traj_counter = 1 << 40                   # AC_IRL._gen_offset's first id, shared
+        self._demo_store = TrajectoryStore(self.d, EPISODE_STEPS, dev)
+        self._demo_np = demo_np
+        if demo_np is not None:
+            self._demo_store.push(torch.from_numpy(demo_np[0]), torch.from_numpy(demo_np[1]))
+        self._gen_store = StackedTrajectoryStore(K, self.d, EPISODE_STEPS, dev)
+        self._adam_m = self._adam_v = None
+        if self.per_learner_net:
+            self._adam_m = torch.zeros_like(self._flat)
+            self._adam_v = torch.zeros_like(self._flat)
+        self._rt_stats = torch.zeros(K, 4, dtype=torch.float32, device=dev)
+        self._rt_ws = self._rt_plan_dev = self._fw_scratch = None
 
     # ------------------------------------------------------------------ state
+    @property
+    def _reward_calls(self):
+        """The learners' reward-call count: an int while they agree (train() alone), else the per-learner array [K]."""
+        c = self._calls_k
+        return int(c[0]) if np.all(c == c[0]) else c.copy()
+
     @property
     def K(self):
         return int(self._theta.shape[0])
@@ -176,19 +280,20 @@ class AC_IRLPopulation:
         lra = torch.as_tensor(broadcast('lr_actor', lr_actor, K), device=self.device)
         acc = torch.zeros(K, num_episodes, dtype=torch.float64, device=self.device)
         b = self._buffers()
-        common = dict(first_step=self._rng_step, reward_acc=acc, precision=self.precision)
+        common = dict(first_step=self._rng_step, reward_acc=acc, precision=self.precision, net_stride=self._net_stride)
+        calls = torch.as_tensor(self._calls_k, device=self.device)      # per-learner reward-call counters
         if self.update_every == 'step':
             ops.train_episodes_irl_pop(self._mat_pi0_dev, b['pi'], T, num_episodes, first_episode + 1, constant, self._theta,
                                        self._shifts_dev, self._alphas_dev, self._w, gamma, lrc, lra, self._seeds_dev,
-                                       self._net_struct, self.per_learner_net, self._rn_seeds_dev, self._reward_calls, b['G'],
+                                       self._net_struct, self.per_learner_net, self._rn_seeds_dev, calls, b['G'],
                                        b['ws'], b['run'], **common)
-            self._reward_calls += num_episodes * T
+            self._calls_k += num_episodes * T
         else:
             ops.train_rollouts_irl_pop(self._mat_pi0_dev, T, num_episodes, first_episode + 1, constant, self._theta,
                                        self._shifts_dev, self._alphas_dev, self._w, gamma, lrc, lra, self._seeds_dev,
-                                       self._net_struct, self.per_learner_net, self._rn_seeds_dev, self._reward_calls, b['G'],
+                                       self._net_struct, self.per_learner_net, self._rn_seeds_dev, calls, b['G'],
                                        b['ws'], b['run'], **common)
-            self._reward_calls += num_episodes
+            self._calls_k += num_episodes
         self._rng_step += num_episodes * T
         out = acc.cpu().numpy()
         if self.update_every == 'rollout':
@@ -196,6 +301,8 @@ class AC_IRLPopulation:
         if self.precision == 'mixed' and self._ctx.status(synchronize=True):
             raise L.MfgError('a mixed-precision sampling launch of this population ran with |theta| (1/2 + |shift|) > 86 '
                              '(or theta not finite): its outputs are NaN; use precision=\'f64\', then clear_status()')
+        for k, t in enumerate(self.thetas):             # AC_IRL.train records the policy (list_policies FIFO)
+            self.list_policies[k] = (self.list_policies[k] + [float(t)])[1:]
         return out
 
     def status(self, synchronize=True) -> int:
@@ -206,8 +313,10 @@ class AC_IRLPopulation:
         self._ctx.clear_status()
 
     def learner(self, k):
-        """An AC_IRL holding learner k's theta, w, reward network, Philox position and reward-call counter.  Its
-        construction leaves the global np.random stream (and torch's CPU generator) as they were."""
+        """An AC_IRL holding learner k's theta, w, reward network, Philox position and reward-call counter and, for the reward
+        half of the loop, the demonstrations, D_samp, the reward trainer's Adam state, lr_reward, the policy FIFO and the
+        reward-update counters.  Its construction leaves the global np.random stream (and torch's CPU generator) as they were;
+        the module `random` stream is set to learner k's (AC_IRL.update_reward draws its batches from it)."""
         if not 0 <= k < self.K:
             raise IndexError('learner %d of %d' % (k, self.K))
         net = self.reward_net(k)
@@ -215,7 +324,7 @@ class AC_IRLPopulation:
         try:
             with torch.random.fork_rng(devices=[]):
                 ac = AC_IRL(float(self.thetas[k]), float(self.shifts[k]), float(self.alpha_scales[k]), self.d,
-                            reg=net.reg, n_fc3=net.fc3.out_features, n_fc4=net.fc4.out_features, pi0=self.mat_pi0,
+                            lr_reward=float(self.lr_reward[k]), num_policies=self.num_policies, reg=net.reg, n_fc3=net.fc3.out_features, n_fc4=net.fc4.out_features, pi0=self.mat_pi0,
                             demonstrations=[], batch=self.batch, seed=int(self.seeds[k]), update_every=self.update_every,
                             precision=self.precision, device=self.device, verbose=self.verbose)
         finally:
@@ -225,5 +334,199 @@ class AC_IRLPopulation:
         ac.w = self.w[k]
         ac.theta = np.array([self.thetas[k]]) if self._rng_step else float(self.thetas[k])
         ac._rng_step = self._rng_step
-        ac._reward_calls = self._reward_calls
+        ac._reward_calls = int(self._calls_k[k])
+        ac.lr_reward = float(self.lr_reward[k])
+        ac.num_policies = self.num_policies
+        ac.theta_initial = float(self.theta_initial[k])
+        ac.list_policies = list(self.list_policies[k])
+        ac.reward_update_count = int(self.reward_update_count[k])
+        ac._reward_train_calls = int(self._reward_train_calls[k])
+        ac._gen_traj_counter = self._gen_traj_counter
+        if self._demo_np is not None:
+            ac.list_demonstrations = [[(s_.astype(np.float64), a_.astype(np.float64)) for s_, a_ in zip(st, at)]
+                                      for st, at in zip(*self._demo_np)]
+        if len(self._gen_store):
+            ac._gen_store.push(*self._gen_store.gather(k=k))
+        if self.per_learner_net and ac._trainer is not None:
+            ac.lr_reward = float(self.lr_reward[k])
+            ac._trainer.lr = float(self.lr_reward[k])
+            npar = ac._trainer.flat.numel()
+            ac._trainer.load_state_dict({'m': self._adam_m[k, :npar], 'v': self._adam_v[k, :npar],
+                                         'step': int(self._adam_step[k]), 'stats': self._rt_stats[k]})
+        ac._stats_host = None
+        # the module `random` stream now continues learner k's (AC_IRL.update_reward draws from it)
+        random.setstate(self._random[k].getstate())
         return ac
+
+    def host_random_state(self, k):
+        """Learner k's random.Random state (the stream its update_reward batches are drawn from)."""
+        return self._random[k].getstate()
+
+    # ------------------------------------------------------------------ reward learning (AC_IRL.update_reward ...)
+    def _check_reward_learning(self):
+        if not self.per_learner_net:
+            raise ValueError('reward learning needs one reward network per learner (a shared network cannot take K updates)')
+        if self._demo_np is None:
+            raise ValueError('reward learning needs demonstrations (constructor argument demonstrations=...)')
+        nd = min(len(self._demo_store), NUM_DEMO_SAMPLES)
+        ng = min(len(self._gen_store), NUM_GEN_SAMPLES)
+        if not batch_fits(nd, ng, self._rn_dims[4]):
+            raise ValueError('update_reward batch of %d + %d trajectories is outside the HIP training step\'s limits' % (nd, ng))
+        return nd, ng
+
+    def _train_rewards(self, active, n_updates):
+        """n_updates update_reward calls of the learners `active` (store sizes fixed): the batches drawn from each learner's
+        random.Random in AC_IRL.update_reward's order, then ONE mfg_reward_net_train_steps_pop call."""
+        nd, ng = self._check_reward_learning()
+        n_active = len(active)
+        if n_updates < 1 or n_active == 0:
+            return
+        plan = ops.rn_train_plan(n_updates * n_active).reshape(n_updates, n_active)     # update-major, as the C call reads it
+        nd_all, ng_all = len(self._demo_store), len(self._gen_store)
+        drow = np.asarray(self._demo_store.rows, dtype=np.int32)
+        grow = np.asarray(self._gen_store.rows, dtype=np.int32)
+        for s_, k in enumerate(active):           # (column-wise: the host side is one random.sample pair per update)
+            batches = draw_batches(self._random[k], nd_all, ng_all, n_updates)
+            seed_k = int(self.seeds[k]) + RT_SEED_OFFSET
+            c0 = int(self._reward_train_calls[k])
+            col = plan[:, s_]
+            col['learner'] = k
+            col['key'] = [(seed_k ^ ((c0 + 1 + u) * KEY_MUL)) & MASK64 for u in range(n_updates)]
+            col['lr'] = float(self.lr_reward[k])
+            col['adam_step'] = int(self._adam_step[k]) + 1 + np.arange(n_updates)
+            col['demo_rows'][:, :nd] = drow[np.array([b[0] for b in batches], dtype=np.int64).reshape(n_updates, nd)]
+            col['gen_rows'][:, :ng] = grow[np.array([b[1] for b in batches], dtype=np.int64).reshape(n_updates, ng)]
+            self._reward_train_calls[k] += n_updates
+            self._adam_step[k] += n_updates
+        plan = plan.reshape(-1)
+        net = self._templates[0]
+        need_ws = (int(L.lib().mfg_reward_net_train_workspace_bytes(*self._rn_dims, (nd + ng) * EPISODE_STEPS)) + 255) // 256 * 256
+        need_ws *= n_active
+        if self._rt_ws is None or self._rt_ws.numel() * 4 < need_ws:
+            self._rt_ws = torch.empty((need_ws + 3) // 4, dtype=torch.float32, device=self.device)
+        if self._rt_plan_dev is None or self._rt_plan_dev.numel() < plan.nbytes:
+            self._rt_plan_dev = torch.empty(plan.nbytes, dtype=torch.uint8, device=self.device)
+        ds, da = self._demo_store.state, self._demo_store.action
+        gs, ga = self._gen_store.state, self._gen_store.action
+        keep = float(net.keep_prob) if net.use_dropout else 1.0
+        ops.reward_net_train_steps_pop(self._flat, self._adam_m, self._adam_v, self._net_stride, self.K, self._rn_dims, (ds, da),
+                                       (gs, ga), plan, n_updates, n_active, nd, ng, EPISODE_STEPS, NUM_DEMO_SAMPLES, keep,
+                                       net.use_l1l2, self._rt_stats, self._rt_ws, self._rt_plan_dev,
+                                       RewardTrainer.BETA1, RewardTrainer.BETA2, RewardTrainer.EPS)
+
+    @_with_ctx
+    def update_reward(self, learners=None):
+        """One AC_IRL.update_reward of every learner (or of the listed ones): two launches for all of them."""
+        active = list(range(self.K)) if learners is None else [int(k) for k in learners]
+        self._train_rewards(active, 1)
+
+    def _reward_averages(self, active):
+        """AC_IRL._eval_reward_averages of the learners `active`: one population forward over the demonstrations, one over
+        the learners' D_samp, ONE host read; sums as there (r.double().sum() on a contiguous row).  [n_active, 2]."""
+        K = self.K
+        ds, da = self._demo_store.gather_flat()
+        gs, ga = self._gen_store.gather_flat()
+        nd, ng = ds.shape[0], gs.shape[1]
+        if self._fw_scratch is None:
+            self._fw_scratch = torch.empty(2 * K, dtype=torch.float64, device=self.device)
+        sums = []
+        outs = []
+        for n, (st, ac) in ((nd, (ds, da)), (ng, (gs, ga))):
+            if n == 0:
+                outs.append(None)
+                continue
+            self._calls_k[active] += 1
+            keys = [((int(self.seeds[k]) + RN_SEED_OFFSET) ^ (int(self._calls_k[k]) * KEY_MUL)) & MASK64 for k in active]
+            outs.append(ops.reward_net_forward_pop(self._net_struct, True, K, st, ac, active, keys, net_stride=self._net_stride,
+                                                   scratch=self._fw_scratch))
+        zero = torch.zeros((), dtype=torch.float64, device=self.device)
+        for r in outs:
+            for k in active:
+                sums.append(r[k].double().sum() if r is not None else zero)
+        host = torch.stack(sums).cpu().numpy().reshape(2, len(active))
+        avg = np.full((len(active), 2), np.nan)
+        if nd:
+            avg[:, 0] = [float(v) / nd for v in host[0]]
+        if ng:
+            avg[:, 1] = [float(v) / ng for v in host[1]]
+        return avg
+
+    @_with_ctx
+    def reward_iteration(self, max_iterations=500, stop_criteria=0.01, iter_check=10):
+        """AC_IRL.reward_iteration for every learner, each stopping on its own.  Between two checks every batch is known in
+        advance (the stores do not change), so one native call runs up to `iter_check` updates of all running learners.
+        Returns (iterations [K] at which each learner left, averages [K, 2] of its last check: demo / generated; NaN where
+        there was none)."""
+        K = self.K
+        self._check_reward_learning()
+        max_iterations, iter_check = int(max_iterations), int(iter_check)
+        if iter_check < 1:
+            raise ValueError('iter_check < 1')
+        prev = np.full(K, -100.0)
+        its = np.zeros(K, dtype=np.int64)
+        last = np.full((K, 2), np.nan)
+        active = list(range(K))
+        it = 0
+        while it < max_iterations and active:
+            u = min(iter_check - it % iter_check, max_iterations - it)
+            self.reward_update_count[active] += u
+            self._train_rewards(active, u)
+            it += u
+            its[active] = it
+            if it % iter_check:
+                continue
+            avg = self._reward_averages(active)
+            still = []
+            for i, k in enumerate(active):
+                demo_avg, gen_avg = avg[i]
+                last[k] = avg[i]
+                if np.isnan(demo_avg) or np.isnan(gen_avg):
+                    continue
+                if stop_criteria != -1 and abs(demo_avg - prev[k]) < stop_criteria:
+                    continue
+                prev[k] = demo_avg
+                still.append(k)
+            active = still
+        return its, last
+
+    def _generate(self, n):
+        """AC_IRL._generate_device(n) of every learner (its seed, theta, shift, alpha_scale; shared Philox step and
+        trajectory ids): K draw + rollout launch pairs.  Returns (pi_traj [K,n,16,d], P [K,n,15,d,d])."""
+        K, T, d = self.K, EPISODE_STEPS, self.d
+        off = self._gen_traj_counter
+        self._gen_traj_counter = off + n
+        states = torch.empty(K, n, T + 1, d, dtype=torch.float32, device=self.device)
+        actions = torch.empty(K, n, T, d, d, dtype=torch.float32, device=self.device)
+        for k in range(K):
+            seed = int(self.seeds[k])
+            _, pi0 = ops.draw_start(self._mat_pi0_dev, n, seed, self._rng_step, off)
+            ops.rollout(pi0, T, self._theta[k:k + 1], float(self.shifts[k]), float(self.alpha_scales[k]), seed=seed,
+                        first_step=self._rng_step, traj_offset=off, td=False, write_P=True, precision=self.precision,
+                        out={'pi_traj': states[k], 'P': actions[k]})
+        self._rng_step += T
+        return states, actions
+
+    @_with_ctx
+    def outerloop(self, num_iterations=20, num_gen_from_policy=5, max_reward_iterations=100, max_forward_episodes=200, gamma=1,
+                  constant=False, lr_critic=0.1, lr_actor=0.001, *, final_training=True):
+        """AC_IRL.outerloop for every learner: alternate reward_iteration (stop criterion 1e-4, a check every 10 updates) and
+        forward solves from theta_initial, D_samp refreshed as a FIFO; closes with a 2000-episode forward solve unless
+        final_training=False.  lr_critic / lr_actor: scalars or [K].  Returns the thetas [K]."""
+        nd = min(len(self._demo_store), NUM_DEMO_SAMPLES)
+        self._check_reward_learning()
+        if not batch_fits(nd, min(int(num_gen_from_policy) * self.num_policies, NUM_GEN_SAMPLES), self._rn_dims[4]):
+            raise ValueError('update_reward batch outside the HIP training step\'s limits')
+        num_gen_from_policy = int(num_gen_from_policy)
+        self._gen_store.clear()
+        self._gen_store.push(*self._generate(num_gen_from_policy * self.num_policies))
+        self.reward_update_count[:] = 0
+        th0 = torch.as_tensor(self.theta_initial, device=self.device)
+        for _ in range(int(num_iterations)):
+            self._gen_store.push(*self._generate(num_gen_from_policy), drop=num_gen_from_policy)
+            self.reward_iteration(max_iterations=max_reward_iterations, stop_criteria=0.0001, iter_check=10)
+            self._theta.copy_(th0)
+            self.train(max_forward_episodes, gamma, constant, lr_critic, lr_actor)
+        if final_training:
+            self._theta.copy_(th0)
+            self.train(2000, gamma, constant, lr_critic, lr_actor)
+        return self.thetas

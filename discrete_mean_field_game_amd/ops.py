@@ -660,12 +660,15 @@ def _chk_irl_pop(K, B, d, T, episodes, theta, w, G, ws, bufs, reward_acc, mat_pi
 
 def train_episodes_irl_pop(mat_pi0, pi, T, episodes, first_episode, constant, theta, shifts, alpha_scales, w, gamma, lr_critic,
                            lr_actor, seeds, net_struct, per_learner_net, rn_seeds, rn_call0, G, ws, bufs, first_step=0,
-                           traj_offset=0, reward_acc=None, precision='mixed'):
+                           traj_offset=0, reward_acc=None, precision='mixed', net_stride=0):
     """AC_IRL.train's step mode for K independent learners (mfg_train_episodes_irl_pop): `pi` [K,Bk,d] (output: the final
     states), theta [K], w [K,F], G [K,F+3], ws [K, slice] fp64; shifts, alpha_scales, lr_critic, lr_actor fp64 and seeds,
     rn_seeds int64 (read as uint64) device arrays [K]; net_struct = reward_net_struct(...) of the shared network or of the
     stacked parameters (per_learner_net); bufs = dict(scratch [K,Bk,d] f32, P [K,Bk,d,d] f32, reward [K,Bk] f32, delta / g
-    [K,Bk] f64); reward_acc [K,episodes] fp64 or None.  The episode numbers of the schedule start at first_episode."""
+    [K,Bk] f64); reward_acc [K,episodes] fp64 or None.  The episode numbers of the schedule start at first_episode.
+    rn_call0: the shared reward-call counter (int), or an int64 device array [K] of per-learner counters
+    (mfg_train_episodes_irl_pop_calls); net_stride: elements between two learners' weights in one flat buffer (0: stacked
+    tensors)."""
     import ctypes as C
     _chk_f32(mat_pi0, 'mat_pi0'); _chk_f32(pi, 'pi'); _chk_f64(theta, 'theta'); _chk_f64(w, 'w'); _chk_f64(G, 'G')
     if pi.dim() != 3:
@@ -676,22 +679,29 @@ def train_episodes_irl_pop(mat_pi0, pi, T, episodes, first_episode, constant, th
                  shifts, alpha_scales, lr_critic, lr_actor, seeds, rn_seeds, net_struct)
     if tuple(P.shape) != (K, B, d, d) or not P.is_contiguous() or not P.is_cuda or P.dtype != torch.float32:
         raise ValueError('P: expected a contiguous f32 device tensor [%d, %d, %d, %d]' % (K, B, d, d))
-    L.check(L.lib().mfg_train_episodes_irl_pop(
-        mat_pi0.data_ptr(), mat_pi0.shape[0], pi.data_ptr(), bufs['scratch'].data_ptr(), B, K, d, int(T), int(episodes),
-        int(first_episode), int(bool(constant)), theta.data_ptr(), shifts.data_ptr(), alpha_scales.data_ptr(), w.data_ptr(),
-        float(gamma), seeds.data_ptr(), int(first_step), int(traj_offset), L.PRECISIONS[precision], lr_critic.data_ptr(),
-        lr_actor.data_ptr(), C.byref(net_struct), int(bool(per_learner_net)), rn_seeds.data_ptr(), int(rn_call0), P.data_ptr(),
-        bufs['reward'].data_ptr(), bufs['delta'].data_ptr(), bufs['g'].data_ptr(), G.data_ptr(), _ptr(reward_acc),
-        ws.data_ptr(), ws.shape[1] * ws.element_size(), _stream()), 'mfg_train_episodes_irl_pop')
+    head = (mat_pi0.data_ptr(), mat_pi0.shape[0], pi.data_ptr(), bufs['scratch'].data_ptr(), B, K, d, int(T), int(episodes),
+            int(first_episode), int(bool(constant)), theta.data_ptr(), shifts.data_ptr(), alpha_scales.data_ptr(), w.data_ptr(),
+            float(gamma), seeds.data_ptr(), int(first_step), int(traj_offset), L.PRECISIONS[precision], lr_critic.data_ptr(),
+            lr_actor.data_ptr(), C.byref(net_struct), int(bool(per_learner_net)))
+    tail = (P.data_ptr(), bufs['reward'].data_ptr(), bufs['delta'].data_ptr(), bufs['g'].data_ptr(), G.data_ptr(),
+            _ptr(reward_acc), ws.data_ptr(), ws.shape[1] * ws.element_size(), _stream())
+    if isinstance(rn_call0, torch.Tensor):
+        _chk_pop(K, 'rn_call0', rn_call0, torch.int64)
+        L.check(L.lib().mfg_train_episodes_irl_pop_calls(*head, int(net_stride), rn_seeds.data_ptr(), rn_call0.data_ptr(), *tail),
+                'mfg_train_episodes_irl_pop_calls')
+    else:
+        if net_stride:
+            raise ValueError('net_stride needs the per-learner counter form (rn_call0 as a device array)')
+        L.check(L.lib().mfg_train_episodes_irl_pop(*head, rn_seeds.data_ptr(), int(rn_call0), *tail), 'mfg_train_episodes_irl_pop')
     return pi
 
 
 def train_rollouts_irl_pop(mat_pi0, T, episodes, first_episode, constant, theta, shifts, alpha_scales, w, gamma, lr_critic,
                            lr_actor, seeds, net_struct, per_learner_net, rn_seeds, rn_call0, G, ws, bufs, first_step=0,
-                           traj_offset=0, discount_pow=True, reward_acc=None, precision='mixed'):
+                           traj_offset=0, discount_pow=True, reward_acc=None, precision='mixed', net_stride=0):
     """AC_IRL.train's rollout mode for K independent learners (mfg_train_rollouts_irl_pop): bufs = dict(pi_traj
     [K,Bk,T+1,d] f32, pi_last [K,Bk,d] f32 (optional), P [K,Bk,T,d,d] f32, reward [K,Bk,T] f32, delta / g [K,Bk,T] f64);
-    the other arrays as for train_episodes_irl_pop."""
+    the other arrays, rn_call0 and net_stride as for train_episodes_irl_pop."""
     import ctypes as C
     _chk_f32(mat_pi0, 'mat_pi0'); _chk_f64(theta, 'theta'); _chk_f64(w, 'w'); _chk_f64(G, 'G')
     if bufs['pi_traj'].dim() != 4:
@@ -705,14 +715,98 @@ def train_rollouts_irl_pop(mat_pi0, T, episodes, first_episode, constant, theta,
     flags = L.ROLLOUT_DISCOUNT_POW if discount_pow else 0
     if L.PRECISIONS[precision] == L.PRECISION_F64:
         flags |= L.ROLLOUT_F64
-    L.check(L.lib().mfg_train_rollouts_irl_pop(
-        mat_pi0.data_ptr(), mat_pi0.shape[0], B, K, d, int(T), int(episodes), int(first_episode), int(bool(constant)),
-        theta.data_ptr(), shifts.data_ptr(), alpha_scales.data_ptr(), w.data_ptr(), float(gamma), seeds.data_ptr(),
-        int(first_step), int(traj_offset), flags, lr_critic.data_ptr(), lr_actor.data_ptr(), C.byref(net_struct),
-        int(bool(per_learner_net)), rn_seeds.data_ptr(), int(rn_call0), bufs['pi_traj'].data_ptr(), _ptr(bufs.get('pi_last')),
-        P.data_ptr(), bufs['reward'].data_ptr(), bufs['delta'].data_ptr(), bufs['g'].data_ptr(), G.data_ptr(),
-        _ptr(reward_acc), ws.data_ptr(), ws.shape[1] * ws.element_size(), _stream()), 'mfg_train_rollouts_irl_pop')
+    head = (mat_pi0.data_ptr(), mat_pi0.shape[0], B, K, d, int(T), int(episodes), int(first_episode), int(bool(constant)),
+            theta.data_ptr(), shifts.data_ptr(), alpha_scales.data_ptr(), w.data_ptr(), float(gamma), seeds.data_ptr(),
+            int(first_step), int(traj_offset), flags, lr_critic.data_ptr(), lr_actor.data_ptr(), C.byref(net_struct),
+            int(bool(per_learner_net)))
+    tail = (bufs['pi_traj'].data_ptr(), _ptr(bufs.get('pi_last')), P.data_ptr(), bufs['reward'].data_ptr(),
+            bufs['delta'].data_ptr(), bufs['g'].data_ptr(), G.data_ptr(), _ptr(reward_acc), ws.data_ptr(),
+            ws.shape[1] * ws.element_size(), _stream())
+    if isinstance(rn_call0, torch.Tensor):
+        _chk_pop(K, 'rn_call0', rn_call0, torch.int64)
+        L.check(L.lib().mfg_train_rollouts_irl_pop_calls(*head, int(net_stride), rn_seeds.data_ptr(), rn_call0.data_ptr(), *tail),
+                'mfg_train_rollouts_irl_pop_calls')
+    else:
+        if net_stride:
+            raise ValueError('net_stride needs the per-learner counter form (rn_call0 as a device array)')
+        L.check(L.lib().mfg_train_rollouts_irl_pop(*head, rn_seeds.data_ptr(), int(rn_call0), *tail), 'mfg_train_rollouts_irl_pop')
     return bufs
+
+
+def reward_net_forward_pop(net_struct, per_learner_net, K, state, action, learners, keys, out=None, net_stride=0, scratch=None):
+    """mfg_reward_net_forward_pop: the reward network of the listed learners (distinct, in [0, K)) in one launch.  state [N,d] /
+    action [N,d,d] (shared by every learner) or [K,N,d] / [K,N,d,d] (learner k reads row k); keys: the Philox keys of the listed
+    learners (Python ints, read as uint64).  Returns out [K,N] f32 (rows of unlisted learners untouched); sample offset 0."""
+    import ctypes as C
+    import numpy as np
+    _chk_f32(state, 'state'); _chk_f32(action, 'action')
+    shared = state.dim() == 2
+    if shared:
+        N, d = state.shape
+        if tuple(action.shape) != (N, d, d):
+            raise ValueError('action: expected [%d, %d, %d]' % (N, d, d))
+    else:
+        if state.dim() != 3 or state.shape[0] != K:
+            raise ValueError('state: expected [N, d] or [%d, N, d]' % K)
+        _, N, d = state.shape
+        if tuple(action.shape) != (K, N, d, d):
+            raise ValueError('action: expected [%d, %d, %d, %d]' % (K, N, d, d))
+    lr = np.ascontiguousarray(learners, dtype=np.int32).reshape(-1)
+    ky = np.array([int(k) & 0xFFFFFFFFFFFFFFFF for k in keys], dtype=np.uint64).reshape(-1)
+    if ky.shape != lr.shape:
+        raise ValueError('one key per listed learner')
+    if out is None:
+        out = torch.empty(K, N, dtype=torch.float32, device=state.device)
+    elif tuple(out.shape) != (K, N):
+        raise ValueError('out: expected [%d, %d]' % (K, N))
+    _chk_f32(out, 'out')
+    if scratch is None:
+        scratch = torch.empty(max(2 * lr.size, 2), dtype=torch.float64, device=state.device)
+    L.check(L.lib().mfg_reward_net_forward_pop(
+        state.data_ptr(), action.data_ptr(), 0 if shared else N * d, 0 if shared else N * d * d, N, d, C.byref(net_struct),
+        int(bool(per_learner_net)), int(net_stride), int(K), lr.ctypes.data, ky.ctypes.data, int(lr.size), 0, out.data_ptr(),
+        scratch.data_ptr(), scratch.numel() * scratch.element_size(), _stream()), 'mfg_reward_net_forward_pop')
+    return out
+
+
+RN_TRAIN_PLAN = None     # numpy dtype of mfg_rn_train_plan_t (L.RnTrainPlan)
+
+
+def rn_train_plan(n):
+    """A zeroed NumPy array of n mfg_rn_train_plan_t entries (fields learner, lr_t, key, lr, adam_step, demo_rows, gen_rows)."""
+    import numpy as np
+    global RN_TRAIN_PLAN
+    if RN_TRAIN_PLAN is None:
+        RN_TRAIN_PLAN = np.dtype(L.RnTrainPlan)
+    return np.zeros(n, dtype=RN_TRAIN_PLAN)
+
+
+def reward_net_train_steps_pop(params, m, v, param_stride, K, dims, demo, gen, plan, n_updates, n_active, n_demo, n_gen, steps,
+                               demo_divisor, keep_prob, l1l2, stats, ws, plan_dev, beta1=0.9, beta2=0.999, eps=1e-8):
+    """mfg_reward_net_train_steps_pop: n_updates update_reward steps of n_active learners.  params / m / v [K, param_stride] f32,
+    dims = (d, k1, f2, k2, n3, n4), demo = (state [rows,T,d], action [rows,T,d,d]) shared, gen = (state [K,cap,T,d], action
+    [K,cap,T,d,d]), plan = rn_train_plan(n_updates * n_active), stats [K,4] f32, ws / plan_dev device byte buffers (uint8)."""
+    for name, t in (('params', params), ('adam_m', m), ('adam_v', v)):
+        _chk_f32(t, name)
+        if tuple(t.shape) != (K, param_stride):
+            raise ValueError('%s: expected [%d, %d]' % (name, K, param_stride))
+    _chk_f32(stats, 'stats')
+    if tuple(stats.shape) != (K, 4):
+        raise ValueError('stats: expected [%d, 4]' % K)
+    ds, da = demo
+    gs, ga = gen
+    for name, t in (('demo state', ds), ('demo action', da), ('gen state', gs), ('gen action', ga)):
+        _chk_f32(t, name)
+    if gs.dim() != 4 or gs.shape[0] != K or ga.shape[:2] != gs.shape[:2]:
+        raise ValueError('generated stores: expected [%d, cap, T, d] / [%d, cap, T, d, d]' % (K, K))
+    if plan.size < n_updates * n_active:
+        raise ValueError('plan: fewer than n_updates * n_active entries')
+    L.check(L.lib().mfg_reward_net_train_steps_pop(
+        params.data_ptr(), m.data_ptr(), v.data_ptr(), int(param_stride), int(K), *[int(x) for x in dims], ds.data_ptr(),
+        da.data_ptr(), ds.shape[0], gs.data_ptr(), ga.data_ptr(), gs.shape[1], plan.ctypes.data, plan_dev.data_ptr(),
+        plan_dev.numel() * plan_dev.element_size(), int(n_updates), int(n_active), int(n_demo), int(n_gen), int(steps),
+        int(demo_divisor), float(keep_prob), int(bool(l1l2)), float(beta1), float(beta2), float(eps), stats.data_ptr(),
+        ws.data_ptr(), ws.numel() * ws.element_size(), _stream()), 'mfg_reward_net_train_steps_pop')
 
 
 def episode_buffers(B, d, device):

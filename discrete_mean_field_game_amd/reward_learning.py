@@ -126,6 +126,89 @@ class TrajectoryStore:
         return self._list
 
 
+class StackedTrajectoryStore(TrajectoryStore):
+    """K learners' trajectory stores under ONE row mapping (AC_IRLPopulation's D_samp): states [K, cap, steps, d], actions
+    [K, cap, steps, d, d].  Every push adds n trajectories to each learner and drops the same `drop` oldest ones, so the rows,
+    the free list and the logical order are those of a single TrajectoryStore given the same pushes."""
+
+    def __init__(self, K, d, steps, device, capacity=0):
+        self.K = int(K)
+        self.d, self.steps, self.device = int(d), int(steps), torch.device(device)
+        self.state = torch.empty(self.K, 0, self.steps, self.d, dtype=torch.float32, device=self.device)
+        self.action = torch.empty(self.K, 0, self.steps, self.d, self.d, dtype=torch.float32, device=self.device)
+        self.rows = []
+        self._free = []
+        self._list = None
+        self.version = 0
+        if capacity:
+            self._grow(capacity)
+
+    @property
+    def capacity(self):
+        return int(self.state.shape[1])
+
+    def _grow(self, need):
+        cap = self.capacity
+        if cap >= need:
+            return
+        new = max(need, 2 * cap, 8)
+        s = torch.empty(self.K, new, self.steps, self.d, dtype=torch.float32, device=self.device)
+        a = torch.empty(self.K, new, self.steps, self.d, self.d, dtype=torch.float32, device=self.device)
+        if cap:
+            s[:, :cap].copy_(self.state)
+            a[:, :cap].copy_(self.action)
+        self.state, self.action = s, a
+        self._free.extend(range(cap, new))
+
+    def clear(self):
+        self._free = list(range(self.capacity))
+        self.rows = []
+        self._changed()
+
+    def push(self, states, actions, drop=0):
+        """Append n trajectories per learner (device tensors [K, n, steps(+1), d], [K, n, steps, d, d]) after dropping the
+        `drop` oldest ones (the FIFO of TrajectoryStore.push)."""
+        n = int(states.shape[1])
+        if (states.dim() != 4 or states.shape[0] != self.K or actions.shape != (self.K, n, self.steps, self.d, self.d)
+                or states.shape[2] < self.steps or states.shape[3] != self.d):
+            raise ValueError('StackedTrajectoryStore.push: bad shapes %s / %s' % (tuple(states.shape), tuple(actions.shape)))
+        total = self.rows + [None] * n
+        dropped, kept = total[:drop], total[drop:]
+        self._free.extend(r for r in dropped if r is not None)
+        n_new = sum(1 for r in kept if r is None)
+        if n_new > len(self._free):
+            self._grow(self.capacity + n_new - len(self._free))
+        first_new = n - n_new
+        new_rows = [self._free.pop(0) for _ in range(n_new)]
+        if n_new:
+            idx = torch.as_tensor(new_rows, dtype=torch.int64, device=self.device)
+            self.state.index_copy_(1, idx, states[:, first_new:, :self.steps].to(self.device, torch.float32))
+            self.action.index_copy_(1, idx, actions[:, first_new:].to(self.device, torch.float32))
+        it = iter(new_rows)
+        self.rows = [r if r is not None else next(it) for r in kept]
+        self._changed()
+
+    def gather(self, logical=None, k=None):
+        """(states [K, n, steps, d], actions [K, n, steps, d, d]) of the given logical trajectories, in order (k: learner k's
+        [n, ...] only)."""
+        rows = self.rows if logical is None else [self.rows[i] for i in logical]
+        idx = torch.as_tensor(rows, dtype=torch.int64, device=self.device)
+        if k is not None:
+            return self.state[k].index_select(0, idx), self.action[k].index_select(0, idx)
+        return self.state.index_select(1, idx), self.action.index_select(1, idx)
+
+    def gather_flat(self):
+        """(states [K, n steps, d], actions [K, n steps, d, d]) of all trajectories in logical order, cached until a change."""
+        if getattr(self, '_flat_version', None) != self.version:
+            st, ac = self.gather()
+            self._flat = (st.reshape(self.K, -1, self.d).contiguous(), ac.reshape(self.K, -1, self.d, self.d).contiguous())
+            self._flat_version = self.version
+        return self._flat
+
+    def to_list(self):
+        raise NotImplementedError('StackedTrajectoryStore: use gather(k=...) for one learner\'s trajectories')
+
+
 class RewardTrainer:
     """Flat fp32 parameter / Adam-moment buffers of a RewardNet and the HIP training step (tf.train.AdamOptimizer
     semantics, ac_irl.py:417: beta1 0.9, beta2 0.999, epsilon 1e-8)."""

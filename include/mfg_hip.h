@@ -532,6 +532,77 @@ int mfg_train_rollouts_irl_pop(const float* mat_pi0, int64_t num_start, int64_t 
                                float* P, float* reward, double* delta, double* g, double* G, double* reward_acc, void* workspace,
                                size_t workspace_bytes, mfg_stream_t stream);
 
+/* The same two flows with a reward-call counter PER LEARNER (AC_IRLPopulation after reward_iteration, where each learner's
+ * early stop has consumed its own number of reward calls): rn_call0 is a device array [K] (uint64) and learner k's keys are
+ * those above with rn_call0[k] in place of the shared counter.  net_stride > 0 (per_learner_net = 1): learner k's tensor t at
+ * base_t + k net_stride (one padded flat parameter row per learner, the layout of mfg_reward_net_train_steps_pop); 0: the
+ * numel_t strides above.  Everything else, checks included, as for the shared-counter entries, which give the same bits when
+ * every rn_call0[k] equals their scalar. */
+int mfg_train_episodes_irl_pop_calls(const float* mat_pi0, int64_t num_start, float* pi_out, float* pi_scratch, int64_t B, int K,
+                                     int d, int T, int64_t episodes, int64_t first_episode, int constant, double* theta,
+                                     const double* shift, const double* alpha_scale, double* w, double gamma, const uint64_t* seed,
+                                     uint32_t first_step, uint64_t traj_offset, int precision, const double* lr_critic,
+                                     const double* lr_actor, const mfg_reward_net_t* net_host, int per_learner_net,
+                                     int64_t net_stride, const uint64_t* rn_seed, const uint64_t* rn_call0, float* P, float* reward,
+                                     double* delta, double* g, double* G, double* reward_acc, void* workspace,
+                                     size_t workspace_bytes, mfg_stream_t stream);
+int mfg_train_rollouts_irl_pop_calls(const float* mat_pi0, int64_t num_start, int64_t B, int K, int d, int T, int64_t episodes,
+                                     int64_t first_episode, int constant, double* theta, const double* shift,
+                                     const double* alpha_scale, double* w, double gamma, const uint64_t* seed, uint32_t first_step,
+                                     uint64_t traj_offset, int flags, const double* lr_critic, const double* lr_actor,
+                                     const mfg_reward_net_t* net_host, int per_learner_net, int64_t net_stride,
+                                     const uint64_t* rn_seed, const uint64_t* rn_call0, float* pi_traj, float* pi_last, float* P,
+                                     float* reward, double* delta, double* g, double* G, double* reward_acc, void* workspace,
+                                     size_t workspace_bytes, mfg_stream_t stream);
+
+/* The reward network of n listed learners of a population in ONE launch of the matrix-core kernel (grid rows = the list):
+ * for slot s, learner k = learners_host[s] (distinct, in [0, K)):
+ *   reward[k N .. k N + N) = mfg_reward_net_forward(state + k s_state, action + k s_action, N, learner k's weights,
+ *                                                   seed = keys_host[s], sample_offset)
+ * bit for bit.  s_state / s_action: elements between two learners' inputs, 0 = one input shared by all (>= N d / N d^2
+ * otherwise).  Weights: as for mfg_train_episodes_irl_pop_calls (per_learner_net, net_stride).  reward [K,N]; rows of learners
+ * not listed are left alone.  The keys and the list are uploaded into `scratch` (device, >= 16 n bytes) and the stream is
+ * drained once before the launch.  MFG_EINVAL: null pointers, counts, a learner out of range or listed twice; MFG_EUNSUPPORTED
+ * outside the matrix-core geometry; MFG_EWORKSPACE: scratch too small -- all before anything is launched. */
+int mfg_reward_net_forward_pop(const float* state, const float* action, int64_t s_state, int64_t s_action, int64_t N, int d,
+                               const mfg_reward_net_t* net_host, int per_learner_net, int64_t net_stride, int K,
+                               const int32_t* learners_host, const uint64_t* keys_host, int n, uint64_t sample_offset,
+                               float* reward, void* scratch, size_t scratch_bytes, mfg_stream_t stream);
+
+/* One entry of the plan of mfg_reward_net_train_steps_pop: one update_reward of one learner. */
+typedef struct mfg_rn_train_plan {
+  int32_t learner;    /* in [0, K), once per update */
+  float lr_t;         /* written by the call: (float)(lr sqrt(1 - beta2^t) / (1 - beta1^t)), t = adam_step, as the single step */
+  uint64_t key;       /* Philox key of the dropout masks, as the seed of mfg_reward_net_train_step */
+  double lr;          /* Adam learning rate */
+  int64_t adam_step;  /* >= 1, the adam_step of mfg_reward_net_train_step */
+  int32_t demo_rows[MFG_RN_TRAIN_MAX_TRAJ];  /* rows of the shared demonstration store (n_demo used) */
+  int32_t gen_rows[MFG_RN_TRAIN_MAX_TRAJ];   /* rows of learner k's generated store (n_gen used) */
+} mfg_rn_train_plan_t;
+
+/* n_updates consecutive update_reward steps of n_active learners of a population: update u, slot s runs, for learner
+ * k = plan[u n_active + s].learner, exactly mfg_reward_net_train_step(params + k param_stride, adam_m + k param_stride,
+ * adam_v + k param_stride, geometry, demo store, the entry's demo_rows, learner k's generated store (gen_state +
+ * k gen_capacity steps d, gen_action + k gen_capacity steps d^2), the entry's gen_rows, steps, demo_divisor, keep_prob, l1l2,
+ * the entry's key, lr and adam_step, flags 0, stats + 4 k) -- the same bits.  Two launches per update: the sample kernel on
+ * grid (N + 1, n_active) and the combine kernel on grid (ceil(NP / 64), n_active), N = (n_demo + n_gen) steps.  Learners
+ * without an entry in an update are not touched (no blocks).
+ * params / adam_m / adam_v [K, param_stride] fp32 (param_stride >= mfg_reward_net_num_params); stats [K, 4] fp32.
+ * plan_host [n_updates n_active] (its lr_t fields written first) is uploaded ONCE into plan_dev (device, >= n_updates n_active
+ * sizeof(mfg_rn_train_plan_t) bytes) and the stream is drained once before the first launch.  workspace: n_active slices, each
+ * mfg_reward_net_train_workspace_bytes(geometry, N) rounded up to 256 bytes.
+ * Checked before anything is launched: MFG_EINVAL for null pointers, bad counts, param_stride < NP, a learner id out of
+ * range or twice in one update, a store row negative or >= its capacity, adam_step < 1; MFG_EUNSUPPORTED outside
+ * d = 15 / 21, k1 = 5, f2 = 2, k2 = 3, n_fc3 <= 16, n_fc4 <= 32, or for a batch beyond the single step's limits (n_demo, n_gen
+ * <= MFG_RN_TRAIN_MAX_TRAJ, N <= 2048, N (1 + n_fc3) 4 B <= 60 KB); MFG_EWORKSPACE for a too small workspace or plan_dev. */
+int mfg_reward_net_train_steps_pop(float* params, float* adam_m, float* adam_v, int64_t param_stride, int K, int d, int k1, int f2,
+                                   int k2, int n3, int n4, const float* demo_state, const float* demo_action, int64_t demo_capacity,
+                                   const float* gen_state, const float* gen_action, int64_t gen_capacity,
+                                   mfg_rn_train_plan_t* plan_host, void* plan_dev, size_t plan_dev_bytes, int n_updates,
+                                   int n_active, int n_demo, int n_gen, int steps, int demo_divisor, float keep_prob, int l1l2,
+                                   double beta1, double beta2, double eps, float* stats, void* workspace, size_t workspace_bytes,
+                                   mfg_stream_t stream);
+
 /* f1 (optional importance weights, ac_irl.py:270-289 calc_pdf_action, :324-379 calc_z): log-density of the
  * product-Dirichlet policy for N (state, action) pairs under K policies theta_k (device array):
  *   out[n*K + k] = sum_i log Dirichlet(P_n[i,:] ; a_i),  a_ij = max(alpha_floor, alpha_scale * softplus(theta_k x_ij)).
