@@ -11,17 +11,22 @@ call of the reference's train() surface (mfg_ac2.py:448) -- over the rank's traj
     action sampling, pi' = P^T pi, reward, value, TD error, score) -> batch gradient sums -> [one RCCL all-reduce
     of the fused gradient buffer when N > 1] -> (theta, w) update on device.
 value = (ranks * B * T * K) / max-over-ranks wall time between barriers.  STRONG scaling by default: the global
-batch (65536, the north-star target point d=21, T=15) is split over the N GPUs; for N > 1 the same line also carries
+batch (65536, the north-star target point d=21, T=15) is split over the N GPUs; with --full, for N > 1 the same line also carries
 the weak-scaling leg (65536 per GPU, `other_scaling`) and BASELINE config 5 (d=256, T=40, 131072 split N ways,
 `c5_strong`); for N == 1 a bounded `configs` array covers C2 / C3 / C4 / the C5 share / the f64 headline.
 
-The same JSON line carries
+A plain run does only what the headline needs: set-up, device heat-up, the W warm-up and K timed steps, --dump-outputs, and
+the JSON line (`roofline`, `fused_kernel` and `cpu_baseline` null).  Everything else this file measures runs only with
+--full, and the same line then also carries
   roofline     : the HBM-bound given-P kernel (transition + reward over materialised actions; the fused
                  rollout never sends P through HBM), timed live with events on the
                  launch stream over B*T transitions (P slab > L3), algorithmic bytes 4(d^2+2d+1)/step;
   fused_kernel : per-launch time of the fused rollout kernel (compute bound: transcendental + RNG);
   cpu_baseline : the NumPy restatement of the reference loop (oracle/, batch 1, 1 thread) timed on
-                 this box's host cores on a bounded sample (rank 0, N == 1 only).
+                 the host cores on a bounded sample (rank 0, N == 1 only);
+  configs      : the other BASELINE.json configurations (N == 1);
+  loops, collective, other_scaling, c5_strong : the N > 1 (or --force-dist) legs described above.
+--no-roofline (which also drops `configs`), --no-configs and --no-cpu-baseline leave single parts out of a --full run.
 """
 import argparse
 import json
@@ -47,10 +52,13 @@ def parse():
     ap.add_argument('--batch', type=int, default=65536,
                     help='GLOBAL batch, split over the GPUs (strong scaling, default); per-GPU batch with --scaling weak')
     ap.add_argument('--scaling', choices=['weak', 'strong'], default='strong')
-    ap.add_argument('--no-configs', action='store_true', help='skip the other BASELINE.json configurations (N == 1)')
-    ap.add_argument('--cpu-seconds', type=float, default=12.0, help='budget of the CPU baseline leg')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-roofline', action='store_true')
+    ap.add_argument('--full', action='store_true',
+                    help='also run every leg besides the headline: roofline / fused-kernel probes, the other BASELINE.json '
+                         'configurations, the CPU baseline, and at N > 1 (or --force-dist) the loop, collective and scaling legs')
+    ap.add_argument('--no-configs', action='store_true', help='with --full: skip the other BASELINE.json configurations (N == 1)')
+    ap.add_argument('--cpu-seconds', type=float, default=12.0, help='budget of the CPU baseline leg (--full)')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip the CPU baseline')
+    ap.add_argument('--no-roofline', action='store_true', help='with --full: skip the roofline, fused-kernel and configs legs')
     ap.add_argument('--backend', choices=['nccl', 'gloo'], default='nccl',
                     help="collective backend; 'gloo' (+ --share-gpu) only exists to smoke-test the N>1 path on a 1-GPU box")
     ap.add_argument('--share-gpu', action='store_true', help='debug: all ranks use GPU 0')
@@ -345,7 +353,7 @@ def main():
     other = None
     c5 = None
     loops = None
-    if multi:
+    if multi and args.full:
         # both episode loops of the multi-GPU path in the same run: the headline above took the library's own RCCL loop
         # (mfg_train_rollouts_dist: all episodes of the call issued natively, ncclAllReduce on the launch stream) if its canary
         # passed on every rank, else the class's per-episode loop over torch.distributed; the other one is timed here
@@ -358,7 +366,7 @@ def main():
                  'torch_dist_ms_per_update': et / args.steps * 1e3,
                  'torch_dist_value': world * B * T * args.steps / et,
                  'canary': (dict(parallel.CANARY_LOG[-1]) if parallel.CANARY_LOG else None)}
-    if world > 1:
+    if world > 1 and args.full:
         # the other scaling mode, same run (not the headline value)
         Bo = args.batch if args.scaling == 'strong' else args.batch // world
         eo, _, ac = training_leg(d, T, Bo, args.steps, args.warmup)
@@ -373,7 +381,7 @@ def main():
         del ac
 
     collective = None
-    if multi:
+    if multi and args.full:
         # latency of the ONE exchange step of an update: all-reduce of the fused gradient buffer
         # [G_w | G_theta | sum r | count] (fp64, F+3 entries) and the replicated parameter update that follows it, timed
         # with events on the launch stream, every rank in lock-step
@@ -421,7 +429,7 @@ def main():
         roofline = None
         fused = None
         configs = None
-        if not args.no_roofline:
+        if args.full and not args.no_roofline:
             # the HBM-bound kernel of the path on THIS GPU: materialised actions of one rollout of the global batch
             # (B*T transitions, a 1.7 GB slab > L3 at the default size), the same leg at every N
             Br = args.batch if args.scaling == 'strong' else B
@@ -477,7 +485,7 @@ def main():
             if world == 1 and not args.no_configs:
                 configs = other_configs(training_leg, native_leg, given_p_leg, d, T, B, args)
         cpu = None
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             cpu = cpu_baseline(d, args.cpu_seconds)
         out = {
             'metric': 'env-steps/sec for batched d-bin population rollouts', 'value': value, 'unit': 'env-steps/s',

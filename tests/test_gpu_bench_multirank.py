@@ -1,4 +1,4 @@
-"""-m gpu: the N > 1 legs of bench.py (`other_scaling`, `c5_strong`, `collective`) executed for real in fresh child processes:
+"""-m gpu: the N > 1 legs of bench.py --full (`other_scaling`, `c5_strong`, `collective`) executed for real in fresh child processes:
 two ranks share GPU 0 and talk over gloo (`--share-gpu --backend gloo`: the debug switches bench.py has for exactly this; RCCL
 refuses two ranks on one GPU), launched like the driver launches the scaling bench (`python -m torch.distributed.run
 --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 ...`).  What is validated is the code path and the JSON contract of the
@@ -30,7 +30,7 @@ def test_bench_two_ranks_prints_one_valid_line():
         pytest.skip('needs a GPU')
     cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '2', '--master-addr', '127.0.0.1',
            '--master-port', str(_free_port()), os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '2', '--warmup', '1',
-           '--share-gpu', '--backend', 'gloo', '--no-cpu-baseline', '--batch', '8192', '--c5-batch', '64']
+           '--share-gpu', '--backend', 'gloo', '--full', '--no-cpu-baseline', '--batch', '8192', '--c5-batch', '64']
     env = dict(os.environ, MFG_BENCH_HEAT='5', HSA_ENABLE_IPC_MODE_LEGACY='0')
     p = subprocess.run(cmd, cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
     assert p.returncode == 0, p.stderr.decode()[-3000:]

@@ -6,7 +6,7 @@ two ranks cannot share one device under RCCL.  What they leave unexecuted is the
 `init_process_group('nccl', device_id=...)`, a device-tensor `all_reduce` of G, `mfg_apply_update` after it, the barrier +
 max-over-ranks timing of bench.py.  Here a FRESH child process (started before it touches the GPU) runs
 
-    bench.py --gpus 1 --force-dist ...     -> the N > 1 code path of bench.py with a 1-rank RCCL communicator
+    bench.py --gpus 1 --force-dist --full ...     -> the N > 1 code path of bench.py with a 1-rank RCCL communicator
     actor_critic / AC_IRL .train(group=WORLD) with backend nccl
 
 and the parent checks the exit code, the JSON line and the trained parameters against the single-process run.
@@ -44,7 +44,7 @@ def _env():
 def test_bench_force_dist_runs_the_rccl_all_reduce():
     if not torch.cuda.is_available():
         pytest.fail('-m gpu tests need a GPU')
-    cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--force-dist', '--steps', '2', '--warmup', '1',
+    cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--force-dist', '--full', '--steps', '2', '--warmup', '1',
            '--no-configs', '--no-cpu-baseline', '--no-roofline', '--batch', '8192']
     p = subprocess.run(cmd, cwd=ROOT, env=_env(), stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
     assert p.returncode == 0, p.stderr.decode()[-2000:]

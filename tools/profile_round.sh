@@ -5,9 +5,9 @@
 # usage: bash tools/profile_round.sh <tag>     (outputs under gpurun_out/<tag>/; copy the summaries into profiles/)
 R=$GRAFT_REPO_ROOT; TAG=${1:-r06}; O=$R/gpurun_out/$TAG; mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-python3 $R/bench.py > $O/bench.json 2> $O/bench.err
+python3 $R/bench.py --full > $O/bench.json 2> $O/bench.err
 # (the CPU-baseline leg forks one process per host core; it is left out of the traced run -- the kernels are the same)
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -o bench -- python3 $R/bench.py --no-cpu-baseline > $O/bench_under_rocprof.json 2> $O/prof.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -o bench -- python3 $R/bench.py --full --no-cpu-baseline > $O/bench_under_rocprof.json 2> $O/prof.err
 cp $(find $O/prof -name "*kernel_stats.csv" | head -1) $O/bench_kernel_stats.csv
 # round 6: the same at EXACTLY the arguments the driver runs at round end (--steps 20 --warmup 5): the line, and the
 # rocprofv3 per-kernel table of that command
@@ -63,7 +63,7 @@ cd /tmp
 # ONE all-reduce per update) at the 8-GPU shard and the full batch, with the measured latency of the exchange step
 for BB in 8192 65536; do
   MASTER_ADDR=127.0.0.1 MASTER_PORT=29541 RANK=0 LOCAL_RANK=0 WORLD_SIZE=1 python3 $R/bench.py --gpus 1 --force-dist --steps 50 --warmup 10 \
-    --no-configs --no-cpu-baseline --no-roofline --batch $BB > $O/collective_1rank_$BB.json 2> $O/collective_1rank_$BB.err
+    --full --no-configs --no-cpu-baseline --no-roofline --batch $BB > $O/collective_1rank_$BB.json 2> $O/collective_1rank_$BB.err
 done
 # round 6: the two lane mappings of the d = 21 sampling launches side by side (mfg_set_core_mapping: 1 packed, 2 one trajectory
 # per wave): update times at the under-filled batch sizes, SQ counters of both kernels at 4 096 and 1 024 trajectories
