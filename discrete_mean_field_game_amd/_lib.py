@@ -160,6 +160,9 @@ SIGNATURES['mfg_reward_net_train_steps_pop'] = (_i32, [_p, _p, _p, _i64, _i32, _
                                                        _p, _i64, _p, _p, _sz, _i32, _i32, _i32, _i32, _i32, _i32, C.c_float,
                                                        _i32, _f64, _f64, _f64, _p, _p, _sz, _p])
 
+SIGNATURES['mfg_evaluate_pop_workspace_bytes'] = (_sz, [_i64, _i32, _i32, _i32, _i32, _i32])
+SIGNATURES['mfg_evaluate_pop'] = (_i32, [_p, _p, _i64, _i32, _i32, _i32, _p, _p, _p, _p, _u32, _i32, _i32, _p, _p, _p, _sz, _p])
+
 _lib = None
 
 

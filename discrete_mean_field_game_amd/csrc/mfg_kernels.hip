@@ -23,6 +23,7 @@
 
 #include "../../include/mfg_hip.h"
 #include "mfg_core.h"
+#include "mfg_evaluate_pop.h"
 #include "mfg_irl_population.h"
 #include "mfg_population.h"
 
@@ -1897,7 +1898,7 @@ static bool traj_ids_ok(uint64_t traj_offset, int64_t B) {
 // pop != NULL: the population form (mfg_population.h; training launches at d <= 64, packed lane mapping); ipop != NULL: the IRL
 // population form (mfg_irl_population.h; d = 21 / 15)
 static int launch_core(const CoreArgs& a_in, bool sample, bool td, int precision, hipStream_t st, const PopArgs* pop = nullptr,
-                       const IrlCorePop* ipop = nullptr) {
+                       const IrlCorePop* ipop = nullptr, const EvalPop* epop = nullptr) {
   CoreArgs a = a_in;
   if (!traj_ids_ok(a.traj_offset, a.B))
     return fail(MFG_EINVAL, "trajectory ids traj_offset + B = %llu + %lld exceed 2^48 (MFG_TRAJ_ID_LIMIT)",
@@ -1924,7 +1925,8 @@ static int launch_core(const CoreArgs& a_in, bool sample, bool td, int precision
     if (!a.htab) return fail(MFG_ELAUNCH, "%s", "h(z) table initialisation failed");
   }
   int rc;
-  if (ipop) rc = (sample && td) ? launch_core_irl_pop(a, *ipop, precision == MFG_PRECISION_MIXED, num_cus(), st) : MFG_EUNSUPPORTED;
+  if (epop) rc = (sample && !td) ? launch_eval_rollout_pop(a, *epop, precision == MFG_PRECISION_MIXED, num_cus(), st) : MFG_EUNSUPPORTED;
+  else if (ipop) rc = (sample && td) ? launch_core_irl_pop(a, *ipop, precision == MFG_PRECISION_MIXED, num_cus(), st) : MFG_EUNSUPPORTED;
   else if (pop) rc = (sample && td) ? launch_core_small_pop(a, *pop, precision == MFG_PRECISION_MIXED, num_cus(), st) : MFG_EUNSUPPORTED;
   else if (a.d <= WAVE) rc = launch_core_small(a, sample, td, precision == MFG_PRECISION_MIXED, num_cus(), st);
   else if (precision == MFG_PRECISION_MIXED) rc = launch_core_large_mixed(a, sample, td, num_cus(), st);
@@ -3124,6 +3126,60 @@ int mfg_train_rollouts_pop(const float* mat_pi0, int64_t num_start, int64_t B, i
     if (rc != MFG_OK) return rc;
   }
   return MFG_OK;
+}
+
+// ---- population evaluation (mfg_evaluate_pop.h): the test rollouts and metrics of K policies in two launches -----------------
+size_t mfg_evaluate_pop_workspace_bytes(int64_t N, int L, int d, int K, int repeats, int traj_given) {
+  if (N < 1 || L < 1 || d < 1 || K < 1 || repeats < 1) return 0;
+  return eval_pop_workspace_bytes(N, L, d, K, repeats, traj_given != 0);
+}
+
+int mfg_evaluate_pop(const float* emp32, const double* emp64, int64_t N, int L, int d, int K, const double* theta,
+                     const double* shift, const double* alpha_scale, const uint64_t* seed, uint32_t first_step, int repeats,
+                     int precision, double* metrics, float* pi_traj, void* workspace, size_t workspace_bytes,
+                     mfg_stream_t stream) {
+  REQUIRE(K >= 1 && K <= MFG_POP_MAX_K, "population size K outside [1, MFG_POP_MAX_K]");
+  REQUIRE(d >= 1, "d < 1");
+  if (d > WAVE) return fail(MFG_EUNSUPPORTED, "population evaluation: d=%d > 64 (as for the populations)", d);
+  REQUIRE(L >= 2, "episode_length L < 2");
+  REQUIRE(N >= 1, "no test trajectories (N < 1)");
+  REQUIRE(repeats >= 1, "repeats < 1");
+  REQUIRE(N * (int64_t)L <= 0x7FFFFFFF && N * (int64_t)repeats <= 0x7FFFFFFF, "N L or N repeats too large");
+  REQUIRE(emp32 && emp64 && theta && shift && alpha_scale && seed && metrics && workspace, "null pointer");
+  CHECK_PRECISION();
+  REQUIRE((uint64_t)first_step + (uint64_t)(L - 1) <= 0xFFFFFFFFull, "Philox step counter would wrap");
+  const size_t need = eval_pop_workspace_bytes(N, L, d, K, repeats, pi_traj != nullptr);
+  if (workspace_bytes < need)
+    return fail(MFG_EWORKSPACE, "population evaluation workspace: need %lld bytes, have %lld", (long long)need,
+                (long long)workspace_bytes);
+  const int64_t NR = N * repeats;
+  EvalPop p{};
+  p.K = K;
+  p.N = N;
+  p.L = L;
+  p.s_traj = NR * L * d;
+  p.s_idx = eval_pop_idx_stride(NR);
+  p.idx = reinterpret_cast<int32_t*>(workspace);
+  p.seed = seed;
+  p.shift = shift;
+  p.alpha_scale = alpha_scale;
+  double* per_traj = reinterpret_cast<double*>(reinterpret_cast<char*>(workspace) + (size_t)K * p.s_idx * 4);
+  float* traj = pi_traj ? pi_traj : reinterpret_cast<float*>(per_traj + (size_t)K * NR * 4);
+  CoreArgs a{};
+  a.pi0 = emp32;  // viewed as [N L, d]; row (j mod N) L is the start state of trajectory j
+  a.num_start = N * L;
+  a.theta = theta;
+  a.gamma = 1.0;
+  a.B = NR;
+  a.d = d;
+  a.T = L - 1;
+  a.reward_kind = MFG_REWARD_EXTERNAL;  // (states only: no reward is formed)
+  a.first_step = first_step;
+  a.pi_traj = traj;
+  const int rc = launch_core(a, true, false, precision, S(stream), nullptr, nullptr, &p);
+  if (rc != MFG_OK) return rc;
+  launch_eval_metrics_pop(traj, emp32, emp64, N, L, d, NR, K, per_traj, metrics, S(stream));
+  return check_launch("evaluate_pop metrics");
 }
 
 // ---- IRL populations (mfg_irl_population.h): K forward learners of AC_IRL.train in the launches of one ----------------------

@@ -36,7 +36,7 @@ from . import ops
 from .ac_irl import AC_IRL
 from .mfg_ac2 import EPISODE_STEPS, actor_critic
 from .networks import RewardNet
-from .population import _with_ctx, broadcast, resolve_start_table
+from .population import _with_ctx, broadcast, evaluate_population, resolve_start_table
 from .reward_learning import RewardTrainer, StackedTrajectoryStore, TrajectoryStore
 
 # the tensors of mfg_reward_net_t, in the order of the struct, and the module parameter each one comes from
@@ -311,6 +311,13 @@ class AC_IRLPopulation:
 
     def clear_status(self):
         self._ctx.clear_status()
+
+    @_with_ctx
+    def evaluate(self, episode_length=16, indir='test_normalized_round2', outfile='eval_mfg_round2/validation.csv', write_header=0,
+                 *, repeats=1):
+        """ActorCriticPopulation.evaluate with the defaults of AC_IRL.evaluate (ac_irl.py:1495-1571: the population's d,
+        validation.csv): learner k gets what learner(k).evaluate(thetas[k], shifts[k], alpha_scales[k], d, ...) gives."""
+        return evaluate_population(self, episode_length, indir, outfile, write_header, repeats)
 
     def learner(self, k):
         """An AC_IRL holding learner k's theta, w, reward network, Philox position and reward-call counter and, for the reward

@@ -794,6 +794,7 @@ class actor_critic:
 
     _EVAL_HEADER = ('theta,shift,alpha_scale,mean_l1_final,std_l1_final,mean_l1_mean,std_l1_mean,'
                     'mean_JSD_final,std_JSD_final,mean_JSD_mean,std_JSD_mean\n')
+    _EVAL_FMT = '%f,%f,%f,%.3e,%.3e,%.3e,%.3e,%.3e,%.3e,%.3e,%.3e\n'    # one CSV line: theta, shift, alpha_scale, the 8 metrics
 
     def _load_empirical(self, indir, d, episode_length):
         """Every file of cwd/indir as [N, L, d] (mfg_ac2.py:612-626): fp64 for the L1 metric, fp32 for the kernels."""
@@ -832,7 +833,7 @@ class actor_critic:
         with open(outfile, 'a') as f:
             if write_header:
                 f.write(self._EVAL_HEADER)
-            f.write('%f,%f,%f,%.3e,%.3e,%.3e,%.3e,%.3e,%.3e,%.3e,%.3e\n' % ((theta, shift, alpha_scale) + tuple(res)))
+            f.write(self._EVAL_FMT % ((theta, shift, alpha_scale) + tuple(res)))
         return res[0], res[2], res[4], res[6]
 
     @_with_ctx
@@ -859,7 +860,7 @@ class actor_critic:
         table = torch.stack(rows).cpu().numpy()                                # the only synchronisation of the sweep
         with open(outfile, 'a') as f:
             for (theta, shift, alpha_scale), res in zip(points, table):
-                f.write('%f,%f,%f,%.3e,%.3e,%.3e,%.3e,%.3e,%.3e,%.3e,%.3e\n' % ((theta, shift, alpha_scale) + tuple(res)))
+                f.write(self._EVAL_FMT % ((theta, shift, alpha_scale) + tuple(res)))
                 result = (res[0], res[2], res[4], res[6])
                 for idx in range(4):
                     if result[idx] <= list_tuples[idx][0]:

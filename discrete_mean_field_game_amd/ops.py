@@ -824,6 +824,44 @@ def jsd(p, q):
     return out
 
 
+def evaluate_pop_workspace(N, L_rows, d, K, repeats, traj_given, device):
+    """The scratch buffer of one evaluate_pop call (mfg_evaluate_pop_workspace_bytes, rounded up to whole doubles)."""
+    nbytes = int(L.lib().mfg_evaluate_pop_workspace_bytes(int(N), int(L_rows), int(d), int(K), int(repeats), int(bool(traj_given))))
+    return torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=device)
+
+
+def evaluate_pop(emp32, emp64, thetas, shifts, alpha_scales, seeds, first_step=0, repeats=1, precision='mixed', want_traj=False,
+                 ws=None):
+    """The eight evaluate() metrics of K policies in two launches (mfg_evaluate_pop, mfg_ac2.py:595-689): emp32 / emp64
+    [N,L,d] the test files' rows; thetas, shifts, alpha_scales fp64 and seeds int64 (read as uint64) device arrays [K].
+    Learner k's trajectory j (0 <= j < N repeats) starts at emp32[j mod N, 0] under Philox (seeds[k], first_step + t, j).
+    Returns the device fp64 tensor [K, 8] (mean / std of l1_final, l1_mean, JSD_final, JSD_mean), and with want_traj also
+    the trajectories [K, N repeats, L, d] fp32."""
+    _chk_f32(emp32, 'emp32'); _chk_f64(emp64, 'emp64')
+    if emp32.dim() != 3 or tuple(emp64.shape) != tuple(emp32.shape):
+        raise ValueError('emp32 / emp64: expected two [N, L, d] tensors of the same shape, got %s and %s'
+                         % (tuple(emp32.shape), tuple(emp64.shape)))
+    N, Lr, d = emp32.shape
+    K = thetas.numel()
+    _chk_pop(K, 'thetas', thetas, torch.float64)
+    for name, t in (('shifts', shifts), ('alpha_scales', alpha_scales)):
+        _chk_pop(K, name, t, torch.float64)
+    _chk_pop(K, 'seeds', seeds, torch.int64)
+    repeats = int(repeats)
+    if repeats < 1:
+        raise ValueError('repeats=%d: at least one rollout per test file' % repeats)
+    dev = emp32.device
+    metrics = torch.empty(K, 8, dtype=torch.float64, device=dev)
+    traj = torch.empty(K, N * repeats, Lr, d, dtype=torch.float32, device=dev) if want_traj else None
+    if ws is None:
+        ws = evaluate_pop_workspace(N, Lr, d, K, repeats, want_traj, dev)
+    L.check(L.lib().mfg_evaluate_pop(emp32.data_ptr(), emp64.data_ptr(), N, Lr, d, K, thetas.data_ptr(), shifts.data_ptr(),
+                                     alpha_scales.data_ptr(), seeds.data_ptr(), int(first_step), repeats, L.PRECISIONS[precision],
+                                     metrics.data_ptr(), _ptr(traj), ws.data_ptr(), ws.numel() * ws.element_size(), _stream()),
+            'mfg_evaluate_pop')
+    return (metrics, traj) if want_traj else metrics
+
+
 def policy_logpdf(pi, P, thetas, shift, alpha_scale=1.0, alpha_floor=0.0, p_floor=0.0):
     """log q_k(P_n | pi_n) [N,K] of the product-Dirichlet policy under K thetas (ac_irl.py:270-289, :324-379)."""
     _chk_f32(pi, 'pi'); _chk_f32(P, 'P'); _chk_f64(thetas, 'thetas')

@@ -76,6 +76,122 @@ def resolve_start_table(d, pi0=None, path_to_dir=None):
     return np.array([[float('%.3e' % v) for v in row] for row in m])
 
 
+# ---------------------------------------------------------------------------------------------------------- evaluation
+# The selection step (evaluate / gridsearch, mfg_ac2.py:595-689, ac_irl.py:1495-1590) for K policies at once: one
+# mfg_evaluate_pop call rolls every policy over every test file and reduces the eight metrics on the device.
+GRID_CHUNK = L.POP_MAX_K    # grid points per evaluate_pop call of gridsearch (a grid beyond goes in chunks)
+
+
+def load_empirical(indir, d, episode_length):
+    """Every file of cwd/indir, in listdir order, as actor_critic._load_empirical reads them: a NumPy [N, L, d] fp64 array of
+    each file's first `episode_length` rows and `d` columns.  ValueError for an unusable argument or directory."""
+    if not 1 <= int(d) <= 64:
+        raise ValueError('d=%d: population evaluation covers d <= 64 (as the populations do)' % d)
+    if int(episode_length) < 2:
+        raise ValueError('episode_length=%d: an evaluation rolls at least one step (episode_length >= 2)' % episode_length)
+    path_to_dir = os.getcwd() + '/' + indir
+    names = os.listdir(path_to_dir)
+    if not names:
+        raise ValueError('%s: no test files' % path_to_dir)
+    emp = []
+    for filename in names:
+        with open(path_to_dir + '/' + filename, 'r') as f:
+            m = np.loadtxt(f, delimiter=' ', ndmin=2)[:, 0:d]
+        if m.shape[0] < episode_length or m.shape[1] < d:
+            raise ValueError('%s: %d rows of %d entries, the evaluation needs %d rows of %d'
+                             % (filename, m.shape[0], m.shape[1], episode_length, d))
+        emp.append(m[:episode_length])
+    return np.array(emp)
+
+
+def evaluate_policies(emp, thetas, shifts, alpha_scales, seeds, first_step, repeats, precision, device, ctx):
+    """The eight metrics [K, 8] (NumPy) of K policies on the test rows `emp` [N, L, d]: one ops.evaluate_pop call.  `thetas`,
+    `shifts`, `alpha_scales` fp64 and `seeds` int64 device tensors [K].  MfgError when a mixed-precision policy left the
+    fp32 range (ctx: the bound context whose status word the launch reports into)."""
+    emp64 = torch.as_tensor(emp, dtype=torch.float64, device=device)
+    emp32 = torch.as_tensor(emp.astype(np.float32), device=device)
+    metrics = ops.evaluate_pop(emp32, emp64, thetas, shifts, alpha_scales, seeds, first_step=first_step, repeats=repeats,
+                               precision=precision).cpu().numpy()
+    if precision == 'mixed' and ctx.status(synchronize=True):
+        raise L.MfgError('a mixed-precision evaluation ran a policy with |theta| (1/2 + |shift|) > 86 (or theta not finite): '
+                         'its metrics are NaN; use precision=\'f64\'')
+    return metrics
+
+
+def write_eval_rows(outfile, write_header, points, table):
+    """Append one CSV line per (theta, shift, alpha_scale) point, in the format of actor_critic.evaluate."""
+    with open(outfile, 'a') as f:
+        if write_header:
+            f.write(actor_critic._EVAL_HEADER)
+        for (theta, shift, alpha_scale), res in zip(points, table):
+            f.write(actor_critic._EVAL_FMT % ((theta, shift, alpha_scale) + tuple(res)))
+
+
+def grid_points(theta_range, shift_range, alpha_range):
+    """The grid in the reference's loop order (theta outermost, alpha innermost, mfg_ac2.py:680-683)."""
+    return [(theta, shift, alpha_scale) for theta in theta_range for shift in shift_range for alpha_scale in alpha_range]
+
+
+def best_points(points, table):
+    """The reference's list_tuples (mfg_ac2.py:684-688): per metric (mean l1_final, l1_mean, JSD_final, JSD_mean) the
+    value and the point of the LAST minimum in grid order (its `<=`), starting from [100, 0, 0, 0]."""
+    list_tuples = [[100, 0, 0, 0], [100, 0, 0, 0], [100, 0, 0, 0], [100, 0, 0, 0]]
+    for (theta, shift, alpha_scale), res in zip(points, table):
+        result = (res[0], res[2], res[4], res[6])
+        for idx in range(4):
+            if result[idx] <= list_tuples[idx][0]:
+                list_tuples[idx] = [float(result[idx]), theta, shift, alpha_scale]
+    return list_tuples
+
+
+def gridsearch(theta_range, shift_range, alpha_range, indir, outfile, *, d=21, seed=0, episode_length=16, repeats=1,
+               precision='mixed', device=None, verbose=0):
+    """mfg_ac2.gridsearch (mfg_ac2.py:673-689) with every grid point a policy of one evaluate_pop call (GRID_CHUNK points per
+    call).  Appends one CSV line per point in the reference's theta-major order and returns its list_tuples.
+    Unlike actor_critic.gridsearch, every point uses the same seed and the same Philox step (0): common random numbers, so
+    the points are compared on the same noise, and point p equals a fresh actor_critic(theta, shift, alpha_scale, d,
+    seed=seed).evaluate(theta, shift, alpha_scale, d, episode_length, indir, ...).  repeats = R rolls R trajectories per test
+    file.  Runs on a context of its own: a diverged mixed-precision point raises MfgError, writes no line and leaves the
+    caller's status word alone."""
+    if precision not in ('mixed', 'f64'):
+        raise ValueError("precision must be 'mixed' or 'f64'")
+    if int(repeats) < 1:
+        raise ValueError('repeats=%d: at least one rollout per test file' % repeats)
+    emp = load_empirical(indir, int(d), int(episode_length))
+    points = grid_points(theta_range, shift_range, alpha_range)
+    if verbose:
+        for theta, shift, alpha_scale in points:
+            print('Theta %f, shift %f, alpha %d' % (theta, shift, alpha_scale))
+    if not points:
+        return best_points(points, [])
+    if not torch.cuda.is_available():
+        raise L.MfgError('gridsearch needs a ROCm GPU: the HIP hot path has no CPU fallback')
+    L.lib()
+    ops.init()
+    dev = torch.device(device) if device is not None else torch.device('cuda', torch.cuda.current_device())
+    ctx = ops.Context(dev)
+    prev = ctx.bind_scoped()
+    try:
+        par = np.array(points, dtype=np.float64).reshape(-1, 3)
+        tables = []
+        for c0 in range(0, len(points), GRID_CHUNK):
+            p = par[c0:c0 + GRID_CHUNK]
+            n = p.shape[0]
+            seeds = torch.full((n,), int(np.array(seed, dtype=np.uint64).view(np.int64)), dtype=torch.int64, device=dev)
+            tables.append(evaluate_policies(emp, torch.as_tensor(p[:, 0].copy(), device=dev),
+                                            torch.as_tensor(p[:, 1].copy(), device=dev), torch.as_tensor(p[:, 2].copy(), device=dev),
+                                            seeds, 0, int(repeats), precision, dev, ctx))
+        table = np.concatenate(tables)
+    finally:
+        ctx.restore(prev)
+        ctx.close()
+    write_eval_rows(outfile, 0, points, table)
+    list_tuples = best_points(points, table)
+    if verbose:
+        print(list_tuples)
+    return list_tuples
+
+
 def _with_ctx(method):
     """Run a method with the instance's own context bound (as actor_critic's public methods do)."""
     @functools.wraps(method)
@@ -205,6 +321,17 @@ class ActorCriticPopulation:
     def clear_status(self):
         self._ctx.clear_status()
 
+    @_with_ctx
+    def evaluate(self, episode_length=16, indir='test_normalized_round2', outfile='eval_mfg_round2/test_eval_fixed_reward.csv',
+                 write_header=0, *, repeats=1):
+        """actor_critic.evaluate (mfg_ac2.py:595-670) for every learner's current policy in one evaluate_pop call: the test files
+        are read once, learner k rolls with its own seed from the population's Philox step, and K CSV lines are appended in
+        learner order.  Returns a NumPy [K, 4] array (mean l1_final, l1_mean, JSD_final, JSD_mean per learner) and advances the
+        Philox step by episode_length - 1, as each learner's own evaluate() would.  With repeats=1 learner k gets what
+        learner(k).evaluate(thetas[k], shifts[k], alpha_scales[k], d, episode_length, ...) gives; repeats = R rolls R
+        trajectories per test file.  MfgError (and no CSV line) when a mixed-precision policy left the fp32 range."""
+        return evaluate_population(self, episode_length, indir, outfile, write_header, repeats)
+
     def learner(self, k):
         """An actor_critic holding learner k's parameters, table and Philox position (for evaluate / generate_trajectory
         / further single training).  Its construction leaves the global np.random stream as it was."""
@@ -222,3 +349,23 @@ class ActorCriticPopulation:
         ac.theta = np.array([self.thetas[k]]) if self._rng_step else float(self.thetas[k])
         ac._rng_step = self._rng_step
         return ac
+
+
+def evaluate_population(pop, episode_length, indir, outfile, write_header, repeats):
+    """The body of ActorCriticPopulation.evaluate and AC_IRLPopulation.evaluate (the population's context bound)."""
+    if int(repeats) < 1:
+        raise ValueError('repeats=%d: at least one rollout per test file' % repeats)
+    emp = load_empirical(indir, pop.d, int(episode_length))
+    first_step = pop._rng_step
+    pop._rng_step += int(episode_length) - 1     # (a diverged launch has run: its step is spent, as in train())
+    try:
+        table = evaluate_policies(emp, pop._theta, pop._shifts_dev, pop._alphas_dev, pop._seeds_dev, first_step, int(repeats),
+                                  pop.precision, pop.device, pop._ctx)
+    except L.MfgError as e:
+        if e.code:                               # refused by the library before anything was launched
+            pop._rng_step = first_step
+        raise
+    thetas = pop.thetas
+    write_eval_rows(outfile, write_header, [(float(thetas[k]), float(pop.shifts[k]), float(pop.alpha_scales[k]))
+                                            for k in range(pop.K)], table)
+    return table[:, 0::2].copy()

@@ -437,6 +437,28 @@ int mfg_train_rollouts_pop(const float* mat_pi0, int64_t num_start, int64_t B, i
                            float* pi_last, float* reward, double* delta, double* g, double* G, double* reward_acc,
                            void* workspace, size_t workspace_bytes, mfg_stream_t stream);
 
+/* Population evaluation (evaluate / gridsearch, mfg_ac2.py:595-689; ac_irl.py:1495-1590 is the same with d = 15): the test
+ * rollouts and the eight metrics of K policies in at most two launches, with no host synchronisation.
+ *   emp32 / emp64 [N,L,d]: the N test files' first L rows (fp32 for the rollouts and the JSD, fp64 for the L1 metric).
+ *   theta, shift, alpha_scale [K] fp64 and seed [K] uint64: learner k's policy; first_step: shared by all K.
+ *   repeats R >= 1: learner k's trajectory j (0 <= j < N R) starts at emp32[j mod N, 0] and is keyed by Philox
+ *   (seed[k], first_step + t, trajectory id j) -- bit for bit the states of mfg_rollout over those start rows (no TD).
+ *   metrics [K,8] fp64, the CSV's column order: mean / std (ddof = 0) over the N R trajectories of l1_final, l1_mean,
+ *   JSD_final, JSD_mean; L1 per step in fp64 against emp64, JSD per step as mfg_jsd(emp32 row, generated row); "final" is
+ *   row L-1, "mean" the mean over the L rows.  Reduced in a fixed order, no floating-point atomics: learner k's row depends
+ *   on its own inputs only, run to run and whatever K is.
+ *   pi_traj [K, N R, L, d] fp32 or NULL (then the trajectories stay in the workspace).
+ *   workspace: mfg_evaluate_pop_workspace_bytes(N, L, d, K, repeats, pi_traj != NULL) bytes; contents are scratch.
+ * Checked before anything is launched: 1 <= K <= MFG_POP_MAX_K, d <= 64 (MFG_EUNSUPPORTED beyond, as for the populations),
+ * L >= 2, N >= 1, repeats >= 1, no null pointer, the Philox step counter does not wrap (MFG_EINVAL), the workspace
+ * (MFG_EWORKSPACE).  Mixed precision reports into and is refused on the bound context's status word like every sampling
+ * launch. */
+size_t mfg_evaluate_pop_workspace_bytes(int64_t N, int L, int d, int K, int repeats, int traj_given);
+int mfg_evaluate_pop(const float* emp32, const double* emp64, int64_t N, int L, int d, int K, const double* theta,
+                     const double* shift, const double* alpha_scale, const uint64_t* seed, uint32_t first_step, int repeats,
+                     int precision, double* metrics, float* pi_traj, void* workspace, size_t workspace_bytes,
+                     mfg_stream_t stream);
+
 /* Weights of the reward network of networks.py:46-81 as device pointers (layouts as for mfg_reward_net_forward). */
 typedef struct mfg_reward_net {
   int k1, f2, k2, n3, n4;
