@@ -1,7 +1,5 @@
 // Instantiations of the packed small-d core kernel (d <= 64): generic runtime d plus compile-time
 // specialisations for the reference's two problem sizes (d = 21: mfg_ac2.py:25, d = 15: ac_irl.py:33).
-#include <atomic>
-
 #include "mfg_core.h"
 
 namespace mfg {
@@ -13,22 +11,7 @@ namespace mfg {
 // a static tile split.
 template <bool SAMPLE, bool TD, bool FAST, int D, bool SUMS = false, int STEP = 0>
 static void go(const CoreArgs& a, int num_cus, size_t lds, hipStream_t st) {
-  // occupancy of this instantiation at this LDS size, cached per device
-  static std::atomic<size_t> cached_lds[64];
-  static std::atomic<int> cached_bpc[64];
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-  if (cached_lds[dev].load() != lds + 1) {  // (+1: zero-initialised slots never match)
-    int n = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_core_small<SAMPLE, TD, FAST, D, SUMS, STEP>, BLOCK, lds) != hipSuccess || n < 1)
-      n = 1;
-    cached_bpc[dev].store(n);
-    cached_lds[dev].store(lds + 1);
-  }
-  const int G = WAVE / a.d, TB = WAVES * G;
-  // (single-step launches: x2 -- a block's weight staging and first state load are then shared by ~3-4 tiles; measured
-  //  1.64 -> 1.61 ms per 15-step episode of per-step updates at B = 65 536, x1 1.70, x4 1.62)
-  const int grid = core_grid(a.B, TB, cached_bpc[dev].load() * (a.T == 1 ? 2 : MFG_CORE_OVERSUBSCRIBE), num_cus);
+  const int grid = core_small_grid<k_core_small<SAMPLE, TD, FAST, D, SUMS, STEP>>(a, lds, num_cus);
   // (STEP: the blocks that reduce the previous env step's partial rows ride behind the sampling blocks)
   hipLaunchKernelGGL((k_core_small<SAMPLE, TD, FAST, D, SUMS, STEP>), dim3(grid + (STEP == 1 ? core_step_red_blocks(a.d * (a.d + 1) / 2 + a.d + 1 + 3) : 0)), dim3(BLOCK), lds, st, a);
 }

@@ -1,7 +1,7 @@
 // Population evaluation (mfg_evaluate_pop): the test rollouts and the L1 / JSD metrics of K policies in two launches
 // (evaluate / gridsearch, mfg_ac2.py:595-689, ac_irl.py:1495-1590).
 //   launch 1, k_eval_rollout_pop, grid (gx, K): learner blockIdx.y's N R test trajectories -- the packed core kernel's body
-//     (core_small_body, sampling without TD) on an argument block rebased to the learner, exactly as k_core_small_pop does,
+//     (core_small_body, sampling without TD) on the argument block rebased to the learner by pop_core_args (mfg_population.h),
 //     so trajectory j carries the Philox keys (seed[k], first_step + t, j) of a single mfg_rollout over the same start rows.
 //     Start row of trajectory j: emp32[j mod N, 0], gathered through a per-learner index table that each block writes for
 //     its OWN tiles before it runs the body (the body reads the rows of no other tile).
@@ -14,19 +14,9 @@
 #include <stdint.h>
 
 #include "mfg_core.h"
+#include "mfg_population.h"
 
 namespace mfg {
-
-struct EvalPop {
-  int K;
-  int64_t N;        // test files
-  int L;            // rows per file (episode_length): T = L - 1 steps
-  int64_t s_traj;   // pi_traj floats of one learner: N R L d
-  int64_t s_idx;    // int32 entries between the learners' start-index tables (padded to 256 bytes)
-  int32_t* idx;     // [K][s_idx] start-index tables (workspace)
-  const uint64_t* seed;
-  const double *shift, *alpha_scale;  // [K]
-};
 
 // workspace layout of mfg_evaluate_pop: [idx tables | per-trajectory metrics [K][N R][4] fp64 | pi_traj if not given]
 inline int64_t eval_pop_idx_stride(int64_t NR) { return (NR * 4 + 255) / 256 * 256 / 4; }
@@ -37,7 +27,6 @@ inline size_t eval_pop_workspace_bytes(int64_t N, int L, int d, int K, int repea
   return b;
 }
 
-int launch_eval_rollout_pop(const CoreArgs& a, const EvalPop& p, bool fast, int num_cus, hipStream_t st);
 void launch_eval_metrics_pop(const float* pi_traj, const float* emp32, const double* emp64, int64_t N, int L, int d, int64_t NR,
                              int K, double* per_traj, double* metrics, hipStream_t st);
 

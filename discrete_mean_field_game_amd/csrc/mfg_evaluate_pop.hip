@@ -1,7 +1,5 @@
 // Population evaluation kernels (mfg_evaluate_pop.h): the test rollouts of K policies (the packed core kernel's body on an
 // argument block rebased per learner) and their L1 / JSD metrics, reduced per learner in a fixed order.
-#include <atomic>
-
 #include "mfg_core.h"
 #include "mfg_evaluate_pop.h"
 
@@ -11,7 +9,7 @@ namespace mfg {
 // (strict precision: two waves per SIMD -- at the single kernel's three the body spills 12 .. 296 bytes per lane, and an
 //  evaluation launch is far too small to need the occupancy)
 template <bool FAST, int D>
-__global__ __launch_bounds__(BLOCK, FAST ? MFG_CORE_SMALL_WAVES : 2) void k_eval_rollout_pop(CoreArgs a, EvalPop p) {
+__global__ __launch_bounds__(BLOCK, FAST ? MFG_CORE_SMALL_WAVES : 2) void k_eval_rollout_pop(CoreArgs a, PopArgs p) {
   const int k = blockIdx.y;
   const int d = D ? D : a.d;
   const int TB = WAVES * (WAVE / d);
@@ -24,35 +22,18 @@ __global__ __launch_bounds__(BLOCK, FAST ? MFG_CORE_SMALL_WAVES : 2) void k_eval
   }
   __threadfence();  // (written by other waves of the block than the ones that read them; each learner's table has lines of its own)
   __syncthreads();
-  CoreArgs c = a;
+  CoreArgs c = pop_core_args<false, 0>(a, p, k);
   c.start_idx = idx;
-  c.theta = a.theta + k;
-  c.shift = p.shift[k];
-  c.alpha_scale = p.alpha_scale[k];
-  c.seed = p.seed[k];
-  c.pi_traj = a.pi_traj + p.s_traj * k;
   core_small_body<true, false, FAST, D, false, 0>(c);
 }
 
 template <bool FAST, int D>
-static void go_eval(const CoreArgs& a, const EvalPop& p, int num_cus, size_t lds, hipStream_t st) {
-  // occupancy of this instantiation at this LDS size, cached per device (as launch_core_small does for the single kernel)
-  static std::atomic<size_t> cached_lds[64];
-  static std::atomic<int> cached_bpc[64];
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-  if (cached_lds[dev].load() != lds + 1) {
-    int n = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_eval_rollout_pop<FAST, D>, BLOCK, lds) != hipSuccess || n < 1) n = 1;
-    cached_bpc[dev].store(n);
-    cached_lds[dev].store(lds + 1);
-  }
-  const int TB = WAVES * (WAVE / a.d);
-  const int grid = core_grid(a.B, TB, cached_bpc[dev].load() * (a.T == 1 ? 2 : MFG_CORE_OVERSUBSCRIBE), num_cus);
+static void go_eval(const CoreArgs& a, const PopArgs& p, int num_cus, size_t lds, hipStream_t st) {
+  const int grid = core_small_grid<k_eval_rollout_pop<FAST, D>>(a, lds, num_cus);
   hipLaunchKernelGGL((k_eval_rollout_pop<FAST, D>), dim3((unsigned)grid, (unsigned)p.K), dim3(BLOCK), lds, st, a, p);
 }
 
-int launch_eval_rollout_pop(const CoreArgs& a, const EvalPop& p, bool fast, int num_cus, hipStream_t st) {
+int launch_eval_rollout_pop(const CoreArgs& a, const PopArgs& p, bool fast, int num_cus, hipStream_t st) {
   const int d = a.d;
   if (d > WAVE) return MFG_EUNSUPPORTED;
   const size_t lds = core_small_lds(d, false, true);

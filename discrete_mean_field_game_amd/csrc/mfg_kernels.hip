@@ -1895,10 +1895,9 @@ static bool traj_ids_ok(uint64_t traj_offset, int64_t B) {
   return traj_offset <= MFG_TRAJ_ID_LIMIT && (uint64_t)(B > 0 ? B : 0) <= MFG_TRAJ_ID_LIMIT - traj_offset;
 }
 
-// pop != NULL: the population form (mfg_population.h; training launches at d <= 64, packed lane mapping); ipop != NULL: the IRL
-// population form (mfg_irl_population.h; d = 21 / 15)
-static int launch_core(const CoreArgs& a_in, bool sample, bool td, int precision, hipStream_t st, const PopArgs* pop = nullptr,
-                       const IrlCorePop* ipop = nullptr, const EvalPop* epop = nullptr) {
+// pop != NULL: the population form (mfg_population.h; d <= 64, packed lane mapping): sampling + TD the training kernel,
+// sampling alone the evaluation kernel (mfg_evaluate_pop.h)
+static int launch_core(const CoreArgs& a_in, bool sample, bool td, int precision, hipStream_t st, const PopArgs* pop = nullptr) {
   CoreArgs a = a_in;
   if (!traj_ids_ok(a.traj_offset, a.B))
     return fail(MFG_EINVAL, "trajectory ids traj_offset + B = %llu + %lld exceed 2^48 (MFG_TRAJ_ID_LIMIT)",
@@ -1925,9 +1924,9 @@ static int launch_core(const CoreArgs& a_in, bool sample, bool td, int precision
     if (!a.htab) return fail(MFG_ELAUNCH, "%s", "h(z) table initialisation failed");
   }
   int rc;
-  if (epop) rc = (sample && !td) ? launch_eval_rollout_pop(a, *epop, precision == MFG_PRECISION_MIXED, num_cus(), st) : MFG_EUNSUPPORTED;
-  else if (ipop) rc = (sample && td) ? launch_core_irl_pop(a, *ipop, precision == MFG_PRECISION_MIXED, num_cus(), st) : MFG_EUNSUPPORTED;
-  else if (pop) rc = (sample && td) ? launch_core_small_pop(a, *pop, precision == MFG_PRECISION_MIXED, num_cus(), st) : MFG_EUNSUPPORTED;
+  if (pop) rc = !sample ? MFG_EUNSUPPORTED
+                : td  ? launch_core_pop(a, *pop, precision == MFG_PRECISION_MIXED, num_cus(), st)
+                      : launch_eval_rollout_pop(a, *pop, precision == MFG_PRECISION_MIXED, num_cus(), st);
   else if (a.d <= WAVE) rc = launch_core_small(a, sample, td, precision == MFG_PRECISION_MIXED, num_cus(), st);
   else if (precision == MFG_PRECISION_MIXED) rc = launch_core_large_mixed(a, sample, td, num_cus(), st);
   else rc = launch_core_large_f64(a, sample, td, num_cus(), st);
@@ -3041,20 +3040,30 @@ static size_t pop_workspace_need(int d, int64_t N, bool sums_rows) {
   return (size_t)(nsb * FO * 8) + MFG_WS_CONTROL_BYTES;
 }
 
-#define CHECK_POP()                                                                                                   \
-  REQUIRE(K >= 1 && K <= MFG_POP_MAX_K, "population size K outside [1, MFG_POP_MAX_K]");                            \
-  CHECK_BD();                                                                                                         \
-  if (d > WAVE) return fail(MFG_EUNSUPPORTED, "population: d=%d > 64 (one wave per trajectory fills the machine)", d); \
-  REQUIRE(T >= 1, "T < 1");                                                                                           \
-  REQUIRE(mat_pi0 && num_start > 0 && num_start <= 0x7FFFFFFF, "null / empty / oversized start-state table");         \
-  REQUIRE(theta && shift && alpha_scale && w && seed && lr_critic && lr_actor && reward && delta && g && G && workspace, \
-          "null pointer");                                                                                            \
-  REQUIRE(reward_kind == MFG_REWARD_MFG_AC2 || reward_kind == MFG_REWARD_SYNTHETIC, "needs an in-kernel reward");     \
-  REQUIRE(workspace_bytes % 256 == 0, "population: workspace_bytes (one learner's slice) must be a multiple of 256");  \
-  REQUIRE(episodes >= 0 && first_episode >= 0, "bad episode range");                                                  \
-  REQUIRE((uint64_t)first_step + (uint64_t)episodes * (uint64_t)T <= 0xFFFFFFFFull, "Philox step counter would wrap"); \
+// the checks every population training call shares (shape_check: the call's own limits on d / B T, right after the shape
+// checks; extra_ptrs: its own pointers, checked with the shared ones)
+#define CHECK_POP(shape_check, extra_ptrs)                                                                             \
+  REQUIRE(K >= 1 && K <= MFG_POP_MAX_K, "population size K outside [1, MFG_POP_MAX_K]");                              \
+  CHECK_BD();                                                                                                           \
+  shape_check;                                                                                                          \
+  REQUIRE(T >= 1, "T < 1");                                                                                             \
+  REQUIRE(mat_pi0 && num_start > 0 && num_start <= 0x7FFFFFFF, "null / empty / oversized start-state table");           \
+  REQUIRE(theta && shift && alpha_scale && w && seed && lr_critic && lr_actor && reward && delta && g && G && workspace && \
+              (extra_ptrs),                                                                                             \
+          "null pointer");                                                                                              \
+  REQUIRE(workspace_bytes % 256 == 0, "population: workspace_bytes (one learner's slice) must be a multiple of 256");    \
+  REQUIRE(episodes >= 0 && first_episode >= 0, "bad episode range");                                                    \
+  REQUIRE((uint64_t)first_step + (uint64_t)episodes * (uint64_t)T <= 0xFFFFFFFFull, "Philox step counter would wrap");   \
   REQUIRE(traj_ids_ok(traj_offset, B), "trajectory ids traj_offset + B exceed 2^48 (MFG_TRAJ_ID_LIMIT)")
 
+// the in-kernel-reward populations (d <= 64)
+#define CHECK_AC_POP()                                                                                                  \
+  CHECK_POP(if (d > WAVE)                                                                                               \
+              return fail(MFG_EUNSUPPORTED, "population: d=%d > 64 (one wave per trajectory fills the machine)", d),    \
+            true);                                                                                                      \
+  REQUIRE(reward_kind == MFG_REWARD_MFG_AC2 || reward_kind == MFG_REWARD_SYNTHETIC, "needs an in-kernel reward")
+
+// the argument block of a population call (the call sets the strides that depend on its flow: s_pi0, s_gpi, s_n, s_P)
 static PopArgs pop_args(int K, int64_t B, int d, int64_t T, int64_t episodes, const uint64_t* seed, const double* shift,
                         const double* alpha_scale, const double* lr_critic, const double* lr_actor, size_t workspace_bytes) {
   PopArgs p{};
@@ -3064,6 +3073,7 @@ static PopArgs pop_args(int K, int64_t B, int d, int64_t T, int64_t episodes, co
   p.s_state = B * d;
   p.s_acc = episodes;
   p.s_ws = (int64_t)workspace_bytes;
+  p.s_theta_b = sizeof(double);
   p.seed = seed;
   p.shift = shift;
   p.alpha_scale = alpha_scale;
@@ -3078,7 +3088,7 @@ int mfg_train_episodes_pop(const float* mat_pi0, int64_t num_start, float* pi_io
                            uint32_t first_step, uint64_t traj_offset, int precision, const double* lr_critic,
                            const double* lr_actor, float* reward, double* delta, double* g, double* G, double* reward_acc,
                            void* workspace, size_t workspace_bytes, mfg_stream_t stream) {
-  CHECK_POP();
+  CHECK_AC_POP();
   CHECK_PRECISION();
   REQUIRE(pi_io && pi_scratch, "null pointer");
   const bool sums = core_sums_ok(d, B, 1, reward_kind, workspace, workspace_bytes);
@@ -3107,7 +3117,7 @@ int mfg_train_rollouts_pop(const float* mat_pi0, int64_t num_start, int64_t B, i
                            uint64_t traj_offset, int flags, const double* lr_critic, const double* lr_actor, float* pi_traj,
                            float* pi_last, float* reward, double* delta, double* g, double* G, double* reward_acc,
                            void* workspace, size_t workspace_bytes, mfg_stream_t stream) {
-  CHECK_POP();
+  CHECK_AC_POP();
   REQUIRE(pi_traj, "null pointer");
   const size_t need = pop_workspace_need(d, B * T, false);
   if (workspace_bytes < need)
@@ -3153,16 +3163,11 @@ int mfg_evaluate_pop(const float* emp32, const double* emp64, int64_t N, int L, 
     return fail(MFG_EWORKSPACE, "population evaluation workspace: need %lld bytes, have %lld", (long long)need,
                 (long long)workspace_bytes);
   const int64_t NR = N * repeats;
-  EvalPop p{};
-  p.K = K;
+  PopArgs p = pop_args(K, NR, d, L - 1, 0, seed, shift, alpha_scale, nullptr, nullptr, 0);
   p.N = N;
   p.L = L;
-  p.s_traj = NR * L * d;
   p.s_idx = eval_pop_idx_stride(NR);
   p.idx = reinterpret_cast<int32_t*>(workspace);
-  p.seed = seed;
-  p.shift = shift;
-  p.alpha_scale = alpha_scale;
   double* per_traj = reinterpret_cast<double*>(reinterpret_cast<char*>(workspace) + (size_t)K * p.s_idx * 4);
   float* traj = pi_traj ? pi_traj : reinterpret_cast<float*>(per_traj + (size_t)K * NR * 4);
   CoreArgs a{};
@@ -3176,49 +3181,22 @@ int mfg_evaluate_pop(const float* emp32, const double* emp64, int64_t N, int L, 
   a.reward_kind = MFG_REWARD_EXTERNAL;  // (states only: no reward is formed)
   a.first_step = first_step;
   a.pi_traj = traj;
-  const int rc = launch_core(a, true, false, precision, S(stream), nullptr, nullptr, &p);
+  const int rc = launch_core(a, true, false, precision, S(stream), &p);
   if (rc != MFG_OK) return rc;
   launch_eval_metrics_pop(traj, emp32, emp64, N, L, d, NR, K, per_traj, metrics, S(stream));
   return check_launch("evaluate_pop metrics");
 }
 
-// ---- IRL populations (mfg_irl_population.h): K forward learners of AC_IRL.train in the launches of one ----------------------
+// ---- IRL populations (mfg_population.h, mfg_irl_population.h): K forward learners of AC_IRL.train in the launches of one ----
+// the IRL populations: B T samples per learner (checked ahead of T >= 1, which changes nothing: a T < 1 keeps B T small), the
+// reward network's settings and the matrix-core kernel's geometry
 #define CHECK_IRL_POP()                                                                                                  \
-  REQUIRE(K >= 1 && K <= MFG_POP_MAX_K, "population size K outside [1, MFG_POP_MAX_K]");                               \
-  CHECK_BD();                                                                                                            \
-  REQUIRE(T >= 1, "T < 1");                                                                                              \
-  REQUIRE(B * (int64_t)T <= 0x7FFFFFFF, "B * T too large");                                                             \
-  REQUIRE(mat_pi0 && num_start > 0 && num_start <= 0x7FFFFFFF, "null / empty / oversized start-state table");            \
-  REQUIRE(theta && shift && alpha_scale && w && seed && lr_critic && lr_actor && net && rn_seed && P && reward && delta && \
-              g && G && workspace,                                                                                       \
-          "null pointer");                                                                                               \
+  CHECK_POP(REQUIRE(B * (int64_t)T <= 0x7FFFFFFF, "B * T too large"), net && rn_seed && P);                             \
   REQUIRE(net->keep_prob > 0.0f && net->keep_prob <= 1.0f, "reward net: keep_prob must be in (0,1]");                    \
-  REQUIRE(workspace_bytes % 256 == 0, "population: workspace_bytes (one learner's slice) must be a multiple of 256");     \
-  REQUIRE(episodes >= 0 && first_episode >= 0, "bad episode range");                                                     \
-  REQUIRE((uint64_t)first_step + (uint64_t)episodes * (uint64_t)T <= 0xFFFFFFFFull, "Philox step counter would wrap");    \
-  REQUIRE(traj_ids_ok(traj_offset, B), "trajectory ids traj_offset + B exceed 2^48 (MFG_TRAJ_ID_LIMIT)");               \
-  if (!reward_net_pop_ready(d, net, per_learner_net, K, net_stride))                                                               \
-    return fail(MFG_EUNSUPPORTED, "IRL population: d=%d, k1=%d, f2=%d, k2=%d, n_fc3=%d, n_fc4=%d: not the matrix-core "      \
+  if (!reward_net_pop_ready(d, net, per_learner_net, K, net_stride))                                                     \
+    return fail(MFG_EUNSUPPORTED, "IRL population: d=%d, k1=%d, f2=%d, k2=%d, n_fc3=%d, n_fc4=%d: not the matrix-core "  \
                 "reward network (d = 21 / 15, 5 / 2 / 3, n_fc3 <= 16, 8-byte aligned fc3_w of every learner)",           \
                 d, net->k1, net->f2, net->k2, net->n3, net->n4)
-
-static IrlCorePop irl_core_pop(int K, int64_t B, int d, int T, int64_t episodes, const uint64_t* seed, const double* shift,
-                               const double* alpha_scale, const double* lr_critic, const double* lr_actor, size_t workspace_bytes) {
-  IrlCorePop p{};
-  p.K = K;
-  p.s_state = B * d;
-  p.s_theta_b = sizeof(double);
-  p.F = mfg_num_features(d);
-  p.s_traj = B * (T + 1) * d;
-  p.s_acc = episodes;
-  p.s_ws = (int64_t)workspace_bytes;
-  p.seed = seed;
-  p.shift = shift;
-  p.alpha_scale = alpha_scale;
-  p.lr_c = lr_critic;
-  p.lr_a = lr_actor;
-  return p;
-}
 
 static uint64_t rn_key_ctr(uint64_t call) { return call * 0x9E3779B97F4A7C15ull; }
 
@@ -3243,7 +3221,7 @@ static int train_episodes_irl_pop(const float* mat_pi0, int64_t num_start, float
     return fail(MFG_EWORKSPACE, "IRL population workspace: need %lld bytes per learner, have %lld", (long long)need,
                 (long long)workspace_bytes);
   hipStream_t st = S(stream);
-  IrlCorePop p = irl_core_pop(K, B, d, 1, episodes, seed, shift, alpha_scale, lr_critic, lr_actor, workspace_bytes);
+  PopArgs p = pop_args(K, B, d, 1, episodes, seed, shift, alpha_scale, lr_critic, lr_actor, workspace_bytes);
   p.s_n = B;
   p.s_P = B * d * d;
   RnPop rp{};
@@ -3302,7 +3280,7 @@ static int train_episodes_irl_pop(const float* mat_pi0, int64_t num_start, float
         a.step_nrows = nrows;
         a.theta_out = th_slot + (s & 1);
       }
-      int rc = launch_core(a, true, true, precision, st, nullptr, &p);
+      int rc = launch_core(a, true, true, precision, st, &p);
       if (rc != MFG_OK) return rc;
       if (s > 0) {
         th_in = th_slot + (s & 1);
@@ -3329,7 +3307,8 @@ static int train_episodes_irl_pop(const float* mat_pi0, int64_t num_start, float
       cur = nxt;
       nxt = t;
     }
-    launch_reduce_rows_apply_pop(rows_buf, nrows, FO, G, (double)B, w, th_in, s_th_in, theta, acc, p, st);
+    p.s_theta_b = s_th_in;
+    launch_reduce_rows_apply_pop(rows_buf, nrows, FO, G, (double)B, w, th_in, theta, acc, p, st);
     const int rc = check_launch("train_episodes_irl_pop");
     if (rc != MFG_OK) return rc;
   }
@@ -3351,13 +3330,11 @@ static int train_rollouts_irl_pop(const float* mat_pi0, int64_t num_start, int64
     return fail(MFG_EWORKSPACE, "IRL population workspace: need %lld bytes per learner, have %lld", (long long)need,
                 (long long)workspace_bytes);
   hipStream_t st = S(stream);
-  IrlCorePop p = irl_core_pop(K, B, d, T, episodes, seed, shift, alpha_scale, lr_critic, lr_actor, workspace_bytes);
+  PopArgs p = pop_args(K, B, d, T, episodes, seed, shift, alpha_scale, lr_critic, lr_actor, workspace_bytes);
   p.s_pi0 = 0;  // (the shared start-state table: the rows are drawn in the kernel)
+  p.s_gpi = p.s_traj;
   p.s_n = B * T;
   p.s_P = B * T * d * d;
-  PopArgs q = pop_args(K, B, d, T, episodes, seed, shift, alpha_scale, lr_critic, lr_actor, workspace_bytes);
-  q.s_gpi = q.s_traj;
-  q.s_n = B * T;
   RnPop rp{};
   rp.K = K;
   rp.per_learner_net = per_learner_net ? 1 : 0;
@@ -3371,8 +3348,6 @@ static int train_rollouts_irl_pop(const float* mat_pi0, int64_t num_start, int64
   const int precision = (flags & MFG_ROLLOUT_F64) ? MFG_PRECISION_F64 : MFG_PRECISION_MIXED;
   for (int64_t e = 0; e < episodes; ++e) {
     lr_schedule(first_episode + e, constant, &p.sc, &p.sa);
-    q.sc = p.sc;
-    q.sa = p.sa;
     CoreArgs a{};
     a.pi0 = mat_pi0;
     a.start_draw = 1;
@@ -3392,7 +3367,7 @@ static int train_rollouts_irl_pop(const float* mat_pi0, int64_t num_start, int64
     a.delta = delta;
     a.g = g;
     a.P_out = P;
-    int rc = launch_core(a, true, true, precision, st, nullptr, &p);
+    int rc = launch_core(a, true, true, precision, st, &p);
     if (rc != MFG_OK) return rc;
     // ONE reward-network pass over each learner's Bk T transitions, states read in place from pi_traj
     rp.key_ctr = rn_key_ctr(rn_call0 + (uint64_t)e + 1ull);
@@ -3402,7 +3377,7 @@ static int train_rollouts_irl_pop(const float* mat_pi0, int64_t num_start, int64
     const ApplyArgs ap{0.0, 0.0, w, theta, reward_acc ? reward_acc + e : nullptr};
     bool applied = false;
     rc = launch_grad(pi_traj, (int64_t)(T + 1) * d, delta, g, reward, B * T, T, d, G, 0, workspace, workspace_bytes, st, &ap,
-                     &applied, true, &q);
+                     &applied, true, &p);
     if (rc != MFG_OK) return rc;
     if (!applied) return fail(MFG_ELAUNCH, "%s", "IRL population: update not applied");  // (not reached: d <= 64)
   }

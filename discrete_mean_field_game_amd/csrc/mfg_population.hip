@@ -1,8 +1,7 @@
 // Population forms of the kernels of a training episode at d <= 64 (mfg_population.h): the start draw, the packed core kernel
-// (plain and SUMS), the gradient kernels and the row reduction with its update.  Each wrapper rebases the argument block to
-// learner k and runs the body of the single kernel (core_small_body, grad_*_body, reduce_partials_body, draw_start_body).
-#include <atomic>
-
+// (plain, SUMS and the IRL env-step variants), the gradient kernels and the two row reductions with their update.  Each wrapper
+// rebases the argument block to learner k and runs the body of the single kernel (core_small_body, grad_*_body,
+// reduce_partials_body, reduce_rows_apply_body, draw_start_body).
 #include "mfg_core.h"
 #define MFG_GRAD_BODIES_ONLY
 #include "mfg_grad.h"
@@ -10,76 +9,55 @@
 
 namespace mfg {
 
-template <class P>
-__device__ __forceinline__ P* pop_at(P* p, int64_t stride, int k) {
-  return p ? p + stride * k : p;
-}
-__device__ __forceinline__ double* pop_ws(double* p, const PopArgs& q, int k) {
-  return p ? reinterpret_cast<double*>(reinterpret_cast<char*>(p) + q.s_ws * k) : p;
-}
-
-// ---- packed core kernel: sampling, transition, reward, value, TD error, score (and the SUMS rows) of learner blockIdx.y ----
-template <bool FAST, int D, bool SUMS>
-__global__ __launch_bounds__(BLOCK, SUMS ? 2 : (FAST ? MFG_CORE_SMALL_WAVES : MFG_CORE_SMALL_WAVES_F64)) void k_core_small_pop(
-    CoreArgs a, PopArgs p) {
-  const int k = blockIdx.y;
-  CoreArgs b = a;
-  b.pi0 = pop_at(a.pi0, p.s_pi0, k);
-  b.theta = a.theta + k;
-  b.w = pop_at(a.w, p.F, k);
-  b.shift = p.shift[k];
-  b.alpha_scale = p.alpha_scale[k];
-  b.seed = p.seed[k];
-  b.pi_traj = pop_at(a.pi_traj, p.s_traj, k);
-  b.pi_next_out = pop_at(a.pi_next_out, p.s_state, k);
-  b.reward_out = pop_at(a.reward_out, p.s_n, k);
-  b.delta = pop_at(a.delta, p.s_n, k);
-  b.g = pop_at(a.g, p.s_n, k);
-  b.part_rows = pop_ws(a.part_rows, p, k);
-  core_small_body<true, true, FAST, D, SUMS, 0>(b);
+// ---- packed core kernel: sampling, transition, value, TD error, score of learner blockIdx.y; SUMS: the tile's batch-sum rows;
+//      STEP 1 / 2: an IRL env step (external reward, P materialised) ----
+template <bool FAST, int D, bool SUMS, int STEP>
+__global__ __launch_bounds__(BLOCK, SUMS ? 2 : (FAST ? MFG_CORE_SMALL_WAVES : MFG_CORE_SMALL_WAVES_F64)) void k_core_pop(CoreArgs a,
+                                                                                                                   PopArgs p) {
+  core_small_body<true, true, FAST, D, SUMS, STEP>(pop_core_args<SUMS, STEP>(a, p, blockIdx.y));
 }
 
-template <bool FAST, int D, bool SUMS>
+template <bool FAST, int D, bool SUMS, int STEP>
 static void go_pop(const CoreArgs& a, const PopArgs& p, int num_cus, size_t lds, hipStream_t st) {
-  // occupancy of this instantiation at this LDS size, cached per device (as launch_core_small does for the single kernel)
-  static std::atomic<size_t> cached_lds[64];
-  static std::atomic<int> cached_bpc[64];
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-  if (cached_lds[dev].load() != lds + 1) {
-    int n = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_core_small_pop<FAST, D, SUMS>, BLOCK, lds) != hipSuccess || n < 1) n = 1;
-    cached_bpc[dev].store(n);
-    cached_lds[dev].store(lds + 1);
-  }
-  const int TB = WAVES * (WAVE / a.d);
-  const int grid = core_grid(a.B, TB, cached_bpc[dev].load() * (a.T == 1 ? 2 : MFG_CORE_OVERSUBSCRIBE), num_cus);
-  hipLaunchKernelGGL((k_core_small_pop<FAST, D, SUMS>), dim3((unsigned)grid, (unsigned)p.K), dim3(BLOCK), lds, st, a, p);
+  const int grid = core_small_grid<k_core_pop<FAST, D, SUMS, STEP>>(a, lds, num_cus) +
+                   (STEP == 1 ? core_step_red_blocks(a.d * (a.d + 1) / 2 + a.d + 1 + 3) : 0);
+  hipLaunchKernelGGL((k_core_pop<FAST, D, SUMS, STEP>), dim3((unsigned)grid, (unsigned)p.K), dim3(BLOCK), lds, st, a, p);
 }
 
+// (as dispatch<D> in mfg_core_small.hip, sampling + TD only)
 template <int D>
 static void dispatch_pop(const CoreArgs& a, const PopArgs& p, bool fast, int num_cus, size_t lds, hipStream_t st) {
   if constexpr (D > 0) {
+    if (a.step_nrows > 0) {
+      if (fast) go_pop<true, D, false, 1>(a, p, num_cus, lds, st);
+      else go_pop<false, D, false, 1>(a, p, num_cus, lds, st);
+      return;
+    }
+    if (a.step_nrows < 0) {
+      if (fast) go_pop<true, D, false, 2>(a, p, num_cus, lds, st);
+      else go_pop<false, D, false, 2>(a, p, num_cus, lds, st);
+      return;
+    }
     if (a.part_rows) {
-      if (fast) go_pop<true, D, true>(a, p, num_cus, lds, st);
-      else go_pop<false, D, true>(a, p, num_cus, lds, st);
+      if (fast) go_pop<true, D, true, 0>(a, p, num_cus, lds, st);
+      else go_pop<false, D, true, 0>(a, p, num_cus, lds, st);
       return;
     }
   }
-  if (fast) go_pop<true, D, false>(a, p, num_cus, lds, st);
-  else go_pop<false, D, false>(a, p, num_cus, lds, st);
+  if (fast) go_pop<true, D, false, 0>(a, p, num_cus, lds, st);
+  else go_pop<false, D, false, 0>(a, p, num_cus, lds, st);
 }
 
 // Always the packed lane mapping: k_core_row3 is for batches that under-fill the machine, a population fills it (both
 // mappings give the same bits).  Training launches only (sampling + TD).
-int launch_core_small_pop(const CoreArgs& a, const PopArgs& p, bool fast, int num_cus, hipStream_t st) {
+int launch_core_pop(const CoreArgs& a, const PopArgs& p, bool fast, int num_cus, hipStream_t st) {
   const int d = a.d;
   if (d > WAVE) return MFG_EUNSUPPORTED;
   const size_t lds = core_small_lds(d, a.w != nullptr, true);
   if (d == 21) dispatch_pop<21>(a, p, fast, num_cus, lds, st);
   else if (d == 15) dispatch_pop<15>(a, p, fast, num_cus, lds, st);
-  else if (!a.part_rows) dispatch_pop<0>(a, p, fast, num_cus, lds, st);
-  else return MFG_EUNSUPPORTED;  // (SUMS rows: compile-time d only, core_sums_rows)
+  else if (!a.part_rows && a.step_nrows == 0) dispatch_pop<0>(a, p, fast, num_cus, lds, st);
+  else return MFG_EUNSUPPORTED;  // (SUMS rows and the STEP variants: compile-time d only)
   return MFG_OK;
 }
 
@@ -102,8 +80,8 @@ __device__ __forceinline__ void pop_rebase_grad(GradArgs& a, const PopArgs& p, i
   a.delta += p.s_n * k;
   a.g += p.s_n * k;
   a.reward = pop_at(a.reward, p.s_n, k);
-  a.partial = pop_ws(a.partial, p, k);
-  if (a.counter) a.counter = reinterpret_cast<unsigned*>(reinterpret_cast<char*>(a.counter) + p.s_ws * k);
+  a.partial = pop_bytes(a.partial, p.s_ws, k);
+  a.counter = pop_bytes(a.counter, p.s_ws, k);
   a.G = pop_at(a.G, p.F + 3, k);
   a.w = pop_at(a.w, p.F, k);
   a.theta = pop_at(a.theta, 1, k);
@@ -144,6 +122,7 @@ __global__ __launch_bounds__(RP_SLICES* RP_OUT) void k_reduce_partials_pop(const
     q.lr_c = p.lr_c[k] * p.sc;
     q.lr_a = p.lr_a[k] * p.sa;
   }
+  // (partial is never null: moved without pop_bytes' null test, which cost the kernel an SGPR)
   reduce_partials_body(reinterpret_cast<const double*>(reinterpret_cast<const char*>(partial) + p.s_ws * k), nsb, FO, 0,
                        G + FO * k, q);
 }
@@ -171,6 +150,22 @@ void launch_grad_mfma_pop(int npf, unsigned nsb, unsigned ny, size_t lds, const 
 void launch_reduce_partials_pop(unsigned nob, const double* partial, int64_t nsb, int64_t FO, double* G, const ReduceApply& ap,
                                 const PopArgs& p, hipStream_t st) {
   hipLaunchKernelGGL(k_reduce_partials_pop, dim3(nob, (unsigned)p.K), dim3(RP_SLICES * RP_OUT), 0, st, partial, nsb, FO, G, ap, p);
+}
+
+// ---- the row reduction + update that closes a step-mode IRL episode, learner blockIdx.y ----
+__global__ __launch_bounds__(BLOCK) void k_reduce_rows_apply_pop(const double* __restrict__ rows, int nrows, int64_t FO,
+                                                                 double* __restrict__ G, double count, double* __restrict__ w,
+                                                                 const double* theta_in, double* theta_out,
+                                                                 double* __restrict__ reward_acc, PopArgs p) {
+  const int k = blockIdx.y;
+  reduce_rows_apply_body(pop_bytes(rows, p.s_ws, k), nrows, FO, G + FO * k, p.lr_c[k] * p.sc, p.lr_a[k] * p.sa, count,
+                         w + p.F * k, pop_bytes(theta_in, p.s_theta_b, k), theta_out + k, pop_at(reward_acc, p.s_acc, k));
+}
+
+void launch_reduce_rows_apply_pop(const double* rows, int nrows, int64_t FO, double* G, double count, double* w,
+                                  const double* theta_in, double* theta_out, double* reward_acc, const PopArgs& p, hipStream_t st) {
+  hipLaunchKernelGGL(k_reduce_rows_apply_pop, dim3((unsigned)((FO + WAVES - 1) / WAVES), (unsigned)p.K), dim3(BLOCK), 0, st, rows,
+                     nrows, FO, G, count, w, theta_in, theta_out, reward_acc, p);
 }
 
 }  // namespace mfg

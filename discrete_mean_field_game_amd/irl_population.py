@@ -34,9 +34,9 @@ import torch
 from . import _lib as L
 from . import ops
 from .ac_irl import AC_IRL
-from .mfg_ac2 import EPISODE_STEPS, actor_critic
+from .mfg_ac2 import EPISODE_STEPS
 from .networks import RewardNet
-from .population import _with_ctx, broadcast, evaluate_population, resolve_start_table
+from .population import _Population, _with_ctx, broadcast
 from .reward_learning import RewardTrainer, StackedTrajectoryStore, TrajectoryStore
 
 # the tensors of mfg_reward_net_t, in the order of the struct, and the module parameter each one comes from
@@ -108,7 +108,8 @@ def check_args(K, d, batch, update_every, precision, reward_nets):
     return nets
 
 
-class AC_IRLPopulation:
+class AC_IRLPopulation(_Population):
+    _WITH_P = True
 
     def __init__(self, thetas, shifts=0.0, alpha_scales=1e4, d=15, *, batch, reward_nets, seeds=None, w0=None, pi0=None,
                  path_to_dir=None, update_every='step', precision='mixed', device=None, verbose=0, demonstrations=None,
@@ -120,32 +121,10 @@ class AC_IRLPopulation:
         if int(num_policies) < 1:
             raise ValueError('num_policies < 1')
         demo_np = check_demonstrations(demonstrations, int(d)) if demonstrations is not None else None
-        if not torch.cuda.is_available():
-            raise L.MfgError('AC_IRLPopulation needs a ROCm GPU: the HIP hot path has no CPU fallback')
-        L.lib()
-        ops.init()
-        self.device = torch.device(device) if device is not None else torch.device('cuda', torch.cuda.current_device())
-        self._ctx = ops.Context(self.device)
-        self.d, self.batch, self.episode_steps = int(d), int(batch), EPISODE_STEPS
-        self.update_every, self.precision, self.verbose = update_every, precision, verbose
-        F = ops.num_features(self.d)
-        self.shifts = broadcast('shifts', shifts, K)
-        self.alpha_scales = broadcast('alpha_scales', alpha_scales, K)
-        self.seeds = broadcast('seeds', np.arange(K) if seeds is None else seeds, K, np.uint64)
+        super().__init__(th, d, batch, EPISODE_STEPS, shifts, alpha_scales, seeds, w0, pi0, path_to_dir, update_every, precision,
+                         device, verbose)
         dev = self.device
-        self._theta = torch.as_tensor(th.copy(), device=dev)
-        if w0 is None:
-            w = np.stack([np.asarray(actor_critic.init_w(None, self.d), dtype=np.float64).reshape(-1) for _ in range(K)])
-        else:
-            w = np.asarray(w0, dtype=np.float64)
-            w = np.broadcast_to(w.reshape(1, -1), (K, F)) if w.size == F else w.reshape(K, F)
-        self._w = torch.as_tensor(np.array(w, dtype=np.float64), device=dev)   # (a copy: w may be a read-only broadcast view)
-        self.mat_pi0 = resolve_start_table(self.d, pi0, path_to_dir)
-        self._mat_pi0_dev = torch.as_tensor(np.ascontiguousarray(self.mat_pi0, dtype=np.float32), device=dev)
-        self._seeds_dev = torch.as_tensor(self.seeds.view(np.int64), device=dev)
         self._rn_seeds_dev = torch.as_tensor((self.seeds + np.uint64(RN_SEED_OFFSET)).view(np.int64), device=dev)
-        self._shifts_dev = torch.as_tensor(self.shifts, device=dev)
-        self._alphas_dev = torch.as_tensor(self.alpha_scales, device=dev)
         # the networks: owned copies, one stacked fp32 tensor per parameter ([1, ...] when shared); per-learner networks live
         # in one flat buffer [K, ld] (the reward trainer's parameter layout, rows padded to PARAM_ALIGN floats) and the
         # stacked tensors are views into it
@@ -182,10 +161,8 @@ class AC_IRLPopulation:
             setattr(st, field, self._net_params[field].data_ptr())
         st.keep_prob = keep
         self._net_struct = st
-        self._rng_step = 0       # Philox step counter, shared by the learners (they advance in lock-step)
         # AC_IRL's reward-call counters (dropout keys), one per learner: reward_iteration's checks stop per learner
         self._calls_k = np.zeros(K, dtype=np.int64)
-        self._bufs = None
         # the reward half of the IRL loop (AC_IRL.update_reward / reward_iteration / outerloop)
         self.lr_reward = lr_reward
         self.num_policies = int(num_policies)
@@ -216,18 +193,6 @@ class AC_IRLPopulation:
         c = self._calls_k
         return int(c[0]) if np.all(c == c[0]) else c.copy()
 
-    @property
-    def K(self):
-        return int(self._theta.shape[0])
-
-    @property
-    def thetas(self):
-        return self._theta.cpu().numpy().copy()
-
-    @property
-    def w(self):
-        return self._w.cpu().numpy().copy()
-
     def reward_net(self, k):
         """Learner k's reward network as a networks.RewardNet (a copy, on the population's device)."""
         if not 0 <= k < self.K:
@@ -239,30 +204,6 @@ class AC_IRLPopulation:
                 net.get_parameter(pname).copy_(self._net_params[field][j].cpu())
         return net.to(self.device)
 
-    def _buffers(self):
-        K, B, d, T = self.K, self.batch, self.d, self.episode_steps
-        if self._bufs is None:
-            dev, F = self.device, ops.num_features(d)
-            sb = ops.irl_pop_workspace_slice(B, d, T)
-            b = {'G': torch.zeros(K, F + 3, dtype=torch.float64, device=dev),
-                 'ws': torch.zeros(K, sb // 8, dtype=torch.float64, device=dev)}
-            if self.update_every == 'step':
-                b['pi'] = torch.empty(K, B, d, dtype=torch.float32, device=dev)
-                b['run'] = {'scratch': torch.empty(K, B, d, dtype=torch.float32, device=dev),
-                            'P': torch.empty(K, B, d, d, dtype=torch.float32, device=dev),
-                            'reward': torch.empty(K, B, dtype=torch.float32, device=dev),
-                            'delta': torch.empty(K, B, dtype=torch.float64, device=dev),
-                            'g': torch.empty(K, B, dtype=torch.float64, device=dev)}
-            else:
-                b['run'] = {'pi_traj': torch.empty(K, B, T + 1, d, dtype=torch.float32, device=dev),
-                            'pi_last': torch.empty(K, B, d, dtype=torch.float32, device=dev),
-                            'P': torch.empty(K, B, T, d, d, dtype=torch.float32, device=dev),
-                            'reward': torch.empty(K, B, T, dtype=torch.float32, device=dev),
-                            'delta': torch.empty(K, B, T, dtype=torch.float64, device=dev),
-                            'g': torch.empty(K, B, T, dtype=torch.float64, device=dev)}
-            self._bufs = b
-        return self._bufs
-
     # ------------------------------------------------------------------ training
     @_with_ctx
     def train(self, num_episodes, gamma=1, constant=False, lr_critic=0.1, lr_actor=0.001, *, first_episode=0):
@@ -270,77 +211,42 @@ class AC_IRLPopulation:
         reward network (episodes numbered first_episode + 1 ... in the learning-rate schedule, as there).  lr_critic /
         lr_actor: scalars or [K].  Returns a NumPy array [K, num_episodes] of the per-episode returns as AC_IRL.train books
         them: step mode the sum of the T updates' mean rewards, rollout mode T x the update's mean reward per transition."""
-        K, T = self.K, self.episode_steps
-        num_episodes = int(num_episodes)
-        if num_episodes < 0:
-            raise ValueError('num_episodes < 0')
-        if num_episodes == 0:
-            return np.zeros((K, 0))
-        lrc = torch.as_tensor(broadcast('lr_critic', lr_critic, K), device=self.device)
-        lra = torch.as_tensor(broadcast('lr_actor', lr_actor, K), device=self.device)
-        acc = torch.zeros(K, num_episodes, dtype=torch.float64, device=self.device)
-        b = self._buffers()
-        common = dict(first_step=self._rng_step, reward_acc=acc, precision=self.precision, net_stride=self._net_stride)
-        calls = torch.as_tensor(self._calls_k, device=self.device)      # per-learner reward-call counters
-        if self.update_every == 'step':
-            ops.train_episodes_irl_pop(self._mat_pi0_dev, b['pi'], T, num_episodes, first_episode + 1, constant, self._theta,
-                                       self._shifts_dev, self._alphas_dev, self._w, gamma, lrc, lra, self._seeds_dev,
-                                       self._net_struct, self.per_learner_net, self._rn_seeds_dev, calls, b['G'],
-                                       b['ws'], b['run'], **common)
-            self._calls_k += num_episodes * T
-        else:
-            ops.train_rollouts_irl_pop(self._mat_pi0_dev, T, num_episodes, first_episode + 1, constant, self._theta,
-                                       self._shifts_dev, self._alphas_dev, self._w, gamma, lrc, lra, self._seeds_dev,
-                                       self._net_struct, self.per_learner_net, self._rn_seeds_dev, calls, b['G'],
-                                       b['ws'], b['run'], **common)
-            self._calls_k += num_episodes
-        self._rng_step += num_episodes * T
-        out = acc.cpu().numpy()
-        if self.update_every == 'rollout':
-            out = out * T
-        if self.precision == 'mixed' and self._ctx.status(synchronize=True):
-            raise L.MfgError('a mixed-precision sampling launch of this population ran with |theta| (1/2 + |shift|) > 86 '
-                             '(or theta not finite): its outputs are NaN; use precision=\'f64\', then clear_status()')
-        for k, t in enumerate(self.thetas):             # AC_IRL.train records the policy (list_policies FIFO)
-            self.list_policies[k] = (self.list_policies[k] + [float(t)])[1:]
-        return out
+        T = self.episode_steps
 
-    def status(self, synchronize=True) -> int:
-        """Bits of this population's status word (0 = healthy), shared by its K learners."""
-        return self._ctx.status(synchronize)
-
-    def clear_status(self):
-        self._ctx.clear_status()
+        def run(b, lrc, lra, acc):
+            common = dict(first_step=self._rng_step, reward_acc=acc, precision=self.precision, net_stride=self._net_stride)
+            calls = torch.as_tensor(self._calls_k, device=self.device)      # per-learner reward-call counters
+            if self.update_every == 'step':
+                ops.train_episodes_irl_pop(self._mat_pi0_dev, b['pi'], T, int(num_episodes), first_episode + 1, constant,
+                                           self._theta, self._shifts_dev, self._alphas_dev, self._w, gamma, lrc, lra,
+                                           self._seeds_dev, self._net_struct, self.per_learner_net, self._rn_seeds_dev, calls,
+                                           b['G'], b['ws'], b['run'], **common)
+                self._calls_k += int(num_episodes) * T
+            else:
+                ops.train_rollouts_irl_pop(self._mat_pi0_dev, T, int(num_episodes), first_episode + 1, constant, self._theta,
+                                           self._shifts_dev, self._alphas_dev, self._w, gamma, lrc, lra, self._seeds_dev,
+                                           self._net_struct, self.per_learner_net, self._rn_seeds_dev, calls, b['G'],
+                                           b['ws'], b['run'], **common)
+                self._calls_k += int(num_episodes)
+        out = self._train(num_episodes, lr_critic, lr_actor, run)
+        if out.shape[1]:
+            for k, t in enumerate(self.thetas):         # AC_IRL.train records the policy (list_policies FIFO)
+                self.list_policies[k] = (self.list_policies[k] + [float(t)])[1:]
+        return out * T if self.update_every == 'rollout' else out
 
     @_with_ctx
     def evaluate(self, episode_length=16, indir='test_normalized_round2', outfile='eval_mfg_round2/validation.csv', write_header=0,
                  *, repeats=1):
         """ActorCriticPopulation.evaluate with the defaults of AC_IRL.evaluate (ac_irl.py:1495-1571: the population's d,
         validation.csv): learner k gets what learner(k).evaluate(thetas[k], shifts[k], alpha_scales[k], d, ...) gives."""
-        return evaluate_population(self, episode_length, indir, outfile, write_header, repeats)
+        return self._evaluate(episode_length, indir, outfile, write_header, repeats)
 
     def learner(self, k):
         """An AC_IRL holding learner k's theta, w, reward network, Philox position and reward-call counter and, for the reward
         half of the loop, the demonstrations, D_samp, the reward trainer's Adam state, lr_reward, the policy FIFO and the
         reward-update counters.  Its construction leaves the global np.random stream (and torch's CPU generator) as they were;
         the module `random` stream is set to learner k's (AC_IRL.update_reward draws its batches from it)."""
-        if not 0 <= k < self.K:
-            raise IndexError('learner %d of %d' % (k, self.K))
-        net = self.reward_net(k)
-        state = np.random.get_state()
-        try:
-            with torch.random.fork_rng(devices=[]):
-                ac = AC_IRL(float(self.thetas[k]), float(self.shifts[k]), float(self.alpha_scales[k]), self.d,
-                            lr_reward=float(self.lr_reward[k]), num_policies=self.num_policies, reg=net.reg, n_fc3=net.fc3.out_features, n_fc4=net.fc4.out_features, pi0=self.mat_pi0,
-                            demonstrations=[], batch=self.batch, seed=int(self.seeds[k]), update_every=self.update_every,
-                            precision=self.precision, device=self.device, verbose=self.verbose)
-        finally:
-            np.random.set_state(state)
-        ac.reward_net = net
-        ac.create_training_method()
-        ac.w = self.w[k]
-        ac.theta = np.array([self.thetas[k]]) if self._rng_step else float(self.thetas[k])
-        ac._rng_step = self._rng_step
+        ac = super().learner(k)
         ac._reward_calls = int(self._calls_k[k])
         ac.lr_reward = float(self.lr_reward[k])
         ac.num_policies = self.num_policies
@@ -363,6 +269,17 @@ class AC_IRLPopulation:
         ac._stats_host = None
         # the module `random` stream now continues learner k's (AC_IRL.update_reward draws from it)
         random.setstate(self._random[k].getstate())
+        return ac
+
+    def _new_learner(self, k):
+        net = self.reward_net(k)
+        with torch.random.fork_rng(devices=[]):
+            ac = AC_IRL(float(self.thetas[k]), float(self.shifts[k]), float(self.alpha_scales[k]), self.d,
+                        lr_reward=float(self.lr_reward[k]), num_policies=self.num_policies, reg=net.reg, n_fc3=net.fc3.out_features, n_fc4=net.fc4.out_features, pi0=self.mat_pi0,
+                        demonstrations=[], batch=self.batch, seed=int(self.seeds[k]), update_every=self.update_every,
+                        precision=self.precision, device=self.device, verbose=self.verbose)
+        ac.reward_net = net
+        ac.create_training_method()
         return ac
 
     def host_random_state(self, k):

@@ -26,6 +26,12 @@ def _chk_f64(t, name):
     return t
 
 
+def _rollout_flags(discount_pow, precision):
+    """The MFG_ROLLOUT_DISCOUNT_POW / MFG_ROLLOUT_F64 bits of a rollout call's flags (callers add ROLLOUT_TD, ROLLOUT_WRITE_P
+    or TRAIN_APPLY)."""
+    return (L.ROLLOUT_DISCOUNT_POW if discount_pow else 0) | (L.ROLLOUT_F64 if L.PRECISIONS[precision] == L.PRECISION_F64 else 0)
+
+
 def _ptr(t):
     """Device address of a tensor; None -> NULL; a plain int is taken as an address already (e.g. one entry of a
     per-episode accumulator array: base.data_ptr() + 8 * k, without building a tensor view per episode)."""
@@ -299,10 +305,7 @@ def rollout(pi0, T, theta, shift, alpha_scale, w=None, gamma=1.0, reward_kind=L.
     if write_P:
         flags |= L.ROLLOUT_WRITE_P
         P = o.get('P') if 'P' in o else torch.empty(B, T, d, d, dtype=torch.float32, device=dev)
-    if discount_pow:
-        flags |= L.ROLLOUT_DISCOUNT_POW
-    if L.PRECISIONS[precision] == L.PRECISION_F64:
-        flags |= L.ROLLOUT_F64
+    flags |= _rollout_flags(discount_pow, precision)
     L.check(L.lib().mfg_rollout(pi0.data_ptr(), B, d, T, theta.data_ptr(), float(shift), float(alpha_scale),
                                 _ptr(w) if td else None, float(gamma), int(reward_kind), int(seed), int(first_step),
                                 int(traj_offset), flags, pi_traj.data_ptr(), _ptr(pi_last), _ptr(reward), _ptr(delta),
@@ -325,9 +328,7 @@ def train_rollout(mat_pi0, idx, T, theta, shift, alpha_scale, w, gamma, G, ws, b
     B, d = bufs['pi_traj'].shape[0], mat_pi0.shape[1]
     if idx is not None and idx.numel() != B:
         raise ValueError('idx must have one entry per trajectory of the buffers')
-    flags = (L.TRAIN_APPLY if apply else 0) | (L.ROLLOUT_DISCOUNT_POW if discount_pow else 0)
-    if L.PRECISIONS[precision] == L.PRECISION_F64:
-        flags |= L.ROLLOUT_F64
+    flags = _rollout_flags(discount_pow, precision) | (L.TRAIN_APPLY if apply else 0)
     L.check(L.lib().mfg_train_rollout(mat_pi0.data_ptr(), mat_pi0.shape[0], _ptr(idx), B, d, int(T), theta.data_ptr(),
                                       float(shift), float(alpha_scale), w.data_ptr(), float(gamma), int(reward_kind),
                                       int(seed), int(first_step), int(traj_offset), flags, float(lr_critic),
@@ -346,9 +347,7 @@ def train_rollout_deferred(mat_pi0, idx, T, theta, w, pending, theta_out, w_out,
     the updated parameters land in (theta_out, w_out) -- other tensors than (theta, w).  G = this rank's sums afterwards."""
     _chk_f32(mat_pi0, 'mat_pi0'); _chk_f64(theta, 'theta'); _chk_f64(w, 'w'); _chk_f64(G, 'G')
     B, d = bufs['pi_traj'].shape[0], mat_pi0.shape[1]
-    flags = L.ROLLOUT_DISCOUNT_POW if discount_pow else 0
-    if L.PRECISIONS[precision] == L.PRECISION_F64:
-        flags |= L.ROLLOUT_F64
+    flags = _rollout_flags(discount_pow, precision)
     pG, plc, pla, pacc = pending if pending is not None else (None, 0.0, 0.0, None)
     L.check(L.lib().mfg_train_rollout_deferred(mat_pi0.data_ptr(), mat_pi0.shape[0], _ptr(idx), B, d, int(T), theta.data_ptr(),
                                                w.data_ptr(), _ptr(pG), float(plc), float(pla), _ptr(pacc), _ptr(theta_out),
@@ -369,9 +368,7 @@ def train_rollouts(mat_pi0, T, episodes, first_episode, constant, theta, shift, 
     of episode k's update."""
     _chk_f32(mat_pi0, 'mat_pi0'); _chk_f64(theta, 'theta'); _chk_f64(w, 'w'); _chk_f64(G, 'G')
     B, d = bufs['pi_traj'].shape[0], mat_pi0.shape[1]
-    flags = L.ROLLOUT_DISCOUNT_POW if discount_pow else 0
-    if L.PRECISIONS[precision] == L.PRECISION_F64:
-        flags |= L.ROLLOUT_F64
+    flags = _rollout_flags(discount_pow, precision)
     L.check(L.lib().mfg_train_rollouts(mat_pi0.data_ptr(), mat_pi0.shape[0], B, d, int(T), int(episodes), int(first_episode),
                                        int(bool(constant)), theta.data_ptr(), float(shift), float(alpha_scale), w.data_ptr(),
                                        float(gamma), int(reward_kind), int(seed), int(first_step), int(traj_offset), flags,
@@ -391,9 +388,7 @@ def train_rollouts_dist(comm, mat_pi0, T, episodes, first_episode, constant, the
     _chk_f32(mat_pi0, 'mat_pi0'); _chk_f64(theta, 'theta'); _chk_f64(w, 'w'); _chk_f64(theta_alt, 'theta_alt'); _chk_f64(w_alt, 'w_alt')
     _chk_f64(G, 'G')
     B, d = bufs['pi_traj'].shape[0], mat_pi0.shape[1]
-    flags = L.ROLLOUT_DISCOUNT_POW if discount_pow else 0
-    if L.PRECISIONS[precision] == L.PRECISION_F64:
-        flags |= L.ROLLOUT_F64
+    flags = _rollout_flags(discount_pow, precision)
     L.check(L.lib().mfg_train_rollouts_dist(comm, mat_pi0.data_ptr(), mat_pi0.shape[0], B, d, int(T), int(episodes), int(first_episode),
                                             int(bool(constant)), theta.data_ptr(), w.data_ptr(), theta_alt.data_ptr(),
                                             w_alt.data_ptr(), float(shift), float(alpha_scale), float(gamma), int(reward_kind),
@@ -463,13 +458,29 @@ def train_episodes(mat_pi0, pi, T, episodes, first_episode, constant, theta, shi
     return pi
 
 
+def pop_workspace_slice(B, d, T):
+    """Bytes of ONE learner's workspace slice for every population flow (in-kernel and IRL rewards, step and rollout mode):
+    what the single-learner calls get for B T samples (ops.workspace), rounded up to 256."""
+    return (max(int(L.lib().mfg_workspace_bytes(B * T, d)), 8) + 255) // 256 * 256
+
+
+irl_pop_workspace_slice = pop_workspace_slice   # (its name in the IRL population calls' API)
+
+
 def _chk_pop(K, name, t, dtype):
     if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == dtype and t.is_contiguous() and t.numel() == K):
         raise ValueError('%s: expected a contiguous %s device tensor of %d entries (one per learner)' % (name, dtype, K))
 
 
-def _chk_pop_shapes(K, B, d, T, episodes, theta, w, G, ws, bufs, reward_acc, mat_pi0):
-    """Shapes of the learner-major arrays of a population call: an undersized one would be written past its end."""
+def _chk_pop_args(K, B, d, T, episodes, theta, w, G, ws, bufs, reward_acc, mat_pi0, shifts, alpha_scales, lr_critic, lr_actor,
+                  seeds, rn_seeds=None):
+    """The per-learner arrays [K] and the shapes of the learner-major arrays of a population training call: an undersized
+    one would be written past its end."""
+    for name, t in (('shifts', shifts), ('alpha_scales', alpha_scales), ('lr_critic', lr_critic), ('lr_actor', lr_actor)):
+        _chk_pop(K, name, t, torch.float64)
+    _chk_pop(K, 'seeds', seeds, torch.int64)
+    if rn_seeds is not None:
+        _chk_pop(K, 'rn_seeds', rn_seeds, torch.int64)
     F = num_features(d)
     want = dict(theta=(theta, (K,)), w=(w, (K, F)), G=(G, (K, F + 3)))
     for key, t in bufs.items():
@@ -502,10 +513,8 @@ def train_episodes_pop(mat_pi0, pi, T, episodes, first_episode, constant, theta,
     _chk_f32(mat_pi0, 'mat_pi0'); _chk_f32(pi, 'pi'); _chk_f64(theta, 'theta'); _chk_f64(w, 'w'); _chk_f64(G, 'G')
     K, B, d = pi.shape
     bufs = dict(bufs, pi=pi)
-    for name, t in (('shifts', shifts), ('alpha_scales', alpha_scales), ('lr_critic', lr_critic), ('lr_actor', lr_actor)):
-        _chk_pop(K, name, t, torch.float64)
-    _chk_pop(K, 'seeds', seeds, torch.int64)
-    _chk_pop_shapes(K, B, d, T, episodes, theta, w, G, ws, bufs, reward_acc, mat_pi0)
+    _chk_pop_args(K, B, d, T, episodes, theta, w, G, ws, bufs, reward_acc, mat_pi0, shifts, alpha_scales, lr_critic, lr_actor,
+                  seeds)
     L.check(L.lib().mfg_train_episodes_pop(mat_pi0.data_ptr(), mat_pi0.shape[0], pi.data_ptr(), bufs['scratch'].data_ptr(), B, K,
                                            d, int(T), int(episodes), int(first_episode), int(bool(constant)), theta.data_ptr(),
                                            shifts.data_ptr(), alpha_scales.data_ptr(), w.data_ptr(), float(gamma),
@@ -525,13 +534,9 @@ def train_rollouts_pop(mat_pi0, T, episodes, first_episode, constant, theta, shi
     for train_episodes_pop."""
     _chk_f32(mat_pi0, 'mat_pi0'); _chk_f64(theta, 'theta'); _chk_f64(w, 'w'); _chk_f64(G, 'G')
     K, B, d = bufs['pi_traj'].shape[0], bufs['pi_traj'].shape[1], mat_pi0.shape[1]
-    for name, t in (('shifts', shifts), ('alpha_scales', alpha_scales), ('lr_critic', lr_critic), ('lr_actor', lr_actor)):
-        _chk_pop(K, name, t, torch.float64)
-    _chk_pop(K, 'seeds', seeds, torch.int64)
-    _chk_pop_shapes(K, B, d, T, episodes, theta, w, G, ws, bufs, reward_acc, mat_pi0)
-    flags = L.ROLLOUT_DISCOUNT_POW if discount_pow else 0
-    if L.PRECISIONS[precision] == L.PRECISION_F64:
-        flags |= L.ROLLOUT_F64
+    _chk_pop_args(K, B, d, T, episodes, theta, w, G, ws, bufs, reward_acc, mat_pi0, shifts, alpha_scales, lr_critic, lr_actor,
+                  seeds)
+    flags = _rollout_flags(discount_pow, precision)
     L.check(L.lib().mfg_train_rollouts_pop(mat_pi0.data_ptr(), mat_pi0.shape[0], B, K, d, int(T), int(episodes),
                                            int(first_episode), int(bool(constant)), theta.data_ptr(), shifts.data_ptr(),
                                            alpha_scales.data_ptr(), w.data_ptr(), float(gamma), int(reward_kind),
@@ -595,9 +600,7 @@ def train_rollout_irl(mat_pi0, idx, T, theta, shift, alpha_scale, w, gamma, lr_c
     import ctypes as C
     _chk_f32(mat_pi0, 'mat_pi0'); _chk_f64(theta, 'theta'); _chk_f64(w, 'w'); _chk_f64(G, 'G')
     B, d = bufs['pi_traj'].shape[0], mat_pi0.shape[1]
-    flags = (L.ROLLOUT_DISCOUNT_POW if discount_pow else 0) | (L.TRAIN_APPLY if apply else 0)
-    if L.PRECISIONS[precision] == L.PRECISION_F64:
-        flags |= L.ROLLOUT_F64
+    flags = _rollout_flags(discount_pow, precision) | (L.TRAIN_APPLY if apply else 0)
     st = reward_net_struct(net)
     L.check(L.lib().mfg_train_rollout_irl(mat_pi0.data_ptr(), mat_pi0.shape[0], _ptr(idx), B, d, int(T), theta.data_ptr(),
                                           float(shift), float(alpha_scale), w.data_ptr(), float(gamma), int(seed), int(first_step),
@@ -637,21 +640,12 @@ def irl_pop_net_geometry(nets):
     return d, n3, n4, k0
 
 
-def irl_pop_workspace_slice(B, d, T):
-    """Bytes of ONE learner's workspace slice for both IRL population flows: what the single-learner IRL calls get for B T
-    samples (ops.workspace), rounded up to 256."""
-    return (max(int(L.lib().mfg_workspace_bytes(B * T, d)), 8) + 255) // 256 * 256
-
-
 def _chk_irl_pop(K, B, d, T, episodes, theta, w, G, ws, bufs, reward_acc, mat_pi0, per_learner, shifts, alpha_scales,
                  lr_critic, lr_actor, seeds, rn_seeds, net_struct):
     if not 1 <= K <= L.POP_MAX_K:
         raise ValueError('population size %d outside [1, %d]' % (K, L.POP_MAX_K))
-    for name, t in (('shifts', shifts), ('alpha_scales', alpha_scales), ('lr_critic', lr_critic), ('lr_actor', lr_actor)):
-        _chk_pop(K, name, t, torch.float64)
-    _chk_pop(K, 'seeds', seeds, torch.int64)
-    _chk_pop(K, 'rn_seeds', rn_seeds, torch.int64)
-    _chk_pop_shapes(K, B, d, T, episodes, theta, w, G, ws, bufs, reward_acc, mat_pi0)
+    _chk_pop_args(K, B, d, T, episodes, theta, w, G, ws, bufs, reward_acc, mat_pi0, shifts, alpha_scales, lr_critic, lr_actor,
+                  seeds, rn_seeds)
     if d not in IRL_POP_D:
         raise ValueError('d=%d: IRL populations cover d = 15 / 21 (the matrix-core reward-network kernel)' % d)
     if net_struct.n3 > IRL_POP_MAX_FC3:
@@ -712,9 +706,7 @@ def train_rollouts_irl_pop(mat_pi0, T, episodes, first_episode, constant, theta,
                  alpha_scales, lr_critic, lr_actor, seeds, rn_seeds, net_struct)
     if tuple(P.shape) != (K, B, T, d, d) or not P.is_contiguous() or not P.is_cuda or P.dtype != torch.float32:
         raise ValueError('P: expected a contiguous f32 device tensor [%d, %d, %d, %d, %d]' % (K, B, T, d, d))
-    flags = L.ROLLOUT_DISCOUNT_POW if discount_pow else 0
-    if L.PRECISIONS[precision] == L.PRECISION_F64:
-        flags |= L.ROLLOUT_F64
+    flags = _rollout_flags(discount_pow, precision)
     head = (mat_pi0.data_ptr(), mat_pi0.shape[0], B, K, d, int(T), int(episodes), int(first_episode), int(bool(constant)),
             theta.data_ptr(), shifts.data_ptr(), alpha_scales.data_ptr(), w.data_ptr(), float(gamma), seeds.data_ptr(),
             int(first_step), int(traj_offset), flags, lr_critic.data_ptr(), lr_actor.data_ptr(), C.byref(net_struct),

@@ -204,23 +204,23 @@ def _with_ctx(method):
     return bound
 
 
-class ActorCriticPopulation:
+class _Population:
+    """What ActorCriticPopulation and AC_IRLPopulation share: the K learners' theta, w, shifts, alpha_scales and seeds (host
+    and device copies), the start-state table, the Philox step counter and the instance's own ops.Context.  Subclasses say
+    whether their buffers hold the actions P (_WITH_P) and build their learner's single-learner object (_new_learner)."""
+    _WITH_P = False
 
-    def __init__(self, thetas, shifts=0.16, alpha_scales=12000, d=21, *, batch, seeds=None, w0=None, pi0=None,
-                 path_to_dir=None, update_every='step', reward='mfg_ac2', precision='mixed', episode_steps=EPISODE_STEPS,
-                 device=None, verbose=0):
-        th = np.asarray(thetas, dtype=np.float64).reshape(-1)
+    def __init__(self, th, d, batch, episode_steps, shifts, alpha_scales, seeds, w0, pi0, path_to_dir, update_every, precision,
+                 device, verbose):
         K = th.shape[0]
-        check_args(K, int(d), int(batch), update_every, reward, precision, int(episode_steps))
         if not torch.cuda.is_available():
-            raise L.MfgError('ActorCriticPopulation needs a ROCm GPU: the HIP hot path has no CPU fallback')
+            raise L.MfgError('%s needs a ROCm GPU: the HIP hot path has no CPU fallback' % type(self).__name__)
         L.lib()
         ops.init()
         self.device = torch.device(device) if device is not None else torch.device('cuda', torch.cuda.current_device())
         self._ctx = ops.Context(self.device)
         self.d, self.batch, self.episode_steps = int(d), int(batch), int(episode_steps)
-        self.update_every, self.reward, self.precision, self.verbose = update_every, reward, precision, verbose
-        self.reward_kind = REWARDS[reward]
+        self.update_every, self.precision, self.verbose = update_every, precision, verbose
         F = ops.num_features(self.d)
         self.shifts = broadcast('shifts', shifts, K)
         self.alpha_scales = broadcast('alpha_scales', alpha_scales, K)
@@ -233,11 +233,10 @@ class ActorCriticPopulation:
         else:
             w = np.asarray(w0, dtype=np.float64)
             w = np.broadcast_to(w.reshape(1, -1), (K, F)) if w.size == F else w.reshape(K, F)
-        self._w = torch.as_tensor(np.ascontiguousarray(w), device=dev)
+        self._w = torch.as_tensor(np.array(w, dtype=np.float64, order='C'), device=dev)   # (a C-ordered copy of a broadcast view)
         # the start-state table, resolved as actor_critic resolves it, shared by all learners
-        table = resolve_start_table(self.d, pi0, path_to_dir)
-        self.mat_pi0 = table
-        self._mat_pi0_dev = torch.as_tensor(np.ascontiguousarray(table, dtype=np.float32), device=dev)
+        self.mat_pi0 = resolve_start_table(self.d, pi0, path_to_dir)
+        self._mat_pi0_dev = torch.as_tensor(np.ascontiguousarray(self.mat_pi0, dtype=np.float32), device=dev)
         self._seeds_dev = torch.as_tensor(self.seeds.view(np.int64), device=dev)
         self._shifts_dev = torch.as_tensor(self.shifts, device=dev)
         self._alphas_dev = torch.as_tensor(self.alpha_scales, device=dev)
@@ -261,53 +260,41 @@ class ActorCriticPopulation:
         K, B, d, T = self.K, self.batch, self.d, self.episode_steps
         if self._bufs is None:
             dev, F = self.device, ops.num_features(d)
-            # one learner's workspace slice: what actor_critic allocates for B T samples, rounded up to 256 bytes
-            sb = (max(int(L.lib().mfg_workspace_bytes(B * T, d)), 8) + 255) // 256 * 256
             b = {'G': torch.zeros(K, F + 3, dtype=torch.float64, device=dev),
-                 'ws': torch.zeros(K, sb // 8, dtype=torch.float64, device=dev)}
-            if self.update_every == 'step':
+                 'ws': torch.zeros(K, ops.pop_workspace_slice(B, d, T) // 8, dtype=torch.float64, device=dev)}
+            step = self.update_every == 'step'
+            n = (K, B) if step else (K, B, T)      # reward / delta / g: one entry per env step of a learner
+            if step:
                 b['pi'] = torch.empty(K, B, d, dtype=torch.float32, device=dev)
-                b['run'] = {'scratch': torch.empty(K, B, d, dtype=torch.float32, device=dev),
-                            'reward': torch.empty(K, B, dtype=torch.float32, device=dev),
-                            'delta': torch.empty(K, B, dtype=torch.float64, device=dev),
-                            'g': torch.empty(K, B, dtype=torch.float64, device=dev)}
+                run = {'scratch': torch.empty(K, B, d, dtype=torch.float32, device=dev)}
             else:
-                b['run'] = {'pi_traj': torch.empty(K, B, T + 1, d, dtype=torch.float32, device=dev),
-                            'pi_last': torch.empty(K, B, d, dtype=torch.float32, device=dev),
-                            'reward': torch.empty(K, B, T, dtype=torch.float32, device=dev),
-                            'delta': torch.empty(K, B, T, dtype=torch.float64, device=dev),
-                            'g': torch.empty(K, B, T, dtype=torch.float64, device=dev)}
+                run = {'pi_traj': torch.empty(K, B, T + 1, d, dtype=torch.float32, device=dev),
+                       'pi_last': torch.empty(K, B, d, dtype=torch.float32, device=dev)}
+            if self._WITH_P:
+                run['P'] = torch.empty(*n, d, d, dtype=torch.float32, device=dev)
+            run.update(reward=torch.empty(*n, dtype=torch.float32, device=dev),
+                       delta=torch.empty(*n, dtype=torch.float64, device=dev),
+                       g=torch.empty(*n, dtype=torch.float64, device=dev))
+            b['run'] = run
             self._bufs = b
         return self._bufs
 
     # ------------------------------------------------------------------ training
-    @_with_ctx
-    def train(self, num_episodes, gamma=1, constant=0, lr_critic=0.1, lr_actor=0.001, *, first_episode=0):
-        """`num_episodes` episodes of every learner (mfg_ac2.py:448-539; update per env step or per episode as chosen at
-        construction).  lr_critic / lr_actor: scalars or [K].  Returns a NumPy array [K, num_episodes] of what
-        actor_critic.train books per episode (step mode: the sum of the T updates' mean rewards; rollout mode: the one
-        update's mean reward).  The Philox step counter carries over to the next call."""
-        K, T = self.K, self.episode_steps
+    def _train(self, num_episodes, lr_critic, lr_actor, run):
+        """The frame of train(): checks, learning rates as device arrays [K], run(buffers, lrc, lra, acc) -- the native calls
+        -- and the Philox step; returns acc [K, num_episodes] as a NumPy array.  MfgError when a mixed-precision launch left the
+        fp32 range."""
+        K = self.K
         num_episodes = int(num_episodes)
         if num_episodes < 0:
             raise ValueError('num_episodes < 0')
         lrc = torch.as_tensor(broadcast('lr_critic', lr_critic, K), device=self.device)
         lra = torch.as_tensor(broadcast('lr_actor', lr_actor, K), device=self.device)
-        acc = torch.zeros(K, max(num_episodes, 1), dtype=torch.float64, device=self.device)
         if num_episodes == 0:
             return np.zeros((K, 0))
-        b = self._buffers()
-        if self.update_every == 'step':
-            ops.train_episodes_pop(self._mat_pi0_dev, b['pi'], T, num_episodes, first_episode, constant == 1, self._theta,
-                                   self._shifts_dev, self._alphas_dev, self._w, gamma, lrc, lra, self._seeds_dev, b['G'],
-                                   b['ws'], b['run'], reward_kind=self.reward_kind, first_step=self._rng_step,
-                                   reward_acc=acc, precision=self.precision)
-        else:
-            ops.train_rollouts_pop(self._mat_pi0_dev, T, num_episodes, first_episode, constant == 1, self._theta,
-                                   self._shifts_dev, self._alphas_dev, self._w, gamma, b['G'], b['ws'], b['run'], lrc, lra,
-                                   self._seeds_dev, reward_kind=self.reward_kind, first_step=self._rng_step,
-                                   reward_acc=acc, precision=self.precision)
-        self._rng_step += num_episodes * T
+        acc = torch.zeros(K, num_episodes, dtype=torch.float64, device=self.device)
+        run(self._buffers(), lrc, lra, acc)
+        self._rng_step += num_episodes * self.episode_steps
         out = acc.cpu().numpy()
         if self.precision == 'mixed' and self._ctx.status(synchronize=True):
             raise L.MfgError('a mixed-precision sampling launch of this population ran with |theta| (1/2 + |shift|) > 86 '
@@ -321,6 +308,74 @@ class ActorCriticPopulation:
     def clear_status(self):
         self._ctx.clear_status()
 
+    def _evaluate(self, episode_length, indir, outfile, write_header, repeats):
+        """The body of evaluate() (the population's context bound)."""
+        if int(repeats) < 1:
+            raise ValueError('repeats=%d: at least one rollout per test file' % repeats)
+        emp = load_empirical(indir, self.d, int(episode_length))
+        first_step = self._rng_step
+        self._rng_step += int(episode_length) - 1    # (a diverged launch has run: its step is spent, as in train())
+        try:
+            table = evaluate_policies(emp, self._theta, self._shifts_dev, self._alphas_dev, self._seeds_dev, first_step,
+                                      int(repeats), self.precision, self.device, self._ctx)
+        except L.MfgError as e:
+            if e.code:                               # refused by the library before anything was launched
+                self._rng_step = first_step
+            raise
+        thetas = self.thetas
+        write_eval_rows(outfile, write_header, [(float(thetas[k]), float(self.shifts[k]), float(self.alpha_scales[k]))
+                                                for k in range(self.K)], table)
+        return table[:, 0::2].copy()
+
+    def learner(self, k):
+        """An actor_critic holding learner k's parameters, table and Philox position (for evaluate / generate_trajectory
+        / further single training).  Its construction leaves the global np.random stream as it was."""
+        if not 0 <= k < self.K:
+            raise IndexError('learner %d of %d' % (k, self.K))
+        state = np.random.get_state()
+        try:
+            ac = self._new_learner(k)
+        finally:
+            np.random.set_state(state)
+        ac.w = self.w[k]
+        ac.theta = np.array([self.thetas[k]]) if self._rng_step else float(self.thetas[k])
+        ac._rng_step = self._rng_step
+        return ac
+
+
+class ActorCriticPopulation(_Population):
+
+    def __init__(self, thetas, shifts=0.16, alpha_scales=12000, d=21, *, batch, seeds=None, w0=None, pi0=None,
+                 path_to_dir=None, update_every='step', reward='mfg_ac2', precision='mixed', episode_steps=EPISODE_STEPS,
+                 device=None, verbose=0):
+        th = np.asarray(thetas, dtype=np.float64).reshape(-1)
+        check_args(th.shape[0], int(d), int(batch), update_every, reward, precision, int(episode_steps))
+        super().__init__(th, d, batch, episode_steps, shifts, alpha_scales, seeds, w0, pi0, path_to_dir, update_every,
+                         precision, device, verbose)
+        self.reward = reward
+        self.reward_kind = REWARDS[reward]
+
+    @_with_ctx
+    def train(self, num_episodes, gamma=1, constant=0, lr_critic=0.1, lr_actor=0.001, *, first_episode=0):
+        """`num_episodes` episodes of every learner (mfg_ac2.py:448-539; update per env step or per episode as chosen at
+        construction).  lr_critic / lr_actor: scalars or [K].  Returns a NumPy array [K, num_episodes] of what
+        actor_critic.train books per episode (step mode: the sum of the T updates' mean rewards; rollout mode: the one
+        update's mean reward).  The Philox step counter carries over to the next call."""
+        T = self.episode_steps
+
+        def run(b, lrc, lra, acc):
+            if self.update_every == 'step':
+                ops.train_episodes_pop(self._mat_pi0_dev, b['pi'], T, int(num_episodes), first_episode, constant == 1,
+                                       self._theta, self._shifts_dev, self._alphas_dev, self._w, gamma, lrc, lra,
+                                       self._seeds_dev, b['G'], b['ws'], b['run'], reward_kind=self.reward_kind,
+                                       first_step=self._rng_step, reward_acc=acc, precision=self.precision)
+            else:
+                ops.train_rollouts_pop(self._mat_pi0_dev, T, int(num_episodes), first_episode, constant == 1, self._theta,
+                                       self._shifts_dev, self._alphas_dev, self._w, gamma, b['G'], b['ws'], b['run'], lrc, lra,
+                                       self._seeds_dev, reward_kind=self.reward_kind, first_step=self._rng_step,
+                                       reward_acc=acc, precision=self.precision)
+        return self._train(num_episodes, lr_critic, lr_actor, run)
+
     @_with_ctx
     def evaluate(self, episode_length=16, indir='test_normalized_round2', outfile='eval_mfg_round2/test_eval_fixed_reward.csv',
                  write_header=0, *, repeats=1):
@@ -330,42 +385,10 @@ class ActorCriticPopulation:
         Philox step by episode_length - 1, as each learner's own evaluate() would.  With repeats=1 learner k gets what
         learner(k).evaluate(thetas[k], shifts[k], alpha_scales[k], d, episode_length, ...) gives; repeats = R rolls R
         trajectories per test file.  MfgError (and no CSV line) when a mixed-precision policy left the fp32 range."""
-        return evaluate_population(self, episode_length, indir, outfile, write_header, repeats)
+        return self._evaluate(episode_length, indir, outfile, write_header, repeats)
 
-    def learner(self, k):
-        """An actor_critic holding learner k's parameters, table and Philox position (for evaluate / generate_trajectory
-        / further single training).  Its construction leaves the global np.random stream as it was."""
-        if not 0 <= k < self.K:
-            raise IndexError('learner %d of %d' % (k, self.K))
-        state = np.random.get_state()
-        try:
-            ac = actor_critic(float(self.thetas[k]), float(self.shifts[k]), float(self.alpha_scales[k]), self.d,
-                              pi0=self.mat_pi0, batch=self.batch, seed=int(self.seeds[k]), update_every=self.update_every,
-                              reward=self.reward, precision=self.precision, device=self.device, verbose=self.verbose,
-                              episode_steps=self.episode_steps)
-        finally:
-            np.random.set_state(state)
-        ac.w = self.w[k]
-        ac.theta = np.array([self.thetas[k]]) if self._rng_step else float(self.thetas[k])
-        ac._rng_step = self._rng_step
-        return ac
-
-
-def evaluate_population(pop, episode_length, indir, outfile, write_header, repeats):
-    """The body of ActorCriticPopulation.evaluate and AC_IRLPopulation.evaluate (the population's context bound)."""
-    if int(repeats) < 1:
-        raise ValueError('repeats=%d: at least one rollout per test file' % repeats)
-    emp = load_empirical(indir, pop.d, int(episode_length))
-    first_step = pop._rng_step
-    pop._rng_step += int(episode_length) - 1     # (a diverged launch has run: its step is spent, as in train())
-    try:
-        table = evaluate_policies(emp, pop._theta, pop._shifts_dev, pop._alphas_dev, pop._seeds_dev, first_step, int(repeats),
-                                  pop.precision, pop.device, pop._ctx)
-    except L.MfgError as e:
-        if e.code:                               # refused by the library before anything was launched
-            pop._rng_step = first_step
-        raise
-    thetas = pop.thetas
-    write_eval_rows(outfile, write_header, [(float(thetas[k]), float(pop.shifts[k]), float(pop.alpha_scales[k]))
-                                            for k in range(pop.K)], table)
-    return table[:, 0::2].copy()
+    def _new_learner(self, k):
+        return actor_critic(float(self.thetas[k]), float(self.shifts[k]), float(self.alpha_scales[k]), self.d,
+                            pi0=self.mat_pi0, batch=self.batch, seed=int(self.seeds[k]), update_every=self.update_every,
+                            reward=self.reward, precision=self.precision, device=self.device, verbose=self.verbose,
+                            episode_steps=self.episode_steps)
