@@ -16,10 +16,28 @@ constexpr double LN2 = 0.6931471805599453, INV_LN2 = 1.4426950408889634;
 // Philox4x32-10 (Salmon et al., SC'11).  Counter layout used by every sampler:
 //   c0 = element index i*d + j, c1 = env step, c2 = low 32 bits of the global trajectory id,
 //   c3 = (high 16 bits of the trajectory id) | (draw block << 16); key = 64-bit seed.
+// Cost on gfx950: a full block is 20 v_mad_u64_u32 + 20 v_bitop3_b32 (xor3 below); in the quad loops, where the first rounds
+// are partly loop invariant, 18 + 19 (+ 1 add for the element id) per quad (profiles/bitop3_loop_table_d21.txt).
 // ---------------------------------------------------------------------------
 struct u32x4 {
   uint32_t x, y, z, w;
 };
+
+// a ^ b ^ c.  Each round ends in two of these (mulhi ^ counter word ^ round key).  gfx950 has v_bitop3_b32, any boolean
+// function of three inputs in one VOP3 instruction (truth table 0x96 = three-way xor; the round key stays in its SGPR); the
+// compiler does not form it from the expression, so the device side asks for it.  Host code and targets without the builtin
+// keep the two xors: same bits either way.
+__host__ __device__ __forceinline__ uint32_t xor3(uint32_t a, uint32_t b, uint32_t c) {
+#if defined(__HIP_DEVICE_COMPILE__) && defined(__has_builtin)
+#if __has_builtin(__builtin_amdgcn_bitop3_b32)
+  return __builtin_amdgcn_bitop3_b32(a, b, c, 0x96);
+#else
+  return a ^ b ^ c;
+#endif
+#else
+  return a ^ b ^ c;
+#endif
+}
 
 __host__ __device__ __forceinline__ u32x4 philox4x32_10(u32x4 c, uint32_t k0, uint32_t k1) {
   constexpr uint32_t M0 = 0xD2511F53u, M1 = 0xCD9E8D57u, W0 = 0x9E3779B9u, W1 = 0xBB67AE85u;
@@ -28,9 +46,9 @@ __host__ __device__ __forceinline__ u32x4 philox4x32_10(u32x4 c, uint32_t k0, ui
     const uint64_t p0 = (uint64_t)M0 * c.x;
     const uint64_t p1 = (uint64_t)M1 * c.z;
     u32x4 n;
-    n.x = (uint32_t)(p1 >> 32) ^ c.y ^ k0;
+    n.x = xor3((uint32_t)(p1 >> 32), c.y, k0);
     n.y = (uint32_t)p1;
-    n.z = (uint32_t)(p0 >> 32) ^ c.w ^ k1;
+    n.z = xor3((uint32_t)(p0 >> 32), c.w, k1);
     n.w = (uint32_t)p0;
     c = n;
     k0 += W0;

@@ -11,6 +11,7 @@ clang-offload-bundler --unbundle of each bundle's gfx950 code object, llvm-objdu
 Exit status 0 when every kernel of A is identical in B (kernels only in B are listed, not counted as differences).
 """
 import argparse
+import collections
 import os
 import re
 import subprocess
@@ -111,6 +112,10 @@ def main():
     ap.add_argument('a', help='build A: libmfg_hip.so (e.g. the parent commit)')
     ap.add_argument('b', help='build B: libmfg_hip.so')
     ap.add_argument('--verbose', action='store_true', help='list identical kernels too')
+    ap.add_argument('--histogram', action='append', default=[], metavar='SYMBOL',
+                    help='also print the opcode histogram (A, B) of this mangled kernel symbol; may be repeated')
+    ap.add_argument('--resources', metavar='SUBSTRING', default=None,
+                    help='also print registers / scratch (A -> B) of every kernel whose symbol contains SUBSTRING')
     args = ap.parse_args()
     with tempfile.TemporaryDirectory() as tmp:
         isa_a, meta_a = kernels(args.a, tmp, 'a')
@@ -139,6 +144,20 @@ def main():
     only_b = sorted(set(isa_b) - set(isa_a))
     for name in only_b:
         print('new   %s' % name)
+    for sym in args.histogram:
+        ha, hb = (collections.Counter(i.split()[0] for i in isa.get(sym, [])) for isa in (isa_a, isa_b))
+        print('\nopcode histogram of %s: %d -> %d instructions, .vgpr_count %s -> %s, .private_segment_fixed_size %s -> %s' % (
+            sym, sum(ha.values()), sum(hb.values()), meta_a.get(sym, {}).get('.vgpr_count'), meta_b.get(sym, {}).get('.vgpr_count'),
+            meta_a.get(sym, {}).get('.private_segment_fixed_size'), meta_b.get(sym, {}).get('.private_segment_fixed_size')))
+        for op in sorted(set(ha) | set(hb), key=lambda o: -max(ha[o], hb[o])):
+            if ha[op] != hb[op] or max(ha[op], hb[op]) >= 40:
+                print('  %-28s %6d %6d  %+d' % (op, ha[op], hb[op], hb[op] - ha[op]))
+    if args.resources:
+        print('\nregisters / scratch of the kernels matching %r (A -> B; * = rises)' % args.resources)
+        for name in sorted(n for n in isa_a if args.resources in n and n in isa_b):
+            va, vb = (int(m.get(name, {}).get('.vgpr_count', 0)) for m in (meta_a, meta_b))
+            sa, sb = (int(m.get(name, {}).get('.private_segment_fixed_size', 0)) for m in (meta_a, meta_b))
+            print('  %-78s vgpr %3d -> %3d%s  scratch %4d -> %4d%s' % (name, va, vb, ' *' if vb > va else '  ', sa, sb, ' *' if sb > sa else ''))
     print('%d kernels of A: %d identical, %d differ; %d kernels only in B' % (len(isa_a), same, len(diff), len(only_b)))
     return 1 if diff else 0
 

@@ -12,13 +12,13 @@ import collections, os, re, subprocess, sys, tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, 'discrete_mean_field_game_amd', 'csrc')
-KERNEL = '_ZN3mfg12k_core_smallILb1ELb1ELb1ELi21ELb0EEEvNS_8CoreArgsE'
+KERNEL = '_ZN3mfg12k_core_smallILb1ELb1ELb1ELi21ELb0ELi0EEEvNS_8CoreArgsE'
 COST = {'mad64': 6.4, 'trans': 8.0, 'f64': 4.6, 'plain': 2.2}          # cycles per wave64 instruction (profiles/r03_valu_rates.txt)
 
 # piece -> opcode multiset PER QUAD (4 matrix elements per lane)
 LEDGER = collections.OrderedDict([
-    ('Philox4x32-10 block (one per quad; rounds 1-2 partly loop invariant) + element id',
-     {'v_mad_u64_u32': 18, 'v_xor_b32': 34, 'v_add_u32': 1}),
+    ('Philox4x32-10 block (one per quad; rounds 1-2 partly loop invariant; one v_bitop3_b32 per round word) + element id',
+     {'v_mad_u64_u32': 18, 'v_bitop3_b32': 19, 'v_add_u32': 1}),
     ('fields of the block: 2 radius uniforms (shift, convert, fma), 2 angles (half-word convert, fma), 4 acceptance integers',
      {'v_lshrrev_b32': 2, 'v_cvt_f32_u32': 8, 'v_fmamk_f32': 4, 'v_and_b32': 2}),
     ('Box-Muller, two pairs: log2 u, sqrt(-.) (the factor 2 ln 2 is folded into c and the squeeze slope); sin, cos; 4 products',

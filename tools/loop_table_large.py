@@ -17,7 +17,7 @@ COST = {'mad64': 6.4, 'trans': 8.0, 'f64': 4.6, 'plain': 2.2}          # cycles 
 
 QUAD = collections.OrderedDict([    # the sampling of one quad: the pieces of tools/loop_table.py, same opcodes
     ('Philox4x32-10 block (one per quad; rounds 1-2 partly loop invariant) + element ids',
-     {'v_mad_u64_u32': 18, 'v_xor_b32': 34}),
+     {'v_mad_u64_u32': 18, 'v_bitop3_b32': 19}),
     ('fields of the block: 2 radius uniforms, 2 angles, 4 acceptance integers',
      {'v_lshrrev_b32': 2, 'v_cvt_f32_u32': 8, 'v_fmamk_f32': 4, 'v_and_b32': 2}),
     ('Box-Muller, two pairs: log2 u, sqrt, sin, cos, 4 products',

@@ -39,6 +39,44 @@ OP_KERNEL(k_sin_f32, float, seed + 0.01f * (float)(threadIdx.x + c), x = __built
 OP_KERNEL(k_cvt_f64_f32, double, seed + (double)(threadIdx.x + c), x = (double)((float)x) + 1.0)
 OP_KERNEL(k_rcp_f64, double, seed + 2.0 + (double)(threadIdx.x + c), x = __builtin_amdgcn_rcp(x) + 1.0)
 
+// Three-way xor with the third operand in an SGPR (seed is a kernel argument), as at the end of a Philox round: one
+// v_bitop3_b32 (truth table 0x96) against the two v_xor_b32 the compiler makes of a ^ b ^ c.  Both forms get the same glue
+// (a rotate: one v_alignbit_b32) so that neither folds across iterations.  INDEP: CHAINS chains, each reading its
+// neighbour's value as the second operand; DEP: one serial chain, every instruction waits for the one before it.
+template <bool BITOP3>
+__device__ __forceinline__ uint32_t xor3_form(uint32_t a, uint32_t b, uint32_t c) {
+  if constexpr (BITOP3) return __builtin_amdgcn_bitop3_b32(a, b, c, 0x96);
+  return a ^ b ^ c;
+}
+__device__ __forceinline__ uint32_t rotl7(uint32_t x) { return __builtin_amdgcn_alignbit(x, x, 25); }
+template <bool BITOP3>
+__global__ __launch_bounds__(256) void k_xor3_indep(uint32_t* out, uint32_t seed) {
+  uint32_t v[CHAINS];
+#pragma unroll
+  for (int c = 0; c < CHAINS; ++c) v[c] = seed + threadIdx.x * 0x9E3779B9u + c;
+  for (int it = 0; it < ITERS; ++it) {
+#pragma unroll
+    for (int c = 0; c < CHAINS; ++c) v[c] = rotl7(xor3_form<BITOP3>(v[c], v[(c + 1) % CHAINS], seed));
+  }
+  uint32_t s = v[0];
+#pragma unroll
+  for (int c = 1; c < CHAINS; ++c) s += v[c];
+  out[blockIdx.x * blockDim.x + threadIdx.x] = s;
+}
+template <bool BITOP3>
+__global__ __launch_bounds__(256) void k_xor3_dep(uint32_t* out, uint32_t seed) {
+  uint32_t x = seed + threadIdx.x * 0x9E3779B9u, y = x * 0xBB67AE85u + 1u;
+  const uint32_t seed2 = seed * 0xCD9E8D57u;  // a second SGPR: with one key, y ^ seed would be shared by both lines of the body
+  for (int it = 0; it < ITERS; ++it) {
+#pragma unroll
+    for (int c = 0; c < CHAINS / 2; ++c) {  // CHAINS bodies per iteration, like the other rows
+      x = rotl7(xor3_form<BITOP3>(x, y, seed));
+      y = rotl7(xor3_form<BITOP3>(y, x, seed2));
+    }
+  }
+  out[blockIdx.x * blockDim.x + threadIdx.x] = x + y;
+}
+
 typedef float v2f __attribute__((ext_vector_type(2)));
 __global__ __launch_bounds__(256) void k_pk_fma_f32(float* out, float seed) {
   v2f v[CHAINS];
@@ -100,6 +138,12 @@ int main() {
   run<float>("v_sin_f32+add", k_sin_f32, 2, buf, 0.5f, ghz, cus);
   run<double>("cvt f64<->f32+add", k_cvt_f64_f32, 3, buf, 1.0, ghz, cus);
   run<double>("v_rcp_f64+add", k_rcp_f64, 2, buf, 1.0, ghz, cus);
+  for (int wps : {3, 8}) {
+    run<uint32_t>("2 v_xor+rot indep", k_xor3_indep<false>, 3, buf, 1u, ghz, cus, wps);
+    run<uint32_t>("v_bitop3+rot indep", k_xor3_indep<true>, 2, buf, 1u, ghz, cus, wps);
+    run<uint32_t>("2 v_xor+rot dep", k_xor3_dep<false>, 3, buf, 1u, ghz, cus, wps);
+    run<uint32_t>("v_bitop3+rot dep", k_xor3_dep<true>, 2, buf, 1u, ghz, cus, wps);
+  }
   for (int wps : {1, 2, 3, 4, 6}) {
     run<float>("v_fma_f32", k_fma_f32, 1, buf, 1.0f, ghz, cus, wps);
     run<uint32_t>("v_xor+add", k_xor_u32, 2, buf, 1u, ghz, cus, wps);
