@@ -137,12 +137,15 @@ struct RnSums {
 };
 // true: a reward_net_forward_sums call of this shape runs the matrix-core SUMS kernel with the TD error formed in the kernel
 // (d = 21 / 15 at the reference's layer geometry, n_fc3 <= 16, aligned FC3 weights, one row per block fits max_rows)
-bool reward_net_sums_td_ready(int64_t B, int d, int k1, int f2, int k2, int n3, int n4, const float* fc3_w, int64_t max_rows);
-int reward_net_forward_sums(const float* state, const float* action, int64_t B, int d, int k1, int f2, int k2, int n3, int n4,
-                            const float* conv1_w, const float* conv1_b, const float* conv2_w, const float* conv2_b,
-                            const float* fc3_w, const float* fc3_b, const float* fc4_w, const float* fc4_b,
-                            const float* out_w, const float* out_b, float keep_prob, uint64_t seed, uint64_t sample_offset,
-                            float* reward, const RnSums* sums, int* rows_out, mfg_stream_t stream, int state_T = 0);
+bool reward_net_sums_td_ready(int64_t B, int d, const mfg_reward_net_t& net, int64_t max_rows);
+// the reward network over B samples.  sums != NULL: ask for the SUMS variant; *rows_out = partial rows written (0: this shape
+// has no SUMS kernel -- the plain forward ran and the caller takes the separate gradient kernel).  state_T > 0: the states are
+// read in place from a rollout's pi_traj (rows b (state_T + 1) + t).  pop != NULL: the network of K learners in one launch
+// (mfg_irl_population.h; the keys come from `pop`): the matrix-core kernel only, no room for the rows is an error
+struct RnPop;
+int reward_net_forward_sums(const float* state, const float* action, int64_t B, int d, const mfg_reward_net_t& net, uint64_t key,
+                            uint64_t sample_offset, float* reward, const RnSums* sums, int* rows_out, hipStream_t st,
+                            int state_T = 0, const RnPop* pop = nullptr);
 
 // launchers defined in mfg_core_small.hip / mfg_core_large_*.hip; return 0 or MFG_EUNSUPPORTED
 int launch_core_small(const CoreArgs& a, bool sample, bool td, bool fast, int num_cus, hipStream_t st);

@@ -1,8 +1,8 @@
 // IRL populations (mfg_train_episodes_irl_pop / mfg_train_rollouts_irl_pop): K independent forward learners of AC_IRL.train served
 // by every launch of an episode, as mfg_population.h describes.  The core kernel and the closing row reduction are the population
-// kernels of mfg_population.hip; this header declares the reward network's population form (k_reward_net_mfma_pop,
-// mfg_reward_net.hip): grid (the single call's grid for Bk, K), learner = blockIdx.y, plain over a rollout's pi_traj or SUMS with
-// the TD error.
+// kernels of mfg_population.hip; this header declares the argument block of the reward network's population form
+// (k_reward_net_mfma_pop, mfg_reward_net.hip, launched by reward_net_forward_sums with an RnPop): grid (the single call's grid for
+// Bk, K), learner = blockIdx.y, plain over a rollout's pi_traj or SUMS with the TD error.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -34,10 +34,5 @@ struct RnPop {
 // true: K learners' networks of this geometry (fc3_w of every learner 8-byte aligned) run the matrix-core kernel
 // (net_stride > 0: learner k's tensors at base + k net_stride; 0: the numel_t strides)
 bool reward_net_pop_ready(int d, const mfg_reward_net_t* net, int per_learner_net, int K, int64_t net_stride = 0);
-// the population form of reward_net_forward_sums for the matrix-core kernel (reward_net_pop_ready said yes); sums: the SUMS
-// variant with the TD error (*rows_out = partial rows per learner), NULL: the plain forward
-int reward_net_forward_pop(const float* state, const float* action, int64_t B, int d, const mfg_reward_net_t* net,
-                           uint64_t sample_offset, float* reward, const RnSums* sums, int* rows_out, const RnPop& p, hipStream_t st,
-                           int state_T);
 
 }  // namespace mfg

@@ -1609,6 +1609,12 @@ struct ApplyArgs {
   double lr_c, lr_a;
   double *w, *theta, *reward_acc;
 };
+// the update as a launch of its own (where no kernel applied it while it formed G)
+static void launch_apply_update(const double* G, int d, double lr_c, double lr_a, double* w, double* theta, double* reward_acc,
+                                hipStream_t st) {
+  const int64_t F = mfg_num_features(d);
+  hipLaunchKernelGGL(k_apply_update, dim3((unsigned)((F + 255) / 256)), dim3(256), 0, st, G, F, lr_c, lr_a, w, theta, reward_acc);
+}
 
 // Large-d rollouts evaluate the critic values of all states in one matrix-core pass after the rollout (k_value_mfma): room
 // for V[B (T+1)] <= 2 N doubles behind the partial rows of the gradient sums.
@@ -2486,9 +2492,7 @@ int mfg_td_pg_accumulate(const float* pi, const float* pi_next, const float* P, 
 int mfg_apply_update(const double* G, int d, double lr_critic, double lr_actor, double* w, double* theta,
                      double* reward_acc, mfg_stream_t stream) {
   REQUIRE(G && w && theta && d >= 1, "null pointer");
-  const int64_t F = mfg_num_features(d);
-  hipLaunchKernelGGL(k_apply_update, dim3((unsigned)((F + 255) / 256)), dim3(256), 0, S(stream), G, F, lr_critic,
-                     lr_actor, w, theta, reward_acc);
+  launch_apply_update(G, d, lr_critic, lr_actor, w, theta, reward_acc, S(stream));
   return check_launch("apply_update");
 }
 
@@ -2602,14 +2606,25 @@ struct DeferredUpdate {
   double *theta_out, *w_out;
 };
 
+// the external reward of an IRL rollout (reward_kind = MFG_REWARD_EXTERNAL): the core launch also writes the actions P and
+// leaves delta = discount V(pi') - V(pi); ONE reward-network pass over all B T transitions follows, the states read in place
+// from pi_traj (rows b (T+1) + t), and the reward joins delta in the gradient kernel
+struct ExtReward {
+  const mfg_reward_net_t* net;
+  float* P;
+  uint64_t key, sample_offset;  // dropout: Philox key (population: per learner, from `pop`) and first sample counter
+  const RnPop* pop;
+};
+
 // one training update per episode: [rollout kernel (start rows: drawn in the kernel when idx == NULL, else gathered) |
-// values + delta (large d) | batch sums | row reduction (+ update)]
+// reward network (ext) | values + delta (large d) | batch sums | row reduction (+ update)]
 static int train_rollout_impl(const float* mat_pi0, int64_t num_start, const int32_t* idx, int64_t B, int d, int T, double* theta,
                               double shift, double alpha_scale, double* w, double gamma, int reward_kind, uint64_t seed,
                               uint32_t first_step, uint64_t traj_offset, int flags, double lr_critic, double lr_actor,
                               float* pi_traj, float* pi_last, float* reward, double* delta, double* g, double* G,
                               double* reward_acc, void* workspace, size_t workspace_bytes, hipStream_t st,
-                              const DeferredUpdate* du = nullptr, const PopArgs* pop = nullptr) {
+                              const DeferredUpdate* du = nullptr, const PopArgs* pop = nullptr, const ExtReward* ext = nullptr) {
+  REQUIRE(!du || !ext, "deferred update: needs an in-kernel reward");
   CoreArgs a{};
   if (du) {
     if (d <= WAVE) {
@@ -2648,31 +2663,34 @@ static int train_rollout_impl(const float* mat_pi0, int64_t num_start, const int
   a.traj_offset = traj_offset;
   a.pi_traj = pi_traj;
   a.pi_next_out = pi_last;
-  a.reward_out = reward;
+  a.reward_out = ext ? nullptr : reward;
   a.delta = delta;
   a.g = g;
+  a.P_out = ext ? ext->P : nullptr;
   const int precision = (flags & MFG_ROLLOUT_F64) ? MFG_PRECISION_F64 : MFG_PRECISION_MIXED;
   const bool deferred = defer_values(d, B, T, pi_traj, workspace, workspace_bytes);
   if (deferred && pop) return fail(MFG_EUNSUPPORTED, "%s", "population: d > 64");
   if (deferred) a.w = nullptr;
   int rc = launch_core(a, true, true, precision, st, pop);
   if (rc != MFG_OK) return rc;
+  if (ext) {
+    rc = reward_net_forward_sums(pi_traj, ext->P, B * (int64_t)T, d, *ext->net, ext->key, ext->sample_offset, reward, nullptr,
+                                 nullptr, st, T, ext->pop);
+    if (rc != MFG_OK) return rc;
+  }
   if (deferred) {
-    rc = launch_values_and_delta(pi_traj, B, T, d, w, reward, gamma, a.discount_pow, delta, workspace, workspace_bytes, st);
+    rc = launch_values_and_delta(pi_traj, B, T, d, w, ext ? nullptr : reward, gamma, a.discount_pow, delta, workspace,
+                                 workspace_bytes, st);
     if (rc != MFG_OK) return rc;
   }
   const ApplyArgs ap{lr_critic, lr_actor, w, theta, reward_acc};
   const bool want_apply = (flags & MFG_TRAIN_APPLY) != 0;
   bool applied = false;
   rc = launch_grad(pi_traj, (int64_t)(T + 1) * d, delta, g, reward, B * T, T, d, G, 0, workspace, workspace_bytes, st,
-                   want_apply ? &ap : nullptr, &applied, false, pop);
+                   want_apply ? &ap : nullptr, &applied, ext != nullptr, pop);
   if (rc != MFG_OK) return rc;
   if (pop && want_apply && !applied) return fail(MFG_ELAUNCH, "%s", "population: update not applied");  // (not reached: d <= 64)
-  if (want_apply && !applied) {
-    const int64_t F = mfg_num_features(d);
-    hipLaunchKernelGGL(k_apply_update, dim3((unsigned)((F + 255) / 256)), dim3(256), 0, st, G, F, lr_critic, lr_actor, w, theta,
-                       reward_acc);
-  }
+  if (want_apply && !applied) launch_apply_update(G, d, lr_critic, lr_actor, w, theta, reward_acc, st);
   return check_launch("train_rollout");
 }
 
@@ -2764,6 +2782,12 @@ const RcclApi& rccl() {
   }();
   return api;
 }
+// the entry points, or NULL with the refusal recorded (MFG_EUNSUPPORTED)
+const RcclApi* rccl_or_fail() {
+  const RcclApi& r = rccl();
+  if (!r.ok) (void)fail(MFG_EUNSUPPORTED, "%s", "librccl.so is not available in this process");
+  return r.ok ? &r : nullptr;
+}
 int rccl_fail(const char* what, int rc) {
   const RcclApi& r = rccl();
   return fail(MFG_ELAUNCH, "%s: RCCL error %d (%s)", what, rc, r.GetErrorString ? r.GetErrorString(rc) : "?");
@@ -2776,18 +2800,18 @@ int mfg_dist_available(void) { return rccl().ok ? 1 : 0; }
 
 int mfg_dist_unique_id(mfg_rccl_id_t* id_host) {
   REQUIRE(id_host, "null pointer");
-  const RcclApi& r = rccl();
-  if (!r.ok) return fail(MFG_EUNSUPPORTED, "%s", "librccl.so is not available in this process");
-  const int rc = r.GetUniqueId(id_host);
+  const RcclApi* r = rccl_or_fail();
+  if (!r) return MFG_EUNSUPPORTED;
+  const int rc = r->GetUniqueId(id_host);
   return rc == 0 ? MFG_OK : rccl_fail("ncclGetUniqueId", rc);
 }
 
 int mfg_dist_init(const mfg_rccl_id_t* id_host, int nranks, int rank, void** comm_out) {
   REQUIRE(id_host && comm_out && nranks >= 1 && rank >= 0 && rank < nranks, "bad arguments");
-  const RcclApi& r = rccl();
-  if (!r.ok) return fail(MFG_EUNSUPPORTED, "%s", "librccl.so is not available in this process");
+  const RcclApi* r = rccl_or_fail();
+  if (!r) return MFG_EUNSUPPORTED;
   void* comm = nullptr;
-  const int rc = r.CommInitRank(&comm, nranks, *id_host, rank);   // collective: every rank of the job calls it (current device)
+  const int rc = r->CommInitRank(&comm, nranks, *id_host, rank);   // collective: every rank of the job calls it (current device)
   if (rc != 0) return rccl_fail("ncclCommInitRank", rc);
   *comm_out = comm;
   return MFG_OK;
@@ -2795,9 +2819,9 @@ int mfg_dist_init(const mfg_rccl_id_t* id_host, int nranks, int rank, void** com
 
 int mfg_dist_destroy(void* comm) {
   if (!comm) return MFG_OK;
-  const RcclApi& r = rccl();
-  if (!r.ok) return fail(MFG_EUNSUPPORTED, "%s", "librccl.so is not available in this process");
-  const int rc = r.CommDestroy(comm);
+  const RcclApi* r = rccl_or_fail();
+  if (!r) return MFG_EUNSUPPORTED;
+  const int rc = r->CommDestroy(comm);
   return rc == 0 ? MFG_OK : rccl_fail("ncclCommDestroy", rc);
 }
 
@@ -2811,9 +2835,9 @@ int mfg_dist_abort(void* comm) {
 
 int mfg_dist_all_reduce(void* comm, double* G, int64_t n, mfg_stream_t stream) {
   REQUIRE(comm && G && n >= 1, "bad arguments");
-  const RcclApi& r = rccl();
-  if (!r.ok) return fail(MFG_EUNSUPPORTED, "%s", "librccl.so is not available in this process");
-  const int rc = r.AllReduce(G, G, (size_t)n, RCCL_FLOAT64, RCCL_SUM, comm, S(stream));
+  const RcclApi* r = rccl_or_fail();
+  if (!r) return MFG_EUNSUPPORTED;
+  const int rc = r->AllReduce(G, G, (size_t)n, RCCL_FLOAT64, RCCL_SUM, comm, S(stream));
   return rc == 0 ? MFG_OK : rccl_fail("ncclAllReduce", rc);
 }
 
@@ -2828,8 +2852,8 @@ int mfg_train_rollouts_dist(void* comm, const float* mat_pi0, int64_t num_start,
   REQUIRE(episodes >= 0 && first_episode >= 0, "bad episode range");
   REQUIRE(!(flags & MFG_TRAIN_APPLY), "MFG_TRAIN_APPLY makes no sense here");
   REQUIRE((uint64_t)first_step + (uint64_t)episodes * (uint64_t)T <= 0xFFFFFFFFull, "Philox step counter would wrap");
-  const RcclApi& r = rccl();
-  if (!r.ok) return fail(MFG_EUNSUPPORTED, "%s", "librccl.so is not available in this process");
+  const RcclApi* r = rccl_or_fail();
+  if (!r) return MFG_EUNSUPPORTED;
   if (episodes == 0) return MFG_OK;
   const int64_t F = mfg_num_features(d);
   hipStream_t st = S(stream);
@@ -2858,8 +2882,8 @@ int mfg_train_rollouts_dist(void* comm, const float* mat_pi0, int64_t num_start,
                                 nullptr, workspace, workspace_bytes, st, pending ? &du : nullptr);
     if (rc != MFG_OK) {
       // (the communicator is dead afterwards: MFG_ECOMM tells the caller to forget the handle; mfg_last_error keeps the cause)
-      if (r.CommAbort) {
-        (void)r.CommAbort(comm);
+      if (r->CommAbort) {
+        (void)r->CommAbort(comm);
         return MFG_ECOMM;
       }
       return rc;
@@ -2868,11 +2892,11 @@ int mfg_train_rollouts_dist(void* comm, const float* mat_pi0, int64_t num_start,
       double* t = tc; tc = tn; tn = t;
       t = wc; wc = wn; wn = t;
     }
-    rc = r.AllReduce(G, G, (size_t)(F + 3), RCCL_FLOAT64, RCCL_SUM, comm, st);   // the ONE exchange of the update
+    rc = r->AllReduce(G, G, (size_t)(F + 3), RCCL_FLOAT64, RCCL_SUM, comm, st);   // the ONE exchange of the update
     if (rc != 0) {
       (void)rccl_fail("ncclAllReduce", rc);
-      if (r.CommAbort) {
-        (void)r.CommAbort(comm);
+      if (r->CommAbort) {
+        (void)r->CommAbort(comm);
         return MFG_ECOMM;
       }
       return MFG_ELAUNCH;
@@ -2885,7 +2909,7 @@ int mfg_train_rollouts_dist(void* comm, const float* mat_pi0, int64_t num_start,
     pending = true;
   }
   // the last update, and the parameters back in the caller's primary set
-  hipLaunchKernelGGL(k_apply_update, dim3((unsigned)((F + 255) / 256)), dim3(256), 0, st, G, F, plc, pla, wc, tc, pacc);
+  launch_apply_update(G, d, plc, pla, wc, tc, pacc, st);
   if (tc != theta) {
     if (hipMemcpyAsync(theta, tc, sizeof(double), hipMemcpyDeviceToDevice, st) != hipSuccess ||
         hipMemcpyAsync(w, wc, (size_t)F * sizeof(double), hipMemcpyDeviceToDevice, st) != hipSuccess)
@@ -2923,11 +2947,7 @@ int mfg_grad_apply(const float* pi, int64_t stride_b, double* delta, const doubl
   int rc = launch_grad(pi, stride_b, delta, g, reward, B * T, T, d, G, 0, workspace, workspace_bytes, S(stream), &ap, &applied,
                        add_reward != 0);
   if (rc != MFG_OK) return rc;
-  if (!applied) {
-    const int64_t F = mfg_num_features(d);
-    hipLaunchKernelGGL(k_apply_update, dim3((unsigned)((F + 255) / 256)), dim3(256), 0, S(stream), G, F, lr_critic, lr_actor,
-                       w, theta, reward_acc);
-  }
+  if (!applied) launch_apply_update(G, d, lr_critic, lr_actor, w, theta, reward_acc, S(stream));
   return check_launch("grad_apply");
 }
 
@@ -2971,11 +2991,7 @@ static int train_episode_impl(float* pi_io, float* pi_scratch, int64_t B, int d,
     }
     if (rc != MFG_OK) return rc;
     if (pop && !applied) return fail(MFG_ELAUNCH, "%s", "population: update not applied");  // (not reached: d <= 64)
-    if (!applied) {
-      const int64_t F = mfg_num_features(d);
-      hipLaunchKernelGGL(k_apply_update, dim3((unsigned)((F + 255) / 256)), dim3(256), 0, st, G, F, lr_critic, lr_actor,
-                         w, theta, reward_acc);
-    }
+    if (!applied) launch_apply_update(G, d, lr_critic, lr_actor, w, theta, reward_acc, st);
     float* t = cur;
     cur = nxt;
     nxt = t;
@@ -3187,10 +3203,20 @@ int mfg_evaluate_pop(const float* emp32, const double* emp64, int64_t N, int L, 
   return check_launch("evaluate_pop metrics");
 }
 
-// ---- IRL populations (mfg_population.h, mfg_irl_population.h): K forward learners of AC_IRL.train in the launches of one ----
+// ---- IRL forward learners (AC_IRL.train): the reward comes from the reward network, launched between the core kernel and the
+// update.  One driver per flow serves the single learner and the population of K (mfg_population.h, mfg_irl_population.h):
+// train_rollout_impl with an ExtReward (rollout mode) and train_episode_irl_step (step mode, two launches per env step) ----
+// the checks the single-learner calls share (pre_check: the call's own, right after the shape checks; extra_ptrs: its pointers)
+#define CHECK_IRL(pre_check, extra_ptrs)                                                                                 \
+  CHECK_BD();                                                                                                            \
+  pre_check;                                                                                                             \
+  REQUIRE(T >= 1, "T < 1");                                                                                              \
+  REQUIRE(theta && w && net && P && reward && delta && g && G && workspace && (extra_ptrs), "null pointer")
+
 // the IRL populations: B T samples per learner (checked ahead of T >= 1, which changes nothing: a T < 1 keeps B T small), the
 // reward network's settings and the matrix-core kernel's geometry
 #define CHECK_IRL_POP()                                                                                                  \
+  REQUIRE(net_stride >= 0, "net_stride < 0");                                                                            \
   CHECK_POP(REQUIRE(B * (int64_t)T <= 0x7FFFFFFF, "B * T too large"), net && rn_seed && P);                             \
   REQUIRE(net->keep_prob > 0.0f && net->keep_prob <= 1.0f, "reward net: keep_prob must be in (0,1]");                    \
   if (!reward_net_pop_ready(d, net, per_learner_net, K, net_stride))                                                     \
@@ -3198,10 +3224,253 @@ int mfg_evaluate_pop(const float* emp32, const double* emp64, int64_t N, int L, 
                 "reward network (d = 21 / 15, 5 / 2 / 3, n_fc3 <= 16, 8-byte aligned fc3_w of every learner)",           \
                 d, net->k1, net->f2, net->k2, net->n3, net->n4)
 
-static uint64_t rn_key_ctr(uint64_t call) { return call * 0x9E3779B97F4A7C15ull; }
+// dropout key of reward-network call number `call` (1-based) under rn_seed; a population xors its learners' seeds in the
+// kernel: RnPop::key_ctr is the key under seed 0
+static uint64_t rn_dropout_key(uint64_t rn_seed, uint64_t call) { return rn_seed ^ (call * 0x9E3779B97F4A7C15ull); }
 
-// (rn_call0_k: the per-learner reward-call counters [K] of mfg_train_episodes_irl_pop_calls, NULL: the shared rn_call0;
+// the reward network's population block (the call sets the strides of its flow: s_state, s_action, s_n, s_next, s_w)
+// (rn_call0_k: the per-learner reward-call counters [K] of the *_irl_pop_calls entry points, NULL: the shared rn_call0;
 //  net_stride: elements between two learners' weights, 0: the numel strides of the stacked tensors)
+static RnPop rn_pop_args(int K, int per_learner_net, int64_t net_stride, const uint64_t* rn_seed, const uint64_t* rn_call0_k,
+                         size_t workspace_bytes) {
+  RnPop rp{};
+  rp.K = K;
+  rp.per_learner_net = per_learner_net ? 1 : 0;
+  rp.s_ws = (int64_t)workspace_bytes;
+  rp.rn_seed = rn_seed;
+  rp.call_base = rn_call0_k;
+  rp.s_net = per_learner_net ? net_stride : 0;
+  return rp;
+}
+
+// one learner's workspace (slice) in the two-launch step flow: control block, with two theta slots at bytes 16 / 24 (theta
+// after odd / even steps) | column F of the rows, contiguous [max_rows] | the rows [max_rows][F+3]; max_rows <= 256: one row
+// per block of the reward-network launch
+struct IrlStepWs {
+  int64_t max_rows;
+  size_t bytes;
+  double *theta_slot, *col_f, *rows;
+};
+static IrlStepWs irl_step_ws(void* workspace, int64_t B, int d) {
+  IrlStepWs l{};
+  l.max_rows = (B + 15) / 16 < 256 ? (B + 15) / 16 : 256;
+  l.bytes = MFG_WS_CONTROL_BYTES + (size_t)l.max_rows * (mfg_num_features(d) + 3 + 1) * 8;
+  l.theta_slot = reinterpret_cast<double*>((char*)workspace + 16);
+  l.col_f = reinterpret_cast<double*>((char*)workspace + MFG_WS_CONTROL_BYTES);
+  l.rows = l.col_f + l.max_rows;
+  return l;
+}
+
+// the row reduction + update that closes a step-mode episode (population: learner k's theta_in at k pop->s_theta_b bytes)
+static void launch_reduce_rows_apply(const double* rows, int nrows, int64_t FO, double* G, double lr_c, double lr_a, double count,
+                                     double* w, const double* theta_in, double* theta_out, double* reward_acc, hipStream_t st,
+                                     const PopArgs* pop) {
+  if (pop) launch_reduce_rows_apply_pop(rows, nrows, FO, G, count, w, theta_in, theta_out, reward_acc, *pop, st);
+  else hipLaunchKernelGGL(k_reduce_rows_apply, dim3((unsigned)((FO + WAVES - 1) / WAVES)), dim3(BLOCK), 0, st, rows, nrows, FO,
+                          G, lr_c, lr_a, count, w, theta_in, theta_out, reward_acc);
+}
+
+// One step-mode episode, two launches per env step where the matrix-core reward-network kernel serves (d = 21 / 15, n_fc3 <= 16;
+// the caller asked reward_net_sums_td_ready / reward_net_pop_ready and checked the room for irl_step_ws):
+//   step kernel (STEP variant): sampling + transition + score with theta formed from the PREVIOUS step's partial rows by
+//     every wave; the grid's last blocks reduce those rows and publish w, theta, G, the return;
+//   reward network: r, the TD error delta = r + discount V(pi') - V(pi) from the updated w, this step's partial rows.
+// The row reduction -- a launch of its own between two dependent launches before -- leaves the critical path; ONE closes the
+// episode.  mat_pi0 != NULL: the start states are DRAWN from the table [num_start,d] inside the first step kernel (the draw of
+// mfg_draw_start at step = first_step) and pi_io is an output only; NULL (single learner): pi_io holds them.
+// rn_call0: reward-network calls before this episode.  pop / rp != NULL: the population; the per-learner scalars (shift,
+// alpha_scale, seed, the learning rates, rn_seed) then come from their device arrays and the ones passed here are not read;
+// the strides that change from step to step (s_pi0, s_theta_b) and the reward-call number are set here.
+static int train_episode_irl_step(const float* mat_pi0, int64_t num_start, float* pi_io, float* pi_scratch, int64_t B, int d, int T,
+                                  double* theta, double shift, double alpha_scale, double* w, double gamma, uint64_t seed,
+                                  uint32_t first_step, uint64_t traj_offset, int precision, double lr_critic, double lr_actor,
+                                  const mfg_reward_net_t& net, uint64_t rn_seed, uint64_t rn_call0, uint64_t rn_sample_offset,
+                                  float* P, float* reward, double* delta, double* g, double* G, double* reward_acc, void* workspace,
+                                  size_t workspace_bytes, hipStream_t st, PopArgs* pop = nullptr, RnPop* rp = nullptr) {
+  const int64_t FO = mfg_num_features(d) + 3;
+  const IrlStepWs ws = irl_step_ws(workspace, B, d);
+  // drawn start states: the buffers alternate so that the LAST step writes pi_io (no copy); given ones start in pi_io and,
+  // after an odd number of steps, the final states are copied back
+  const bool last_in_io = mat_pi0 && (T & 1);
+  float* cur = last_in_io ? pi_scratch : pi_io;
+  float* nxt = last_in_io ? pi_io : pi_scratch;
+  const double* th_in = theta;          // theta [K] before the first update, then the slot the previous step kernel wrote
+  int64_t s_th_in = sizeof(double);     // (bytes between two learners' th_in)
+  double discount = 1.0;                // running gamma^t of ac_irl.py:691, :710
+  int nrows = 0;
+  for (int s = 0; s < T; ++s) {
+    CoreArgs a{};
+    a.pi0 = cur;
+    if (s == 0 && mat_pi0) {  // the first step kernel draws its start states itself and leaves them in `cur` for the network
+      a.pi0 = mat_pi0;
+      a.num_start = num_start;
+      a.start_draw = 1;
+      a.pi_start_out = cur;
+      a.step_nrows = -1;
+    }
+    a.theta = th_in;
+    a.w = nullptr;  // no value part here
+    a.shift = shift;
+    a.alpha_scale = alpha_scale;
+    a.gamma = discount;
+    a.B = B;
+    a.d = d;
+    a.T = 1;
+    a.reward_kind = MFG_REWARD_EXTERNAL;
+    a.seed = seed;
+    a.first_step = first_step + (uint32_t)s;
+    a.traj_offset = traj_offset;
+    a.pi_next_out = nxt;
+    a.g = g;
+    a.P_out = P;
+    if (s > 0) {  // (the first step has nothing to reduce: the plain kernel, without its value part)
+      a.step_G = G;
+      a.pend_lr_c = lr_critic;
+      a.pend_lr_a = lr_actor;
+      a.w_out = w;
+      a.pend_reward_acc = reward_acc;
+      a.step_rows = ws.rows;
+      a.step_nrows = nrows;
+      a.theta_out = ws.theta_slot + (s & 1);
+    }
+    if (pop) {
+      pop->s_pi0 = a.start_draw ? 0 : B * d;  // (0: the shared start-state table)
+      pop->s_theta_b = s_th_in;
+    }
+    int rc = launch_core(a, true, true, precision, st, pop);
+    if (rc != MFG_OK) return rc;
+    if (s > 0) {
+      th_in = ws.theta_slot + (s & 1);
+      s_th_in = (int64_t)workspace_bytes;
+    }
+    const uint64_t call = rn_call0 + (uint64_t)s + 1ull;
+    if (rp) {
+      rp->key_ctr = rn_dropout_key(0, call);
+      rp->call_j = call;  // (read with per-learner counters only, which come with rn_call0 = 0: the call's own count)
+    }
+    RnSums sm{};
+    sm.g = g;
+    sm.delta_out = delta;
+    sm.part_rows = ws.rows;
+    sm.max_rows = ws.max_rows;
+    sm.td_w = w;
+    sm.state_next = nxt;
+    sm.td_gamma = discount;
+    sm.col_f = ws.col_f;
+    int rows = 0;
+    rc = reward_net_forward_sums(cur, P, B, d, net, rn_dropout_key(rn_seed, call), rn_sample_offset, reward, &sm, &rows, st, 0, rp);
+    if (rc != MFG_OK) return rc;
+    if (rows != (int)ws.max_rows) return fail(MFG_ELAUNCH, "%s", "train_episode_irl: the reward-network launch left no partial rows");
+    nrows = rows;
+    discount *= gamma;
+    float* t = cur;
+    cur = nxt;
+    nxt = t;
+  }
+  if (pop) pop->s_theta_b = s_th_in;
+  launch_reduce_rows_apply(ws.rows, nrows, FO, G, lr_critic, lr_actor, (double)B, w, th_in, theta, reward_acc, st, pop);
+  if (cur != pi_io && hipMemcpyAsync(pi_io, cur, (size_t)B * d * sizeof(float) * (pop ? pop->K : 1), hipMemcpyDeviceToDevice,
+                                     st) != hipSuccess)
+    return fail(MFG_ELAUNCH, "%s", "train_episode_irl: final state copy failed");
+  return check_launch("train_episode_irl");
+}
+
+// The same episode where the two-launch flow does not serve (single learner): three launches per env step, [step kernel with
+// its value part | reward network | update]
+static int train_episode_irl_3launch(const float* mat_pi0, int64_t num_start, float* pi_io, float* pi_scratch, int64_t B, int d,
+                                     int T, double* theta, double shift, double alpha_scale, double* w, double gamma, uint64_t seed,
+                                     uint32_t first_step, uint64_t traj_offset, int precision, double lr_critic, double lr_actor,
+                                     const mfg_reward_net_t& net, uint64_t rn_seed, uint64_t rn_call0, uint64_t rn_sample_offset,
+                                     float* P, float* reward, double* delta, double* g, double* G, double* reward_acc,
+                                     void* workspace, size_t workspace_bytes, hipStream_t st) {
+  float* cur = pi_io;
+  float* nxt = pi_scratch;
+  double discount = 1.0;
+  if (mat_pi0) {
+    hipLaunchKernelGGL(k_draw_start, dim3(grid_for(B * d, 256, 8)), dim3(256), 0, st, mat_pi0, num_start, B, d, seed, first_step,
+                       traj_offset, (int32_t*)nullptr, pi_io);
+    const int rc = check_launch("draw_start");
+    if (rc != MFG_OK) return rc;
+  }
+  for (int s = 0; s < T; ++s) {
+    CoreArgs a{};
+    a.pi0 = cur;
+    a.theta = theta;
+    a.w = w;
+    a.shift = shift;
+    a.alpha_scale = alpha_scale;
+    a.gamma = discount;
+    a.B = B;
+    a.d = d;
+    a.T = 1;
+    a.reward_kind = MFG_REWARD_EXTERNAL;  // delta = discount V(pi') - V(pi); the reward joins it in the gradient kernel
+    a.seed = seed;
+    a.first_step = first_step + (uint32_t)s;
+    a.traj_offset = traj_offset;
+    a.pi_next_out = nxt;
+    a.delta = delta;
+    a.g = g;
+    a.P_out = P;
+    int rc = launch_core(a, true, true, precision, st);
+    if (rc != MFG_OK) return rc;
+    // reward network; at the packed sizes the same launch folds delta = delta0 + r and leaves the partial rows of the batch
+    // sums (one per block of eight samples), so the update is a row reduction instead of a gradient kernel
+    const int64_t FO = mfg_num_features(d) + 3;
+    const int64_t room = workspace_bytes > MFG_WS_CONTROL_BYTES ? (int64_t)((workspace_bytes - MFG_WS_CONTROL_BYTES) / (size_t)(FO * 8)) : 0;
+    const RnSums sm{delta, g, delta, reinterpret_cast<double*>((char*)workspace + MFG_WS_CONTROL_BYTES), room};
+    int rows = 0;
+    rc = reward_net_forward_sums(cur, P, B, d, net, rn_dropout_key(rn_seed, rn_call0 + (uint64_t)s + 1ull), rn_sample_offset, reward,
+                                 &sm, &rows, st);
+    if (rc != MFG_OK) return rc;
+    const ApplyArgs ap{lr_critic, lr_actor, w, theta, reward_acc};
+    bool applied = false;
+    if (rows > 0) {
+      ReduceApply rap{};
+      rap.on = 1;
+      rap.lr_c = lr_critic;
+      rap.lr_a = lr_actor;
+      rap.count = (double)B;
+      rap.w = w;
+      rap.theta = theta;
+      rap.reward_acc = reward_acc;
+      hipLaunchKernelGGL(k_reduce_partials, dim3((unsigned)((FO + RP_OUT - 1) / RP_OUT)), dim3(RP_SLICES * RP_OUT), 0, st,
+                         (const double*)sm.part_rows, (int64_t)rows, FO, 0, G, rap);
+      applied = true;
+      rc = check_launch("irl_sums");
+    } else {
+      rc = launch_grad(cur, d, delta, g, reward, B, 1, d, G, 0, workspace, workspace_bytes, st, &ap, &applied, true);
+    }
+    if (rc != MFG_OK) return rc;
+    if (!applied) launch_apply_update(G, d, lr_critic, lr_actor, w, theta, reward_acc, st);
+    discount *= gamma;
+    float* t = cur;
+    cur = nxt;
+    nxt = t;
+  }
+  if (cur != pi_io && hipMemcpyAsync(pi_io, cur, (size_t)B * d * sizeof(float), hipMemcpyDeviceToDevice, st) != hipSuccess)
+    return fail(MFG_ELAUNCH, "%s", "train_episode_irl: final state copy failed");
+  return check_launch("train_episode_irl");
+}
+
+// the single learner's episode: the two-launch flow where it serves and the workspace has room, else three launches per step
+static int train_episode_irl_impl(const float* mat_pi0, int64_t num_start, float* pi_io, float* pi_scratch, int64_t B, int d, int T,
+                                  double* theta, double shift, double alpha_scale, double* w, double gamma, uint64_t seed,
+                                  uint32_t first_step, uint64_t traj_offset, int precision, double lr_critic, double lr_actor,
+                                  const mfg_reward_net_t* net, uint64_t rn_seed, uint64_t rn_call0, uint64_t rn_sample_offset,
+                                  float* P, float* reward, double* delta, double* g, double* G, double* reward_acc, void* workspace,
+                                  size_t workspace_bytes, mfg_stream_t stream) {
+  CHECK_IRL(CHECK_PRECISION(), pi_io && pi_scratch);
+  REQUIRE(!mat_pi0 || (num_start > 0 && num_start <= 0x7FFFFFFF), "empty / oversized start-state table");
+  const IrlStepWs ws = irl_step_ws(workspace, B, d);
+  if (d <= WAVE && reward_net_sums_td_ready(B, d, *net, workspace_bytes >= ws.bytes ? ws.max_rows : 0))
+    return train_episode_irl_step(mat_pi0, num_start, pi_io, pi_scratch, B, d, T, theta, shift, alpha_scale, w, gamma, seed,
+                                  first_step, traj_offset, precision, lr_critic, lr_actor, *net, rn_seed, rn_call0, rn_sample_offset,
+                                  P, reward, delta, g, G, reward_acc, workspace, workspace_bytes, S(stream));
+  return train_episode_irl_3launch(mat_pi0, num_start, pi_io, pi_scratch, B, d, T, theta, shift, alpha_scale, w, gamma, seed,
+                                   first_step, traj_offset, precision, lr_critic, lr_actor, *net, rn_seed, rn_call0,
+                                   rn_sample_offset, P, reward, delta, g, G, reward_acc, workspace, workspace_bytes, S(stream));
+}
+
 static int train_episodes_irl_pop(const float* mat_pi0, int64_t num_start, float* pi_out, float* pi_scratch, int64_t B, int K, int d,
                                   int T, int64_t episodes, int64_t first_episode, int constant, double* theta, const double* shift,
                                   const double* alpha_scale, double* w, double gamma, const uint64_t* seed, uint32_t first_step,
@@ -3210,106 +3479,26 @@ static int train_episodes_irl_pop(const float* mat_pi0, int64_t num_start, float
                                   uint64_t rn_call0, const uint64_t* rn_call0_k, float* P, float* reward, double* delta, double* g,
                                   double* G, double* reward_acc, void* workspace, size_t workspace_bytes, mfg_stream_t stream) {
   REQUIRE(pi_out && pi_scratch, "null pointer");
-  REQUIRE(net_stride >= 0, "net_stride < 0");
   CHECK_IRL_POP();
   CHECK_PRECISION();
-  // one learner's slice: control block (two theta slots at bytes 16 / 24) | column F of the rows [max_rows] | rows [max_rows][FO]
-  const int64_t FO = mfg_num_features(d) + 3;
-  const int64_t max_rows = (B + 15) / 16 < 256 ? (B + 15) / 16 : 256;
-  const size_t need = MFG_WS_CONTROL_BYTES + (size_t)max_rows * (FO + 1) * 8;
+  const size_t need = irl_step_ws(workspace, B, d).bytes;
   if (workspace_bytes < need)
     return fail(MFG_EWORKSPACE, "IRL population workspace: need %lld bytes per learner, have %lld", (long long)need,
                 (long long)workspace_bytes);
-  hipStream_t st = S(stream);
   PopArgs p = pop_args(K, B, d, 1, episodes, seed, shift, alpha_scale, lr_critic, lr_actor, workspace_bytes);
   p.s_n = B;
   p.s_P = B * d * d;
-  RnPop rp{};
-  rp.K = K;
-  rp.per_learner_net = per_learner_net ? 1 : 0;
+  RnPop rp = rn_pop_args(K, per_learner_net, net_stride, rn_seed, rn_call0_k, workspace_bytes);
   rp.s_state = rp.s_next = B * d;
   rp.s_action = B * d * d;
   rp.s_n = B;
-  rp.s_w = FO - 3;
-  rp.s_ws = (int64_t)workspace_bytes;
-  rp.rn_seed = rn_seed;
-  rp.call_base = rn_call0_k;
-  rp.s_net = per_learner_net ? net_stride : 0;
-  double* rows_buf = reinterpret_cast<double*>((char*)workspace + MFG_WS_CONTROL_BYTES) + max_rows;
-  double* th_slot = reinterpret_cast<double*>((char*)workspace + 16);  // two slots: theta after odd / even steps
+  rp.s_w = p.F;
   for (int64_t e = 0; e < episodes; ++e) {
-    const uint32_t step0 = first_step + (uint32_t)(e * T);
     lr_schedule(first_episode + e, constant, &p.sc, &p.sa);
-    double* acc = reward_acc ? reward_acc + e : nullptr;
-    // the buffers alternate so that the LAST step writes pi_out (as mfg_train_episode_irl_draw does)
-    float* cur = (T & 1) ? pi_scratch : pi_out;
-    float* nxt = (T & 1) ? pi_out : pi_scratch;
-    const double* th_in = theta;
-    int64_t s_th_in = sizeof(double);
-    double discount = 1.0;
-    int nrows = 0;
-    for (int s = 0; s < T; ++s) {
-      CoreArgs a{};
-      a.pi0 = cur;
-      p.s_pi0 = B * d;
-      if (s == 0) {  // the first step kernel draws the start states and leaves them in `cur` for the network
-        a.pi0 = mat_pi0;
-        a.num_start = num_start;
-        a.start_draw = 1;
-        a.pi_start_out = cur;
-        a.step_nrows = -1;
-        p.s_pi0 = 0;
-      }
-      a.theta = th_in;
-      p.s_theta_b = s_th_in;
-      a.gamma = discount;
-      a.B = B;
-      a.d = d;
-      a.T = 1;
-      a.reward_kind = MFG_REWARD_EXTERNAL;
-      a.first_step = step0 + (uint32_t)s;
-      a.traj_offset = traj_offset;
-      a.pi_next_out = nxt;
-      a.g = g;
-      a.P_out = P;
-      if (s > 0) {
-        a.step_G = G;
-        a.w_out = w;
-        a.pend_reward_acc = acc;
-        a.step_rows = rows_buf;
-        a.step_nrows = nrows;
-        a.theta_out = th_slot + (s & 1);
-      }
-      int rc = launch_core(a, true, true, precision, st, &p);
-      if (rc != MFG_OK) return rc;
-      if (s > 0) {
-        th_in = th_slot + (s & 1);
-        s_th_in = (int64_t)workspace_bytes;
-      }
-      rp.key_ctr = rn_key_ctr(rn_call0 + (uint64_t)(e * T + s) + 1ull);
-      rp.call_j = (uint64_t)(e * T + s) + 1ull;
-      RnSums sm{};
-      sm.g = g;
-      sm.delta_out = delta;
-      sm.part_rows = rows_buf;
-      sm.max_rows = max_rows;
-      sm.td_w = w;
-      sm.state_next = nxt;
-      sm.td_gamma = discount;
-      sm.col_f = rows_buf - max_rows;
-      int rows = 0;
-      rc = reward_net_forward_pop(cur, P, B, d, net, traj_offset, reward, &sm, &rows, rp, st, 0);
-      if (rc != MFG_OK) return rc;
-      if (rows != (int)max_rows) return fail(MFG_ELAUNCH, "%s", "train_episodes_irl_pop: the reward-network launch left no partial rows");
-      nrows = rows;
-      discount *= gamma;
-      float* t = cur;
-      cur = nxt;
-      nxt = t;
-    }
-    p.s_theta_b = s_th_in;
-    launch_reduce_rows_apply_pop(rows_buf, nrows, FO, G, (double)B, w, th_in, theta, acc, p, st);
-    const int rc = check_launch("train_episodes_irl_pop");
+    const int rc = train_episode_irl_step(mat_pi0, num_start, pi_out, pi_scratch, B, d, T, theta, 0.0, 0.0, w, gamma, 0,
+                                          first_step + (uint32_t)(e * T), traj_offset, precision, 0.0, 0.0, *net, 0,
+                                          rn_call0 + (uint64_t)(e * T), traj_offset, P, reward, delta, g, G,
+                                          reward_acc ? reward_acc + e : nullptr, workspace, workspace_bytes, S(stream), &p, &rp);
     if (rc != MFG_OK) return rc;
   }
   return MFG_OK;
@@ -3323,65 +3512,32 @@ static int train_rollouts_irl_pop(const float* mat_pi0, int64_t num_start, int64
                                   float* pi_traj, float* pi_last, float* P, float* reward, double* delta, double* g, double* G,
                                   double* reward_acc, void* workspace, size_t workspace_bytes, mfg_stream_t stream) {
   REQUIRE(pi_traj, "null pointer");
-  REQUIRE(net_stride >= 0, "net_stride < 0");
   CHECK_IRL_POP();
   const size_t need = pop_workspace_need(d, B * T, false);
   if (workspace_bytes < need)
     return fail(MFG_EWORKSPACE, "IRL population workspace: need %lld bytes per learner, have %lld", (long long)need,
                 (long long)workspace_bytes);
-  hipStream_t st = S(stream);
   PopArgs p = pop_args(K, B, d, T, episodes, seed, shift, alpha_scale, lr_critic, lr_actor, workspace_bytes);
   p.s_pi0 = 0;  // (the shared start-state table: the rows are drawn in the kernel)
   p.s_gpi = p.s_traj;
   p.s_n = B * T;
   p.s_P = B * T * d * d;
-  RnPop rp{};
-  rp.K = K;
-  rp.per_learner_net = per_learner_net ? 1 : 0;
+  RnPop rp = rn_pop_args(K, per_learner_net, net_stride, rn_seed, rn_call0_k, workspace_bytes);
   rp.s_state = B * (T + 1) * d;
   rp.s_action = B * T * d * d;
   rp.s_n = B * T;
-  rp.s_ws = (int64_t)workspace_bytes;
-  rp.rn_seed = rn_seed;
-  rp.call_base = rn_call0_k;
-  rp.s_net = per_learner_net ? net_stride : 0;
-  const int precision = (flags & MFG_ROLLOUT_F64) ? MFG_PRECISION_F64 : MFG_PRECISION_MIXED;
+  const ExtReward ext{net, P, 0, traj_offset * (uint64_t)T, &rp};
   for (int64_t e = 0; e < episodes; ++e) {
     lr_schedule(first_episode + e, constant, &p.sc, &p.sa);
-    CoreArgs a{};
-    a.pi0 = mat_pi0;
-    a.start_draw = 1;
-    a.num_start = num_start;
-    a.theta = theta;
-    a.w = w;
-    a.gamma = gamma;
-    a.B = B;
-    a.d = d;
-    a.T = T;
-    a.reward_kind = MFG_REWARD_EXTERNAL;  // delta = discount V(pi') - V(pi); the reward joins it in the gradient kernel
-    a.discount_pow = (flags & MFG_ROLLOUT_DISCOUNT_POW) ? 1 : 0;
-    a.first_step = first_step + (uint32_t)(e * T);
-    a.traj_offset = traj_offset;
-    a.pi_traj = pi_traj;
-    a.pi_next_out = pi_last;
-    a.delta = delta;
-    a.g = g;
-    a.P_out = P;
-    int rc = launch_core(a, true, true, precision, st, &p);
-    if (rc != MFG_OK) return rc;
-    // ONE reward-network pass over each learner's Bk T transitions, states read in place from pi_traj
-    rp.key_ctr = rn_key_ctr(rn_call0 + (uint64_t)e + 1ull);
+    rp.key_ctr = rn_dropout_key(0, rn_call0 + (uint64_t)e + 1ull);
     rp.call_j = (uint64_t)e + 1ull;
-    rc = reward_net_forward_pop(pi_traj, P, B * (int64_t)T, d, net, traj_offset * (uint64_t)T, reward, nullptr, nullptr, rp, st, T);
+    const int rc = train_rollout_impl(mat_pi0, num_start, nullptr, B, d, T, theta, 0.0, 0.0, w, gamma, MFG_REWARD_EXTERNAL, 0,
+                                      first_step + (uint32_t)(e * T), traj_offset, flags | MFG_TRAIN_APPLY, 0.0, 0.0, pi_traj,
+                                      pi_last, reward, delta, g, G, reward_acc ? reward_acc + e : nullptr, workspace,
+                                      workspace_bytes, S(stream), nullptr, &p, &ext);
     if (rc != MFG_OK) return rc;
-    const ApplyArgs ap{0.0, 0.0, w, theta, reward_acc ? reward_acc + e : nullptr};
-    bool applied = false;
-    rc = launch_grad(pi_traj, (int64_t)(T + 1) * d, delta, g, reward, B * T, T, d, G, 0, workspace, workspace_bytes, st, &ap,
-                     &applied, true, &p);
-    if (rc != MFG_OK) return rc;
-    if (!applied) return fail(MFG_ELAUNCH, "%s", "IRL population: update not applied");  // (not reached: d <= 64)
   }
-  return check_launch("train_rollouts_irl_pop");
+  return MFG_OK;
 }
 
 int mfg_train_episodes_irl_pop(const float* mat_pi0, int64_t num_start, float* pi_out, float* pi_scratch, int64_t B, int K, int d,
@@ -3446,234 +3602,14 @@ int mfg_train_rollout_irl(const float* mat_pi0, int64_t num_start, const int32_t
                           uint64_t rn_key, uint64_t rn_sample_offset, float* pi_traj, float* pi_last, float* P, float* reward,
                           double* delta, double* g, double* G, double* reward_acc, void* workspace, size_t workspace_bytes,
                           mfg_stream_t stream) {
-  CHECK_BD();
-  REQUIRE(T >= 1, "T < 1");
-  REQUIRE(mat_pi0 && num_start > 0 && num_start <= 0x7FFFFFFF, "null / empty / oversized start-state table");
-  REQUIRE(theta && w && net && pi_traj && P && reward && delta && g && G && workspace, "null pointer");
+  CHECK_IRL(REQUIRE(mat_pi0 && num_start > 0 && num_start <= 0x7FFFFFFF, "null / empty / oversized start-state table"), pi_traj);
   REQUIRE(B * (int64_t)T <= 0x7FFFFFFF, "B * T too large");
-  hipStream_t st = S(stream);
-  CoreArgs a{};
-  a.pi0 = mat_pi0;
-  a.start_idx = idx;
-  a.start_draw = idx ? 0 : 1;
-  a.num_start = num_start;
-  a.theta = theta;
-  a.w = w;
-  a.shift = shift;
-  a.alpha_scale = alpha_scale;
-  a.gamma = gamma;
-  a.B = B;
-  a.d = d;
-  a.T = T;
-  a.reward_kind = MFG_REWARD_EXTERNAL;  // delta = discount V(pi') - V(pi); the reward joins it in the gradient kernel
-  a.discount_pow = (flags & MFG_ROLLOUT_DISCOUNT_POW) ? 1 : 0;
-  a.seed = seed;
-  a.first_step = first_step;
-  a.traj_offset = traj_offset;
-  a.pi_traj = pi_traj;
-  a.pi_next_out = pi_last;
-  a.delta = delta;
-  a.g = g;
-  a.P_out = P;
-  const int precision = (flags & MFG_ROLLOUT_F64) ? MFG_PRECISION_F64 : MFG_PRECISION_MIXED;
-  int rc = launch_core(a, true, true, precision, st);
-  if (rc != MFG_OK) return rc;
-  // ONE reward-network pass over all B*T transitions; the states are read in place from pi_traj (rows b (T+1) + t)
-  rc = reward_net_forward_sums(pi_traj, P, B * (int64_t)T, d, net->k1, net->f2, net->k2, net->n3, net->n4, net->conv1_w, net->conv1_b,
-                               net->conv2_w, net->conv2_b, net->fc3_w, net->fc3_b, net->fc4_w, net->fc4_b, net->out_w, net->out_b,
-                               net->keep_prob, rn_key, rn_sample_offset, reward, nullptr, nullptr, stream, T);
-  if (rc != MFG_OK) return rc;
-  const ApplyArgs ap{lr_critic, lr_actor, w, theta, reward_acc};
-  const bool want_apply = (flags & MFG_TRAIN_APPLY) != 0;
-  bool applied = false;
-  rc = launch_grad(pi_traj, (int64_t)(T + 1) * d, delta, g, reward, B * T, T, d, G, 0, workspace, workspace_bytes, st,
-                   want_apply ? &ap : nullptr, &applied, true);
-  if (rc != MFG_OK) return rc;
-  if (want_apply && !applied) {
-    const int64_t F = mfg_num_features(d);
-    hipLaunchKernelGGL(k_apply_update, dim3((unsigned)((F + 255) / 256)), dim3(256), 0, st, G, F, lr_critic, lr_actor, w, theta,
-                       reward_acc);
-  }
-  return check_launch("train_rollout_irl");
+  const ExtReward ext{net, P, rn_key, rn_sample_offset, nullptr};
+  return train_rollout_impl(mat_pi0, num_start, idx, B, d, T, theta, shift, alpha_scale, w, gamma, MFG_REWARD_EXTERNAL, seed,
+                            first_step, traj_offset, flags, lr_critic, lr_actor, pi_traj, pi_last, reward, delta, g, G, reward_acc,
+                            workspace, workspace_bytes, S(stream), nullptr, nullptr, &ext);
 }
 
-}  // extern "C"
-// mat_pi0 != NULL: the start states are DRAWN from the table [num_start,d] (the draw of mfg_draw_start at step = first_step) --
-// inside the first step kernel where the two-launch flow serves -- and pi_io is an output only
-static int train_episode_irl_impl(const float* mat_pi0, int64_t num_start, float* pi_io, float* pi_scratch, int64_t B, int d, int T,
-                                  double* theta, double shift, double alpha_scale, double* w, double gamma, uint64_t seed,
-                                  uint32_t first_step, uint64_t traj_offset, int precision, double lr_critic, double lr_actor,
-                                  const mfg_reward_net_t* net, uint64_t rn_seed, uint64_t rn_call0, uint64_t rn_sample_offset,
-                                  float* P, float* reward, double* delta, double* g, double* G, double* reward_acc, void* workspace,
-                                  size_t workspace_bytes, mfg_stream_t stream) {
-  CHECK_BD();
-  CHECK_PRECISION();
-  REQUIRE(T >= 1, "T < 1");
-  REQUIRE(pi_io && pi_scratch && theta && w && net && P && reward && delta && g && G && workspace, "null pointer");
-  REQUIRE(!mat_pi0 || (num_start > 0 && num_start <= 0x7FFFFFFF), "empty / oversized start-state table");
-  hipStream_t st = S(stream);
-  float* cur = pi_io;
-  float* nxt = pi_scratch;
-  double discount = 1.0;  // running gamma^t of ac_irl.py:691, :710
-  {
-    // Two launches per env step where the matrix-core reward-network kernel serves (d = 21 / 15, n_fc3 <= 16):
-    //   step kernel (STEP variant): sampling + transition + score with theta formed from the PREVIOUS step's partial rows by
-    //     every wave; the grid's last blocks reduce those rows and publish w, theta, G, the return;
-    //   reward network: r, the TD error delta = r + discount V(pi') - V(pi) from the updated w, this step's partial rows.
-    // The row reduction -- a launch of its own between two dependent launches before -- leaves the critical path.
-    const int64_t FO = mfg_num_features(d) + 3;
-    // workspace: control block | column F of the rows, contiguous [nrows] | the rows [nrows][FO]   (nrows <= 256: one per block)
-    const int64_t max_rows = (B + 15) / 16 < 256 ? (B + 15) / 16 : 256;
-    const int64_t room = workspace_bytes >= MFG_WS_CONTROL_BYTES + (size_t)max_rows * (FO + 1) * 8 ? max_rows : 0;
-    if (d <= WAVE && reward_net_sums_td_ready(B, d, net->k1, net->f2, net->k2, net->n3, net->n4, net->fc3_w, room)) {
-      double* rows_buf = reinterpret_cast<double*>((char*)workspace + MFG_WS_CONTROL_BYTES) + max_rows;
-      double* th_slot = reinterpret_cast<double*>((char*)workspace + 16);  // two slots: theta after odd / even steps
-      const double* th_in = theta;
-      int nrows = 0;
-      if (mat_pi0 && (T & 1)) {  // drawn start states: the buffers alternate so that the LAST step writes pi_io (no copy)
-        cur = pi_scratch;
-        nxt = pi_io;
-      }
-      for (int s = 0; s < T; ++s) {
-        CoreArgs a{};
-        a.pi0 = cur;
-        if (s == 0 && mat_pi0) {  // the first step kernel draws its start states itself and leaves them in `cur` for the network
-          a.pi0 = mat_pi0;
-          a.num_start = num_start;
-          a.start_draw = 1;
-          a.pi_start_out = cur;
-          a.step_nrows = -1;
-        }
-        a.theta = th_in;
-        a.w = nullptr;  // no value part here
-        a.shift = shift;
-        a.alpha_scale = alpha_scale;
-        a.gamma = discount;
-        a.B = B;
-        a.d = d;
-        a.T = 1;
-        a.reward_kind = MFG_REWARD_EXTERNAL;
-        a.seed = seed;
-        a.first_step = first_step + (uint32_t)s;
-        a.traj_offset = traj_offset;
-        a.pi_next_out = nxt;
-        a.g = g;
-        a.P_out = P;
-        if (s > 0) {  // (the first step has nothing to reduce: the plain kernel, without its value part)
-          a.step_G = G;
-          a.pend_lr_c = lr_critic;
-          a.pend_lr_a = lr_actor;
-          a.w_out = w;
-          a.pend_reward_acc = reward_acc;
-          a.step_rows = rows_buf;
-          a.step_nrows = nrows;
-          a.theta_out = th_slot + (s & 1);
-        }
-        int rc = launch_core(a, true, true, precision, st);
-        if (rc != MFG_OK) return rc;
-        if (s > 0) th_in = th_slot + (s & 1);
-        const uint64_t key = rn_seed ^ ((rn_call0 + (uint64_t)s + 1ull) * 0x9E3779B97F4A7C15ull);
-        RnSums sm{};
-        sm.g = g;
-        sm.delta_out = delta;
-        sm.part_rows = rows_buf;
-        sm.max_rows = room;
-        sm.td_w = w;
-        sm.state_next = nxt;
-        sm.td_gamma = discount;
-        sm.col_f = rows_buf - max_rows;
-        int rows = 0;
-        rc = reward_net_forward_sums(cur, P, B, d, net->k1, net->f2, net->k2, net->n3, net->n4, net->conv1_w, net->conv1_b,
-                                     net->conv2_w, net->conv2_b, net->fc3_w, net->fc3_b, net->fc4_w, net->fc4_b, net->out_w,
-                                     net->out_b, net->keep_prob, key, rn_sample_offset, reward, &sm, &rows, stream);
-        if (rc != MFG_OK) return rc;
-        if (rows != (int)max_rows) return fail(MFG_ELAUNCH, "%s", "train_episode_irl: the reward-network launch left no partial rows");
-        nrows = rows;
-        discount *= gamma;
-        float* t = cur;
-        cur = nxt;
-        nxt = t;
-      }
-      hipLaunchKernelGGL(k_reduce_rows_apply, dim3((unsigned)((FO + WAVES - 1) / WAVES)), dim3(BLOCK), 0, st, (const double*)rows_buf,
-                         nrows, FO, G, lr_critic, lr_actor, (double)B, w, th_in, theta, reward_acc);
-      if (cur != pi_io && hipMemcpyAsync(pi_io, cur, (size_t)B * d * sizeof(float), hipMemcpyDeviceToDevice, st) != hipSuccess)
-        return fail(MFG_ELAUNCH, "%s", "train_episode_irl: final state copy failed");
-      return check_launch("train_episode_irl");
-    }
-  }
-  if (mat_pi0) {
-    hipLaunchKernelGGL(k_draw_start, dim3(grid_for(B * d, 256, 8)), dim3(256), 0, st, mat_pi0, num_start, B, d, seed, first_step,
-                       traj_offset, (int32_t*)nullptr, pi_io);
-    const int rc = check_launch("draw_start");
-    if (rc != MFG_OK) return rc;
-  }
-  for (int s = 0; s < T; ++s) {
-    CoreArgs a{};
-    a.pi0 = cur;
-    a.theta = theta;
-    a.w = w;
-    a.shift = shift;
-    a.alpha_scale = alpha_scale;
-    a.gamma = discount;
-    a.B = B;
-    a.d = d;
-    a.T = 1;
-    a.reward_kind = MFG_REWARD_EXTERNAL;  // delta = discount V(pi') - V(pi); the reward joins it in the gradient kernel
-    a.seed = seed;
-    a.first_step = first_step + (uint32_t)s;
-    a.traj_offset = traj_offset;
-    a.pi_next_out = nxt;
-    a.delta = delta;
-    a.g = g;
-    a.P_out = P;
-    int rc = launch_core(a, true, true, precision, st);
-    if (rc != MFG_OK) return rc;
-    const uint64_t key = rn_seed ^ ((rn_call0 + (uint64_t)s + 1ull) * 0x9E3779B97F4A7C15ull);
-    // reward network; at the packed sizes the same launch folds delta = delta0 + r and leaves the partial rows of the batch
-    // sums (one per block of eight samples), so the update is a row reduction instead of a gradient kernel
-    const int64_t FO = mfg_num_features(d) + 3;
-    const int64_t room = workspace_bytes > MFG_WS_CONTROL_BYTES ? (int64_t)((workspace_bytes - MFG_WS_CONTROL_BYTES) / (size_t)(FO * 8)) : 0;
-    const RnSums sm{delta, g, delta, reinterpret_cast<double*>((char*)workspace + MFG_WS_CONTROL_BYTES), room};
-    int rows = 0;
-    rc = reward_net_forward_sums(cur, P, B, d, net->k1, net->f2, net->k2, net->n3, net->n4, net->conv1_w, net->conv1_b,
-                                 net->conv2_w, net->conv2_b, net->fc3_w, net->fc3_b, net->fc4_w, net->fc4_b, net->out_w,
-                                 net->out_b, net->keep_prob, key, rn_sample_offset, reward, &sm, &rows, stream);
-    if (rc != MFG_OK) return rc;
-    const ApplyArgs ap{lr_critic, lr_actor, w, theta, reward_acc};
-    bool applied = false;
-    if (rows > 0) {
-      ReduceApply rap{};
-      rap.on = 1;
-      rap.lr_c = lr_critic;
-      rap.lr_a = lr_actor;
-      rap.count = (double)B;
-      rap.w = w;
-      rap.theta = theta;
-      rap.reward_acc = reward_acc;
-      hipLaunchKernelGGL(k_reduce_partials, dim3((unsigned)((FO + RP_OUT - 1) / RP_OUT)), dim3(RP_SLICES * RP_OUT), 0, st,
-                         (const double*)sm.part_rows, (int64_t)rows, FO, 0, G, rap);
-      applied = true;
-      rc = check_launch("irl_sums");
-    } else {
-      rc = launch_grad(cur, d, delta, g, reward, B, 1, d, G, 0, workspace, workspace_bytes, st, &ap, &applied, true);
-    }
-    if (rc != MFG_OK) return rc;
-    if (!applied) {
-      const int64_t F = mfg_num_features(d);
-      hipLaunchKernelGGL(k_apply_update, dim3((unsigned)((F + 255) / 256)), dim3(256), 0, st, G, F, lr_critic, lr_actor,
-                         w, theta, reward_acc);
-    }
-    discount *= gamma;
-    float* t = cur;
-    cur = nxt;
-    nxt = t;
-  }
-  if (cur != pi_io && hipMemcpyAsync(pi_io, cur, (size_t)B * d * sizeof(float), hipMemcpyDeviceToDevice, st) != hipSuccess)
-    return fail(MFG_ELAUNCH, "%s", "train_episode_irl: final state copy failed");
-  return check_launch("train_episode_irl");
-}
-
-extern "C" {
 int mfg_train_episode_irl(float* pi_io, float* pi_scratch, int64_t B, int d, int T, double* theta, double shift,
                           double alpha_scale, double* w, double gamma, uint64_t seed, uint32_t first_step,
                           uint64_t traj_offset, int precision, double lr_critic, double lr_actor,

@@ -1182,31 +1182,38 @@ __global__ __launch_bounds__(RM_BLOCK) void k_reward_net_mfma_pop(RewardNetArgs 
   reward_net_mfma_body<D, RUN, RPR, P1, SUMS>(b);
 }
 
-// dynamic LDS above 64 KB needs the attribute, which applies to the CURRENT device: once per device, result kept -- a device
-// where it failed takes the run-mapped kernels
-template <int D, int RUN, int RPR, int P1>
-static bool mfma_lds_attribute() {
+// dynamic LDS above 64 KB needs the attribute, which applies to the CURRENT device: once per device, result kept in
+// attr_state [64] (0 = not tried, 1 = ok, -1 = failed) -- a device where it failed takes the run-mapped kernels
+static bool lds_attribute_once(signed char* attr_state, const void* k_sums, const void* k_plain) {
   static std::mutex attr_mu;
-  static signed char attr_state[64] = {0};   // 0 = not tried, 1 = ok, -1 = failed
   int dev = 0;
   if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return false;
   std::lock_guard<std::mutex> lock(attr_mu);
   if (attr_state[dev] == 0) {
-    const hipError_t e1 = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_reward_net_mfma<D, RUN, RPR, P1, true>),
-                                              hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024);
-    const hipError_t e2 = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_reward_net_mfma<D, RUN, RPR, P1, false>),
-                                              hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024);
+    const hipError_t e1 = hipFuncSetAttribute(k_sums, hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024);
+    const hipError_t e2 = hipFuncSetAttribute(k_plain, hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024);
     attr_state[dev] = (e1 == hipSuccess && e2 == hipSuccess) ? 1 : -1;
     (void)hipGetLastError();
   }
   return attr_state[dev] > 0;
 }
+template <int D, int RUN, int RPR, int P1>
+static bool mfma_lds_attribute() {
+  static signed char attr_state[64] = {0};
+  return lds_attribute_once(attr_state, reinterpret_cast<const void*>(&k_reward_net_mfma<D, RUN, RPR, P1, true>),
+                            reinterpret_cast<const void*>(&k_reward_net_mfma<D, RUN, RPR, P1, false>));
+}
+
+// blocks of a matrix-core launch over B samples = its partial rows: one 16-wave block per CU (LDS: 137 KB at d = 21)
+static int64_t mfma_grid(int64_t B) {
+  const int64_t grid = (B + RM_WAVES - 1) / RM_WAVES;
+  return grid > 256 ? 256 : grid;
+}
 
 template <int D, int RUN, int RPR, int P1>
 static int launch_reward_net_mfma(const RewardNetArgs& a, bool want_sums, int64_t max_rows, int* rows_out, hipStream_t st) {
   using Gm = MfmaGeom<D, RUN, RPR, P1>;
-  int64_t grid = (a.B + RM_WAVES - 1) / RM_WAVES;
-  if (grid > 256) grid = 256;  // one 16-wave block per CU (LDS: 137 KB at d = 21)
+  const int64_t grid = mfma_grid(a.B);
   const bool sums = want_sums && grid <= max_rows;
   const size_t lds = Gm::lds_floats(a.n3, a.n4, sums) * 4;
   // (return 1: the caller falls through to the run-mapped kernels)
@@ -1228,32 +1235,35 @@ namespace mfg {
 static bool mfma_shape_ok(int d, int k1, int f2, int k2, int n3, const float* fc3_w) {
   return MFG_RN_MFMA && k1 == 5 && k2 == 3 && f2 == 2 && n3 <= 16 && (d == 21 || d == 15) && (((uintptr_t)fc3_w & 7) == 0);
 }
-bool reward_net_sums_td_ready(int64_t B, int d, int k1, int f2, int k2, int n3, int n4, const float* fc3_w, int64_t max_rows) {
-  if (B < 1 || n3 < 1 || n4 < 1 || n4 > RN_MAXN || !mfma_shape_ok(d, k1, f2, k2, n3, fc3_w)) return false;
-  int64_t grid = (B + RM_WAVES - 1) / RM_WAVES;
-  if (grid > 256) grid = 256;
-  if (grid > max_rows) return false;
+bool reward_net_sums_td_ready(int64_t B, int d, const mfg_reward_net_t& n, int64_t max_rows) {
+  if (B < 1 || n.n3 < 1 || n.n4 < 1 || n.n4 > RN_MAXN || !mfma_shape_ok(d, n.k1, n.f2, n.k2, n.n3, n.fc3_w)) return false;
+  if (mfma_grid(B) > max_rows) return false;
   return d == 21 ? mfma_lds_attribute<21, 7, 3, MFG_RM_P21>() : mfma_lds_attribute<15, 5, 3, MFG_RM_P15>();
 }
 
-// sums != NULL: ask for the SUMS variant; *rows_out = partial rows written (0: this shape has no SUMS kernel -- the plain
-// forward ran and the caller takes the separate gradient kernel)
-int reward_net_forward_sums(const float* state, const float* action, int64_t B, int d, int k1, int f2, int k2, int n3, int n4,
-                            const float* conv1_w, const float* conv1_b, const float* conv2_w, const float* conv2_b,
-                            const float* fc3_w, const float* fc3_b, const float* fc4_w, const float* fc4_b,
-                            const float* out_w, const float* out_b, float keep_prob, uint64_t seed, uint64_t sample_offset,
-                            float* reward, const RnSums* sums, int* rows_out, mfg_stream_t stream, int state_T) {
+// the matrix-core launch of a population (defined with the population kernels' set-up below)
+static void launch_reward_net_pop(const RewardNetArgs& a, bool sums, const RnPop& p, int* rows_out, hipStream_t st);
+
+// (mfg_core.h).  The kernel choice: the matrix-core kernel (d = 21 / 15 at the reference's geometry; SUMS with the TD error
+// formed in the kernel), else the run-mapped kernels (the same d; SUMS over a given delta0), else k_reward_net<PP> (plain only)
+int reward_net_forward_sums(const float* state, const float* action, int64_t B, int d, const mfg_reward_net_t& n, uint64_t key,
+                            uint64_t sample_offset, float* reward, const RnSums* sums, int* rows_out, hipStream_t st, int state_T,
+                            const RnPop* pop) {
   if (rows_out) *rows_out = 0;
-  if (B < 0 || d < 1 || !state || !action || !reward || !conv1_w || !conv1_b || !conv2_w || !conv2_b || !fc3_w ||
-      !fc3_b || !fc4_w || !fc4_b || !out_w || !out_b)
+  const int k1 = n.k1, f2 = n.f2, k2 = n.k2, n3 = n.n3, n4 = n.n4;
+  // the population's stricter rule: the matrix-core geometry only (every fall-back below is a single-learner kernel)
+  if (pop && (B < 1 || !state || !action || !reward || !reward_net_pop_ready(d, &n, pop->per_learner_net, pop->K, pop->s_net)))
+    return set_error(MFG_EUNSUPPORTED, "reward_net population: not the matrix-core geometry");
+  if (B < 0 || d < 1 || !state || !action || !reward || !n.conv1_w || !n.conv1_b || !n.conv2_w || !n.conv2_b || !n.fc3_w ||
+      !n.fc3_b || !n.fc4_w || !n.fc4_b || !n.out_w || !n.out_b)
     return set_error(MFG_EINVAL, "reward_net: null pointer / bad shape");
-  if (!(keep_prob > 0.0f && keep_prob <= 1.0f)) return set_error(MFG_EINVAL, "reward_net: keep_prob must be in (0,1]");
+  if (!(n.keep_prob > 0.0f && n.keep_prob <= 1.0f)) return set_error(MFG_EINVAL, "reward_net: keep_prob must be in (0,1]");
   if (d > 32 || f2 < 1 || f2 > RN_MAXF2 || n3 < 1 || n3 > RN_MAXN || n4 < 1 || n4 > RN_MAXN || (k1 & 1) == 0 ||
       (k2 & 1) == 0 || k1 > 7 || k2 > 7)
     return set_error(MFG_EUNSUPPORTED, "reward_net: supported d <= 32, f2 <= 2, n_fc <= 32, odd kernels <= 7");
   if (B == 0) return MFG_OK;
-  RewardNetArgs a{state, action, B, d, k1, f2, k2, n3, n4, conv1_w, conv1_b, conv2_w, conv2_b, fc3_w, fc3_b,
-                  fc4_w, fc4_b, out_w, out_b, keep_prob, seed, sample_offset, reward, 0, nullptr, nullptr, nullptr, nullptr};
+  RewardNetArgs a{state, action, B, d, k1, f2, k2, n3, n4, n.conv1_w, n.conv1_b, n.conv2_w, n.conv2_b, n.fc3_w, n.fc3_b,
+                  n.fc4_w, n.fc4_b, n.out_w, n.out_b, n.keep_prob, key, sample_offset, reward, 0, nullptr, nullptr, nullptr, nullptr};
   a.state_T = state_T;
   if (sums) {
     a.delta0 = sums->delta0;
@@ -1265,6 +1275,11 @@ int reward_net_forward_sums(const float* state, const float* action, int64_t B, 
     a.td_gamma = sums->td_gamma;
     a.col_f = sums->col_f;
   }
+  // (the matrix-core SUMS kernel forms the TD error itself: it wants the critic weights and the next states, not delta0)
+  const bool sums_ptrs = sums && sums->td_w && sums->state_next && sums->col_f && sums->g && sums->delta_out && sums->part_rows;
+  // ... and in a population no room for the rows is an error, not a fall-back to the plain forward
+  if (pop && sums && !(sums_ptrs && mfma_grid(B) <= sums->max_rows))
+    return set_error(MFG_EWORKSPACE, "reward_net population: no room for the partial rows");
   const int dd = d * d;
   const int W1 = d + 2 * (k1 / 2), W2 = d + 2 * (k2 / 2);
   size_t fl = (size_t)(k1 * k1 + 1) + (size_t)(f2 * k2 * k2 + f2) + (size_t)(n4 * (n3 + d) + 2 * n4 + 1 + n3);
@@ -1279,25 +1294,25 @@ int reward_net_forward_sums(const float* state, const float* action, int64_t B, 
   //  0.527 -> 0.625 ms per 15-step episode: the block barrier in front of FC3 makes all eight waves wait for the slowest
   //  convolution, which costs more than the L2 round trips it removes.  Not kept.)
   const int64_t samples_per_block = (B + grid - 1) / grid;
-  a.w3_in_lds = (w3fl * 4 <= 64 * 1024 && samples_per_block >= MFG_RN_LDS_MIN && (((uintptr_t)fc3_w & 15) == 0)) ? 1 : 0;
+  a.w3_in_lds = (w3fl * 4 <= 64 * 1024 && samples_per_block >= MFG_RN_LDS_MIN && (((uintptr_t)n.fc3_w & 15) == 0)) ? 1 : 0;
   if (a.w3_in_lds) fl += w3fl;
   fl = (fl + 3) & ~(size_t)3;
   fl += (size_t)RN_WAVES * (W1 * W1 + W2 * W2);
   const size_t lds = fl * 4;
   const int pp = (dd + WAVE - 1) / WAVE;
-  hipStream_t st = (hipStream_t)stream;
   const bool ref_geom = (k1 == 5 && k2 == 3 && f2 == 2);
 #define RN_LAUNCH(PP)                                                                                                 \
   if (ref_geom) hipLaunchKernelGGL((k_reward_net<PP, 5, 3, 2, 0>), dim3((unsigned)grid), dim3(RN_BLOCK), lds, st, a); \
   else hipLaunchKernelGGL((k_reward_net<PP, 0, 0, 0, 0>), dim3((unsigned)grid), dim3(RN_BLOCK), lds, st, a);
   // w3 rows are read as float2 at even offsets: needs an 8-byte aligned fc3_w when it is not staged in LDS
-  const bool runs_ok = ref_geom && (a.w3_in_lds || (((uintptr_t)fc3_w & 7) == 0));
+  const bool runs_ok = ref_geom && (a.w3_in_lds || (((uintptr_t)n.fc3_w & 7) == 0));
   const bool want_sums = sums && sums->delta0 && sums->g && sums->delta_out && sums->part_rows && grid <= sums->max_rows;
-  // (the matrix-core SUMS kernel forms the TD error itself: it wants the critic weights and the next states, not delta0)
-  const bool sums_ptrs = sums && sums->td_w && sums->state_next && sums->col_f && sums->g && sums->delta_out && sums->part_rows;
-  const bool mfma_ok = mfma_shape_ok(d, k1, f2, k2, n3, fc3_w);
+  const bool mfma_ok = mfma_shape_ok(d, k1, f2, k2, n3, n.fc3_w);
   bool mfma_done = false;
-  if (mfma_ok) {
+  if (pop) {
+    launch_reward_net_pop(a, sums != nullptr, *pop, rows_out, st);
+    mfma_done = true;
+  } else if (mfma_ok) {
     int rows = 0;
     const int rc = d == 21 ? launch_reward_net_mfma<21, 7, 3, MFG_RM_P21>(a, sums_ptrs, sums_ptrs ? sums->max_rows : 0, &rows, st)
                            : launch_reward_net_mfma<15, 5, 3, MFG_RM_P15>(a, sums_ptrs, sums_ptrs ? sums->max_rows : 0, &rows, st);
@@ -1337,20 +1352,9 @@ int reward_net_forward_sums(const float* state, const float* action, int64_t B, 
 // ---- populations (mfg_irl_population.h) ----
 template <int D, int RUN, int RPR, int P1>
 static bool mfma_lds_attribute_pop() {
-  static std::mutex attr_mu;
   static signed char attr_state[64] = {0};
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return false;
-  std::lock_guard<std::mutex> lock(attr_mu);
-  if (attr_state[dev] == 0) {
-    const hipError_t e1 = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_reward_net_mfma_pop<D, RUN, RPR, P1, true>),
-                                              hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024);
-    const hipError_t e2 = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_reward_net_mfma_pop<D, RUN, RPR, P1, false>),
-                                              hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024);
-    attr_state[dev] = (e1 == hipSuccess && e2 == hipSuccess) ? 1 : -1;
-    (void)hipGetLastError();
-  }
-  return attr_state[dev] > 0;
+  return lds_attribute_once(attr_state, reinterpret_cast<const void*>(&k_reward_net_mfma_pop<D, RUN, RPR, P1, true>),
+                            reinterpret_cast<const void*>(&k_reward_net_mfma_pop<D, RUN, RPR, P1, false>));
 }
 
 bool reward_net_pop_ready(int d, const mfg_reward_net_t* net, int per_learner_net, int K, int64_t net_stride) {
@@ -1367,43 +1371,16 @@ bool reward_net_pop_ready(int d, const mfg_reward_net_t* net, int per_learner_ne
 template <int D, int RUN, int RPR, int P1>
 static void launch_reward_net_mfma_pop(const RewardNetArgs& a, bool sums, const RnPop& p, int* rows_out, hipStream_t st) {
   using Gm = MfmaGeom<D, RUN, RPR, P1>;
-  int64_t grid = (a.B + RM_WAVES - 1) / RM_WAVES;  // (the single launch's grid for one learner)
-  if (grid > 256) grid = 256;
+  const int64_t grid = mfma_grid(a.B);  // (the single launch's grid for one learner)
   const size_t lds = Gm::lds_floats(a.n3, a.n4, sums) * 4;
   const dim3 g((unsigned)grid, (unsigned)(p.n_y > 0 ? p.n_y : p.K));
   if (sums) hipLaunchKernelGGL((k_reward_net_mfma_pop<D, RUN, RPR, P1, true>), g, dim3(RM_BLOCK), lds, st, a, p);
   else hipLaunchKernelGGL((k_reward_net_mfma_pop<D, RUN, RPR, P1, false>), g, dim3(RM_BLOCK), lds, st, a, p);
   if (rows_out) *rows_out = sums ? (int)grid : 0;
 }
-
-int reward_net_forward_pop(const float* state, const float* action, int64_t B, int d, const mfg_reward_net_t* net,
-                           uint64_t sample_offset, float* reward, const RnSums* sums, int* rows_out, const RnPop& p, hipStream_t st,
-                           int state_T) {
-  if (rows_out) *rows_out = 0;
-  if (B < 1 || !state || !action || !reward || !reward_net_pop_ready(d, net, p.per_learner_net, p.K, p.s_net))
-    return set_error(MFG_EUNSUPPORTED, "reward_net population: not the matrix-core geometry");
-  if (!(net->keep_prob > 0.0f && net->keep_prob <= 1.0f)) return set_error(MFG_EINVAL, "reward_net: keep_prob must be in (0,1]");
-  RewardNetArgs a{state, action, B, d, net->k1, net->f2, net->k2, net->n3, net->n4, net->conv1_w, net->conv1_b, net->conv2_w,
-                  net->conv2_b, net->fc3_w, net->fc3_b, net->fc4_w, net->fc4_b, net->out_w, net->out_b, net->keep_prob, 0,
-                  sample_offset, reward, 0, nullptr, nullptr, nullptr, nullptr};
-  a.state_T = state_T;
-  const bool want = sums != nullptr;
-  if (want) {
-    int64_t grid = (B + RM_WAVES - 1) / RM_WAVES;
-    if (grid > 256) grid = 256;
-    if (!(sums->td_w && sums->state_next && sums->col_f && sums->g && sums->delta_out && sums->part_rows) || grid > sums->max_rows)
-      return set_error(MFG_EWORKSPACE, "reward_net population: no room for the partial rows");
-    a.gsc = sums->g;
-    a.delta_out = sums->delta_out;
-    a.part_rows = sums->part_rows;
-    a.td_w = sums->td_w;
-    a.state_next = sums->state_next;
-    a.td_gamma = sums->td_gamma;
-    a.col_f = sums->col_f;
-  }
-  if (d == 21) launch_reward_net_mfma_pop<21, 7, 3, MFG_RM_P21>(a, want, p, rows_out, st);
-  else launch_reward_net_mfma_pop<15, 5, 3, MFG_RM_P15>(a, want, p, rows_out, st);
-  return hipGetLastError() == hipSuccess ? MFG_OK : set_error(MFG_ELAUNCH, "reward_net population: launch failed");
+static void launch_reward_net_pop(const RewardNetArgs& a, bool sums, const RnPop& p, int* rows_out, hipStream_t st) {
+  if (a.d == 21) launch_reward_net_mfma_pop<21, 7, 3, MFG_RM_P21>(a, sums, p, rows_out, st);
+  else launch_reward_net_mfma_pop<15, 5, 3, MFG_RM_P15>(a, sums, p, rows_out, st);
 }
 }  // namespace mfg
 
@@ -1412,8 +1389,8 @@ extern "C" int mfg_reward_net_forward(const float* state, const float* action, i
                                       const float* conv2_b, const float* fc3_w, const float* fc3_b, const float* fc4_w,
                                       const float* fc4_b, const float* out_w, const float* out_b, float keep_prob,
                                       uint64_t seed, uint64_t sample_offset, float* reward, mfg_stream_t stream) {
-  return mfg::reward_net_forward_sums(state, action, B, d, k1, f2, k2, n3, n4, conv1_w, conv1_b, conv2_w, conv2_b, fc3_w, fc3_b,
-                                      fc4_w, fc4_b, out_w, out_b, keep_prob, seed, sample_offset, reward, nullptr, nullptr, stream, 0);
+  const mfg_reward_net_t net{k1, f2, k2, n3, n4, conv1_w, conv1_b, conv2_w, conv2_b, fc3_w, fc3_b, fc4_w, fc4_b, out_w, out_b, keep_prob};
+  return mfg::reward_net_forward_sums(state, action, B, d, net, seed, sample_offset, reward, nullptr, nullptr, (hipStream_t)stream);
 }
 
 extern "C" int mfg_reward_net_forward_pop(const float* state, const float* action, int64_t s_state, int64_t s_action, int64_t N,
@@ -1453,7 +1430,7 @@ extern "C" int mfg_reward_net_forward_pop(const float* state, const float* actio
   rp.key = (const uint64_t*)scratch;
   rp.learner = (const int32_t*)((const char*)scratch + (size_t)n * 8);
   rp.n_y = n;
-  return reward_net_forward_pop(state, action, N, d, net, sample_offset, reward, nullptr, nullptr, rp, st, 0);
+  return reward_net_forward_sums(state, action, N, d, *net, 0, sample_offset, reward, nullptr, nullptr, st, 0, &rp);
 }
 
 #ifdef MFG_RN_STAMPS

@@ -43,8 +43,8 @@ def _population(mode, d, K, B, precision, nets, seeds, thetas, shifts, alphas, w
                             w0=w0, pi0=_table(d), update_every=mode, precision=precision, device=dev)
 
 
-def _single(mode, d, B, precision, net, seed, theta, shift, alpha, w0, E, gamma, constant, lrc, lra, first_episode, dev):
-    """Learner outputs from the single-learner native IRL calls, as AC_IRL.train issues them."""
+def _single(mode, d, B, precision, net, seed, theta, shift, alpha, w0, E, gamma, constant, lrc, lra, first_episode, dev, T=T):
+    """Learner outputs from the single-learner native IRL calls, as AC_IRL.train issues them (T env steps per episode)."""
     from discrete_mean_field_game_amd import ops
     from discrete_mean_field_game_amd.parallel import lr_scales
     F = ops.num_features(d)
@@ -142,6 +142,79 @@ def test_population_equals_single_learner_calls(dev, case):
         for key, v in got.items():
             assert torch.equal(v, ref[key].view(v.shape)), (k, key)
         assert np.array_equal(ret[k], ref['acc'].cpu().numpy()), k
+
+
+@pytest.mark.parametrize('mode', ['step', 'rollout'])
+def test_even_T_population_equals_single_learner_calls(dev, mode):
+    """The native population calls at an even number of env steps per episode (the class fixes T = 15): the step flow's buffer
+    alternation and theta slots depend on the parity of T."""
+    from discrete_mean_field_game_amd import ops
+    Te, d, K, B, E, gamma, fe = 4, 21, 3, 1000, 2, 0.9, 0
+    thetas, shifts, alphas, seeds = _settings(K, d)
+    nets = _nets(d, 8, 0.4, K, 40 + d, dev)
+    np.random.seed(5)
+    F = ops.num_features(d)
+    w0 = np.stack([np.random.randn(F) * 0.1 for _ in range(K)])
+    lrc = [0.1 * (1 + 0.5 * k) for k in range(K)]
+    lra = [0.001 * (1 + 0.25 * k) for k in range(K)]
+    pop = _population(mode, d, K, B, 'mixed', nets, seeds, thetas, shifts, alphas, w0, dev)
+    f32, f64 = dict(dtype=torch.float32, device=dev), dict(dtype=torch.float64, device=dev)
+    G = torch.zeros(K, F + 3, **f64)
+    ws = torch.zeros(K, ops.pop_workspace_slice(B, d, Te) // 8, **f64)
+    acc = torch.zeros(K, E, **f64)
+    n = (K, B) if mode == 'step' else (K, B, Te)
+    bufs = dict(P=torch.empty(*n, d, d, **f32), reward=torch.empty(*n, **f32), delta=torch.empty(*n, **f64),
+                g=torch.empty(*n, **f64))
+    args = (pop._theta, pop._shifts_dev, pop._alphas_dev, pop._w, gamma, torch.tensor(lrc, **f64), torch.tensor(lra, **f64),
+            pop._seeds_dev, pop._net_struct, True, pop._rn_seeds_dev, torch.zeros(K, dtype=torch.int64, device=dev), G, ws, bufs)
+    if mode == 'step':
+        pi = torch.empty(K, B, d, **f32)
+        bufs['scratch'] = torch.empty(K, B, d, **f32)
+        ops.train_episodes_irl_pop(pop._mat_pi0_dev, pi, Te, E, fe + 1, 0, *args, reward_acc=acc, net_stride=pop._net_stride)
+    else:
+        bufs.update(pi_traj=torch.empty(K, B, Te + 1, d, **f32), pi_last=torch.empty(K, B, d, **f32))
+        ops.train_rollouts_irl_pop(pop._mat_pi0_dev, Te, E, fe + 1, 0, *args, reward_acc=acc, net_stride=pop._net_stride)
+        pi = bufs['pi_last']
+    torch.cuda.synchronize()
+    for k in range(K):
+        ref = _single(mode, d, B, 'mixed', nets[k], seeds[k], thetas[k], shifts[k], alphas[k], w0[k], E, gamma, 0, lrc[k], lra[k],
+                      fe, dev, T=Te)
+        got = dict(theta=pop._theta[k:k + 1], w=pop._w[k], G=G[k], pi=pi[k], P=bufs['P'][k], reward=bufs['reward'][k],
+                   delta=bufs['delta'][k], g=bufs['g'][k], acc=acc[k] * Te if mode == 'rollout' else acc[k])
+        if mode == 'rollout':
+            got['pi_traj'] = bufs['pi_traj'][k]
+        for key, v in got.items():
+            assert torch.equal(v, ref[key].view(v.shape)), (k, key)
+
+
+@pytest.mark.parametrize('Tn', [3, 4])
+def test_given_start_states_equal_drawn_ones(dev, Tn):
+    """mfg_train_episode_irl on given start states (final states copied back into `pi` after an odd number of steps) against
+    mfg_train_episode_irl_draw, which draws the same states in its first step kernel and alternates its buffers instead."""
+    from discrete_mean_field_game_amd import ops
+    d, B, seed, step0, gamma = 21, 1000, 11, 30, 0.9
+    net = _nets(d, 8, 0.4, 1, 61, dev)[0]
+    mat = torch.as_tensor(np.ascontiguousarray(_table(d), dtype=np.float32), device=dev)
+    F = ops.num_features(d)
+    np.random.seed(6)
+    w0 = torch.as_tensor(np.random.randn(F) * 0.1, device=dev)
+    outs = []
+    for drawn in (True, False):
+        th = torch.tensor([8.64], dtype=torch.float64, device=dev)
+        w = w0.clone()
+        G = torch.zeros(F + 3, dtype=torch.float64, device=dev)
+        acc = torch.zeros(1, dtype=torch.float64, device=dev)
+        ws = ops.workspace(B, d, dev)
+        bufs = dict(ops.episode_buffers(B, d, dev), P=torch.empty(B, 1, d, d, dtype=torch.float32, device=dev))
+        pi = torch.empty(B, d, dtype=torch.float32, device=dev) if drawn else ops.draw_start(mat, B, seed, step0)[1]
+        ops.train_episode_irl(pi, Tn, th, 0.02, 1e4, w, gamma, 0.1, 0.001, net, G, ws, bufs, seed=seed, first_step=step0,
+                              rn_seed=seed + 0x5EED, rn_call0=7, rn_sample_offset=0, reward_acc=acc, precision='mixed',
+                              mat_pi0=mat if drawn else None)
+        torch.cuda.synchronize()
+        outs.append(dict(pi=pi, theta=th, w=w, G=G, acc=acc, P=bufs['P'], reward=bufs['reward'], delta=bufs['delta'], g=bufs['g']))
+    for key, v in outs[0].items():
+        assert torch.equal(v, outs[1][key]), key
+    assert float(outs[0]['theta']) != 8.64 and not torch.equal(outs[0]['w'], w0)
 
 
 @pytest.mark.parametrize('mode', ['step', 'rollout'])
