@@ -234,7 +234,7 @@ __device__ __forceinline__ void policy_accumulate(const PolicyElem<FAST>& e, con
                                                   float v, double& A, double& D, double& gacc) {
   if (!TD) return;
   if (FAST) {
-    const float lnv = (!SAMPLE && v == 0.0f) ? (float)(LOG_ZERO_P * INV_LN2) : __builtin_amdgcn_logf(v);  // log2 units
+    const float lnv = (!SAMPLE && v == 0.0f) ? (float)(LOG_ZERO_P * INV_LN2) : (SAMPLE ? __builtin_amdgcn_logf(v) : log2_pos(v));  // log2 units
     A += (double)e.al_f;
     D += (double)e.ad_f;
     gacc += (double)__builtin_fmaf(lnv, e.ad_f, -e.psi_ad);
@@ -263,7 +263,9 @@ __device__ __forceinline__ PolicyTerms<FAST> policy_terms(const PolicyElem<FAST>
     const float lnv = v;
 #else
     // log2 units: the h table is stored divided by ln 2 (mfg_device.h), the sums are scaled by ln 2 once per row / step
-    const float lnv = (!SAMPLE && v == 0.0f) ? (float)(LOG_ZERO_P * INV_LN2) : __builtin_amdgcn_logf(v);
+    // (sampling: the hardware logarithm as it is -- a variate below 2^-126, where it returns -inf, can only come out of the
+    //  rare continuation, which then redoes the term with log2_pos: policy_term_denormal)
+    const float lnv = (!SAMPLE && v == 0.0f) ? (float)(LOG_ZERO_P * INV_LN2) : (SAMPLE ? __builtin_amdgcn_logf(v) : log2_pos(v));
 #endif
     o.al = e.al_f;
     o.ad = e.ad_f;
@@ -275,6 +277,11 @@ __device__ __forceinline__ PolicyTerms<FAST> policy_terms(const PolicyElem<FAST>
     o.gt = (-digamma_pos(e.al_d) + lnv) * e.ad_d;
   }
   return o;
+}
+
+// The score term of a sampled element whose variate lies in the fp32 denormal range (see log2_pos, mfg_device.h).
+__device__ __forceinline__ float policy_term_denormal(const PolicyElem<true>& e, float v) {
+  return __builtin_fmaf(log2_pos(v), e.ad_f, -e.psi_ad);
 }
 
 // NE (1..4) matrix elements from ONE Philox block (keyed by elem[0]).  Elements 2h, 2h+1 share a Box-Muller pair.
@@ -378,6 +385,17 @@ __device__ __forceinline__ void sample_elems_gq(const CoreArgs& a, double theta,
         if (!ALLVALID && !valid[e]) y[e] = 0.0f;
       }
     }
+    if constexpr (TD && FAST) {
+      // a boosted variate (shape < 1: the continuation above) may land below 2^-126, where the hardware logarithm of
+      // policy_terms returned -inf: redo those terms.  Behind the same wave-uniform test: nothing on the hot path.
+      if (__builtin_expect(any_cold, 0)) {
+#pragma unroll
+        for (int u = 0; u < PW; ++u) {
+          const int e = PW * h + u;
+          if (u < n2 && (ALLVALID || valid[e]) && y[e] < FLT_MIN_NORMAL) gt[e] = policy_term_denormal(pe[u], y[e]);
+        }
+      }
+    }
   }
 }
 
@@ -474,6 +492,9 @@ __device__ __forceinline__ void sample_tail1(const CoreArgs& a, double theta, co
     al = t.al;
     ad = t.ad;
     gt = t.gt;
+    if constexpr (FAST) {
+      if (__builtin_expect(cm != 0, 0) && y < FLT_MIN_NORMAL) gt = policy_term_denormal(pe, y);  // (see sample_elems_gq)
+    }
   }
 }
 
@@ -595,10 +616,11 @@ __device__ __forceinline__ void core_small_body(const CoreArgs& a) {
   }
   const ThetaSplit ts = theta_split(theta, a.shift);
   const float inv_d = 1.0f / (float)d;
-  // mixed sampling kernels: separable e^z = E_j F_i (mfg_device.h), in range while |theta| (1/2 + |shift|) <= 86; beyond
-  // that the launch reports MFG_STATUS_MIXED_RANGE and its outputs are NaN (precision 'f64' has no such limit).
+  // mixed kernels: e^z in fp32 -- separable E_j F_i when sampling, one exponential on given actions (mfg_device.h) -- in range
+  // while |theta| (1 + |shift|) <= 86; beyond that the launch reports MFG_STATUS_MIXED_RANGE and its outputs are unspecified
+  // (precision 'f64' has no such limit).
   constexpr bool sep = SAMPLE && FAST;
-  if (sep) report_sep_range(a.status, theta, a.shift);
+  if (FAST && (SAMPLE || TD)) report_sep_range(a.status, theta, a.shift);
   // first tile's start state: the load is issued BEFORE the weight staging so that its latency (L2 / HBM, ~1 us) overlaps
   // the staging instead of stalling the first use (a T = 1 launch spent 4 300 of its 20 900 cycles waiting for it)
   if constexpr (STEP != 1) {
@@ -1325,7 +1347,7 @@ void k_core_large(CoreArgs a) {
   const double theta = *a.theta;
   const ThetaSplit ts = theta_split(theta, a.shift);
   constexpr bool sep = SAMPLE && FAST;
-  if (sep) report_sep_range(a.status, theta, a.shift);
+  if (FAST && (SAMPLE || TD)) report_sep_range(a.status, theta, a.shift);  // (see core_small_body)
   using TT = typename PolicyTerms<FAST>::T;
   const int64_t nw = (int64_t)gridDim.x * WAVES;
   for (int64_t b = (int64_t)blockIdx.x * WAVES + wv; b < a.B; b += nw) {

@@ -340,14 +340,19 @@ __device__ __forceinline__ void softplus_sigmoid_fast(float zh, float zl, float&
 // F_i = e^{-theta (pi_i + shift - 1/2)}: the lane that owns state entry i evaluates E_i, F_i once per env step (fp64
 // argument, hardware exp2 on its fp32 head, first-order correction for the tail: ~1e-7 relative) and an element costs ONE
 // multiply instead of (hi/lo product, v_exp, correction).  Both factors are centred on pi = 1/2 (state entries lie in
-// [0, 1]), so they stay inside the fp32 range while |theta| (1/2 + |shift|) <= 86.  There is NO per-element fall-back
-// beyond that: the sampling kernels report MFG_STATUS_MIXED_RANGE (report_sep_range, include/mfg_hip.h) and their outputs
-// are NaN; precision f64 has no limit.
+// [0, 1]), so each stays inside the fp32 range while |theta| (1/2 + |shift|) <= 86.  That is not enough: their PRODUCT is
+// e^z, z = theta (pi_j - pi_i - shift), and |z| reaches |theta| (1 + |shift|) on a state with pi_j - pi_i near +-1 -- above
+// z = 88.7 the product is +inf and softplus_sigmoid_e returns NaN (inf * rcp(inf)), below -87.3 it is subnormal; the h table
+// ends at z = 88 as well.  The range of the mixed kernels is therefore |theta| (1 + |shift|) <= 86, which keeps every e^z a
+// normal fp32 number whatever the state.  There is NO per-element fall-back beyond that: the kernels report
+// MFG_STATUS_MIXED_RANGE (report_sep_range, include/mfg_hip.h) and their outputs are unspecified (NaN where a product
+// overflowed); precision f64 has no limit.  The given-P kernels form e^z from one fp32 exponential (softplus_sigmoid_fast):
+// same range, same report.
 constexpr double SEP_CENTRE = 0.5;
 constexpr double SEP_LIMIT = 86.0;  // ln(fp32 max) = 88.7, ln(fp32 min normal) = -87.3; margin for the fp32 head / tail split
 __device__ __forceinline__ void report_sep_range(unsigned* status, double theta, double shift) {
   // written as !(x <= limit) so that a NaN theta is reported too; one lane of the launch stores the bit (host-mapped word)
-  if (status && blockIdx.x == 0 && threadIdx.x == 0 && !(fabs(theta) * (SEP_CENTRE + fabs(shift)) <= SEP_LIMIT))
+  if (status && blockIdx.x == 0 && threadIdx.x == 0 && !(fabs(theta) * (1.0 + fabs(shift)) <= SEP_LIMIT))
     __hip_atomic_fetch_or(status, 1u /* MFG_STATUS_MIXED_RANGE */, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 __device__ __forceinline__ float exp_f64arg(double z) {
@@ -441,6 +446,16 @@ __device__ __forceinline__ float fast_rcp_f32_of_f64(double x) {
   float r = __builtin_amdgcn_rcpf(xf);
   r = __builtin_fmaf(__builtin_fmaf(-xf, r, 1.0f), r, r);
   return r;
+}
+
+// log2(v) for ANY positive fp32 v.  v_log_f32 takes a denormal argument as zero and returns -inf; a gamma variate of a small
+// shape (the U^(1/a) boost) or a stored probability can lie below 2^-126, and its score term log2(v) alpha' must stay finite.
+// The product with 2^32 is exact (fp32 denormals are kept by v_mul_f32).  Used off the hot path only: by the given-P kernels
+// and by the rare continuation of the sampling loops (sample_elems_gq / sample_tail1, mfg_core.h).
+constexpr float FLT_MIN_NORMAL = 1.17549435e-38f;
+__device__ __forceinline__ float log2_pos(float v) {
+  const bool sub = v < FLT_MIN_NORMAL;
+  return __builtin_amdgcn_logf(sub ? v * 4294967296.0f : v) - (sub ? 32.0f : 0.0f);
 }
 
 // Split-constant helper: z = theta * (pj - pi - shift) evaluated in fp32 with the rounding of the

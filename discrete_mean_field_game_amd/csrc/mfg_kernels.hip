@@ -1885,7 +1885,7 @@ static StatusWord status_word() {
 }
 static int status_error(unsigned bits) {
   if (bits & MFG_STATUS_MIXED_RANGE)
-    return fail(MFG_ERANGE, "%s", "an earlier mixed-precision sampling launch ran with |theta| (1/2 + |shift|) > 86 (or theta not "
+    return fail(MFG_ERANGE, "%s", "an earlier mixed-precision launch ran with |theta| (1 + |shift|) > 86 (or theta not "
                                   "finite): the fp32 factors of the separable exponential left their range and that launch's "
                                   "outputs are NaN; use MFG_PRECISION_F64 / precision='f64' for such policies, then mfg_clear_status()");
   return fail(MFG_ERANGE, "device status word = 0x%x", bits);

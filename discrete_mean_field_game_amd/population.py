@@ -113,7 +113,7 @@ def evaluate_policies(emp, thetas, shifts, alpha_scales, seeds, first_step, repe
     metrics = ops.evaluate_pop(emp32, emp64, thetas, shifts, alpha_scales, seeds, first_step=first_step, repeats=repeats,
                                precision=precision).cpu().numpy()
     if precision == 'mixed' and ctx.status(synchronize=True):
-        raise L.MfgError('a mixed-precision evaluation ran a policy with |theta| (1/2 + |shift|) > 86 (or theta not finite): '
+        raise L.MfgError('a mixed-precision evaluation ran a policy with |theta| (1 + |shift|) > 86 (or theta not finite): '
                          'its metrics are NaN; use precision=\'f64\'')
     return metrics
 
@@ -297,7 +297,7 @@ class _Population:
         self._rng_step += num_episodes * self.episode_steps
         out = acc.cpu().numpy()
         if self.precision == 'mixed' and self._ctx.status(synchronize=True):
-            raise L.MfgError('a mixed-precision sampling launch of this population ran with |theta| (1/2 + |shift|) > 86 '
+            raise L.MfgError('a mixed-precision sampling launch of this population ran with |theta| (1 + |shift|) > 86 '
                              '(or theta not finite): its outputs are NaN; use precision=\'f64\', then clear_status()')
         return out
 

@@ -92,14 +92,16 @@ int mfg_set_core_mapping(int mode);
 int mfg_init(void);
 
 /* Device status word.  The mixed-precision SAMPLING kernels form e^{theta (pi_j - pi_i - shift)} as a product of two fp32
- * factors e^{theta (pi_j - 1/2)} e^{-theta (pi_i + shift - 1/2)}; that is exact business as usual while
- * |theta| (1/2 + |shift|) <= 86 (theta ~ 130 at the reference's shift 0.16; the reference trains at theta ~ 9).  theta lives
- * on the device, so the host cannot check it before a launch: a sampling kernel that finds theta outside that range (or
- * not finite) sets MFG_STATUS_MIXED_RANGE in a host-visible status word and its outputs are NaN.  Every later call that
+ * factors e^{theta (pi_j - 1/2)} e^{-theta (pi_i + shift - 1/2)}; their product, and the single fp32 exponential of the
+ * mixed-precision kernels on given actions, is a normal fp32 number on every state while
+ * |theta| (1 + |shift|) <= 86 (theta ~ 74 at the reference's shift 0.16; the reference trains at theta ~ 9).  theta lives
+ * on the device, so the host cannot check it before a launch: a mixed-precision kernel that finds theta outside that range (or
+ * not finite) sets MFG_STATUS_MIXED_RANGE in a host-visible status word and its outputs are unspecified (NaN where e^z
+ * overflowed).  Every later call that
  * launches a mixed-precision SAMPLING kernel (sample / rollout / train entry points with MFG_PRECISION_MIXED) then fails
  * with MFG_ERANGE until mfg_clear_status() -- a diverged run stops with an error code instead of carrying NaNs.  The word is
- * one per CONTEXT (below; one per device and process for callers that never bind one): launches the condition does not concern (MFG_PRECISION_F64, kernels on given actions) are
- * not refused, so another model instance or thread on the device keeps working.  mfg_status() reads the word without
+ * one per CONTEXT (below; one per device and process for callers that never bind one): launches of MFG_PRECISION_F64 kernels and of kernels on given actions are
+ * not refused (the latter report, but are never held up), so another model instance or thread on the device keeps working.  mfg_status() reads the word without
  * synchronising (synchronise the stream first to be sure a given launch has reported); it returns MFG_OK or MFG_ERANGE and
  * stores the bits in *bits_host (may be NULL). */
 enum { MFG_STATUS_MIXED_RANGE = 1 };

@@ -768,10 +768,12 @@ def test_step_kernel_fused_batch_sums(dev, d, B, precision):
 
 def test_mixed_sampler_range_of_the_separable_exponential(dev):
     """Mixed precision forms e^{theta (pi_j - pi_i - shift)} as E_j F_i, fp32 factors centred on pi = 1/2.  Inside the
-    documented range, |theta| (1/2 + |shift|) <= 86, the sampler is still exact (KS on Beta marginals at theta = 40 and,
-    on a peaked state, at theta = 100, where the uncentred factors of round 2 overflowed).  Beyond it the launch must not
-    fail silently: the outputs are NaN, the device status word reports MFG_STATUS_MIXED_RANGE, and every later
-    mixed-precision sampling launch is refused with MFG_ERANGE until mfg_clear_status(); precision 'f64' has no such limit."""
+    documented range, |theta| (1 + |shift|) <= 86 -- the product e^z, not only each factor, is a normal fp32 number on every
+    state -- the sampler is still exact (KS on Beta marginals at theta = 40 and, on a peaked state, at theta = 78).  Beyond it
+    the launch must not fail silently: the device status word reports MFG_STATUS_MIXED_RANGE (theta = 100 at shift 0.1, which
+    the factors alone survive: 100 * 0.6 <= 86, but a state with pi_j - pi_i near 1 does not: tests/test_gpu_score_regimes.py
+    steep.5; and theta = 200, where the outputs are NaN), and every later mixed-precision sampling launch is refused with
+    MFG_ERANGE until mfg_clear_status(); precision 'f64' has no such limit."""
     from scipy import stats
     from discrete_mean_field_game_amd import _lib as L
     o_ = ops()
@@ -780,7 +782,7 @@ def test_mixed_sampler_range_of_the_separable_exponential(dev):
     pi1 = np.array([0.05, 0.3, 0.1, 0.35, 0.15, 0.05], dtype=np.float32)
     pi = np.repeat(pi1[None], B, 0)
     shift, scale = 0.1, 50.0
-    for theta, pi1 in ((40.0, pi1), (100.0, np.array([0.97, 0.006, 0.006, 0.006, 0.006, 0.006], dtype=np.float32))):
+    for theta, pi1 in ((40.0, pi1), (78.0, np.array([0.97, 0.006, 0.006, 0.006, 0.006, 0.006], dtype=np.float32))):
         pi = np.repeat(pi1[None], B, 0)
         P = o_.sample_dirichlet(t32(pi, dev), t64([theta], dev), shift, scale, seed=11, precision='mixed').cpu().numpy().astype(np.float64)
         assert np.all(np.isfinite(P)) and np.allclose(P.sum(-1), 1.0, atol=1e-5)
@@ -792,9 +794,14 @@ def test_mixed_sampler_range_of_the_separable_exponential(dev):
             ks = stats.kstest(P[:, i, j], stats.beta(a, b).cdf)
             assert ks.pvalue > 1e-4, (theta, i, j, a, b, ks)
     assert o_.status() == 0
-    # |theta| (1/2 + |shift|) = 120 > 86: out of range
-    big = t64([200.0], dev)
     peaked = np.repeat(np.array([[0.97, 0.006, 0.006, 0.006, 0.006, 0.006]], dtype=np.float32), 64, 0)
+    # |theta| (1 + |shift|) = 110 > 86 although each factor is in range (100 * 0.6 = 60): reported
+    o_.sample_dirichlet(t32(peaked, dev), t64([100.0], dev), shift, scale, seed=11, precision='mixed')
+    assert o_.status() == L.STATUS_MIXED_RANGE
+    o_.clear_status()
+    assert o_.status() == 0
+    # |theta| (1 + |shift|) = 220 > 86: out of range, and the factors overflow
+    big = t64([200.0], dev)
     Pm = o_.sample_dirichlet(t32(peaked, dev), big, shift, scale, seed=11, precision='mixed')
     assert not bool(torch.isfinite(Pm).all())                     # NaN, not a silently wrong sample
     assert o_.status() == L.STATUS_MIXED_RANGE

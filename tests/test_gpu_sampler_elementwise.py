@@ -22,8 +22,6 @@ D_LARGE = [65, 100, 128, 129, 192, 193, 256, 320, 448, 449, 512]
 BIG = {15, 21, 128, 256}           # >= 1e6 elements per case there, >= 2.5e5 elsewhere
 REGIMES = ['policy', 'mid', 'small', 'straddle']
 STEPS = [0, 7, 0xFFFFFFFE, 0xFFFFFFFF]
-STRADDLE_TARGETS = [1.0, 2.0 / 3.0, 1.0 / 3.0]
-X0 = float(np.log(np.e - 1.0))     # softplus(X0) = 1
 
 
 @pytest.fixture(scope='module')
@@ -52,25 +50,7 @@ def _ref():
     return sampler_ref
 
 
-def regime_case(regime, B, d, rs, k=0, jitter=1e-6):
-    """(pi [B, d] fp32, theta, shift, scale) of a shape regime."""
-    if regime == 'policy':           # the reference policy (mfg_ac2.py:832): shapes 1e3 .. 1e5
-        return rs.dirichlet(np.ones(d), size=B).astype(np.float32), 8.86349, 0.16, 12000.0
-    if regime == 'mid':              # shapes ~1 .. 100
-        pi = rs.uniform(0.0, 0.8, size=(B, d)).astype(np.float32)
-        return pi, 4.0, 0.0, 30.0
-    if regime == 'small':            # every shape below 1, down to ~0.02 (the boost and its underflow)
-        pi = rs.uniform(0.2, 0.8, size=(B, d)).astype(np.float32)
-        return pi, 4.0, 0.3, 0.65
-    # straddle: half the state entries ~1e-6, half X0 + jitter: x = pi_j - pi_i lands on +X0, -X0 and ~0, so with theta = 1,
-    # shift = 0 the shapes are target * {1, softplus(-X0), ln 2} (softplus(X0) = 1).  f64 (fp64 alpha, one fp32 rounding):
-    # jitter 1e-6, a dense band around the target that resolves the rounding of fl32(alpha * scale) at 1;  mixed (alpha to
-    # ~2e-7): jitter 0.1, so that the classification's near ties stay rare
-    tgt = STRADDLE_TARGETS[(k // 4) % len(STRADDLE_TARGETS)]
-    lo = rs.uniform(0.0, 2e-6, size=(B, d))
-    hi = X0 + rs.uniform(-jitter, jitter, size=(B, d))
-    pi = np.where(rs.rand(B, d) < 0.5, lo, hi).astype(np.float32)
-    return pi, 1.0, 0.0, tgt
+from oracle.score_ref import regime_case  # noqa: E402  (shared with tests/test_gpu_score_regimes.py)
 
 
 def _batch(d, big=False):
