@@ -160,6 +160,22 @@ SIGNATURES['mfg_reward_net_train_steps_pop'] = (_i32, [_p, _p, _p, _i64, _i32, _
                                                        _p, _i64, _p, _p, _sz, _i32, _i32, _i32, _i32, _i32, _i32, C.c_float,
                                                        _i32, _f64, _f64, _f64, _p, _p, _sz, _p])
 
+
+class RnGeomStruct(C.Structure):
+    """mfg_rn_geom_t of include/mfg_hip.h: one learner's n_fc3, n_fc4, keep_prob and l1_l2 flag (16 bytes)."""
+    _fields_ = [('n3', C.c_int32), ('n4', C.c_int32), ('keep_prob', C.c_float), ('l1l2', C.c_int32)]
+
+
+# the same calls with a per-learner geometry table (host copy, device copy) behind net_stride / k2
+SIGNATURES['mfg_train_episodes_irl_pop_nets'] = (_i32, SIGNATURES['mfg_train_episodes_irl_pop_calls'][1][:25] + [_p, _p]
+                                                 + SIGNATURES['mfg_train_episodes_irl_pop_calls'][1][25:])
+SIGNATURES['mfg_train_rollouts_irl_pop_nets'] = (_i32, SIGNATURES['mfg_train_rollouts_irl_pop_calls'][1][:23] + [_p, _p]
+                                                 + SIGNATURES['mfg_train_rollouts_irl_pop_calls'][1][23:])
+SIGNATURES['mfg_reward_net_forward_pop_nets'] = (_i32, SIGNATURES['mfg_reward_net_forward_pop'][1][:9] + [_p, _p]
+                                                 + SIGNATURES['mfg_reward_net_forward_pop'][1][9:])
+_steps = SIGNATURES['mfg_reward_net_train_steps_pop'][1]
+SIGNATURES['mfg_reward_net_train_steps_pop_nets'] = (_i32, _steps[:9] + [_p, _p] + _steps[11:26] + _steps[28:])
+
 SIGNATURES['mfg_evaluate_pop_workspace_bytes'] = (_sz, [_i64, _i32, _i32, _i32, _i32, _i32])
 SIGNATURES['mfg_evaluate_pop'] = (_i32, [_p, _p, _i64, _i32, _i32, _i32, _p, _p, _p, _p, _u32, _i32, _i32, _p, _p, _p, _sz, _p])
 

@@ -29,7 +29,30 @@ struct RnPop {
   const uint64_t* key;                           // [n_y] device, by slot (NULL: from rn_seed)
   const int32_t* learner;                        // [n_y] device (NULL: slot = learner)
   int n_y;
+  const mfg_rn_geom_t* geom;                     // [K] device (NULL: the launch's n3 / n4 / keep_prob for every learner)
 };
+
+// Per-learner geometry (the *_nets entry points, include/mfg_hip.h): learner k's entry is read by its blocks -- block-uniform,
+// one 16-byte scalar load -- before they run the single kernel's body with its n3 / n4 / keep_prob (/ l1l2).  Learner k's ten
+// tensors are one flat row, at the offsets of rt_layout(d, 5, 2, 3, n3_k, n4_k) from row_base + k net_stride; the launch's own
+// n3 / n4 are the table's maxima and size the dynamic LDS and the workspace slices only.
+typedef const __attribute__((address_space(4))) mfg_rn_geom_t* RnGeomConst;  // read-only global memory: a scalar load
+__device__ __forceinline__ mfg_rn_geom_t rn_geom_entry(const mfg_rn_geom_t* geom, int k) {
+  RnGeomConst g = (RnGeomConst)geom + k;
+  mfg_rn_geom_t e;
+  e.n3 = g->n3; e.n4 = g->n4; e.keep_prob = g->keep_prob; e.l1l2 = g->l1l2;
+  return e;
+}
+
+// the checks a geometry table adds, before anything is launched (0, or the MFG_E* code with the message in `why`): both copies
+// given, one row per learner with room for the longest, every entry inside the matrix-core kernel's limits.  n3_max / n4_max /
+// np_max: the largest n3, n4 and parameter count of the table.
+int rn_geom_check(const mfg_rn_geom_t* geom_host, const mfg_rn_geom_t* geom_dev, int K, int d, int k1, int f2, int k2,
+                  int per_learner_net, int64_t net_stride, int* n3_max, int* n4_max, int64_t* np_max, const char** why);
+// ... and the network the launches of such a population are set up with: conv1_w = the base of row 0, the other pointers at the
+// offsets of the LARGEST geometry (n3 / n4 = the table's maxima: LDS and workspace sizes), keep_prob 1; sets the error on refusal
+int rn_pop_nets_struct(const mfg_reward_net_t* net, const mfg_rn_geom_t* geom_host, const mfg_rn_geom_t* geom_dev, int K, int d,
+                       int per_learner_net, int64_t net_stride, mfg_reward_net_t* out);
 
 // true: K learners' networks of this geometry (fc3_w of every learner 8-byte aligned) run the matrix-core kernel
 // (net_stride > 0: learner k's tensors at base + k net_stride; 0: the numel_t strides)

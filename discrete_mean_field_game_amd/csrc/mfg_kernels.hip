@@ -3224,6 +3224,17 @@ int mfg_evaluate_pop(const float* emp32, const double* emp64, int64_t N, int L, 
                 "reward network (d = 21 / 15, 5 / 2 / 3, n_fc3 <= 16, 8-byte aligned fc3_w of every learner)",           \
                 d, net->k1, net->f2, net->k2, net->n3, net->n4)
 
+// a population with a geometry table (the *_nets entry points; rn_pop_nets_struct, mfg_irl_population.h): its checks, then the
+// launches are set up with the row base and the table's maxima
+#define IRL_POP_NETS()                                                                                                   \
+  mfg_reward_net_t net_max;                                                                                              \
+  if (geom_given) {                                                                                                      \
+    REQUIRE(net && net->conv1_w, "null pointer");                                                                        \
+    const int rc_g = rn_pop_nets_struct(net, geom_host, geom_dev, K, d, per_learner_net, net_stride, &net_max);          \
+    if (rc_g != MFG_OK) return rc_g;                                                                                     \
+    net = &net_max;                                                                                                      \
+  }
+
 // dropout key of reward-network call number `call` (1-based) under rn_seed; a population xors its learners' seeds in the
 // kernel: RnPop::key_ctr is the key under seed 0
 static uint64_t rn_dropout_key(uint64_t rn_seed, uint64_t call) { return rn_seed ^ (call * 0x9E3779B97F4A7C15ull); }
@@ -3232,7 +3243,7 @@ static uint64_t rn_dropout_key(uint64_t rn_seed, uint64_t call) { return rn_seed
 // (rn_call0_k: the per-learner reward-call counters [K] of the *_irl_pop_calls entry points, NULL: the shared rn_call0;
 //  net_stride: elements between two learners' weights, 0: the numel strides of the stacked tensors)
 static RnPop rn_pop_args(int K, int per_learner_net, int64_t net_stride, const uint64_t* rn_seed, const uint64_t* rn_call0_k,
-                         size_t workspace_bytes) {
+                         size_t workspace_bytes, const mfg_rn_geom_t* geom_dev = nullptr) {
   RnPop rp{};
   rp.K = K;
   rp.per_learner_net = per_learner_net ? 1 : 0;
@@ -3240,6 +3251,7 @@ static RnPop rn_pop_args(int K, int per_learner_net, int64_t net_stride, const u
   rp.rn_seed = rn_seed;
   rp.call_base = rn_call0_k;
   rp.s_net = per_learner_net ? net_stride : 0;
+  rp.geom = geom_dev;
   return rp;
 }
 
@@ -3477,8 +3489,11 @@ static int train_episodes_irl_pop(const float* mat_pi0, int64_t num_start, float
                                   uint64_t traj_offset, int precision, const double* lr_critic, const double* lr_actor,
                                   const mfg_reward_net_t* net, int per_learner_net, int64_t net_stride, const uint64_t* rn_seed,
                                   uint64_t rn_call0, const uint64_t* rn_call0_k, float* P, float* reward, double* delta, double* g,
-                                  double* G, double* reward_acc, void* workspace, size_t workspace_bytes, mfg_stream_t stream) {
+                                  double* G, double* reward_acc, void* workspace, size_t workspace_bytes, mfg_stream_t stream,
+                                  bool geom_given = false, const mfg_rn_geom_t* geom_host = nullptr,
+                                  const mfg_rn_geom_t* geom_dev = nullptr) {
   REQUIRE(pi_out && pi_scratch, "null pointer");
+  IRL_POP_NETS();
   CHECK_IRL_POP();
   CHECK_PRECISION();
   const size_t need = irl_step_ws(workspace, B, d).bytes;
@@ -3488,7 +3503,7 @@ static int train_episodes_irl_pop(const float* mat_pi0, int64_t num_start, float
   PopArgs p = pop_args(K, B, d, 1, episodes, seed, shift, alpha_scale, lr_critic, lr_actor, workspace_bytes);
   p.s_n = B;
   p.s_P = B * d * d;
-  RnPop rp = rn_pop_args(K, per_learner_net, net_stride, rn_seed, rn_call0_k, workspace_bytes);
+  RnPop rp = rn_pop_args(K, per_learner_net, net_stride, rn_seed, rn_call0_k, workspace_bytes, geom_given ? geom_dev : nullptr);
   rp.s_state = rp.s_next = B * d;
   rp.s_action = B * d * d;
   rp.s_n = B;
@@ -3510,8 +3525,11 @@ static int train_rollouts_irl_pop(const float* mat_pi0, int64_t num_start, int64
                                   const double* lr_critic, const double* lr_actor, const mfg_reward_net_t* net, int per_learner_net,
                                   int64_t net_stride, const uint64_t* rn_seed, uint64_t rn_call0, const uint64_t* rn_call0_k,
                                   float* pi_traj, float* pi_last, float* P, float* reward, double* delta, double* g, double* G,
-                                  double* reward_acc, void* workspace, size_t workspace_bytes, mfg_stream_t stream) {
+                                  double* reward_acc, void* workspace, size_t workspace_bytes, mfg_stream_t stream,
+                                  bool geom_given = false, const mfg_rn_geom_t* geom_host = nullptr,
+                                  const mfg_rn_geom_t* geom_dev = nullptr) {
   REQUIRE(pi_traj, "null pointer");
+  IRL_POP_NETS();
   CHECK_IRL_POP();
   const size_t need = pop_workspace_need(d, B * T, false);
   if (workspace_bytes < need)
@@ -3522,7 +3540,7 @@ static int train_rollouts_irl_pop(const float* mat_pi0, int64_t num_start, int64
   p.s_gpi = p.s_traj;
   p.s_n = B * T;
   p.s_P = B * T * d * d;
-  RnPop rp = rn_pop_args(K, per_learner_net, net_stride, rn_seed, rn_call0_k, workspace_bytes);
+  RnPop rp = rn_pop_args(K, per_learner_net, net_stride, rn_seed, rn_call0_k, workspace_bytes, geom_given ? geom_dev : nullptr);
   rp.s_state = B * (T + 1) * d;
   rp.s_action = B * T * d * d;
   rp.s_n = B * T;
@@ -3594,6 +3612,37 @@ int mfg_train_rollouts_irl_pop_calls(const float* mat_pi0, int64_t num_start, in
                                 gamma, seed, first_step, traj_offset, flags, lr_critic, lr_actor, net, per_learner_net, net_stride,
                                 rn_seed, 0, rn_call0, pi_traj, pi_last, P, reward, delta, g, G, reward_acc, workspace,
                                 workspace_bytes, stream);
+}
+
+int mfg_train_episodes_irl_pop_nets(const float* mat_pi0, int64_t num_start, float* pi_out, float* pi_scratch, int64_t B, int K,
+                                    int d, int T, int64_t episodes, int64_t first_episode, int constant, double* theta,
+                                    const double* shift, const double* alpha_scale, double* w, double gamma, const uint64_t* seed,
+                                    uint32_t first_step, uint64_t traj_offset, int precision, const double* lr_critic,
+                                    const double* lr_actor, const mfg_reward_net_t* net, int per_learner_net, int64_t net_stride,
+                                    const mfg_rn_geom_t* geom_host, const mfg_rn_geom_t* geom_dev, const uint64_t* rn_seed,
+                                    const uint64_t* rn_call0, float* P, float* reward, double* delta, double* g, double* G,
+                                    double* reward_acc, void* workspace, size_t workspace_bytes, mfg_stream_t stream) {
+  REQUIRE(rn_call0, "null pointer");
+  return train_episodes_irl_pop(mat_pi0, num_start, pi_out, pi_scratch, B, K, d, T, episodes, first_episode, constant, theta, shift,
+                                alpha_scale, w, gamma, seed, first_step, traj_offset, precision, lr_critic, lr_actor, net,
+                                per_learner_net, net_stride, rn_seed, 0, rn_call0, P, reward, delta, g, G, reward_acc, workspace,
+                                workspace_bytes, stream, true, geom_host, geom_dev);
+}
+
+int mfg_train_rollouts_irl_pop_nets(const float* mat_pi0, int64_t num_start, int64_t B, int K, int d, int T, int64_t episodes,
+                                    int64_t first_episode, int constant, double* theta, const double* shift,
+                                    const double* alpha_scale, double* w, double gamma, const uint64_t* seed, uint32_t first_step,
+                                    uint64_t traj_offset, int flags, const double* lr_critic, const double* lr_actor,
+                                    const mfg_reward_net_t* net, int per_learner_net, int64_t net_stride,
+                                    const mfg_rn_geom_t* geom_host, const mfg_rn_geom_t* geom_dev, const uint64_t* rn_seed,
+                                    const uint64_t* rn_call0, float* pi_traj, float* pi_last, float* P, float* reward,
+                                    double* delta, double* g, double* G, double* reward_acc, void* workspace,
+                                    size_t workspace_bytes, mfg_stream_t stream) {
+  REQUIRE(rn_call0, "null pointer");
+  return train_rollouts_irl_pop(mat_pi0, num_start, B, K, d, T, episodes, first_episode, constant, theta, shift, alpha_scale, w,
+                                gamma, seed, first_step, traj_offset, flags, lr_critic, lr_actor, net, per_learner_net, net_stride,
+                                rn_seed, 0, rn_call0, pi_traj, pi_last, P, reward, delta, g, G, reward_acc, workspace,
+                                workspace_bytes, stream, true, geom_host, geom_dev);
 }
 
 int mfg_train_rollout_irl(const float* mat_pi0, int64_t num_start, const int32_t* idx, int64_t B, int d, int T, double* theta,

@@ -1150,7 +1150,22 @@ __global__ __launch_bounds__(RM_BLOCK) void k_reward_net_mfma_pop(RewardNetArgs 
   const int slot = blockIdx.y;
   const int k = p.learner ? p.learner[slot] : slot;
   RewardNetArgs b = a;
-  if (p.per_learner_net && p.s_net > 0) {
+  if (p.geom) {  // learner k's own n3 / n4 / keep_prob; its tensors at its own offsets (rt_layout) in its flat row
+    using Gm = MfmaGeom<D, RUN, RPR, P1>;
+    const mfg_rn_geom_t e = rn_geom_entry(p.geom, k);
+    const float* row = a.c1w + p.s_net * k;
+    b.n3 = e.n3; b.n4 = e.n4; b.keep_prob = e.keep_prob;
+    b.c1w = row;
+    b.c1b = b.c1w + Gm::K1 * Gm::K1;
+    b.c2w = b.c1b + 1;
+    b.c2b = b.c2w + Gm::F2 * Gm::K2 * Gm::K2;
+    b.w3 = b.c2b + Gm::F2;
+    b.b3 = b.w3 + e.n3 * Gm::K;
+    b.w4 = b.b3 + e.n3;
+    b.b4 = b.w4 + e.n4 * (e.n3 + D);
+    b.wo = b.b4 + e.n4;
+    b.bo = b.wo + e.n4;
+  } else if (p.per_learner_net && p.s_net > 0) {
     const int64_t o = p.s_net * k;
     b.c1w += o; b.c1b += o; b.c2w += o; b.c2b += o; b.w3 += o; b.b3 += o; b.w4 += o; b.b4 += o; b.wo += o; b.bo += o;
   } else if (p.per_learner_net) {
@@ -1368,6 +1383,51 @@ bool reward_net_pop_ready(int d, const mfg_reward_net_t* net, int per_learner_ne
   return d == 21 ? mfma_lds_attribute_pop<21, 7, 3, MFG_RM_P21>() : mfma_lds_attribute_pop<15, 5, 3, MFG_RM_P15>();
 }
 
+int rn_geom_check(const mfg_rn_geom_t* geom_host, const mfg_rn_geom_t* geom_dev, int K, int d, int k1, int f2, int k2,
+                  int per_learner_net, int64_t net_stride, int* n3_max, int* n4_max, int64_t* np_max, const char** why) {
+  *n3_max = *n4_max = 0;
+  *np_max = 0;
+  if (!geom_host || !geom_dev || K < 1) { *why = "geometry table: both copies (host and device) and K >= 1 are required"; return MFG_EINVAL; }
+  if (!per_learner_net || net_stride <= 0) { *why = "geometry table: needs one flat parameter row per learner (per_learner_net = 1, stride > 0)"; return MFG_EINVAL; }
+  if (!((d == 15 || d == 21) && k1 == 5 && f2 == 2 && k2 == 3)) { *why = "geometry table: d = 15 / 21, k1 = 5, f2 = 2, k2 = 3 only"; return MFG_EUNSUPPORTED; }
+  for (int k = 0; k < K; ++k) {
+    const mfg_rn_geom_t& e = geom_host[k];
+    if (e.n3 < 1 || e.n3 > 16 || e.n4 < 1 || e.n4 > RN_MAXN) { *why = "geometry table: an entry outside 1 <= n_fc3 <= 16, 1 <= n_fc4 <= 32"; return MFG_EUNSUPPORTED; }
+    if (!(e.keep_prob > 0.0f && e.keep_prob <= 1.0f)) { *why = "geometry table: keep_prob must be in (0,1]"; return MFG_EINVAL; }
+    const int64_t np = mfg_reward_net_num_params(d, k1, f2, k2, e.n3, e.n4);
+    if (e.n3 > *n3_max) *n3_max = e.n3;
+    if (e.n4 > *n4_max) *n4_max = e.n4;
+    if (np > *np_max) *np_max = np;
+  }
+  if (net_stride < *np_max) { *why = "geometry table: the learner stride is below the largest parameter count"; return MFG_EINVAL; }
+  return MFG_OK;
+}
+
+int rn_pop_nets_struct(const mfg_reward_net_t* net, const mfg_rn_geom_t* geom_host, const mfg_rn_geom_t* geom_dev, int K, int d,
+                       int per_learner_net, int64_t net_stride, mfg_reward_net_t* out) {
+  int n3m = 0, n4m = 0;
+  int64_t npm = 0;
+  const char* why = "";
+  const int rc = rn_geom_check(geom_host, geom_dev, K, d, net->k1, net->f2, net->k2, per_learner_net, net_stride, &n3m, &n4m, &npm, &why);
+  if (rc != MFG_OK) return set_error(rc, why);
+  const float* row = net->conv1_w;
+  const int a2 = net->f2 * d * d;
+  *out = *net;
+  out->n3 = n3m;
+  out->n4 = n4m;
+  out->keep_prob = 1.0f;
+  out->conv1_b = row + net->k1 * net->k1;
+  out->conv2_w = out->conv1_b + 1;
+  out->conv2_b = out->conv2_w + net->f2 * net->k2 * net->k2;
+  out->fc3_w = out->conv2_b + net->f2;   // (these five do not depend on n3 / n4: fc3_w + k net_stride is learner k's)
+  out->fc3_b = out->fc3_w + (int64_t)n3m * a2;
+  out->fc4_w = out->fc3_b + n3m;
+  out->fc4_b = out->fc4_w + n4m * (n3m + d);
+  out->out_w = out->fc4_b + n4m;
+  out->out_b = out->out_w + n4m;
+  return MFG_OK;
+}
+
 template <int D, int RUN, int RPR, int P1>
 static void launch_reward_net_mfma_pop(const RewardNetArgs& a, bool sums, const RnPop& p, int* rows_out, hipStream_t st) {
   using Gm = MfmaGeom<D, RUN, RPR, P1>;
@@ -1393,10 +1453,19 @@ extern "C" int mfg_reward_net_forward(const float* state, const float* action, i
   return mfg::reward_net_forward_sums(state, action, B, d, net, seed, sample_offset, reward, nullptr, nullptr, (hipStream_t)stream);
 }
 
-extern "C" int mfg_reward_net_forward_pop(const float* state, const float* action, int64_t s_state, int64_t s_action, int64_t N,
-                                          int d, const mfg_reward_net_t* net, int per_learner_net, int64_t net_stride, int K,
-                                          const int32_t* learners_host, const uint64_t* keys_host, int n, uint64_t sample_offset,
-                                          float* reward, void* scratch, size_t scratch_bytes, mfg_stream_t stream) {
+// mfg_reward_net_forward_pop with (geom_given) or without a geometry table
+static int reward_net_forward_pop_impl(const float* state, const float* action, int64_t s_state, int64_t s_action, int64_t N,
+                                       int d, const mfg_reward_net_t* net, int per_learner_net, int64_t net_stride,
+                                       bool geom_given, const mfg_rn_geom_t* geom_host, const mfg_rn_geom_t* geom_dev, int K,
+                                       const int32_t* learners_host, const uint64_t* keys_host, int n, uint64_t sample_offset,
+                                       float* reward, void* scratch, size_t scratch_bytes, mfg_stream_t stream) {
+  mfg_reward_net_t nm;  // with a table: the launch's network = the row base and the table's maxima
+  if (geom_given) {
+    if (!net || !net->conv1_w) return set_error(MFG_EINVAL, "reward_net_forward_pop_nets: null pointer");
+    int rc = rn_pop_nets_struct(net, geom_host, geom_dev, K, d, per_learner_net, net_stride, &nm);
+    if (rc != MFG_OK) return rc;
+    net = &nm;
+  }
   if (!state || !action || !net || !reward || !learners_host || !keys_host || !scratch || K < 1 || K > MFG_POP_MAX_K || n < 0 ||
       n > K || N < 0 || s_state < 0 || s_action < 0 || net_stride < 0 || (s_state && s_state < N * d) ||
       (s_action && s_action < N * d * d))
@@ -1430,7 +1499,26 @@ extern "C" int mfg_reward_net_forward_pop(const float* state, const float* actio
   rp.key = (const uint64_t*)scratch;
   rp.learner = (const int32_t*)((const char*)scratch + (size_t)n * 8);
   rp.n_y = n;
+  rp.geom = geom_given ? geom_dev : nullptr;
   return reward_net_forward_sums(state, action, N, d, *net, 0, sample_offset, reward, nullptr, nullptr, st, 0, &rp);
+}
+
+extern "C" int mfg_reward_net_forward_pop(const float* state, const float* action, int64_t s_state, int64_t s_action, int64_t N,
+                                          int d, const mfg_reward_net_t* net, int per_learner_net, int64_t net_stride, int K,
+                                          const int32_t* learners_host, const uint64_t* keys_host, int n, uint64_t sample_offset,
+                                          float* reward, void* scratch, size_t scratch_bytes, mfg_stream_t stream) {
+  return reward_net_forward_pop_impl(state, action, s_state, s_action, N, d, net, per_learner_net, net_stride, false, nullptr,
+                                     nullptr, K, learners_host, keys_host, n, sample_offset, reward, scratch, scratch_bytes, stream);
+}
+
+extern "C" int mfg_reward_net_forward_pop_nets(const float* state, const float* action, int64_t s_state, int64_t s_action,
+                                               int64_t N, int d, const mfg_reward_net_t* net, int per_learner_net,
+                                               int64_t net_stride, const mfg_rn_geom_t* geom_host, const mfg_rn_geom_t* geom_dev,
+                                               int K, const int32_t* learners_host, const uint64_t* keys_host, int n,
+                                               uint64_t sample_offset, float* reward, void* scratch, size_t scratch_bytes,
+                                               mfg_stream_t stream) {
+  return reward_net_forward_pop_impl(state, action, s_state, s_action, N, d, net, per_learner_net, net_stride, true, geom_host,
+                                     geom_dev, K, learners_host, keys_host, n, sample_offset, reward, scratch, scratch_bytes, stream);
 }
 
 #ifdef MFG_RN_STAMPS

@@ -32,6 +32,7 @@
 
 #include "../../include/mfg_hip.h"
 #include "mfg_core.h"
+#include "mfg_irl_population.h"
 #include "mfg_rn_common.h"
 
 namespace mfg {
@@ -86,6 +87,7 @@ struct RtPop {
   int64_t s_params;                 // elements between two learners' params / adam_m / adam_v
   int64_t s_gen_state, s_gen_action;  // elements between two learners' generated stores
   int64_t s_ws;                     // floats between two slots' workspace slices
+  const mfg_rn_geom_t* geom;        // [K] device: learner k's n3 / n4 / keep_prob / l1l2 (NULL: the launch's for every learner)
 };
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -485,6 +487,14 @@ __global__ __launch_bounds__(RT_BLOCK) void k_rn_train_sample_pop(RtNet a, RtPop
   const int64_t o = p.s_ws * blockIdx.y;
   b.reg = a.reg + o; b.r = a.r + o; b.dz3 = a.dz3 + o; b.js = a.js + o; b.a2 = a.a2 + o;
   const int n = blockIdx.x, N = (a.n_demo + a.n_gen) * a.steps;
+  if (p.geom) {  // the learner's own geometry and regulariser; its slice carved as the single step carves its workspace
+    const mfg_rn_geom_t ge = rn_geom_entry(p.geom, k);
+    b.n3 = ge.n3; b.n4 = ge.n4; b.keep_prob = ge.keep_prob; b.l1l2 = ge.l1l2;
+    const RtLayout Lk = rt_layout(a.d, K1, F2, K2, ge.n3, ge.n4);
+    b.dz3 = b.r + N;
+    b.js = b.dz3 + (int64_t)N * ge.n3;
+    b.a2 = b.js + (int64_t)N * Lk.ns;
+  }
   int32_t row = 0;
   if (n < N) {
     const int j = n / a.steps;
@@ -668,6 +678,16 @@ __global__ __launch_bounds__(RT_BLOCK) void k_rn_train_combine_pop(RtCombineArgs
   const int64_t o = p.s_ws * blockIdx.y;
   b.r = a.r + o; b.a2 = a.a2 + o; b.dz3 = a.dz3 + o; b.js = a.js + o; b.reg = a.reg + o;
   b.lr_t = e.lr_t;
+  if (p.geom) {  // (as in k_rn_train_sample_pop; the grid is as wide as the longest learner's row needs)
+    const mfg_rn_geom_t ge = rn_geom_entry(p.geom, k);
+    b.n3 = ge.n3; b.n4 = ge.n4; b.l1l2 = ge.l1l2;
+    const RtLayout Lk = rt_layout(a.d, a.k1, a.f2, a.k2, ge.n3, ge.n4);
+    if ((int)blockIdx.x * RT_CP >= Lk.np) return;
+    const int N = (a.n_demo + a.n_gen) * a.steps;
+    b.dz3 = b.r + N;
+    b.js = b.dz3 + (int64_t)N * ge.n3;
+    b.a2 = b.js + (int64_t)N * Lk.ns;
+  }
   rn_train_combine_body(b);
 }
 
@@ -796,13 +816,14 @@ int mfg_reward_net_adam(float* params, float* adam_m, float* adam_v, const float
   return hipGetLastError() == hipSuccess ? MFG_OK : set_error(MFG_ELAUNCH, "reward_net_adam: launch failed");
 }
 
-int mfg_reward_net_train_steps_pop(float* params, float* adam_m, float* adam_v, int64_t param_stride, int K, int d, int k1, int f2,
-                                   int k2, int n3, int n4, const float* demo_state, const float* demo_action, int64_t demo_capacity,
-                                   const float* gen_state, const float* gen_action, int64_t gen_capacity,
-                                   mfg_rn_train_plan_t* plan_host, void* plan_dev, size_t plan_dev_bytes, int n_updates,
-                                   int n_active, int n_demo, int n_gen, int steps, int demo_divisor, float keep_prob, int l1l2,
-                                   double beta1, double beta2, double eps, float* stats, void* workspace, size_t workspace_bytes,
-                                   mfg_stream_t stream) {
+// mfg_reward_net_train_steps_pop; geom_given: n3 / n4 are the maxima of the (checked) table, which the kernels read per learner
+static int reward_net_train_steps_pop_impl(float* params, float* adam_m, float* adam_v, int64_t param_stride, int K, int d, int k1,
+                                           int f2, int k2, int n3, int n4, const mfg_rn_geom_t* geom_dev, int64_t np_max, const float* demo_state,
+                                           const float* demo_action, int64_t demo_capacity, const float* gen_state,
+                                           const float* gen_action, int64_t gen_capacity, mfg_rn_train_plan_t* plan_host,
+                                           void* plan_dev, size_t plan_dev_bytes, int n_updates, int n_active, int n_demo, int n_gen,
+                                           int steps, int demo_divisor, float keep_prob, int l1l2, double beta1, double beta2,
+                                           double eps, float* stats, void* workspace, size_t workspace_bytes, mfg_stream_t stream) {
   if (!params || !adam_m || !adam_v || !stats || !workspace || !plan_host || !plan_dev || K < 1 || n_updates < 0 ||
       n_active < 0 || n_active > K || n_demo < 0 || n_gen < 0 || steps < 1 || demo_divisor < 1 ||
       (n_demo && (!demo_state || !demo_action || demo_capacity < 1)) || (n_gen && (!gen_state || !gen_action || gen_capacity < 1)))
@@ -812,7 +833,7 @@ int mfg_reward_net_train_steps_pop(float* params, float* adam_m, float* adam_v, 
     return set_error(MFG_EUNSUPPORTED, "reward_net_train_steps_pop: the population geometry is d = 15 / 21, k1 = 5, f2 = 2, k2 = 3, "
                                        "n_fc3 <= 16, n_fc4 <= 32");
   const RtLayout L = rt_layout(d, k1, f2, k2, n3, n4);
-  if (param_stride < L.np) return set_error(MFG_EINVAL, "reward_net_train_steps_pop: param_stride < the parameter count");
+  if (!geom_dev && param_stride < L.np) return set_error(MFG_EINVAL, "reward_net_train_steps_pop: param_stride < the parameter count");
   if (n_demo > RT_MAX_TRAJ || n_gen > RT_MAX_TRAJ)
     return set_error(MFG_EUNSUPPORTED, "reward_net_train_steps_pop: at most MFG_RN_TRAIN_MAX_TRAJ trajectories per batch half");
   const int64_t N = (int64_t)(n_demo + n_gen) * steps;
@@ -877,9 +898,11 @@ int mfg_reward_net_train_steps_pop(float* params, float* adam_m, float* adam_v, 
   p.s_gen_state = gen_capacity * steps * d;
   p.s_gen_action = gen_capacity * steps * d * d;
   p.s_ws = (int64_t)(slice / sizeof(float));
+  p.geom = geom_dev;
+  const int64_t np_grid = geom_dev ? np_max : L.np;  // (the longest row of the table)
   const int h1 = k1 / 2, h2 = k2 / 2, W1 = d + 2 * h1, W2 = d + 2 * h2;
   const size_t lds = (size_t)(W1 * W1 + W2 * W2 + L.a2 + f2 * W2 * W2 + L.ns) * sizeof(float);
-  const dim3 g1((unsigned)N + 1, (unsigned)n_active), g2((unsigned)((L.np + RT_CP - 1) / RT_CP), (unsigned)n_active);
+  const dim3 g1((unsigned)N + 1, (unsigned)n_active), g2((unsigned)((np_grid + RT_CP - 1) / RT_CP), (unsigned)n_active);
   const mfg_rn_train_plan_t* pd = (const mfg_rn_train_plan_t*)plan_dev;
   for (int64_t u = 0; u < n_updates; ++u) {
     p.plan = pd + u * n_active;
@@ -888,6 +911,39 @@ int mfg_reward_net_train_steps_pop(float* params, float* adam_m, float* adam_v, 
     hipLaunchKernelGGL(k_rn_train_combine_pop, g2, dim3(RT_BLOCK), (size_t)N * (1 + n3) * sizeof(float), st, c, p);
   }
   return hipGetLastError() == hipSuccess ? MFG_OK : set_error(MFG_ELAUNCH, "reward_net_train_steps_pop: launch failed");
+}
+
+int mfg_reward_net_train_steps_pop(float* params, float* adam_m, float* adam_v, int64_t param_stride, int K, int d, int k1, int f2,
+                                   int k2, int n3, int n4, const float* demo_state, const float* demo_action, int64_t demo_capacity,
+                                   const float* gen_state, const float* gen_action, int64_t gen_capacity,
+                                   mfg_rn_train_plan_t* plan_host, void* plan_dev, size_t plan_dev_bytes, int n_updates,
+                                   int n_active, int n_demo, int n_gen, int steps, int demo_divisor, float keep_prob, int l1l2,
+                                   double beta1, double beta2, double eps, float* stats, void* workspace, size_t workspace_bytes,
+                                   mfg_stream_t stream) {
+  return reward_net_train_steps_pop_impl(params, adam_m, adam_v, param_stride, K, d, k1, f2, k2, n3, n4, nullptr, 0, demo_state,
+                                         demo_action, demo_capacity, gen_state, gen_action, gen_capacity, plan_host, plan_dev,
+                                         plan_dev_bytes, n_updates, n_active, n_demo, n_gen, steps, demo_divisor, keep_prob, l1l2,
+                                         beta1, beta2, eps, stats, workspace, workspace_bytes, stream);
+}
+
+int mfg_reward_net_train_steps_pop_nets(float* params, float* adam_m, float* adam_v, int64_t param_stride, int K, int d, int k1,
+                                        int f2, int k2, const mfg_rn_geom_t* geom_host, const mfg_rn_geom_t* geom_dev,
+                                        const float* demo_state, const float* demo_action, int64_t demo_capacity,
+                                        const float* gen_state, const float* gen_action, int64_t gen_capacity,
+                                        mfg_rn_train_plan_t* plan_host, void* plan_dev, size_t plan_dev_bytes, int n_updates,
+                                        int n_active, int n_demo, int n_gen, int steps, int demo_divisor, double beta1,
+                                        double beta2, double eps, float* stats, void* workspace, size_t workspace_bytes,
+                                        mfg_stream_t stream) {
+  int n3m = 0, n4m = 0;
+  int64_t npm = 0;
+  const char* why = "";
+  const int rc = rn_geom_check(geom_host, geom_dev, K, d, k1, f2, k2, 1, param_stride, &n3m, &n4m, &npm, &why);
+  if (rc != MFG_OK) return set_error(rc, why);
+  // the batch limits and the workspace slices at the largest n3 / n4; keep_prob and l1l2 of the launch are never read
+  return reward_net_train_steps_pop_impl(params, adam_m, adam_v, param_stride, K, d, k1, f2, k2, n3m, n4m, geom_dev, npm,
+                                         demo_state, demo_action, demo_capacity, gen_state, gen_action, gen_capacity, plan_host,
+                                         plan_dev, plan_dev_bytes, n_updates, n_active, n_demo, n_gen, steps, demo_divisor, 1.0f, 0,
+                                         beta1, beta2, eps, stats, workspace, workspace_bytes, stream);
 }
 
 }  // extern "C"

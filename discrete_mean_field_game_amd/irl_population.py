@@ -21,11 +21,20 @@ reward_iteration check is one population forward (mfg_reward_net_forward_pop) ov
 learners' D_samp, plus one host read.  D_samp is generated as AC_IRL._generate_device does, one draw + one rollout launch per
 learner.  Out of scope: CSV / checkpoint files, a population state_dict, multi-GPU, calc_z and eval-set overrides.
 
+Mixed populations (mixed_nets=True): the learners' networks may differ in n_fc3, n_fc4 and regulariser -- the three axes of
+the reference's sweep gridsearch.py:8-31.  Each learner's parameters are one flat row of a [K, stride] buffer in its OWN layout
+(mfg_reward_net_param_offsets of its geometry; stride = the longest row rounded up to PARAM_ALIGN, tails zero and never
+written), the Adam moments likewise, and a geometry table (mfg_rn_geom_t, one 16-byte entry per learner, host and device)
+tells the kernels of the *_nets entry points which shape a learner's blocks run.  Learner k still gives exactly what AC_IRL
+gives with learner k's shape and regulariser.  test_reward_network() is AC_IRL.test_reward_network for every learner, and
+gridsearch() below runs the reference's sweep as one such population.
+
 The instance owns one ops.Context; its sticky status word is shared by the K learners (as for ActorCriticPopulation).
 """
 from __future__ import annotations
 
 import copy
+import os
 import random
 
 import numpy as np
@@ -108,15 +117,57 @@ def check_args(K, d, batch, update_every, precision, reward_nets):
     return nets
 
 
+def check_args_mixed(K, d, batch, update_every, precision, reward_nets):
+    """check_args for a population with per-learner network shapes (mixed_nets=True): one network per learner, each inside the
+    matrix-core kernel's limits, d / k1 / f2 / k2 shared.  Returns (networks, [(n3, n4, keep_prob, l1l2), ...])."""
+    if K < 1 or K > L.POP_MAX_K:
+        raise ValueError('population size %d outside [1, %d]' % (K, L.POP_MAX_K))
+    if d not in ops.IRL_POP_D:
+        raise ValueError('d=%d: IRL populations cover d = 15 / 21 (the matrix-core reward-network kernel)' % d)
+    if batch < 2:
+        raise ValueError('batch=%d: a population draws its start states on the device, which AC_IRL does from batch 2 on'
+                         % batch)
+    if update_every not in ('step', 'rollout'):
+        raise ValueError("update_every must be 'step' or 'rollout'")
+    if precision not in ('mixed', 'f64'):
+        raise ValueError("precision must be 'mixed' or 'f64'")
+    if isinstance(reward_nets, torch.nn.Module):
+        raise ValueError('mixed_nets: one network per learner is needed, got one shared network')
+    nets = list(reward_nets)
+    if len(nets) != K:
+        raise ValueError('mixed_nets: one network per learner is needed (%d), got %d' % (K, len(nets)))
+    if not all(isinstance(n, RewardNet) for n in nets):
+        raise ValueError('reward_nets: expected networks.RewardNet modules')
+    nd, geoms = ops.irl_pop_net_geometries(nets)
+    if nd != d:
+        raise ValueError('reward network d=%d, population d=%d' % (nd, d))
+    return nets, geoms
+
+
+def net_row_offsets(d, n3, n4):
+    """The 11 offsets (ten tensors of NET_TENSORS and the parameter count) of one learner's flat row."""
+    import ctypes as C
+    offs = (C.c_int64 * 11)()
+    L.check(L.lib().mfg_reward_net_param_offsets(int(d), 5, 2, 3, int(n3), int(n4), offs), 'mfg_reward_net_param_offsets')
+    return [int(o) for o in offs]
+
+
 class AC_IRLPopulation(_Population):
     _WITH_P = True
 
     def __init__(self, thetas, shifts=0.0, alpha_scales=1e4, d=15, *, batch, reward_nets, seeds=None, w0=None, pi0=None,
                  path_to_dir=None, update_every='step', precision='mixed', device=None, verbose=0, demonstrations=None,
-                 lr_reward=1e-4, num_policies=10, host_seeds=None):
+                 lr_reward=1e-4, num_policies=10, host_seeds=None, mixed_nets=False, demonstrations_test=None):
         th = np.asarray(thetas, dtype=np.float64).reshape(-1)
         K = th.shape[0]
-        nets = check_args(K, int(d), int(batch), update_every, precision, reward_nets)
+        geoms = None
+        if mixed_nets:
+            nets, geoms = check_args_mixed(K, int(d), int(batch), update_every, precision, reward_nets)
+        else:
+            nets = check_args(K, int(d), int(batch), update_every, precision, reward_nets)
+        self.mixed_nets = bool(mixed_nets)
+        self._geom = None                      # (host table, device copy) of the *_nets entry points
+        test_np = check_demonstrations(demonstrations_test, int(d)) if demonstrations_test else None
         lr_reward = broadcast('lr_reward', lr_reward, K)
         if int(num_policies) < 1:
             raise ValueError('num_policies < 1')
@@ -129,15 +180,33 @@ class AC_IRLPopulation(_Population):
         # in one flat buffer [K, ld] (the reward trainer's parameter layout, rows padded to PARAM_ALIGN floats) and the
         # stacked tensors are views into it
         self._templates = [copy.deepcopy(n).to('cpu') for n in nets]
-        self.per_learner_net = len(nets) > 1
+        self.per_learner_net = len(nets) > 1 or bool(mixed_nets)      # (a mixed population of one learner owns its network)
         self._net_params = {}
         self._flat = None
         self._net_stride = 0
         n0 = nets[0]
         self._rn_dims = (n0.d, n0.conv1.kernel_size[0], n0.conv2.out_channels, n0.conv2.kernel_size[0], n0.fc3.out_features,
                          n0.fc4.out_features)
+        if mixed_nets:
+            self._rn_dims = self._rn_dims[:4] + (max(g[0] for g in geoms), max(g[1] for g in geoms))    # the largest learner
         with torch.no_grad():
-            if self.per_learner_net:
+            if mixed_nets:
+                # learner k's row in ITS layout; the tail of a row beyond its own parameter count stays zero
+                rows = [net_row_offsets(d, g[0], g[1]) for g in geoms]
+                self._row_offsets = rows
+                self._net_stride = (max(r[10] for r in rows) + PARAM_ALIGN - 1) // PARAM_ALIGN * PARAM_ALIGN
+                self._flat = torch.zeros(K, self._net_stride, dtype=torch.float32, device=dev)
+                self._net_views = []
+                for k, n in enumerate(nets):
+                    views = {}
+                    for i, (field, pname) in enumerate(NET_TENSORS):
+                        par = n.get_parameter(pname).detach()
+                        view = self._flat[k, rows[k][i]:rows[k][i + 1]].view(*par.shape)
+                        view.copy_(par.to(device=dev, dtype=torch.float32))
+                        views[field] = view
+                    self._net_views.append(views)
+                self._geom = ops.rn_geom_table(geoms, dev)
+            elif self.per_learner_net:
                 import ctypes as C
                 offs = (C.c_int64 * 11)()
                 L.check(L.lib().mfg_reward_net_param_offsets(*self._rn_dims, offs), 'mfg_reward_net_param_offsets')
@@ -153,13 +222,19 @@ class AC_IRLPopulation(_Population):
                 for field, pname in NET_TENSORS:
                     ts = [n.get_parameter(pname).detach().to(device=dev, dtype=torch.float32) for n in nets]
                     self._net_params[field] = torch.stack(ts).contiguous()
-        _, _, _, keep = ops.irl_pop_net_geometry(nets)
         st = L.RewardNetStruct()
         st.k1, st.f2, st.k2 = nets[0].conv1.kernel_size[0], nets[0].conv2.out_channels, nets[0].conv2.kernel_size[0]
-        st.n3, st.n4 = nets[0].fc3.out_features, nets[0].fc4.out_features
-        for field, _ in NET_TENSORS:
-            setattr(st, field, self._net_params[field].data_ptr())
-        st.keep_prob = keep
+        if mixed_nets:      # conv1_w = the base of row 0 is what the *_nets entry points read; n3 / n4: the largest
+            st.n3, st.n4 = self._rn_dims[4], self._rn_dims[5]
+            for field, _ in NET_TENSORS:
+                setattr(st, field, self._flat.data_ptr())
+            st.keep_prob = 1.0
+        else:
+            _, _, _, keep = ops.irl_pop_net_geometry(nets)
+            st.n3, st.n4 = nets[0].fc3.out_features, nets[0].fc4.out_features
+            for field, _ in NET_TENSORS:
+                setattr(st, field, self._net_params[field].data_ptr())
+            st.keep_prob = keep
         self._net_struct = st
         # AC_IRL's reward-call counters (dropout keys), one per learner: reward_iteration's checks stop per learner
         self._calls_k = np.zeros(K, dtype=np.int64)
@@ -178,6 +253,8 @@ class AC_IRLPopulation(_Population):
         self._demo_np = demo_np
         if demo_np is not None:
             self._demo_store.push(torch.from_numpy(demo_np[0]), torch.from_numpy(demo_np[1]))
+        self._test_np = test_np                # the test demonstrations of test_reward_network (None: no test set)
+        self._test_dev = None
         self._gen_store = StackedTrajectoryStore(K, self.d, EPISODE_STEPS, dev)
         self._adam_m = self._adam_v = None
         if self.per_learner_net:
@@ -201,7 +278,8 @@ class AC_IRLPopulation(_Population):
         net = copy.deepcopy(self._templates[j])
         with torch.no_grad():
             for field, pname in NET_TENSORS:
-                net.get_parameter(pname).copy_(self._net_params[field][j].cpu())
+                src = self._net_views[j][field] if self.mixed_nets else self._net_params[field][j]
+                net.get_parameter(pname).copy_(src.cpu())
         return net.to(self.device)
 
     # ------------------------------------------------------------------ training
@@ -214,7 +292,8 @@ class AC_IRLPopulation(_Population):
         T = self.episode_steps
 
         def run(b, lrc, lra, acc):
-            common = dict(first_step=self._rng_step, reward_acc=acc, precision=self.precision, net_stride=self._net_stride)
+            common = dict(first_step=self._rng_step, reward_acc=acc, precision=self.precision, net_stride=self._net_stride,
+                          geom=self._geom)
             calls = torch.as_tensor(self._calls_k, device=self.device)      # per-learner reward-call counters
             if self.update_every == 'step':
                 ops.train_episodes_irl_pop(self._mat_pi0_dev, b['pi'], T, int(num_episodes), first_episode + 1, constant,
@@ -258,6 +337,9 @@ class AC_IRLPopulation(_Population):
         if self._demo_np is not None:
             ac.list_demonstrations = [[(s_.astype(np.float64), a_.astype(np.float64)) for s_, a_ in zip(st, at)]
                                       for st, at in zip(*self._demo_np)]
+        if self._test_np is not None:
+            ac.list_demonstrations_test = [[(s_.astype(np.float64), a_.astype(np.float64)) for s_, a_ in zip(st, at)]
+                                           for st, at in zip(*self._test_np)]
         if len(self._gen_store):
             ac._gen_store.push(*self._gen_store.gather(k=k))
         if self.per_learner_net and ac._trainer is not None:
@@ -336,13 +418,20 @@ class AC_IRLPopulation(_Population):
         ops.reward_net_train_steps_pop(self._flat, self._adam_m, self._adam_v, self._net_stride, self.K, self._rn_dims, (ds, da),
                                        (gs, ga), plan, n_updates, n_active, nd, ng, EPISODE_STEPS, NUM_DEMO_SAMPLES, keep,
                                        net.use_l1l2, self._rt_stats, self._rt_ws, self._rt_plan_dev,
-                                       RewardTrainer.BETA1, RewardTrainer.BETA2, RewardTrainer.EPS)
+                                       RewardTrainer.BETA1, RewardTrainer.BETA2, RewardTrainer.EPS, geom=self._geom)
 
     @_with_ctx
     def update_reward(self, learners=None):
         """One AC_IRL.update_reward of every learner (or of the listed ones): two launches for all of them."""
         active = list(range(self.K)) if learners is None else [int(k) for k in learners]
         self._train_rewards(active, 1)
+
+    def _forward(self, st, ac, active, keys):
+        """One population forward of the learners `active` under `keys` (shared [N, ...] or per-learner [K, N, ...] inputs)."""
+        if self._fw_scratch is None:
+            self._fw_scratch = torch.empty(2 * self.K, dtype=torch.float64, device=self.device)
+        return ops.reward_net_forward_pop(self._net_struct, True, self.K, st, ac, active, keys, net_stride=self._net_stride,
+                                          scratch=self._fw_scratch, geom=self._geom)
 
     def _reward_averages(self, active):
         """AC_IRL._eval_reward_averages of the learners `active`: one population forward over the demonstrations, one over
@@ -351,8 +440,6 @@ class AC_IRLPopulation(_Population):
         ds, da = self._demo_store.gather_flat()
         gs, ga = self._gen_store.gather_flat()
         nd, ng = ds.shape[0], gs.shape[1]
-        if self._fw_scratch is None:
-            self._fw_scratch = torch.empty(2 * K, dtype=torch.float64, device=self.device)
         sums = []
         outs = []
         for n, (st, ac) in ((nd, (ds, da)), (ng, (gs, ga))):
@@ -361,8 +448,7 @@ class AC_IRLPopulation(_Population):
                 continue
             self._calls_k[active] += 1
             keys = [((int(self.seeds[k]) + RN_SEED_OFFSET) ^ (int(self._calls_k[k]) * KEY_MUL)) & MASK64 for k in active]
-            outs.append(ops.reward_net_forward_pop(self._net_struct, True, K, st, ac, active, keys, net_stride=self._net_stride,
-                                                   scratch=self._fw_scratch))
+            outs.append(self._forward(st, ac, active, keys))
         zero = torch.zeros((), dtype=torch.float64, device=self.device)
         for r in outs:
             for k in active:
@@ -413,6 +499,41 @@ class AC_IRLPopulation(_Population):
             active = still
         return its, last
 
+    @_with_ctx
+    def test_reward_network(self):
+        """AC_IRL.test_reward_network (ac_irl.py:1008-1046) for every learner: D_samp is replaced by len(demonstrations) fresh
+        trajectories per learner, then one population forward over the training demonstrations, one over D_samp and one over
+        the test demonstrations (constructor argument demonstrations_test).  Returns a NumPy array [K, 3]:
+        (reward_demo_avg_train, reward_demo_avg_test, reward_gen_avg) per learner, NaN in the second column without a test set.
+        The reward-call counters advance as AC_IRL's do (one per forward)."""
+        if not self.per_learner_net:
+            raise ValueError('test_reward_network needs one reward network per learner')
+        K = self.K
+        active = list(range(K))
+        num_demos = len(self._demo_store)
+        self._gen_store.clear()
+        if num_demos:
+            self._gen_store.push(*self._generate(num_demos))
+        avg = self._reward_averages(active)
+        out = np.full((K, 3), np.nan)
+        out[:, 0] = avg[:, 0]
+        out[:, 2] = avg[:, 1]
+        if self._test_np is not None:
+            if self._test_dev is None:
+                d = self.d
+                self._test_dev = (torch.from_numpy(self._test_np[0]).reshape(-1, d).contiguous().to(self.device),
+                                  torch.from_numpy(self._test_np[1]).reshape(-1, d, d).contiguous().to(self.device))
+            ts, ta = self._test_dev
+            self._calls_k[active] += 1
+            keys = [((int(self.seeds[k]) + RN_SEED_OFFSET) ^ (int(self._calls_k[k]) * KEY_MUL)) & MASK64 for k in active]
+            r = self._forward(ts, ta, active, keys)
+            host = torch.stack([r[k].double().sum() for k in active]).cpu().numpy()
+            out[:, 1] = [float(v) / ts.shape[0] for v in host]
+        if self.verbose:
+            for k in active:
+                print('learner %d: Avg reward demo train %f | Avg reward demo test %f | Avg reward gen %f' % ((k,) + tuple(out[k])))
+        return out
+
     def _generate(self, n):
         """AC_IRL._generate_device(n) of every learner (its seed, theta, shift, alpha_scale; shared Philox step and
         trajectory ids): K draw + rollout launch pairs.  Returns (pi_traj [K,n,16,d], P [K,n,15,d,d])."""
@@ -454,3 +575,61 @@ class AC_IRLPopulation(_Population):
             self._theta.copy_(th0)
             self.train(2000, gamma, constant, lr_critic, lr_actor)
         return self.thetas
+
+
+# ---------------------------------------------------------------------- the reference's sweep (gridsearch.py:8-31)
+GRIDSEARCH_HEADER = 'reg,n_fc3,n_fc4,reward_demo_avg_train,reward_demo_avg_test,reward_gen_avg,theta\n'
+GRIDSEARCH_LINE = '%s,%d,%d,%f,%f,%f,%f\n'
+
+
+def gridsearch_points(list_reg, list_nfc3, list_nfc4):
+    """The sweep's points (reg, n_fc3, n_fc4) in the reference's loop order: reg outermost, n_fc4 innermost."""
+    return [(str(reg), int(n3), int(n4)) for reg in list_reg for n3 in list_nfc3 for n4 in list_nfc4]
+
+
+def gridsearch_nets(points, d, net_seed=0):
+    """Network p of the sweep: RewardNet(d, reg, n_fc3, n_fc4) initialised under torch.manual_seed(net_seed + p); the caller's
+    torch generator is left as it was."""
+    nets = []
+    with torch.random.fork_rng(devices=[]):
+        for p, (reg, n3, n4) in enumerate(points):
+            torch.manual_seed(int(net_seed) + p)
+            nets.append(RewardNet(d, reg, n_fc3=n3, n_fc4=n4))
+    return nets
+
+
+def gridsearch(list_reg=('dropout', 'l1l2', 'dropout_l1l2'), list_nfc3=range(4, 10, 2), list_nfc4=range(4, 10, 2), *,
+               demonstrations, demonstrations_test=None, theta=6.5, shift=0, alpha_scale=1e4, d=15, batch, seed=0,
+               net_seed=0, outfile='results/reward_gridsearch.csv', outerloop_kwargs=None, update_every='step',
+               precision='mixed', pi0=None, device=None, verbose=0, return_population=False):
+    """The reference's sweep gridsearch.py:8-31 -- for every (reg, n_fc3, n_fc4): AC_IRL(theta, reg=..., n_fc3=..., n_fc4=...),
+    outerloop(), test_reward_network(), one CSV line -- as ONE mixed population: point p is learner p, with the network of
+    gridsearch_nets, Philox seed and host seed `seed + p`.  Runs outerloop(**outerloop_kwargs) and test_reward_network() once
+    for all points and appends the reference's lines ('%s,%d,%d,%f,%f,%f,%f', theta = the point's final theta) to `outfile`
+    (None: no file; its header is written when the file is created).  Returns the rows [(reg, n_fc3, n_fc4, train, test, gen,
+    theta), ...] in the reference's order, and the population as well with return_population=True."""
+    points = gridsearch_points(list_reg, list_nfc3, list_nfc4)
+    if not points:
+        raise ValueError('gridsearch: empty grid')
+    K = len(points)
+    nets = gridsearch_nets(points, int(d), net_seed)
+    seeds = [int(seed) + p for p in range(K)]
+    pop = AC_IRLPopulation([float(theta)] * K, shift, alpha_scale, d, batch=batch, reward_nets=nets, seeds=seeds, pi0=pi0,
+                           update_every=update_every, precision=precision, device=device, verbose=verbose,
+                           demonstrations=demonstrations, demonstrations_test=demonstrations_test, host_seeds=seeds,
+                           mixed_nets=True)
+    thetas = np.asarray(pop.outerloop(**dict(outerloop_kwargs or {})), dtype=np.float64).reshape(-1)
+    avgs = np.asarray(pop.test_reward_network(), dtype=np.float64)
+    rows = [(reg, n3, n4, float(avgs[p, 0]), float(avgs[p, 1]), float(avgs[p, 2]), float(thetas[p]))
+            for p, (reg, n3, n4) in enumerate(points)]
+    if outfile is not None:
+        folder = os.path.dirname(outfile)
+        if folder:
+            os.makedirs(folder, exist_ok=True)
+        new = not os.path.exists(outfile)
+        with open(outfile, 'a') as f:
+            if new:
+                f.write(GRIDSEARCH_HEADER)
+            for row in rows:
+                f.write(GRIDSEARCH_LINE % row)
+    return (rows, pop) if return_population else rows

@@ -640,6 +640,59 @@ def irl_pop_net_geometry(nets):
     return d, n3, n4, k0
 
 
+def irl_pop_net_geometries(nets):
+    """(d, [(n_fc3, n_fc4, keep_prob, l1l2), ...]) of the networks.RewardNet modules `nets`, one entry per network: what a
+    population with a per-learner geometry table (mfg_rn_geom_t, the *_nets entry points) reads.  d, k1 = 5, f2 = 2, k2 = 3 are
+    shared; ValueError where they differ or an entry is outside the matrix-core kernel (d = 15 / 21, n_fc3 <= 16, n_fc4 <= 32,
+    keep_prob in (0, 1])."""
+    if not nets:
+        raise ValueError('no reward network')
+    d0, out = nets[0].d, []
+    for n in nets:
+        d, f1, k1, f2, k2 = n.d, n.conv1.out_channels, n.conv1.kernel_size[0], n.conv2.out_channels, n.conv2.kernel_size[0]
+        n3, n4 = n.fc3.out_features, n.fc4.out_features
+        if d != d0:
+            raise ValueError('reward networks of one population must share d: %d vs %d' % (d, d0))
+        if d not in IRL_POP_D or f1 != 1 or k1 != 5 or f2 != 2 or k2 != 3 or not 1 <= n3 <= IRL_POP_MAX_FC3 or not 1 <= n4 <= 32:
+            raise ValueError('reward network d=%d, f1=%d, k1=%d, f2=%d, k2=%d, n_fc3=%d, n_fc4=%d: IRL populations need the '
+                             'matrix-core kernel (d = 15 / 21, 1 / 5 / 2 / 3, n_fc3 <= %d, n_fc4 <= 32)'
+                             % (d, f1, k1, f2, k2, n3, n4, IRL_POP_MAX_FC3))
+        keep = float(n.keep_prob) if (n.use_dropout and (n.dropout_always or n.training)) else 1.0
+        if not 0.0 < keep <= 1.0:
+            raise ValueError('reward network keep_prob=%g outside (0, 1]' % keep)
+        out.append((n3, n4, keep, bool(n.use_l1l2)))
+    return d0, out
+
+
+RN_GEOM = None           # numpy dtype of mfg_rn_geom_t (L.RnGeomStruct)
+
+
+def rn_geom_table(geoms, device=None):
+    """The geometry table of the *_nets entry points from [(n3, n4, keep_prob, l1l2), ...]: (host NumPy array of mfg_rn_geom_t,
+    its device copy as a uint8 tensor, or None without a device)."""
+    import numpy as np
+    global RN_GEOM
+    if RN_GEOM is None:
+        RN_GEOM = np.dtype(L.RnGeomStruct)
+    host = np.zeros(len(geoms), dtype=RN_GEOM)
+    for k, (n3, n4, keep, l1l2) in enumerate(geoms):
+        host[k] = (int(n3), int(n4), float(keep), int(bool(l1l2)))
+    dev = None
+    if device is not None:
+        dev = torch.from_numpy(host.view(np.uint8).copy()).to(device)
+    return host, dev
+
+
+def _geom_ptrs(geom, K):
+    """(host pointer, device pointer) of a table built by rn_geom_table, [K] entries."""
+    host, dev = geom
+    if host.shape != (K,) or host.dtype.itemsize != 16 or not host.flags['C_CONTIGUOUS']:
+        raise ValueError('geometry table: expected %d contiguous mfg_rn_geom_t entries on the host' % K)
+    if dev is None or not dev.is_cuda or not dev.is_contiguous() or dev.numel() * dev.element_size() != 16 * K:
+        raise ValueError('geometry table: expected a contiguous device copy of %d bytes' % (16 * K))
+    return host.ctypes.data, dev.data_ptr()
+
+
 def _chk_irl_pop(K, B, d, T, episodes, theta, w, G, ws, bufs, reward_acc, mat_pi0, per_learner, shifts, alpha_scales,
                  lr_critic, lr_actor, seeds, rn_seeds, net_struct):
     if not 1 <= K <= L.POP_MAX_K:
@@ -654,7 +707,7 @@ def _chk_irl_pop(K, B, d, T, episodes, theta, w, G, ws, bufs, reward_acc, mat_pi
 
 def train_episodes_irl_pop(mat_pi0, pi, T, episodes, first_episode, constant, theta, shifts, alpha_scales, w, gamma, lr_critic,
                            lr_actor, seeds, net_struct, per_learner_net, rn_seeds, rn_call0, G, ws, bufs, first_step=0,
-                           traj_offset=0, reward_acc=None, precision='mixed', net_stride=0):
+                           traj_offset=0, reward_acc=None, precision='mixed', net_stride=0, geom=None):
     """AC_IRL.train's step mode for K independent learners (mfg_train_episodes_irl_pop): `pi` [K,Bk,d] (output: the final
     states), theta [K], w [K,F], G [K,F+3], ws [K, slice] fp64; shifts, alpha_scales, lr_critic, lr_actor fp64 and seeds,
     rn_seeds int64 (read as uint64) device arrays [K]; net_struct = reward_net_struct(...) of the shared network or of the
@@ -662,7 +715,8 @@ def train_episodes_irl_pop(mat_pi0, pi, T, episodes, first_episode, constant, th
     [K,Bk] f64); reward_acc [K,episodes] fp64 or None.  The episode numbers of the schedule start at first_episode.
     rn_call0: the shared reward-call counter (int), or an int64 device array [K] of per-learner counters
     (mfg_train_episodes_irl_pop_calls); net_stride: elements between two learners' weights in one flat buffer (0: stacked
-    tensors)."""
+    tensors).  geom: a per-learner geometry table (rn_geom_table) -- mfg_train_episodes_irl_pop_nets; needs the counter array
+    and net_stride > 0, and net_struct.conv1_w as the base of learner 0's flat row."""
     import ctypes as C
     _chk_f32(mat_pi0, 'mat_pi0'); _chk_f32(pi, 'pi'); _chk_f64(theta, 'theta'); _chk_f64(w, 'w'); _chk_f64(G, 'G')
     if pi.dim() != 3:
@@ -679,7 +733,13 @@ def train_episodes_irl_pop(mat_pi0, pi, T, episodes, first_episode, constant, th
             lr_actor.data_ptr(), C.byref(net_struct), int(bool(per_learner_net)))
     tail = (P.data_ptr(), bufs['reward'].data_ptr(), bufs['delta'].data_ptr(), bufs['g'].data_ptr(), G.data_ptr(),
             _ptr(reward_acc), ws.data_ptr(), ws.shape[1] * ws.element_size(), _stream())
-    if isinstance(rn_call0, torch.Tensor):
+    if geom is not None:
+        if not isinstance(rn_call0, torch.Tensor):
+            raise ValueError('a geometry table needs the per-learner counter form (rn_call0 as a device array)')
+        _chk_pop(K, 'rn_call0', rn_call0, torch.int64)
+        L.check(L.lib().mfg_train_episodes_irl_pop_nets(*head, int(net_stride), *_geom_ptrs(geom, K), rn_seeds.data_ptr(),
+                                                        rn_call0.data_ptr(), *tail), 'mfg_train_episodes_irl_pop_nets')
+    elif isinstance(rn_call0, torch.Tensor):
         _chk_pop(K, 'rn_call0', rn_call0, torch.int64)
         L.check(L.lib().mfg_train_episodes_irl_pop_calls(*head, int(net_stride), rn_seeds.data_ptr(), rn_call0.data_ptr(), *tail),
                 'mfg_train_episodes_irl_pop_calls')
@@ -692,10 +752,10 @@ def train_episodes_irl_pop(mat_pi0, pi, T, episodes, first_episode, constant, th
 
 def train_rollouts_irl_pop(mat_pi0, T, episodes, first_episode, constant, theta, shifts, alpha_scales, w, gamma, lr_critic,
                            lr_actor, seeds, net_struct, per_learner_net, rn_seeds, rn_call0, G, ws, bufs, first_step=0,
-                           traj_offset=0, discount_pow=True, reward_acc=None, precision='mixed', net_stride=0):
+                           traj_offset=0, discount_pow=True, reward_acc=None, precision='mixed', net_stride=0, geom=None):
     """AC_IRL.train's rollout mode for K independent learners (mfg_train_rollouts_irl_pop): bufs = dict(pi_traj
     [K,Bk,T+1,d] f32, pi_last [K,Bk,d] f32 (optional), P [K,Bk,T,d,d] f32, reward [K,Bk,T] f32, delta / g [K,Bk,T] f64);
-    the other arrays, rn_call0 and net_stride as for train_episodes_irl_pop."""
+    the other arrays, rn_call0, net_stride and geom (mfg_train_rollouts_irl_pop_nets) as for train_episodes_irl_pop."""
     import ctypes as C
     _chk_f32(mat_pi0, 'mat_pi0'); _chk_f64(theta, 'theta'); _chk_f64(w, 'w'); _chk_f64(G, 'G')
     if bufs['pi_traj'].dim() != 4:
@@ -714,7 +774,13 @@ def train_rollouts_irl_pop(mat_pi0, T, episodes, first_episode, constant, theta,
     tail = (bufs['pi_traj'].data_ptr(), _ptr(bufs.get('pi_last')), P.data_ptr(), bufs['reward'].data_ptr(),
             bufs['delta'].data_ptr(), bufs['g'].data_ptr(), G.data_ptr(), _ptr(reward_acc), ws.data_ptr(),
             ws.shape[1] * ws.element_size(), _stream())
-    if isinstance(rn_call0, torch.Tensor):
+    if geom is not None:
+        if not isinstance(rn_call0, torch.Tensor):
+            raise ValueError('a geometry table needs the per-learner counter form (rn_call0 as a device array)')
+        _chk_pop(K, 'rn_call0', rn_call0, torch.int64)
+        L.check(L.lib().mfg_train_rollouts_irl_pop_nets(*head, int(net_stride), *_geom_ptrs(geom, K), rn_seeds.data_ptr(),
+                                                        rn_call0.data_ptr(), *tail), 'mfg_train_rollouts_irl_pop_nets')
+    elif isinstance(rn_call0, torch.Tensor):
         _chk_pop(K, 'rn_call0', rn_call0, torch.int64)
         L.check(L.lib().mfg_train_rollouts_irl_pop_calls(*head, int(net_stride), rn_seeds.data_ptr(), rn_call0.data_ptr(), *tail),
                 'mfg_train_rollouts_irl_pop_calls')
@@ -725,10 +791,12 @@ def train_rollouts_irl_pop(mat_pi0, T, episodes, first_episode, constant, theta,
     return bufs
 
 
-def reward_net_forward_pop(net_struct, per_learner_net, K, state, action, learners, keys, out=None, net_stride=0, scratch=None):
+def reward_net_forward_pop(net_struct, per_learner_net, K, state, action, learners, keys, out=None, net_stride=0, scratch=None,
+                           geom=None):
     """mfg_reward_net_forward_pop: the reward network of the listed learners (distinct, in [0, K)) in one launch.  state [N,d] /
     action [N,d,d] (shared by every learner) or [K,N,d] / [K,N,d,d] (learner k reads row k); keys: the Philox keys of the listed
-    learners (Python ints, read as uint64).  Returns out [K,N] f32 (rows of unlisted learners untouched); sample offset 0."""
+    learners (Python ints, read as uint64).  Returns out [K,N] f32 (rows of unlisted learners untouched); sample offset 0.
+    geom: a per-learner geometry table (rn_geom_table) -- mfg_reward_net_forward_pop_nets."""
     import ctypes as C
     import numpy as np
     _chk_f32(state, 'state'); _chk_f32(action, 'action')
@@ -754,10 +822,14 @@ def reward_net_forward_pop(net_struct, per_learner_net, K, state, action, learne
     _chk_f32(out, 'out')
     if scratch is None:
         scratch = torch.empty(max(2 * lr.size, 2), dtype=torch.float64, device=state.device)
-    L.check(L.lib().mfg_reward_net_forward_pop(
-        state.data_ptr(), action.data_ptr(), 0 if shared else N * d, 0 if shared else N * d * d, N, d, C.byref(net_struct),
-        int(bool(per_learner_net)), int(net_stride), int(K), lr.ctypes.data, ky.ctypes.data, int(lr.size), 0, out.data_ptr(),
-        scratch.data_ptr(), scratch.numel() * scratch.element_size(), _stream()), 'mfg_reward_net_forward_pop')
+    head = (state.data_ptr(), action.data_ptr(), 0 if shared else N * d, 0 if shared else N * d * d, N, d, C.byref(net_struct),
+            int(bool(per_learner_net)), int(net_stride))
+    tail = (int(K), lr.ctypes.data, ky.ctypes.data, int(lr.size), 0, out.data_ptr(), scratch.data_ptr(),
+            scratch.numel() * scratch.element_size(), _stream())
+    if geom is not None:
+        L.check(L.lib().mfg_reward_net_forward_pop_nets(*head, *_geom_ptrs(geom, K), *tail), 'mfg_reward_net_forward_pop_nets')
+    else:
+        L.check(L.lib().mfg_reward_net_forward_pop(*head, *tail), 'mfg_reward_net_forward_pop')
     return out
 
 
@@ -774,10 +846,12 @@ def rn_train_plan(n):
 
 
 def reward_net_train_steps_pop(params, m, v, param_stride, K, dims, demo, gen, plan, n_updates, n_active, n_demo, n_gen, steps,
-                               demo_divisor, keep_prob, l1l2, stats, ws, plan_dev, beta1=0.9, beta2=0.999, eps=1e-8):
+                               demo_divisor, keep_prob, l1l2, stats, ws, plan_dev, beta1=0.9, beta2=0.999, eps=1e-8, geom=None):
     """mfg_reward_net_train_steps_pop: n_updates update_reward steps of n_active learners.  params / m / v [K, param_stride] f32,
     dims = (d, k1, f2, k2, n3, n4), demo = (state [rows,T,d], action [rows,T,d,d]) shared, gen = (state [K,cap,T,d], action
-    [K,cap,T,d,d]), plan = rn_train_plan(n_updates * n_active), stats [K,4] f32, ws / plan_dev device byte buffers (uint8)."""
+    [K,cap,T,d,d]), plan = rn_train_plan(n_updates * n_active), stats [K,4] f32, ws / plan_dev device byte buffers (uint8).
+    geom: a per-learner geometry table (rn_geom_table) -- mfg_reward_net_train_steps_pop_nets: n3, n4, keep_prob and l1l2 come
+    from the table (dims[4:], keep_prob and l1l2 are not read), rows hold learner k's own layout."""
     for name, t in (('params', params), ('adam_m', m), ('adam_v', v)):
         _chk_f32(t, name)
         if tuple(t.shape) != (K, param_stride):
@@ -793,12 +867,18 @@ def reward_net_train_steps_pop(params, m, v, param_stride, K, dims, demo, gen, p
         raise ValueError('generated stores: expected [%d, cap, T, d] / [%d, cap, T, d, d]' % (K, K))
     if plan.size < n_updates * n_active:
         raise ValueError('plan: fewer than n_updates * n_active entries')
-    L.check(L.lib().mfg_reward_net_train_steps_pop(
-        params.data_ptr(), m.data_ptr(), v.data_ptr(), int(param_stride), int(K), *[int(x) for x in dims], ds.data_ptr(),
-        da.data_ptr(), ds.shape[0], gs.data_ptr(), ga.data_ptr(), gs.shape[1], plan.ctypes.data, plan_dev.data_ptr(),
-        plan_dev.numel() * plan_dev.element_size(), int(n_updates), int(n_active), int(n_demo), int(n_gen), int(steps),
-        int(demo_divisor), float(keep_prob), int(bool(l1l2)), float(beta1), float(beta2), float(eps), stats.data_ptr(),
-        ws.data_ptr(), ws.numel() * ws.element_size(), _stream()), 'mfg_reward_net_train_steps_pop')
+    stores = (ds.data_ptr(), da.data_ptr(), ds.shape[0], gs.data_ptr(), ga.data_ptr(), gs.shape[1], plan.ctypes.data,
+              plan_dev.data_ptr(), plan_dev.numel() * plan_dev.element_size(), int(n_updates), int(n_active), int(n_demo),
+              int(n_gen), int(steps), int(demo_divisor))
+    tail = (float(beta1), float(beta2), float(eps), stats.data_ptr(), ws.data_ptr(), ws.numel() * ws.element_size(), _stream())
+    if geom is not None:
+        L.check(L.lib().mfg_reward_net_train_steps_pop_nets(
+            params.data_ptr(), m.data_ptr(), v.data_ptr(), int(param_stride), int(K), *[int(x) for x in dims[:4]],
+            *_geom_ptrs(geom, K), *stores, *tail), 'mfg_reward_net_train_steps_pop_nets')
+    else:
+        L.check(L.lib().mfg_reward_net_train_steps_pop(
+            params.data_ptr(), m.data_ptr(), v.data_ptr(), int(param_stride), int(K), *[int(x) for x in dims], *stores,
+            float(keep_prob), int(bool(l1l2)), *tail), 'mfg_reward_net_train_steps_pop')
 
 
 def episode_buffers(B, d, device):

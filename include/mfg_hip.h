@@ -530,7 +530,7 @@ int mfg_train_rollout_irl(const float* mat_pi0, int64_t num_start, const int32_t
  * 0x9E3779B97F4A7C15);  rollout mode, episode e:  rn_seed[k] ^ ((rn_call0 + e + 1) x 0x9E3779B97F4A7C15)  (mod 2^64).
  * Reward networks: `net` (host struct).  per_learner_net = 0: every learner reads the same tensors; 1: every pointer is the
  * base of a stacked tensor, learner k's tensor t at base_t + k numel_t (numel_t from the geometry: k1^2, 1, f2 k2^2, f2,
- * n3 f2 d^2, n3, n4 (n3 + d), n4, n4, 1).  Geometry and keep_prob are shared.
+ * n3 f2 d^2, n3, n4 (n3 + d), n4, n4, 1).  Geometry and keep_prob are shared (per learner: the *_nets entry points below).
  * Per-learner scalars and learner-major arrays as for mfg_train_episodes_pop / mfg_train_rollouts_pop, plus P: step mode
  * pi_out / pi_scratch [K,Bk,d], P [K,Bk,d,d], reward / delta / g [K,Bk]; rollout mode pi_traj [K,Bk,T+1,d], pi_last [K,Bk,d]
  * (may be NULL), P [K,Bk,T,d,d], reward / delta / g [K,Bk,T].  reward_acc [K,episodes] (may be NULL; step mode: += every
@@ -626,6 +626,64 @@ int mfg_reward_net_train_steps_pop(float* params, float* adam_m, float* adam_v, 
                                    int n_active, int n_demo, int n_gen, int steps, int demo_divisor, float keep_prob, int l1l2,
                                    double beta1, double beta2, double eps, float* stats, void* workspace, size_t workspace_bytes,
                                    mfg_stream_t stream);
+
+/* Populations whose learners differ in the SHAPE and the REGULARISER of their reward networks: the reference's sweep
+ * gridsearch.py:8-31 (reg x n_fc3 x n_fc4, one AC_IRL per point) as ONE population.  Entry k of a geometry table is learner
+ * k's n_fc3, n_fc4, keep_prob (1: no dropout) and l1_l2 flag (read by the training steps only); d, k1 = 5, f2 = 2, k2 = 3 stay
+ * shared.  Limits per entry, those of the matrix-core kernel: 1 <= n3 <= 16, 1 <= n4 <= 32, keep_prob in (0, 1]. */
+typedef struct mfg_rn_geom { int32_t n3, n4; float keep_prob; int32_t l1l2; } mfg_rn_geom_t;   /* 16 bytes */
+
+/* The four *_nets entry points below are mfg_train_episodes_irl_pop_calls, mfg_train_rollouts_irl_pop_calls,
+ * mfg_reward_net_forward_pop and mfg_reward_net_train_steps_pop with such a table: geom_host [K] is read by the checks,
+ * geom_dev [K] (device, the same entries) by the kernels.  Both are required, and so are per_learner_net = 1 and
+ * net_stride / param_stride > 0: learner k's parameters are ONE flat row at conv1_w + k net_stride (params + k param_stride)
+ * in the order and at the offsets of mfg_reward_net_param_offsets(d, 5, 2, 3, n3_k, n4_k); rows are as long as the longest
+ * learner's and nothing beyond a learner's own NP_k floats is read or written.  Of the struct, k1 / f2 / k2 and conv1_w (the
+ * base of row 0) are read; n3, n4, keep_prob and the other nine pointers are ignored.
+ * Learner k of a mixed call gives, bit for bit, what the single entry point (mfg_train_episode_irl_draw,
+ * mfg_train_rollout_irl, mfg_reward_net_forward, mfg_reward_net_train_step) gives with learner k's geometry; a table whose
+ * entries are all equal gives the bits of the entry point without a table.  Dynamic LDS and workspace slices are sized for
+ * the largest n3 and the largest n4 of the table; the combine kernel's grid is ceil(max NP_k / 64) wide and blocks beyond a
+ * learner's own NP_k do nothing.  No allocation; the training entry points do not synchronise.
+ * Checked before anything is launched, on top of the checks of the entry point without a table: MFG_EINVAL for a null table
+ * (either copy), per_learner_net = 0, a stride below the largest NP_k, an entry's keep_prob outside (0, 1]; MFG_EUNSUPPORTED
+ * for an entry outside n3 <= 16 / n4 <= 32, d other than 15 / 21, an fc3_w of any learner not 8-byte aligned, a training batch
+ * beyond the single step's limits at the largest n3; MFG_EWORKSPACE as without a table, at the largest geometry. */
+/* AC_IRL.train in step mode (ac_irl.py:634-732) for the K points of gridsearch.py:8-31 */
+int mfg_train_episodes_irl_pop_nets(const float* mat_pi0, int64_t num_start, float* pi_out, float* pi_scratch, int64_t B, int K,
+                                    int d, int T, int64_t episodes, int64_t first_episode, int constant, double* theta,
+                                    const double* shift, const double* alpha_scale, double* w, double gamma, const uint64_t* seed,
+                                    uint32_t first_step, uint64_t traj_offset, int precision, const double* lr_critic,
+                                    const double* lr_actor, const mfg_reward_net_t* net_host, int per_learner_net,
+                                    int64_t net_stride, const mfg_rn_geom_t* geom_host, const mfg_rn_geom_t* geom_dev,
+                                    const uint64_t* rn_seed, const uint64_t* rn_call0, float* P, float* reward, double* delta,
+                                    double* g, double* G, double* reward_acc, void* workspace, size_t workspace_bytes,
+                                    mfg_stream_t stream);
+/* ... in rollout mode (one update per episode) */
+int mfg_train_rollouts_irl_pop_nets(const float* mat_pi0, int64_t num_start, int64_t B, int K, int d, int T, int64_t episodes,
+                                    int64_t first_episode, int constant, double* theta, const double* shift,
+                                    const double* alpha_scale, double* w, double gamma, const uint64_t* seed, uint32_t first_step,
+                                    uint64_t traj_offset, int flags, const double* lr_critic, const double* lr_actor,
+                                    const mfg_reward_net_t* net_host, int per_learner_net, int64_t net_stride,
+                                    const mfg_rn_geom_t* geom_host, const mfg_rn_geom_t* geom_dev, const uint64_t* rn_seed,
+                                    const uint64_t* rn_call0, float* pi_traj, float* pi_last, float* P, float* reward,
+                                    double* delta, double* g, double* G, double* reward_acc, void* workspace,
+                                    size_t workspace_bytes, mfg_stream_t stream);
+/* the reward averages of reward_iteration and test_reward_network (ac_irl.py:848-897, :1008-1046) for the listed points */
+int mfg_reward_net_forward_pop_nets(const float* state, const float* action, int64_t s_state, int64_t s_action, int64_t N, int d,
+                                    const mfg_reward_net_t* net_host, int per_learner_net, int64_t net_stride,
+                                    const mfg_rn_geom_t* geom_host, const mfg_rn_geom_t* geom_dev, int K,
+                                    const int32_t* learners_host, const uint64_t* keys_host, int n, uint64_t sample_offset,
+                                    float* reward, void* scratch, size_t scratch_bytes, mfg_stream_t stream);
+/* update_reward (ac_irl.py:804-846) of the points of a plan; n3, n4, keep_prob and l1l2 come from the table */
+int mfg_reward_net_train_steps_pop_nets(float* params, float* adam_m, float* adam_v, int64_t param_stride, int K, int d, int k1,
+                                        int f2, int k2, const mfg_rn_geom_t* geom_host, const mfg_rn_geom_t* geom_dev,
+                                        const float* demo_state, const float* demo_action, int64_t demo_capacity,
+                                        const float* gen_state, const float* gen_action, int64_t gen_capacity,
+                                        mfg_rn_train_plan_t* plan_host, void* plan_dev, size_t plan_dev_bytes, int n_updates,
+                                        int n_active, int n_demo, int n_gen, int steps, int demo_divisor, double beta1,
+                                        double beta2, double eps, float* stats, void* workspace, size_t workspace_bytes,
+                                        mfg_stream_t stream);
 
 /* f1 (optional importance weights, ac_irl.py:270-289 calc_pdf_action, :324-379 calc_z): log-density of the
  * product-Dirichlet policy for N (state, action) pairs under K policies theta_k (device array):

@@ -1,0 +1,480 @@
+"""Mixed IRL populations on the GPU: learners whose reward networks differ in n_fc3, n_fc4 and regulariser (the axes of the
+reference's sweep gridsearch.py:8-31) in the launches of one population.  Every comparison is torch.equal / array_equal:
+learner k of a mixed call gives what the single entry point gives with learner k's geometry, a uniform table gives the bits
+of the shared-geometry path, and the class's train / outerloop / test_reward_network / gridsearch give learner k what AC_IRL
+gives."""
+import ctypes as C
+import random
+import types
+
+import numpy as np
+import pytest
+
+torch = pytest.importorskip('torch')
+
+pytestmark = pytest.mark.gpu
+T = 15
+# (reg, n_fc3, n_fc4): the shared-draw branch and the shortest row | keep_prob = 1 next to dropout | both maxima | no regulariser
+M4 = (('dropout', 4, 4), ('l1l2', 8, 6), ('dropout_l1l2', 16, 32), ('none', 6, 8))
+NOT_COMPARED = ('np_random_key', 'np_random_pos', 'np_random_has_gauss', 'np_random_cached_gaussian', 'torch_rng_state',
+                'torch_cuda_rng_state')
+EINVAL, EUNSUPPORTED = -1, -3
+
+
+@pytest.fixture(scope='module')
+def dev():
+    if not torch.cuda.is_available():
+        pytest.fail('-m gpu tests need a GPU')
+    return torch.device('cuda:0')
+
+
+def _nets(d, points, seed0, dev):
+    from discrete_mean_field_game_amd.networks import RewardNet
+    out = []
+    for j, (reg, n3, n4) in enumerate(points):
+        torch.manual_seed(seed0 + j)
+        net = RewardNet(d=d, reg=reg, n_fc3=n3, n_fc4=n4).to(dev)
+        with torch.no_grad():          # non-zero biases: every tensor of the network matters
+            for p in net.parameters():
+                if p.dim() == 1:
+                    p.uniform_(-0.2, 0.2)
+        out.append(net)
+    return out
+
+
+def _table(d, seed=3):
+    return np.random.RandomState(seed).dirichlet(np.ones(d), size=9)
+
+
+def _demos(d, n, seed=5):
+    rs = np.random.RandomState(seed)
+    return [[(rs.dirichlet(np.ones(d)), rs.dirichlet(np.ones(d), size=d)) for _ in range(T)] for _ in range(n)]
+
+
+def _population(d, nets, dev, mode='step', B=32, precision='mixed', mixed=True, lr_reward=1e-3, demos=None, demos_test=None,
+                num_policies=3, w0=None, seeds=None):
+    from discrete_mean_field_game_amd.irl_population import AC_IRLPopulation
+    K = len(nets)
+    seeds = list(range(11, 11 + K)) if seeds is None else seeds
+    return AC_IRLPopulation(np.linspace(8.0, 9.0, K), 0.1, 1e4, d, batch=B, reward_nets=nets, seeds=seeds, pi0=_table(d),
+                            update_every=mode, precision=precision, device=dev, w0=w0,
+                            demonstrations=_demos(d, 7) if demos is None else demos, lr_reward=lr_reward,
+                            num_policies=num_policies, mixed_nets=mixed, demonstrations_test=demos_test)
+
+
+def _flat_rows(nets, dev, fill=0.0):
+    """(flat [K, stride] in the mixed layout, trainers, geometry table, stride): row k = learner k's own flat parameters."""
+    from discrete_mean_field_game_amd import ops
+    from discrete_mean_field_game_amd.reward_learning import RewardTrainer
+    trainers = [RewardTrainer(n, 1e-3 * (k + 1)) for k, n in enumerate(nets)]
+    stride = (max(t.flat.numel() for t in trainers) + 63) // 64 * 64
+    flat = torch.full((len(nets), stride), fill, device=dev)
+    for k, t in enumerate(trainers):
+        flat[k, :t.flat.numel()] = t.flat
+    _, geoms = ops.irl_pop_net_geometries(nets)
+    return flat, trainers, ops.rn_geom_table(geoms, dev), stride
+
+
+def _row_struct(flat):
+    from discrete_mean_field_game_amd import _lib as L
+    st = L.RewardNetStruct()
+    st.k1, st.f2, st.k2, st.n3, st.n4, st.keep_prob = 5, 2, 3, 1, 1, 1.0
+    for f in ('conv1_w', 'conv1_b', 'conv2_w', 'conv2_b', 'fc3_w', 'fc3_b', 'fc4_w', 'fc4_b', 'out_w', 'out_b'):
+        setattr(st, f, flat.data_ptr())
+    return st
+
+
+def _compare(a, b, path=''):
+    if isinstance(a, dict):
+        assert set(a) == set(b), path
+        for k in a:
+            if k not in NOT_COMPARED:
+                _compare(a[k], b[k], path + '/' + str(k))
+    elif isinstance(a, torch.Tensor):
+        assert torch.equal(a.cpu(), b.cpu()), path
+    elif isinstance(a, (list, tuple)):
+        assert len(a) == len(b), path
+        for i, (x, y) in enumerate(zip(a, b)):
+            _compare(x, y, '%s[%d]' % (path, i))
+    else:
+        assert a == b, (path, a, b)
+
+
+# ------------------------------------------------------------------ 1. forward
+@pytest.mark.parametrize('d', [15, 21])
+def test_forward_pop_nets_equals_single_forward(dev, d):
+    from discrete_mean_field_game_amd import ops
+    K, N = 4, 37                           # 37: not a multiple of the 16-sample group
+    nets = _nets(d, M4, 200 + d, dev)
+    flat, _, geom, stride = _flat_rows(nets, dev)
+    g = torch.Generator(device='cpu').manual_seed(d)
+    st = torch.rand(K, N, d, generator=g).to(dev)
+    ac = torch.rand(K, N, d, d, generator=g)
+    ac = (ac / ac.sum(-1, keepdim=True)).to(dev)
+    keys = [123, 2 ** 63 + 5, 77, 9001]
+    out = torch.full((K, N), -9.0, device=dev)
+    listed = [2, 0, 3]
+    ops.reward_net_forward_pop(_row_struct(flat), True, K, st, ac, listed, [keys[k] for k in listed], out=out, net_stride=stride,
+                               geom=geom)
+    for k in listed:
+        ref = ops.reward_net_forward(nets[k], st[k], ac[k], seed=keys[k])
+        assert torch.equal(out[k], ref.reshape(-1)), k
+    assert torch.equal(out[1], torch.full((N,), -9.0, device=dev))
+
+
+# ------------------------------------------------------------------ 2. training steps
+@pytest.mark.parametrize('d', [15, 21])
+def test_train_steps_pop_nets_equals_single_steps(dev, d):
+    from discrete_mean_field_game_amd import ops
+    from discrete_mean_field_game_amd.reward_learning import StackedTrajectoryStore, TrajectoryStore
+    K, U, PATTERN = 4, 3, 7.25
+    nets = _nets(d, M4, 300 + d, dev)
+    flat, trainers, geom, stride = _flat_rows(nets, dev, fill=PATTERN)
+    m = torch.full_like(flat, PATTERN)
+    v = torch.full_like(flat, PATTERN)
+    g = torch.Generator(device='cpu').manual_seed(K + d)
+    for k, tr in enumerate(trainers):      # a different Adam history per learner
+        np_ = tr.flat.numel()
+        tr.m.copy_((torch.rand(np_, generator=g) * 1e-3).to(dev))
+        tr.v.copy_((torch.rand(np_, generator=g) * 1e-6).to(dev))
+        tr.step_count = 3 * k
+        m[k, :np_] = tr.m
+        v[k, :np_] = tr.v
+    # stores whose physical rows differ from the logical order: pushes with drops in between
+    rs = np.random.RandomState(d)
+    demo = TrajectoryStore(d, T, dev)
+    gen = StackedTrajectoryStore(K, d, T, dev)
+    demo.push(torch.as_tensor(rs.dirichlet(np.ones(d), size=(3, T)), dtype=torch.float32),
+              torch.as_tensor(rs.dirichlet(np.ones(d), size=(3, T, d)), dtype=torch.float32))
+    demo.push(torch.as_tensor(rs.dirichlet(np.ones(d) * 0.7, size=(5, T)), dtype=torch.float32),
+              torch.as_tensor(rs.dirichlet(np.ones(d) * 0.5, size=(5, T, d)), dtype=torch.float32), drop=2)
+    gen.push(torch.as_tensor(rs.dirichlet(np.ones(d), size=(K, 3, T)), dtype=torch.float32).to(dev),
+             torch.as_tensor(rs.dirichlet(np.ones(d), size=(K, 3, T, d)), dtype=torch.float32).to(dev))
+    gen.push(torch.as_tensor(rs.dirichlet(np.ones(d) * 0.7, size=(K, 5, T)), dtype=torch.float32).to(dev),
+             torch.as_tensor(rs.dirichlet(np.ones(d) * 0.5, size=(K, 5, T, d)), dtype=torch.float32).to(dev), drop=2)
+    drow, grow = list(demo.rows), list(gen.rows)
+    assert drow != list(range(len(drow))) and grow != list(range(len(grow)))
+    rnd = random.Random(7)
+    skipped = 1                            # the second update skips learner 1
+    plans = []
+    for u in range(U):
+        learners = [k for k in range(K) if not (u == 1 and k == skipped)]
+        plan = ops.rn_train_plan(len(learners))
+        for s, k in enumerate(learners):
+            e = plan[s]
+            e['learner'] = k
+            e['key'] = rnd.getrandbits(64)
+            e['lr'] = trainers[k].lr
+            e['adam_step'] = trainers[k].step_count + 1 + sum(1 for p in plans if k in p['learner'])
+            e['demo_rows'][:5] = [drow[i] for i in rnd.sample(range(len(drow)), 5)]
+            e['gen_rows'][:5] = [grow[i] for i in rnd.sample(range(len(grow)), 5)]
+        plans.append(plan)
+    stats = torch.zeros(K, 4, device=dev)
+    dims = (d, 5, 2, 3, 16, 32)
+    from discrete_mean_field_game_amd import _lib as L
+    # K slices of the single step's workspace at the largest n_fc3 / n_fc4, each rounded up to 256 bytes
+    ws = torch.empty(K * ((int(L.lib().mfg_reward_net_train_workspace_bytes(*dims, 10 * T)) + 255) // 256 * 256), dtype=torch.uint8,
+                     device=dev)
+    snapshot = None
+    for u, plan in enumerate(plans):
+        if u == 1:
+            snapshot = (flat[skipped].clone(), m[skipped].clone(), v[skipped].clone(), stats[skipped].clone())
+        plan_dev = torch.empty(plan.nbytes, dtype=torch.uint8, device=dev)
+        ops.reward_net_train_steps_pop(flat, m, v, stride, K, dims, (demo.state, demo.action), (gen.state, gen.action), plan, 1,
+                                       len(plan), 5, 5, T, 5, 1.0, False, stats, ws, plan_dev, geom=geom)
+        if u == 1:                         # the skipped learner's rows are untouched by this update
+            torch.cuda.synchronize()
+            for got, was in zip((flat[skipped], m[skipped], v[skipped], stats[skipped]), snapshot):
+                assert torch.equal(got, was)
+    dstore = types.SimpleNamespace(state=demo.state, action=demo.action, steps=T)
+    for k, tr in enumerate(trainers):
+        gstore = types.SimpleNamespace(state=gen.state[k], action=gen.action[k], steps=T)
+        for plan in plans:
+            for e in plan:
+                if int(e['learner']) == k:
+                    tr.step(dstore, [int(r) for r in e['demo_rows'][:5]], gstore, [int(r) for r in e['gen_rows'][:5]], 5,
+                            int(e['key']))
+        np_ = tr.flat.numel()
+        assert torch.equal(flat[k, :np_], tr.flat), k
+        assert torch.equal(m[k, :np_], tr.m) and torch.equal(v[k, :np_], tr.v), k
+        assert torch.equal(stats[k], tr.stats), k
+        for buf in (flat, m, v):           # nothing beyond the learner's own parameter count is written
+            assert torch.equal(buf[k, np_:], torch.full((stride - np_,), PATTERN, device=dev)), k
+
+
+# ------------------------------------------------------------------ 3. a uniform table gives the shared-geometry bits
+@pytest.mark.parametrize('mode', ['step', 'rollout'])
+def test_uniform_table_equals_shared_geometry(dev, mode):
+    d = 15
+    points = (('dropout_l1l2', 8, 4),) * 4
+    pops = []
+    for mixed in (True, False):
+        np.random.seed(2)                  # the same initial critic weights
+        pop = _population(d, _nets(d, points, 400, dev), dev, mode=mode, B=50, mixed=mixed)
+        ret = pop.train(2, 0.9)
+        pop._gen_store.push(*pop._generate(6))
+        its, last = pop.reward_iteration(20, 1e-4, 10)
+        pops.append((pop, ret, its, last))
+    (a, ra, ia, la), (b, rb, ib, lb) = pops
+    assert a._geom is not None and b._geom is None
+    assert np.array_equal(ra, rb) and np.array_equal(ia, ib) and np.array_equal(la, lb)
+    assert torch.equal(a._theta, b._theta) and torch.equal(a._w, b._w)
+    assert torch.equal(a._flat, b._flat) and torch.equal(a._adam_m, b._adam_m) and torch.equal(a._adam_v, b._adam_v)
+    assert torch.equal(a._rt_stats, b._rt_stats) and np.array_equal(a._calls_k, b._calls_k)
+
+
+# ------------------------------------------------------------------ 4. forward solve
+def _single_returns(mode, d, B, precision, net, seed, theta, shift, alpha, w0, E, gamma, dev):
+    """theta, w and the per-episode returns from the single-learner native IRL calls, as AC_IRL.train issues them."""
+    from discrete_mean_field_game_amd import ops
+    from discrete_mean_field_game_amd.parallel import lr_scales
+    F = ops.num_features(d)
+    mat = torch.as_tensor(np.ascontiguousarray(_table(d), dtype=np.float32), device=dev)
+    th = torch.tensor([theta], dtype=torch.float64, device=dev)
+    w = torch.as_tensor(np.ascontiguousarray(w0, dtype=np.float64), device=dev).clone()
+    G = torch.zeros(F + 3, dtype=torch.float64, device=dev)
+    acc = torch.zeros(E, dtype=torch.float64, device=dev)
+    if mode == 'step':
+        ws = ops.workspace(B, d, dev)
+        bufs = dict(ops.episode_buffers(B, d, dev), P=torch.empty(B, 1, d, d, dtype=torch.float32, device=dev))
+        pi = torch.empty(B, d, dtype=torch.float32, device=dev)
+        for e in range(E):
+            sc, sa = lr_scales(1 + e, False)
+            ops.train_episode_irl(pi, T, th, shift, alpha, w, gamma, 0.1 * sc, 0.001 * sa, net, G, ws, bufs, seed=seed,
+                                  first_step=e * T, rn_seed=seed + 0x5EED, rn_call0=e * T, rn_sample_offset=0,
+                                  reward_acc=acc[e:e + 1], precision=precision, mat_pi0=mat)
+    else:
+        ws = ops.workspace(B * T, d, dev)
+        bufs = {'pi_traj': torch.empty(B, T + 1, d, dtype=torch.float32, device=dev),
+                'pi_last': torch.empty(B, d, dtype=torch.float32, device=dev),
+                'P': torch.empty(B, T, d, d, dtype=torch.float32, device=dev),
+                'reward': torch.empty(B * T, dtype=torch.float32, device=dev),
+                'delta': torch.empty(B, T, dtype=torch.float64, device=dev),
+                'g': torch.empty(B, T, dtype=torch.float64, device=dev)}
+        for e in range(E):
+            sc, sa = lr_scales(1 + e, False)
+            key = ((seed + 0x5EED) ^ ((e + 1) * 0x9E3779B97F4A7C15)) & 0xFFFFFFFFFFFFFFFF
+            ops.train_rollout_irl(mat, None, T, th, shift, alpha, w, gamma, 0.1 * sc, 0.001 * sa, net, G, ws, bufs, seed=seed,
+                                  first_step=e * T, rn_key=key, rn_sample_offset=0, reward_acc=acc[e:e + 1], precision=precision)
+    return th, w, (acc * T if mode == 'rollout' else acc).cpu().numpy()
+
+
+@pytest.mark.parametrize('mode,d,precision', [('step', 15, 'mixed'), ('rollout', 15, 'mixed'), ('step', 21, 'mixed'),
+                                               ('rollout', 21, 'mixed'), ('step', 21, 'f64')])
+def test_train_equals_ac_irl(dev, mode, d, precision):
+    from discrete_mean_field_game_amd.ac_irl import AC_IRL
+    K, B, E = 4, 50, 2                     # 50: ragged against the 12 / 16 trajectories per block of the packed mapping
+    np.random.seed(9)
+    pop = _population(d, _nets(d, M4, 500 + d, dev), dev, mode=mode, B=B, precision=precision)
+    w0 = pop.w
+    ret = pop.train(E, 0.9, False, 0.1, 0.001)
+    for k in range(K):
+        ac = AC_IRL(float(pop.theta_initial[k]), 0.1, 1e4, d, pi0=_table(d), demonstrations=[], batch=B, seed=int(pop.seeds[k]),
+                    update_every=mode, precision=precision, device=dev, verbose=0)
+        ac.reward_net = pop.reward_net(k)
+        ac.create_training_method()
+        ac.w = w0[k]
+        ac.train(max_episodes=E, stop_criteria=-1, gamma=0.9, constant=False, lr_critic=0.1, lr_actor=0.001)
+        lk = pop.learner(k)
+        assert (lk.reward_net.reg, lk.reward_net.fc3.out_features, lk.reward_net.fc4.out_features) == M4[k]
+        assert float(np.ravel(lk.theta)[0]) == float(np.ravel(ac.theta)[0]), k
+        assert np.array_equal(np.asarray(lk.w), np.asarray(ac.w)), k
+        assert lk._rng_step == ac._rng_step and lk._reward_calls == ac._reward_calls
+        th, w, acc = _single_returns(mode, d, B, precision, pop.reward_net(k), int(pop.seeds[k]), float(pop.theta_initial[k]),
+                                     0.1, 1e4, w0[k], E, 0.9, dev)
+        assert torch.equal(pop._theta[k:k + 1], th) and torch.equal(pop._w[k], w), k
+        assert np.array_equal(ret[k], acc), k
+
+
+# ------------------------------------------------------------------ 5. the whole loop
+@pytest.mark.parametrize('mode,d', [('step', 21), ('rollout', 15)])
+def test_outerloop_equals_ac_irl(dev, mode, d):
+    K = 4
+    pop = _population(d, _nets(d, M4, 600 + d, dev), dev, mode=mode, lr_reward=[2e-3, 5e-4, 1e-3, 3e-3])
+    kw = dict(num_iterations=2, num_gen_from_policy=2, max_reward_iterations=20, max_forward_episodes=3)
+    singles = []
+    for k in range(K):
+        ac = pop.learner(k)
+        ac.outerloop(final_training=False, **kw)
+        singles.append((float(np.ravel(ac.theta)[0]), ac.state_dict()))
+    state = random.getstate()
+    thetas = pop.outerloop(final_training=False, **kw)
+    assert random.getstate() == state
+    for k, (theta, st) in enumerate(singles):
+        assert thetas[k] == theta, k
+        _compare(pop.learner(k).state_dict(), st)
+    assert torch.equal(pop._flat[0, pop._row_offsets[0][10]:], torch.zeros_like(pop._flat[0, pop._row_offsets[0][10]:]))
+
+
+def test_reward_iteration_learners_leave_at_different_checks(dev):
+    d, K = 15, 4
+    pop = _population(d, _nets(d, M4, 700, dev), dev, lr_reward=[1e-3, 0.0, 3e-3, 1e-3])
+    pop._gen_store.push(*pop._generate(8))
+    singles = []
+    for k in range(K):
+        ac = pop.learner(k)                       # the module random stream now is Random(host_seed_k)
+        ac.reward_iteration(max_iterations=60, stop_criteria=2e-4, iter_check=10)
+        singles.append((ac, random.getstate()))
+    its, last = pop.reward_iteration(max_iterations=60, stop_criteria=2e-4, iter_check=10)
+    print('iterations', its.tolist(), 'averages', last.tolist())
+    assert len(set(its.tolist())) > 1, its
+    assert its[1] == 20                          # lr_reward = 0 without dropout: the second check repeats the first average
+    for k, (ac, rstate) in enumerate(singles):
+        assert ac.reward_update_count == its[k]
+        assert pop.host_random_state(k) == rstate
+        _compare(pop.learner(k).state_dict(), ac.state_dict())
+
+
+# ------------------------------------------------------------------ 6. test_reward_network
+@pytest.mark.parametrize('with_test', [True, False])
+def test_test_reward_network_equals_ac_irl(dev, with_test):
+    d, K = 15, 4
+    demos_test = _demos(d, 3, seed=8) if with_test else None
+    pops = []
+    for _ in range(2):
+        np.random.seed(4)
+        pop = _population(d, _nets(d, M4, 800, dev), dev, demos_test=demos_test)
+        pop.train(1, 0.9)
+        pops.append(pop)
+    pop, other = pops
+    got = pop.test_reward_network()
+    assert got.shape == (K, 3)
+    for k in range(K):
+        ref = other.learner(k).test_reward_network()
+        assert np.array_equal(got[k], np.asarray(ref, dtype=np.float64), equal_nan=True), (k, got[k], ref)
+    assert bool(np.isnan(got[:, 1]).all()) == (not with_test)
+    assert not np.isnan(got[:, [0, 2]]).any()
+    assert np.array_equal(pop._calls_k, other._calls_k + (3 if with_test else 2))
+
+
+# ------------------------------------------------------------------ 7. gridsearch
+def test_gridsearch_equals_ac_irl_runs(dev, tmp_path):
+    from discrete_mean_field_game_amd import irl_population as ip
+    from discrete_mean_field_game_amd.ac_irl import AC_IRL
+    from discrete_mean_field_game_amd.networks import RewardNet
+    d, B, seed, net_seed = 15, 32, 40, 7
+    demos, demos_test = _demos(d, 6), _demos(d, 2, seed=9)
+    kw = dict(num_iterations=1, num_gen_from_policy=2, max_reward_iterations=10, max_forward_episodes=2, final_training=False)
+    out = tmp_path / 'sub' / 'grid.csv'
+    np.random.seed(6)
+    rows, pop = ip.gridsearch(('dropout', 'l1l2'), (4, 6), (4,), demonstrations=demos, demonstrations_test=demos_test, d=d,
+                              batch=B, seed=seed, net_seed=net_seed, outfile=str(out), outerloop_kwargs=kw, pi0=_table(d),
+                              device=dev, return_population=True)
+    lines = out.read_text().splitlines(keepends=True)
+    assert lines[0] == 'reg,n_fc3,n_fc4,reward_demo_avg_train,reward_demo_avg_test,reward_gen_avg,theta\n'
+    points = [('dropout', 4, 4), ('dropout', 6, 4), ('l1l2', 4, 4), ('l1l2', 6, 4)]
+    assert [r[:3] for r in rows] == points and len(lines) == 5
+    from discrete_mean_field_game_amd import ops
+    rs = np.random.RandomState(6)           # the population drew its critic weights first, learner by learner
+    w0 = [rs.rand(ops.num_features(d), 1).reshape(-1) for _ in points]
+    for p, (reg, n3, n4) in enumerate(points):
+        with torch.random.fork_rng(devices=[]):
+            torch.manual_seed(net_seed + p)
+            net = RewardNet(d, reg, n_fc3=n3, n_fc4=n4)
+        with torch.random.fork_rng(devices=[]):
+            ac = AC_IRL(6.5, 0.0, 1e4, d, lr_reward=1e-4, num_policies=10, reg=reg, n_fc3=n3, n_fc4=n4, pi0=_table(d),
+                        demonstrations=[], batch=B, seed=seed + p, update_every='step', precision='mixed', device=dev, verbose=0)
+        ac.reward_net = net.to(dev)
+        ac.create_training_method()
+        ac.w = w0[p]
+        ac.list_demonstrations = [[(np.asarray(s, np.float32).astype(np.float64), np.asarray(a, np.float32).astype(np.float64))
+                                   for s, a in tr] for tr in demos]
+        ac.list_demonstrations_test = [[(np.asarray(s, np.float32).astype(np.float64), np.asarray(a, np.float32).astype(np.float64))
+                                        for s, a in tr] for tr in demos_test]
+        random.seed(seed + p)
+        final_theta = ac.outerloop(**kw)
+        tr_avg, te_avg, gen_avg = ac.test_reward_network()
+        line = '%s,%d,%d,%f,%f,%f,%f\n' % (reg, n3, n4, tr_avg, te_avg, gen_avg, float(np.ravel(final_theta)[0]))
+        assert lines[1 + p] == line, p
+        assert rows[p][3:] == (tr_avg, te_avg, gen_avg, float(np.ravel(final_theta)[0])), p
+    # a second sweep appends to the file without a second header
+    ip.gridsearch(('none',), (4,), (4,), demonstrations=demos, d=d, batch=B, outfile=str(out), outerloop_kwargs=kw, pi0=_table(d),
+                  device=dev)
+    again = out.read_text().splitlines()
+    assert len(again) == 6 and again[5].startswith('none,4,4,') and ',nan,' in again[5]
+
+
+# ------------------------------------------------------------------ 8. refusals
+def test_refusals_before_any_launch(dev):
+    from discrete_mean_field_game_amd import _lib as L
+    from discrete_mean_field_game_amd import ops
+    from discrete_mean_field_game_amd.networks import RewardNet
+    d, K = 15, 4
+    nets = _nets(d, M4, 900, dev)
+    with pytest.raises(ValueError):
+        _population(d, nets, dev, mixed=False)                      # a list mixed by mistake
+    for bad in (RewardNet(d, n_fc3=17), RewardNet(d, n_fc4=33), RewardNet(d, k1=3)):
+        with pytest.raises(ValueError):
+            _population(d, nets[:3] + [bad.to(dev)], dev)
+    from discrete_mean_field_game_amd.irl_population import AC_IRLPopulation
+    with pytest.raises(ValueError):
+        AC_IRLPopulation(np.linspace(8, 9, K), 0.1, 1e4, d, batch=32, reward_nets=nets[0], pi0=_table(d), mixed_nets=True)
+    # C level
+    flat, _, geom, stride = _flat_rows(nets, dev)
+    before = flat.clone()
+    g = torch.Generator(device='cpu').manual_seed(1)
+    N = 8
+    st = torch.rand(K, N, d, generator=g).to(dev)
+    ac = torch.rand(K, N, d, d, generator=g).to(dev)
+    out = torch.full((K, N), -9.0, device=dev)
+    m, v = torch.zeros_like(flat), torch.zeros_like(flat)
+    stats = torch.full((K, 4), 7.0, device=dev)
+    ds = torch.rand(6, T, d, generator=g).to(dev)
+    da = torch.rand(6, T, d, d, generator=g).to(dev)
+    gs = torch.rand(K, 6, T, d, generator=g).to(dev)
+    ga = torch.rand(K, 6, T, d, d, generator=g).to(dev)
+    plan = ops.rn_train_plan(1)
+    plan[0]['learner'], plan[0]['lr'], plan[0]['adam_step'] = 2, 1e-3, 1
+    plan[0]['demo_rows'][:5] = plan[0]['gen_rows'][:5] = [0, 1, 2, 3, 4]
+
+    def forward(geom_, stride_):
+        ops.reward_net_forward_pop(_row_struct(flat), True, K, st, ac, [0, 2], [1, 2], out=out, net_stride=stride_, geom=geom_)
+
+    def steps(geom_, stride_):
+        bufs = (flat, m, v) if stride_ == stride else tuple(t[:, :stride_].contiguous() for t in (flat, m, v))
+        ops.reward_net_train_steps_pop(*bufs, stride_, K, (d, 5, 2, 3, 16, 32), (ds, da), (gs, ga), plan, 1, 1, 5, 5, T, 5, 1.0,
+                                       False, stats, torch.empty(1 << 22, dtype=torch.uint8, device=dev),
+                                       torch.empty(plan.nbytes, dtype=torch.uint8, device=dev), geom=geom_)
+
+    def table(k, **kw):
+        host = geom[0].copy()
+        for f, val in kw.items():
+            host[k][f] = val
+        return host, torch.from_numpy(host.view(np.uint8).copy()).to(dev)
+
+    short = stride - 64                     # below the largest NP_k (its row is rounded up by less than 64 floats)
+    cases = [(table(1, n3=17), stride, EUNSUPPORTED), (table(3, n4=33), stride, EUNSUPPORTED), (table(0, n3=0), stride, EUNSUPPORTED),
+             (table(2, keep_prob=0.0), stride, EINVAL), (geom, short, EINVAL)]
+    for call in (forward, steps):
+        for geom_, stride_, code in cases:
+            with pytest.raises(L.MfgError) as e:
+                call(geom_, stride_)
+            assert e.value.code == code, (call.__name__, code)
+    # geom_dev null with geom_host given
+    host_ptr = geom[0].ctypes.data
+    scratch = torch.empty(16, dtype=torch.float64, device=dev)
+    lr = np.array([0, 2], dtype=np.int32)
+    ky = np.array([1, 2], dtype=np.uint64)
+    rc = L.lib().mfg_reward_net_forward_pop_nets(st.data_ptr(), ac.data_ptr(), N * d, N * d * d, N, d, C.byref(_row_struct(flat)), 1,
+                                                 stride, host_ptr, None, K, lr.ctypes.data, ky.ctypes.data, 2, 0, out.data_ptr(),
+                                                 scratch.data_ptr(), 128, None)
+    assert rc == EINVAL
+    rc = L.lib().mfg_reward_net_train_steps_pop_nets(
+        flat.data_ptr(), m.data_ptr(), v.data_ptr(), stride, K, d, 5, 2, 3, host_ptr, None, ds.data_ptr(), da.data_ptr(), 6,
+        gs.data_ptr(), ga.data_ptr(), 6, plan.ctypes.data, scratch.data_ptr(), 0, 1, 1, 5, 5, T, 5, 0.9, 0.999, 1e-8,
+        stats.data_ptr(), scratch.data_ptr(), 128, None)
+    assert rc == EINVAL
+    # the training flows refuse the same table before their first launch
+    pop = _population(d, nets, dev)
+    theta, w = pop._theta.clone(), pop._w.clone()
+    good = pop._geom
+    for bad, code in ((table(1, n3=17), EUNSUPPORTED), (table(2, keep_prob=0.0), EINVAL)):
+        pop._geom = bad
+        with pytest.raises(L.MfgError) as e:
+            pop.train(1, 0.9)
+        assert e.value.code == code
+    pop._geom = good
+    torch.cuda.synchronize()
+    assert torch.equal(pop._theta, theta) and torch.equal(pop._w, w)
+    assert torch.equal(flat, before) and not m.any() and not v.any()
+    assert torch.equal(out, torch.full((K, N), -9.0, device=dev)) and torch.equal(stats, torch.full((K, 4), 7.0, device=dev))
