@@ -85,8 +85,9 @@ def l1_l2(params):
 
 
 def irl_loss(r_demo, r_gen, n_demo, n_traj, reg=0.0, steps=15):
+    """n_traj == 0 (no generated trajectories): the second term is 0, as the kernel reports it; an empty r_demo gives first = 0."""
     first = -1.0 / n_demo * np.sum(r_demo)
-    second = np.log(1.0 / n_traj * np.sum(np.exp(np.reshape(r_gen, (n_traj, steps)).sum(1))))
+    second = np.log(1.0 / n_traj * np.sum(np.exp(np.reshape(r_gen, (n_traj, steps)).sum(1)))) if n_traj else 0.0
     return first + second + reg, first, second
 
 
@@ -177,24 +178,143 @@ def backward(params, cache, dr):
 
 
 def irl_loss_and_grad(params, demo_state, demo_action, gen_state, gen_action, n_demo_div, n_traj, l1l2=False, steps=15,
-                      masks=None):
+                      masks=None, dr=None):
     """Loss of ac_irl.py:390-413 and its gradient for one update_reward batch.  masks: (m3, m4) over the concatenated batch
-    (demonstrations first) or None.  Returns ((loss, first, second, reg), grads dict, rewards [N,1])."""
+    (demonstrations first) or None.  Either half may be empty (arrays of shape [0, d] / [0, d, d]; n_traj == 0: second term 0,
+    no generated coefficients).  dr [N,1]: coefficients dL/dr_n computed elsewhere (coefficients_from_rewards) that replace the
+    ones derived from this function's own rewards in the backward pass; the loss terms stay this function's own.
+    Returns ((loss, first, second, reg), grads dict, rewards [N,1])."""
     nd = demo_state.shape[0]
     state = np.concatenate([demo_state, gen_state], 0)
     action = np.concatenate([demo_action, gen_action], 0)
     r, cache = forward_cache(params, state, action, masks)
     reg = l1_l2(params) if l1l2 else 0.0
     loss, first, second = irl_loss(r[:nd], r[nd:], n_demo_div, n_traj, reg, steps)
-    S = r[nd:].reshape(n_traj, steps).sum(1)
-    soft = np.exp(S - S.max())
-    soft = soft / soft.sum()
-    dr = np.concatenate([np.full((nd, 1), -1.0 / n_demo_div), np.repeat(soft, steps)[:, None]], 0)
-    g = backward(params, cache, dr)
+    if dr is None:
+        dr = _coefficients(r, nd, n_traj, steps, -1.0 / n_demo_div)
+    g = backward(params, cache, np.asarray(dr, dtype=np.float64).reshape(-1, 1))
     if l1l2:
         for k in ('fc3_w', 'fc4_w'):
             g[k] = g[k] + np.sign(params[k]) + params[k]
     return (loss, first, second, reg), g, r
+
+
+def _coefficients(r, nd, n_traj, steps, demo_coefficient):
+    """dL/dr_n [N,1] from fp64 rewards r [N,1]: demo_coefficient for the nd demonstration transitions, the soft-max over the
+    generated trajectories' reward sums for theirs."""
+    if n_traj == 0:
+        return np.full((nd, 1), demo_coefficient)
+    S = r[nd:].reshape(n_traj, steps).sum(1)
+    soft = np.exp(S - S.max())
+    soft = soft / soft.sum()
+    return np.concatenate([np.full((nd, 1), demo_coefficient), np.repeat(soft, steps)[:, None]], 0)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# The coefficient phase of the combine kernel (csrc/mfg_reward_train.hip, rn_train_combine_body), restated from the fp32
+# rewards that launch 1 left in the workspace.  Everything the kernel does between those rewards and the coefficients c_n is
+# a handful of fp32 operations; the budgets below are first order in
+#     U = 2^-24, the unit roundoff of fp32: one correctly rounded +, -, *, / loses at most U of its result
+#     (the library is built without fast-math: fp32 division is correctly rounded; additions are not reassociated);
+#     expf, logf: 1 ulp = 2 U of the result (HIP math API, "maximum ULP error" of expf / logf on the device).
+#
+# S_j.  `for t: sacc += s_cn[(nd + j) T + t]`: an fp32 running sum in step order, one add per step, nothing to fuse.  NumPy
+#   float32 additions are the same IEEE operation: S32 below IS the kernel's S_j, bit for bit, given the kernel's rewards.
+#
+# c_j = e_j / z, e_j = expf(S_j - mx), mx = max_j S_j (fmaxf / shuffles: exact), z = DPP sum of the 64 lanes' e_j.
+#   d_j = fl(S_j - mx)              |d_j - (S_j - mx)| <= U |S_j - mx|;   exp turns it into a RELATIVE error |S_j - mx| U
+#   e_j = expf(d_j)                 2 U
+#   z   = 6 tree levels of adds     non-negative terms (lanes >= ng add an exact 0): 6 U of z, besides the e_j's own errors,
+#                                   which z inherits as a weighted mean  sum_j c_j (|S_j - mx| + 2) U  <=  max_j of it
+#   e_j / z                         U
+#   With e_i (1 + delta_i), |delta_i| <= (|S_i - mx| + 2) U, the tree returns z (1 + sum_i c_i delta_i + 6 U): z inherits the
+#   e_i's errors as their c-weighted mean, at most (zbar + 2) U with zbar = sum_i c_i |S_i - mx| (small: the weight sits where
+#   |S_i - mx| ~ 0).  Together
+#       eps_j = (|S_j - mx| + 2  +  zbar + 2 + 6  +  1  +  1) U = (|S_j - mx| + zbar + C0) U,   C0 = 12,
+#   the last 1 covering every second-order term ((|d| + 11)^2 U^2 < U while |d| < 4000).  The bound is claimed while e_j is
+#   a normal fp32 number, S_j - mx > -87; below that expf flushes and eps_j is reported as inf (such a trajectory adds at
+#   most e^-87 to z's relative error, nothing next to U).
+#
+# second = mx + logf(z / ng):   z / ng carries z's relative error (zbar + 2 + 6) U and the division's U; logf turns a relative
+#   error of its argument into an absolute one and adds 2 U |log(z / ng)| of its own; the final addition rounds once:
+#   second_bound = (zbar + 2 + 6 + 1 + 2 |ln(z / ng)| + 1) U + U |second|.          (ng = 0: second = 0 exactly, bound 0)
+#
+# first = -fl(1 / divisor) * sd:   sd is the demonstration rewards summed by one wave: lane l adds n = l, l + 64, ... in
+#   order (k = ceil(nd T / 64) terms, k - 1 additions), then the 6-level tree; every addition loses at most U of a partial sum
+#   that is at most sum |r_demo|: (k - 1 + 6) U sum |r_demo|.  fl(1 / divisor) and the product round once each:
+#   first_bound = (k + 5 + 2 + 1) U sum |r_demo| / divisor                           (nd = 0: first = -0 exactly, bound 0)
+#
+# loss = fl(fl(first + second) + reg): two more roundings, U |first + second| + U |loss|, on top of the terms' own bounds.
+# ---------------------------------------------------------------------------------------------------------------------
+U32 = 2.0 ** -24
+C0_SOFTMAX = 12.0
+EXPF_NORMAL_MIN = -87.0
+
+
+def coefficients_from_rewards(r, n_demo, n_gen, steps, demo_divisor):
+    """The combine kernel's coefficient phase on fp32 rewards r [N] (N = (n_demo + n_gen) steps, demonstrations first).
+    Returns a dict:
+      S32 [n_gen] float32   the per-trajectory sums exactly as the kernel forms them (fp32 running sum in step order)
+      c [N,1] float64       dL/dr_n: -1/demo_divisor (demonstrations), soft-max of S32 (generated); c_traj [n_demo + n_gen]
+      first, second         the loss terms in fp64 from the same inputs
+      eps [n_gen]           relative bound on the kernel's fp32 soft-max weight (derivation above); inf where expf flushes
+      first_bound, second_bound   absolute bounds on the kernel's stats[1], stats[2];  loss_rounding(reg): the two final adds"""
+    r32 = np.asarray(r, dtype=np.float32).reshape(-1)
+    nd_t = n_demo * steps
+    if r32.size != (n_demo + n_gen) * steps:
+        raise ValueError('coefficients_from_rewards: %d rewards for (%d + %d) x %d' % (r32.size, n_demo, n_gen, steps))
+    S32 = np.zeros(n_gen, dtype=np.float32)
+    rg = r32[nd_t:].reshape(n_gen, steps)
+    for t in range(steps):
+        S32 = (S32 + rg[:, t]).astype(np.float32)         # one fp32 add per step
+    r_demo = r32[:nd_t].astype(np.float64)
+    sum_abs = float(np.abs(r_demo).sum())
+    first = -1.0 / demo_divisor * float(r_demo.sum())
+    k = -(-nd_t // 64)
+    first_bound = (k + 8) * U32 * sum_abs / demo_divisor if n_demo else 0.0
+    if n_gen:
+        S = S32.astype(np.float64)
+        dj = S - S.max()
+        e = np.exp(dj)
+        z = e.sum()
+        soft = e / z
+        zbar = float((soft * np.abs(dj)).sum())
+        eps = np.where(dj > EXPF_NORMAL_MIN, (np.abs(dj) + zbar + C0_SOFTMAX) * U32, np.inf)
+        second = float(S.max() + np.log(z / n_gen))
+        second_bound = (zbar + 10.0 + 2.0 * abs(np.log(z / n_gen))) * U32 + U32 * abs(second)
+    else:
+        soft, eps, second, second_bound = np.zeros(0), np.zeros(0), 0.0, 0.0
+    c_traj = np.concatenate([np.full(n_demo, -1.0 / demo_divisor), soft])
+    return dict(S32=S32, c=np.repeat(c_traj, steps)[:, None], c_traj=c_traj, first=first, second=second, eps=eps,
+                first_bound=first_bound, second_bound=second_bound,
+                loss_rounding=lambda reg: U32 * (abs(first + second) + abs(first + second + reg)))
+
+
+def grad_scale(prm, ds, da, gs, ga, n_div, n_traj, masks, l1l2, steps=None, coeff=None, gen_only=False, cache=None):
+    """Per-parameter magnitude of the terms the batch gradient sums: the gradient with |dL/dr_n| as sample weights.  The
+    demonstration (-) and generated (+) halves cancel to a small net value (e.g. out_b: 15 - 15 -> 0.03), and an fp32
+    result can only be accurate relative to what was summed; the GPU tests' tolerances are 1e-5 of max(|net|, this scale).
+    steps: transitions per trajectory (default: the generated half split evenly over n_traj); coeff [N] / [N,1]: given
+    coefficients dL/dr_n instead of the ones derived from the oracle's own rewards; gen_only: the generated half alone (the
+    demonstrations get weight 0); cache: forward_cache of this batch, if the caller has it.  Flat kernel order."""
+    nd = ds.shape[0]
+    if cache is None:
+        state, action = np.concatenate([ds, gs], 0), np.concatenate([da, ga], 0)
+        _, cache = forward_cache(prm, state, action, masks)
+    r = cache['r']
+    if coeff is not None:
+        dr = np.abs(np.asarray(coeff, dtype=np.float64).reshape(-1, 1))
+    elif n_traj:
+        S = r[nd:].reshape(n_traj, -1 if steps is None else steps).sum(1)
+        soft = np.exp(S - S.max()); soft /= soft.sum()
+        dr = np.concatenate([np.full((nd, 1), 1.0 / n_div), np.repeat(soft, r[nd:].shape[0] // n_traj)[:, None]], 0)
+    else:
+        dr = np.full((nd, 1), 1.0 / n_div)
+    if gen_only:
+        dr = dr.copy()
+        dr[:nd] = 0.0
+    g = backward(prm, dict(cache), dr)
+    return np.abs(flatten_like_kernel(g))
 
 
 def adam_tf(p, g, m, v, step, lr=1e-4, beta1=0.9, beta2=0.999, eps=1e-8):

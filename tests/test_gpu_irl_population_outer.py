@@ -55,7 +55,7 @@ def _population(d, K, nets, dev, mode='step', B=32, seeds=None, lr_reward=1e-3, 
                             num_policies=num_policies, host_seeds=host_seeds)
 
 
-def _stores(d, K, rows, dev, seed=1):
+def _stores(d, K, rows, dev, seed=1, T=T):
     g = torch.Generator(device='cpu').manual_seed(seed)
     ds = torch.rand(rows, T, d, generator=g)
     da = torch.rand(rows, T, d, d, generator=g)
@@ -81,9 +81,19 @@ def _compare(a, b, path=''):
 
 
 # ------------------------------------------------------------------ 1. the training steps
-@pytest.mark.parametrize('reg,d,n3,K,U', [('none', 15, 8, 1, 1), ('dropout_l1l2', 21, 16, 3, 10), ('dropout_l1l2', 15, 16, 16, 10),
-                                          ('none', 21, 8, 16, 1), ('dropout_l1l2', 21, 8, 3, 1)])
-def test_train_steps_pop_equals_single_steps(dev, reg, d, n3, K, U):
+# batch = (n_demo, n_gen, steps): the last two leave the reference's 5 + 5 x 15 -- N = 153 is the first batch into the combine
+# kernel's second round of column reads, with steps != 15; 3 + 40 x 4 has a different count in each half, more than 32 generated
+# trajectories (the soft-max crosses lane 32) and N n3 = 2752 entries of c_n dz3_n, past the 2048 staged in registers
+@pytest.mark.parametrize('reg,d,n3,K,U,batch', [
+    pytest.param('none', 15, 8, 1, 1, (5, 5, 15), id='none-15-8-1-1'),
+    pytest.param('dropout_l1l2', 21, 16, 3, 10, (5, 5, 15), id='dropout_l1l2-21-16-3-10'),
+    pytest.param('dropout_l1l2', 15, 16, 16, 10, (5, 5, 15), id='dropout_l1l2-15-16-16-10'),
+    pytest.param('none', 21, 8, 16, 1, (5, 5, 15), id='none-21-8-16-1'),
+    pytest.param('dropout_l1l2', 21, 8, 3, 1, (5, 5, 15), id='dropout_l1l2-21-8-3-1'),
+    pytest.param('none', 15, 8, 3, 2, (9, 8, 9), id='none-15-8-3-2-9x8x9'),
+    pytest.param('dropout_l1l2', 15, 16, 3, 2, (3, 40, 4), id='dropout_l1l2-15-16-3-2-3x40x4')])
+def test_train_steps_pop_equals_single_steps(dev, reg, d, n3, K, U, batch):
+    nd, ng, T = batch
     from discrete_mean_field_game_amd import ops
     from discrete_mean_field_game_amd.reward_learning import RewardTrainer
     nets = _nets(d, n3, reg, K, 40, dev)
@@ -101,8 +111,8 @@ def test_train_steps_pop_equals_single_steps(dev, reg, d, n3, K, U):
         flat[k, :np_] = tr.flat
         m[k, :np_] = tr.m
         v[k, :np_] = tr.v
-    rows = 9
-    ds, da, gs, ga = _stores(d, K, rows, dev)
+    rows = max(9, nd, ng)
+    ds, da, gs, ga = _stores(d, K, rows, dev, T=T)
     demo = types.SimpleNamespace(state=ds, action=da, steps=T)
     rs = random.Random(7)
     plan = ops.rn_train_plan(U * K)
@@ -114,18 +124,18 @@ def test_train_steps_pop_equals_single_steps(dev, reg, d, n3, K, U):
             e['key'] = rs.getrandbits(64)
             e['lr'] = trainers[k].lr
             e['adam_step'] = trainers[k].step_count + 1 + u
-            e['demo_rows'][:5] = rs.sample(range(rows), 5)
-            e['gen_rows'][:5] = rs.sample(range(rows + 2), 5)
+            e['demo_rows'][:nd] = rs.sample(range(rows), nd)
+            e['gen_rows'][:ng] = rs.sample(range(rows + 2), ng)
     stats = torch.zeros(K, 4, device=dev)
     ws = torch.empty(K * 1 << 20, dtype=torch.uint8, device=dev)
     plan_dev = torch.empty(plan.nbytes, dtype=torch.uint8, device=dev)
-    ops.reward_net_train_steps_pop(flat, m, v, ld, K, trainers[0].dims, (ds, da), (gs, ga), plan, U, K, 5, 5, T, 5, keep,
+    ops.reward_net_train_steps_pop(flat, m, v, ld, K, trainers[0].dims, (ds, da), (gs, ga), plan, U, K, nd, ng, T, 5, keep,
                                    nets[0].use_l1l2, stats, ws, plan_dev)
     for k, tr in enumerate(trainers):
         gen = types.SimpleNamespace(state=gs[k], action=ga[k], steps=T)
         for u in range(U):
             e = plan[u * K + k]
-            tr.step(demo, [int(r) for r in e['demo_rows'][:5]], gen, [int(r) for r in e['gen_rows'][:5]], 5, int(e['key']))
+            tr.step(demo, [int(r) for r in e['demo_rows'][:nd]], gen, [int(r) for r in e['gen_rows'][:ng]], 5, int(e['key']))
         assert torch.equal(flat[k, :np_], tr.flat), k
         assert torch.equal(m[k, :np_], tr.m) and torch.equal(v[k, :np_], tr.v), k
         assert torch.equal(stats[k], tr.stats), k

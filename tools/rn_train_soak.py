@@ -2,7 +2,7 @@
 tf.train.AdamOptimizer formula of oracle/reward_net_oracle.py (developer tool; uses oracle/ as the checker only).
 Random geometry (d, conv sizes, filters, n_fc3, n_fc4), batch composition (1 .. 12 trajectories per half, permuted store rows),
 regulariser variant and dropout key; three consecutive updates per configuration.  Reports, per kernel template, the largest
-gradient deviation relative to the magnitude of what was summed (see tests/test_gpu_reward_train.py::_grad_scale) and the largest
+gradient deviation relative to the magnitude of what was summed (see oracle/reward_net_oracle.py::grad_scale) and the largest
 parameter deviation after the Adam steps in units of the learning rate.   usage: rn_train_soak.py [seconds]"""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
