@@ -19,6 +19,7 @@ ROLLOUT_WRITE_P, ROLLOUT_TD, ROLLOUT_DISCOUNT_POW, ROLLOUT_F64, TRAIN_APPLY = 1,
 PRECISION_F64, PRECISION_MIXED = 0, 1
 POP_MAX_K = 65535                # MFG_POP_MAX_K: learners of one population call
 STATUS_MIXED_RANGE = 1
+STATUS_POP_NONFINITE = 2        # MFG_STATUS_POP_NONFINITE: per-learner words of a population control block only
 ECOMM = -6                      # MFG_ECOMM: the call aborted its RCCL communicator, the handle is dead
 RN_TRAIN_MAX_TRAJ = 64          # MFG_RN_TRAIN_MAX_TRAJ
 PRECISIONS = {'f64': PRECISION_F64, 'mixed': PRECISION_MIXED, 0: 0, 1: 1}
@@ -175,6 +176,15 @@ SIGNATURES['mfg_reward_net_forward_pop_nets'] = (_i32, SIGNATURES['mfg_reward_ne
                                                  + SIGNATURES['mfg_reward_net_forward_pop'][1][9:])
 _steps = SIGNATURES['mfg_reward_net_train_steps_pop'][1]
 SIGNATURES['mfg_reward_net_train_steps_pop_nets'] = (_i32, _steps[:9] + [_p, _p] + _steps[11:26] + _steps[28:])
+
+
+class PopControlStruct(C.Structure):
+    """mfg_pop_control_t of include/mfg_hip.h: the per-learner activity states of a population (device arrays [K])."""
+    _fields_ = [('state', C.c_void_p), ('status', C.c_void_p), ('theta_prev', C.c_void_p), ('episodes_run', C.c_void_p),
+                ('stop_criteria', C.c_void_p), ('K', C.c_int32)]
+
+
+SIGNATURES['mfg_ctx_set_pop_control'] = (_i32, [_p, C.POINTER(PopControlStruct)])
 
 SIGNATURES['mfg_evaluate_pop_workspace_bytes'] = (_sz, [_i64, _i32, _i32, _i32, _i32, _i32])
 SIGNATURES['mfg_evaluate_pop'] = (_i32, [_p, _p, _i64, _i32, _i32, _i32, _p, _p, _p, _p, _u32, _i32, _i32, _p, _p, _p, _sz, _p])

@@ -30,6 +30,8 @@ struct RnPop {
   const int32_t* learner;                        // [n_y] device (NULL: slot = learner)
   int n_y;
   const mfg_rn_geom_t* geom;                     // [K] device (NULL: the launch's n3 / n4 / keep_prob for every learner)
+  const int32_t* state;                          // [K] device, training flows with a control block (mfg_population.h): the
+                                                 // blocks of a learner whose state is not 0 return at once (NULL: all run)
 };
 
 // Per-learner geometry (the *_nets entry points, include/mfg_hip.h): learner k's entry is read by its blocks -- block-uniform,

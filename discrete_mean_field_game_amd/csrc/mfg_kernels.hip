@@ -1831,6 +1831,8 @@ struct mfg_ctx {
   int device = -1;
   StatusWord sw;
   void* comm = nullptr;  // adopted RCCL communicator (mfg_ctx_adopt_comm), destroyed with the context
+  bool has_ctl = false;  // population control block (mfg_ctx_set_pop_control): the population training calls carry it
+  mfg_pop_control_t ctl{};
 };
 // The binding is per THREAD, the object's lifetime is not: a context may be destroyed by another thread than the one(s) it is
 // bound on (a garbage collector drops the last reference wherever it runs).  Every live context is therefore registered with
@@ -2092,6 +2094,24 @@ int mfg_ctx_adopt_comm(mfg_ctx_t* ctx, void* comm) {
 }
 
 void* mfg_ctx_comm(mfg_ctx_t* ctx) { return (ctx && ctx_is_live(ctx)) ? ctx->comm : nullptr; }
+
+static bool pop_control_complete(const mfg_pop_control_t& c) {
+  return c.state && c.status && c.theta_prev && c.episodes_run && c.stop_criteria;
+}
+
+int mfg_ctx_set_pop_control(mfg_ctx_t* ctx, const mfg_pop_control_t* block) {
+  REQUIRE(ctx && ctx_is_live(ctx), "null or destroyed context");
+  if (!block) {
+    ctx->has_ctl = false;
+    ctx->ctl = mfg_pop_control_t{};
+    return MFG_OK;
+  }
+  REQUIRE(pop_control_complete(*block), "population control block: null pointer");
+  REQUIRE(block->K >= 1 && block->K <= MFG_POP_MAX_K, "population control block: K outside [1, MFG_POP_MAX_K]");
+  ctx->ctl = *block;
+  ctx->has_ctl = true;
+  return MFG_OK;
+}
 
 int mfg_device_info(int* cu_count_host, char* arch_host, int arch_len) {
   int dev = 0;
@@ -3079,6 +3099,34 @@ static size_t pop_workspace_need(int d, int64_t N, bool sums_rows) {
             true);                                                                                                      \
   REQUIRE(reward_kind == MFG_REWARD_MFG_AC2 || reward_kind == MFG_REWARD_SYNTHETIC, "needs an in-kernel reward")
 
+// The control block a population training call runs under -- that of the bound context, none without one -- and the arrays
+// k_pop_retire reads.  begin() checks the block before anything is launched, hands the learners' states to the launches (p.state,
+// p.status) and enqueues the check ahead of the first episode (also when the call has no episode); retire() enqueues the step
+// after an episode's closing update.  Without a block neither launches anything and p stays as it was.
+struct PopControl {
+  const mfg_pop_control_t* ctl = nullptr;
+  const double *theta = nullptr, *w = nullptr, *shift = nullptr;
+  int64_t F = 0;
+  bool mixed = false;
+  hipStream_t st = nullptr;
+
+  int begin(PopArgs& p, const double* theta_, const double* w_, const double* shift_, bool mixed_, hipStream_t st_) {
+    const mfg_ctx* c = bound_ctx();
+    if (!c || !c->has_ctl) return MFG_OK;
+    REQUIRE(pop_control_complete(c->ctl), "population control block: null pointer");
+    REQUIRE(c->ctl.K == p.K, "population control block: set for another population size K");
+    ctl = &c->ctl;
+    theta = theta_, w = w_, shift = shift_, F = p.F, mixed = mixed_, st = st_;
+    p.state = ctl->state;
+    p.status = ctl->status;
+    launch_pop_retire(*ctl, theta, w, F, shift, mixed, false, st);
+    return MFG_OK;
+  }
+  void retire() const {
+    if (ctl) launch_pop_retire(*ctl, theta, w, F, shift, mixed, true, st);
+  }
+};
+
 // the argument block of a population call (the call sets the strides that depend on its flow: s_pi0, s_gpi, s_n, s_P)
 static PopArgs pop_args(int K, int64_t B, int d, int64_t T, int64_t episodes, const uint64_t* seed, const double* shift,
                         const double* alpha_scale, const double* lr_critic, const double* lr_actor, size_t workspace_bytes) {
@@ -3115,6 +3163,8 @@ int mfg_train_episodes_pop(const float* mat_pi0, int64_t num_start, float* pi_io
   PopArgs p = pop_args(K, B, d, 1, episodes, seed, shift, alpha_scale, lr_critic, lr_actor, workspace_bytes);
   p.s_pi0 = p.s_gpi = B * d;  // (the env step reads and the batch sums read the learner's current states)
   p.s_n = B;
+  PopControl pc;
+  if (const int rc = pc.begin(p, theta, w, shift, precision == MFG_PRECISION_MIXED, S(stream)); rc != MFG_OK) return rc;
   for (int64_t k = 0; k < episodes; ++k) {
     const uint32_t step0 = first_step + (uint32_t)(k * T);
     launch_draw_start_pop(grid_for(B * d, 256, 8), mat_pi0, num_start, B, d, step0, traj_offset, pi_io, p, S(stream));
@@ -3123,6 +3173,7 @@ int mfg_train_episodes_pop(const float* mat_pi0, int64_t num_start, float* pi_io
                                       precision, 0.0, 0.0, reward, delta, g, G, reward_acc ? reward_acc + k : nullptr, workspace,
                                       workspace_bytes, S(stream), &p);
     if (rc != MFG_OK) return rc;
+    pc.retire();
   }
   return MFG_OK;
 }
@@ -3143,6 +3194,8 @@ int mfg_train_rollouts_pop(const float* mat_pi0, int64_t num_start, int64_t B, i
   p.s_pi0 = 0;  // (the shared start-state table: the rows are drawn in the kernel)
   p.s_gpi = p.s_traj;
   p.s_n = B * T;
+  PopControl pc;
+  if (const int rc = pc.begin(p, theta, w, shift, !(flags & MFG_ROLLOUT_F64), S(stream)); rc != MFG_OK) return rc;
   for (int64_t k = 0; k < episodes; ++k) {
     lr_schedule(first_episode + k, constant, &p.sc, &p.sa);
     const int rc = train_rollout_impl(mat_pi0, num_start, nullptr, B, d, T, theta, 0.0, 0.0, w, gamma, reward_kind, 0,
@@ -3150,6 +3203,7 @@ int mfg_train_rollouts_pop(const float* mat_pi0, int64_t num_start, int64_t B, i
                                       pi_last, reward, delta, g, G, reward_acc ? reward_acc + k : nullptr, workspace,
                                       workspace_bytes, S(stream), nullptr, &p);
     if (rc != MFG_OK) return rc;
+    pc.retire();
   }
   return MFG_OK;
 }
@@ -3508,6 +3562,9 @@ static int train_episodes_irl_pop(const float* mat_pi0, int64_t num_start, float
   rp.s_action = B * d * d;
   rp.s_n = B;
   rp.s_w = p.F;
+  PopControl pc;
+  if (const int rc = pc.begin(p, theta, w, shift, precision == MFG_PRECISION_MIXED, S(stream)); rc != MFG_OK) return rc;
+  rp.state = p.state;
   for (int64_t e = 0; e < episodes; ++e) {
     lr_schedule(first_episode + e, constant, &p.sc, &p.sa);
     const int rc = train_episode_irl_step(mat_pi0, num_start, pi_out, pi_scratch, B, d, T, theta, 0.0, 0.0, w, gamma, 0,
@@ -3515,6 +3572,7 @@ static int train_episodes_irl_pop(const float* mat_pi0, int64_t num_start, float
                                           rn_call0 + (uint64_t)(e * T), traj_offset, P, reward, delta, g, G,
                                           reward_acc ? reward_acc + e : nullptr, workspace, workspace_bytes, S(stream), &p, &rp);
     if (rc != MFG_OK) return rc;
+    pc.retire();
   }
   return MFG_OK;
 }
@@ -3544,6 +3602,9 @@ static int train_rollouts_irl_pop(const float* mat_pi0, int64_t num_start, int64
   rp.s_state = B * (T + 1) * d;
   rp.s_action = B * T * d * d;
   rp.s_n = B * T;
+  PopControl pc;
+  if (const int rc = pc.begin(p, theta, w, shift, !(flags & MFG_ROLLOUT_F64), S(stream)); rc != MFG_OK) return rc;
+  rp.state = p.state;
   const ExtReward ext{net, P, 0, traj_offset * (uint64_t)T, &rp};
   for (int64_t e = 0; e < episodes; ++e) {
     lr_schedule(first_episode + e, constant, &p.sc, &p.sa);
@@ -3554,6 +3615,7 @@ static int train_rollouts_irl_pop(const float* mat_pi0, int64_t num_start, int64
                                       pi_last, reward, delta, g, G, reward_acc ? reward_acc + e : nullptr, workspace,
                                       workspace_bytes, S(stream), nullptr, &p, &ext);
     if (rc != MFG_OK) return rc;
+    pc.retire();
   }
   return MFG_OK;
 }

@@ -6,6 +6,11 @@
 // [K]) and then runs the body of the single kernel unchanged, so the summation trees and the Philox keys (trajectory ids
 // traj_offset .. traj_offset + Bk - 1 under the learner's seed) are those of a single-learner call: the same bits.  The
 // kernels are in mfg_population.hip and mfg_evaluate_pop.hip, the episode loops in mfg_kernels.hip.
+//
+// Retiring learners (mfg_ctx_set_pop_control, include/mfg_hip.h): with a control block every training launch carries the learners'
+// activity state [K] (PopArgs::state) and runs the _ctl form of each wrapper, which returns before the single kernel's body when
+// its learner's state is not 0 -- block-uniform, ahead of every barrier -- so a learner that stopped early or diverged leaves the
+// launches at once while the others run on; a launch without a block runs the plain form, which has no such test.  k_pop_retire, one wave per learner, moves the states between two episodes; nothing is read back by the host.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -39,7 +44,13 @@ struct PopArgs {
   int64_t N;         // evaluation: test files
   int64_t s_idx;     // evaluation: int32 entries between the learners' start-index tables (padded to 256 bytes)
   int32_t* idx;      // evaluation: [K][s_idx] start-index tables (workspace)
+  const int32_t* state;  // control block: [K] 0 active, 1 stopped, 2 failed (NULL: no control block, every learner runs)
+  unsigned* status;      // control block: [K] per-learner status words (the core kernel's range report of learner k)
 };
+
+// true: learner k of a launch with a control block has been retired (the _ctl wrappers, which the launchers run exactly when
+// p.state is set, return before the body; the plain wrappers never read it)
+__device__ __forceinline__ bool pop_retired(const PopArgs& p, int k) { return p.state[k] != 0; }
 
 // p moved by k x `stride` elements / bytes; a null pointer stays null
 template <class P>
@@ -57,7 +68,8 @@ __device__ __forceinline__ P* pop_bytes(P* p, int64_t bytes, int k) {
 // Fields a variant never reads stay as they are: a rebased pointer is one more value the kernel keeps live (measured: with
 // reward_out rebased in the STEP forms too, k_core_pop<false, 21, false, 1> spilled 4 more bytes per lane; with P_out and a
 // byte-strided theta in the SUMS forms, the per-step population episodes took 1 % longer).
-template <bool SUMS, int STEP>
+// CTL: the launch carries a control block (status is set, as mfg_ctx_set_pop_control demands).
+template <bool SUMS, int STEP, bool CTL = false>
 __device__ __forceinline__ CoreArgs pop_core_args(const CoreArgs& a, const PopArgs& p, int k) {
   CoreArgs b = a;
   b.pi0 = pop_at(a.pi0, p.s_pi0, k);
@@ -67,6 +79,7 @@ __device__ __forceinline__ CoreArgs pop_core_args(const CoreArgs& a, const PopAr
   b.shift = p.shift[k];
   b.alpha_scale = p.alpha_scale[k];
   b.seed = p.seed[k];
+  if constexpr (CTL) b.status = p.status + k;  // (an out-of-range theta is booked to the learner, not to the context)
   b.pi_traj = pop_at(a.pi_traj, p.s_traj, k);
   b.pi_next_out = pop_at(a.pi_next_out, p.s_state, k);
   if constexpr (STEP == 0) b.reward_out = pop_at(a.reward_out, p.s_n, k);  // (the STEP forms take an external reward)
@@ -103,5 +116,11 @@ void launch_reduce_partials_pop(unsigned nob, const double* partial, int64_t nsb
 // the row reduction + update that closes a step-mode IRL episode: learner k's theta in at theta_in + k p.s_theta_b bytes
 void launch_reduce_rows_apply_pop(const double* rows, int nrows, int64_t FO, double* G, double count, double* w,
                                   const double* theta_in, double* theta_out, double* reward_acc, const PopArgs& p, hipStream_t st);
+
+// the step between two episodes of a call with a control block (k_pop_retire): the non-finite scan of theta and w, in mixed
+// precision the range predicate of report_sep_range and the learner's status word -> state 2; after_episode: episodes_run += 1,
+// |theta - theta_prev| < stop_criteria -> state 1, theta_prev = theta (0, before the first episode: the checks and theta_prev)
+void launch_pop_retire(const mfg_pop_control_t& c, const double* theta, const double* w, int64_t F, const double* shift, bool mixed,
+                       bool after_episode, hipStream_t st);
 
 }  // namespace mfg

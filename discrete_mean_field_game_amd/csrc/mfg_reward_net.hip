@@ -1144,58 +1144,72 @@ __global__ __launch_bounds__(RM_BLOCK) void k_reward_net_mfma(RewardNetArgs a) {
   reward_net_mfma_body<D, RUN, RPR, P1, SUMS>(a);
 }
 
-// population form (mfg_irl_population.h): learner blockIdx.y -- its weights, key, states, actions, outputs and workspace rows
+// population form (mfg_irl_population.h): learner blockIdx.y -- its weights, key, states, actions, outputs and workspace rows.
+// Two kernels, as in mfg_population.hip: k_reward_net_mfma_pop for a launch without a control block (instruction for instruction
+// what it was before control blocks existed) and k_reward_net_mfma_pop_ctl for a training launch with one (RnPop::state set),
+// which first tests its learner's state.  The rebase is a macro and not an inlined function: handing the argument blocks to a
+// function changed the plain kernel's schedule (tools/kernel_isa_diff.py).
+#define MFG_RN_POP_REBASE()                                                                                              \
+  RewardNetArgs b = a;                                                                                                   \
+  if (p.geom) { /* learner k's own n3 / n4 / keep_prob; its tensors at its own offsets (rt_layout) in its flat row */    \
+    using Gm = MfmaGeom<D, RUN, RPR, P1>;                                                                                \
+    const mfg_rn_geom_t e = rn_geom_entry(p.geom, k);                                                                    \
+    const float* row = a.c1w + p.s_net * k;                                                                              \
+    b.n3 = e.n3; b.n4 = e.n4; b.keep_prob = e.keep_prob;                                                                 \
+    b.c1w = row;                                                                                                         \
+    b.c1b = b.c1w + Gm::K1 * Gm::K1;                                                                                     \
+    b.c2w = b.c1b + 1;                                                                                                   \
+    b.c2b = b.c2w + Gm::F2 * Gm::K2 * Gm::K2;                                                                            \
+    b.w3 = b.c2b + Gm::F2;                                                                                               \
+    b.b3 = b.w3 + e.n3 * Gm::K;                                                                                          \
+    b.w4 = b.b3 + e.n3;                                                                                                  \
+    b.b4 = b.w4 + e.n4 * (e.n3 + D);                                                                                     \
+    b.wo = b.b4 + e.n4;                                                                                                  \
+    b.bo = b.wo + e.n4;                                                                                                  \
+  } else if (p.per_learner_net && p.s_net > 0) {                                                                         \
+    const int64_t o = p.s_net * k;                                                                                       \
+    b.c1w += o; b.c1b += o; b.c2w += o; b.c2b += o; b.w3 += o; b.b3 += o; b.w4 += o; b.b4 += o; b.wo += o; b.bo += o;    \
+  } else if (p.per_learner_net) {                                                                                        \
+    const int64_t n3 = a.n3, n4 = a.n4;                                                                                  \
+    b.c1w += (int64_t)MfmaGeom<D, RUN, RPR, P1>::K1 * MfmaGeom<D, RUN, RPR, P1>::K1 * k;                                 \
+    b.c1b += k;                                                                                                          \
+    b.c2w += (int64_t)MfmaGeom<D, RUN, RPR, P1>::F2 * MfmaGeom<D, RUN, RPR, P1>::K2 * MfmaGeom<D, RUN, RPR, P1>::K2 * k; \
+    b.c2b += (int64_t)MfmaGeom<D, RUN, RPR, P1>::F2 * k;                                                                 \
+    b.w3 += n3 * MfmaGeom<D, RUN, RPR, P1>::K * k;                                                                       \
+    b.b3 += n3 * k;                                                                                                      \
+    b.w4 += n4 * (n3 + D) * k;                                                                                           \
+    b.b4 += n4 * k;                                                                                                      \
+    b.wo += n4 * k;                                                                                                      \
+    b.bo += k;                                                                                                           \
+  }                                                                                                                      \
+  b.seed = p.key ? p.key[slot]                                                                                           \
+                 : p.rn_seed[k] ^ (p.call_base ? (p.call_base[k] + p.call_j) * 0x9E3779B97F4A7C15ull : p.key_ctr);       \
+  b.state += p.s_state * k;                                                                                              \
+  b.action += p.s_action * k;                                                                                            \
+  b.reward += p.s_n * k;                                                                                                 \
+  if constexpr (SUMS) {                                                                                                  \
+    b.gsc += p.s_n * k;                                                                                                  \
+    b.delta_out += p.s_n * k;                                                                                            \
+    b.td_w += p.s_w * k;                                                                                                 \
+    b.state_next += p.s_next * k;                                                                                        \
+    b.part_rows = reinterpret_cast<double*>(reinterpret_cast<char*>(a.part_rows) + p.s_ws * k);                          \
+    b.col_f = reinterpret_cast<double*>(reinterpret_cast<char*>(a.col_f) + p.s_ws * k);                                  \
+  }                                                                                                                      \
+  reward_net_mfma_body<D, RUN, RPR, P1, SUMS>(b)
 template <int D, int RUN, int RPR, int P1, bool SUMS>
 __global__ __launch_bounds__(RM_BLOCK) void k_reward_net_mfma_pop(RewardNetArgs a, RnPop p) {
   const int slot = blockIdx.y;
   const int k = p.learner ? p.learner[slot] : slot;
-  RewardNetArgs b = a;
-  if (p.geom) {  // learner k's own n3 / n4 / keep_prob; its tensors at its own offsets (rt_layout) in its flat row
-    using Gm = MfmaGeom<D, RUN, RPR, P1>;
-    const mfg_rn_geom_t e = rn_geom_entry(p.geom, k);
-    const float* row = a.c1w + p.s_net * k;
-    b.n3 = e.n3; b.n4 = e.n4; b.keep_prob = e.keep_prob;
-    b.c1w = row;
-    b.c1b = b.c1w + Gm::K1 * Gm::K1;
-    b.c2w = b.c1b + 1;
-    b.c2b = b.c2w + Gm::F2 * Gm::K2 * Gm::K2;
-    b.w3 = b.c2b + Gm::F2;
-    b.b3 = b.w3 + e.n3 * Gm::K;
-    b.w4 = b.b3 + e.n3;
-    b.b4 = b.w4 + e.n4 * (e.n3 + D);
-    b.wo = b.b4 + e.n4;
-    b.bo = b.wo + e.n4;
-  } else if (p.per_learner_net && p.s_net > 0) {
-    const int64_t o = p.s_net * k;
-    b.c1w += o; b.c1b += o; b.c2w += o; b.c2b += o; b.w3 += o; b.b3 += o; b.w4 += o; b.b4 += o; b.wo += o; b.bo += o;
-  } else if (p.per_learner_net) {
-    const int64_t n3 = a.n3, n4 = a.n4;
-    b.c1w += (int64_t)MfmaGeom<D, RUN, RPR, P1>::K1 * MfmaGeom<D, RUN, RPR, P1>::K1 * k;
-    b.c1b += k;
-    b.c2w += (int64_t)MfmaGeom<D, RUN, RPR, P1>::F2 * MfmaGeom<D, RUN, RPR, P1>::K2 * MfmaGeom<D, RUN, RPR, P1>::K2 * k;
-    b.c2b += (int64_t)MfmaGeom<D, RUN, RPR, P1>::F2 * k;
-    b.w3 += n3 * MfmaGeom<D, RUN, RPR, P1>::K * k;
-    b.b3 += n3 * k;
-    b.w4 += n4 * (n3 + D) * k;
-    b.b4 += n4 * k;
-    b.wo += n4 * k;
-    b.bo += k;
-  }
-  b.seed = p.key ? p.key[slot]
-                 : p.rn_seed[k] ^ (p.call_base ? (p.call_base[k] + p.call_j) * 0x9E3779B97F4A7C15ull : p.key_ctr);
-  b.state += p.s_state * k;
-  b.action += p.s_action * k;
-  b.reward += p.s_n * k;
-  if constexpr (SUMS) {
-    b.gsc += p.s_n * k;
-    b.delta_out += p.s_n * k;
-    b.td_w += p.s_w * k;
-    b.state_next += p.s_next * k;
-    b.part_rows = reinterpret_cast<double*>(reinterpret_cast<char*>(a.part_rows) + p.s_ws * k);
-    b.col_f = reinterpret_cast<double*>(reinterpret_cast<char*>(a.col_f) + p.s_ws * k);
-  }
-  reward_net_mfma_body<D, RUN, RPR, P1, SUMS>(b);
+  MFG_RN_POP_REBASE();
 }
+template <int D, int RUN, int RPR, int P1, bool SUMS>
+__global__ __launch_bounds__(RM_BLOCK) void k_reward_net_mfma_pop_ctl(RewardNetArgs a, RnPop p) {
+  const int slot = blockIdx.y;
+  const int k = p.learner ? p.learner[slot] : slot;
+  if (p.state[k] != 0) return;  // (a retired learner: block-uniform, before any barrier)
+  MFG_RN_POP_REBASE();
+}
+#undef MFG_RN_POP_REBASE
 
 // dynamic LDS above 64 KB needs the attribute, which applies to the CURRENT device: once per device, result kept in
 // attr_state [64] (0 = not tried, 1 = ok, -1 = failed) -- a device where it failed takes the run-mapped kernels
@@ -1367,9 +1381,11 @@ int reward_net_forward_sums(const float* state, const float* action, int64_t B, 
 // ---- populations (mfg_irl_population.h) ----
 template <int D, int RUN, int RPR, int P1>
 static bool mfma_lds_attribute_pop() {
-  static signed char attr_state[64] = {0};
+  static signed char attr_state[64] = {0}, attr_state_ctl[64] = {0};
   return lds_attribute_once(attr_state, reinterpret_cast<const void*>(&k_reward_net_mfma_pop<D, RUN, RPR, P1, true>),
-                            reinterpret_cast<const void*>(&k_reward_net_mfma_pop<D, RUN, RPR, P1, false>));
+                            reinterpret_cast<const void*>(&k_reward_net_mfma_pop<D, RUN, RPR, P1, false>)) &&
+         lds_attribute_once(attr_state_ctl, reinterpret_cast<const void*>(&k_reward_net_mfma_pop_ctl<D, RUN, RPR, P1, true>),
+                            reinterpret_cast<const void*>(&k_reward_net_mfma_pop_ctl<D, RUN, RPR, P1, false>));
 }
 
 bool reward_net_pop_ready(int d, const mfg_reward_net_t* net, int per_learner_net, int K, int64_t net_stride) {
@@ -1434,8 +1450,9 @@ static void launch_reward_net_mfma_pop(const RewardNetArgs& a, bool sums, const 
   const int64_t grid = mfma_grid(a.B);  // (the single launch's grid for one learner)
   const size_t lds = Gm::lds_floats(a.n3, a.n4, sums) * 4;
   const dim3 g((unsigned)grid, (unsigned)(p.n_y > 0 ? p.n_y : p.K));
-  if (sums) hipLaunchKernelGGL((k_reward_net_mfma_pop<D, RUN, RPR, P1, true>), g, dim3(RM_BLOCK), lds, st, a, p);
-  else hipLaunchKernelGGL((k_reward_net_mfma_pop<D, RUN, RPR, P1, false>), g, dim3(RM_BLOCK), lds, st, a, p);
+  auto* k = sums ? (p.state ? k_reward_net_mfma_pop_ctl<D, RUN, RPR, P1, true> : k_reward_net_mfma_pop<D, RUN, RPR, P1, true>)
+                 : (p.state ? k_reward_net_mfma_pop_ctl<D, RUN, RPR, P1, false> : k_reward_net_mfma_pop<D, RUN, RPR, P1, false>);
+  hipLaunchKernelGGL(k, g, dim3(RM_BLOCK), lds, st, a, p);
   if (rows_out) *rows_out = sums ? (int)grid : 0;
 }
 static void launch_reward_net_pop(const RewardNetArgs& a, bool sums, const RnPop& p, int* rows_out, hipStream_t st) {

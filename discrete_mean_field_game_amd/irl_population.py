@@ -8,8 +8,19 @@ all), and trains them in lock-step: after the same train() calls learner k holds
 `AC_IRL(theta_k, shift_k, alpha_k, d, seed=seed_k, batch=batch, update_every=...)` with the same w and network holds after
 `train(E, stop_criteria=-1)`.
 
+Early stop: train(E, stop_criteria=c) (a scalar or [K]) gives learner k, bit for bit, what AC_IRL.train(E, stop_criteria=c_k)
+gives -- theta, w, episodes_run[k], the list_policies FIFO, and the episode returns up to episodes_run[k] (0 beyond).  The
+learners' activity states live on the device (the population control block, mfg_ctx_set_pop_control): a learner that has
+converged leaves every later launch of the call at once and the host reads nothing back inside the call.  The shared Philox
+step and the per-learner reward-call counters still advance by the full E for every learner (deterministic, no read-back), so
+a LATER call of a learner that stopped early corresponds to an AC_IRL whose _rng_step and _reward_calls were set to these
+values, not to one that simply went on.  isolate=True, learner_state, episodes_run, learner_status and clear_status(k) are
+those of ActorCriticPopulation (population.py): a diverged learner is frozen and skipped -- by evaluate (NaN rows, no CSV
+line), update_reward, reward_iteration, test_reward_network, the D_samp generation and outerloop -- instead of stopping the
+sweep.
+
 Scope: one GPU, start states drawn on the device (batch >= 2), Philox sampling, the matrix-core reward-network kernel's
-geometry (d = 15 / 21, n_fc3 <= 16), no early stop in train().
+geometry (d = 15 / 21, n_fc3 <= 16).
 
 With per-learner networks and `demonstrations`, the population also runs the reward half of the IRL loop: update_reward,
 reward_iteration and outerloop give learner k exactly what AC_IRL's methods give with learner k's settings, its lr_reward
@@ -29,7 +40,8 @@ tells the kernels of the *_nets entry points which shape a learner's blocks run.
 gives with learner k's shape and regulariser.  test_reward_network() is AC_IRL.test_reward_network for every learner, and
 gridsearch() below runs the reference's sweep as one such population.
 
-The instance owns one ops.Context; its sticky status word is shared by the K learners (as for ActorCriticPopulation).
+The instance owns one ops.Context; its sticky status word is shared by the K learners (as for ActorCriticPopulation; with
+isolate=True a diverged learner is booked to its own word instead).
 """
 from __future__ import annotations
 
@@ -284,11 +296,19 @@ class AC_IRLPopulation(_Population):
 
     # ------------------------------------------------------------------ training
     @_with_ctx
-    def train(self, num_episodes, gamma=1, constant=False, lr_critic=0.1, lr_actor=0.001, *, first_episode=0):
-        """`num_episodes` episodes of every learner: AC_IRL.train(num_episodes, stop_criteria=-1, ...) under each learner's
+    def train(self, num_episodes, gamma=1, constant=False, lr_critic=0.1, lr_actor=0.001, *, first_episode=0, stop_criteria=-1,
+              isolate=False):
+        """`num_episodes` episodes of every learner: AC_IRL.train(num_episodes, stop_criteria[k], ...) under each learner's
         reward network (episodes numbered first_episode + 1 ... in the learning-rate schedule, as there).  lr_critic /
         lr_actor: scalars or [K].  Returns a NumPy array [K, num_episodes] of the per-episode returns as AC_IRL.train books
-        them: step mode the sum of the T updates' mean rewards, rollout mode T x the update's mean reward per transition."""
+        them: step mode the sum of the T updates' mean rewards, rollout mode T x the update's mean reward per transition.
+        stop_criteria (a scalar or [K]; the default -1: none, unlike AC_IRL.train's 0.01): learner k leaves the call after the
+        first episode with |theta - prev_theta| < stop_criteria[k] (ac_irl.py:726) and holds what AC_IRL.train holds then;
+        episodes_run[k] says when, its returns are 0 beyond.  The Philox step and the reward-call counters advance by the full
+        num_episodes all the same: a later call of learner k corresponds to an AC_IRL whose _rng_step and _reward_calls were
+        set to the population's values.  isolate=True: a learner that diverges is frozen instead of raising for everybody
+        (ActorCriticPopulation.train).  isolate=False with a criterion (or after an uncleared failure): the diverged learner is
+        frozen all the same, the context's status word stays 0, the others finish the call, and train() raises afterwards."""
         T = self.episode_steps
 
         def run(b, lrc, lra, acc):
@@ -307,10 +327,11 @@ class AC_IRLPopulation(_Population):
                                            self._net_struct, self.per_learner_net, self._rn_seeds_dev, calls, b['G'],
                                            b['ws'], b['run'], **common)
                 self._calls_k += int(num_episodes)
-        out = self._train(num_episodes, lr_critic, lr_actor, run)
+        out = self._train(num_episodes, lr_critic, lr_actor, run, stop_criteria, isolate)
         if out.shape[1]:
             for k, t in enumerate(self.thetas):         # AC_IRL.train records the policy (list_policies FIFO)
-                self.list_policies[k] = (self.list_policies[k] + [float(t)])[1:]
+                if self._act.state[k] != 2:            # (a failed learner has no policy to record)
+                    self.list_policies[k] = (self.list_policies[k] + [float(t)])[1:]
         return out * T if self.update_every == 'rollout' else out
 
     @_with_ctx
@@ -423,7 +444,7 @@ class AC_IRLPopulation(_Population):
     @_with_ctx
     def update_reward(self, learners=None):
         """One AC_IRL.update_reward of every learner (or of the listed ones): two launches for all of them."""
-        active = list(range(self.K)) if learners is None else [int(k) for k in learners]
+        active = self._healthy() if learners is None else [int(k) for k in learners if self._act.state[int(k)] != 2]
         self._train_rewards(active, 1)
 
     def _forward(self, st, ac, active, keys):
@@ -475,7 +496,7 @@ class AC_IRLPopulation(_Population):
         prev = np.full(K, -100.0)
         its = np.zeros(K, dtype=np.int64)
         last = np.full((K, 2), np.nan)
-        active = list(range(K))
+        active = self._healthy()                  # (failed learners take no part: iterations 0, NaN averages)
         it = 0
         while it < max_iterations and active:
             u = min(iter_check - it % iter_check, max_iterations - it)
@@ -509,15 +530,17 @@ class AC_IRLPopulation(_Population):
         if not self.per_learner_net:
             raise ValueError('test_reward_network needs one reward network per learner')
         K = self.K
-        active = list(range(K))
+        active = self._healthy()                  # (failed learners: NaN rows)
         num_demos = len(self._demo_store)
         self._gen_store.clear()
         if num_demos:
             self._gen_store.push(*self._generate(num_demos))
-        avg = self._reward_averages(active)
         out = np.full((K, 3), np.nan)
-        out[:, 0] = avg[:, 0]
-        out[:, 2] = avg[:, 1]
+        if not active:
+            return out
+        avg = self._reward_averages(active)
+        out[active, 0] = avg[:, 0]
+        out[active, 2] = avg[:, 1]
         if self._test_np is not None:
             if self._test_dev is None:
                 d = self.d
@@ -528,7 +551,7 @@ class AC_IRLPopulation(_Population):
             keys = [((int(self.seeds[k]) + RN_SEED_OFFSET) ^ (int(self._calls_k[k]) * KEY_MUL)) & MASK64 for k in active]
             r = self._forward(ts, ta, active, keys)
             host = torch.stack([r[k].double().sum() for k in active]).cpu().numpy()
-            out[:, 1] = [float(v) / ts.shape[0] for v in host]
+            out[active, 1] = [float(v) / ts.shape[0] for v in host]
         if self.verbose:
             for k in active:
                 print('learner %d: Avg reward demo train %f | Avg reward demo test %f | Avg reward gen %f' % ((k,) + tuple(out[k])))
@@ -540,9 +563,11 @@ class AC_IRLPopulation(_Population):
         K, T, d = self.K, EPISODE_STEPS, self.d
         off = self._gen_traj_counter
         self._gen_traj_counter = off + n
-        states = torch.empty(K, n, T + 1, d, dtype=torch.float32, device=self.device)
-        actions = torch.empty(K, n, T, d, d, dtype=torch.float32, device=self.device)
-        for k in range(K):
+        live = self._healthy()                     # (a failed learner rolls nothing: its rows stay zero and are never read)
+        new = torch.empty if len(live) == K else torch.zeros
+        states = new(K, n, T + 1, d, dtype=torch.float32, device=self.device)
+        actions = new(K, n, T, d, d, dtype=torch.float32, device=self.device)
+        for k in live:
             seed = int(self.seeds[k])
             _, pi0 = ops.draw_start(self._mat_pi0_dev, n, seed, self._rng_step, off)
             ops.rollout(pi0, T, self._theta[k:k + 1], float(self.shifts[k]), float(self.alpha_scales[k]), seed=seed,
@@ -553,15 +578,20 @@ class AC_IRLPopulation(_Population):
 
     @_with_ctx
     def outerloop(self, num_iterations=20, num_gen_from_policy=5, max_reward_iterations=100, max_forward_episodes=200, gamma=1,
-                  constant=False, lr_critic=0.1, lr_actor=0.001, *, final_training=True):
+                  constant=False, lr_critic=0.1, lr_actor=0.001, *, final_training=True, isolate=False):
         """AC_IRL.outerloop for every learner: alternate reward_iteration (stop criterion 1e-4, a check every 10 updates) and
         forward solves from theta_initial, D_samp refreshed as a FIFO; closes with a 2000-episode forward solve unless
-        final_training=False.  lr_critic / lr_actor: scalars or [K].  Returns the thetas [K]."""
+        final_training=False.  lr_critic / lr_actor: scalars or [K].  Returns the thetas [K].
+        isolate=True: the learners' range is checked on the device before the first D_samp generation and every forward solve
+        runs with train(..., isolate=True), so a learner that is or goes out of range is frozen and skipped while the loop
+        completes for the others."""
         nd = min(len(self._demo_store), NUM_DEMO_SAMPLES)
         self._check_reward_learning()
         if not batch_fits(nd, min(int(num_gen_from_policy) * self.num_policies, NUM_GEN_SAMPLES), self._rn_dims[4]):
             raise ValueError('update_reward batch outside the HIP training step\'s limits')
         num_gen_from_policy = int(num_gen_from_policy)
+        if isolate:
+            self.train(0, isolate=True)            # (no episode: the control block's check alone, before anything samples)
         self._gen_store.clear()
         self._gen_store.push(*self._generate(num_gen_from_policy * self.num_policies))
         self.reward_update_count[:] = 0
@@ -570,10 +600,10 @@ class AC_IRLPopulation(_Population):
             self._gen_store.push(*self._generate(num_gen_from_policy), drop=num_gen_from_policy)
             self.reward_iteration(max_iterations=max_reward_iterations, stop_criteria=0.0001, iter_check=10)
             self._theta.copy_(th0)
-            self.train(max_forward_episodes, gamma, constant, lr_critic, lr_actor)
+            self.train(max_forward_episodes, gamma, constant, lr_critic, lr_actor, isolate=isolate)
         if final_training:
             self._theta.copy_(th0)
-            self.train(2000, gamma, constant, lr_critic, lr_actor)
+            self.train(2000, gamma, constant, lr_critic, lr_actor, isolate=isolate)
         return self.thetas
 
 

@@ -121,6 +121,25 @@ class Context:
     def clear_status(self):
         L.check(L.lib().mfg_ctx_clear_status(self._ptr), 'mfg_ctx_clear_status')
 
+    def set_pop_control(self, state=None, status=None, theta_prev=None, episodes_run=None, stop_criteria=None):
+        """mfg_ctx_set_pop_control: bind a population control block -- device tensors [K]: state / status / episodes_run int32,
+        theta_prev / stop_criteria float64 -- to this context; every population training call made with the context bound
+        then retires learners on the device (include/mfg_hip.h).  No arguments: clear it.  The caller keeps the tensors alive
+        while the block is set."""
+        import ctypes as C
+        if state is None:
+            L.check(L.lib().mfg_ctx_set_pop_control(self._ptr, None), 'mfg_ctx_set_pop_control')
+            return
+        K = int(state.shape[0])
+        for name, t, dt in (('state', state, torch.int32), ('status', status, torch.int32),
+                            ('theta_prev', theta_prev, torch.float64), ('episodes_run', episodes_run, torch.int32),
+                            ('stop_criteria', stop_criteria, torch.float64)):
+            if t is None or t.dtype != dt or t.dim() != 1 or t.shape[0] != K or not t.is_contiguous() or not t.is_cuda:
+                raise ValueError('set_pop_control: %s must be a contiguous %s device tensor [%d]' % (name, dt, K))
+        blk = L.PopControlStruct(state.data_ptr(), status.data_ptr(), theta_prev.data_ptr(), episodes_run.data_ptr(),
+                                 stop_criteria.data_ptr(), K)
+        L.check(L.lib().mfg_ctx_set_pop_control(self._ptr, C.byref(blk)), 'mfg_ctx_set_pop_control')
+
     def close(self):
         if self._ptr is not None:
             try:

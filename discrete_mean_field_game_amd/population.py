@@ -11,8 +11,19 @@ Start states are drawn on the device, as actor_critic does for batch > 1 (hence 
 in-kernel rewards ('mfg_ac2', 'synthetic'); IRL and several GPUs are out of scope.
 
 The instance owns one ops.Context: its sticky mixed-range status word (include/mfg_hip.h, mfg_status) is shared by the K
-learners, so ONE learner whose policy leaves the fp32 range of mixed-precision sampling stops the population's next launch
-(train() raises MfgError; clear_status() resets it; precision='f64' has no such range).
+learners, so by default ONE learner whose policy leaves the fp32 range of mixed-precision sampling stops the population's next
+launch (train() raises MfgError; clear_status() resets it; precision='f64' has no such range).
+
+Retiring learners on the device: train(..., stop_criteria=c, isolate=True) runs under a population control block
+(mfg_ctx_set_pop_control, include/mfg_hip.h) -- an activity state per learner in device memory that every launch of the call
+carries.  A learner whose |theta_e - theta_{e-1}| falls below its criterion stops after that episode (AC_IRL.train's early
+stop, ac_irl.py:726), a learner whose theta leaves the mixed-precision range or whose theta / w stop being finite is marked
+failed at the episode boundary at which that is seen; either way its blocks leave the remaining launches at once, the other
+learners run on with the same bits, and the host reads nothing back inside the call.  With isolate=True a failed learner does
+not raise and does not touch the context's status word: `learner_state` (0 active, 1 stopped, 2 failed), `episodes_run` and
+`learner_status` tell what happened, failed learners are skipped (NaN rows) by everything after training, and
+clear_status(k) revives one.  The Philox step (and an IRL population's reward-call counters) advance by the whole call for
+every learner, stopped or not.
 """
 from __future__ import annotations
 
@@ -38,6 +49,44 @@ def broadcast(name, value, K, dtype=np.float64):
     if a.shape[0] != K:
         raise ValueError('%s: expected a scalar or %d values (one per learner), got %d' % (name, K, a.shape[0]))
     return a.copy()
+
+
+def stop_criteria_array(stop_criteria, K):
+    """train()'s stop_criteria (a scalar or K values) as a NumPy fp64 array [K]; a negative entry (the default -1, as in
+    AC_IRL.train) means no early stop for that learner.  ValueError for a wrong count or a NaN."""
+    a = broadcast('stop_criteria', stop_criteria, K)
+    if np.any(np.isnan(a)):
+        raise ValueError('stop_criteria: NaN')
+    return a
+
+
+ACTIVE, STOPPED, FAILED = 0, 1, 2      # mfg_pop_control_t::state
+
+
+class LearnerActivity:
+    """The host mirror of a population's control block: per learner the state (ACTIVE / STOPPED / FAILED), the episodes it
+    completed in the last train() call and its own status bits.  All zero until a call reports otherwise."""
+
+    def __init__(self, K):
+        self.state = np.zeros(K, dtype=np.int32)
+        self.episodes = np.zeros(K, dtype=np.int32)
+        self.status = np.zeros(K, dtype=np.int32)
+
+    def healthy(self):
+        """The learners that have not failed, in order."""
+        return [k for k in range(self.state.shape[0]) if self.state[k] != FAILED]
+
+    def clear(self, k=None):
+        """Revive the failed learner k (None: all): state and status bits back to 0; a stopped learner stays as it is."""
+        K = self.state.shape[0]
+        if k is None:
+            sel = slice(None)
+        else:
+            if not 0 <= int(k) < K:
+                raise IndexError('learner %d of %d' % (k, K))
+            sel = slice(int(k), int(k) + 1)
+        self.state[sel] = np.where(self.state[sel] == FAILED, ACTIVE, self.state[sel])
+        self.status[sel] = 0
 
 
 def check_args(K, d, batch, update_every, reward, precision, episode_steps):
@@ -242,6 +291,9 @@ class _Population:
         self._alphas_dev = torch.as_tensor(self.alpha_scales, device=dev)
         self._rng_step = 0  # Philox step counter, shared by the learners (they advance in lock-step)
         self._bufs = None
+        # per-learner activity (the population control block): host mirrors, read back with train()'s one synchronisation
+        self._act = LearnerActivity(K)
+        self._ctl = None     # the block's device tensors, made by the first train() call that needs one
 
     # ------------------------------------------------------------------ state
     @property
@@ -255,6 +307,26 @@ class _Population:
     @property
     def w(self):
         return self._w.cpu().numpy().copy()
+
+    @property
+    def learner_state(self):
+        """[K] of 0 (active), 1 (stopped early in the last train() call) or 2 (failed, until clear_status)."""
+        return self._act.state.copy()
+
+    @property
+    def episodes_run(self):
+        """[K] episodes each learner completed while active in the last train() call (a call without a control block: all of
+        its episodes)."""
+        return self._act.episodes.copy()
+
+    @property
+    def learner_status(self):
+        """[K] status bits of each learner's own word (_lib.STATUS_MIXED_RANGE, _lib.STATUS_POP_NONFINITE; 0 = healthy)."""
+        return self._act.status.copy()
+
+    def _healthy(self):
+        """The learners that have not failed, in order."""
+        return self._act.healthy()
 
     def _buffers(self):
         K, B, d, T = self.K, self.batch, self.d, self.episode_steps
@@ -280,33 +352,74 @@ class _Population:
         return self._bufs
 
     # ------------------------------------------------------------------ training
-    def _train(self, num_episodes, lr_critic, lr_actor, run):
+    def _train(self, num_episodes, lr_critic, lr_actor, run, stop_criteria=-1, isolate=False):
         """The frame of train(): checks, learning rates as device arrays [K], run(buffers, lrc, lra, acc) -- the native calls
         -- and the Philox step; returns acc [K, num_episodes] as a NumPy array.  MfgError when a mixed-precision launch left the
-        fp32 range."""
+        fp32 range.  A stop criterion, isolate=True or a learner that failed earlier: the call runs under the population's
+        control block (set on the context for the call only) and the per-learner states are read back with acc."""
         K = self.K
         num_episodes = int(num_episodes)
         if num_episodes < 0:
             raise ValueError('num_episodes < 0')
         lrc = torch.as_tensor(broadcast('lr_critic', lr_critic, K), device=self.device)
         lra = torch.as_tensor(broadcast('lr_actor', lr_actor, K), device=self.device)
-        if num_episodes == 0:
+        stop = stop_criteria_array(stop_criteria, K)
+        control = bool(isolate) or bool(np.any(stop >= 0)) or bool(np.any(self._act.state == 2))
+        if not control:
+            # (no learner has failed here, or the call would be a controlled one: everybody is active for the whole call)
+            self._act.state[:] = ACTIVE
+            self._act.episodes[:] = num_episodes
+        if num_episodes == 0 and not control:
             return np.zeros((K, 0))
         acc = torch.zeros(K, num_episodes, dtype=torch.float64, device=self.device)
-        run(self._buffers(), lrc, lra, acc)
+        if not control:
+            run(self._buffers(), lrc, lra, acc)
+            self._rng_step += num_episodes * self.episode_steps
+            out = acc.cpu().numpy()
+            if self.precision == 'mixed' and self._ctx.status(synchronize=True):
+                raise L.MfgError('a mixed-precision sampling launch of this population ran with |theta| (1 + |shift|) > 86 '
+                                 '(or theta not finite): its outputs are NaN; use precision=\'f64\', then clear_status()')
+            return out
+        if self._ctl is None:
+            self._ctl = {'ints': torch.zeros(3, K, dtype=torch.int32, device=self.device),     # state | status | episodes_run
+                         'theta_prev': torch.zeros(K, dtype=torch.float64, device=self.device),
+                         'stop': torch.zeros(K, dtype=torch.float64, device=self.device)}
+        c = self._ctl
+        # `stopped` is reset by every call, `failed` (with its status bits) persists until clear_status
+        failed = self._act.state == 2
+        host = np.zeros((3, K), dtype=np.int32)
+        host[0, failed] = 2
+        host[1, failed] = self._act.status[failed]
+        c['ints'].copy_(torch.from_numpy(host))
+        c['stop'].copy_(torch.from_numpy(stop))
+        self._ctx.set_pop_control(c['ints'][0], c['ints'][1], c['theta_prev'], c['ints'][2], c['stop'])
+        try:
+            run(self._buffers(), lrc, lra, acc)
+        finally:
+            self._ctx.set_pop_control()
         self._rng_step += num_episodes * self.episode_steps
         out = acc.cpu().numpy()
-        if self.precision == 'mixed' and self._ctx.status(synchronize=True):
+        ints = c['ints'].cpu().numpy()
+        self._act.state, self._act.status, self._act.episodes = ints[0].copy(), ints[1].copy(), ints[2].copy()
+        if self.precision == 'mixed' and self._ctx.status(synchronize=False):
             raise L.MfgError('a mixed-precision sampling launch of this population ran with |theta| (1 + |shift|) > 86 '
                              '(or theta not finite): its outputs are NaN; use precision=\'f64\', then clear_status()')
+        if not isolate and np.any(self._act.state == 2):
+            raise L.MfgError('learner(s) %s of this population failed (theta outside |theta| (1 + |shift|) <= 86 in mixed '
+                             'precision, or theta / w not finite; learner_status has the bits): they are frozen, the others '
+                             'trained on; isolate=True does not raise, clear_status() revives them'
+                             % np.flatnonzero(self._act.state == 2).tolist())
         return out
 
     def status(self, synchronize=True) -> int:
         """Bits of this population's status word (0 = healthy), shared by its K learners."""
         return self._ctx.status(synchronize)
 
-    def clear_status(self):
+    def clear_status(self, k=None):
+        """Reset the context's status word and revive the failed learner k (None: all of them): its state and status bits go
+        back to 0 -- give it a theta (and w) it can train with first."""
         self._ctx.clear_status()
+        self._act.clear(k)
 
     def _evaluate(self, episode_length, indir, outfile, write_header, repeats):
         """The body of evaluate() (the population's context bound)."""
@@ -315,16 +428,21 @@ class _Population:
         emp = load_empirical(indir, self.d, int(episode_length))
         first_step = self._rng_step
         self._rng_step += int(episode_length) - 1    # (a diverged launch has run: its step is spent, as in train())
+        live = self._healthy()                       # failed learners are not launched: NaN rows, no CSV line
+        sub = (lambda t: t) if len(live) == self.K else (lambda t: t[torch.as_tensor(live, device=self.device)].contiguous())
+        table = np.full((self.K, 8), np.nan)
         try:
-            table = evaluate_policies(emp, self._theta, self._shifts_dev, self._alphas_dev, self._seeds_dev, first_step,
-                                      int(repeats), self.precision, self.device, self._ctx)
+            if live:
+                table[live] = evaluate_policies(emp, sub(self._theta), sub(self._shifts_dev), sub(self._alphas_dev),
+                                                sub(self._seeds_dev), first_step, int(repeats), self.precision, self.device,
+                                                self._ctx)
         except L.MfgError as e:
             if e.code:                               # refused by the library before anything was launched
                 self._rng_step = first_step
             raise
         thetas = self.thetas
         write_eval_rows(outfile, write_header, [(float(thetas[k]), float(self.shifts[k]), float(self.alpha_scales[k]))
-                                                for k in range(self.K)], table)
+                                                for k in live], table[live])
         return table[:, 0::2].copy()
 
     def learner(self, k):
@@ -332,6 +450,9 @@ class _Population:
         / further single training).  Its construction leaves the global np.random stream as it was."""
         if not 0 <= k < self.K:
             raise IndexError('learner %d of %d' % (k, self.K))
+        if self._act.state[k] == 2:
+            raise L.MfgError('learner %d has failed (learner_status 0x%x): clear_status(%d) revives it'
+                             % (k, int(self._act.status[k]), k))
         state = np.random.get_state()
         try:
             ac = self._new_learner(k)
@@ -356,11 +477,23 @@ class ActorCriticPopulation(_Population):
         self.reward_kind = REWARDS[reward]
 
     @_with_ctx
-    def train(self, num_episodes, gamma=1, constant=0, lr_critic=0.1, lr_actor=0.001, *, first_episode=0):
+    def train(self, num_episodes, gamma=1, constant=0, lr_critic=0.1, lr_actor=0.001, *, first_episode=0, stop_criteria=-1,
+              isolate=False):
         """`num_episodes` episodes of every learner (mfg_ac2.py:448-539; update per env step or per episode as chosen at
         construction).  lr_critic / lr_actor: scalars or [K].  Returns a NumPy array [K, num_episodes] of what
         actor_critic.train books per episode (step mode: the sum of the T updates' mean rewards; rollout mode: the one
-        update's mean reward).  The Philox step counter carries over to the next call."""
+        update's mean reward).  The Philox step counter carries over to the next call.
+        stop_criteria (a scalar or [K]; negative: none): learner k stops after the first episode e with |theta_e - theta_{e-1}|
+        < stop_criteria[k] (theta_0: its theta at the start of the call) and then holds exactly what the population holds
+        after train(e); its row of the result is 0 beyond.  isolate=True: a learner that leaves the mixed-precision range or
+        turns non-finite is frozen at the episode boundary at which that is seen (one that is out of range at the start never
+        launches) instead of raising for everybody; see learner_state / episodes_run / learner_status.  The defaults issue the
+        launches this method always issued.
+        isolate=False under a control block -- a stop criterion is given, or a learner failed in an earlier call and was not
+        cleared -- differs from the plain call in how a diverging learner is reported: it is booked to its own word and
+        frozen, the context's status word stays 0, the other learners finish the call, and train() then raises MfgError
+        naming the failed learners.  Later calls are not refused; they skip those learners (and raise again when
+        isolate=False) until clear_status()."""
         T = self.episode_steps
 
         def run(b, lrc, lra, acc):
@@ -374,7 +507,7 @@ class ActorCriticPopulation(_Population):
                                        self._shifts_dev, self._alphas_dev, self._w, gamma, b['G'], b['ws'], b['run'], lrc, lra,
                                        self._seeds_dev, reward_kind=self.reward_kind, first_step=self._rng_step,
                                        reward_acc=acc, precision=self.precision)
-        return self._train(num_episodes, lr_critic, lr_actor, run)
+        return self._train(num_episodes, lr_critic, lr_actor, run, stop_criteria, isolate)
 
     @_with_ctx
     def evaluate(self, episode_length=16, indir='test_normalized_round2', outfile='eval_mfg_round2/test_eval_fixed_reward.csv',

@@ -104,7 +104,8 @@ int mfg_init(void);
  * not refused (the latter report, but are never held up), so another model instance or thread on the device keeps working.  mfg_status() reads the word without
  * synchronising (synchronise the stream first to be sure a given launch has reported); it returns MFG_OK or MFG_ERANGE and
  * stores the bits in *bits_host (may be NULL). */
-enum { MFG_STATUS_MIXED_RANGE = 1 };
+enum { MFG_STATUS_MIXED_RANGE = 1,
+       MFG_STATUS_POP_NONFINITE = 2 /* per-learner words of a population control block only: theta or w not finite */ };
 int mfg_status(unsigned* bits_host);
 int mfg_clear_status(void);
 
@@ -132,6 +133,34 @@ int mfg_ctx_status(mfg_ctx_t* ctx, unsigned* bits_host);
 int mfg_ctx_clear_status(mfg_ctx_t* ctx);
 int mfg_ctx_adopt_comm(mfg_ctx_t* ctx, void* comm);
 void* mfg_ctx_comm(mfg_ctx_t* ctx);
+
+/* Population control block: per-learner activity states that live on the device, so that learners of a population call (the
+ * mfg_train_*_pop entry points below) can be retired between two episodes -- early stop, divergence -- without a host round
+ * trip and without stopping the others.  Device arrays, one entry per learner, owned by the caller:
+ *   state [K]          0 active, 1 stopped (early stop), 2 failed; the blocks of a learner whose state is not 0 return at once
+ *   status [K]         learner k's own status word: with a block, a mixed-precision launch books MFG_STATUS_MIXED_RANGE to the
+ *                      learner whose theta left the range and not to the context, whose word stays 0
+ *   theta_prev [K]     theta after the previous episode
+ *   episodes_run [K]   += 1 after every episode the learner completed while active (the caller zeroes it)
+ *   stop_criteria [K]  the learner stops once |theta - theta_prev| < stop_criteria[k] (AC_IRL.train, ac_irl.py:726); < 0: never
+ * mfg_ctx_set_pop_control(ctx, block) binds a copy of the block to the context (NULL clears); every population training call
+ * issued with that context bound then launches one small kernel (K waves) before its first episode and after every episode's
+ * closing update.  For a learner still active it scans theta and the learner's w for non-finite values (MFG_STATUS_POP_NONFINITE),
+ * in mixed precision tests !(|theta| (1 + |shift|) <= 86) (MFG_STATUS_MIXED_RANGE) and reads the learner's status word: any of
+ * these -> the bits go to status[k] and state[k] = 2.  Otherwise, after an episode: episodes_run[k] += 1, state[k] = 1 when the
+ * criterion is met, theta_prev[k] = theta (before the first episode: the checks and theta_prev only).  A call still enqueues all
+ * its episodes and reads nothing back; the Philox step and the reward-call counters advance by the whole call for every learner.
+ * Without a block the calls issue exactly the launches they always did.  Checked when the block is set and again before a
+ * call launches anything: every pointer non-null, K the call's K (MFG_EINVAL). */
+typedef struct mfg_pop_control {
+  int32_t* state;
+  unsigned* status;
+  double* theta_prev;
+  int32_t* episodes_run;
+  const double* stop_criteria;
+  int32_t K;
+} mfg_pop_control_t;
+int mfg_ctx_set_pop_control(mfg_ctx_t* ctx, const mfg_pop_control_t* block);
 
 /* Host-side query: multiprocessor count and gcnArchName of the current device. */
 int mfg_device_info(int* cu_count_host, char* arch_host, int arch_len);
@@ -421,7 +450,9 @@ int mfg_train_episodes(const float* mat_pi0, int64_t num_start, float* pi_io, fl
  * Checked before anything is launched: 1 <= K <= MFG_POP_MAX_K, no null pointer, d <= 64 (MFG_EUNSUPPORTED beyond: one wave
  * per trajectory fills the machine there), an in-kernel reward_kind, the Philox step counter does not wrap (MFG_EINVAL);
  * the slice holds the update's partial rows (MFG_EWORKSPACE).  The sticky mixed-range status word (mfg_status) is per
- * device / context: one learner whose policy left the fp32 range blocks the population's next mixed-precision launch. */
+ * device / context: one learner whose policy left the fp32 range blocks the population's next mixed-precision launch --
+ * unless the bound context carries a population control block (mfg_ctx_set_pop_control), which books the condition to that
+ * learner alone, retires it at the next episode boundary and lets the others run on. */
 #define MFG_POP_MAX_K 65535
 /* step mode (update_every = 'step', mfg_ac2.py:478-526): mfg_train_episodes for K learners */
 int mfg_train_episodes_pop(const float* mat_pi0, int64_t num_start, float* pi_io, float* pi_scratch, int64_t B, int K, int d, int T,
@@ -515,7 +546,9 @@ int mfg_train_rollout_irl(const float* mat_pi0, int64_t num_start, const int32_t
                           double* delta, double* g, double* G, double* reward_acc, void* workspace, size_t workspace_bytes,
                           mfg_stream_t stream);
 
-/* IRL populations: K independent forward learners of AC_IRL.train (ac_irl.py:634-732, stop_criteria = -1 as in outerloop)
+/* IRL populations: K independent forward learners of AC_IRL.train (ac_irl.py:634-732; without a population control block
+ * stop_criteria = -1 as in outerloop, with one -- mfg_ctx_set_pop_control -- learner k stops after the episode at which
+ * |theta - theta_prev| < stop_criteria[k], as ac_irl.py:726 does, and holds what the single learner holds at that point)
  * trained in lock-step on ONE GPU, every launch of an episode serving all K.  Learner k of a population call gives, bit for bit
  * (theta, w, G, reward_acc, final states and the last step's P / reward / delta / g), what the single-learner path gives with
  * B = Bk, the same traj_offset and learner k's seed, theta, w, shift, alpha_scale, learning rates and reward network:
