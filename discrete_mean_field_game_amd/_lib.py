@@ -115,7 +115,6 @@ SIGNATURES = {
 }
 
 
-
 class RewardNetStruct(C.Structure):
     """mfg_reward_net_t of include/mfg_hip.h."""
     _fields_ = ([(n, C.c_int) for n in ('k1', 'f2', 'k2', 'n3', 'n4')]
@@ -134,21 +133,9 @@ SIGNATURES['mfg_train_rollout_irl'] = (_i32, [_p, _i64, _p, _i64, _i32, _i32, _p
                                               _f64, C.POINTER(RewardNetStruct), _u64, _u64, _p, _p, _p, _p, _p, _p, _p, _p, _p, _sz,
                                               _p])
 
-SIGNATURES['mfg_train_episodes_irl_pop'] = (_i32, [_p, _i64, _p, _p, _i64, _i32, _i32, _i32, _i64, _i64, _i32, _p, _p, _p, _p, _f64,
-                                                   _p, _u32, _u64, _i32, _p, _p, C.POINTER(RewardNetStruct), _i32, _p, _u64, _p,
-                                                   _p, _p, _p, _p, _p, _p, _sz, _p])
-
-SIGNATURES['mfg_train_rollouts_irl_pop'] = (_i32, [_p, _i64, _i64, _i32, _i32, _i32, _i64, _i64, _i32, _p, _p, _p, _p, _f64, _p,
-                                                   _u32, _u64, _i32, _p, _p, C.POINTER(RewardNetStruct), _i32, _p, _u64, _p, _p,
-                                                   _p, _p, _p, _p, _p, _p, _p, _sz, _p])
-
-# per-learner reward-call counters (device array [K]) and the learner stride of one flat parameter row per learner
-SIGNATURES['mfg_train_episodes_irl_pop_calls'] = (_i32, SIGNATURES['mfg_train_episodes_irl_pop'][1][:23] + [_i32, _i64, _p, _p]
-                                                  + SIGNATURES['mfg_train_episodes_irl_pop'][1][26:])
-SIGNATURES['mfg_train_rollouts_irl_pop_calls'] = (_i32, SIGNATURES['mfg_train_rollouts_irl_pop'][1][:21] + [_i32, _i64, _p, _p]
-                                                  + SIGNATURES['mfg_train_rollouts_irl_pop'][1][24:])
-SIGNATURES['mfg_reward_net_forward_pop'] = (_i32, [_p, _p, _i64, _i64, _i64, _i32, C.POINTER(RewardNetStruct), _i32, _i64, _i32, _p,
-                                                   _p, _i32, _u64, _p, _p, _sz, _p])
+class RnGeomStruct(C.Structure):
+    """mfg_rn_geom_t of include/mfg_hip.h: one learner's n_fc3, n_fc4, keep_prob and l1_l2 flag (16 bytes)."""
+    _fields_ = [('n3', C.c_int32), ('n4', C.c_int32), ('keep_prob', C.c_float), ('l1l2', C.c_int32)]
 
 
 class RnTrainPlan(C.Structure):
@@ -157,25 +144,22 @@ class RnTrainPlan(C.Structure):
                 ('demo_rows', C.c_int32 * RN_TRAIN_MAX_TRAJ), ('gen_rows', C.c_int32 * RN_TRAIN_MAX_TRAJ)]
 
 
-SIGNATURES['mfg_reward_net_train_steps_pop'] = (_i32, [_p, _p, _p, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _p, _p, _i64, _p,
-                                                       _p, _i64, _p, _p, _sz, _i32, _i32, _i32, _i32, _i32, _i32, C.c_float,
-                                                       _i32, _f64, _f64, _f64, _p, _p, _sz, _p])
+# the IRL population calls: ..., net, per_learner_net, net_stride, geom_host, geom_dev (the optional geometry table: two NULLs
+# without one), rn_seed [K], rn_call0 [K], ...
+SIGNATURES['mfg_train_episodes_irl_pop'] = (_i32, [_p, _i64, _p, _p, _i64, _i32, _i32, _i32, _i64, _i64, _i32, _p, _p, _p, _p, _f64,
+                                                   _p, _u32, _u64, _i32, _p, _p, C.POINTER(RewardNetStruct), _i32, _i64, _p, _p,
+                                                   _p, _p, _p, _p, _p, _p, _p, _p, _p, _sz, _p])
 
+SIGNATURES['mfg_train_rollouts_irl_pop'] = (_i32, [_p, _i64, _i64, _i32, _i32, _i32, _i64, _i64, _i32, _p, _p, _p, _p, _f64, _p,
+                                                   _u32, _u64, _i32, _p, _p, C.POINTER(RewardNetStruct), _i32, _i64, _p, _p, _p,
+                                                   _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _sz, _p])
 
-class RnGeomStruct(C.Structure):
-    """mfg_rn_geom_t of include/mfg_hip.h: one learner's n_fc3, n_fc4, keep_prob and l1_l2 flag (16 bytes)."""
-    _fields_ = [('n3', C.c_int32), ('n4', C.c_int32), ('keep_prob', C.c_float), ('l1l2', C.c_int32)]
+SIGNATURES['mfg_reward_net_forward_pop'] = (_i32, [_p, _p, _i64, _i64, _i64, _i32, C.POINTER(RewardNetStruct), _i32, _i64, _p, _p,
+                                                   _i32, _p, _p, _i32, _u64, _p, _p, _sz, _p])
 
-
-# the same calls with a per-learner geometry table (host copy, device copy) behind net_stride / k2
-SIGNATURES['mfg_train_episodes_irl_pop_nets'] = (_i32, SIGNATURES['mfg_train_episodes_irl_pop_calls'][1][:25] + [_p, _p]
-                                                 + SIGNATURES['mfg_train_episodes_irl_pop_calls'][1][25:])
-SIGNATURES['mfg_train_rollouts_irl_pop_nets'] = (_i32, SIGNATURES['mfg_train_rollouts_irl_pop_calls'][1][:23] + [_p, _p]
-                                                 + SIGNATURES['mfg_train_rollouts_irl_pop_calls'][1][23:])
-SIGNATURES['mfg_reward_net_forward_pop_nets'] = (_i32, SIGNATURES['mfg_reward_net_forward_pop'][1][:9] + [_p, _p]
-                                                 + SIGNATURES['mfg_reward_net_forward_pop'][1][9:])
-_steps = SIGNATURES['mfg_reward_net_train_steps_pop'][1]
-SIGNATURES['mfg_reward_net_train_steps_pop_nets'] = (_i32, _steps[:9] + [_p, _p] + _steps[11:26] + _steps[28:])
+SIGNATURES['mfg_reward_net_train_steps_pop'] = (_i32, [_p, _p, _p, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _p, _p, _p, _p,
+                                                       _i64, _p, _p, _i64, _p, _p, _sz, _i32, _i32, _i32, _i32, _i32, _i32,
+                                                       C.c_float, _i32, _f64, _f64, _f64, _p, _p, _sz, _p])
 
 
 class PopControlStruct(C.Structure):

@@ -22,7 +22,7 @@ struct RnPop {
   int64_t s_state, s_action, s_n, s_next, s_w;  // elements
   int64_t s_ws;                                  // bytes (part_rows, col_f: in the learner's workspace slice)
   const uint64_t* rn_seed;
-  uint64_t key_ctr;
+  uint64_t key_ctr;                              // (no host call sets it any more: the training calls always give call_base)
   int64_t s_net;                                 // elements between two learners' weights (0: numel_t per tensor)
   const uint64_t* call_base;                     // [K] device (NULL: the shared key_ctr)
   uint64_t call_j;
@@ -34,7 +34,7 @@ struct RnPop {
                                                  // blocks of a learner whose state is not 0 return at once (NULL: all run)
 };
 
-// Per-learner geometry (the *_nets entry points, include/mfg_hip.h): learner k's entry is read by its blocks -- block-uniform,
+// Per-learner geometry (the optional table, include/mfg_hip.h): learner k's entry is read by its blocks -- block-uniform,
 // one 16-byte scalar load -- before they run the single kernel's body with its n3 / n4 / keep_prob (/ l1l2).  Learner k's ten
 // tensors are one flat row, at the offsets of rt_layout(d, 5, 2, 3, n3_k, n4_k) from row_base + k net_stride; the launch's own
 // n3 / n4 are the table's maxima and size the dynamic LDS and the workspace slices only.

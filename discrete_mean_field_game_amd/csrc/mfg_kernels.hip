@@ -1990,7 +1990,7 @@ static int reduce_core_sums(int d, int64_t B, double* G, int accumulate, void* w
 extern "C" {
 
 const char* mfg_last_error(void) { return g_err; }
-int mfg_abi_version(void) { return 17; }
+int mfg_abi_version(void) { return 18; }
 
 int mfg_init(void) {
   if (!htab_ptr()) return fail(MFG_ELAUNCH, "%s", "mfg_init: no HIP device / table initialisation failed");
@@ -3278,32 +3278,32 @@ int mfg_evaluate_pop(const float* emp32, const double* emp64, int64_t N, int L, 
                 "reward network (d = 21 / 15, 5 / 2 / 3, n_fc3 <= 16, 8-byte aligned fc3_w of every learner)",           \
                 d, net->k1, net->f2, net->k2, net->n3, net->n4)
 
-// a population with a geometry table (the *_nets entry points; rn_pop_nets_struct, mfg_irl_population.h): its checks, then the
-// launches are set up with the row base and the table's maxima
+// a population with a geometry table (geom_host / geom_dev given; rn_pop_nets_struct, mfg_irl_population.h): its checks, then
+// the launches are set up with the row base and the table's maxima
 #define IRL_POP_NETS()                                                                                                   \
   mfg_reward_net_t net_max;                                                                                              \
-  if (geom_given) {                                                                                                      \
+  if (geom_host || geom_dev) {                                                                                           \
     REQUIRE(net && net->conv1_w, "null pointer");                                                                        \
     const int rc_g = rn_pop_nets_struct(net, geom_host, geom_dev, K, d, per_learner_net, net_stride, &net_max);          \
     if (rc_g != MFG_OK) return rc_g;                                                                                     \
     net = &net_max;                                                                                                      \
   }
 
-// dropout key of reward-network call number `call` (1-based) under rn_seed; a population xors its learners' seeds in the
-// kernel: RnPop::key_ctr is the key under seed 0
+// dropout key of reward-network call number `call` (1-based) under rn_seed (a population forms its learners' keys in the
+// kernel, from rn_seed[k] and the counter call_base[k] + call_j)
 static uint64_t rn_dropout_key(uint64_t rn_seed, uint64_t call) { return rn_seed ^ (call * 0x9E3779B97F4A7C15ull); }
 
 // the reward network's population block (the call sets the strides of its flow: s_state, s_action, s_n, s_next, s_w)
-// (rn_call0_k: the per-learner reward-call counters [K] of the *_irl_pop_calls entry points, NULL: the shared rn_call0;
-//  net_stride: elements between two learners' weights, 0: the numel strides of the stacked tensors)
-static RnPop rn_pop_args(int K, int per_learner_net, int64_t net_stride, const uint64_t* rn_seed, const uint64_t* rn_call0_k,
-                         size_t workspace_bytes, const mfg_rn_geom_t* geom_dev = nullptr) {
+// (rn_call0: the per-learner reward-call counters [K]; net_stride: elements between two learners' weights, 0: the numel
+//  strides of the stacked tensors; geom_dev: the geometry table, NULL without one)
+static RnPop rn_pop_args(int K, int per_learner_net, int64_t net_stride, const uint64_t* rn_seed, const uint64_t* rn_call0,
+                         size_t workspace_bytes, const mfg_rn_geom_t* geom_dev) {
   RnPop rp{};
   rp.K = K;
   rp.per_learner_net = per_learner_net ? 1 : 0;
   rp.s_ws = (int64_t)workspace_bytes;
   rp.rn_seed = rn_seed;
-  rp.call_base = rn_call0_k;
+  rp.call_base = rn_call0;
   rp.s_net = per_learner_net ? net_stride : 0;
   rp.geom = geom_dev;
   return rp;
@@ -3410,10 +3410,7 @@ static int train_episode_irl_step(const float* mat_pi0, int64_t num_start, float
       s_th_in = (int64_t)workspace_bytes;
     }
     const uint64_t call = rn_call0 + (uint64_t)s + 1ull;
-    if (rp) {
-      rp->key_ctr = rn_dropout_key(0, call);
-      rp->call_j = call;  // (read with per-learner counters only, which come with rn_call0 = 0: the call's own count)
-    }
+    if (rp) rp->call_j = call;  // (a population passes rn_call0 = its own count: learner k's counter is rp->call_base[k])
     RnSums sm{};
     sm.g = g;
     sm.delta_out = delta;
@@ -3537,16 +3534,17 @@ static int train_episode_irl_impl(const float* mat_pi0, int64_t num_start, float
                                    rn_sample_offset, P, reward, delta, g, G, reward_acc, workspace, workspace_bytes, S(stream));
 }
 
-static int train_episodes_irl_pop(const float* mat_pi0, int64_t num_start, float* pi_out, float* pi_scratch, int64_t B, int K, int d,
-                                  int T, int64_t episodes, int64_t first_episode, int constant, double* theta, const double* shift,
-                                  const double* alpha_scale, double* w, double gamma, const uint64_t* seed, uint32_t first_step,
-                                  uint64_t traj_offset, int precision, const double* lr_critic, const double* lr_actor,
-                                  const mfg_reward_net_t* net, int per_learner_net, int64_t net_stride, const uint64_t* rn_seed,
-                                  uint64_t rn_call0, const uint64_t* rn_call0_k, float* P, float* reward, double* delta, double* g,
-                                  double* G, double* reward_acc, void* workspace, size_t workspace_bytes, mfg_stream_t stream,
-                                  bool geom_given = false, const mfg_rn_geom_t* geom_host = nullptr,
-                                  const mfg_rn_geom_t* geom_dev = nullptr) {
-  REQUIRE(pi_out && pi_scratch, "null pointer");
+// The IRL populations (include/mfg_hip.h): K learners in the launches of one, with or without a geometry table; rn_call0 [K].
+// step mode: `episodes` x train_episode_irl_step over all K
+int mfg_train_episodes_irl_pop(const float* mat_pi0, int64_t num_start, float* pi_out, float* pi_scratch, int64_t B, int K, int d,
+                               int T, int64_t episodes, int64_t first_episode, int constant, double* theta, const double* shift,
+                               const double* alpha_scale, double* w, double gamma, const uint64_t* seed, uint32_t first_step,
+                               uint64_t traj_offset, int precision, const double* lr_critic, const double* lr_actor,
+                               const mfg_reward_net_t* net, int per_learner_net, int64_t net_stride,
+                               const mfg_rn_geom_t* geom_host, const mfg_rn_geom_t* geom_dev, const uint64_t* rn_seed,
+                               const uint64_t* rn_call0, float* P, float* reward, double* delta, double* g, double* G,
+                               double* reward_acc, void* workspace, size_t workspace_bytes, mfg_stream_t stream) {
+  REQUIRE(rn_call0 && pi_out && pi_scratch, "null pointer");
   IRL_POP_NETS();
   CHECK_IRL_POP();
   CHECK_PRECISION();
@@ -3557,7 +3555,7 @@ static int train_episodes_irl_pop(const float* mat_pi0, int64_t num_start, float
   PopArgs p = pop_args(K, B, d, 1, episodes, seed, shift, alpha_scale, lr_critic, lr_actor, workspace_bytes);
   p.s_n = B;
   p.s_P = B * d * d;
-  RnPop rp = rn_pop_args(K, per_learner_net, net_stride, rn_seed, rn_call0_k, workspace_bytes, geom_given ? geom_dev : nullptr);
+  RnPop rp = rn_pop_args(K, per_learner_net, net_stride, rn_seed, rn_call0, workspace_bytes, geom_dev);
   rp.s_state = rp.s_next = B * d;
   rp.s_action = B * d * d;
   rp.s_n = B;
@@ -3569,7 +3567,7 @@ static int train_episodes_irl_pop(const float* mat_pi0, int64_t num_start, float
     lr_schedule(first_episode + e, constant, &p.sc, &p.sa);
     const int rc = train_episode_irl_step(mat_pi0, num_start, pi_out, pi_scratch, B, d, T, theta, 0.0, 0.0, w, gamma, 0,
                                           first_step + (uint32_t)(e * T), traj_offset, precision, 0.0, 0.0, *net, 0,
-                                          rn_call0 + (uint64_t)(e * T), traj_offset, P, reward, delta, g, G,
+                                          (uint64_t)(e * T), traj_offset, P, reward, delta, g, G,
                                           reward_acc ? reward_acc + e : nullptr, workspace, workspace_bytes, S(stream), &p, &rp);
     if (rc != MFG_OK) return rc;
     pc.retire();
@@ -3577,16 +3575,16 @@ static int train_episodes_irl_pop(const float* mat_pi0, int64_t num_start, float
   return MFG_OK;
 }
 
-static int train_rollouts_irl_pop(const float* mat_pi0, int64_t num_start, int64_t B, int K, int d, int T, int64_t episodes,
-                                  int64_t first_episode, int constant, double* theta, const double* shift, const double* alpha_scale,
-                                  double* w, double gamma, const uint64_t* seed, uint32_t first_step, uint64_t traj_offset, int flags,
-                                  const double* lr_critic, const double* lr_actor, const mfg_reward_net_t* net, int per_learner_net,
-                                  int64_t net_stride, const uint64_t* rn_seed, uint64_t rn_call0, const uint64_t* rn_call0_k,
-                                  float* pi_traj, float* pi_last, float* P, float* reward, double* delta, double* g, double* G,
-                                  double* reward_acc, void* workspace, size_t workspace_bytes, mfg_stream_t stream,
-                                  bool geom_given = false, const mfg_rn_geom_t* geom_host = nullptr,
-                                  const mfg_rn_geom_t* geom_dev = nullptr) {
-  REQUIRE(pi_traj, "null pointer");
+// rollout mode: `episodes` x train_rollout_impl with the reward network as its ExtReward
+int mfg_train_rollouts_irl_pop(const float* mat_pi0, int64_t num_start, int64_t B, int K, int d, int T, int64_t episodes,
+                               int64_t first_episode, int constant, double* theta, const double* shift, const double* alpha_scale,
+                               double* w, double gamma, const uint64_t* seed, uint32_t first_step, uint64_t traj_offset, int flags,
+                               const double* lr_critic, const double* lr_actor, const mfg_reward_net_t* net, int per_learner_net,
+                               int64_t net_stride, const mfg_rn_geom_t* geom_host, const mfg_rn_geom_t* geom_dev,
+                               const uint64_t* rn_seed, const uint64_t* rn_call0, float* pi_traj, float* pi_last, float* P,
+                               float* reward, double* delta, double* g, double* G, double* reward_acc, void* workspace,
+                               size_t workspace_bytes, mfg_stream_t stream) {
+  REQUIRE(rn_call0 && pi_traj, "null pointer");
   IRL_POP_NETS();
   CHECK_IRL_POP();
   const size_t need = pop_workspace_need(d, B * T, false);
@@ -3598,7 +3596,7 @@ static int train_rollouts_irl_pop(const float* mat_pi0, int64_t num_start, int64
   p.s_gpi = p.s_traj;
   p.s_n = B * T;
   p.s_P = B * T * d * d;
-  RnPop rp = rn_pop_args(K, per_learner_net, net_stride, rn_seed, rn_call0_k, workspace_bytes, geom_given ? geom_dev : nullptr);
+  RnPop rp = rn_pop_args(K, per_learner_net, net_stride, rn_seed, rn_call0, workspace_bytes, geom_dev);
   rp.s_state = B * (T + 1) * d;
   rp.s_action = B * T * d * d;
   rp.s_n = B * T;
@@ -3608,7 +3606,6 @@ static int train_rollouts_irl_pop(const float* mat_pi0, int64_t num_start, int64
   const ExtReward ext{net, P, 0, traj_offset * (uint64_t)T, &rp};
   for (int64_t e = 0; e < episodes; ++e) {
     lr_schedule(first_episode + e, constant, &p.sc, &p.sa);
-    rp.key_ctr = rn_dropout_key(0, rn_call0 + (uint64_t)e + 1ull);
     rp.call_j = (uint64_t)e + 1ull;
     const int rc = train_rollout_impl(mat_pi0, num_start, nullptr, B, d, T, theta, 0.0, 0.0, w, gamma, MFG_REWARD_EXTERNAL, 0,
                                       first_step + (uint32_t)(e * T), traj_offset, flags | MFG_TRAIN_APPLY, 0.0, 0.0, pi_traj,
@@ -3618,93 +3615,6 @@ static int train_rollouts_irl_pop(const float* mat_pi0, int64_t num_start, int64
     pc.retire();
   }
   return MFG_OK;
-}
-
-int mfg_train_episodes_irl_pop(const float* mat_pi0, int64_t num_start, float* pi_out, float* pi_scratch, int64_t B, int K, int d,
-                               int T, int64_t episodes, int64_t first_episode, int constant, double* theta, const double* shift,
-                               const double* alpha_scale, double* w, double gamma, const uint64_t* seed, uint32_t first_step,
-                               uint64_t traj_offset, int precision, const double* lr_critic, const double* lr_actor,
-                               const mfg_reward_net_t* net, int per_learner_net, const uint64_t* rn_seed, uint64_t rn_call0,
-                               float* P, float* reward, double* delta, double* g, double* G, double* reward_acc, void* workspace,
-                               size_t workspace_bytes, mfg_stream_t stream) {
-  return train_episodes_irl_pop(mat_pi0, num_start, pi_out, pi_scratch, B, K, d, T, episodes, first_episode, constant, theta, shift,
-                                alpha_scale, w, gamma, seed, first_step, traj_offset, precision, lr_critic, lr_actor, net,
-                                per_learner_net, 0, rn_seed, rn_call0, nullptr, P, reward, delta, g, G, reward_acc, workspace,
-                                workspace_bytes, stream);
-}
-
-int mfg_train_episodes_irl_pop_calls(const float* mat_pi0, int64_t num_start, float* pi_out, float* pi_scratch, int64_t B, int K,
-                                     int d, int T, int64_t episodes, int64_t first_episode, int constant, double* theta,
-                                     const double* shift, const double* alpha_scale, double* w, double gamma, const uint64_t* seed,
-                                     uint32_t first_step, uint64_t traj_offset, int precision, const double* lr_critic,
-                                     const double* lr_actor, const mfg_reward_net_t* net, int per_learner_net, int64_t net_stride,
-                                     const uint64_t* rn_seed, const uint64_t* rn_call0, float* P, float* reward, double* delta,
-                                     double* g, double* G, double* reward_acc, void* workspace, size_t workspace_bytes,
-                                     mfg_stream_t stream) {
-  REQUIRE(rn_call0, "null pointer");
-  return train_episodes_irl_pop(mat_pi0, num_start, pi_out, pi_scratch, B, K, d, T, episodes, first_episode, constant, theta, shift,
-                                alpha_scale, w, gamma, seed, first_step, traj_offset, precision, lr_critic, lr_actor, net,
-                                per_learner_net, net_stride, rn_seed, 0, rn_call0, P, reward, delta, g, G, reward_acc, workspace,
-                                workspace_bytes, stream);
-}
-
-int mfg_train_rollouts_irl_pop(const float* mat_pi0, int64_t num_start, int64_t B, int K, int d, int T, int64_t episodes,
-                               int64_t first_episode, int constant, double* theta, const double* shift, const double* alpha_scale,
-                               double* w, double gamma, const uint64_t* seed, uint32_t first_step, uint64_t traj_offset, int flags,
-                               const double* lr_critic, const double* lr_actor, const mfg_reward_net_t* net, int per_learner_net,
-                               const uint64_t* rn_seed, uint64_t rn_call0, float* pi_traj, float* pi_last, float* P, float* reward,
-                               double* delta, double* g, double* G, double* reward_acc, void* workspace, size_t workspace_bytes,
-                               mfg_stream_t stream) {
-  return train_rollouts_irl_pop(mat_pi0, num_start, B, K, d, T, episodes, first_episode, constant, theta, shift, alpha_scale, w,
-                                gamma, seed, first_step, traj_offset, flags, lr_critic, lr_actor, net, per_learner_net, 0, rn_seed,
-                                rn_call0, nullptr, pi_traj, pi_last, P, reward, delta, g, G, reward_acc, workspace,
-                                workspace_bytes, stream);
-}
-
-int mfg_train_rollouts_irl_pop_calls(const float* mat_pi0, int64_t num_start, int64_t B, int K, int d, int T, int64_t episodes,
-                                     int64_t first_episode, int constant, double* theta, const double* shift,
-                                     const double* alpha_scale, double* w, double gamma, const uint64_t* seed, uint32_t first_step,
-                                     uint64_t traj_offset, int flags, const double* lr_critic, const double* lr_actor,
-                                     const mfg_reward_net_t* net, int per_learner_net, int64_t net_stride, const uint64_t* rn_seed,
-                                     const uint64_t* rn_call0, float* pi_traj, float* pi_last, float* P, float* reward,
-                                     double* delta, double* g, double* G, double* reward_acc, void* workspace,
-                                     size_t workspace_bytes, mfg_stream_t stream) {
-  REQUIRE(rn_call0, "null pointer");
-  return train_rollouts_irl_pop(mat_pi0, num_start, B, K, d, T, episodes, first_episode, constant, theta, shift, alpha_scale, w,
-                                gamma, seed, first_step, traj_offset, flags, lr_critic, lr_actor, net, per_learner_net, net_stride,
-                                rn_seed, 0, rn_call0, pi_traj, pi_last, P, reward, delta, g, G, reward_acc, workspace,
-                                workspace_bytes, stream);
-}
-
-int mfg_train_episodes_irl_pop_nets(const float* mat_pi0, int64_t num_start, float* pi_out, float* pi_scratch, int64_t B, int K,
-                                    int d, int T, int64_t episodes, int64_t first_episode, int constant, double* theta,
-                                    const double* shift, const double* alpha_scale, double* w, double gamma, const uint64_t* seed,
-                                    uint32_t first_step, uint64_t traj_offset, int precision, const double* lr_critic,
-                                    const double* lr_actor, const mfg_reward_net_t* net, int per_learner_net, int64_t net_stride,
-                                    const mfg_rn_geom_t* geom_host, const mfg_rn_geom_t* geom_dev, const uint64_t* rn_seed,
-                                    const uint64_t* rn_call0, float* P, float* reward, double* delta, double* g, double* G,
-                                    double* reward_acc, void* workspace, size_t workspace_bytes, mfg_stream_t stream) {
-  REQUIRE(rn_call0, "null pointer");
-  return train_episodes_irl_pop(mat_pi0, num_start, pi_out, pi_scratch, B, K, d, T, episodes, first_episode, constant, theta, shift,
-                                alpha_scale, w, gamma, seed, first_step, traj_offset, precision, lr_critic, lr_actor, net,
-                                per_learner_net, net_stride, rn_seed, 0, rn_call0, P, reward, delta, g, G, reward_acc, workspace,
-                                workspace_bytes, stream, true, geom_host, geom_dev);
-}
-
-int mfg_train_rollouts_irl_pop_nets(const float* mat_pi0, int64_t num_start, int64_t B, int K, int d, int T, int64_t episodes,
-                                    int64_t first_episode, int constant, double* theta, const double* shift,
-                                    const double* alpha_scale, double* w, double gamma, const uint64_t* seed, uint32_t first_step,
-                                    uint64_t traj_offset, int flags, const double* lr_critic, const double* lr_actor,
-                                    const mfg_reward_net_t* net, int per_learner_net, int64_t net_stride,
-                                    const mfg_rn_geom_t* geom_host, const mfg_rn_geom_t* geom_dev, const uint64_t* rn_seed,
-                                    const uint64_t* rn_call0, float* pi_traj, float* pi_last, float* P, float* reward,
-                                    double* delta, double* g, double* G, double* reward_acc, void* workspace,
-                                    size_t workspace_bytes, mfg_stream_t stream) {
-  REQUIRE(rn_call0, "null pointer");
-  return train_rollouts_irl_pop(mat_pi0, num_start, B, K, d, T, episodes, first_episode, constant, theta, shift, alpha_scale, w,
-                                gamma, seed, first_step, traj_offset, flags, lr_critic, lr_actor, net, per_learner_net, net_stride,
-                                rn_seed, 0, rn_call0, pi_traj, pi_last, P, reward, delta, g, G, reward_acc, workspace,
-                                workspace_bytes, stream, true, geom_host, geom_dev);
 }
 
 int mfg_train_rollout_irl(const float* mat_pi0, int64_t num_start, const int32_t* idx, int64_t B, int d, int T, double* theta,

@@ -1470,15 +1470,15 @@ extern "C" int mfg_reward_net_forward(const float* state, const float* action, i
   return mfg::reward_net_forward_sums(state, action, B, d, net, seed, sample_offset, reward, nullptr, nullptr, (hipStream_t)stream);
 }
 
-// mfg_reward_net_forward_pop with (geom_given) or without a geometry table
-static int reward_net_forward_pop_impl(const float* state, const float* action, int64_t s_state, int64_t s_action, int64_t N,
-                                       int d, const mfg_reward_net_t* net, int per_learner_net, int64_t net_stride,
-                                       bool geom_given, const mfg_rn_geom_t* geom_host, const mfg_rn_geom_t* geom_dev, int K,
-                                       const int32_t* learners_host, const uint64_t* keys_host, int n, uint64_t sample_offset,
-                                       float* reward, void* scratch, size_t scratch_bytes, mfg_stream_t stream) {
-  mfg_reward_net_t nm;  // with a table: the launch's network = the row base and the table's maxima
-  if (geom_given) {
-    if (!net || !net->conv1_w) return set_error(MFG_EINVAL, "reward_net_forward_pop_nets: null pointer");
+// (geom_host / geom_dev given: the launch's network = the row base and the table's maxima)
+extern "C" int mfg_reward_net_forward_pop(const float* state, const float* action, int64_t s_state, int64_t s_action, int64_t N,
+                                          int d, const mfg_reward_net_t* net, int per_learner_net, int64_t net_stride,
+                                          const mfg_rn_geom_t* geom_host, const mfg_rn_geom_t* geom_dev, int K,
+                                          const int32_t* learners_host, const uint64_t* keys_host, int n, uint64_t sample_offset,
+                                          float* reward, void* scratch, size_t scratch_bytes, mfg_stream_t stream) {
+  mfg_reward_net_t nm;
+  if (geom_host || geom_dev) {
+    if (!net || !net->conv1_w) return set_error(MFG_EINVAL, "reward_net_forward_pop: null pointer");
     int rc = rn_pop_nets_struct(net, geom_host, geom_dev, K, d, per_learner_net, net_stride, &nm);
     if (rc != MFG_OK) return rc;
     net = &nm;
@@ -1516,26 +1516,8 @@ static int reward_net_forward_pop_impl(const float* state, const float* action, 
   rp.key = (const uint64_t*)scratch;
   rp.learner = (const int32_t*)((const char*)scratch + (size_t)n * 8);
   rp.n_y = n;
-  rp.geom = geom_given ? geom_dev : nullptr;
+  rp.geom = geom_dev;
   return reward_net_forward_sums(state, action, N, d, *net, 0, sample_offset, reward, nullptr, nullptr, st, 0, &rp);
-}
-
-extern "C" int mfg_reward_net_forward_pop(const float* state, const float* action, int64_t s_state, int64_t s_action, int64_t N,
-                                          int d, const mfg_reward_net_t* net, int per_learner_net, int64_t net_stride, int K,
-                                          const int32_t* learners_host, const uint64_t* keys_host, int n, uint64_t sample_offset,
-                                          float* reward, void* scratch, size_t scratch_bytes, mfg_stream_t stream) {
-  return reward_net_forward_pop_impl(state, action, s_state, s_action, N, d, net, per_learner_net, net_stride, false, nullptr,
-                                     nullptr, K, learners_host, keys_host, n, sample_offset, reward, scratch, scratch_bytes, stream);
-}
-
-extern "C" int mfg_reward_net_forward_pop_nets(const float* state, const float* action, int64_t s_state, int64_t s_action,
-                                               int64_t N, int d, const mfg_reward_net_t* net, int per_learner_net,
-                                               int64_t net_stride, const mfg_rn_geom_t* geom_host, const mfg_rn_geom_t* geom_dev,
-                                               int K, const int32_t* learners_host, const uint64_t* keys_host, int n,
-                                               uint64_t sample_offset, float* reward, void* scratch, size_t scratch_bytes,
-                                               mfg_stream_t stream) {
-  return reward_net_forward_pop_impl(state, action, s_state, s_action, N, d, net, per_learner_net, net_stride, true, geom_host,
-                                     geom_dev, K, learners_host, keys_host, n, sample_offset, reward, scratch, scratch_bytes, stream);
 }
 
 #ifdef MFG_RN_STAMPS

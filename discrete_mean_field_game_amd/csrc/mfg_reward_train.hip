@@ -816,14 +816,24 @@ int mfg_reward_net_adam(float* params, float* adam_m, float* adam_v, const float
   return hipGetLastError() == hipSuccess ? MFG_OK : set_error(MFG_ELAUNCH, "reward_net_adam: launch failed");
 }
 
-// mfg_reward_net_train_steps_pop; geom_given: n3 / n4 are the maxima of the (checked) table, which the kernels read per learner
-static int reward_net_train_steps_pop_impl(float* params, float* adam_m, float* adam_v, int64_t param_stride, int K, int d, int k1,
-                                           int f2, int k2, int n3, int n4, const mfg_rn_geom_t* geom_dev, int64_t np_max, const float* demo_state,
-                                           const float* demo_action, int64_t demo_capacity, const float* gen_state,
-                                           const float* gen_action, int64_t gen_capacity, mfg_rn_train_plan_t* plan_host,
-                                           void* plan_dev, size_t plan_dev_bytes, int n_updates, int n_active, int n_demo, int n_gen,
-                                           int steps, int demo_divisor, float keep_prob, int l1l2, double beta1, double beta2,
-                                           double eps, float* stats, void* workspace, size_t workspace_bytes, mfg_stream_t stream) {
+// (geom_host / geom_dev given: the table is checked first; the batch limits and the workspace slices are then those of its largest
+//  n3 / n4, which the kernels read per learner with keep_prob and l1l2 -- the arguments of those names are not read)
+int mfg_reward_net_train_steps_pop(float* params, float* adam_m, float* adam_v, int64_t param_stride, int K, int d, int k1, int f2,
+                                   int k2, int n3, int n4, const mfg_rn_geom_t* geom_host, const mfg_rn_geom_t* geom_dev,
+                                   const float* demo_state, const float* demo_action, int64_t demo_capacity,
+                                   const float* gen_state, const float* gen_action, int64_t gen_capacity,
+                                   mfg_rn_train_plan_t* plan_host, void* plan_dev, size_t plan_dev_bytes, int n_updates,
+                                   int n_active, int n_demo, int n_gen, int steps, int demo_divisor, float keep_prob, int l1l2,
+                                   double beta1, double beta2, double eps, float* stats, void* workspace, size_t workspace_bytes,
+                                   mfg_stream_t stream) {
+  int64_t np_max = 0;  // (the longest row of the table)
+  if (geom_host || geom_dev) {
+    const char* why = "";
+    const int rc = rn_geom_check(geom_host, geom_dev, K, d, k1, f2, k2, 1, param_stride, &n3, &n4, &np_max, &why);
+    if (rc != MFG_OK) return set_error(rc, why);
+    keep_prob = 1.0f;
+    l1l2 = 0;
+  }
   if (!params || !adam_m || !adam_v || !stats || !workspace || !plan_host || !plan_dev || K < 1 || n_updates < 0 ||
       n_active < 0 || n_active > K || n_demo < 0 || n_gen < 0 || steps < 1 || demo_divisor < 1 ||
       (n_demo && (!demo_state || !demo_action || demo_capacity < 1)) || (n_gen && (!gen_state || !gen_action || gen_capacity < 1)))
@@ -899,7 +909,7 @@ static int reward_net_train_steps_pop_impl(float* params, float* adam_m, float* 
   p.s_gen_action = gen_capacity * steps * d * d;
   p.s_ws = (int64_t)(slice / sizeof(float));
   p.geom = geom_dev;
-  const int64_t np_grid = geom_dev ? np_max : L.np;  // (the longest row of the table)
+  const int64_t np_grid = geom_dev ? np_max : L.np;
   const int h1 = k1 / 2, h2 = k2 / 2, W1 = d + 2 * h1, W2 = d + 2 * h2;
   const size_t lds = (size_t)(W1 * W1 + W2 * W2 + L.a2 + f2 * W2 * W2 + L.ns) * sizeof(float);
   const dim3 g1((unsigned)N + 1, (unsigned)n_active), g2((unsigned)((np_grid + RT_CP - 1) / RT_CP), (unsigned)n_active);
@@ -911,39 +921,6 @@ static int reward_net_train_steps_pop_impl(float* params, float* adam_m, float* 
     hipLaunchKernelGGL(k_rn_train_combine_pop, g2, dim3(RT_BLOCK), (size_t)N * (1 + n3) * sizeof(float), st, c, p);
   }
   return hipGetLastError() == hipSuccess ? MFG_OK : set_error(MFG_ELAUNCH, "reward_net_train_steps_pop: launch failed");
-}
-
-int mfg_reward_net_train_steps_pop(float* params, float* adam_m, float* adam_v, int64_t param_stride, int K, int d, int k1, int f2,
-                                   int k2, int n3, int n4, const float* demo_state, const float* demo_action, int64_t demo_capacity,
-                                   const float* gen_state, const float* gen_action, int64_t gen_capacity,
-                                   mfg_rn_train_plan_t* plan_host, void* plan_dev, size_t plan_dev_bytes, int n_updates,
-                                   int n_active, int n_demo, int n_gen, int steps, int demo_divisor, float keep_prob, int l1l2,
-                                   double beta1, double beta2, double eps, float* stats, void* workspace, size_t workspace_bytes,
-                                   mfg_stream_t stream) {
-  return reward_net_train_steps_pop_impl(params, adam_m, adam_v, param_stride, K, d, k1, f2, k2, n3, n4, nullptr, 0, demo_state,
-                                         demo_action, demo_capacity, gen_state, gen_action, gen_capacity, plan_host, plan_dev,
-                                         plan_dev_bytes, n_updates, n_active, n_demo, n_gen, steps, demo_divisor, keep_prob, l1l2,
-                                         beta1, beta2, eps, stats, workspace, workspace_bytes, stream);
-}
-
-int mfg_reward_net_train_steps_pop_nets(float* params, float* adam_m, float* adam_v, int64_t param_stride, int K, int d, int k1,
-                                        int f2, int k2, const mfg_rn_geom_t* geom_host, const mfg_rn_geom_t* geom_dev,
-                                        const float* demo_state, const float* demo_action, int64_t demo_capacity,
-                                        const float* gen_state, const float* gen_action, int64_t gen_capacity,
-                                        mfg_rn_train_plan_t* plan_host, void* plan_dev, size_t plan_dev_bytes, int n_updates,
-                                        int n_active, int n_demo, int n_gen, int steps, int demo_divisor, double beta1,
-                                        double beta2, double eps, float* stats, void* workspace, size_t workspace_bytes,
-                                        mfg_stream_t stream) {
-  int n3m = 0, n4m = 0;
-  int64_t npm = 0;
-  const char* why = "";
-  const int rc = rn_geom_check(geom_host, geom_dev, K, d, k1, f2, k2, 1, param_stride, &n3m, &n4m, &npm, &why);
-  if (rc != MFG_OK) return set_error(rc, why);
-  // the batch limits and the workspace slices at the largest n3 / n4; keep_prob and l1l2 of the launch are never read
-  return reward_net_train_steps_pop_impl(params, adam_m, adam_v, param_stride, K, d, k1, f2, k2, n3m, n4m, geom_dev, npm,
-                                         demo_state, demo_action, demo_capacity, gen_state, gen_action, gen_capacity, plan_host,
-                                         plan_dev, plan_dev_bytes, n_updates, n_active, n_demo, n_gen, steps, demo_divisor, 1.0f, 0,
-                                         beta1, beta2, eps, stats, workspace, workspace_bytes, stream);
 }
 
 }  // extern "C"

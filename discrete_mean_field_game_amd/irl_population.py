@@ -36,7 +36,7 @@ Mixed populations (mixed_nets=True): the learners' networks may differ in n_fc3,
 the reference's sweep gridsearch.py:8-31.  Each learner's parameters are one flat row of a [K, stride] buffer in its OWN layout
 (mfg_reward_net_param_offsets of its geometry; stride = the longest row rounded up to PARAM_ALIGN, tails zero and never
 written), the Adam moments likewise, and a geometry table (mfg_rn_geom_t, one 16-byte entry per learner, host and device)
-tells the kernels of the *_nets entry points which shape a learner's blocks run.  Learner k still gives exactly what AC_IRL
+tells the kernels of the population calls which shape a learner's blocks run.  Learner k still gives exactly what AC_IRL
 gives with learner k's shape and regulariser.  test_reward_network() is AC_IRL.test_reward_network for every learner, and
 gridsearch() below runs the reference's sweep as one such population.
 
@@ -105,8 +105,8 @@ def draw_batches(rng, nd_all, ng_all, n_updates, n_demo=NUM_DEMO_SAMPLES, n_gen=
     return out
 
 
-def check_args(K, d, batch, update_every, precision, reward_nets):
-    """Validation of the constructor's arguments (no GPU needed); returns the networks as a list (1 = shared)."""
+def _check_common(K, d, batch, update_every, precision):
+    """The checks check_args and check_args_mixed share, ahead of those on the networks."""
     if K < 1 or K > L.POP_MAX_K:
         raise ValueError('population size %d outside [1, %d]' % (K, L.POP_MAX_K))
     if d not in ops.IRL_POP_D:
@@ -118,41 +118,39 @@ def check_args(K, d, batch, update_every, precision, reward_nets):
         raise ValueError("update_every must be 'step' or 'rollout'")
     if precision not in ('mixed', 'f64'):
         raise ValueError("precision must be 'mixed' or 'f64'")
+
+
+def _check_nets(nets, d, geometry):
+    """... and behind them: RewardNet modules of the population's d; returns what `geometry` (ops.irl_pop_net_geometry /
+    ops.irl_pop_net_geometries) gives behind d."""
+    if not all(isinstance(n, RewardNet) for n in nets):
+        raise ValueError('reward_nets: expected networks.RewardNet modules')
+    nd, *rest = geometry(nets)
+    if nd != d:
+        raise ValueError('reward network d=%d, population d=%d' % (nd, d))
+    return rest
+
+
+def check_args(K, d, batch, update_every, precision, reward_nets):
+    """Validation of the constructor's arguments (no GPU needed); returns the networks as a list (1 = shared)."""
+    _check_common(K, d, batch, update_every, precision)
     nets = [reward_nets] if isinstance(reward_nets, torch.nn.Module) else list(reward_nets)
     if len(nets) not in (1, K):
         raise ValueError('reward_nets: one network (shared) or %d (one per learner), got %d' % (K, len(nets)))
-    if not all(isinstance(n, RewardNet) for n in nets):
-        raise ValueError('reward_nets: expected networks.RewardNet modules')
-    nd, _, _, _ = ops.irl_pop_net_geometry(nets)
-    if nd != d:
-        raise ValueError('reward network d=%d, population d=%d' % (nd, d))
+    _check_nets(nets, d, ops.irl_pop_net_geometry)
     return nets
 
 
 def check_args_mixed(K, d, batch, update_every, precision, reward_nets):
     """check_args for a population with per-learner network shapes (mixed_nets=True): one network per learner, each inside the
     matrix-core kernel's limits, d / k1 / f2 / k2 shared.  Returns (networks, [(n3, n4, keep_prob, l1l2), ...])."""
-    if K < 1 or K > L.POP_MAX_K:
-        raise ValueError('population size %d outside [1, %d]' % (K, L.POP_MAX_K))
-    if d not in ops.IRL_POP_D:
-        raise ValueError('d=%d: IRL populations cover d = 15 / 21 (the matrix-core reward-network kernel)' % d)
-    if batch < 2:
-        raise ValueError('batch=%d: a population draws its start states on the device, which AC_IRL does from batch 2 on'
-                         % batch)
-    if update_every not in ('step', 'rollout'):
-        raise ValueError("update_every must be 'step' or 'rollout'")
-    if precision not in ('mixed', 'f64'):
-        raise ValueError("precision must be 'mixed' or 'f64'")
+    _check_common(K, d, batch, update_every, precision)
     if isinstance(reward_nets, torch.nn.Module):
         raise ValueError('mixed_nets: one network per learner is needed, got one shared network')
     nets = list(reward_nets)
     if len(nets) != K:
         raise ValueError('mixed_nets: one network per learner is needed (%d), got %d' % (K, len(nets)))
-    if not all(isinstance(n, RewardNet) for n in nets):
-        raise ValueError('reward_nets: expected networks.RewardNet modules')
-    nd, geoms = ops.irl_pop_net_geometries(nets)
-    if nd != d:
-        raise ValueError('reward network d=%d, population d=%d' % (nd, d))
+    geoms, = _check_nets(nets, d, ops.irl_pop_net_geometries)
     return nets, geoms
 
 
@@ -178,7 +176,7 @@ class AC_IRLPopulation(_Population):
         else:
             nets = check_args(K, int(d), int(batch), update_every, precision, reward_nets)
         self.mixed_nets = bool(mixed_nets)
-        self._geom = None                      # (host table, device copy) of the *_nets entry points
+        self._geom = None                      # (host table, device copy) of a mixed population (None: no table)
         test_np = check_demonstrations(demonstrations_test, int(d)) if demonstrations_test else None
         lr_reward = broadcast('lr_reward', lr_reward, K)
         if int(num_policies) < 1:
@@ -236,7 +234,7 @@ class AC_IRLPopulation(_Population):
                     self._net_params[field] = torch.stack(ts).contiguous()
         st = L.RewardNetStruct()
         st.k1, st.f2, st.k2 = nets[0].conv1.kernel_size[0], nets[0].conv2.out_channels, nets[0].conv2.kernel_size[0]
-        if mixed_nets:      # conv1_w = the base of row 0 is what the *_nets entry points read; n3 / n4: the largest
+        if mixed_nets:      # conv1_w = the base of row 0 is what the calls read with a table; n3 / n4: the largest
             st.n3, st.n4 = self._rn_dims[4], self._rn_dims[5]
             for field, _ in NET_TENSORS:
                 setattr(st, field, self._flat.data_ptr())

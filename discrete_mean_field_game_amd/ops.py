@@ -635,59 +635,55 @@ IRL_POP_D = (15, 21)     # the matrix-core reward-network kernel's sizes (mfg_tr
 IRL_POP_MAX_FC3 = 16
 
 
-def irl_pop_net_geometry(nets):
-    """(d, n_fc3, n_fc4, keep_prob) shared by the networks.RewardNet modules `nets`; ValueError where they differ or where the
-    matrix-core reward-network kernel does not serve them (d = 15 / 21, k1 = 5, f2 = 2, k2 = 3, n_fc3 <= 16, n_fc4 <= 32)."""
-    if not nets:
-        raise ValueError('no reward network')
-    def geom(n):
-        return (n.d, n.conv1.out_channels, n.conv1.kernel_size[0], n.conv2.out_channels, n.conv2.kernel_size[0],
-                n.fc3.out_features, n.fc4.out_features)
-    def keep(n):
-        return float(n.keep_prob) if (n.use_dropout and (n.dropout_always or n.training)) else 1.0
-    g0, k0 = geom(nets[0]), keep(nets[0])
-    for n in nets[1:]:
-        if geom(n) != g0:
-            raise ValueError('reward networks of one population must share their geometry: %s vs %s' % (geom(n), g0))
-        if keep(n) != k0:
-            raise ValueError('reward networks of one population must share their dropout setting: keep %g vs %g' % (keep(n), k0))
-    d, f1, k1, f2, k2, n3, n4 = g0
-    if d not in IRL_POP_D or f1 != 1 or k1 != 5 or f2 != 2 or k2 != 3 or not 1 <= n3 <= IRL_POP_MAX_FC3 or not 1 <= n4 <= 32:
-        raise ValueError('reward network d=%d, f1=%d, k1=%d, f2=%d, k2=%d, n_fc3=%d, n_fc4=%d: IRL populations need the '
-                         'matrix-core kernel (d = 15 / 21, 1 / 5 / 2 / 3, n_fc3 <= %d, n_fc4 <= 32)'
-                         % (d, f1, k1, f2, k2, n3, n4, IRL_POP_MAX_FC3))
-    return d, n3, n4, k0
+def _irl_pop_net_shape(n):
+    """((d, f1, k1, f2, k2, n_fc3, n_fc4), keep_prob in effect) of a networks.RewardNet."""
+    keep = float(n.keep_prob) if (n.use_dropout and (n.dropout_always or n.training)) else 1.0
+    return (n.d, n.conv1.out_channels, n.conv1.kernel_size[0], n.conv2.out_channels, n.conv2.kernel_size[0],
+            n.fc3.out_features, n.fc4.out_features), keep
 
 
 def irl_pop_net_geometries(nets):
     """(d, [(n_fc3, n_fc4, keep_prob, l1l2), ...]) of the networks.RewardNet modules `nets`, one entry per network: what a
-    population with a per-learner geometry table (mfg_rn_geom_t, the *_nets entry points) reads.  d, k1 = 5, f2 = 2, k2 = 3 are
-    shared; ValueError where they differ or an entry is outside the matrix-core kernel (d = 15 / 21, n_fc3 <= 16, n_fc4 <= 32,
-    keep_prob in (0, 1])."""
+    population with a per-learner geometry table (mfg_rn_geom_t) reads.  d, k1 = 5, f2 = 2, k2 = 3 are shared; ValueError where
+    they differ or an entry is outside the matrix-core kernel (d = 15 / 21, n_fc3 <= 16, n_fc4 <= 32, keep_prob in (0, 1])."""
     if not nets:
         raise ValueError('no reward network')
     d0, out = nets[0].d, []
     for n in nets:
-        d, f1, k1, f2, k2 = n.d, n.conv1.out_channels, n.conv1.kernel_size[0], n.conv2.out_channels, n.conv2.kernel_size[0]
-        n3, n4 = n.fc3.out_features, n.fc4.out_features
+        (d, f1, k1, f2, k2, n3, n4), keep = _irl_pop_net_shape(n)
         if d != d0:
             raise ValueError('reward networks of one population must share d: %d vs %d' % (d, d0))
         if d not in IRL_POP_D or f1 != 1 or k1 != 5 or f2 != 2 or k2 != 3 or not 1 <= n3 <= IRL_POP_MAX_FC3 or not 1 <= n4 <= 32:
             raise ValueError('reward network d=%d, f1=%d, k1=%d, f2=%d, k2=%d, n_fc3=%d, n_fc4=%d: IRL populations need the '
                              'matrix-core kernel (d = 15 / 21, 1 / 5 / 2 / 3, n_fc3 <= %d, n_fc4 <= 32)'
                              % (d, f1, k1, f2, k2, n3, n4, IRL_POP_MAX_FC3))
-        keep = float(n.keep_prob) if (n.use_dropout and (n.dropout_always or n.training)) else 1.0
         if not 0.0 < keep <= 1.0:
             raise ValueError('reward network keep_prob=%g outside (0, 1]' % keep)
         out.append((n3, n4, keep, bool(n.use_l1l2)))
     return d0, out
 
 
+def irl_pop_net_geometry(nets):
+    """(d, n_fc3, n_fc4, keep_prob) shared by the networks.RewardNet modules `nets`; ValueError where they differ or where the
+    matrix-core reward-network kernel does not serve them (d = 15 / 21, k1 = 5, f2 = 2, k2 = 3, n_fc3 <= 16, n_fc4 <= 32)."""
+    if not nets:
+        raise ValueError('no reward network')
+    g0, k0 = _irl_pop_net_shape(nets[0])
+    for n in nets[1:]:
+        g, k = _irl_pop_net_shape(n)
+        if g != g0:
+            raise ValueError('reward networks of one population must share their geometry: %s vs %s' % (g, g0))
+        if k != k0:
+            raise ValueError('reward networks of one population must share their dropout setting: keep %g vs %g' % (k, k0))
+    d, ((n3, n4, keep, _),) = irl_pop_net_geometries(nets[:1])      # (all equal: the kernel's limits, checked once)
+    return d, n3, n4, keep
+
+
 RN_GEOM = None           # numpy dtype of mfg_rn_geom_t (L.RnGeomStruct)
 
 
 def rn_geom_table(geoms, device=None):
-    """The geometry table of the *_nets entry points from [(n3, n4, keep_prob, l1l2), ...]: (host NumPy array of mfg_rn_geom_t,
+    """The geometry table of the IRL population calls from [(n3, n4, keep_prob, l1l2), ...]: (host NumPy array of mfg_rn_geom_t,
     its device copy as a uint8 tensor, or None without a device)."""
     import numpy as np
     global RN_GEOM
@@ -703,13 +699,23 @@ def rn_geom_table(geoms, device=None):
 
 
 def _geom_ptrs(geom, K):
-    """(host pointer, device pointer) of a table built by rn_geom_table, [K] entries."""
+    """(host pointer, device pointer) of a table built by rn_geom_table, [K] entries; two NULLs for geom = None."""
+    if geom is None:
+        return None, None
     host, dev = geom
     if host.shape != (K,) or host.dtype.itemsize != 16 or not host.flags['C_CONTIGUOUS']:
         raise ValueError('geometry table: expected %d contiguous mfg_rn_geom_t entries on the host' % K)
     if dev is None or not dev.is_cuda or not dev.is_contiguous() or dev.numel() * dev.element_size() != 16 * K:
         raise ValueError('geometry table: expected a contiguous device copy of %d bytes' % (16 * K))
     return host.ctypes.data, dev.data_ptr()
+
+
+def _rn_call0_ptr(rn_call0, K, like):
+    """The per-learner reward-call counters [K] (int64 device array); an int counts for every learner."""
+    if not isinstance(rn_call0, torch.Tensor):
+        rn_call0 = torch.full((K,), int(rn_call0), dtype=torch.int64, device=like.device)
+    _chk_pop(K, 'rn_call0', rn_call0, torch.int64)
+    return rn_call0
 
 
 def _chk_irl_pop(K, B, d, T, episodes, theta, w, G, ws, bufs, reward_acc, mat_pi0, per_learner, shifts, alpha_scales,
@@ -732,10 +738,9 @@ def train_episodes_irl_pop(mat_pi0, pi, T, episodes, first_episode, constant, th
     rn_seeds int64 (read as uint64) device arrays [K]; net_struct = reward_net_struct(...) of the shared network or of the
     stacked parameters (per_learner_net); bufs = dict(scratch [K,Bk,d] f32, P [K,Bk,d,d] f32, reward [K,Bk] f32, delta / g
     [K,Bk] f64); reward_acc [K,episodes] fp64 or None.  The episode numbers of the schedule start at first_episode.
-    rn_call0: the shared reward-call counter (int), or an int64 device array [K] of per-learner counters
-    (mfg_train_episodes_irl_pop_calls); net_stride: elements between two learners' weights in one flat buffer (0: stacked
-    tensors).  geom: a per-learner geometry table (rn_geom_table) -- mfg_train_episodes_irl_pop_nets; needs the counter array
-    and net_stride > 0, and net_struct.conv1_w as the base of learner 0's flat row."""
+    rn_call0: the reward calls made before, an int64 device array [K] of per-learner counters or an int for all of them;
+    net_stride: elements between two learners' weights in one flat buffer (0: stacked tensors).  geom: a per-learner geometry
+    table (rn_geom_table); needs net_stride > 0 and net_struct.conv1_w as the base of learner 0's flat row."""
     import ctypes as C
     _chk_f32(mat_pi0, 'mat_pi0'); _chk_f32(pi, 'pi'); _chk_f64(theta, 'theta'); _chk_f64(w, 'w'); _chk_f64(G, 'G')
     if pi.dim() != 3:
@@ -746,26 +751,15 @@ def train_episodes_irl_pop(mat_pi0, pi, T, episodes, first_episode, constant, th
                  shifts, alpha_scales, lr_critic, lr_actor, seeds, rn_seeds, net_struct)
     if tuple(P.shape) != (K, B, d, d) or not P.is_contiguous() or not P.is_cuda or P.dtype != torch.float32:
         raise ValueError('P: expected a contiguous f32 device tensor [%d, %d, %d, %d]' % (K, B, d, d))
-    head = (mat_pi0.data_ptr(), mat_pi0.shape[0], pi.data_ptr(), bufs['scratch'].data_ptr(), B, K, d, int(T), int(episodes),
-            int(first_episode), int(bool(constant)), theta.data_ptr(), shifts.data_ptr(), alpha_scales.data_ptr(), w.data_ptr(),
-            float(gamma), seeds.data_ptr(), int(first_step), int(traj_offset), L.PRECISIONS[precision], lr_critic.data_ptr(),
-            lr_actor.data_ptr(), C.byref(net_struct), int(bool(per_learner_net)))
-    tail = (P.data_ptr(), bufs['reward'].data_ptr(), bufs['delta'].data_ptr(), bufs['g'].data_ptr(), G.data_ptr(),
-            _ptr(reward_acc), ws.data_ptr(), ws.shape[1] * ws.element_size(), _stream())
-    if geom is not None:
-        if not isinstance(rn_call0, torch.Tensor):
-            raise ValueError('a geometry table needs the per-learner counter form (rn_call0 as a device array)')
-        _chk_pop(K, 'rn_call0', rn_call0, torch.int64)
-        L.check(L.lib().mfg_train_episodes_irl_pop_nets(*head, int(net_stride), *_geom_ptrs(geom, K), rn_seeds.data_ptr(),
-                                                        rn_call0.data_ptr(), *tail), 'mfg_train_episodes_irl_pop_nets')
-    elif isinstance(rn_call0, torch.Tensor):
-        _chk_pop(K, 'rn_call0', rn_call0, torch.int64)
-        L.check(L.lib().mfg_train_episodes_irl_pop_calls(*head, int(net_stride), rn_seeds.data_ptr(), rn_call0.data_ptr(), *tail),
-                'mfg_train_episodes_irl_pop_calls')
-    else:
-        if net_stride:
-            raise ValueError('net_stride needs the per-learner counter form (rn_call0 as a device array)')
-        L.check(L.lib().mfg_train_episodes_irl_pop(*head, rn_seeds.data_ptr(), int(rn_call0), *tail), 'mfg_train_episodes_irl_pop')
+    calls = _rn_call0_ptr(rn_call0, K, theta)
+    L.check(L.lib().mfg_train_episodes_irl_pop(
+        mat_pi0.data_ptr(), mat_pi0.shape[0], pi.data_ptr(), bufs['scratch'].data_ptr(), B, K, d, int(T), int(episodes),
+        int(first_episode), int(bool(constant)), theta.data_ptr(), shifts.data_ptr(), alpha_scales.data_ptr(), w.data_ptr(),
+        float(gamma), seeds.data_ptr(), int(first_step), int(traj_offset), L.PRECISIONS[precision], lr_critic.data_ptr(),
+        lr_actor.data_ptr(), C.byref(net_struct), int(bool(per_learner_net)), int(net_stride), *_geom_ptrs(geom, K),
+        rn_seeds.data_ptr(), calls.data_ptr(), P.data_ptr(), bufs['reward'].data_ptr(), bufs['delta'].data_ptr(),
+        bufs['g'].data_ptr(), G.data_ptr(), _ptr(reward_acc), ws.data_ptr(), ws.shape[1] * ws.element_size(), _stream()),
+        'mfg_train_episodes_irl_pop')
     return pi
 
 
@@ -774,7 +768,7 @@ def train_rollouts_irl_pop(mat_pi0, T, episodes, first_episode, constant, theta,
                            traj_offset=0, discount_pow=True, reward_acc=None, precision='mixed', net_stride=0, geom=None):
     """AC_IRL.train's rollout mode for K independent learners (mfg_train_rollouts_irl_pop): bufs = dict(pi_traj
     [K,Bk,T+1,d] f32, pi_last [K,Bk,d] f32 (optional), P [K,Bk,T,d,d] f32, reward [K,Bk,T] f32, delta / g [K,Bk,T] f64);
-    the other arrays, rn_call0, net_stride and geom (mfg_train_rollouts_irl_pop_nets) as for train_episodes_irl_pop."""
+    the other arrays, rn_call0, net_stride and geom as for train_episodes_irl_pop."""
     import ctypes as C
     _chk_f32(mat_pi0, 'mat_pi0'); _chk_f64(theta, 'theta'); _chk_f64(w, 'w'); _chk_f64(G, 'G')
     if bufs['pi_traj'].dim() != 4:
@@ -786,27 +780,15 @@ def train_rollouts_irl_pop(mat_pi0, T, episodes, first_episode, constant, theta,
     if tuple(P.shape) != (K, B, T, d, d) or not P.is_contiguous() or not P.is_cuda or P.dtype != torch.float32:
         raise ValueError('P: expected a contiguous f32 device tensor [%d, %d, %d, %d, %d]' % (K, B, T, d, d))
     flags = _rollout_flags(discount_pow, precision)
-    head = (mat_pi0.data_ptr(), mat_pi0.shape[0], B, K, d, int(T), int(episodes), int(first_episode), int(bool(constant)),
-            theta.data_ptr(), shifts.data_ptr(), alpha_scales.data_ptr(), w.data_ptr(), float(gamma), seeds.data_ptr(),
-            int(first_step), int(traj_offset), flags, lr_critic.data_ptr(), lr_actor.data_ptr(), C.byref(net_struct),
-            int(bool(per_learner_net)))
-    tail = (bufs['pi_traj'].data_ptr(), _ptr(bufs.get('pi_last')), P.data_ptr(), bufs['reward'].data_ptr(),
-            bufs['delta'].data_ptr(), bufs['g'].data_ptr(), G.data_ptr(), _ptr(reward_acc), ws.data_ptr(),
-            ws.shape[1] * ws.element_size(), _stream())
-    if geom is not None:
-        if not isinstance(rn_call0, torch.Tensor):
-            raise ValueError('a geometry table needs the per-learner counter form (rn_call0 as a device array)')
-        _chk_pop(K, 'rn_call0', rn_call0, torch.int64)
-        L.check(L.lib().mfg_train_rollouts_irl_pop_nets(*head, int(net_stride), *_geom_ptrs(geom, K), rn_seeds.data_ptr(),
-                                                        rn_call0.data_ptr(), *tail), 'mfg_train_rollouts_irl_pop_nets')
-    elif isinstance(rn_call0, torch.Tensor):
-        _chk_pop(K, 'rn_call0', rn_call0, torch.int64)
-        L.check(L.lib().mfg_train_rollouts_irl_pop_calls(*head, int(net_stride), rn_seeds.data_ptr(), rn_call0.data_ptr(), *tail),
-                'mfg_train_rollouts_irl_pop_calls')
-    else:
-        if net_stride:
-            raise ValueError('net_stride needs the per-learner counter form (rn_call0 as a device array)')
-        L.check(L.lib().mfg_train_rollouts_irl_pop(*head, rn_seeds.data_ptr(), int(rn_call0), *tail), 'mfg_train_rollouts_irl_pop')
+    calls = _rn_call0_ptr(rn_call0, K, theta)
+    L.check(L.lib().mfg_train_rollouts_irl_pop(
+        mat_pi0.data_ptr(), mat_pi0.shape[0], B, K, d, int(T), int(episodes), int(first_episode), int(bool(constant)),
+        theta.data_ptr(), shifts.data_ptr(), alpha_scales.data_ptr(), w.data_ptr(), float(gamma), seeds.data_ptr(),
+        int(first_step), int(traj_offset), flags, lr_critic.data_ptr(), lr_actor.data_ptr(), C.byref(net_struct),
+        int(bool(per_learner_net)), int(net_stride), *_geom_ptrs(geom, K), rn_seeds.data_ptr(), calls.data_ptr(),
+        bufs['pi_traj'].data_ptr(), _ptr(bufs.get('pi_last')), P.data_ptr(), bufs['reward'].data_ptr(),
+        bufs['delta'].data_ptr(), bufs['g'].data_ptr(), G.data_ptr(), _ptr(reward_acc), ws.data_ptr(),
+        ws.shape[1] * ws.element_size(), _stream()), 'mfg_train_rollouts_irl_pop')
     return bufs
 
 
@@ -815,7 +797,7 @@ def reward_net_forward_pop(net_struct, per_learner_net, K, state, action, learne
     """mfg_reward_net_forward_pop: the reward network of the listed learners (distinct, in [0, K)) in one launch.  state [N,d] /
     action [N,d,d] (shared by every learner) or [K,N,d] / [K,N,d,d] (learner k reads row k); keys: the Philox keys of the listed
     learners (Python ints, read as uint64).  Returns out [K,N] f32 (rows of unlisted learners untouched); sample offset 0.
-    geom: a per-learner geometry table (rn_geom_table) -- mfg_reward_net_forward_pop_nets."""
+    geom: a per-learner geometry table (rn_geom_table)."""
     import ctypes as C
     import numpy as np
     _chk_f32(state, 'state'); _chk_f32(action, 'action')
@@ -841,14 +823,11 @@ def reward_net_forward_pop(net_struct, per_learner_net, K, state, action, learne
     _chk_f32(out, 'out')
     if scratch is None:
         scratch = torch.empty(max(2 * lr.size, 2), dtype=torch.float64, device=state.device)
-    head = (state.data_ptr(), action.data_ptr(), 0 if shared else N * d, 0 if shared else N * d * d, N, d, C.byref(net_struct),
-            int(bool(per_learner_net)), int(net_stride))
-    tail = (int(K), lr.ctypes.data, ky.ctypes.data, int(lr.size), 0, out.data_ptr(), scratch.data_ptr(),
-            scratch.numel() * scratch.element_size(), _stream())
-    if geom is not None:
-        L.check(L.lib().mfg_reward_net_forward_pop_nets(*head, *_geom_ptrs(geom, K), *tail), 'mfg_reward_net_forward_pop_nets')
-    else:
-        L.check(L.lib().mfg_reward_net_forward_pop(*head, *tail), 'mfg_reward_net_forward_pop')
+    L.check(L.lib().mfg_reward_net_forward_pop(
+        state.data_ptr(), action.data_ptr(), 0 if shared else N * d, 0 if shared else N * d * d, N, d, C.byref(net_struct),
+        int(bool(per_learner_net)), int(net_stride), *_geom_ptrs(geom, K), int(K), lr.ctypes.data, ky.ctypes.data, int(lr.size),
+        0, out.data_ptr(), scratch.data_ptr(), scratch.numel() * scratch.element_size(), _stream()),
+        'mfg_reward_net_forward_pop')
     return out
 
 
@@ -869,8 +848,8 @@ def reward_net_train_steps_pop(params, m, v, param_stride, K, dims, demo, gen, p
     """mfg_reward_net_train_steps_pop: n_updates update_reward steps of n_active learners.  params / m / v [K, param_stride] f32,
     dims = (d, k1, f2, k2, n3, n4), demo = (state [rows,T,d], action [rows,T,d,d]) shared, gen = (state [K,cap,T,d], action
     [K,cap,T,d,d]), plan = rn_train_plan(n_updates * n_active), stats [K,4] f32, ws / plan_dev device byte buffers (uint8).
-    geom: a per-learner geometry table (rn_geom_table) -- mfg_reward_net_train_steps_pop_nets: n3, n4, keep_prob and l1l2 come
-    from the table (dims[4:], keep_prob and l1l2 are not read), rows hold learner k's own layout."""
+    geom: a per-learner geometry table (rn_geom_table): n3, n4, keep_prob and l1l2 come from the table (dims[4:], keep_prob and
+    l1l2 are not read), rows hold learner k's own layout."""
     for name, t in (('params', params), ('adam_m', m), ('adam_v', v)):
         _chk_f32(t, name)
         if tuple(t.shape) != (K, param_stride):
@@ -886,18 +865,13 @@ def reward_net_train_steps_pop(params, m, v, param_stride, K, dims, demo, gen, p
         raise ValueError('generated stores: expected [%d, cap, T, d] / [%d, cap, T, d, d]' % (K, K))
     if plan.size < n_updates * n_active:
         raise ValueError('plan: fewer than n_updates * n_active entries')
-    stores = (ds.data_ptr(), da.data_ptr(), ds.shape[0], gs.data_ptr(), ga.data_ptr(), gs.shape[1], plan.ctypes.data,
-              plan_dev.data_ptr(), plan_dev.numel() * plan_dev.element_size(), int(n_updates), int(n_active), int(n_demo),
-              int(n_gen), int(steps), int(demo_divisor))
-    tail = (float(beta1), float(beta2), float(eps), stats.data_ptr(), ws.data_ptr(), ws.numel() * ws.element_size(), _stream())
-    if geom is not None:
-        L.check(L.lib().mfg_reward_net_train_steps_pop_nets(
-            params.data_ptr(), m.data_ptr(), v.data_ptr(), int(param_stride), int(K), *[int(x) for x in dims[:4]],
-            *_geom_ptrs(geom, K), *stores, *tail), 'mfg_reward_net_train_steps_pop_nets')
-    else:
-        L.check(L.lib().mfg_reward_net_train_steps_pop(
-            params.data_ptr(), m.data_ptr(), v.data_ptr(), int(param_stride), int(K), *[int(x) for x in dims], *stores,
-            float(keep_prob), int(bool(l1l2)), *tail), 'mfg_reward_net_train_steps_pop')
+    L.check(L.lib().mfg_reward_net_train_steps_pop(
+        params.data_ptr(), m.data_ptr(), v.data_ptr(), int(param_stride), int(K), *[int(x) for x in dims],
+        *_geom_ptrs(geom, K), ds.data_ptr(), da.data_ptr(), ds.shape[0], gs.data_ptr(), ga.data_ptr(), gs.shape[1],
+        plan.ctypes.data, plan_dev.data_ptr(), plan_dev.numel() * plan_dev.element_size(), int(n_updates), int(n_active),
+        int(n_demo), int(n_gen), int(steps), int(demo_divisor), float(keep_prob), int(bool(l1l2)), float(beta1), float(beta2),
+        float(eps), stats.data_ptr(), ws.data_ptr(), ws.numel() * ws.element_size(), _stream()),
+        'mfg_reward_net_train_steps_pop')
 
 
 def episode_buffers(B, d, device):

@@ -546,6 +546,31 @@ int mfg_train_rollout_irl(const float* mat_pi0, int64_t num_start, const int32_t
                           double* delta, double* g, double* G, double* reward_acc, void* workspace, size_t workspace_bytes,
                           mfg_stream_t stream);
 
+/* Per-learner reward-network geometry, the optional TABLE of the four IRL population calls below: populations whose learners
+ * differ in the SHAPE and the REGULARISER of their reward networks, the reference's sweep gridsearch.py:8-31 (reg x n_fc3 x
+ * n_fc4, one AC_IRL per point) as ONE population.  Entry k is learner k's n_fc3, n_fc4, keep_prob (1: no dropout) and l1_l2
+ * flag (read by the training steps only); d, k1 = 5, f2 = 2, k2 = 3 stay shared.  Limits per entry, those of the matrix-core
+ * kernel: 1 <= n3 <= 16, 1 <= n4 <= 32, keep_prob in (0, 1]. */
+typedef struct mfg_rn_geom { int32_t n3, n4; float keep_prob; int32_t l1l2; } mfg_rn_geom_t;   /* 16 bytes */
+
+/* The table arguments geom_host / geom_dev of mfg_train_episodes_irl_pop, mfg_train_rollouts_irl_pop,
+ * mfg_reward_net_forward_pop and mfg_reward_net_train_steps_pop.  Both NULL: no table, every learner has the geometry and
+ * keep_prob (and l1l2) the call passes.  Both given: geom_host [K] is read by the checks, geom_dev [K] (device, the same
+ * entries) by the kernels.  Then per_learner_net = 1 and net_stride / param_stride > 0 are required: learner k's parameters
+ * are ONE flat row at conv1_w + k net_stride (params + k param_stride) in the order and at the offsets of
+ * mfg_reward_net_param_offsets(d, 5, 2, 3, n3_k, n4_k); rows are as long as the longest learner's and nothing beyond a
+ * learner's own NP_k floats is read or written.  Of the struct, k1 / f2 / k2 and conv1_w (the base of row 0) are read; n3,
+ * n4, keep_prob and the other nine pointers are ignored (mfg_reward_net_train_steps_pop: its n3, n4, keep_prob and l1l2).
+ * Learner k of a call with a table gives, bit for bit, what the single entry point (mfg_train_episode_irl_draw,
+ * mfg_train_rollout_irl, mfg_reward_net_forward, mfg_reward_net_train_step) gives with learner k's geometry; a table whose
+ * entries are all equal gives the bits of the call without a table.  Dynamic LDS and workspace slices are sized for
+ * the largest n3 and the largest n4 of the table; the combine kernel's grid is ceil(max NP_k / 64) wide and blocks beyond a
+ * learner's own NP_k do nothing.  No allocation; the training entry points do not synchronise.
+ * Checked before anything is launched, on top of the checks of the call without a table: MFG_EINVAL for exactly one copy
+ * NULL, per_learner_net = 0, a stride below the largest NP_k, an entry's keep_prob outside (0, 1]; MFG_EUNSUPPORTED
+ * for an entry outside n3 <= 16 / n4 <= 32, d other than 15 / 21, an fc3_w of any learner not 8-byte aligned, a training batch
+ * beyond the single step's limits at the largest n3; MFG_EWORKSPACE as without a table, at the largest geometry. */
+
 /* IRL populations: K independent forward learners of AC_IRL.train (ac_irl.py:634-732; without a population control block
  * stop_criteria = -1 as in outerloop, with one -- mfg_ctx_set_pop_control -- learner k stops after the episode at which
  * |theta - theta_prev| < stop_criteria[k], as ac_irl.py:726 does, and holds what the single learner holds at that point)
@@ -553,17 +578,21 @@ int mfg_train_rollout_irl(const float* mat_pi0, int64_t num_start, const int32_t
  * (theta, w, G, reward_acc, final states and the last step's P / reward / delta / g), what the single-learner path gives with
  * B = Bk, the same traj_offset and learner k's seed, theta, w, shift, alpha_scale, learning rates and reward network:
  *   step mode     `episodes` calls of mfg_train_episode_irl_draw (first_step + e T, lr x lr_schedule(first_episode + e),
- *                 reward_acc + e, rn_seed[k], rn_call0 + e T, rn_sample_offset = traj_offset);
+ *                 reward_acc + e, rn_seed[k], rn_call0[k] + e T, rn_sample_offset = traj_offset);
  *   rollout mode  `episodes` calls of mfg_train_rollout_irl with idx = NULL and MFG_TRAIN_APPLY (first_step + e T, the same
- *                 rates, rn_key = rn_seed[k] ^ ((rn_call0 + e + 1) 0x9E3779B97F4A7C15), rn_sample_offset = traj_offset T).
+ *                 rates, rn_key = rn_seed[k] ^ ((rn_call0[k] + e + 1) 0x9E3779B97F4A7C15), rn_sample_offset = traj_offset T).
  * Learning rates in episode e: lr_critic[k] x, lr_actor[k] x the schedule of mfg_train_rollouts at episode number
  * first_episode + e (AC_IRL.train numbers its episodes from 1: pass first_episode + 1 to reproduce it).
- * Dropout keys: rn_seed is a device array [K] (AC_IRL passes its seed + 0x5EED); rn_call0 the count of reward calls made before,
- * shared (the learners move in lock-step).  Step mode, episode e, env step s:  rn_seed[k] ^ ((rn_call0 + e T + s + 1) x
- * 0x9E3779B97F4A7C15);  rollout mode, episode e:  rn_seed[k] ^ ((rn_call0 + e + 1) x 0x9E3779B97F4A7C15)  (mod 2^64).
+ * Dropout keys: rn_seed is a device array [K] (AC_IRL passes its seed + 0x5EED); rn_call0 a device array [K] (uint64,
+ * required), learner k's count of reward calls made before (AC_IRLPopulation after reward_iteration, where each learner's
+ * early stop has consumed its own number of reward calls; learners in lock-step pass K equal counts).  Step mode, episode e,
+ * env step s:  rn_seed[k] ^ ((rn_call0[k] + e T + s + 1) x 0x9E3779B97F4A7C15);  rollout mode, episode e:
+ * rn_seed[k] ^ ((rn_call0[k] + e + 1) x 0x9E3779B97F4A7C15)  (mod 2^64).
  * Reward networks: `net` (host struct).  per_learner_net = 0: every learner reads the same tensors; 1: every pointer is the
  * base of a stacked tensor, learner k's tensor t at base_t + k numel_t (numel_t from the geometry: k1^2, 1, f2 k2^2, f2,
- * n3 f2 d^2, n3, n4 (n3 + d), n4, n4, 1).  Geometry and keep_prob are shared (per learner: the *_nets entry points below).
+ * n3 f2 d^2, n3, n4 (n3 + d), n4, n4, 1) when net_stride = 0, at base_t + k net_stride when net_stride > 0 (one padded flat
+ * parameter row per learner, the layout of mfg_reward_net_train_steps_pop).  Geometry and keep_prob are shared, or per
+ * learner with a table (geom_host / geom_dev, above; both NULL: none).
  * Per-learner scalars and learner-major arrays as for mfg_train_episodes_pop / mfg_train_rollouts_pop, plus P: step mode
  * pi_out / pi_scratch [K,Bk,d], P [K,Bk,d,d], reward / delta / g [K,Bk]; rollout mode pi_traj [K,Bk,T+1,d], pi_last [K,Bk,d]
  * (may be NULL), P [K,Bk,T,d,d], reward / delta / g [K,Bk,T].  reward_acc [K,episodes] (may be NULL; step mode: += every
@@ -573,56 +602,39 @@ int mfg_train_rollout_irl(const float* mat_pi0, int64_t num_start, const int32_t
  * (d = 21 / 15, k1 = 5, f2 = 2, k2 = 3, n_fc3 <= 16, n_fc4 <= 32, every learner's fc3_w 8-byte aligned); MFG_EWORKSPACE when
  * one learner's slice (workspace_bytes, a multiple of 256) cannot hold the control block and the partial rows of the update:
  * 64 + min(ceil(Bk / 16), 256) (F + 4) 8 bytes in step mode, those of the gradient kernels over Bk T samples in rollout mode. */
+/* step mode (AC_IRL.train, ac_irl.py:634-732; with a table: for the K points of gridsearch.py:8-31) */
 int mfg_train_episodes_irl_pop(const float* mat_pi0, int64_t num_start, float* pi_out, float* pi_scratch, int64_t B, int K, int d,
                                int T, int64_t episodes, int64_t first_episode, int constant, double* theta, const double* shift,
                                const double* alpha_scale, double* w, double gamma, const uint64_t* seed, uint32_t first_step,
                                uint64_t traj_offset, int precision, const double* lr_critic, const double* lr_actor,
-                               const mfg_reward_net_t* net_host, int per_learner_net, const uint64_t* rn_seed, uint64_t rn_call0,
-                               float* P, float* reward, double* delta, double* g, double* G, double* reward_acc, void* workspace,
-                               size_t workspace_bytes, mfg_stream_t stream);
-/* rollout mode; flags: MFG_ROLLOUT_DISCOUNT_POW | MFG_ROLLOUT_F64 */
+                               const mfg_reward_net_t* net_host, int per_learner_net, int64_t net_stride,
+                               const mfg_rn_geom_t* geom_host, const mfg_rn_geom_t* geom_dev, const uint64_t* rn_seed,
+                               const uint64_t* rn_call0, float* P, float* reward, double* delta, double* g, double* G,
+                               double* reward_acc, void* workspace, size_t workspace_bytes, mfg_stream_t stream);
+/* rollout mode (one update per episode); flags: MFG_ROLLOUT_DISCOUNT_POW | MFG_ROLLOUT_F64 */
 int mfg_train_rollouts_irl_pop(const float* mat_pi0, int64_t num_start, int64_t B, int K, int d, int T, int64_t episodes,
                                int64_t first_episode, int constant, double* theta, const double* shift, const double* alpha_scale,
                                double* w, double gamma, const uint64_t* seed, uint32_t first_step, uint64_t traj_offset, int flags,
                                const double* lr_critic, const double* lr_actor, const mfg_reward_net_t* net_host,
-                               int per_learner_net, const uint64_t* rn_seed, uint64_t rn_call0, float* pi_traj, float* pi_last,
-                               float* P, float* reward, double* delta, double* g, double* G, double* reward_acc, void* workspace,
-                               size_t workspace_bytes, mfg_stream_t stream);
+                               int per_learner_net, int64_t net_stride, const mfg_rn_geom_t* geom_host,
+                               const mfg_rn_geom_t* geom_dev, const uint64_t* rn_seed, const uint64_t* rn_call0, float* pi_traj,
+                               float* pi_last, float* P, float* reward, double* delta, double* g, double* G, double* reward_acc,
+                               void* workspace, size_t workspace_bytes, mfg_stream_t stream);
 
-/* The same two flows with a reward-call counter PER LEARNER (AC_IRLPopulation after reward_iteration, where each learner's
- * early stop has consumed its own number of reward calls): rn_call0 is a device array [K] (uint64) and learner k's keys are
- * those above with rn_call0[k] in place of the shared counter.  net_stride > 0 (per_learner_net = 1): learner k's tensor t at
- * base_t + k net_stride (one padded flat parameter row per learner, the layout of mfg_reward_net_train_steps_pop); 0: the
- * numel_t strides above.  Everything else, checks included, as for the shared-counter entries, which give the same bits when
- * every rn_call0[k] equals their scalar. */
-int mfg_train_episodes_irl_pop_calls(const float* mat_pi0, int64_t num_start, float* pi_out, float* pi_scratch, int64_t B, int K,
-                                     int d, int T, int64_t episodes, int64_t first_episode, int constant, double* theta,
-                                     const double* shift, const double* alpha_scale, double* w, double gamma, const uint64_t* seed,
-                                     uint32_t first_step, uint64_t traj_offset, int precision, const double* lr_critic,
-                                     const double* lr_actor, const mfg_reward_net_t* net_host, int per_learner_net,
-                                     int64_t net_stride, const uint64_t* rn_seed, const uint64_t* rn_call0, float* P, float* reward,
-                                     double* delta, double* g, double* G, double* reward_acc, void* workspace,
-                                     size_t workspace_bytes, mfg_stream_t stream);
-int mfg_train_rollouts_irl_pop_calls(const float* mat_pi0, int64_t num_start, int64_t B, int K, int d, int T, int64_t episodes,
-                                     int64_t first_episode, int constant, double* theta, const double* shift,
-                                     const double* alpha_scale, double* w, double gamma, const uint64_t* seed, uint32_t first_step,
-                                     uint64_t traj_offset, int flags, const double* lr_critic, const double* lr_actor,
-                                     const mfg_reward_net_t* net_host, int per_learner_net, int64_t net_stride,
-                                     const uint64_t* rn_seed, const uint64_t* rn_call0, float* pi_traj, float* pi_last, float* P,
-                                     float* reward, double* delta, double* g, double* G, double* reward_acc, void* workspace,
-                                     size_t workspace_bytes, mfg_stream_t stream);
-
-/* The reward network of n listed learners of a population in ONE launch of the matrix-core kernel (grid rows = the list):
- * for slot s, learner k = learners_host[s] (distinct, in [0, K)):
+/* The reward network of n listed learners of a population in ONE launch of the matrix-core kernel (grid rows = the list; the
+ * reward averages of reward_iteration and test_reward_network, ac_irl.py:848-897, :1008-1046): for slot s, learner
+ * k = learners_host[s] (distinct, in [0, K)):
  *   reward[k N .. k N + N) = mfg_reward_net_forward(state + k s_state, action + k s_action, N, learner k's weights,
  *                                                   seed = keys_host[s], sample_offset)
  * bit for bit.  s_state / s_action: elements between two learners' inputs, 0 = one input shared by all (>= N d / N d^2
- * otherwise).  Weights: as for mfg_train_episodes_irl_pop_calls (per_learner_net, net_stride).  reward [K,N]; rows of learners
- * not listed are left alone.  The keys and the list are uploaded into `scratch` (device, >= 16 n bytes) and the stream is
- * drained once before the launch.  MFG_EINVAL: null pointers, counts, a learner out of range or listed twice; MFG_EUNSUPPORTED
- * outside the matrix-core geometry; MFG_EWORKSPACE: scratch too small -- all before anything is launched. */
+ * otherwise).  Weights: as for mfg_train_episodes_irl_pop (per_learner_net, net_stride), with the same optional table
+ * (geom_host / geom_dev, above; both NULL: none).  reward [K,N]; rows of learners not listed are left alone.  The keys and the
+ * list are uploaded into `scratch` (device, >= 16 n bytes) and the stream is drained once before the launch.  MFG_EINVAL:
+ * null pointers, counts, a learner out of range or listed twice; MFG_EUNSUPPORTED outside the matrix-core geometry;
+ * MFG_EWORKSPACE: scratch too small -- all before anything is launched. */
 int mfg_reward_net_forward_pop(const float* state, const float* action, int64_t s_state, int64_t s_action, int64_t N, int d,
-                               const mfg_reward_net_t* net_host, int per_learner_net, int64_t net_stride, int K,
+                               const mfg_reward_net_t* net_host, int per_learner_net, int64_t net_stride,
+                               const mfg_rn_geom_t* geom_host, const mfg_rn_geom_t* geom_dev, int K,
                                const int32_t* learners_host, const uint64_t* keys_host, int n, uint64_t sample_offset,
                                float* reward, void* scratch, size_t scratch_bytes, mfg_stream_t stream);
 
@@ -637,14 +649,16 @@ typedef struct mfg_rn_train_plan {
   int32_t gen_rows[MFG_RN_TRAIN_MAX_TRAJ];   /* rows of learner k's generated store (n_gen used) */
 } mfg_rn_train_plan_t;
 
-/* n_updates consecutive update_reward steps of n_active learners of a population: update u, slot s runs, for learner
- * k = plan[u n_active + s].learner, exactly mfg_reward_net_train_step(params + k param_stride, adam_m + k param_stride,
+/* n_updates consecutive update_reward steps (ac_irl.py:804-846) of n_active learners of a population: update u, slot s runs,
+ * for learner k = plan[u n_active + s].learner, exactly mfg_reward_net_train_step(params + k param_stride, adam_m + k param_stride,
  * adam_v + k param_stride, geometry, demo store, the entry's demo_rows, learner k's generated store (gen_state +
  * k gen_capacity steps d, gen_action + k gen_capacity steps d^2), the entry's gen_rows, steps, demo_divisor, keep_prob, l1l2,
  * the entry's key, lr and adam_step, flags 0, stats + 4 k) -- the same bits.  Two launches per update: the sample kernel on
  * grid (N + 1, n_active) and the combine kernel on grid (ceil(NP / 64), n_active), N = (n_demo + n_gen) steps.  Learners
  * without an entry in an update are not touched (no blocks).
  * params / adam_m / adam_v [K, param_stride] fp32 (param_stride >= mfg_reward_net_num_params); stats [K, 4] fp32.
+ * Optional table (geom_host / geom_dev, above; both NULL: none): learner k's n3, n4, keep_prob and l1l2 come from entry k, and
+ * the arguments n3, n4, keep_prob and l1l2 are not read.
  * plan_host [n_updates n_active] (its lr_t fields written first) is uploaded ONCE into plan_dev (device, >= n_updates n_active
  * sizeof(mfg_rn_train_plan_t) bytes) and the stream is drained once before the first launch.  workspace: n_active slices, each
  * mfg_reward_net_train_workspace_bytes(geometry, N) rounded up to 256 bytes.
@@ -653,70 +667,13 @@ typedef struct mfg_rn_train_plan {
  * d = 15 / 21, k1 = 5, f2 = 2, k2 = 3, n_fc3 <= 16, n_fc4 <= 32, or for a batch beyond the single step's limits (n_demo, n_gen
  * <= MFG_RN_TRAIN_MAX_TRAJ, N <= 2048, N (1 + n_fc3) 4 B <= 60 KB); MFG_EWORKSPACE for a too small workspace or plan_dev. */
 int mfg_reward_net_train_steps_pop(float* params, float* adam_m, float* adam_v, int64_t param_stride, int K, int d, int k1, int f2,
-                                   int k2, int n3, int n4, const float* demo_state, const float* demo_action, int64_t demo_capacity,
+                                   int k2, int n3, int n4, const mfg_rn_geom_t* geom_host, const mfg_rn_geom_t* geom_dev,
+                                   const float* demo_state, const float* demo_action, int64_t demo_capacity,
                                    const float* gen_state, const float* gen_action, int64_t gen_capacity,
                                    mfg_rn_train_plan_t* plan_host, void* plan_dev, size_t plan_dev_bytes, int n_updates,
                                    int n_active, int n_demo, int n_gen, int steps, int demo_divisor, float keep_prob, int l1l2,
                                    double beta1, double beta2, double eps, float* stats, void* workspace, size_t workspace_bytes,
                                    mfg_stream_t stream);
-
-/* Populations whose learners differ in the SHAPE and the REGULARISER of their reward networks: the reference's sweep
- * gridsearch.py:8-31 (reg x n_fc3 x n_fc4, one AC_IRL per point) as ONE population.  Entry k of a geometry table is learner
- * k's n_fc3, n_fc4, keep_prob (1: no dropout) and l1_l2 flag (read by the training steps only); d, k1 = 5, f2 = 2, k2 = 3 stay
- * shared.  Limits per entry, those of the matrix-core kernel: 1 <= n3 <= 16, 1 <= n4 <= 32, keep_prob in (0, 1]. */
-typedef struct mfg_rn_geom { int32_t n3, n4; float keep_prob; int32_t l1l2; } mfg_rn_geom_t;   /* 16 bytes */
-
-/* The four *_nets entry points below are mfg_train_episodes_irl_pop_calls, mfg_train_rollouts_irl_pop_calls,
- * mfg_reward_net_forward_pop and mfg_reward_net_train_steps_pop with such a table: geom_host [K] is read by the checks,
- * geom_dev [K] (device, the same entries) by the kernels.  Both are required, and so are per_learner_net = 1 and
- * net_stride / param_stride > 0: learner k's parameters are ONE flat row at conv1_w + k net_stride (params + k param_stride)
- * in the order and at the offsets of mfg_reward_net_param_offsets(d, 5, 2, 3, n3_k, n4_k); rows are as long as the longest
- * learner's and nothing beyond a learner's own NP_k floats is read or written.  Of the struct, k1 / f2 / k2 and conv1_w (the
- * base of row 0) are read; n3, n4, keep_prob and the other nine pointers are ignored.
- * Learner k of a mixed call gives, bit for bit, what the single entry point (mfg_train_episode_irl_draw,
- * mfg_train_rollout_irl, mfg_reward_net_forward, mfg_reward_net_train_step) gives with learner k's geometry; a table whose
- * entries are all equal gives the bits of the entry point without a table.  Dynamic LDS and workspace slices are sized for
- * the largest n3 and the largest n4 of the table; the combine kernel's grid is ceil(max NP_k / 64) wide and blocks beyond a
- * learner's own NP_k do nothing.  No allocation; the training entry points do not synchronise.
- * Checked before anything is launched, on top of the checks of the entry point without a table: MFG_EINVAL for a null table
- * (either copy), per_learner_net = 0, a stride below the largest NP_k, an entry's keep_prob outside (0, 1]; MFG_EUNSUPPORTED
- * for an entry outside n3 <= 16 / n4 <= 32, d other than 15 / 21, an fc3_w of any learner not 8-byte aligned, a training batch
- * beyond the single step's limits at the largest n3; MFG_EWORKSPACE as without a table, at the largest geometry. */
-/* AC_IRL.train in step mode (ac_irl.py:634-732) for the K points of gridsearch.py:8-31 */
-int mfg_train_episodes_irl_pop_nets(const float* mat_pi0, int64_t num_start, float* pi_out, float* pi_scratch, int64_t B, int K,
-                                    int d, int T, int64_t episodes, int64_t first_episode, int constant, double* theta,
-                                    const double* shift, const double* alpha_scale, double* w, double gamma, const uint64_t* seed,
-                                    uint32_t first_step, uint64_t traj_offset, int precision, const double* lr_critic,
-                                    const double* lr_actor, const mfg_reward_net_t* net_host, int per_learner_net,
-                                    int64_t net_stride, const mfg_rn_geom_t* geom_host, const mfg_rn_geom_t* geom_dev,
-                                    const uint64_t* rn_seed, const uint64_t* rn_call0, float* P, float* reward, double* delta,
-                                    double* g, double* G, double* reward_acc, void* workspace, size_t workspace_bytes,
-                                    mfg_stream_t stream);
-/* ... in rollout mode (one update per episode) */
-int mfg_train_rollouts_irl_pop_nets(const float* mat_pi0, int64_t num_start, int64_t B, int K, int d, int T, int64_t episodes,
-                                    int64_t first_episode, int constant, double* theta, const double* shift,
-                                    const double* alpha_scale, double* w, double gamma, const uint64_t* seed, uint32_t first_step,
-                                    uint64_t traj_offset, int flags, const double* lr_critic, const double* lr_actor,
-                                    const mfg_reward_net_t* net_host, int per_learner_net, int64_t net_stride,
-                                    const mfg_rn_geom_t* geom_host, const mfg_rn_geom_t* geom_dev, const uint64_t* rn_seed,
-                                    const uint64_t* rn_call0, float* pi_traj, float* pi_last, float* P, float* reward,
-                                    double* delta, double* g, double* G, double* reward_acc, void* workspace,
-                                    size_t workspace_bytes, mfg_stream_t stream);
-/* the reward averages of reward_iteration and test_reward_network (ac_irl.py:848-897, :1008-1046) for the listed points */
-int mfg_reward_net_forward_pop_nets(const float* state, const float* action, int64_t s_state, int64_t s_action, int64_t N, int d,
-                                    const mfg_reward_net_t* net_host, int per_learner_net, int64_t net_stride,
-                                    const mfg_rn_geom_t* geom_host, const mfg_rn_geom_t* geom_dev, int K,
-                                    const int32_t* learners_host, const uint64_t* keys_host, int n, uint64_t sample_offset,
-                                    float* reward, void* scratch, size_t scratch_bytes, mfg_stream_t stream);
-/* update_reward (ac_irl.py:804-846) of the points of a plan; n3, n4, keep_prob and l1l2 come from the table */
-int mfg_reward_net_train_steps_pop_nets(float* params, float* adam_m, float* adam_v, int64_t param_stride, int K, int d, int k1,
-                                        int f2, int k2, const mfg_rn_geom_t* geom_host, const mfg_rn_geom_t* geom_dev,
-                                        const float* demo_state, const float* demo_action, int64_t demo_capacity,
-                                        const float* gen_state, const float* gen_action, int64_t gen_capacity,
-                                        mfg_rn_train_plan_t* plan_host, void* plan_dev, size_t plan_dev_bytes, int n_updates,
-                                        int n_active, int n_demo, int n_gen, int steps, int demo_divisor, double beta1,
-                                        double beta2, double eps, float* stats, void* workspace, size_t workspace_bytes,
-                                        mfg_stream_t stream);
 
 /* f1 (optional importance weights, ac_irl.py:270-289 calc_pdf_action, :324-379 calc_z): log-density of the
  * product-Dirichlet policy for N (state, action) pairs under K policies theta_k (device array):

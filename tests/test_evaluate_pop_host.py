@@ -25,7 +25,7 @@ def test_declared_bound_and_exported(lib):
         decl = re.search(r'\b%s\s*\(([^;]*)\);' % name, text, flags=re.S).group(1)
         assert len(decl.split(',')) == len(lib.SIGNATURES[name][1]), name
         assert getattr(lib.lib(), name) is not None
-    assert lib.lib().mfg_abi_version() == 17
+    assert lib.lib().mfg_abi_version() == 18
 
 
 def test_workspace_bytes(lib):

@@ -187,6 +187,47 @@ def test_even_T_population_equals_single_learner_calls(dev, mode):
             assert torch.equal(v, ref[key].view(v.shape)), (k, key)
 
 
+@pytest.mark.parametrize('mode', ['step', 'rollout'])
+def test_int_counter_equals_counter_array(dev, mode):
+    """rn_call0 as an int is rn_call0 as K equal per-learner counters, bit for bit -- with per-learner networks in flat rows
+    (net_stride > 0).  Bk = 40 is not a multiple of the reward-network launch's 16-sample groups."""
+    from discrete_mean_field_game_amd import ops
+    Te, d, K, B, E, gamma = 3, 15, 3, 40, 2, 0.9
+    thetas, shifts, alphas, seeds = _settings(K, d)
+    np.random.seed(5)
+    F = ops.num_features(d)
+    w0 = np.stack([np.random.randn(F) * 0.1 for _ in range(K)])
+    f32, f64 = dict(dtype=torch.float32, device=dev), dict(dtype=torch.float64, device=dev)
+
+    def run(rn_call0):
+        pop = _population(mode, d, K, B, 'mixed', _nets(d, 8, 0.4, K, 40 + d, dev), seeds, thetas, shifts, alphas, w0, dev)
+        assert pop._net_stride > 0
+        G = torch.zeros(K, F + 3, **f64)
+        ws = torch.zeros(K, ops.pop_workspace_slice(B, d, Te) // 8, **f64)
+        acc = torch.zeros(K, E, **f64)
+        n = (K, B) if mode == 'step' else (K, B, Te)
+        bufs = dict(P=torch.empty(*n, d, d, **f32), reward=torch.empty(*n, **f32), delta=torch.empty(*n, **f64),
+                    g=torch.empty(*n, **f64))
+        args = (pop._theta, pop._shifts_dev, pop._alphas_dev, pop._w, gamma, torch.full((K,), 0.1, **f64),
+                torch.full((K,), 0.001, **f64), pop._seeds_dev, pop._net_struct, True, pop._rn_seeds_dev, rn_call0, G, ws, bufs)
+        if mode == 'step':
+            pi = torch.empty(K, B, d, **f32)
+            bufs['scratch'] = torch.empty(K, B, d, **f32)
+            ops.train_episodes_irl_pop(pop._mat_pi0_dev, pi, Te, E, 1, 0, *args, reward_acc=acc, net_stride=pop._net_stride)
+        else:
+            bufs.update(pi_traj=torch.empty(K, B, Te + 1, d, **f32), pi_last=torch.empty(K, B, d, **f32))
+            ops.train_rollouts_irl_pop(pop._mat_pi0_dev, Te, E, 1, 0, *args, reward_acc=acc, net_stride=pop._net_stride)
+            pi = bufs['pi_last']
+        torch.cuda.synchronize()
+        return dict(theta=pop._theta, w=pop._w, G=G, acc=acc, pi=pi, P=bufs['P'], reward=bufs['reward'], delta=bufs['delta'],
+                    g=bufs['g'])
+    a = run(7)
+    b = run(torch.full((K,), 7, dtype=torch.int64, device=dev))
+    for key in a:
+        assert torch.equal(a[key], b[key]), key
+    assert bool(a['acc'].abs().sum() > 0) and bool(torch.isfinite(a['theta']).all())
+
+
 @pytest.mark.parametrize('Tn', [3, 4])
 def test_given_start_states_equal_drawn_ones(dev, Tn):
     """mfg_train_episode_irl on given start states (final states copied back into `pi` after an odd number of steps) against

@@ -102,7 +102,7 @@ def _compare(a, b, path=''):
 
 # ------------------------------------------------------------------ 1. forward
 @pytest.mark.parametrize('d', [15, 21])
-def test_forward_pop_nets_equals_single_forward(dev, d):
+def test_forward_pop_table_equals_single_forward(dev, d):
     from discrete_mean_field_game_amd import ops
     K, N = 4, 37                           # 37: not a multiple of the 16-sample group
     nets = _nets(d, M4, 200 + d, dev)
@@ -124,7 +124,7 @@ def test_forward_pop_nets_equals_single_forward(dev, d):
 
 # ------------------------------------------------------------------ 2. training steps
 @pytest.mark.parametrize('d', [15, 21])
-def test_train_steps_pop_nets_equals_single_steps(dev, d):
+def test_train_steps_pop_table_equals_single_steps(dev, d):
     from discrete_mean_field_game_amd import ops
     from discrete_mean_field_game_amd.reward_learning import StackedTrajectoryStore, TrajectoryStore
     K, U, PATTERN = 4, 3, 7.25
@@ -455,13 +455,13 @@ def test_refusals_before_any_launch(dev):
     scratch = torch.empty(16, dtype=torch.float64, device=dev)
     lr = np.array([0, 2], dtype=np.int32)
     ky = np.array([1, 2], dtype=np.uint64)
-    rc = L.lib().mfg_reward_net_forward_pop_nets(st.data_ptr(), ac.data_ptr(), N * d, N * d * d, N, d, C.byref(_row_struct(flat)), 1,
-                                                 stride, host_ptr, None, K, lr.ctypes.data, ky.ctypes.data, 2, 0, out.data_ptr(),
-                                                 scratch.data_ptr(), 128, None)
+    rc = L.lib().mfg_reward_net_forward_pop(st.data_ptr(), ac.data_ptr(), N * d, N * d * d, N, d, C.byref(_row_struct(flat)), 1,
+                                            stride, host_ptr, None, K, lr.ctypes.data, ky.ctypes.data, 2, 0, out.data_ptr(),
+                                            scratch.data_ptr(), 128, None)
     assert rc == EINVAL
-    rc = L.lib().mfg_reward_net_train_steps_pop_nets(
-        flat.data_ptr(), m.data_ptr(), v.data_ptr(), stride, K, d, 5, 2, 3, host_ptr, None, ds.data_ptr(), da.data_ptr(), 6,
-        gs.data_ptr(), ga.data_ptr(), 6, plan.ctypes.data, scratch.data_ptr(), 0, 1, 1, 5, 5, T, 5, 0.9, 0.999, 1e-8,
+    rc = L.lib().mfg_reward_net_train_steps_pop(
+        flat.data_ptr(), m.data_ptr(), v.data_ptr(), stride, K, d, 5, 2, 3, 16, 32, host_ptr, None, ds.data_ptr(), da.data_ptr(), 6,
+        gs.data_ptr(), ga.data_ptr(), 6, plan.ctypes.data, scratch.data_ptr(), 0, 1, 1, 5, 5, T, 5, 1.0, 0, 0.9, 0.999, 1e-8,
         stats.data_ptr(), scratch.data_ptr(), 128, None)
     assert rc == EINVAL
     # the training flows refuse the same table before their first launch

@@ -38,7 +38,7 @@ def test_argument_counts_match_header(lib):
 
 
 def test_abi_version_unchanged(lib):
-    assert lib.lib().mfg_abi_version() == 17
+    assert lib.lib().mfg_abi_version() == 18
 
 
 def _net(**kw):

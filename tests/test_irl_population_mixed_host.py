@@ -1,4 +1,4 @@
-"""CPU checks of the mixed IRL population (the *_nets entry points, AC_IRLPopulation(mixed_nets=True), gridsearch): declared in
+"""CPU checks of the mixed IRL population (the calls that take a geometry table, AC_IRLPopulation(mixed_nets=True), gridsearch): declared in
 the header, bound in _lib.SIGNATURES, exported by the library; the geometry struct's layout; the per-learner row layout; the
 argument checks; the grid order and the CSV lines of gridsearch on a stubbed population."""
 import ctypes as C
@@ -10,8 +10,7 @@ import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NETS = ('mfg_train_episodes_irl_pop_nets', 'mfg_train_rollouts_irl_pop_nets', 'mfg_reward_net_forward_pop_nets',
-        'mfg_reward_net_train_steps_pop_nets')
+NETS = ('mfg_train_episodes_irl_pop', 'mfg_train_rollouts_irl_pop', 'mfg_reward_net_forward_pop', 'mfg_reward_net_train_steps_pop')
 M4 = (('dropout', 4, 4), ('l1l2', 8, 6), ('dropout_l1l2', 16, 32), ('none', 6, 8))
 
 
@@ -45,7 +44,7 @@ def test_argument_counts_match_header(lib):
 
 
 def test_abi_version_unchanged(lib):
-    assert lib.lib().mfg_abi_version() == 17
+    assert lib.lib().mfg_abi_version() == 18
 
 
 def test_geom_struct_layout_matches_the_header(lib, tmp_path):
@@ -234,3 +233,98 @@ def test_gridsearch_order_and_csv_on_a_stub(monkeypatch, tmp_path):
     assert sorted(os.listdir(str(tmp_path / 'results'))) == before
     with pytest.raises(ValueError):
         ip.gridsearch((), (8,), (4,), demonstrations=['demo'], batch=8, outfile=None)
+
+
+# ------------------------------------------------------------------ the optional table of the four population calls
+EINVAL, EUNSUPPORTED = -1, -3
+REMOVED = tuple(base + suffix for base, suffixes in (('mfg_train_episodes_irl_pop', ('_calls', '_nets')),
+                                                     ('mfg_train_rollouts_irl_pop', ('_calls', '_nets')),
+                                                     ('mfg_reward_net_forward_pop', ('_nets',)),
+                                                     ('mfg_reward_net_train_steps_pop', ('_nets',))) for suffix in suffixes)
+
+
+def test_suffixed_entry_points_are_gone(lib):
+    text = open(os.path.join(ROOT, 'include', 'mfg_hip.h')).read()
+    for name in REMOVED:
+        assert name not in text, name
+        assert name not in lib.SIGNATURES, name
+        assert not hasattr(lib.lib(), name), name
+    assert lib.lib().mfg_abi_version() == 18
+
+
+def _table_calls(lib, d=15, K=4):
+    """The four calls as functions of (geom_host, geom_dev, per_learner_net, stride) over dummy pointers: a refusal of the
+    table comes before anything dereferences them or reaches the GPU."""
+    h = lib.lib()
+    p = C.c_void_p(16)
+    net = lib.RewardNetStruct()
+    net.k1, net.f2, net.k2, net.n3, net.n4, net.keep_prob = 5, 2, 3, 16, 32, 1.0
+    for f in ('conv1_w', 'conv1_b', 'conv2_w', 'conv2_b', 'fc3_w', 'fc3_b', 'fc4_w', 'fc4_b', 'out_w', 'out_b'):
+        setattr(net, f, 16)
+    lr = np.array([0, 2], dtype=np.int32)
+    ky = np.array([1, 2], dtype=np.uint64)
+    plan = np.zeros(1, dtype=np.dtype(lib.RnTrainPlan))
+    keep = (net, lr, ky, plan)
+
+    def episodes(gh, gd, per, stride):
+        return h.mfg_train_episodes_irl_pop(p, 4, p, p, 32, K, d, 3, 1, 1, 0, p, p, p, p, 1.0, p, 0, 0, 1, p, p, C.byref(net), per,
+                                            stride, gh, gd, p, p, p, p, p, p, p, None, p, 1 << 20, None)
+
+    def rollouts(gh, gd, per, stride):
+        return h.mfg_train_rollouts_irl_pop(p, 4, 32, K, d, 3, 1, 1, 0, p, p, p, p, 1.0, p, 0, 0, 0, p, p, C.byref(net), per, stride,
+                                            gh, gd, p, p, p, None, p, p, p, p, p, None, p, 1 << 20, None)
+
+    def forward(gh, gd, per, stride):
+        return h.mfg_reward_net_forward_pop(p, p, 8 * d, 8 * d * d, 8, d, C.byref(net), per, stride, gh, gd, K, lr.ctypes.data,
+                                            ky.ctypes.data, 2, 0, p, p, 128, None)
+
+    def steps(gh, gd, per, stride):      # (no per_learner_net here: the rows are always per learner)
+        return h.mfg_reward_net_train_steps_pop(p, p, p, stride, K, d, 5, 2, 3, 16, 32, gh, gd, p, p, 6, p, p, 6, plan.ctypes.data,
+                                                p, 0, 1, 1, 5, 5, 15, 5, 1.0, 0, 0.9, 0.999, 1e-8, p, p, 128, None)
+    return (episodes, rollouts, forward, steps), keep
+
+
+def test_one_copy_of_the_table_is_refused(lib):
+    pytest.importorskip('torch')
+    from discrete_mean_field_game_amd import ops
+    d, K = 15, 4
+    host, _ = ops.rn_geom_table([(n3, n4, 1.0 if 'dropout' not in reg else 0.4, 'l1l2' in reg) for reg, n3, n4 in M4])
+    stride = (int(lib.lib().mfg_reward_net_num_params(d, 5, 2, 3, 16, 32)) + 63) // 64 * 64
+    calls, _keep = _table_calls(lib, d, K)
+    for call in calls:
+        assert call(host.ctypes.data, None, 1, stride) == EINVAL, call.__name__
+        assert b'both copies' in lib.lib().mfg_last_error(), call.__name__
+        assert call(None, C.c_void_p(16), 1, stride) == EINVAL, call.__name__
+        assert b'both copies' in lib.lib().mfg_last_error(), call.__name__
+
+
+def test_table_refusals_through_the_unified_calls(lib):
+    """What the calls with a table refused under their own names they refuse with the same codes now: per_learner_net = 0, a
+    stride below the largest NP_k, an entry with n3 = 17, keep_prob = 0 -- from the host copy alone, before the device copy
+    (a dummy pointer here) is handed to a kernel."""
+    pytest.importorskip('torch')
+    from discrete_mean_field_game_amd import ops
+    d, K = 15, 4
+    geoms = [(n3, n4, 1.0 if 'dropout' not in reg else 0.4, 'l1l2' in reg) for reg, n3, n4 in M4]
+    good, _ = ops.rn_geom_table(geoms)
+    np_max = int(lib.lib().mfg_reward_net_num_params(d, 5, 2, 3, 16, 32))
+    stride = (np_max + 63) // 64 * 64
+    dev = C.c_void_p(16)
+
+    def table(k, **kw):
+        host = good.copy()
+        for f, val in kw.items():
+            host[k][f] = val
+        return host
+    calls, _keep = _table_calls(lib, d, K)
+    for call in calls:
+        if call.__name__ != 'steps':
+            assert call(good.ctypes.data, dev, 0, stride) == EINVAL, call.__name__
+            assert b'per_learner_net = 1' in lib.lib().mfg_last_error()
+        assert call(good.ctypes.data, dev, 1, np_max - 1) == EINVAL, call.__name__
+        assert b'below the largest parameter count' in lib.lib().mfg_last_error()
+        bad = table(1, n3=17)
+        assert call(bad.ctypes.data, dev, 1, stride) == EUNSUPPORTED, call.__name__
+        bad = table(2, keep_prob=0.0)
+        assert call(bad.ctypes.data, dev, 1, stride) == EINVAL, call.__name__
+        assert b'keep_prob' in lib.lib().mfg_last_error()

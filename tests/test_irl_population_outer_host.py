@@ -9,8 +9,7 @@ import pytest
 
 T = 15
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NEW = ('mfg_reward_net_train_steps_pop', 'mfg_reward_net_forward_pop', 'mfg_train_episodes_irl_pop_calls',
-       'mfg_train_rollouts_irl_pop_calls')
+NEW = ('mfg_reward_net_train_steps_pop', 'mfg_reward_net_forward_pop', 'mfg_train_episodes_irl_pop', 'mfg_train_rollouts_irl_pop')
 
 
 @pytest.fixture(scope='module')
@@ -71,9 +70,9 @@ def test_plan_layout_and_lr_t(lib):
         plan[i]['lr'] = [1e-4, 3e-3, 0.0][i % 3]
         plan[i]['adam_step'] = 1 + 7 * i
     dummy = C.c_void_p(16)
-    rc = lib.lib().mfg_reward_net_train_steps_pop(dummy, dummy, dummy, 7296, 3, 21, 5, 2, 3, 8, 4, dummy, dummy, 10, dummy,
-                                                 dummy, 10, plan.ctypes.data, dummy, 0, 2, 3, 5, 5, T, 5, 0.4, 1, 0.9, 0.999,
-                                                 1e-8, dummy, dummy, 1 << 30, None)
+    rc = lib.lib().mfg_reward_net_train_steps_pop(dummy, dummy, dummy, 7296, 3, 21, 5, 2, 3, 8, 4, None, None, dummy, dummy, 10,
+                                                 dummy, dummy, 10, plan.ctypes.data, dummy, 0, 2, 3, 5, 5, T, 5, 0.4, 1, 0.9,
+                                                 0.999, 1e-8, dummy, dummy, 1 << 30, None)
     assert rc == -4                          # MFG_EWORKSPACE: plan_dev
     for e in plan:
         t = int(e['adam_step'])
@@ -81,8 +80,8 @@ def test_plan_layout_and_lr_t(lib):
         assert np.float32(e['lr_t']) == ref
     bad = plan.copy()
     bad[5]['learner'] = 1                     # learner 1 twice in update 1 (plan_dev_bytes 0: nothing can reach the GPU)
-    assert lib.lib().mfg_reward_net_train_steps_pop(dummy, dummy, dummy, 7296, 3, 21, 5, 2, 3, 8, 4, dummy, dummy, 10, dummy,
-                                                   dummy, 10, bad.ctypes.data, dummy, 0, 2, 3, 5, 5, T, 5, 0.4, 1, 0.9,
+    assert lib.lib().mfg_reward_net_train_steps_pop(dummy, dummy, dummy, 7296, 3, 21, 5, 2, 3, 8, 4, None, None, dummy, dummy, 10,
+                                                   dummy, dummy, 10, bad.ctypes.data, dummy, 0, 2, 3, 5, 5, T, 5, 0.4, 1, 0.9,
                                                    0.999, 1e-8, dummy, dummy, 1 << 30, None) == -1
 
 
@@ -93,4 +92,4 @@ def test_new_bindings_declared_and_exported(lib):
         assert name + '(' in text
         assert name in lib.SIGNATURES
         assert getattr(handle, name) is not None
-    assert handle.mfg_abi_version() == 17
+    assert handle.mfg_abi_version() == 18

@@ -33,7 +33,7 @@ def test_argument_counts_match_header(lib):
 
 
 def test_abi_version_unchanged(lib):
-    assert lib.lib().mfg_abi_version() == 17
+    assert lib.lib().mfg_abi_version() == 18
 
 
 def test_wrappers_refuse_host_or_misshaped_arrays():

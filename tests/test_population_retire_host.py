@@ -45,7 +45,7 @@ def test_set_pop_control_declared_bound_and_exported(lib):
     decl = re.search(r'\bmfg_ctx_set_pop_control\s*\(([^;]*)\);', text, flags=re.S).group(1)
     assert len(decl.split(',')) == len(lib.SIGNATURES['mfg_ctx_set_pop_control'][1]) == 2
     assert getattr(lib.lib(), 'mfg_ctx_set_pop_control') is not None
-    assert lib.lib().mfg_abi_version() == 17          # an addition: the ABI number stays
+    assert lib.lib().mfg_abi_version() == 18
     assert lib.STATUS_MIXED_RANGE == 1 and lib.STATUS_POP_NONFINITE == 2
     assert re.search(r'MFG_STATUS_POP_NONFINITE\s*=\s*2', text)
 
