@@ -18,6 +18,7 @@ from __future__ import annotations
 
 import os
 import random
+import types
 import warnings
 
 import numpy as np
@@ -27,8 +28,25 @@ from . import _lib as L
 from . import ops
 from .mfg_ac2 import EPISODE_STEPS, _with_ctx, actor_critic
 from .networks import RewardNet, maxent_irl_loss
-from .parallel import all_reduce_gradients_, all_reduce_mean_flat_, broadcast_seed, current_shard, lr_scales
-from .reward_learning import RewardTrainer, TrajectoryStore
+from .parallel import all_reduce_gradients_, all_reduce_mean_flat_, broadcast_seed, lr_scales
+from .reward_learning import (RN_SEED_OFFSET, RT_SEED_OFFSET, RewardTrainer, TrajectoryStore, batch_fits, draw_batches,
+                              philox_call_key)
+
+
+def irl_train_path(update_every, rng, batch, world, has_reward_fn, tracing, write_all, net_supported):
+    """Which of its four episode flows AC_IRL.train takes (AC_IRL._episode_<name>; no tensor, no library call): 'native_rollout'
+    / 'native_step' (one native call per episode), 'fused_rollout' (one update per episode from Python) or 'stepwise' (the
+    per-step Python loop).  The native flows need Philox, one GPU, the reward network inside its HIP kernel's range and
+    nothing that looks at single steps (a reward_fn, tracing, write_all); the native rollout also draws its start states on
+    the device (batch > 1), while a batch-1 native episode takes them from the host draw."""
+    philox = rng == 'philox'
+    fused = update_every == 'rollout' and philox and not write_all
+    native = philox and world == 1 and not has_reward_fn and not tracing and not write_all and net_supported
+    if fused and native and batch > 1:
+        return 'native_rollout'
+    if update_every == 'step' and native:
+        return 'native_step'
+    return 'fused_rollout' if fused else 'stepwise'
 
 
 class AC_IRL(actor_critic):
@@ -235,10 +253,9 @@ class AC_IRL(actor_critic):
     def reward(self, pi, P):
         """r(pi, P) from the reward network: [B,d], [B,d,d] -> [B] (ac_irl.py:683)."""
         if ops.reward_net_supported(self.reward_net) and pi.is_cuda:
-            # fresh dropout masks per call: the FULL call counter goes into the 64-bit Philox key (no wrap-around within
-            # a run), the counter's sample index is the GLOBAL one (rank shard offset + n), so ranks draw different masks
+            # fresh dropout masks per call; the counter's sample index is the GLOBAL one (rank shard offset + n): ranks differ
             self._reward_calls += 1
-            key = ((self.seed + 0x5EED) ^ (self._reward_calls * 0x9E3779B97F4A7C15)) & 0xFFFFFFFFFFFFFFFF
+            key = philox_call_key(self.seed, RN_SEED_OFFSET, self._reward_calls)
             return ops.reward_net_forward(self.reward_net, pi.contiguous(), P.contiguous(), seed=key,
                                           sample_offset=int(self._reward_sample_offset))
         if not getattr(self, '_warned_reward_fallback', False):                  # shapes outside the kernel's range
@@ -267,184 +284,177 @@ class AC_IRL(actor_critic):
         overrides the reward network (used by the parity tests with a closed-form reward).
         first_episode: episodes already run before a resume: `max_episodes` MORE episodes are run, numbered
         first_episode+1 .. first_episode+max_episodes in the lr/(episode+1) schedule (the same meaning as in
-        actor_critic.train; the reference always starts at 1)."""
-        d, T = self.d, EPISODE_STEPS
+        actor_critic.train; the reference always starts at 1).  Every episode runs on the call's path (irl_train_path)."""
         if self.verbose:
             print('----- Starting train -----')
-        shard = current_shard(self.batch, self.group)
-        if shard.world > self.batch:
-            raise ValueError('batch=%d is smaller than the world size %d: every rank needs a trajectory'
-                             % (self.batch, shard.world))
-        F = ops.num_features(d)
-        G = torch.zeros(F + 3, dtype=torch.float64, device=self.device)
-        ws = ops.workspace(shard.local_batch, d, self.device)
-        dg = (torch.empty(shard.local_batch, dtype=torch.float64, device=self.device),
-              torch.empty(shard.local_batch, dtype=torch.float64, device=self.device))
-        rfn = reward_fn if reward_fn is not None else self.reward
-        Bl = shard.local_batch
-        # rollout(T=1) output buffers, reused every step (pi_last is a fresh tensor per step)
-        rbufs = {'pi_traj': torch.empty(Bl, 2, d, dtype=torch.float32, device=self.device),
-                 'P': torch.empty(Bl, 1, d, d, dtype=torch.float32, device=self.device),
-                 'delta': dg[0].view(Bl, 1), 'g': dg[1].view(Bl, 1)}
-        fused_episode = (self.update_every == 'rollout' and self.rng == 'philox' and not write_all)
-        if fused_episode:
-            ws_ep = ops.workspace(Bl * T, d, self.device)
-            ebufs = {'pi_traj': torch.empty(Bl, T + 1, d, dtype=torch.float32, device=self.device),
-                     'pi_last': torch.empty(Bl, d, dtype=torch.float32, device=self.device),
-                     'P': torch.empty(Bl, T, d, d, dtype=torch.float32, device=self.device),
-                     'reward': torch.empty(Bl * T, dtype=torch.float32, device=self.device),
-                     'delta': torch.empty(Bl, T, dtype=torch.float64, device=self.device),
-                     'g': torch.empty(Bl, T, dtype=torch.float64, device=self.device)}
-        # ... and with the reward network's HIP kernel on one GPU the whole episode is ONE native call (mfg_train_rollout_irl:
-        # start states drawn inside the rollout kernel, the network reads its states in place from pi_traj, sums + update)
-        native_rollout = (fused_episode and shard.world == 1 and reward_fn is None and self.trace is None
-                          and self.reward_net is not None and ops.reward_net_supported(self.reward_net)
-                          and self._device_draw())
-        # per-step updates on one GPU with the reward network's HIP kernel: the whole episode (15 x [sample + transition +
-        # score | reward net | batch sums + update]) is issued by native code (mfg_train_episode_irl)
-        native_episode = (self.update_every == 'step' and self.rng == 'philox' and shard.world == 1 and reward_fn is None
-                          and self.trace is None and not write_all and self.reward_net is not None
-                          and ops.reward_net_supported(self.reward_net))
-        if native_episode:
-            nbufs = dict(ops.episode_buffers(Bl, d, self.device), P=rbufs['P'], pi=torch.empty(Bl, d, dtype=torch.float32, device=self.device))
-        # per-episode return accumulators of the native paths: ONE zeroed buffer per train() call instead of a fill kernel per episode
-        ep_acc = torch.zeros(max_episodes + 1, dtype=torch.float64, device=self.device) if (native_rollout or native_episode) else None
-        prev_theta = float(self._theta.cpu()[0])
-        list_reward = []
+        shard = self._train_shard()
+        path = irl_train_path(self.update_every, self.rng, self.batch, shard.world, reward_fn is not None, self.trace is not None,
+                              bool(write_all), self.reward_net is not None and ops.reward_net_supported(self.reward_net))
+        run_episode = getattr(self, '_episode_' + path)
+        c = self._train_call(path, shard, max_episodes, gamma=gamma, write_all=write_all, first_episode=first_episode,
+                             rfn=reward_fn if reward_fn is not None else self.reward, consecutive=consecutive,
+                             stop_criteria=stop_criteria, files=(write_file, file_theta, file_pi, file_reward), list_reward=[])
+        c.prev_theta = float(self._theta.cpu()[0])
         episode = 0
-        pi = None
-        device_draw = self._device_draw()       # batched Philox runs: start states drawn on the device (mfg_draw_start)
         for episode in range(1 + first_episode, first_episode + max_episodes + 1):
             sc, sa = lr_scales(episode, constant)          # lr/(episode+1) with the 1-indexed episode (:700)
-            if native_rollout:
-                self._reward_calls += 1                    # the keys of ONE reward() call over the [B*T] transitions
-                key = ((self.seed + 0x5EED) ^ (self._reward_calls * 0x9E3779B97F4A7C15)) & 0xFFFFFFFFFFFFFFFF
-                total_reward = ep_acc[episode - first_episode:episode - first_episode + 1]
-                ops.train_rollout_irl(self._mat_pi0_dev, None, T, self._theta, self.shift, self.alpha_scale, self._w, gamma,
-                                      lr_critic * sc, lr_actor * sa, self.reward_net, G, ws_ep, ebufs, seed=self.seed,
-                                      first_step=self._rng_step, traj_offset=shard.traj_offset, rn_key=key,
-                                      rn_sample_offset=shard.traj_offset * T, reward_acc=total_reward, precision=self.precision)
-                self._rng_step += T
-                self._reward_sample_offset = shard.traj_offset * T
-                self._theta_is_array = True
-                pi = ebufs['pi_last']
-                list_reward.append(total_reward)           # (mean reward per transition; scaled by T where it is reported)
-                if self.check_finite:
-                    self._raise_if_not_finite(pi, episode)
-                if episode % consecutive == 0:
-                    self._report_irl(list_reward, consecutive, pi, write_file, file_theta, file_pi, file_reward, scale=float(T))
-                    list_reward = []
-                if stop_criteria != -1:
-                    cur = float(self._theta.cpu()[0])
-                    if abs(cur - prev_theta) < stop_criteria:
-                        break
-                    prev_theta = cur
-                continue
-            if native_episode and device_draw:
-                pi = nbufs['pi']                           # (output only: the start states are drawn inside the native call)
-            elif device_draw:
-                _, pi = ops.draw_start(self._mat_pi0_dev, Bl, self.seed, self._rng_step, shard.traj_offset)
-            else:
-                pi = ops.gather_start(self._mat_pi0_dev, self._draw_start(shard))       # ac_irl.py:655
-            discount = 1.0
-            total_reward = (ep_acc[episode - first_episode:episode - first_episode + 1] if native_episode
-                            else torch.zeros(1, dtype=torch.float64, device=self.device))
-            if fused_episode:
-                # one update per episode: theta and w are fixed over the 15 steps, so the whole episode is THREE launches:
-                # the fused rollout (running discount gamma^t, P of every step materialised for the network), one
-                # reward-net pass over all B*T transitions, one gradient pass that folds the rewards into delta
-                o = ops.rollout(pi, T, self._theta, self.shift, self.alpha_scale, w=self._w, gamma=gamma,
-                                reward_kind=L.REWARD_EXTERNAL, seed=self.seed, first_step=self._rng_step,
-                                traj_offset=shard.traj_offset, td=True, write_P=True, discount_pow=True,
-                                precision=self.precision, out=ebufs)
-                self._rng_step += T
-                states = o['pi_traj'][:, :T].reshape(Bl * T, d)
-                self._reward_sample_offset = shard.traj_offset * T
-                r = rfn(states, o['P'].view(Bl * T, d, d))
-                if shard.world == 1:
-                    ops.grad_apply(o['pi_traj'], o['delta'].view(-1), o['g'].view(-1), r, G, ws_ep, lr_critic * sc,
-                                   lr_actor * sa, self._w, self._theta, total_reward, T=T, add_reward=True)
-                else:
-                    ops.grad_accumulate(o['pi_traj'], o['delta'].view(-1), o['g'].view(-1), r, G, ws_ep, T=T, add_reward=True)
-                    all_reduce_gradients_(G, self.group)
-                    ops.apply_update(G, d, lr_critic * sc, lr_actor * sa, self._w, self._theta, total_reward)
-                total_reward = total_reward * T
-                self._theta_is_array = True
-                pi = o['pi_last']
-            if native_episode:
-                ops.train_episode_irl(pi, T, self._theta, self.shift, self.alpha_scale, self._w, gamma, lr_critic * sc,
-                                      lr_actor * sa, self.reward_net, G, ws, nbufs, seed=self.seed, first_step=self._rng_step,
-                                      traj_offset=shard.traj_offset, rn_seed=self.seed + 0x5EED, rn_call0=self._reward_calls,
-                                      rn_sample_offset=shard.traj_offset, reward_acc=total_reward, precision=self.precision,
-                                      mat_pi0=self._mat_pi0_dev if device_draw else None)
-                self._rng_step += T
-                self._reward_calls += T                    # the dropout-mask keys of T reward() calls were consumed
-                self._reward_sample_offset = shard.traj_offset
-                self._theta_is_array = True
-            for step in range(0 if (fused_episode or native_episode) else T):
-                acc = (self.update_every == 'rollout' and step > 0)
-                step_applied = False
-                if self.rng == 'philox':
-                    # ONE launch samples P, takes the transition and evaluates everything of the TD step that does not
-                    # need the reward (score g, gamma V(pi') - V(pi)); P is materialised for the reward network, whose
-                    # output is folded in by the gradient kernel (delta += r) -- no second pass over P
-                    o = ops.rollout(pi, 1, self._theta, self.shift, self.alpha_scale, w=self._w, gamma=discount,
-                                    reward_kind=L.REWARD_EXTERNAL, seed=self.seed, first_step=self._rng_step,
-                                    traj_offset=shard.traj_offset, td=True, write_P=True, precision=self.precision,
-                                    out=rbufs)
-                    self._rng_step += 1
-                    P = o['P'].view(shard.local_batch, d, d)
-                    pi_next = o['pi_last']
-                    if write_all:
-                        self._write_all(pi, P, step + 1)
-                    self._reward_sample_offset = shard.traj_offset
-                    r = rfn(pi, P)
-                    if self.update_every == 'step' and shard.world == 1:
-                        # sums + update in one launch (the step is core -> reward net -> this)
-                        ops.grad_apply(pi, dg[0], dg[1], r, G, ws, lr_critic * sc, lr_actor * sa, self._w, self._theta,
-                                       total_reward, add_reward=True)
-                        step_applied = True
-                    else:
-                        ops.grad_accumulate(pi, dg[0], dg[1], r, G, ws, add_reward=True, accumulate=acc)
-                else:
-                    P = self._sample(pi, shard.traj_offset, snapshot=False)
-                    pi_next, _ = ops.step_given_P(pi, P, want_reward=False)
-                    if write_all:
-                        self._write_all(pi, P, step + 1)
-                    self._reward_sample_offset = shard.traj_offset
-                    r = rfn(pi, P)
-                    ops.td_pg_accumulate(pi, pi_next, P, r, self._w, self._theta, self.shift, discount, G=G, ws=ws,
-                                         precision=self.precision, out=dg, accumulate=acc)
-                if self.update_every == 'step':
-                    if not step_applied:
-                        all_reduce_gradients_(G, self.group)
-                        ops.apply_update(G, d, lr_critic * sc, lr_actor * sa, self._w, self._theta, total_reward)
-                    self._theta_is_array = True
-                    if self.trace is not None:
-                        self.trace.append(float(self._theta.cpu()[0]))
-                discount = discount * gamma
-                pi = pi_next
-            if self.update_every == 'rollout' and not fused_episode:
-                all_reduce_gradients_(G, self.group)
-                ops.apply_update(G, d, lr_critic * sc, lr_actor * sa, self._w, self._theta, total_reward)
-                total_reward = total_reward * T
-                self._theta_is_array = True
-            list_reward.append(total_reward)
-            if self.check_finite:
-                self._raise_if_not_finite(pi, episode)
-            if episode % consecutive == 0:
-                self._report_irl(list_reward, consecutive, pi, write_file, file_theta, file_pi, file_reward)
-                list_reward = []
-            if stop_criteria != -1:
-                cur = float(self._theta.cpu()[0])
-                if abs(cur - prev_theta) < stop_criteria:
-                    break
-                prev_theta = cur
+            pi, total_reward = run_episode(c, episode, lr_critic * sc, lr_actor * sa)
+            if self._end_episode(c, episode, pi, total_reward):
+                break
         self.list_policies = (self.list_policies + [self.theta])[1:]            # record this policy (:731)
         self.episodes_run = episode
         self._check_status()
         if self.verbose:
             print('----- Exiting train at episode %d with theta %f -----' % (episode, float(np.ravel(self.theta)[0])))
+
+    def _train_call(self, path, shard, max_episodes, **call):
+        """The record of one train() call: its arguments, the shard and the device buffers of the chosen path alone, fresh per
+        call (G and the workspaces zeroed).  report_scale: the factor of the path's return entries at report time (the native
+        rollout books the mean reward per transition, x T where reported; the other rollout flows multiply per episode)."""
+        d, T, Bl, dev = self.d, EPISODE_STEPS, shard.local_batch, self.device
+        f32, f64 = dict(dtype=torch.float32, device=dev), dict(dtype=torch.float64, device=dev)
+        c = types.SimpleNamespace(shard=shard, G=torch.zeros(ops.num_features(d) + 3, **f64),
+                                  report_scale=float(T) if path == 'native_rollout' else 1.0, **call)
+        if path in ('native_rollout', 'fused_rollout'):     # the whole episode's transitions: [Bl, T] rows
+            c.ws = ops.workspace(Bl * T, d, dev)
+            c.bufs = {'pi_traj': torch.empty(Bl, T + 1, d, **f32), 'pi_last': torch.empty(Bl, d, **f32),
+                      'P': torch.empty(Bl, T, d, d, **f32), 'reward': torch.empty(Bl * T, **f32),
+                      'delta': torch.empty(Bl, T, **f64), 'g': torch.empty(Bl, T, **f64)}
+        else:                                               # one env step at a time
+            c.ws = ops.workspace(Bl, d, dev)
+            P = torch.empty(Bl, 1, d, d, **f32)
+            if path == 'native_step':
+                c.bufs = dict(ops.episode_buffers(Bl, d, dev), P=P, pi=torch.empty(Bl, d, **f32))
+            else:                                           # rollout(T=1) outputs, reused every step (pi_last is fresh per step)
+                c.dg = (torch.empty(Bl, **f64), torch.empty(Bl, **f64))
+                c.bufs = {'pi_traj': torch.empty(Bl, 2, d, **f32), 'P': P, 'delta': c.dg[0].view(Bl, 1), 'g': c.dg[1].view(Bl, 1)}
+        if path.startswith('native'):
+            # per-episode return accumulators: ONE zeroed buffer per train() call instead of a fill kernel per episode
+            c.ep_acc = torch.zeros(max_episodes + 1, **f64)
+        return c
+
+    def _start_states(self, c):
+        """The episode's start states [Bl, d]: drawn on the device in batched Philox runs, else the host draw (ac_irl.py:655)."""
+        if self._device_draw():
+            return ops.draw_start(self._mat_pi0_dev, c.shard.local_batch, self.seed, self._rng_step, c.shard.traj_offset)[1]
+        return ops.gather_start(self._mat_pi0_dev, self._draw_start(c.shard))
+
+    def _episode_native_rollout(self, c, episode, lrc, lra):
+        """One update per episode, the whole episode ONE native call (mfg_train_rollout_irl: start states drawn inside the
+        rollout kernel, the network reads its states in place from pi_traj, sums + update)."""
+        T, off = EPISODE_STEPS, c.shard.traj_offset
+        self._reward_calls += 1                            # the keys of ONE reward() call over the [B*T] transitions
+        key = philox_call_key(self.seed, RN_SEED_OFFSET, self._reward_calls)
+        total_reward = c.ep_acc[episode - c.first_episode:episode - c.first_episode + 1]
+        ops.train_rollout_irl(self._mat_pi0_dev, None, T, self._theta, self.shift, self.alpha_scale, self._w, c.gamma, lrc, lra,
+                              self.reward_net, c.G, c.ws, c.bufs, seed=self.seed, first_step=self._rng_step, traj_offset=off,
+                              rn_key=key, rn_sample_offset=off * T, reward_acc=total_reward, precision=self.precision)
+        self._rng_step += T
+        self._reward_sample_offset = off * T
+        self._theta_is_array = True
+        return c.bufs['pi_last'], total_reward
+
+    def _episode_native_step(self, c, episode, lrc, lra):
+        """Per-step updates, the whole episode (15 x [sample + transition + score | reward net | batch sums + update]) issued
+        by native code (mfg_train_episode_irl)."""
+        T, off = EPISODE_STEPS, c.shard.traj_offset
+        mat = self._mat_pi0_dev if self._device_draw() else None          # (given: the native call draws the start states)
+        pi = c.bufs['pi'] if mat is not None else self._start_states(c)
+        total_reward = c.ep_acc[episode - c.first_episode:episode - c.first_episode + 1]
+        ops.train_episode_irl(pi, T, self._theta, self.shift, self.alpha_scale, self._w, c.gamma, lrc, lra, self.reward_net, c.G,
+                              c.ws, c.bufs, seed=self.seed, first_step=self._rng_step, traj_offset=off,
+                              rn_seed=self.seed + RN_SEED_OFFSET, rn_call0=self._reward_calls, rn_sample_offset=off,
+                              reward_acc=total_reward, precision=self.precision, mat_pi0=mat)
+        self._rng_step += T
+        self._reward_calls += T                            # the dropout-mask keys of T reward() calls were consumed
+        self._reward_sample_offset = off
+        self._theta_is_array = True
+        return pi, total_reward
+
+    def _episode_fused_rollout(self, c, episode, lrc, lra):
+        """One update per episode: theta and w are fixed over the 15 steps, so the whole episode is THREE launches: the fused
+        rollout (running discount gamma^t, P of every step materialised for the network), one reward pass over all B*T
+        transitions, one gradient pass that folds the rewards into delta (several ranks: sums | all-reduce | update)."""
+        d, T, shard, Bl = self.d, EPISODE_STEPS, c.shard, c.shard.local_batch
+        pi = self._start_states(c)
+        total_reward = torch.zeros(1, dtype=torch.float64, device=self.device)
+        o = ops.rollout(pi, T, self._theta, self.shift, self.alpha_scale, w=self._w, gamma=c.gamma,
+                        reward_kind=L.REWARD_EXTERNAL, seed=self.seed, first_step=self._rng_step, traj_offset=shard.traj_offset,
+                        td=True, write_P=True, discount_pow=True, precision=self.precision, out=c.bufs)
+        self._rng_step += T
+        self._reward_sample_offset = shard.traj_offset * T
+        r = c.rfn(o['pi_traj'][:, :T].reshape(Bl * T, d), o['P'].view(Bl * T, d, d))
+        sums = (o['pi_traj'], o['delta'].view(-1), o['g'].view(-1), r, c.G, c.ws)
+        if shard.world == 1:
+            ops.grad_apply(*sums, lrc, lra, self._w, self._theta, total_reward, T=T, add_reward=True)
+        else:
+            ops.grad_accumulate(*sums, T=T, add_reward=True)
+            all_reduce_gradients_(c.G, self.group)
+            ops.apply_update(c.G, d, lrc, lra, self._w, self._theta, total_reward)
+        self._theta_is_array = True
+        return o['pi_last'], total_reward * T
+
+    def _episode_stepwise(self, c, episode, lrc, lra):
+        """The per-step Python loop (the one that retraces the reference): rollout(T=1) or the NumPy sampler, the reward
+        function, and an update per step or the sums of the episode with one update at its end."""
+        d, shard, dg, per_step = self.d, c.shard, c.dg, self.update_every == 'step'
+        one_launch = per_step and self.rng == 'philox' and shard.world == 1      # sums + update: core -> reward net -> this
+        pi, discount = self._start_states(c), 1.0
+        total_reward = torch.zeros(1, dtype=torch.float64, device=self.device)
+        for step in range(EPISODE_STEPS):
+            acc = not per_step and step > 0
+            if self.rng == 'philox':
+                # ONE launch samples P, takes the transition and evaluates what the TD step needs without the reward (score g,
+                # gamma V(pi') - V(pi)); the reward of the materialised P is folded in by the gradient kernel (delta += r)
+                o = ops.rollout(pi, 1, self._theta, self.shift, self.alpha_scale, w=self._w, gamma=discount,
+                                reward_kind=L.REWARD_EXTERNAL, seed=self.seed, first_step=self._rng_step,
+                                traj_offset=shard.traj_offset, td=True, write_P=True, precision=self.precision, out=c.bufs)
+                self._rng_step += 1
+                P, pi_next = o['P'].view(shard.local_batch, d, d), o['pi_last']
+            else:
+                P = self._sample(pi, shard.traj_offset, snapshot=False)
+                pi_next, _ = ops.step_given_P(pi, P, want_reward=False)
+            if c.write_all:
+                self._write_all(pi, P, step + 1)
+            self._reward_sample_offset = shard.traj_offset
+            r = c.rfn(pi, P)
+            if one_launch:
+                ops.grad_apply(pi, dg[0], dg[1], r, c.G, c.ws, lrc, lra, self._w, self._theta, total_reward, add_reward=True)
+            elif self.rng == 'philox':
+                ops.grad_accumulate(pi, dg[0], dg[1], r, c.G, c.ws, add_reward=True, accumulate=acc)
+            else:
+                ops.td_pg_accumulate(pi, pi_next, P, r, self._w, self._theta, self.shift, discount, G=c.G, ws=c.ws,
+                                     precision=self.precision, out=dg, accumulate=acc)
+            if per_step:
+                if not one_launch:
+                    all_reduce_gradients_(c.G, self.group)
+                    ops.apply_update(c.G, d, lrc, lra, self._w, self._theta, total_reward)
+                self._theta_is_array = True
+                if self.trace is not None:
+                    self.trace.append(float(self._theta.cpu()[0]))
+            discount = discount * c.gamma
+            pi = pi_next
+        if not per_step:
+            all_reduce_gradients_(c.G, self.group)
+            ops.apply_update(c.G, d, lrc, lra, self._w, self._theta, total_reward)
+            total_reward = total_reward * EPISODE_STEPS
+            self._theta_is_array = True
+        return pi, total_reward
+
+    def _end_episode(self, c, episode, pi, total_reward):
+        """The end of every episode, whichever path ran it: book the return, the `consecutive`-episode report, the stop
+        criterion |theta - prev_theta| < stop_criteria (:726; its one host read per episode).  True: stop."""
+        c.list_reward.append(total_reward)
+        if self.check_finite:
+            self._raise_if_not_finite(pi, episode)
+        if episode % c.consecutive == 0:
+            self._report_irl(c.list_reward, c.consecutive, pi, *c.files, scale=c.report_scale)
+            c.list_reward = []
+        if c.stop_criteria == -1:
+            return False
+        cur, prev = float(self._theta.cpu()[0]), c.prev_theta
+        c.prev_theta = cur
+        return abs(cur - prev) < c.stop_criteria
 
     def _report_irl(self, list_reward, consecutive, pi, write_file, file_theta, file_pi, file_reward, scale=1.0):
         """The `consecutive`-episode report of train() (ac_irl.py:714-724): average episode return, theta, one final state."""
@@ -595,26 +605,16 @@ class AC_IRL(actor_critic):
     @_with_ctx
     def update_reward(self, summary=False, iteration=0):
         """One gradient step on the reward network (ac_irl.py:804-846).  The batch is drawn with the reference's
-        `random.sample` calls -- on INDEX ranges: random.sample(population, k) picks positions from len(population) alone, so
-        the same trajectories are chosen and the host stream advances identically -- and the update itself is
-        mfg_reward_net_train_step on the device stores: two launches, nothing copied, no synchronisation."""
+        `random.sample` calls on index ranges (reward_learning.draw_batches, from the module `random` stream) and the update
+        itself is mfg_reward_net_train_step on the device stores: two launches, nothing copied, no synchronisation."""
         self._resync_stores()
         ragged = getattr(self, '_demo_ragged', False)
         nd_all, ng_all = (len(self._demo_list) if ragged else len(self._demo_store)), len(self._gen_store)
-        if nd_all >= self.num_demo_samples:
-            demo_idx = random.sample(range(nd_all), self.num_demo_samples)
-        else:
-            demo_idx = list(range(nd_all))
-        if ng_all >= self.num_gen_samples:
-            gen_idx = random.sample(range(ng_all), self.num_gen_samples)
-        else:
-            gen_idx = list(range(ng_all))
+        (demo_idx, gen_idx), = draw_batches(random, nd_all, ng_all, 1, self.num_demo_samples, self.num_gen_samples)
         self._reward_train_calls += 1
-        n_tr = (len(demo_idx) + len(gen_idx)) * EPISODE_STEPS
-        fits = n_tr <= 2048 and n_tr * (1 + self.n_fc3) * 4 <= 60 * 1024            # limits of mfg_reward_net_train_step's combine kernel
-        if (self._trainer is not None and fits and not ragged and len(demo_idx) <= L.RN_TRAIN_MAX_TRAJ
-                and len(gen_idx) <= L.RN_TRAIN_MAX_TRAJ):
-            key = ((self.seed + 0x7EA1) ^ (self._reward_train_calls * 0x9E3779B97F4A7C15)) & 0xFFFFFFFFFFFFFFFF
+        fits = batch_fits(len(demo_idx), len(gen_idx), self.n_fc3)
+        if self._trainer is not None and fits and not ragged:
+            key = philox_call_key(self.seed, RT_SEED_OFFSET, self._reward_train_calls)
             dist = torch.distributed
             multi = dist.is_available() and dist.is_initialized() and dist.get_world_size(self.group) > 1
             self._trainer.step(self._demo_store, [self._demo_store.rows[i] for i in demo_idx], self._gen_store,

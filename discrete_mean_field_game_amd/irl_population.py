@@ -58,24 +58,15 @@ from .ac_irl import AC_IRL
 from .mfg_ac2 import EPISODE_STEPS
 from .networks import RewardNet
 from .population import _Population, _with_ctx, broadcast
-from .reward_learning import RewardTrainer, StackedTrajectoryStore, TrajectoryStore
+from .reward_learning import (RN_SEED_OFFSET, RT_SEED_OFFSET, RewardTrainer, StackedTrajectoryStore, TrajectoryStore,
+                              batch_fits, draw_batches, philox_call_key)      # (the rules shared with AC_IRL)
 
 # the tensors of mfg_reward_net_t, in the order of the struct, and the module parameter each one comes from
 NET_TENSORS = (('conv1_w', 'conv1.weight'), ('conv1_b', 'conv1.bias'), ('conv2_w', 'conv2.weight'), ('conv2_b', 'conv2.bias'),
                ('fc3_w', 'fc3.weight'), ('fc3_b', 'fc3.bias'), ('fc4_w', 'fc4.weight'), ('fc4_b', 'fc4.bias'),
                ('out_w', 'out.weight'), ('out_b', 'out.bias'))
-RN_SEED_OFFSET = 0x5EED      # AC_IRL's dropout key: (seed + 0x5EED) ^ (call x 0x9E3779B97F4A7C15), ac_irl.py reward()
-RT_SEED_OFFSET = 0x7EA1      # ... and that of the training batches: (seed + 0x7EA1) ^ (train call x ...), AC_IRL.update_reward
-KEY_MUL, MASK64 = 0x9E3779B97F4A7C15, 0xFFFFFFFFFFFFFFFF
 NUM_DEMO_SAMPLES = NUM_GEN_SAMPLES = 5     # AC_IRL.num_demo_samples / num_gen_samples
 PARAM_ALIGN = 64             # floats: one learner's flat parameter row is padded to this (keeps every fc3_w 8-byte aligned)
-
-
-def batch_fits(n_demo, n_gen, n_fc3, steps=EPISODE_STEPS):
-    """True when an update_reward batch is inside mfg_reward_net_train_step's limits (AC_IRL.update_reward's `fits`)."""
-    n_tr = (n_demo + n_gen) * steps
-    return (n_tr <= 2048 and n_tr * (1 + n_fc3) * 4 <= 60 * 1024 and n_demo <= L.RN_TRAIN_MAX_TRAJ
-            and n_gen <= L.RN_TRAIN_MAX_TRAJ)
 
 
 def check_demonstrations(demonstrations, d):
@@ -92,17 +83,6 @@ def check_demonstrations(demonstrations, d):
     if s.shape[2] != d or a.shape[2:] != (d, d):
         raise ValueError('demonstrations: states of %d entries / actions of %d x %d expected' % (d, d, d))
     return s, a
-
-
-def draw_batches(rng, nd_all, ng_all, n_updates, n_demo=NUM_DEMO_SAMPLES, n_gen=NUM_GEN_SAMPLES):
-    """The logical trajectory indices of `n_updates` update_reward calls drawn from random.Random `rng`: AC_IRL.update_reward's
-    random.sample calls on index ranges (demonstrations, then generated, per update)."""
-    out = []
-    for _ in range(n_updates):
-        di = rng.sample(range(nd_all), n_demo) if nd_all >= n_demo else list(range(nd_all))
-        gi = rng.sample(range(ng_all), n_gen) if ng_all >= n_gen else list(range(ng_all))
-        out.append((di, gi))
-    return out
 
 
 def _check_common(K, d, batch, update_every, precision):
@@ -412,11 +392,10 @@ class AC_IRLPopulation(_Population):
         grow = np.asarray(self._gen_store.rows, dtype=np.int32)
         for s_, k in enumerate(active):           # (column-wise: the host side is one random.sample pair per update)
             batches = draw_batches(self._random[k], nd_all, ng_all, n_updates)
-            seed_k = int(self.seeds[k]) + RT_SEED_OFFSET
             c0 = int(self._reward_train_calls[k])
             col = plan[:, s_]
             col['learner'] = k
-            col['key'] = [(seed_k ^ ((c0 + 1 + u) * KEY_MUL)) & MASK64 for u in range(n_updates)]
+            col['key'] = [philox_call_key(self.seeds[k], RT_SEED_OFFSET, c0 + 1 + u) for u in range(n_updates)]
             col['lr'] = float(self.lr_reward[k])
             col['adam_step'] = int(self._adam_step[k]) + 1 + np.arange(n_updates)
             col['demo_rows'][:, :nd] = drow[np.array([b[0] for b in batches], dtype=np.int64).reshape(n_updates, nd)]
@@ -466,7 +445,7 @@ class AC_IRLPopulation(_Population):
                 outs.append(None)
                 continue
             self._calls_k[active] += 1
-            keys = [((int(self.seeds[k]) + RN_SEED_OFFSET) ^ (int(self._calls_k[k]) * KEY_MUL)) & MASK64 for k in active]
+            keys = [philox_call_key(self.seeds[k], RN_SEED_OFFSET, self._calls_k[k]) for k in active]
             outs.append(self._forward(st, ac, active, keys))
         zero = torch.zeros((), dtype=torch.float64, device=self.device)
         for r in outs:
@@ -546,7 +525,7 @@ class AC_IRLPopulation(_Population):
                                   torch.from_numpy(self._test_np[1]).reshape(-1, d, d).contiguous().to(self.device))
             ts, ta = self._test_dev
             self._calls_k[active] += 1
-            keys = [((int(self.seeds[k]) + RN_SEED_OFFSET) ^ (int(self._calls_k[k]) * KEY_MUL)) & MASK64 for k in active]
+            keys = [philox_call_key(self.seeds[k], RN_SEED_OFFSET, self._calls_k[k]) for k in active]
             r = self._forward(ts, ta, active, keys)
             host = torch.stack([r[k].double().sum() for k in active]).cpu().numpy()
             out[active, 1] = [float(v) / ts.shape[0] for v in host]

@@ -26,6 +26,7 @@ There is no CPU fallback: every numeric method calls the C ABI in include/mfg_hi
 """
 from __future__ import annotations
 
+import functools
 import os
 import warnings
 
@@ -49,8 +50,6 @@ def _with_ctx(method):
     so that two instances on one device cannot stop each other (include/mfg_hip.h, mfg_ctx_bind).  The binding the calling
     thread had before is restored on the way out: free-function ops.* calls and other instances' unbound reads made afterwards
     do not report into whichever instance happened to run last."""
-    import functools
-
     @functools.wraps(method)
     def bound(self, *args, **kwargs):
         prev = self._ctx.bind_scoped()
@@ -438,6 +437,14 @@ class actor_critic:
             idx = idx[shard.traj_offset:shard.traj_offset + shard.local_batch]
         return torch.as_tensor(idx.astype(np.int32), device=self.device)
 
+    def _train_shard(self):
+        """This rank's shard of the batch for a train() call; every rank needs a trajectory."""
+        shard = current_shard(self.batch, self.group)
+        if shard.world > self.batch:
+            raise ValueError('batch=%d is smaller than the world size %d: every rank needs a trajectory'
+                             % (self.batch, shard.world))
+        return shard
+
     @_with_ctx
     def train(self, num_episodes=4000, gamma=1, constant=0, lr_critic=0.1, lr_actor=0.001, consecutive=100,
               file_theta='results/theta.csv', file_pi='results/pi.csv', file_reward='results/reward.csv',
@@ -447,11 +454,8 @@ class actor_critic:
         first_episode: episode number the 1/(episode+1) learning-rate schedule starts from (resume after
         load_state_dict)."""
         d, T = self.d, self.episode_steps
-        shard = current_shard(self.batch, self.group)
+        shard = self._train_shard()
         Bl = shard.local_batch
-        if shard.world > self.batch:
-            raise ValueError('batch=%d is smaller than the world size %d: every rank needs a trajectory'
-                             % (self.batch, shard.world))
         F = ops.num_features(d)
         # device buffers: allocated (and the workspace zeroed) once per shape, reused by later train() calls -- the outer
         # loops of the IRL class and resumed runs call train() many times

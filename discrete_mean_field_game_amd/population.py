@@ -27,7 +27,6 @@ every learner, stopped or not.
 """
 from __future__ import annotations
 
-import functools
 import os
 
 import numpy as np
@@ -35,7 +34,7 @@ import torch
 
 from . import _lib as L
 from . import ops
-from .mfg_ac2 import EPISODE_STEPS, actor_critic
+from .mfg_ac2 import EPISODE_STEPS, _with_ctx, actor_critic
 
 REWARDS = {'mfg_ac2': L.REWARD_MFG_AC2, 'synthetic': L.REWARD_SYNTHETIC}
 
@@ -239,18 +238,6 @@ def gridsearch(theta_range, shift_range, alpha_range, indir, outfile, *, d=21, s
     if verbose:
         print(list_tuples)
     return list_tuples
-
-
-def _with_ctx(method):
-    """Run a method with the instance's own context bound (as actor_critic's public methods do)."""
-    @functools.wraps(method)
-    def bound(self, *args, **kwargs):
-        prev = self._ctx.bind_scoped()
-        try:
-            return method(self, *args, **kwargs)
-        finally:
-            self._ctx.restore(prev)
-    return bound
 
 
 class _Population:

@@ -18,6 +18,36 @@ import numpy as np
 import torch
 
 from . import _lib as L
+from .mfg_ac2 import EPISODE_STEPS
+
+# The rules AC_IRL and AC_IRLPopulation share (bit equality of the two rests on them): a call's Philox key, an update's batch.
+RN_SEED_OFFSET = 0x5EED      # dropout masks of a reward() call: key = philox_call_key(seed, RN_SEED_OFFSET, reward call number)
+RT_SEED_OFFSET = 0x7EA1      # ... and of an update_reward's training batch: (seed, RT_SEED_OFFSET, update_reward call number)
+
+
+def philox_call_key(seed, offset, call):
+    """The 64-bit Philox key of call number `call`: (seed + offset) ^ (call x 0x9E3779B97F4A7C15) mod 2^64.  The FULL call
+    counter goes into the key (no wrap-around within a run)."""
+    return ((int(seed) + offset) ^ (int(call) * 0x9E3779B97F4A7C15)) & 0xFFFFFFFFFFFFFFFF
+
+
+def batch_fits(n_demo, n_gen, n_fc3, steps=EPISODE_STEPS):
+    """True when an update_reward batch fits mfg_reward_net_train_step: 2 048 transitions, 60 KB of LDS, RN_TRAIN_MAX_TRAJ per half."""
+    n_tr = (n_demo + n_gen) * steps
+    return (n_tr <= 2048 and n_tr * (1 + n_fc3) * 4 <= 60 * 1024 and n_demo <= L.RN_TRAIN_MAX_TRAJ
+            and n_gen <= L.RN_TRAIN_MAX_TRAJ)
+
+
+def draw_batches(rng, nd_all, ng_all, n_updates, n_demo=5, n_gen=5):
+    """The logical trajectory indices of `n_updates` update_reward calls drawn from `rng` (a random.Random, or the module), per
+    update demonstrations, then generated: the reference's random.sample calls (ac_irl.py:814-829) on INDEX ranges --
+    sample(population, k) picks positions from len(population) alone: the same trajectories, the same stream afterwards."""
+    out = []
+    for _ in range(n_updates):
+        di = rng.sample(range(nd_all), n_demo) if nd_all >= n_demo else list(range(nd_all))
+        gi = rng.sample(range(ng_all), n_gen) if ng_all >= n_gen else list(range(ng_all))
+        out.append((di, gi))
+    return out
 
 
 class TrajectoryStore:

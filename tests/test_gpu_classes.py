@@ -547,6 +547,84 @@ def test_native_irl_episode_equals_python_step_loop(dev, d, B, precision, reg):
     assert runs[0][0][0] != 8.64
 
 
+_REPORT_RUNS = {}       # (mode, variant) -> the logs of one run, shared by the cases of test_ac_irl_reports_per_path
+_REPORT_MEANS = {}      # mode -> the two window means of the K = 1 population
+
+
+def _report_irl_learner(mode):
+    """The learner of test_ac_irl_reports_per_path: d = 15, batch 24, 8 start rows, seed 5, the default dropout_l1l2 network
+    under a fixed torch seed (every call builds the identical object)."""
+    import random
+    np.random.seed(21); torch.manual_seed(21); random.seed(21)
+    ac = IRL(d=15, pi0=np.random.RandomState(39).dirichlet(np.ones(15), size=8), demonstrations=[], batch=24, rng='philox',
+             seed=5, update_every=mode, reg='dropout_l1l2', verbose=0)
+    with torch.no_grad():
+        for p in ac.reward_net.parameters():
+            if p.dim() == 1:
+                p.uniform_(-0.2, 0.2)
+    return ac
+
+
+def _report_run(mode, variant, folder):
+    """4 episodes, a report every 2: (theta lines, pi lines, reward lines, final theta, the 2-episode twin's theta)."""
+    if (mode, variant) not in _REPORT_RUNS:
+        os.makedirs(str(folder), exist_ok=True)
+        files = {n: os.path.join(str(folder), n + '.csv') for n in ('theta', 'pi', 'reward')}
+        thetas = []
+        for episodes in (4, 2):
+            ac = _report_irl_learner(mode)
+            if variant == 'trace':
+                ac.trace = []
+            ac.train(max_episodes=episodes, stop_criteria=-1, gamma=0.9, consecutive=2, file_theta=files['theta'],
+                     file_pi=files['pi'], file_reward=files['reward'], write_file=int(episodes == 4),
+                     reward_fn=ac.reward if variant == 'reward_fn' else None)
+            thetas.append(float(np.ravel(ac.theta)[0]))
+        lines = []
+        for n in ('theta', 'pi', 'reward'):
+            with open(files[n]) as f:
+                lines.append(f.read().strip().split('\n'))
+        _REPORT_RUNS[(mode, variant)] = tuple(lines) + tuple(thetas)
+    return _REPORT_RUNS[(mode, variant)]
+
+
+def _report_window_means(mode):
+    """The means of the two windows' per-episode returns as a K = 1 AC_IRLPopulation (same network, seed, w and mode) returns
+    them from train(4): a route that books the returns without AC_IRL.train."""
+    if mode not in _REPORT_MEANS:
+        from discrete_mean_field_game_amd.irl_population import AC_IRLPopulation
+        ac = _report_irl_learner(mode)
+        pop = AC_IRLPopulation([float(ac.theta)], ac.shift, ac.alpha_scale, 15, batch=24, reward_nets=[ac.reward_net], seeds=[5],
+                               w0=ac.w.reshape(1, -1), pi0=ac.mat_pi0, update_every=mode, device='cuda:0')
+        ret = pop.train(4, 0.9, False, 0.1, 0.001)
+        assert ret.shape == (1, 4) and pop.status() == 0
+        _REPORT_MEANS[mode] = (float(ret[0, 0:2].mean()), float(ret[0, 2:4].mean()))
+    return _REPORT_MEANS[mode]
+
+
+@pytest.mark.parametrize('mode,variant', [('step', 'native'), ('step', 'trace'), ('rollout', 'native'), ('rollout', 'reward_fn')])
+def test_ac_irl_reports_per_path(dev, tmp_path, mode, variant):
+    """The `consecutive`-episode report of AC_IRL.train on each of its four paths (native step, the per-step Python loop forced
+    by tracing, native rollout, the fused rollout in Python forced by reward_fn): every path books its episode returns its own
+    way (the native rollout unscaled with a factor T at report time, the others x T per episode), and the logged window
+    average must be the mean of the episode returns whichever way -- a lost or doubled x T shows at once.  The returns come
+    from a K = 1 population; '%.3e' rounds to at most 5e-4 relative, the differing association of the x T is an ulp: 1e-3."""
+    theta_l, pi_l, reward_l, theta_final, theta_half = _report_run(mode, variant, tmp_path / variant)
+    assert len(theta_l) == len(pi_l) == len(reward_l) == 2
+    assert all(len(line.split(',')) == 15 for line in pi_l)
+    assert theta_l[1] == '%.5e' % theta_final
+    assert theta_l[0] == '%.5e' % theta_half
+    means = _report_window_means(mode)
+    got = [float(line) for line in reward_l]
+    print('%s/%s: logged %r, population window means %r' % (mode, variant, reward_l, means))
+    for g, m in zip(got, means):
+        assert m != 0.0 and abs(g - m) <= 1e-3 * abs(m)
+    if variant != 'native':
+        # the Python flow against the native one of the same mode: two format roundings, the flows agree to ~1e-13
+        native = [float(line) for line in _report_run(mode, 'native', tmp_path / 'native')[2]]
+        for g, n in zip(got, native):
+            assert abs(g - n) <= 2e-3 * abs(n)
+
+
 @pytest.mark.parametrize('d,B,T,n3,precision', [(21, 300, 15, 8, 'mixed'), (21, 4096, 2, 8, 'mixed'), (21, 50, 1, 8, 'f64'),
                                                 (15, 130, 4, 16, 'mixed'), (21, 90, 3, 24, 'mixed'), (12, 40, 3, 8, 'mixed')])
 def test_irl_episode_with_drawn_start_states_equals_draw_then_episode(dev, d, B, T, n3, precision):
