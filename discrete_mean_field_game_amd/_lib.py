@@ -112,7 +112,11 @@ SIGNATURES = {
                                         C.POINTER(C.c_int32), _i32, _i32, _i32, C.c_float, _i32, _u64, _f64, _f64, _f64, _f64, _i64,
                                         _i32, _p, _p, _p, _sz, _p]),
     'mfg_reward_net_adam': (_i32, [_p, _p, _p, _p, _i64, _f64, _f64, _f64, _f64, _i64, _p]),
+    'mfg_traj_log_z_pop': (_i32, [_p, _p, _i64, C.POINTER(C.c_int32), _i32, _i32, _i32, _p, _i32, _p, _i32, _i32, _f64, _f64, _f64,
+                                 _f64, _p, _p, _sz, _p]),
 }
+# the importance-weighted training steps: the unweighted call's arguments with gen_log_z in front of the stream
+SIGNATURES['mfg_reward_net_train_step_z'] = (_i32, SIGNATURES['mfg_reward_net_train_step'][1][:-1] + [_p, _p])
 
 
 class RewardNetStruct(C.Structure):
@@ -160,6 +164,8 @@ SIGNATURES['mfg_reward_net_forward_pop'] = (_i32, [_p, _p, _i64, _i64, _i64, _i3
 SIGNATURES['mfg_reward_net_train_steps_pop'] = (_i32, [_p, _p, _p, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _p, _p, _p, _p,
                                                        _i64, _p, _p, _i64, _p, _p, _sz, _i32, _i32, _i32, _i32, _i32, _i32,
                                                        C.c_float, _i32, _f64, _f64, _f64, _p, _p, _sz, _p])
+
+SIGNATURES['mfg_reward_net_train_steps_pop_z'] = (_i32, SIGNATURES['mfg_reward_net_train_steps_pop'][1][:-1] + [_p, _p])
 
 
 class PopControlStruct(C.Structure):

@@ -54,10 +54,21 @@ class AC_IRL(actor_critic):
     def __init__(self, theta=8.64, shift=0, alpha_scale=1e4, d=15, lr_reward=1e-4, num_policies=10, c=2e11,
                  reg='dropout_l1l2', n_fc3=8, n_fc4=4, saved_network=None, use_tf=True, summarize=False, *,
                  pi0=None, pi0_test=None, demonstrations=None, demonstrations_test=None, batch=1, rng='philox',
-                 seed=0, update_every='step', precision='mixed', device=None, group=None, verbose=1, check_finite=False):
+                 seed=0, update_every='step', precision='mixed', device=None, group=None, verbose=1, check_finite=False,
+                 importance_weights=False):
+        """importance_weights: train the reward network on the loss as the reference WROTE it (ac_irl.py:404-405, commented
+        out there): every sampled trajectory of D_samp is weighted by z_j = [1/k sum_k q_k(tau_j)]^-1 over the policies of
+        `list_policies` (:292-379), carried as ln z in fp64 (see _gen_log_z; importance_log_weights() reads it).  Off, nothing
+        changes.  ln z of a 15-step trajectory is of the order -1e4 with a spread of tens between trajectories, so the weights
+        softmax(S + ln z) of a batch are often close to one-hot -- a property of the estimator, not of the arithmetic.  A
+        generated P with an exact zero gives q = 0 under every policy and ln z = +inf (as tf.distributions.Dirichlet.prob
+        would): the update that samples it turns the parameters NaN, as it would in the reference; nothing hides that, and
+        the loss values / check_finite report it."""
         super().__init__(theta=theta, shift=shift, alpha_scale=alpha_scale, d=d, pi0=pi0, batch=batch, rng=rng,
                          seed=seed, update_every=update_every, precision=precision, device=device, group=group,
                          verbose=verbose, check_finite=check_finite)
+        self.importance_weights = bool(importance_weights)
+        self._lz = self._lz_key = None                  # ln z of D_samp's physical rows and what it was computed from
         self.summarize = summarize
         self.theta_initial = theta                      # reset value used by outerloop (ac_irl.py:45, :942)
         self.lr_reward = lr_reward
@@ -601,6 +612,34 @@ class AC_IRL(actor_critic):
         out = lz if log else torch.exp(lz)
         return out.cpu().numpy()
 
+    def _gen_log_z(self):
+        """ln z [1, capacity] (fp64, device) of the PHYSICAL rows of D_samp under the current list_policies: calc_z(log=True)
+        of every stored trajectory in one launch (mfg_traj_log_z_pop with calc_z's parameters: alpha_scale 1, alpha floor
+        1 + 1e-6, p_floor 0, Pr(s_1) = 1 / num_start_samples).  Derived state, never saved: recomputed only when D_samp
+        (its version), list_policies, shift or num_start_samples changed since the last fill -- once per outer iteration, not
+        once per update.  Rows that hold no trajectory are NaN."""
+        st = self._gen_store
+        key = (st.version, int(st.state.shape[0]), tuple(float(np.ravel(t)[0]) for t in self.list_policies), float(self.shift),
+               int(self.num_start_samples))
+        if self._lz is None or key != self._lz_key:
+            f64 = dict(dtype=torch.float64, device=self.device)
+            lz = torch.full((1, st.state.shape[0]), float('nan'), **f64)
+            if st.rows:
+                ops.traj_log_z_pop(st.state, st.action, st.rows, torch.tensor([key[2]], **f64), torch.tensor([key[3]], **f64),
+                                   float(np.log(key[4])), out=lz)
+            self._lz, self._lz_key = lz, key
+        return self._lz
+
+    @_with_ctx
+    def importance_log_weights(self):
+        """ln z_j of the trajectories of D_samp in their logical (list_generated) order, a NumPy array [len(D_samp)]: what
+        update_reward adds to the trajectory returns with importance_weights=True (works with the flag off as well).
+        softmax of it over a batch shows how close to one-hot the weights are."""
+        self._resync_stores()
+        lz = self._gen_log_z()[0]
+        idx = torch.as_tensor(self._gen_store.rows, dtype=torch.int64, device=self.device)
+        return lz.index_select(0, idx).cpu().numpy()
+
     # ------------------------------------------------------------------ reward learning (ac_irl.py:804-897)
     @_with_ctx
     def update_reward(self, summary=False, iteration=0):
@@ -617,8 +656,11 @@ class AC_IRL(actor_critic):
             key = philox_call_key(self.seed, RT_SEED_OFFSET, self._reward_train_calls)
             dist = torch.distributed
             multi = dist.is_available() and dist.is_initialized() and dist.get_world_size(self.group) > 1
+            # (several ranks: the stores and the policy list are replicated, so every rank forms the same weights)
+            lz = self._gen_log_z()[0] if self.importance_weights else None
             self._trainer.step(self._demo_store, [self._demo_store.rows[i] for i in demo_idx], self._gen_store,
-                               [self._gen_store.rows[i] for i in gen_idx], self.num_demo_samples, key, grad_only=multi)
+                               [self._gen_store.rows[i] for i in gen_idx], self.num_demo_samples, key, grad_only=multi,
+                               gen_log_z=lz)
             if multi:
                 # replicated reward network: ONE all-reduce of the flat gradient, averaged; the ranks train on
                 # identical batches (_sync_host_sampler), so this only keeps them in lock-step
@@ -637,7 +679,10 @@ class AC_IRL(actor_critic):
         r_demo = self.reward_net(ds, da)
         r_gen = self.reward_net(gs, ga)
         reg = self.reward_net.regularization() if self.reward_net.use_l1l2 else None
-        loss, first, second = maxent_irl_loss(r_demo, r_gen, self.num_demo_samples, len(gen_idx), reg)
+        lz = None
+        if self.importance_weights and len(gen_idx):
+            lz = torch.as_tensor(self.calc_z([gens[i] for i in gen_idx], log=True), dtype=torch.float64, device=self.device)
+        loss, first, second = maxent_irl_loss(r_demo, r_gen, self.num_demo_samples, len(gen_idx), reg, log_z=lz)
         self.optimizer.zero_grad(set_to_none=True)
         loss.backward()
         self._all_reduce_reward_grads()

@@ -530,7 +530,12 @@ __device__ __forceinline__ float adam_param(float p, float g, float& m, float& v
 // slice order (fixed association: bit-reproducible).  The first version ran one thread per parameter over all 150 samples
 // with a load and an integer division per iteration: 30 us, all of it L2 latency.
 constexpr int RT_CP = WAVE, RT_CU = 38, RT_DZ = 8;  // RT_CU: one round covers 4 x 38 = 152 samples (the reference batch is 150; a second round of reads cost 4 us)
-__device__ __forceinline__ void rn_train_combine_body(const RtCombineArgs& a) {
+// Z: the importance-weighted loss (mfg_reward_net_train_step_z; the form ac_irl.py:404-406 comments out): trajectory j's
+// soft-max weight is formed from S_j + ln z_j, ln z_j = lz[gen_rows[j]] in fp64 (|ln z| ~ 1e4 with a spread of tens: an fp32
+// ln z is off by 5e-4 before it reaches expf, so the maximum is subtracted in fp64).  Z = false is the unweighted kernel:
+// lz and gen_rows are not read and the code is the one this file had before the weights existed.
+template <bool Z>
+__device__ __forceinline__ void rn_train_combine_body(const RtCombineArgs& a, const double* lz, const int32_t* gen_rows) {
   __shared__ float s_c[2 * RT_MAX_TRAJ];  // dL/dr per trajectory: demonstrations, then generated
   __shared__ float s_S[RT_MAX_TRAJ];
   __shared__ float s_stat[2];
@@ -574,6 +579,8 @@ __device__ __forceinline__ void rn_train_combine_body(const RtCombineArgs& a) {
   const int pc = live ? p : 0;
   const float w_old = a.params[pc];
   const float m_old = a.m ? a.m[pc] : 0.0f, v_old = a.v ? a.v[pc] : 0.0f;   // (uniform pointers: scalar branches)
+  double lz_mine = 0.0;  // (Z: the log-weight of this lane's trajectory, issued with the other early reads; ng >= 1 there)
+  if constexpr (Z) lz_mine = lz[gen_rows[tid < a.n_gen ? tid : 0]];
   // S_j = sum_t r[j, t] in step order (fixed association per trajectory), the first term's sum on another wave
 #pragma unroll
   for (int u = 0; u < 8; ++u)
@@ -593,6 +600,17 @@ __device__ __forceinline__ void rn_train_combine_body(const RtCombineArgs& a) {
   }
   __syncthreads();
   if (wv == 0) {  // soft-max over the generated trajectories (<= 64: one per lane) and log-mean-exp, wave-parallel
+    if constexpr (Z) {
+      // weights softmax_j(S_j + ln z_j): sum and maximum in fp64, the exponential and the normalising tree as below
+      const double Dj = lane < ng ? (double)s_S[lane] + lz_mine : -INFINITY;
+      double mx = Dj;
+#pragma unroll
+      for (int off = 32; off > 0; off >>= 1) mx = fmax(mx, __shfl_xor(mx, off, WAVE));
+      const float ej = lane < ng ? expf((float)(Dj - mx)) : 0.0f;
+      const float z = wave_sum_f32_dpp(ej);
+      if (lane < ng) s_c[nd + lane] = ej / z;
+      if (lane == 0) s_stat[0] = ng ? (float)(mx + log((double)z / (double)ng)) : 0.0f;  // = log( 1/M sum z_j exp S_j ), rounded once
+    } else {
     const float Sj = lane < ng ? s_S[lane] : -INFINITY;
     float mx = Sj;
 #pragma unroll
@@ -601,6 +619,7 @@ __device__ __forceinline__ void rn_train_combine_body(const RtCombineArgs& a) {
     const float z = wave_sum_f32_dpp(ej);
     if (lane < ng) s_c[nd + lane] = ej / z;
     if (lane == 0) s_stat[0] = ng ? mx + logf(z / (float)ng) : 0.0f;  // = log( 1/M sum exp S_j )
+    }
   }
   __syncthreads();
   // per-sample coefficient, and c_n dz3_n for the factored fc3_w gradient
@@ -664,10 +683,18 @@ __device__ __forceinline__ void rn_train_combine_body(const RtCombineArgs& a) {
   }
 }
 
-__global__ __launch_bounds__(RT_BLOCK) void k_rn_train_combine(RtCombineArgs a) { rn_train_combine_body(a); }
+__global__ __launch_bounds__(RT_BLOCK) void k_rn_train_combine(RtCombineArgs a) { rn_train_combine_body<false>(a, nullptr, nullptr); }
+
+// the weighted form: ln z [gen_capacity] and the generated rows of the batch (by value, as the sample kernel gets them)
+struct RtZ {
+  const double* log_z;
+  int32_t gen_rows[RT_MAX_TRAJ];
+};
+__global__ __launch_bounds__(RT_BLOCK) void k_rn_train_combine_z(RtCombineArgs a, RtZ z) { rn_train_combine_body<true>(a, z.log_z, z.gen_rows); }
 
 // population form: slot blockIdx.y updates learner plan[slot].learner with the plan's lr_t; stats [K][4]
-__global__ __launch_bounds__(RT_BLOCK) void k_rn_train_combine_pop(RtCombineArgs a, RtPop p) {
+template <bool Z>
+__device__ __forceinline__ void rn_train_combine_pop_body(RtCombineArgs a, RtPop p, const double* log_z, int64_t s_lz) {
   const mfg_rn_train_plan_t& e = p.plan[blockIdx.y];
   const int k = e.learner;
   RtCombineArgs b = a;
@@ -688,7 +715,14 @@ __global__ __launch_bounds__(RT_BLOCK) void k_rn_train_combine_pop(RtCombineArgs
     b.js = b.dz3 + (int64_t)N * ge.n3;
     b.a2 = b.js + (int64_t)N * Lk.ns;
   }
-  rn_train_combine_body(b);
+  // (weighted: learner k's log-weights at log_z + k s_lz, indexed by the plan entry's gen_rows)
+  rn_train_combine_body<Z>(b, Z ? log_z + s_lz * k : nullptr, Z ? e.gen_rows : nullptr);
+}
+__global__ __launch_bounds__(RT_BLOCK) void k_rn_train_combine_pop(RtCombineArgs a, RtPop p) {
+  rn_train_combine_pop_body<false>(a, p, nullptr, 0);
+}
+__global__ __launch_bounds__(RT_BLOCK) void k_rn_train_combine_pop_z(RtCombineArgs a, RtPop p, const double* log_z, int64_t s_lz) {
+  rn_train_combine_pop_body<true>(a, p, log_z, s_lz);
 }
 
 __global__ __launch_bounds__(RT_BLOCK) void k_rn_adam(float* params, float* m, float* v, const float* grad, int64_t n, float lr_t,
@@ -736,12 +770,15 @@ size_t mfg_reward_net_train_workspace_bytes(int d, int k1, int f2, int k2, int n
   return (size_t)(n_transitions * (1 + L.a2 + n3 + L.ns) + 4) * sizeof(float);
 }
 
-int mfg_reward_net_train_step(float* params, float* adam_m, float* adam_v, int d, int k1, int f2, int k2, int n3, int n4,
-                              const float* demo_state, const float* demo_action, const int32_t* demo_rows_host, int n_demo,
-                              const float* gen_state, const float* gen_action, const int32_t* gen_rows_host, int n_gen, int steps,
-                              int demo_divisor, float keep_prob, int l1l2, uint64_t seed, double lr, double beta1, double beta2,
-                              double eps, int64_t adam_step, int flags, float* grad, float* stats, void* workspace,
-                              size_t workspace_bytes, mfg_stream_t stream) {
+}  // extern "C"
+
+// mfg_reward_net_train_step (gen_log_z = NULL) and mfg_reward_net_train_step_z: one body
+static int rn_train_step(float* params, float* adam_m, float* adam_v, int d, int k1, int f2, int k2, int n3, int n4,
+                         const float* demo_state, const float* demo_action, const int32_t* demo_rows_host, int n_demo,
+                         const float* gen_state, const float* gen_action, const int32_t* gen_rows_host, int n_gen, int steps,
+                         int demo_divisor, float keep_prob, int l1l2, uint64_t seed, double lr, double beta1, double beta2,
+                         double eps, int64_t adam_step, int flags, float* grad, float* stats, void* workspace,
+                         size_t workspace_bytes, const double* gen_log_z, mfg_stream_t stream) {
   if (!params || !workspace || n_demo < 0 || n_gen < 0 || steps < 1 || demo_divisor < 1 || (n_demo && (!demo_state || !demo_action || !demo_rows_host)) ||
       (n_gen && (!gen_state || !gen_action || !gen_rows_host)))
     return set_error(MFG_EINVAL, "reward_net_train_step: null pointer / bad count");
@@ -803,8 +840,41 @@ int mfg_reward_net_train_step(float* params, float* adam_m, float* adam_v, int d
   c.apply = apply ? 1 : 0;
   if (apply) c.lr_t = adam_lr_t(lr, beta1, beta2, adam_step);
   c.beta1 = (float)beta1; c.beta2 = (float)beta2; c.eps = (float)eps;
-  hipLaunchKernelGGL(k_rn_train_combine, dim3((unsigned)((L.np + RT_CP - 1) / RT_CP)), dim3(RT_BLOCK), (size_t)N * (1 + n3) * sizeof(float), st, c);
+  const dim3 g2((unsigned)((L.np + RT_CP - 1) / RT_CP));
+  const size_t lds2 = (size_t)N * (1 + n3) * sizeof(float);
+  if (gen_log_z && n_gen) {  // (no generated trajectory: no weight to form)
+    RtZ z{};
+    z.log_z = gen_log_z;
+    for (int k = 0; k < n_gen; ++k) z.gen_rows[k] = gen_rows_host[k];
+    hipLaunchKernelGGL(k_rn_train_combine_z, g2, dim3(RT_BLOCK), lds2, st, c, z);
+  } else {
+    hipLaunchKernelGGL(k_rn_train_combine, g2, dim3(RT_BLOCK), lds2, st, c);
+  }
   return hipGetLastError() == hipSuccess ? MFG_OK : set_error(MFG_ELAUNCH, "reward_net_train_step: launch failed");
+}
+
+extern "C" {
+
+int mfg_reward_net_train_step(float* params, float* adam_m, float* adam_v, int d, int k1, int f2, int k2, int n3, int n4,
+                              const float* demo_state, const float* demo_action, const int32_t* demo_rows_host, int n_demo,
+                              const float* gen_state, const float* gen_action, const int32_t* gen_rows_host, int n_gen, int steps,
+                              int demo_divisor, float keep_prob, int l1l2, uint64_t seed, double lr, double beta1, double beta2,
+                              double eps, int64_t adam_step, int flags, float* grad, float* stats, void* workspace,
+                              size_t workspace_bytes, mfg_stream_t stream) {
+  return rn_train_step(params, adam_m, adam_v, d, k1, f2, k2, n3, n4, demo_state, demo_action, demo_rows_host, n_demo, gen_state,
+                       gen_action, gen_rows_host, n_gen, steps, demo_divisor, keep_prob, l1l2, seed, lr, beta1, beta2, eps,
+                       adam_step, flags, grad, stats, workspace, workspace_bytes, nullptr, stream);
+}
+
+int mfg_reward_net_train_step_z(float* params, float* adam_m, float* adam_v, int d, int k1, int f2, int k2, int n3, int n4,
+                                const float* demo_state, const float* demo_action, const int32_t* demo_rows_host, int n_demo,
+                                const float* gen_state, const float* gen_action, const int32_t* gen_rows_host, int n_gen, int steps,
+                                int demo_divisor, float keep_prob, int l1l2, uint64_t seed, double lr, double beta1, double beta2,
+                                double eps, int64_t adam_step, int flags, float* grad, float* stats, void* workspace,
+                                size_t workspace_bytes, const double* gen_log_z, mfg_stream_t stream) {
+  return rn_train_step(params, adam_m, adam_v, d, k1, f2, k2, n3, n4, demo_state, demo_action, demo_rows_host, n_demo, gen_state,
+                       gen_action, gen_rows_host, n_gen, steps, demo_divisor, keep_prob, l1l2, seed, lr, beta1, beta2, eps,
+                       adam_step, flags, grad, stats, workspace, workspace_bytes, gen_log_z, stream);
 }
 
 int mfg_reward_net_adam(float* params, float* adam_m, float* adam_v, const float* grad, int64_t n, double lr, double beta1,
@@ -816,16 +886,19 @@ int mfg_reward_net_adam(float* params, float* adam_m, float* adam_v, const float
   return hipGetLastError() == hipSuccess ? MFG_OK : set_error(MFG_ELAUNCH, "reward_net_adam: launch failed");
 }
 
+}  // extern "C"
+
 // (geom_host / geom_dev given: the table is checked first; the batch limits and the workspace slices are then those of its largest
 //  n3 / n4, which the kernels read per learner with keep_prob and l1l2 -- the arguments of those names are not read)
-int mfg_reward_net_train_steps_pop(float* params, float* adam_m, float* adam_v, int64_t param_stride, int K, int d, int k1, int f2,
-                                   int k2, int n3, int n4, const mfg_rn_geom_t* geom_host, const mfg_rn_geom_t* geom_dev,
-                                   const float* demo_state, const float* demo_action, int64_t demo_capacity,
-                                   const float* gen_state, const float* gen_action, int64_t gen_capacity,
-                                   mfg_rn_train_plan_t* plan_host, void* plan_dev, size_t plan_dev_bytes, int n_updates,
-                                   int n_active, int n_demo, int n_gen, int steps, int demo_divisor, float keep_prob, int l1l2,
-                                   double beta1, double beta2, double eps, float* stats, void* workspace, size_t workspace_bytes,
-                                   mfg_stream_t stream) {
+// mfg_reward_net_train_steps_pop (gen_log_z = NULL) and mfg_reward_net_train_steps_pop_z: one body
+static int rn_train_steps_pop(float* params, float* adam_m, float* adam_v, int64_t param_stride, int K, int d, int k1, int f2,
+                              int k2, int n3, int n4, const mfg_rn_geom_t* geom_host, const mfg_rn_geom_t* geom_dev,
+                              const float* demo_state, const float* demo_action, int64_t demo_capacity,
+                              const float* gen_state, const float* gen_action, int64_t gen_capacity,
+                              mfg_rn_train_plan_t* plan_host, void* plan_dev, size_t plan_dev_bytes, int n_updates,
+                              int n_active, int n_demo, int n_gen, int steps, int demo_divisor, float keep_prob, int l1l2,
+                              double beta1, double beta2, double eps, float* stats, void* workspace, size_t workspace_bytes,
+                              const double* gen_log_z, mfg_stream_t stream) {
   int64_t np_max = 0;  // (the longest row of the table)
   if (geom_host || geom_dev) {
     const char* why = "";
@@ -918,9 +991,42 @@ int mfg_reward_net_train_steps_pop(float* params, float* adam_m, float* adam_v, 
     p.plan = pd + u * n_active;
     if (L.a2 <= 4 * RT_BLOCK) hipLaunchKernelGGL((k_rn_train_sample_pop<5, 3, 2, 4>), g1, dim3(RT_BLOCK), lds, st, a, p);
     else hipLaunchKernelGGL((k_rn_train_sample_pop<5, 3, 2, 8>), g1, dim3(RT_BLOCK), lds, st, a, p);
-    hipLaunchKernelGGL(k_rn_train_combine_pop, g2, dim3(RT_BLOCK), (size_t)N * (1 + n3) * sizeof(float), st, c, p);
+    if (gen_log_z && n_gen)
+      hipLaunchKernelGGL(k_rn_train_combine_pop_z, g2, dim3(RT_BLOCK), (size_t)N * (1 + n3) * sizeof(float), st, c, p, gen_log_z, gen_capacity);
+    else
+      hipLaunchKernelGGL(k_rn_train_combine_pop, g2, dim3(RT_BLOCK), (size_t)N * (1 + n3) * sizeof(float), st, c, p);
   }
   return hipGetLastError() == hipSuccess ? MFG_OK : set_error(MFG_ELAUNCH, "reward_net_train_steps_pop: launch failed");
+}
+
+extern "C" {
+
+int mfg_reward_net_train_steps_pop(float* params, float* adam_m, float* adam_v, int64_t param_stride, int K, int d, int k1, int f2,
+                                   int k2, int n3, int n4, const mfg_rn_geom_t* geom_host, const mfg_rn_geom_t* geom_dev,
+                                   const float* demo_state, const float* demo_action, int64_t demo_capacity,
+                                   const float* gen_state, const float* gen_action, int64_t gen_capacity,
+                                   mfg_rn_train_plan_t* plan_host, void* plan_dev, size_t plan_dev_bytes, int n_updates,
+                                   int n_active, int n_demo, int n_gen, int steps, int demo_divisor, float keep_prob, int l1l2,
+                                   double beta1, double beta2, double eps, float* stats, void* workspace, size_t workspace_bytes,
+                                   mfg_stream_t stream) {
+  return rn_train_steps_pop(params, adam_m, adam_v, param_stride, K, d, k1, f2, k2, n3, n4, geom_host, geom_dev, demo_state,
+                            demo_action, demo_capacity, gen_state, gen_action, gen_capacity, plan_host, plan_dev, plan_dev_bytes,
+                            n_updates, n_active, n_demo, n_gen, steps, demo_divisor, keep_prob, l1l2, beta1, beta2, eps, stats,
+                            workspace, workspace_bytes, nullptr, stream);
+}
+
+int mfg_reward_net_train_steps_pop_z(float* params, float* adam_m, float* adam_v, int64_t param_stride, int K, int d, int k1, int f2,
+                                     int k2, int n3, int n4, const mfg_rn_geom_t* geom_host, const mfg_rn_geom_t* geom_dev,
+                                     const float* demo_state, const float* demo_action, int64_t demo_capacity,
+                                     const float* gen_state, const float* gen_action, int64_t gen_capacity,
+                                     mfg_rn_train_plan_t* plan_host, void* plan_dev, size_t plan_dev_bytes, int n_updates,
+                                     int n_active, int n_demo, int n_gen, int steps, int demo_divisor, float keep_prob, int l1l2,
+                                     double beta1, double beta2, double eps, float* stats, void* workspace, size_t workspace_bytes,
+                                     const double* gen_log_z, mfg_stream_t stream) {
+  return rn_train_steps_pop(params, adam_m, adam_v, param_stride, K, d, k1, f2, k2, n3, n4, geom_host, geom_dev, demo_state,
+                            demo_action, demo_capacity, gen_state, gen_action, gen_capacity, plan_host, plan_dev, plan_dev_bytes,
+                            n_updates, n_active, n_demo, n_gen, steps, demo_divisor, keep_prob, l1l2, beta1, beta2, eps, stats,
+                            workspace, workspace_bytes, gen_log_z, stream);
 }
 
 }  // extern "C"

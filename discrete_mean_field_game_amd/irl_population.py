@@ -30,7 +30,13 @@ Adam-step and reward-update counters are per-learner arrays; the Philox step and
 The reward updates of all learners run in the two launches per update of mfg_reward_net_train_steps_pop, each
 reward_iteration check is one population forward (mfg_reward_net_forward_pop) over the demonstrations and one over the
 learners' D_samp, plus one host read.  D_samp is generated as AC_IRL._generate_device does, one draw + one rollout launch per
-learner.  Out of scope: CSV / checkpoint files, a population state_dict, multi-GPU, calc_z and eval-set overrides.
+learner.  Out of scope: CSV / checkpoint files, a population state_dict, multi-GPU and eval-set overrides.
+
+importance_weights=True: every learner trains on the loss as the reference wrote it (ac_irl.py:404-405, commented out there),
+each generated trajectory weighted by z_j = [1/k sum_k q_k(tau_j)]^-1 over the learner's own policy FIFO (calc_z, :292-379).  The
+population keeps ln z [K, capacity] in fp64 beside the stacked D_samp, refreshes it with ONE mfg_traj_log_z_pop launch when
+D_samp or a FIFO changed (once per outer iteration) and hands it to mfg_reward_net_train_steps_pop_z; learner k still equals
+AC_IRL(..., importance_weights=True) with its settings bit for bit.  Off (the default) no `_z` symbol is called.
 
 Mixed populations (mixed_nets=True): the learners' networks may differ in n_fc3, n_fc4 and regulariser -- the three axes of
 the reference's sweep gridsearch.py:8-31.  Each learner's parameters are one flat row of a [K, stride] buffer in its OWN layout
@@ -147,7 +153,8 @@ class AC_IRLPopulation(_Population):
 
     def __init__(self, thetas, shifts=0.0, alpha_scales=1e4, d=15, *, batch, reward_nets, seeds=None, w0=None, pi0=None,
                  path_to_dir=None, update_every='step', precision='mixed', device=None, verbose=0, demonstrations=None,
-                 lr_reward=1e-4, num_policies=10, host_seeds=None, mixed_nets=False, demonstrations_test=None):
+                 lr_reward=1e-4, num_policies=10, host_seeds=None, mixed_nets=False, demonstrations_test=None,
+                 importance_weights=False):
         th = np.asarray(thetas, dtype=np.float64).reshape(-1)
         K = th.shape[0]
         geoms = None
@@ -252,6 +259,9 @@ class AC_IRLPopulation(_Population):
             self._adam_v = torch.zeros_like(self._flat)
         self._rt_stats = torch.zeros(K, 4, dtype=torch.float32, device=dev)
         self._rt_ws = self._rt_plan_dev = self._fw_scratch = None
+        # AC_IRL(importance_weights=True) for every learner: ln z [K, capacity] of the learners' D_samp (see _gen_log_z)
+        self.importance_weights = bool(importance_weights)
+        self._lz = self._lz_key = None
 
     # ------------------------------------------------------------------ state
     @property
@@ -358,7 +368,8 @@ class AC_IRLPopulation(_Population):
             ac = AC_IRL(float(self.thetas[k]), float(self.shifts[k]), float(self.alpha_scales[k]), self.d,
                         lr_reward=float(self.lr_reward[k]), num_policies=self.num_policies, reg=net.reg, n_fc3=net.fc3.out_features, n_fc4=net.fc4.out_features, pi0=self.mat_pi0,
                         demonstrations=[], batch=self.batch, seed=int(self.seeds[k]), update_every=self.update_every,
-                        precision=self.precision, device=self.device, verbose=self.verbose)
+                        precision=self.precision, device=self.device, verbose=self.verbose,
+                        importance_weights=self.importance_weights)
         ac.reward_net = net
         ac.create_training_method()
         return ac
@@ -378,6 +389,31 @@ class AC_IRLPopulation(_Population):
         if not batch_fits(nd, ng, self._rn_dims[4]):
             raise ValueError('update_reward batch of %d + %d trajectories is outside the HIP training step\'s limits' % (nd, ng))
         return nd, ng
+
+    def _gen_log_z(self):
+        """AC_IRL._gen_log_z for the population: ln z [K, capacity] (fp64, device) of every learner's D_samp rows under its own
+        policy FIFO (list_policies[k], uploaded as [K, num_policies]) and shift, ONE mfg_traj_log_z_pop launch per refresh;
+        recomputed only when D_samp, a FIFO, the shifts or the start table changed.  The launch covers all K learners: a failed
+        learner's row is computed from its unused store rows and never read (its updates are skipped)."""
+        st = self._gen_store
+        pol = np.ascontiguousarray(self.list_policies, dtype=np.float64).reshape(self.K, self.num_policies)
+        nss = int(self.mat_pi0.shape[0])
+        key = (st.version, st.capacity, pol.tobytes(), np.asarray(self.shifts, dtype=np.float64).tobytes(), nss)
+        if self._lz is None or key != self._lz_key:
+            lz = torch.full((self.K, st.capacity), float('nan'), dtype=torch.float64, device=self.device)
+            if st.rows:
+                ops.traj_log_z_pop(st.state, st.action, st.rows, torch.as_tensor(pol, device=self.device),
+                                   torch.as_tensor(np.asarray(self.shifts, dtype=np.float64), device=self.device),
+                                   float(np.log(nss)), out=lz)
+            self._lz, self._lz_key = lz, key
+        return self._lz
+
+    @_with_ctx
+    def importance_log_weights(self):
+        """ln z [K, len(D_samp)] of the learners' D_samp in logical order (AC_IRL.importance_log_weights per learner)."""
+        lz = self._gen_log_z()
+        idx = torch.as_tensor(self._gen_store.rows, dtype=torch.int64, device=self.device)
+        return lz.index_select(1, idx).cpu().numpy()
 
     def _train_rewards(self, active, n_updates):
         """n_updates update_reward calls of the learners `active` (store sizes fixed): the batches drawn from each learner's
@@ -416,7 +452,8 @@ class AC_IRLPopulation(_Population):
         ops.reward_net_train_steps_pop(self._flat, self._adam_m, self._adam_v, self._net_stride, self.K, self._rn_dims, (ds, da),
                                        (gs, ga), plan, n_updates, n_active, nd, ng, EPISODE_STEPS, NUM_DEMO_SAMPLES, keep,
                                        net.use_l1l2, self._rt_stats, self._rt_ws, self._rt_plan_dev,
-                                       RewardTrainer.BETA1, RewardTrainer.BETA2, RewardTrainer.EPS, geom=self._geom)
+                                       RewardTrainer.BETA1, RewardTrainer.BETA2, RewardTrainer.EPS, geom=self._geom,
+                                       gen_log_z=self._gen_log_z() if self.importance_weights else None)
 
     @_with_ctx
     def update_reward(self, learners=None):
@@ -608,13 +645,14 @@ def gridsearch_nets(points, d, net_seed=0):
 def gridsearch(list_reg=('dropout', 'l1l2', 'dropout_l1l2'), list_nfc3=range(4, 10, 2), list_nfc4=range(4, 10, 2), *,
                demonstrations, demonstrations_test=None, theta=6.5, shift=0, alpha_scale=1e4, d=15, batch, seed=0,
                net_seed=0, outfile='results/reward_gridsearch.csv', outerloop_kwargs=None, update_every='step',
-               precision='mixed', pi0=None, device=None, verbose=0, return_population=False):
+               precision='mixed', pi0=None, device=None, verbose=0, return_population=False, importance_weights=False):
     """The reference's sweep gridsearch.py:8-31 -- for every (reg, n_fc3, n_fc4): AC_IRL(theta, reg=..., n_fc3=..., n_fc4=...),
     outerloop(), test_reward_network(), one CSV line -- as ONE mixed population: point p is learner p, with the network of
     gridsearch_nets, Philox seed and host seed `seed + p`.  Runs outerloop(**outerloop_kwargs) and test_reward_network() once
     for all points and appends the reference's lines ('%s,%d,%d,%f,%f,%f,%f', theta = the point's final theta) to `outfile`
     (None: no file; its header is written when the file is created).  Returns the rows [(reg, n_fc3, n_fc4, train, test, gen,
-    theta), ...] in the reference's order, and the population as well with return_population=True."""
+    theta), ...] in the reference's order, and the population as well with return_population=True.
+    importance_weights: every point trains on the importance-weighted loss (AC_IRL(importance_weights=True))."""
     points = gridsearch_points(list_reg, list_nfc3, list_nfc4)
     if not points:
         raise ValueError('gridsearch: empty grid')
@@ -624,7 +662,7 @@ def gridsearch(list_reg=('dropout', 'l1l2', 'dropout_l1l2'), list_nfc3=range(4, 
     pop = AC_IRLPopulation([float(theta)] * K, shift, alpha_scale, d, batch=batch, reward_nets=nets, seeds=seeds, pi0=pi0,
                            update_every=update_every, precision=precision, device=device, verbose=verbose,
                            demonstrations=demonstrations, demonstrations_test=demonstrations_test, host_seeds=seeds,
-                           mixed_nets=True)
+                           mixed_nets=True, importance_weights=importance_weights)
     thetas = np.asarray(pop.outerloop(**dict(outerloop_kwargs or {})), dtype=np.float64).reshape(-1)
     avgs = np.asarray(pop.test_reward_network(), dtype=np.float64)
     rows = [(reg, n3, n4, float(avgs[p, 0]), float(avgs[p, 1]), float(avgs[p, 2]), float(thetas[p]))

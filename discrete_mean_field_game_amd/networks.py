@@ -17,6 +17,8 @@ module is checked against a NumPy restatement and hand-derived values only ("par
 """
 from __future__ import annotations
 
+import math
+
 import torch
 import torch.nn as nn
 import torch.nn.functional as Fnn
@@ -121,13 +123,22 @@ class RewardNet(nn.Module):
         return reg
 
 
-def maxent_irl_loss(reward_demo, reward_gen, num_demo_samples, num_sampled_trajectories, reg_loss=None, steps=15):
+def maxent_irl_loss(reward_demo, reward_gen, num_demo_samples, num_sampled_trajectories, reg_loss=None, steps=15, log_z=None):
     """Guided-cost-learning loss of ac_irl.py:390-413 (importance weights z disabled there, :404-406):
         -(1/N_demo) sum r_demo  +  log( (1/M) sum_traj exp( sum_t r_gen ) )  [+ sum reg].
+    log_z [M] (ln z_j of the sampled trajectories, AC_IRL.calc_z(log=True)): the weighted second term the reference wrote and
+    commented out (:404-405),  log( (1/M) sum_traj z_j exp( sum_t r_gen ) ), formed as a logsumexp of S_j + ln z_j in the
+    dtype of log_z (|ln z| ~ 1e4: the linear-space z overflows).  None: today's unweighted result.
     Returns (loss, first_term, second_term)."""
     first = -1.0 / num_demo_samples * reward_demo.sum()
     per_traj = reward_gen.reshape(num_sampled_trajectories, steps).sum(dim=1)
-    second = torch.log(1.0 / num_sampled_trajectories * torch.exp(per_traj).sum())
+    if log_z is None:
+        second = torch.log(1.0 / num_sampled_trajectories * torch.exp(per_traj).sum())
+    else:
+        lz = torch.as_tensor(log_z, device=per_traj.device)
+        lz = lz.reshape(-1) if lz.is_floating_point() else lz.reshape(-1).double()
+        second = (torch.logsumexp(per_traj.to(lz.dtype) + lz, dim=0)
+                  - math.log(num_sampled_trajectories)).to(per_traj.dtype)
     loss = first + second
     if reg_loss is not None:
         loss = loss + reg_loss

@@ -844,12 +844,15 @@ def rn_train_plan(n):
 
 
 def reward_net_train_steps_pop(params, m, v, param_stride, K, dims, demo, gen, plan, n_updates, n_active, n_demo, n_gen, steps,
-                               demo_divisor, keep_prob, l1l2, stats, ws, plan_dev, beta1=0.9, beta2=0.999, eps=1e-8, geom=None):
+                               demo_divisor, keep_prob, l1l2, stats, ws, plan_dev, beta1=0.9, beta2=0.999, eps=1e-8, geom=None,
+                               gen_log_z=None):
     """mfg_reward_net_train_steps_pop: n_updates update_reward steps of n_active learners.  params / m / v [K, param_stride] f32,
     dims = (d, k1, f2, k2, n3, n4), demo = (state [rows,T,d], action [rows,T,d,d]) shared, gen = (state [K,cap,T,d], action
     [K,cap,T,d,d]), plan = rn_train_plan(n_updates * n_active), stats [K,4] f32, ws / plan_dev device byte buffers (uint8).
     geom: a per-learner geometry table (rn_geom_table): n3, n4, keep_prob and l1l2 come from the table (dims[4:], keep_prob and
-    l1l2 are not read), rows hold learner k's own layout."""
+    l1l2 are not read), rows hold learner k's own layout.
+    gen_log_z: fp64 [K, cap], the learners' importance log-weights (traj_log_z_pop) -- the call is then
+    mfg_reward_net_train_steps_pop_z; None: the unweighted symbol, as before."""
     for name, t in (('params', params), ('adam_m', m), ('adam_v', v)):
         _chk_f32(t, name)
         if tuple(t.shape) != (K, param_stride):
@@ -865,13 +868,18 @@ def reward_net_train_steps_pop(params, m, v, param_stride, K, dims, demo, gen, p
         raise ValueError('generated stores: expected [%d, cap, T, d] / [%d, cap, T, d, d]' % (K, K))
     if plan.size < n_updates * n_active:
         raise ValueError('plan: fewer than n_updates * n_active entries')
-    L.check(L.lib().mfg_reward_net_train_steps_pop(
-        params.data_ptr(), m.data_ptr(), v.data_ptr(), int(param_stride), int(K), *[int(x) for x in dims],
-        *_geom_ptrs(geom, K), ds.data_ptr(), da.data_ptr(), ds.shape[0], gs.data_ptr(), ga.data_ptr(), gs.shape[1],
-        plan.ctypes.data, plan_dev.data_ptr(), plan_dev.numel() * plan_dev.element_size(), int(n_updates), int(n_active),
-        int(n_demo), int(n_gen), int(steps), int(demo_divisor), float(keep_prob), int(bool(l1l2)), float(beta1), float(beta2),
-        float(eps), stats.data_ptr(), ws.data_ptr(), ws.numel() * ws.element_size(), _stream()),
-        'mfg_reward_net_train_steps_pop')
+    args = (params.data_ptr(), m.data_ptr(), v.data_ptr(), int(param_stride), int(K), *[int(x) for x in dims],
+            *_geom_ptrs(geom, K), ds.data_ptr(), da.data_ptr(), ds.shape[0], gs.data_ptr(), ga.data_ptr(), gs.shape[1],
+            plan.ctypes.data, plan_dev.data_ptr(), plan_dev.numel() * plan_dev.element_size(), int(n_updates), int(n_active),
+            int(n_demo), int(n_gen), int(steps), int(demo_divisor), float(keep_prob), int(bool(l1l2)), float(beta1), float(beta2),
+            float(eps), stats.data_ptr(), ws.data_ptr(), ws.numel() * ws.element_size())
+    if gen_log_z is None:
+        L.check(L.lib().mfg_reward_net_train_steps_pop(*args, _stream()), 'mfg_reward_net_train_steps_pop')
+        return
+    _chk_f64(gen_log_z, 'gen_log_z')
+    if tuple(gen_log_z.shape) != (K, gs.shape[1]):
+        raise ValueError('gen_log_z: expected [%d, %d]' % (K, gs.shape[1]))
+    L.check(L.lib().mfg_reward_net_train_steps_pop_z(*args, gen_log_z.data_ptr(), _stream()), 'mfg_reward_net_train_steps_pop_z')
 
 
 def episode_buffers(B, d, device):
@@ -938,6 +946,44 @@ def policy_logpdf(pi, P, thetas, shift, alpha_scale=1.0, alpha_floor=0.0, p_floo
     L.check(L.lib().mfg_policy_logpdf(pi.data_ptr(), P.data_ptr(), N, d, thetas.data_ptr(), K, float(shift),
                                       float(alpha_scale), float(alpha_floor), float(p_floor), out.data_ptr(), _stream()),
             'mfg_policy_logpdf')
+    return out
+
+
+def traj_log_z_pop(state, action, rows, thetas, shifts, log_start, alpha_scale=1.0, alpha_floor=1.0 + 1e-6, p_floor=0.0, out=None,
+                   scratch=None):
+    """mfg_traj_log_z_pop: ln z of the listed PHYSICAL rows of a trajectory store under K learners' policy lists, in one launch
+    (ac_irl.py:292-379 calc_z in log space; the defaults are calc_z's alpha_scale 1 and alpha floor 1 + 1e-6):
+        out[k, row] = ln n_pol - logsumexp_p( sum_t ln q_{thetas[k, p]}(a_t; s_t) - log_start ).
+    state [cap, T, d] / action [cap, T, d, d] (one store shared by the K learners) or [K, cap, T, d] / [K, cap, T, d, d] (one
+    store per learner); thetas [K, n_pol] and shifts [K] fp64 device tensors; rows: distinct ints in [0, cap).  Returns out
+    [K, cap] fp64 (given: rows not listed keep their values; created: they hold NaN).  A trajectory whose every density is 0 (an
+    exact zero in P with p_floor = 0) gets +inf."""
+    import ctypes as C
+    _chk_f32(state, 'state'); _chk_f32(action, 'action'); _chk_f64(thetas, 'thetas'); _chk_f64(shifts, 'shifts')
+    if thetas.dim() != 2 or thetas.shape[1] < 1:
+        raise ValueError('thetas: expected [K, n_pol]')
+    K, n_pol = thetas.shape
+    if tuple(shifts.shape) != (K,):
+        raise ValueError('shifts: expected [%d]' % K)
+    per_learner = state.dim() == 4
+    if state.dim() not in (3, 4) or (per_learner and state.shape[0] != K):
+        raise ValueError('state: expected [cap, T, d] or [%d, cap, T, d]' % K)
+    cap, T, d = state.shape[-3:]
+    if tuple(action.shape) != tuple(state.shape) + (d,):
+        raise ValueError('action: expected %s' % (tuple(state.shape) + (d,),))
+    if out is None:
+        out = torch.full((K, cap), float('nan'), dtype=torch.float64, device=state.device)
+    elif tuple(out.shape) != (K, cap):
+        raise ValueError('out: expected [%d, %d]' % (K, cap))
+    _chk_f64(out, 'out')
+    n = len(rows)
+    rw = (C.c_int32 * max(n, 1))(*[int(r) for r in rows])
+    if scratch is None:
+        scratch = torch.empty(max(n, 1), dtype=torch.int32, device=state.device)
+    L.check(L.lib().mfg_traj_log_z_pop(state.data_ptr(), action.data_ptr(), int(cap), rw, n, int(T), int(d), thetas.data_ptr(),
+                                       int(n_pol), shifts.data_ptr(), int(K), int(per_learner), float(alpha_scale),
+                                       float(alpha_floor), float(p_floor), float(log_start), out.data_ptr(), scratch.data_ptr(),
+                                       scratch.numel() * scratch.element_size(), _stream()), 'mfg_traj_log_z_pop')
     return out
 
 

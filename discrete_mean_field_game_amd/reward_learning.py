@@ -275,9 +275,11 @@ class RewardTrainer:
             self._ws = torch.empty((need + 3) // 4, dtype=torch.float32, device=self.device)
         return self._ws
 
-    def step(self, demo, demo_rows, gen, gen_rows, demo_divisor, seed, grad_only=False):
+    def step(self, demo, demo_rows, gen, gen_rows, demo_divisor, seed, grad_only=False, gen_log_z=None):
         """One update_reward on stores `demo` / `gen` (TrajectoryStore) with the PHYSICAL rows of the sampled trajectories.
-        grad_only: leave the gradient in self.grad (the caller all-reduces it and calls apply_grad)."""
+        grad_only: leave the gradient in self.grad (the caller all-reduces it and calls apply_grad).
+        gen_log_z: fp64 device tensor [gen capacity], ln z of the generated store's physical rows (ops.traj_log_z_pop): the
+        importance-weighted loss of ac_irl.py:404-406 through mfg_reward_net_train_step_z.  None: the unweighted call."""
         from .ops import _stream
         net = self.net
         nd, ng = len(demo_rows), len(gen_rows)
@@ -287,13 +289,18 @@ class RewardTrainer:
         gr = (C.c_int32 * max(ng, 1))(*gen_rows)
         if not grad_only:
             self.step_count += 1
-        L.check(L.lib().mfg_reward_net_train_step(
-            self.flat.data_ptr(), self.m.data_ptr(), self.v.data_ptr(), *self.dims,
-            demo.state.data_ptr(), demo.action.data_ptr(), dr, nd, gen.state.data_ptr(), gen.action.data_ptr(), gr, ng,
-            int(demo.steps), int(demo_divisor), keep, 1 if net.use_l1l2 else 0, int(seed) & 0xFFFFFFFFFFFFFFFF, self.lr,
-            self.BETA1, self.BETA2, self.EPS, max(self.step_count, 1), 1 if grad_only else 0,
-            self.grad.data_ptr() if grad_only else None, self.stats.data_ptr(), ws.data_ptr(), ws.numel() * 4, _stream()),
-            'mfg_reward_net_train_step')
+        args = (self.flat.data_ptr(), self.m.data_ptr(), self.v.data_ptr(), *self.dims,
+                demo.state.data_ptr(), demo.action.data_ptr(), dr, nd, gen.state.data_ptr(), gen.action.data_ptr(), gr, ng,
+                int(demo.steps), int(demo_divisor), keep, 1 if net.use_l1l2 else 0, int(seed) & 0xFFFFFFFFFFFFFFFF, self.lr,
+                self.BETA1, self.BETA2, self.EPS, max(self.step_count, 1), 1 if grad_only else 0,
+                self.grad.data_ptr() if grad_only else None, self.stats.data_ptr(), ws.data_ptr(), ws.numel() * 4)
+        if gen_log_z is None:
+            L.check(L.lib().mfg_reward_net_train_step(*args, _stream()), 'mfg_reward_net_train_step')
+            return
+        if not (gen_log_z.is_cuda and gen_log_z.dtype == torch.float64 and gen_log_z.is_contiguous()
+                and gen_log_z.numel() == gen.state.shape[0]):
+            raise ValueError('gen_log_z must be a contiguous float64 CUDA tensor with one entry per row of the generated store')
+        L.check(L.lib().mfg_reward_net_train_step_z(*args, gen_log_z.data_ptr(), _stream()), 'mfg_reward_net_train_step_z')
 
     def apply_grad(self):
         from .ops import _stream

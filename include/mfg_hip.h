@@ -390,6 +390,24 @@ int mfg_reward_net_train_step(float* params, float* adam_m, float* adam_v, int d
 int mfg_reward_net_adam(float* params, float* adam_m, float* adam_v, const float* grad, int64_t n, double lr, double beta1,
                         double beta2, double eps, int64_t adam_step, mfg_stream_t stream);
 
+/* mfg_reward_net_train_step with the importance weights of the max-ent IRL loss as the reference wrote it (ac_irl.py:292-321
+ * z_j, :404-406 the weighted second term  log( 1/M sum_j z_j exp(sum_t r_j,t) ), commented out there because its linear-space
+ * calc_z overflows).  gen_log_z: device fp64 [gen_capacity], ln z of the generated store's rows (mfg_traj_log_z_pop), indexed by
+ * the same physical gen_rows.  The soft-max phase of the combine kernel forms trajectory j's weight as
+ *   D_j = (double)S_j + gen_log_z[row_j];  mx = max_j D_j (fp64);  e_j = expf((float)(D_j - mx));  c_j = e_j / sum e;
+ *   stats[2] = (float)(mx + log(sum e / n_gen)), formed in fp64 and rounded once
+ * (fp64 until the maximum is gone: |ln z| ~ 1e4 with a spread of tens, so an fp32 ln z is off by 5e-4 before it reaches expf).
+ * Everything else -- arguments, checks, per-sample coefficients, the fp64 batch sum, regulariser, Adam, MFG_RN_TRAIN_GRAD_ONLY
+ * -- is mfg_reward_net_train_step's, which is this call with gen_log_z = NULL (then, or with n_gen = 0, the same launches
+ * and the same bits).  A +inf entry (a generated P with an exact zero under p_floor = 0) poisons the update with NaN as it would
+ * in the reference; nothing hides it. */
+int mfg_reward_net_train_step_z(float* params, float* adam_m, float* adam_v, int d, int k1, int f2, int k2, int n3, int n4,
+                                const float* demo_state, const float* demo_action, const int32_t* demo_rows_host, int n_demo,
+                                const float* gen_state, const float* gen_action, const int32_t* gen_rows_host, int n_gen, int steps,
+                                int demo_divisor, float keep_prob, int l1l2, uint64_t seed, double lr, double beta1, double beta2,
+                                double eps, int64_t adam_step, int flags, float* grad, float* stats, void* workspace,
+                                size_t workspace_bytes, const double* gen_log_z, mfg_stream_t stream);
+
 /* f3: backward value recursion of the mfg_synthetic variant: V^n = r^n + P^n V^{n+1}, r^n_i = -1/2 ||P^n_i||^2,
  * V^T = 0 (mfg_synthetic.py:768-774) for P[B,T,d,d] -> V[B,T+1,d] (fp64), plus per (b,n) the consistency
  * metrics of evaluate_synthetic (diff_l1 = sum_ij |P_ij - value_ij|, :776-790) and, if diff_jsd != NULL, of
@@ -675,6 +693,19 @@ int mfg_reward_net_train_steps_pop(float* params, float* adam_m, float* adam_v, 
                                    double beta1, double beta2, double eps, float* stats, void* workspace, size_t workspace_bytes,
                                    mfg_stream_t stream);
 
+/* mfg_reward_net_train_steps_pop with importance weights (ac_irl.py:404-406, see mfg_reward_net_train_step_z): gen_log_z is a
+ * device fp64 array [K, gen_capacity], learner k's ln z at gen_log_z + k gen_capacity, indexed by the plan entries' gen_rows
+ * (already checked against gen_capacity).  Update u, slot s is exactly mfg_reward_net_train_step_z for that learner -- the same
+ * bits, with or without a geometry table.  gen_log_z = NULL: mfg_reward_net_train_steps_pop. */
+int mfg_reward_net_train_steps_pop_z(float* params, float* adam_m, float* adam_v, int64_t param_stride, int K, int d, int k1, int f2,
+                                     int k2, int n3, int n4, const mfg_rn_geom_t* geom_host, const mfg_rn_geom_t* geom_dev,
+                                     const float* demo_state, const float* demo_action, int64_t demo_capacity,
+                                     const float* gen_state, const float* gen_action, int64_t gen_capacity,
+                                     mfg_rn_train_plan_t* plan_host, void* plan_dev, size_t plan_dev_bytes, int n_updates,
+                                     int n_active, int n_demo, int n_gen, int steps, int demo_divisor, float keep_prob, int l1l2,
+                                     double beta1, double beta2, double eps, float* stats, void* workspace, size_t workspace_bytes,
+                                     const double* gen_log_z, mfg_stream_t stream);
+
 /* f1 (optional importance weights, ac_irl.py:270-289 calc_pdf_action, :324-379 calc_z): log-density of the
  * product-Dirichlet policy for N (state, action) pairs under K policies theta_k (device array):
  *   out[n*K + k] = sum_i log Dirichlet(P_n[i,:] ; a_i),  a_ij = max(alpha_floor, alpha_scale * softplus(theta_k x_ij)).
@@ -684,6 +715,26 @@ int mfg_reward_net_train_steps_pop(float* params, float* adam_m, float* adam_v, 
  * (p_floor = 0: ln 0 = -inf, density 0, like tf.distributions.Dirichlet.prob).  fp64 out. */
 int mfg_policy_logpdf(const float* pi, const float* P, int64_t N, int d, const double* thetas, int K, double shift,
                       double alpha_scale, double alpha_floor, double p_floor, double* out, mfg_stream_t stream);
+
+/* f1, the importance log-weights of a trajectory store in ONE launch (ac_irl.py:292-321 calc_z's z_j = [1/k sum_k q_k(tau_j)]^-1
+ * over the last num_policies policies, :324-379 its graph, which multiplies 15 d densities in linear space over c = 2e11 and
+ * overflows): for learner k and every physical store row listed in rows_host,
+ *   log_z[k capacity + row] = ln n_pol - logsumexp_p( sum_t ln q_{thetas[k n_pol + p]}(a_t; s_t) - log_start ),
+ * ln q the formula of mfg_policy_logpdf (alpha_floor / p_floor clamps, shift[k], fp64 throughout), log_start = ln of the number
+ * of start states (Pr(s_1)).  Stores: state [capacity, steps, d], action [capacity, steps, d, d] fp32, shared by all learners
+ * (per_learner_store = 0), or [K, capacity, ...] with learner k's store at k capacity rows (per_learner_store = 1).  thetas
+ * [K, n_pol] and shift [K] are device fp64; K = 1 is the single-learner form; any n_pol >= 1.  Rows not listed are left
+ * alone.  Grid (n_rows, K), one wavefront per policy; the per-policy sums are folded into the logsumexp in policy order by
+ * one thread, so learner k's values are the same bits whatever K and the row list are.  A row whose every density is 0 (an
+ * exact zero in P with p_floor = 0) gets +inf, as tf.distributions.Dirichlet.prob would give.
+ * rows_host is uploaded into `scratch` (device, >= 4 n_rows bytes) and the stream is drained once before the launch; nothing
+ * is read back.  Checked before anything is launched: MFG_EINVAL for null pointers, bad counts (capacity, steps, d, n_pol < 1,
+ * K outside [1, MFG_POP_MAX_K], d > MFG_MAX_D), a row outside [0, capacity) or listed twice; MFG_EWORKSPACE for a scratch
+ * too small for the row list. */
+int mfg_traj_log_z_pop(const float* state, const float* action, int64_t capacity, const int32_t* rows_host, int n_rows,
+                       int steps, int d, const double* thetas, int n_pol, const double* shift, int K, int per_learner_store,
+                       double alpha_scale, double alpha_floor, double p_floor, double log_start, double* log_z, void* scratch,
+                       size_t scratch_bytes, mfg_stream_t stream);
 
 /* a11: out[b] = JSD(p_b, q_b), zeros -> 1e-100, inputs renormalised like scipy.stats.entropy
  * (mfg_ac2.py:546-563).  fp64 out. */
