@@ -18,6 +18,7 @@ REWARD_MFG_AC2, REWARD_SYNTHETIC, REWARD_EXTERNAL = 0, 1, 2
 ROLLOUT_WRITE_P, ROLLOUT_TD, ROLLOUT_DISCOUNT_POW, ROLLOUT_F64, TRAIN_APPLY = 1, 2, 4, 8, 16
 PRECISION_F64, PRECISION_MIXED = 0, 1
 POP_MAX_K = 65535                # MFG_POP_MAX_K: learners of one population call
+POP_RESIDENT_MAX_TILES = 64      # MFG_POP_RESIDENT_MAX_TILES: tiles of one learner the resident step-mode kernel walks
 STATUS_MIXED_RANGE = 1
 STATUS_POP_NONFINITE = 2        # MFG_STATUS_POP_NONFINITE: per-learner words of a population control block only
 ECOMM = -6                      # MFG_ECOMM: the call aborted its RCCL communicator, the handle is dead
@@ -115,6 +116,9 @@ SIGNATURES = {
     'mfg_traj_log_z_pop': (_i32, [_p, _p, _i64, C.POINTER(C.c_int32), _i32, _i32, _i32, _p, _i32, _p, _i32, _i32, _f64, _f64, _f64,
                                  _f64, _p, _p, _sz, _p]),
 }
+# the resident step-mode episodes of a small-batch population: the per-step call's arguments
+SIGNATURES['mfg_pop_resident_supported'] = (_i32, [_i32, _i64, _i32])
+SIGNATURES['mfg_train_episodes_pop_resident'] = (_i32, list(SIGNATURES['mfg_train_episodes_pop'][1]))
 # the importance-weighted training steps: the unweighted call's arguments with gen_log_z in front of the stream
 SIGNATURES['mfg_reward_net_train_step_z'] = (_i32, SIGNATURES['mfg_reward_net_train_step'][1][:-1] + [_p, _p])
 

@@ -3178,6 +3178,82 @@ int mfg_train_episodes_pop(const float* mat_pi0, int64_t num_start, float* pi_io
   return MFG_OK;
 }
 
+// ---- the resident form of the step-mode population episodes (mfg_pop_resident.hip): one workgroup per learner ----
+int mfg_pop_resident_supported(int d, int64_t B, int reward_kind) {
+  if (reward_kind != MFG_REWARD_MFG_AC2 && reward_kind != MFG_REWARD_SYNTHETIC) return 0;
+  if (B < 1) return 0;
+  const int64_t nt = core_sums_rows(d, B);  // (d = 21 / 15: the tiles of the SUMS step; 0 otherwise)
+  return nt >= 1 && nt <= MFG_POP_RESIDENT_MAX_TILES;
+}
+
+int mfg_train_episodes_pop_resident(const float* mat_pi0, int64_t num_start, float* pi_io, float* pi_scratch, int64_t B, int K,
+                                    int d, int T, int64_t episodes, int64_t first_episode, int constant, double* theta,
+                                    const double* shift, const double* alpha_scale, double* w, double gamma, int reward_kind,
+                                    const uint64_t* seed, uint32_t first_step, uint64_t traj_offset, int precision,
+                                    const double* lr_critic, const double* lr_actor, float* reward, double* delta, double* g,
+                                    double* G, double* reward_acc, void* workspace, size_t workspace_bytes, mfg_stream_t stream) {
+  CHECK_AC_POP();
+  CHECK_PRECISION();
+  REQUIRE(pi_io && pi_scratch, "null pointer");
+  if (!mfg_pop_resident_supported(d, B, reward_kind))
+    return fail(MFG_EUNSUPPORTED, "resident population: d=%d, B=%lld is not d = 21 / 15 with at most %d tiles per learner", d,
+                (long long)B, MFG_POP_RESIDENT_MAX_TILES);
+  if (const mfg_ctx* c = bound_ctx(); c && c->has_ctl)
+    return fail(MFG_EUNSUPPORTED, "%s", "resident population: the bound context carries a population control block "
+                                        "(mfg_train_episodes_pop retires learners)");
+  const size_t need = pop_workspace_need(d, B, true);
+  if (workspace_bytes < need)
+    return fail(MFG_EWORKSPACE, "population workspace: need %lld bytes per learner, have %lld", (long long)need,
+                (long long)workspace_bytes);
+  const bool mixed = precision == MFG_PRECISION_MIXED;
+  PopArgs p = pop_args(K, B, d, 1, episodes, seed, shift, alpha_scale, lr_critic, lr_actor, workspace_bytes);
+  p.s_pi0 = p.s_gpi = B * d;
+  p.s_n = B;
+  CoreArgs a{};
+  a.gamma = gamma;
+  a.B = B;
+  a.d = d;
+  a.T = 1;  // (one env step per call of the step body)
+  a.reward_kind = reward_kind;
+  a.traj_offset = traj_offset;
+  a.reward_out = reward;
+  a.delta = delta;
+  a.g = g;
+  a.part_rows = reinterpret_cast<double*>((char*)workspace + MFG_WS_CONTROL_BYTES);
+  if (mixed) {
+    a.htab = htab_ptr();
+    if (!a.htab) return fail(MFG_ELAUNCH, "%s", "h(z) table initialisation failed");
+  }
+  PopResidentArgs r{};
+  r.mat_pi0 = mat_pi0;
+  r.num_start = num_start;
+  r.pi_io = pi_io;
+  r.pi_scratch = pi_scratch;
+  r.theta = theta;
+  r.w = w;
+  r.G = G;
+  r.T = T;
+  for (int64_t k0 = 0; k0 < episodes; k0 += MFG_POP_RESIDENT_EPISODES) {
+    {  // (as launch_core: the sticky range report of an earlier mixed-precision launch refuses this one)
+      const StatusWord sw = status_word();
+      if (!sw.host) return fail(MFG_ELAUNCH, "%s", "status word allocation failed");
+      const unsigned bits = g_status_check_deferred ? 0u : *(volatile unsigned*)sw.host;
+      const unsigned blocking = mixed ? bits : (bits & ~(unsigned)MFG_STATUS_MIXED_RANGE);
+      if (blocking) return status_error(blocking);
+      a.status = sw.dev;
+    }
+    const int64_t n = episodes - k0 < MFG_POP_RESIDENT_EPISODES ? episodes - k0 : MFG_POP_RESIDENT_EPISODES;
+    r.episodes = (int)n;
+    r.first_step = first_step + (uint32_t)(k0 * T);
+    r.reward_acc = reward_acc ? reward_acc + k0 : nullptr;
+    for (int64_t e = 0; e < n; ++e) lr_schedule(first_episode + k0 + e, constant, &r.sc[e], &r.sa[e]);
+    if (const int rc = launch_pop_resident(a, p, r, mixed, S(stream)); rc != MFG_OK)
+      return fail(rc, "%s", "resident population: no kernel for this d");
+    if (const int rc = check_launch("pop_resident"); rc != MFG_OK) return rc;
+  }
+  return MFG_OK;
+}
+
 int mfg_train_rollouts_pop(const float* mat_pi0, int64_t num_start, int64_t B, int K, int d, int T, int64_t episodes,
                            int64_t first_episode, int constant, double* theta, const double* shift, const double* alpha_scale,
                            double* w, double gamma, int reward_kind, const uint64_t* seed, uint32_t first_step,

@@ -117,6 +117,24 @@ void launch_reduce_partials_pop(unsigned nob, const double* partial, int64_t nsb
 void launch_reduce_rows_apply_pop(const double* rows, int nrows, int64_t FO, double* G, double count, double* w,
                                   const double* theta_in, double* theta_out, double* reward_acc, const PopArgs& p, hipStream_t st);
 
+// The resident form of the step-mode episodes (mfg_pop_resident.hip, mfg_train_episodes_pop_resident): what one launch of
+// k_pop_resident needs beyond CoreArgs (shape, gamma, reward_kind, traj_offset, htab, status, reward / delta / g and the rows
+// in part_rows; pi0, theta, w, first_step and pi_next_out are set by the kernel) and PopArgs (strides and per-learner arrays;
+// sc / sa unused).  The learning-rate multipliers of the launch's episodes come from the host (lr_schedule: libm's log), by
+// value: hence at most MFG_POP_RESIDENT_EPISODES episodes per launch.
+struct PopResidentArgs {
+  const float* mat_pi0;  // [num_start, d] start-state table
+  int64_t num_start;
+  float *pi_io, *pi_scratch;  // [K, Bk, d]
+  double *theta, *w, *G;      // [K], [K, F], [K, F + 3]
+  double* reward_acc;         // [K, s_acc] moved to the launch's first episode, or NULL
+  int T, episodes;            // env steps per episode; episodes of this launch
+  uint32_t first_step;        // Philox step of the launch's first episode
+  double sc[MFG_POP_RESIDENT_EPISODES], sa[MFG_POP_RESIDENT_EPISODES];
+};
+// d = 21 / 15 only (MFG_EUNSUPPORTED otherwise); grid (1, K)
+int launch_pop_resident(const CoreArgs& a, const PopArgs& p, const PopResidentArgs& r, bool fast, hipStream_t st);
+
 // the step between two episodes of a call with a control block (k_pop_retire): the non-finite scan of theta and w, in mixed
 // precision the range predicate of report_sep_range and the learner's status word -> state 2; after_episode: episodes_run += 1,
 // |theta - theta_prev| < stop_criteria -> state 1, theta_prev = theta (0, before the first episode: the checks and theta_prev)

@@ -522,6 +522,24 @@ def _chk_pop_args(K, B, d, T, episodes, theta, w, G, ws, bufs, reward_acc, mat_p
         raise ValueError('ws: expected a contiguous fp64 [K, slice] workspace')
 
 
+def _train_episodes_pop(entry, mat_pi0, pi, T, episodes, first_episode, constant, theta, shifts, alpha_scales, w, gamma,
+                        lr_critic, lr_actor, seeds, G, ws, bufs, reward_kind, first_step, traj_offset, reward_acc, precision):
+    """The step-mode population call `entry` (mfg_train_episodes_pop or its resident form: one parameter list)."""
+    _chk_f32(mat_pi0, 'mat_pi0'); _chk_f32(pi, 'pi'); _chk_f64(theta, 'theta'); _chk_f64(w, 'w'); _chk_f64(G, 'G')
+    K, B, d = pi.shape
+    bufs = dict(bufs, pi=pi)
+    _chk_pop_args(K, B, d, T, episodes, theta, w, G, ws, bufs, reward_acc, mat_pi0, shifts, alpha_scales, lr_critic, lr_actor,
+                  seeds)
+    fn = getattr(L.lib(), entry)
+    L.check(fn(mat_pi0.data_ptr(), mat_pi0.shape[0], pi.data_ptr(), bufs['scratch'].data_ptr(), B, K, d, int(T), int(episodes),
+               int(first_episode), int(bool(constant)), theta.data_ptr(), shifts.data_ptr(), alpha_scales.data_ptr(),
+               w.data_ptr(), float(gamma), int(reward_kind), seeds.data_ptr(), int(first_step), int(traj_offset),
+               L.PRECISIONS[precision], lr_critic.data_ptr(), lr_actor.data_ptr(), bufs['reward'].data_ptr(),
+               bufs['delta'].data_ptr(), bufs['g'].data_ptr(), G.data_ptr(), _ptr(reward_acc), ws.data_ptr(),
+               ws.shape[1] * ws.element_size(), _stream()), entry)
+    return pi
+
+
 def train_episodes_pop(mat_pi0, pi, T, episodes, first_episode, constant, theta, shifts, alpha_scales, w, gamma, lr_critic,
                        lr_actor, seeds, G, ws, bufs, reward_kind=L.REWARD_MFG_AC2, first_step=0, traj_offset=0, reward_acc=None,
                        precision='mixed'):
@@ -529,20 +547,21 @@ def train_episodes_pop(mat_pi0, pi, T, episodes, first_episode, constant, theta,
     [K,Bk,d], theta [K], w [K,F], G [K,F+3], ws [K, slice] fp64 (one learner's slice per row); shifts, alpha_scales,
     lr_critic, lr_actor fp64 and seeds int64 (read as uint64) device arrays [K]; bufs = dict(scratch [K,Bk,d] f32,
     reward [K,Bk] f32, delta / g [K,Bk] f64); reward_acc [K,episodes] fp64 or None."""
-    _chk_f32(mat_pi0, 'mat_pi0'); _chk_f32(pi, 'pi'); _chk_f64(theta, 'theta'); _chk_f64(w, 'w'); _chk_f64(G, 'G')
-    K, B, d = pi.shape
-    bufs = dict(bufs, pi=pi)
-    _chk_pop_args(K, B, d, T, episodes, theta, w, G, ws, bufs, reward_acc, mat_pi0, shifts, alpha_scales, lr_critic, lr_actor,
-                  seeds)
-    L.check(L.lib().mfg_train_episodes_pop(mat_pi0.data_ptr(), mat_pi0.shape[0], pi.data_ptr(), bufs['scratch'].data_ptr(), B, K,
-                                           d, int(T), int(episodes), int(first_episode), int(bool(constant)), theta.data_ptr(),
-                                           shifts.data_ptr(), alpha_scales.data_ptr(), w.data_ptr(), float(gamma),
-                                           int(reward_kind), seeds.data_ptr(), int(first_step), int(traj_offset),
-                                           L.PRECISIONS[precision], lr_critic.data_ptr(), lr_actor.data_ptr(),
-                                           bufs['reward'].data_ptr(), bufs['delta'].data_ptr(), bufs['g'].data_ptr(),
-                                           G.data_ptr(), _ptr(reward_acc), ws.data_ptr(), ws.shape[1] * ws.element_size(),
-                                           _stream()), 'mfg_train_episodes_pop')
-    return pi
+    return _train_episodes_pop('mfg_train_episodes_pop', mat_pi0, pi, T, episodes, first_episode, constant, theta, shifts,
+                               alpha_scales, w, gamma, lr_critic, lr_actor, seeds, G, ws, bufs, reward_kind, first_step,
+                               traj_offset, reward_acc, precision)
+
+
+def train_episodes_pop_resident(mat_pi0, pi, T, episodes, first_episode, constant, theta, shifts, alpha_scales, w, gamma,
+                                lr_critic, lr_actor, seeds, G, ws, bufs, reward_kind=L.REWARD_MFG_AC2, first_step=0, traj_offset=0,
+                                reward_acc=None, precision='mixed'):
+    """train_episodes_pop with every learner resident in one workgroup (mfg_train_episodes_pop_resident): the same arguments
+    and, bit for bit, the same outputs, in ceil(episodes / 64) launches instead of episodes x (1 + 2 T).  For learners of few
+    trajectories (mfg_pop_resident_supported, include/mfg_hip.h); MfgError (MFG_EUNSUPPORTED) for another shape or under a
+    population control block."""
+    return _train_episodes_pop('mfg_train_episodes_pop_resident', mat_pi0, pi, T, episodes, first_episode, constant, theta,
+                               shifts, alpha_scales, w, gamma, lr_critic, lr_actor, seeds, G, ws, bufs, reward_kind, first_step,
+                               traj_offset, reward_acc, precision)
 
 
 def train_rollouts_pop(mat_pi0, T, episodes, first_episode, constant, theta, shifts, alpha_scales, w, gamma, G, ws, bufs,

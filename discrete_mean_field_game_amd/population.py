@@ -14,6 +14,10 @@ The instance owns one ops.Context: its sticky mixed-range status word (include/m
 learners, so by default ONE learner whose policy leaves the fp32 range of mixed-precision sampling stops the population's next
 launch (train() raises MfgError; clear_status() resets it; precision='f64' has no such range).
 
+Small learners in step mode: ActorCriticPopulation(..., resident=None) runs the episodes of learners of a few tiles through
+mfg_train_episodes_pop_resident -- one workgroup per learner for the whole call instead of 1 + 2 T launches per episode,
+the same bits -- where resident_rule(K, d, batch) measured it faster; resident=True / False force / forbid it.
+
 Retiring learners on the device: train(..., stop_criteria=c, isolate=True) runs under a population control block
 (mfg_ctx_set_pop_control, include/mfg_hip.h) -- an activity state per learner in device memory that every launch of the call
 carries.  A learner whose |theta_e - theta_{e-1}| falls below its criterion stops after that episode (AC_IRL.train's early
@@ -88,7 +92,82 @@ class LearnerActivity:
         self.status[sel] = 0
 
 
-def check_args(K, d, batch, update_every, reward, precision, episode_steps):
+def needs_control(stop, isolate, state):
+    """True when a train() call runs under the population control block: a stop criterion >= 0 (`stop`: the array of
+    stop_criteria_array), isolate=True, or a learner that failed earlier (`state`: LearnerActivity.state)."""
+    return bool(isolate) or bool(np.any(stop >= 0)) or bool(np.any(state == FAILED))
+
+
+# ------------------------------------------------------------------------------- the resident step-mode path
+# mfg_train_episodes_pop_resident (include/mfg_hip.h): one workgroup holds a learner for a whole launch -- no launch per env
+# step -- and gives the bits of the per-step launches.  It serves d = 21 / 15 up to RESIDENT_MAX_TILES tiles per learner.
+RESIDENT_TILE = {21: 12, 15: 16}      # trajectories per tile of the packed step kernel (4 waves x floor(64 / d))
+RESIDENT_MAX_TILES = L.POP_RESIDENT_MAX_TILES
+
+
+def resident_supported(d, batch):
+    """mfg_pop_resident_supported for the in-kernel rewards of a population, restated on the host (no library call)."""
+    tb = RESIDENT_TILE.get(int(d))
+    return tb is not None and 1 <= -(-int(batch) // tb) <= RESIDENT_MAX_TILES
+
+
+# Measured on one MI355X (tools/pop_resident_probe.py -> profiles/pop_resident_ab.txt; mixed precision, T = 15, five alternating
+# repetitions per side, every difference far outside the sides' spreads): per d and measured tiles per learner, the ratio
+# per-step / resident of the medians at K = 16, at K = 256, and the smaller of those at K = 512 and K = 4 096.
+RESIDENT_AB = {21: {1: (1.89, 3.95, 5.05), 4: (0.53, 1.59, 2.25), 8: (0.27, 1.19, 1.72), 16: (0.14, 0.97, 1.41), 64: (0.07, 0.78, 1.17)},
+               15: {1: (1.94, 2.89, 3.12), 4: (0.54, 1.32, 1.75), 16: (0.14, 0.89, 1.31), 64: (0.07, 0.76, 1.16)}}
+RESIDENT_BLOCKS = 512     # workgroups of the resident kernel the card holds at once: 256 CUs x 2
+
+
+def resident_rule(K, d, batch):
+    """Whether ActorCriticPopulation(resident=None) trains K learners of `batch` trajectories through the resident kernel:
+    where it beat the per-step launches in RESIDENT_AB (DESIGN.md "Populations" has the table), never for a shape the library
+    does not serve.  Off the measured grid the rule only moves to the less favourable measured neighbour: the next measured
+    tile count up (the gain falls with the tiles a workgroup serialises) and the next measured K down (below 512 learners
+    the gain rises with K in every row); K < 16 was not measured: per-step.  From 512 learners on the workgroups run in rounds
+    of RESIDENT_BLOCKS, and the gain measured at full rounds (K = 512, 4 096) is discounted by the fill of the last round --
+    arithmetic, not a measurement, so it has to clear 1.1."""
+    K, d, batch = int(K), int(d), int(batch)
+    if not resident_supported(d, batch) or K < 16:
+        return False
+    tiles = -(-batch // RESIDENT_TILE[d])
+    at16, at256, full = RESIDENT_AB[d][min(t for t in RESIDENT_AB[d] if t >= tiles)]
+    if K < 256:
+        return at16 > 1.0
+    if K < RESIDENT_BLOCKS:
+        return at256 > 1.0
+    rounds = -(-K // RESIDENT_BLOCKS)
+    return full * K / (RESIDENT_BLOCKS * rounds) > 1.1
+
+
+def check_resident(resident, d, batch, update_every):
+    """Validation of the constructor's `resident` (no GPU needed): None, True or False; True needs update_every='step' and a
+    shape the resident kernel serves."""
+    if resident not in (None, True, False):
+        raise ValueError('resident must be None (the measured rule), True or False')
+    if resident is True:
+        if update_every != 'step':
+            raise ValueError("resident=True: the resident kernel runs update_every='step' only")
+        if not resident_supported(d, batch):
+            raise ValueError('resident=True: d=%d, batch=%d is outside the resident kernel\'s shapes (d = 21 / 15, at most %d '
+                             'tiles of %s trajectories per learner)' % (d, batch, RESIDENT_MAX_TILES, RESIDENT_TILE.get(int(d), '-')))
+
+
+def use_resident(resident, rule, control):
+    """Whether a step-mode train() call takes the resident path.  resident: the constructor's argument; rule:
+    resident_rule(K, d, batch); control: needs_control(...) of the call.  A forced resident=True refuses a controlled call
+    (ValueError: retiring learners inside the resident kernel is not supported); under None such a call takes the per-step
+    launches."""
+    if resident is True:
+        if control:
+            raise ValueError('resident=True: this call runs under the population control block (a stop criterion, isolate=True '
+                             'or a learner that failed earlier), which the resident kernel does not serve; use resident=None '
+                             'or False')
+        return True
+    return resident is None and bool(rule) and not control
+
+
+def check_args(K, d, batch, update_every, reward, precision, episode_steps, resident=None):
     """Validation of the constructor's arguments (no GPU needed)."""
     if K < 1 or K > L.POP_MAX_K:
         raise ValueError('population size %d outside [1, %d]' % (K, L.POP_MAX_K))
@@ -105,6 +184,7 @@ def check_args(K, d, batch, update_every, reward, precision, episode_steps):
         raise ValueError("precision must be 'mixed' or 'f64'")
     if episode_steps < 1:
         raise ValueError('episode_steps must be >= 1')
+    check_resident(resident, d, batch, update_every)
 
 
 def resolve_start_table(d, pi0=None, path_to_dir=None):
@@ -351,7 +431,7 @@ class _Population:
         lrc = torch.as_tensor(broadcast('lr_critic', lr_critic, K), device=self.device)
         lra = torch.as_tensor(broadcast('lr_actor', lr_actor, K), device=self.device)
         stop = stop_criteria_array(stop_criteria, K)
-        control = bool(isolate) or bool(np.any(stop >= 0)) or bool(np.any(self._act.state == 2))
+        control = needs_control(stop, isolate, self._act.state)
         if not control:
             # (no learner has failed here, or the call would be a controlled one: everybody is active for the whole call)
             self._act.state[:] = ACTIVE
@@ -455,13 +535,20 @@ class ActorCriticPopulation(_Population):
 
     def __init__(self, thetas, shifts=0.16, alpha_scales=12000, d=21, *, batch, seeds=None, w0=None, pi0=None,
                  path_to_dir=None, update_every='step', reward='mfg_ac2', precision='mixed', episode_steps=EPISODE_STEPS,
-                 device=None, verbose=0):
+                 device=None, verbose=0, resident=None):
+        """resident (update_every='step' only): None -- the step-mode episodes take the resident kernel
+        (mfg_train_episodes_pop_resident: one workgroup per learner, no launch per env step, the same bits) where
+        resident_rule(K, d, batch) says it measured faster (mixed precision only: the rule was not measured in 'f64'), and
+        the per-step launches otherwise and for every call under a control block; True -- always (ValueError here for a
+        shape it does not serve or update_every='rollout', and from train() for a call under a control block); False --
+        never."""
         th = np.asarray(thetas, dtype=np.float64).reshape(-1)
-        check_args(th.shape[0], int(d), int(batch), update_every, reward, precision, int(episode_steps))
+        check_args(th.shape[0], int(d), int(batch), update_every, reward, precision, int(episode_steps), resident)
         super().__init__(th, d, batch, episode_steps, shifts, alpha_scales, seeds, w0, pi0, path_to_dir, update_every,
                          precision, device, verbose)
         self.reward = reward
         self.reward_kind = REWARDS[reward]
+        self.resident = resident
 
     @_with_ctx
     def train(self, num_episodes, gamma=1, constant=0, lr_critic=0.1, lr_actor=0.001, *, first_episode=0, stop_criteria=-1,
@@ -482,13 +569,20 @@ class ActorCriticPopulation(_Population):
         naming the failed learners.  Later calls are not refused; they skip those learners (and raise again when
         isolate=False) until clear_status()."""
         T = self.episode_steps
+        resident = False
+        if self.update_every == 'step':
+            control = needs_control(stop_criteria_array(stop_criteria, self.K), isolate, self._act.state)
+            # (the rule was measured in mixed precision; strict precision keeps the per-step launches unless forced)
+            rule = self.precision == 'mixed' and resident_rule(self.K, self.d, self.batch)
+            resident = use_resident(self.resident, rule, control)
+        step_call = ops.train_episodes_pop_resident if resident else ops.train_episodes_pop
 
         def run(b, lrc, lra, acc):
             if self.update_every == 'step':
-                ops.train_episodes_pop(self._mat_pi0_dev, b['pi'], T, int(num_episodes), first_episode, constant == 1,
-                                       self._theta, self._shifts_dev, self._alphas_dev, self._w, gamma, lrc, lra,
-                                       self._seeds_dev, b['G'], b['ws'], b['run'], reward_kind=self.reward_kind,
-                                       first_step=self._rng_step, reward_acc=acc, precision=self.precision)
+                step_call(self._mat_pi0_dev, b['pi'], T, int(num_episodes), first_episode, constant == 1, self._theta,
+                          self._shifts_dev, self._alphas_dev, self._w, gamma, lrc, lra, self._seeds_dev, b['G'], b['ws'],
+                          b['run'], reward_kind=self.reward_kind, first_step=self._rng_step, reward_acc=acc,
+                          precision=self.precision)
             else:
                 ops.train_rollouts_pop(self._mat_pi0_dev, T, int(num_episodes), first_episode, constant == 1, self._theta,
                                        self._shifts_dev, self._alphas_dev, self._w, gamma, b['G'], b['ws'], b['run'], lrc, lra,

@@ -479,6 +479,30 @@ int mfg_train_episodes_pop(const float* mat_pi0, int64_t num_start, float* pi_io
                            uint32_t first_step, uint64_t traj_offset, int precision, const double* lr_critic,
                            const double* lr_actor, float* reward, double* delta, double* g, double* G, double* reward_acc,
                            void* workspace, size_t workspace_bytes, mfg_stream_t stream);
+/* Step mode for small learners, resident (the reference's per-step updates, mfg_ac2.py:478-526): the parameter list and the
+ * outputs of mfg_train_episodes_pop, with learner k held by ONE workgroup for the whole launch -- start draw, T x [env step |
+ * row reduction + update], episode after episode, a block barrier between the phases; learners never communicate, so the
+ * kernel has no fence wider than the workgroup and no spin, and is correct for any K.
+ *   Bit identity: theta, w, G, pi_io, reward, delta, g and reward_acc of every learner equal, bit for bit, what
+ *   mfg_train_episodes_pop leaves for the same arguments (given a workspace slice from mfg_workspace_bytes, with which that
+ *   call forms its batch sums inside the step kernel); pi_scratch and the workspace are scratch.
+ *   Launches: ceil(episodes / MFG_POP_RESIDENT_EPISODES) -- the learning-rate schedule of a launch's episodes is computed on
+ *   the host and passed by value -- against episodes x (1 + 2 T) launches (+ a copy when T is odd) of mfg_train_episodes_pop.
+ *   Shapes (mfg_pop_resident_supported, host only, no GPU: 1 / 0): d = 21 or 15, an in-kernel reward_kind and
+ *   1 <= ceil(B / TB) <= MFG_POP_RESIDENT_MAX_TILES tiles of TB = 12 (d = 21) / 16 (d = 15) trajectories, i.e. B <= 768 /
+ *   1 024: a functional cap (one row per slice of the row reduction, a bounded launch), not a performance claim.
+ * Checked before anything is launched: everything mfg_train_episodes_pop checks; MFG_EUNSUPPORTED for another shape, and
+ * when the bound context carries a population control block (retiring learners stays with the per-step launches);
+ * MFG_EWORKSPACE when the slice does not hold the tiles' partial rows. */
+#define MFG_POP_RESIDENT_EPISODES 64
+#define MFG_POP_RESIDENT_MAX_TILES 64
+int mfg_pop_resident_supported(int d, int64_t B, int reward_kind);
+int mfg_train_episodes_pop_resident(const float* mat_pi0, int64_t num_start, float* pi_io, float* pi_scratch, int64_t B, int K,
+                                    int d, int T, int64_t episodes, int64_t first_episode, int constant, double* theta,
+                                    const double* shift, const double* alpha_scale, double* w, double gamma, int reward_kind,
+                                    const uint64_t* seed, uint32_t first_step, uint64_t traj_offset, int precision,
+                                    const double* lr_critic, const double* lr_actor, float* reward, double* delta, double* g,
+                                    double* G, double* reward_acc, void* workspace, size_t workspace_bytes, mfg_stream_t stream);
 /* rollout mode (one update per episode, mfg_ac2.py:460-526): mfg_train_rollouts for K learners (flags: MFG_ROLLOUT_F64 /
  * MFG_ROLLOUT_DISCOUNT_POW) */
 int mfg_train_rollouts_pop(const float* mat_pi0, int64_t num_start, int64_t B, int K, int d, int T, int64_t episodes,
