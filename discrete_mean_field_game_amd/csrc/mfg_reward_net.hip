@@ -76,6 +76,7 @@ __device__ __forceinline__ int64_t rn_state_row(const RewardNetArgs& a, int64_t 
 #endif
 // 8 waves share one LDS copy of the FC3 weights (28 KB at d = 21, n3 = 8): 76 KB per block, 2 blocks per CU.
 constexpr int RN_WAVES = MFG_RN_WAVES, RN_BLOCK = RN_WAVES * WAVE, RN_MAXF2 = 2, RN_MAXN = 32;
+constexpr size_t RN_LDS_CU = 160 * 1024;  // LDS of one CU of gfx950: the most one block's launch may ask for
 
 // PPMAX = max pixels per lane (ceil(d*d/64)).  K1 / K2 / F2 > 0: compile-time conv geometry (the reference always
 // uses k1 = 5, k2 = 3, f2 = 2, ac_irl.py:251-267): taps unroll, LDS reads get immediate offsets and can be issued
@@ -1324,6 +1325,10 @@ int reward_net_forward_sums(const float* state, const float* action, int64_t B, 
   //  convolution, which costs more than the L2 round trips it removes.  Not kept.)
   const int64_t samples_per_block = (B + grid - 1) / grid;
   a.w3_in_lds = (w3fl * 4 <= 64 * 1024 && samples_per_block >= MFG_RN_LDS_MIN && (((uintptr_t)n.fc3_w & 15) == 0)) ? 1 : 0;
+  // ... and only when the staged launch's WHOLE request fits the LDS of a CU: the tiles of eight waves at d = 32 with 7 x 7
+  // kernels take 90 KB, the small weights of n4 = 32 another 6 KB -- with 64 KB of FC3 weights on top that is 163 968 B, a
+  // launch the runtime refuses.  (k_reward_net's carve; the run-mapped kernels never come near: 107 232 B + 1 KB for the sums)
+  if ((((fl + w3fl + 3) & ~(size_t)3) + (size_t)RN_WAVES * (W1 * W1 + W2 * W2)) * 4 > RN_LDS_CU) a.w3_in_lds = 0;
   if (a.w3_in_lds) fl += w3fl;
   fl = (fl + 3) & ~(size_t)3;
   fl += (size_t)RN_WAVES * (W1 * W1 + W2 * W2);

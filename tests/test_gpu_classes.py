@@ -515,15 +515,21 @@ def test_native_episode_loop_equals_python_step_loop(dev, d, B, precision):
     assert np.array_equal(runs[0][2], runs[1][2])
 
 
-@pytest.mark.parametrize('d,B,precision,reg', [(21, 300, 'mixed', 'dropout_l1l2'), (21, 4096, 'mixed', 'dropout_l1l2'),
-                                               (15, 64, 'f64', 'l1l2'), (21, 7, 'f64', 'dropout')])
-def test_native_irl_episode_equals_python_step_loop(dev, d, B, precision, reg):
+_IRL_STEP_LOOP = [(21, 300, 'mixed', 'dropout_l1l2', 8), (21, 4096, 'mixed', 'dropout_l1l2', 8), (15, 64, 'f64', 'l1l2', 8),
+                  (21, 7, 'f64', 'dropout', 8), (21, 300, 'mixed', 'dropout_l1l2', 24), (12, 40, 'mixed', 'l1l2', 8)]
+
+
+@pytest.mark.parametrize('d,B,precision,reg,n_fc3', _IRL_STEP_LOOP,
+                         ids=['%d-%d-%s-%s' % c[:4] + ('' if c[4] == 8 else '-n%d' % c[4]) for c in _IRL_STEP_LOOP])
+def test_native_irl_episode_equals_python_step_loop(dev, d, B, precision, reg, n_fc3):
     """mfg_train_episode_irl (ac_irl.py:664-712: per env step sample + transition + score | reward network | batch sums +
     update, the whole 15-step episode issued natively) gives what the per-step Python sequence rollout(T=1, EXTERNAL)
     -> reward() -> grad_apply gives: same sampling / reward kernels, same order, same Philox steps and the same
     dropout-mask keys (dropout stays ON in the reference when the net serves as the RL reward).  The one difference is
     the association of the fp64 batch sums: the native loop forms them inside the reward-network launch (a row per block
-    of eight samples), the Python sequence in the gradient kernel -- so the parameters agree to ~1e-13, not bit for bit."""
+    of eight samples), the Python sequence in the gradient kernel -- so the parameters agree to ~1e-13, not bit for bit.
+    n_fc3 = 24 takes the run-mapped kernel, which forms the sums over a given delta0; d = 12 the pixel-per-lane kernel, a
+    plain forward followed by the gradient kernel."""
     import random
     rs = np.random.RandomState(d + B)
     mat = rs.dirichlet(np.ones(d), size=9)
@@ -531,7 +537,7 @@ def test_native_irl_episode_equals_python_step_loop(dev, d, B, precision, reg):
     for use_native in (True, False):
         np.random.seed(21); torch.manual_seed(21); random.seed(21)
         ac = IRL(d=d, pi0=mat, demonstrations=[], batch=B, rng='philox', seed=5, update_every='step', precision=precision,
-                 reg=reg, verbose=0)
+                 reg=reg, n_fc3=n_fc3, verbose=0)
         with torch.no_grad():
             for p in ac.reward_net.parameters():
                 if p.dim() == 1:
