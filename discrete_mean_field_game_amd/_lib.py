@@ -23,6 +23,8 @@ STATUS_MIXED_RANGE = 1
 STATUS_POP_NONFINITE = 2        # MFG_STATUS_POP_NONFINITE: per-learner words of a population control block only
 ECOMM = -6                      # MFG_ECOMM: the call aborted its RCCL communicator, the handle is dead
 RN_TRAIN_MAX_TRAJ = 64          # MFG_RN_TRAIN_MAX_TRAJ
+FORECAST_MAX_RANKS = 8          # MFG_FORECAST_MAX_RANKS: order statistics of one mfg_forecast_pop call
+FORECAST_MAX_REPEATS = 1024     # MFG_FORECAST_MAX_REPEATS: members per start state of one mfg_forecast_pop call
 PRECISIONS = {'f64': PRECISION_F64, 'mixed': PRECISION_MIXED, 0: 0, 1: 1}
 
 
@@ -182,6 +184,12 @@ SIGNATURES['mfg_ctx_set_pop_control'] = (_i32, [_p, C.POINTER(PopControlStruct)]
 
 SIGNATURES['mfg_evaluate_pop_workspace_bytes'] = (_sz, [_i64, _i32, _i32, _i32, _i32, _i32])
 SIGNATURES['mfg_evaluate_pop'] = (_i32, [_p, _p, _i64, _i32, _i32, _i32, _p, _p, _p, _p, _u32, _i32, _i32, _p, _p, _p, _sz, _p])
+
+# the ensemble forecast: start32, N, H, d, K, theta, shift, alpha_scale, seed, first_step, repeats, precision, ranks (host), Q,
+# emp32, emp64, mean, std, quant, curves, pi_traj, workspace, workspace_bytes, stream
+SIGNATURES['mfg_forecast_pop_workspace_bytes'] = (_sz, [_i64, _i32, _i32, _i32, _i32, _i32])
+SIGNATURES['mfg_forecast_pop'] = (_i32, [_p, _i64, _i32, _i32, _i32, _p, _p, _p, _p, _u32, _i32, _i32, C.POINTER(C.c_int32), _i32,
+                                         _p, _p, _p, _p, _p, _p, _p, _p, _sz, _p])
 
 _lib = None
 

@@ -27,6 +27,33 @@ inline size_t eval_pop_workspace_bytes(int64_t N, int L, int d, int K, int repea
   return b;
 }
 
+// One step's L1 and JSD of a generated row against the test row, by one wave (lane = state entry, `on` = lane < d; every lane
+// of the wave calls): L1 = sum_i |emp64 - gen| in fp64, JSD with k_jsd's formula against emp32 (zeros -> 1e-100, M from the
+// un-normalised vectors, P, Q, M renormalised; mfg_ac2.py:546-563, :631-666).  gp: this lane's entry of the generated row (read when `on`), eo:
+// its offset in emp32 / emp64.  ONE definition for k_eval_metrics_pop (per trajectory) and k_forecast_curves (per step).
+__device__ __forceinline__ void eval_step_l1_jsd(const float* __restrict__ gp, const float* __restrict__ emp32, const double* __restrict__ emp64,
+                                                 int64_t eo, bool on, double& l1, double& jsd) {
+  double a = 1.0, c = 1.0, e1 = 0.0;
+  if (on) {
+    const float g = *gp;
+    e1 = fabs(emp64[eo] - (double)g);
+    a = emp32[eo];
+    c = g;
+    if (a == 0.0) a = 1e-100;
+    if (c == 0.0) c = 1e-100;
+  }
+  l1 = wave_sum(e1);
+  const double sp = wave_sum(on ? a : 0.0), sq = wave_sum(on ? c : 0.0);
+  const double sm = 0.5 * (sp + sq);
+  double acc = 0.0;
+  if (on) {
+    const double m = 0.5 * (a + c) / sm;
+    const double pn = a / sp, qn = c / sq;
+    acc = pn * log(pn / m) + qn * log(qn / m);
+  }
+  jsd = 0.5 * wave_sum(acc);
+}
+
 void launch_eval_metrics_pop(const float* pi_traj, const float* emp32, const double* emp64, int64_t N, int L, int d, int64_t NR,
                              int K, double* per_traj, double* metrics, hipStream_t st);
 

@@ -15,7 +15,8 @@ __global__ __launch_bounds__(BLOCK, FAST ? MFG_CORE_SMALL_WAVES : 2) void k_eval
   const int TB = WAVES * (WAVE / d);
   int32_t* idx = p.idx + p.s_idx * k;
   // start rows of this block's tiles (blockIdx.x + m gridDim.x): the only entries core_small_body reads, its prefetch of the
-  // next tile included.  Trajectory j starts at row (j mod N) L of emp32 viewed as [N L, d], i.e. emp32[j mod N, 0].
+  // next tile included.  Trajectory j starts at row (j mod N) L of emp32 viewed as [N L, d], i.e. emp32[j mod N, 0] (a
+  // forecast, mfg_forecast_pop.h, passes its start rows [N, d] with L = 1).
   for (int64_t b0 = (int64_t)blockIdx.x * TB; b0 < a.B; b0 += (int64_t)gridDim.x * TB) {
     const int64_t b = b0 + threadIdx.x;
     if (threadIdx.x < TB && b < a.B) idx[b] = (int32_t)((b % p.N) * p.L);
@@ -71,25 +72,7 @@ __global__ __launch_bounds__(BLOCK) void k_eval_metrics_pop(const float* __restr
     double l1_sum = 0.0, jsd_sum = 0.0, l1 = 0.0, jsd = 0.0;
     for (int l = 0; l < L; ++l) {
       const int64_t eo = (n * L + l) * d + lane;
-      double a = 1.0, c = 1.0, e1 = 0.0;
-      if (on) {
-        const float g = gen[(j * L + l) * d + lane];
-        e1 = fabs(emp64[eo] - (double)g);
-        a = emp32[eo];
-        c = g;
-        if (a == 0.0) a = 1e-100;
-        if (c == 0.0) c = 1e-100;
-      }
-      l1 = wave_sum(e1);
-      const double sp = wave_sum(on ? a : 0.0), sq = wave_sum(on ? c : 0.0);
-      const double sm = 0.5 * (sp + sq);
-      double acc = 0.0;
-      if (on) {
-        const double m = 0.5 * (a + c) / sm;
-        const double pn = a / sp, qn = c / sq;
-        acc = pn * log(pn / m) + qn * log(qn / m);
-      }
-      jsd = 0.5 * wave_sum(acc);
+      eval_step_l1_jsd(gen + (j * L + l) * d + lane, emp32, emp64, eo, on, l1, jsd);
       l1_sum += l1;
       jsd_sum += jsd;
     }

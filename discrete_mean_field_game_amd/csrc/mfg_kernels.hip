@@ -24,6 +24,7 @@
 #include "../../include/mfg_hip.h"
 #include "mfg_core.h"
 #include "mfg_evaluate_pop.h"
+#include "mfg_forecast_pop.h"
 #include "mfg_irl_population.h"
 #include "mfg_population.h"
 
@@ -3331,6 +3332,71 @@ int mfg_evaluate_pop(const float* emp32, const double* emp64, int64_t N, int L, 
   if (rc != MFG_OK) return rc;
   launch_eval_metrics_pop(traj, emp32, emp64, N, L, d, NR, K, per_traj, metrics, S(stream));
   return check_launch("evaluate_pop metrics");
+}
+
+// ---- ensemble forecast (mfg_forecast_pop.h): R rollouts per start state of K policies, reduced in at most three launches ------
+size_t mfg_forecast_pop_workspace_bytes(int64_t N, int H, int d, int K, int repeats, int traj_given) {
+  if (N < 1 || H < 1 || d < 1 || K < 1 || repeats < 1) return 0;
+  return forecast_pop_workspace_bytes(N, H, d, K, repeats, traj_given != 0);
+}
+
+int mfg_forecast_pop(const float* start32, int64_t N, int H, int d, int K, const double* theta, const double* shift,
+                     const double* alpha_scale, const uint64_t* seed, uint32_t first_step, int repeats, int precision,
+                     const int32_t* ranks, int Q, const float* emp32, const double* emp64, double* mean, double* std, float* quant,
+                     double* curves, float* pi_traj, void* workspace, size_t workspace_bytes, mfg_stream_t stream) {
+  REQUIRE(K >= 1 && K <= MFG_POP_MAX_K, "population size K outside [1, MFG_POP_MAX_K]");
+  REQUIRE(d >= 1, "d < 1");
+  if (d > WAVE) return fail(MFG_EUNSUPPORTED, "ensemble forecast: d=%d > 64 (as for the populations)", d);
+  REQUIRE(H >= 2, "horizon H < 2");
+  REQUIRE(N >= 1, "no start states (N < 1)");
+  REQUIRE(repeats >= 1, "repeats < 1");
+  REQUIRE(N * (int64_t)H <= 0x7FFFFFFF && N * (int64_t)repeats <= 0x7FFFFFFF, "N H or N repeats too large");
+  REQUIRE(start32 && theta && shift && alpha_scale && seed && mean && std && workspace, "null pointer");
+  CHECK_PRECISION();
+  REQUIRE((uint64_t)first_step + (uint64_t)(H - 1) <= 0xFFFFFFFFull, "Philox step counter would wrap");
+  REQUIRE(Q >= 0 && Q <= MFG_FORECAST_MAX_RANKS, "number of ranks Q outside [0, MFG_FORECAST_MAX_RANKS]");
+  REQUIRE(Q == 0 || (ranks && quant), "ranks / quant: null pointer with Q > 0");
+  ForecastRanks fr{};
+  for (int q = 0; q < Q; ++q) {
+    REQUIRE(ranks[q] >= 0 && ranks[q] < repeats, "a rank outside [0, repeats)");
+    fr.r[q] = ranks[q];
+  }
+  REQUIRE((emp32 != nullptr) == (emp64 != nullptr), "emp32 and emp64: both or neither");
+  REQUIRE((curves != nullptr) == (emp32 != nullptr), "curves is given exactly when emp32 / emp64 are");
+  if (repeats > MFG_FORECAST_MAX_REPEATS)
+    return fail(MFG_EUNSUPPORTED, "ensemble forecast: repeats=%d > MFG_FORECAST_MAX_REPEATS=%d", repeats,
+                MFG_FORECAST_MAX_REPEATS);
+  const size_t need = forecast_pop_workspace_bytes(N, H, d, K, repeats, pi_traj != nullptr);
+  if (workspace_bytes < need)
+    return fail(MFG_EWORKSPACE, "ensemble forecast workspace: need %lld bytes, have %lld", (long long)need,
+                (long long)workspace_bytes);
+  const int64_t NR = N * repeats;
+  PopArgs p = pop_args(K, NR, d, H - 1, 0, seed, shift, alpha_scale, nullptr, nullptr, 0);
+  p.N = N;
+  p.L = 1;  // (the start-index table's row stride: member j starts at row j mod N of start32 [N, d])
+  p.s_idx = eval_pop_idx_stride(NR);
+  p.idx = reinterpret_cast<int32_t*>(workspace);
+  double* per_step = reinterpret_cast<double*>(reinterpret_cast<char*>(workspace) + (size_t)K * p.s_idx * 4);
+  float* traj = pi_traj ? pi_traj : reinterpret_cast<float*>(per_step + (size_t)K * H * NR * 2);
+  CoreArgs a{};
+  a.pi0 = start32;
+  a.num_start = N;
+  a.theta = theta;
+  a.gamma = 1.0;
+  a.B = NR;
+  a.d = d;
+  a.T = H - 1;
+  a.reward_kind = MFG_REWARD_EXTERNAL;  // (states only: no reward is formed)
+  a.first_step = first_step;
+  a.pi_traj = traj;
+  int rc = launch_core(a, true, false, precision, S(stream), &p);
+  if (rc != MFG_OK) return rc;
+  rc = launch_forecast_reduce(traj, N, H, d, K, repeats, fr, Q, mean, std, quant, S(stream));
+  if (rc != MFG_OK) return fail(rc, "%s", "forecast reduce: LDS request beyond the budget");
+  if ((rc = check_launch("forecast_pop reduce")) != MFG_OK) return rc;
+  if (!emp32) return MFG_OK;
+  launch_forecast_curves(traj, emp32, emp64, N, H, d, NR, K, per_step, curves, S(stream));
+  return check_launch("forecast_pop curves");
 }
 
 // ---- IRL forward learners (AC_IRL.train): the reward comes from the reward network, launched between the core kernel and the

@@ -26,7 +26,7 @@ namespace mfg {
 // IRL and evaluation forms last: the others keep their offsets in the kernel arguments)
 struct PopArgs {
   int K;
-  int L;             // evaluation: rows per test file (episode_length)
+  int L;             // evaluation: rows of the start table between two start rows (a test file's rows; 1 for a forecast's [N, d])
   int64_t F;         // critic features of one learner (w stride; G stride F + 3)
   int64_t s_pi0;     // floats between the learners' start / current states of the core launch (0: the shared start-state table)
   int64_t s_gpi;     // floats between the learners' states read by the gradient kernels (pi_traj or the step's states)

@@ -60,6 +60,13 @@ def _with_ctx(method):
     return bound
 
 
+def check_forecast_rng(rng):
+    """forecast() draws its ensemble with the counter-based generator (member j is keyed by its trajectory id): the legacy
+    np.random stream of rng='numpy' has no such members.  ValueError for anything but 'philox'."""
+    if rng != 'philox':
+        raise ValueError("forecast needs rng='philox': the ensemble's members are Philox trajectories (got rng=%r)" % (rng,))
+
+
 class actor_critic:
 
     def __init__(self, theta=8.86349, shift=0.16, alpha_scale=12000, d=21, *, pi0=None, path_to_dir=None,
@@ -795,6 +802,41 @@ class actor_critic:
                 trajs.append(torch.cat(rows, dim=0))
             traj = torch.stack(trajs, dim=0)
         return self._out(traj, pi0, single)
+
+    @_with_ctx
+    def forecast(self, pi0, total_hours, repeats=256, probs=(0.05, 0.5, 0.95), *, emp=None, want_traj=False):
+        """The forecast from pi0 with its uncertainty: `repeats` sample paths of generate_trajectory (mfg_ac2.py:566-592) per
+        start row under the current policy, reduced on the device (mfg_forecast_pop, K = 1) to the expected histogram per
+        hour, its spread and the quantile bands the reference reads off one path by hand (visualize_test, mfg_ac2.py:763).
+        pi0 (d,) or [N, d].  Member j (0 <= j < N repeats) starts at row j mod N under this instance's seed, the Philox steps
+        _rng_step .. _rng_step + total_hours - 2 and trajectory id j: member 0 of a single start row is what
+        generate_trajectory(pi0, total_hours) gives from the same state.  Advances _rng_step by total_hours - 1.  emp
+        [N, >= total_hours, >= d] (held-out rows): the error curves per hour.  Returns a population.Forecast of NumPy arrays
+        (tensors when pi0 is one) without the leading K: mean, std [N, H, d], quantiles [N, H, Q, d], curves [H, 4] or None."""
+        from . import population
+        check_forecast_rng(self.rng)
+        as_tensor = isinstance(pi0, torch.Tensor)
+        ranks = population.forecast_ranks(probs, repeats)
+        start, emp = population._forecast_inputs(_as_np(pi0), None if emp is None else _as_np(emp), self.d, total_hours)
+        ops.check_forecast_args(start.shape, total_hours, repeats, ranks, self.precision)
+        H = int(total_hours)
+        first_step = self._rng_step
+        self._rng_step += H - 1
+        dev = self.device
+        one = lambda v: torch.as_tensor(np.array([float(v)], dtype=np.float64), device=dev)
+        seeds = torch.as_tensor(np.array([self.seed & 0xFFFFFFFFFFFFFFFF], dtype=np.uint64).view(np.int64), device=dev)
+        self._flush_pending()
+        try:
+            got = population.forecast_policies(start, emp, self._theta.reshape(1).contiguous(), one(self.shift),
+                                               one(self.alpha_scale), seeds, H, first_step, int(repeats), ranks, self.precision,
+                                               dev, self._ctx, want_traj)
+        except L.MfgError as e:
+            if e.code:                               # refused by the library before anything was launched
+                self._rng_step = first_step
+            raise
+        pick = lambda a: None if a is None else (torch.as_tensor(a[0], device=dev) if as_tensor else a[0])
+        return population.Forecast(pick(got['mean']), pick(got['std']), pick(got['quant']), probs, ranks, pick(got['curves']),
+                                   repeats, pick(got['traj']))
 
     _EVAL_HEADER = ('theta,shift,alpha_scale,mean_l1_final,std_l1_final,mean_l1_mean,std_l1_mean,'
                     'mean_JSD_final,std_JSD_final,mean_JSD_mean,std_JSD_mean\n')

@@ -954,6 +954,83 @@ def evaluate_pop(emp32, emp64, thetas, shifts, alpha_scales, seeds, first_step=0
     return (metrics, traj) if want_traj else metrics
 
 
+def forecast_pop_workspace(N, horizon, d, K, repeats, traj_given, device):
+    """The scratch buffer of one forecast_pop call (mfg_forecast_pop_workspace_bytes, rounded up to whole doubles)."""
+    nbytes = int(L.lib().mfg_forecast_pop_workspace_bytes(int(N), int(horizon), int(d), int(K), int(repeats), int(bool(traj_given))))
+    return torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=device)
+
+
+def check_forecast_args(start_shape, horizon, repeats, ranks, precision, emp32_shape=None, emp64_shape=None):
+    """The argument rules of forecast_pop that need no GPU (ValueError): start32 [N, d], horizon >= 2, 1 <= repeats <=
+    FORECAST_MAX_REPEATS, at most FORECAST_MAX_RANKS ranks, each in [0, repeats), a known precision, emp32 / emp64 both
+    [N, horizon, d] or both absent.  Returns (N, d, horizon, repeats, ranks as a list of ints)."""
+    if len(start_shape) != 2:
+        raise ValueError('start32: expected [N, d], got %s' % (tuple(start_shape),))
+    N, d = int(start_shape[0]), int(start_shape[1])
+    horizon, repeats = int(horizon), int(repeats)
+    if horizon < 2:
+        raise ValueError('horizon=%d: a forecast rolls at least one step (horizon >= 2)' % horizon)
+    if repeats < 1:
+        raise ValueError('repeats=%d: at least one rollout per start state' % repeats)
+    if repeats > L.FORECAST_MAX_REPEATS:
+        raise ValueError('repeats=%d: at most %d members per start state (MFG_FORECAST_MAX_REPEATS)' % (repeats, L.FORECAST_MAX_REPEATS))
+    ranks = [int(r) for r in ranks]
+    if len(ranks) > L.FORECAST_MAX_RANKS:
+        raise ValueError('%d ranks: at most %d order statistics per call (MFG_FORECAST_MAX_RANKS)' % (len(ranks), L.FORECAST_MAX_RANKS))
+    for r in ranks:
+        if not 0 <= r < repeats:
+            raise ValueError('rank %d outside [0, repeats=%d)' % (r, repeats))
+    if precision not in L.PRECISIONS:
+        raise ValueError("precision must be 'mixed' or 'f64'")
+    if (emp32_shape is None) != (emp64_shape is None):
+        raise ValueError('emp32 and emp64: give both or neither')
+    if emp32_shape is not None and (tuple(emp32_shape) != (N, horizon, d) or tuple(emp64_shape) != (N, horizon, d)):
+        raise ValueError('emp32 / emp64: expected two [%d, %d, %d] tensors, got %s and %s'
+                         % (N, horizon, d, tuple(emp32_shape), tuple(emp64_shape)))
+    return N, d, horizon, repeats, ranks
+
+
+def forecast_pop(start32, thetas, shifts, alpha_scales, seeds, horizon, first_step=0, repeats=1, ranks=(), precision='mixed',
+                 emp32=None, emp64=None, want_traj=False, ws=None):
+    """The ensemble forecast of K policies in at most three launches (mfg_forecast_pop; the forecast the reference plots from one
+    path, mfg_ac2.py:566-592, :763): start32 [N,d] the start states; thetas, shifts, alpha_scales fp64 and seeds int64 (read
+    as uint64) device arrays [K].  Learner k's member j (0 <= j < N repeats) starts at start32[j mod N] under Philox (seeds[k],
+    first_step + t, j) and has `horizon` rows, row 0 the start row.  Returns a dict of device tensors: mean, std [K,N,horizon,d]
+    fp64 over the `repeats` members of each start state (std: ddof = 0); quant [K,N,horizon,Q,d] fp32, the order statistics of
+    the 0-based `ranks` among those members (None without ranks); curves [K,horizon,4] fp64 (l1_mean, l1_std, jsd_mean, jsd_std
+    over all N repeats members per hour against emp32 / emp64 [N,horizon,d]; None without them); traj [K, N repeats, horizon, d]
+    fp32 with want_traj (None otherwise)."""
+    import ctypes as C
+    _chk_f32(start32, 'start32')
+    if emp32 is not None:
+        _chk_f32(emp32, 'emp32')
+    if emp64 is not None:
+        _chk_f64(emp64, 'emp64')
+    N, d, H, repeats, ranks = check_forecast_args(start32.shape, horizon, repeats, ranks, precision,
+                                                  None if emp32 is None else emp32.shape, None if emp64 is None else emp64.shape)
+    K = thetas.numel()
+    _chk_pop(K, 'thetas', thetas, torch.float64)
+    for name, t in (('shifts', shifts), ('alpha_scales', alpha_scales)):
+        _chk_pop(K, name, t, torch.float64)
+    _chk_pop(K, 'seeds', seeds, torch.int64)
+    dev = start32.device
+    Q = len(ranks)
+    out = {'mean': torch.empty(K, N, H, d, dtype=torch.float64, device=dev),
+           'std': torch.empty(K, N, H, d, dtype=torch.float64, device=dev),
+           'quant': torch.empty(K, N, H, Q, d, dtype=torch.float32, device=dev) if Q else None,
+           'curves': torch.empty(K, H, 4, dtype=torch.float64, device=dev) if emp32 is not None else None,
+           'traj': torch.empty(K, N * repeats, H, d, dtype=torch.float32, device=dev) if want_traj else None}
+    if ws is None:
+        ws = forecast_pop_workspace(N, H, d, K, repeats, want_traj, dev)
+    rk = (C.c_int32 * max(Q, 1))(*ranks)
+    L.check(L.lib().mfg_forecast_pop(start32.data_ptr(), N, H, d, K, thetas.data_ptr(), shifts.data_ptr(), alpha_scales.data_ptr(),
+                                     seeds.data_ptr(), int(first_step), repeats, L.PRECISIONS[precision], rk, Q, _ptr(emp32),
+                                     _ptr(emp64), out['mean'].data_ptr(), out['std'].data_ptr(), _ptr(out['quant']),
+                                     _ptr(out['curves']), _ptr(out['traj']), ws.data_ptr(), ws.numel() * ws.element_size(),
+                                     _stream()), 'mfg_forecast_pop')
+    return out
+
+
 def policy_logpdf(pi, P, thetas, shift, alpha_scale=1.0, alpha_floor=0.0, p_floor=0.0):
     """log q_k(P_n | pi_n) [N,K] of the product-Dirichlet policy under K thetas (ac_irl.py:270-289, :324-379)."""
     _chk_f32(pi, 'pi'); _chk_f32(P, 'P'); _chk_f64(thetas, 'thetas')

@@ -320,6 +320,143 @@ def gridsearch(theta_range, shift_range, alpha_range, indir, outfile, *, d=21, s
     return list_tuples
 
 
+# ------------------------------------------------------------------------------------------------------------ forecast
+# The forecast the project exists for, with its uncertainty: R rollouts per start state under each policy, reduced on the device
+# (mfg_forecast_pop) to the expected histogram per hour, its spread, quantile bands per topic and -- against held-out rows --
+# the growth of the error with the horizon.  The reference plots one sample path by hand (visualize_test, mfg_ac2.py:763,
+# ac_irl.py:1663); its VAR baseline returns a forecast with intervals (var.py:294-327).
+FORECAST_CHUNK = L.POP_MAX_K    # policies per forecast_pop call of forecast() (more go in chunks)
+FORECAST_PROBS = (0.05, 0.5, 0.95)
+
+
+def forecast_ranks(probs, R):
+    """The 0-based ranks floor(p (R - 1)) among R ascending ensemble members for the probabilities `probs` (each in [0, 1], at
+    most FORECAST_MAX_RANKS of them): the order statistics a forecast returns as its quantiles -- members of the ensemble,
+    not interpolations.  ValueError outside those rules.  Needs no GPU."""
+    R = int(R)
+    if R < 1:
+        raise ValueError('R=%d: an ensemble has at least one member' % R)
+    probs = [float(p) for p in np.asarray(probs, dtype=np.float64).reshape(-1)]
+    if len(probs) > L.FORECAST_MAX_RANKS:
+        raise ValueError('%d probabilities: at most %d quantiles per forecast' % (len(probs), L.FORECAST_MAX_RANKS))
+    for p in probs:
+        if not 0.0 <= p <= 1.0:        # (a NaN fails both comparisons)
+            raise ValueError('probability %r outside [0, 1]' % p)
+    return [int(np.floor(p * (R - 1))) for p in probs]
+
+
+class Forecast:
+    """The result of a forecast (NumPy): mean, std [K, N, H, d] over the ensemble of each start state; quantiles
+    [K, N, H, Q, d], the order statistics of ranks[q] = floor(probs[q] (R - 1)); curves [K, H, 4] = (l1_mean, l1_std, jsd_mean,
+    jsd_std) per hour against the held-out rows, or None without them; traj [K, N R, H, d], the members, only when asked for.
+    A single-policy forecast (actor_critic.forecast) drops the leading K."""
+
+    def __init__(self, mean, std, quantiles, probs, ranks, curves, repeats, traj=None):
+        self.mean, self.std, self.quantiles, self.curves, self.traj = mean, std, quantiles, curves, traj
+        self.probs, self.ranks, self.repeats = tuple(probs), tuple(ranks), int(repeats)
+
+    def learner(self, k):
+        """Row k as a Forecast of its own."""
+        pick = lambda a: None if a is None else a[k]
+        return Forecast(pick(self.mean), pick(self.std), pick(self.quantiles), self.probs, self.ranks, pick(self.curves),
+                        self.repeats, pick(self.traj))
+
+
+def forecast_policies(start, emp, thetas, shifts, alpha_scales, seeds, horizon, first_step, repeats, ranks, precision, device, ctx,
+                      want_traj=False):
+    """One ops.forecast_pop call as NumPy arrays (mean, std, quant, curves, traj): `start` [N, d] fp64 rows, `emp` [N, H, d] or
+    None; `thetas`, `shifts`, `alpha_scales` fp64 and `seeds` int64 device tensors [K].  MfgError when a mixed-precision policy
+    left the fp32 range (ctx: the bound context whose status word the launch reports into)."""
+    start32 = torch.as_tensor(np.ascontiguousarray(start, dtype=np.float32), device=device)
+    emp64 = emp32 = None
+    if emp is not None:
+        emp64 = torch.as_tensor(np.ascontiguousarray(emp, dtype=np.float64), device=device)
+        emp32 = torch.as_tensor(np.ascontiguousarray(emp, dtype=np.float64).astype(np.float32), device=device)
+    out = ops.forecast_pop(start32, thetas, shifts, alpha_scales, seeds, horizon, first_step=first_step, repeats=repeats,
+                           ranks=ranks, precision=precision, emp32=emp32, emp64=emp64, want_traj=want_traj)
+    host = {k: None if v is None else v.cpu().numpy() for k, v in out.items()}
+    if precision == 'mixed' and ctx.status(synchronize=True):
+        raise L.MfgError('a mixed-precision forecast ran a policy with |theta| (1 + |shift|) > 86 (or theta not finite): '
+                         'its rows are NaN; use precision=\'f64\'')
+    if host['quant'] is None:
+        K, N = host['mean'].shape[:2]
+        host['quant'] = np.zeros((K, N, int(horizon), 0, host['mean'].shape[-1]), dtype=np.float32)
+    return host
+
+
+def _forecast_inputs(pi0, emp, d, horizon):
+    """(start [N, d] fp64, emp [N, H, d] fp64 or None) of a forecast: the start rows are `pi0` ((d,) or [N, d]) or, without it,
+    row 0 of each emp matrix.  ValueError for unusable shapes."""
+    d, horizon = int(d), int(horizon)
+    if not 1 <= d <= 64:
+        raise ValueError('d=%d: the ensemble forecast covers d <= 64 (as the populations do)' % d)
+    if horizon < 2:
+        raise ValueError('horizon=%d: a forecast rolls at least one step (horizon >= 2)' % horizon)
+    if emp is not None:
+        emp = np.asarray(emp, dtype=np.float64)
+        if emp.ndim == 2:
+            emp = emp[None]
+        if emp.ndim != 3 or emp.shape[1] < horizon or emp.shape[2] < d:
+            raise ValueError('emp: expected [N, >= %d, >= %d], got %s' % (horizon, d, emp.shape))
+        emp = np.ascontiguousarray(emp[:, :horizon, :d])
+    if pi0 is None:
+        if emp is None:
+            raise ValueError('a forecast needs start rows: pi0, or emp whose row 0 they are')
+        start = emp[:, 0].copy()
+    else:
+        start = np.asarray(pi0, dtype=np.float64)
+        if start.ndim == 1:
+            start = start[None]
+        if start.ndim != 2 or start.shape[1] < d:
+            raise ValueError('pi0: expected (d,) or [N, d] with d >= %d, got %s' % (d, start.shape))
+        start = np.ascontiguousarray(start[:, :d])
+    if emp is not None and emp.shape[0] != start.shape[0]:
+        raise ValueError('pi0 has %d rows, emp %d matrices' % (start.shape[0], emp.shape[0]))
+    return start, emp
+
+
+def forecast(thetas, shifts, alpha_scales, pi0, horizon, *, d, seed=0, repeats=256, probs=FORECAST_PROBS, emp=None,
+             precision='mixed', device=None, first_step=0, want_traj=False):
+    """The ensemble forecast of K policies (thetas, shifts, alpha_scales: scalars or K values) from the start rows `pi0`
+    ((d,) or [N, d]; None: row 0 of each `emp` matrix) over `horizon` hours: `repeats` rollouts per start state and policy,
+    reduced on the device.  Every policy uses the same seed and the Philox steps first_step .. first_step + horizon - 2: common
+    random numbers, so policies are compared on the same noise, and with first_step = 0 policy k's members are the
+    generate_trajectory rows of a fresh actor_critic(theta_k, shift_k, alpha_k, d, seed=seed) over the repeats-fold tiled start
+    rows.  (seed may also be K values, one per policy: a trained population's learners at their own seeds.)  emp [N, >= horizon, >= d]
+    (held-out rows): the error curves are returned too.  More than FORECAST_CHUNK policies go in chunks.  Returns a Forecast.
+    Runs on a context of its own: a diverged mixed-precision policy raises MfgError and leaves the caller's status word alone."""
+    if precision not in ('mixed', 'f64'):
+        raise ValueError("precision must be 'mixed' or 'f64'")
+    th = np.asarray(thetas, dtype=np.float64).reshape(-1)
+    K = th.shape[0]
+    if K < 1:
+        raise ValueError('no policies')
+    sh, al = broadcast('shifts', shifts, K), broadcast('alpha_scales', alpha_scales, K)
+    sd = broadcast('seed', seed, K, np.uint64).view(np.int64)
+    ranks = forecast_ranks(probs, repeats)
+    start, emp = _forecast_inputs(pi0, emp, d, horizon)
+    ops.check_forecast_args(start.shape, horizon, repeats, ranks, precision)
+    if not torch.cuda.is_available():
+        raise L.MfgError('forecast needs a ROCm GPU: the HIP hot path has no CPU fallback')
+    L.lib()
+    ops.init()
+    dev = torch.device(device) if device is not None else torch.device('cuda', torch.cuda.current_device())
+    ctx = ops.Context(dev)
+    prev = ctx.bind_scoped()
+    try:
+        parts = []
+        for c0 in range(0, K, FORECAST_CHUNK):
+            n = min(FORECAST_CHUNK, K - c0)
+            f = lambda a: torch.as_tensor(a[c0:c0 + n].copy(), device=dev)
+            parts.append(forecast_policies(start, emp, f(th), f(sh), f(al), f(sd), int(horizon), int(first_step), int(repeats),
+                                           ranks, precision, dev, ctx, want_traj))
+    finally:
+        ctx.restore(prev)
+        ctx.close()
+    cat = lambda key: None if parts[0][key] is None else np.concatenate([p[key] for p in parts])
+    return Forecast(cat('mean'), cat('std'), cat('quant'), probs, ranks, cat('curves'), repeats, cat('traj'))
+
+
 class _Population:
     """What ActorCriticPopulation and AC_IRLPopulation share: the K learners' theta, w, shifts, alpha_scales and seeds (host
     and device copies), the start-state table, the Philox step counter and the instance's own ops.Context.  Subclasses say
@@ -511,6 +648,42 @@ class _Population:
         write_eval_rows(outfile, write_header, [(float(thetas[k]), float(self.shifts[k]), float(self.alpha_scales[k]))
                                                 for k in live], table[live])
         return table[:, 0::2].copy()
+
+    @_with_ctx
+    def forecast(self, pi0=None, indir=None, horizon=16, repeats=256, probs=FORECAST_PROBS, *, want_traj=False):
+        """The ensemble forecast of every learner's current policy in one forecast_pop call (a Forecast with a leading K):
+        learner k rolls `repeats` members per start row with its own seed from the population's Philox step.  Start rows: `pi0`
+        ((d,) or [N, d]), or row 0 of each file of cwd/indir; with indir the files' first `horizon` rows are the held-out rows
+        and the error curves are returned.  Advances the Philox step by horizon - 1, as each learner's own forecast() would
+        (restored when the library refuses the call).  Failed learners are not launched: NaN rows.  MfgError when a
+        mixed-precision policy left the fp32 range."""
+        emp = load_empirical(indir, self.d, int(horizon)) if indir is not None else None
+        ranks = forecast_ranks(probs, repeats)
+        start, emp = _forecast_inputs(pi0, emp, self.d, horizon)
+        ops.check_forecast_args(start.shape, horizon, repeats, ranks, self.precision)
+        H, R = int(horizon), int(repeats)
+        first_step = self._rng_step
+        self._rng_step += H - 1                      # (a diverged launch has run: its step is spent, as in train())
+        live = self._healthy()
+        sub = (lambda t: t) if len(live) == self.K else (lambda t: t[torch.as_tensor(live, device=self.device)].contiguous())
+        N, Q = start.shape[0], len(ranks)
+        res = {'mean': np.full((self.K, N, H, self.d), np.nan), 'std': np.full((self.K, N, H, self.d), np.nan),
+               'quant': np.full((self.K, N, H, Q, self.d), np.nan, dtype=np.float32),
+               'curves': None if emp is None else np.full((self.K, H, 4), np.nan),
+               'traj': np.full((self.K, N * R, H, self.d), np.nan, dtype=np.float32) if want_traj else None}
+        try:
+            if live:
+                got = forecast_policies(start, emp, sub(self._theta), sub(self._shifts_dev), sub(self._alphas_dev),
+                                        sub(self._seeds_dev), H, first_step, R, ranks, self.precision, self.device, self._ctx,
+                                        want_traj)
+                for key, a in res.items():
+                    if a is not None:
+                        a[live] = got[key]
+        except L.MfgError as e:
+            if e.code:                               # refused by the library before anything was launched
+                self._rng_step = first_step
+            raise
+        return Forecast(res['mean'], res['std'], res['quant'], probs, ranks, res['curves'], R, res['traj'])
 
     def learner(self, k):
         """An actor_critic holding learner k's parameters, table and Philox position (for evaluate / generate_trajectory

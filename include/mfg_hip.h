@@ -534,6 +534,39 @@ int mfg_evaluate_pop(const float* emp32, const double* emp64, int64_t N, int L, 
                      int precision, double* metrics, float* pi_traj, void* workspace, size_t workspace_bytes,
                      mfg_stream_t stream);
 
+/* Ensemble forecast: R rollouts per start state of K policies, reduced on the device -- the expected histogram per hour, its
+ * spread, order statistics per topic and the error against held-out rows per hour.  The reference draws this by hand from ONE
+ * sample path (generate_trajectory, mfg_ac2.py:566-592, plotted by visualize_test, mfg_ac2.py:763, ac_irl.py:1663); its VAR
+ * baseline returns a forecast with intervals (var.py:294-327).  At most THREE launches (the rollouts, the reduction over the
+ * members, and with emp the curves), no host synchronisation.
+ *   start32 [N,d]: the start states.  theta, shift, alpha_scale [K] fp64 and seed [K] uint64: learner k's policy; first_step:
+ *   shared by all K.  H >= 2: rows per member, row 0 the start row.
+ *   Members: learner k's member j (0 <= j < N R, R = repeats) belongs to start state n = j mod N, starts at start32[n] and is
+ *   keyed by Philox (seed[k], first_step + t, trajectory id j): bit for bit the trajectories of mfg_evaluate_pop for an emp32
+ *   whose row 0 is start32, i.e. of mfg_rollout over the R-fold tiled start rows (generate_trajectory's states).
+ *   mean, std [K,N,H,d] fp64: over the R members of (k, n), per hour l and topic i; std with ddof = 0.  Both accumulate in fp64
+ *   from the fp32 trajectory values, std in two passes (the mean first, then sum (x - mean)^2), in a fixed order that depends on
+ *   (R, d) only.  No floating-point atomics: learner k's outputs depend on its own inputs only, whatever K is.
+ *   quant [K,N,H,Q,d] fp32 (NULL allowed iff Q == 0): quant[k,n,l,q,i] is the order statistic of rank ranks[q] (0-based,
+ *   ascending) among the R member values of the cell -- an element of the ensemble, not an interpolation, hence bit exact.
+ *   Ties are legal (row 0 is all ties); ranks (a HOST array [Q]) may repeat and need not be sorted.
+ *   curves [K,H,4] fp64 (NULL iff emp32 and emp64 are NULL): curves[k,l,:] = (l1_mean, l1_std, jsd_mean, jsd_std), mean and
+ *   std (ddof = 0) over all N R members of the step's L1 (fp64, against emp64 [N,H,d]) and JSD (mfg_jsd(emp32 row, generated
+ *   row)): the per-step terms of mfg_evaluate_pop's metrics (mfg_ac2.py:631-666), per step instead of per trajectory.
+ *   pi_traj [K, N R, H, d] fp32 or NULL (then the trajectories stay in the workspace).
+ *   workspace: mfg_forecast_pop_workspace_bytes(N, H, d, K, repeats, pi_traj != NULL) bytes; contents are scratch.
+ * Checked before anything is launched: everything mfg_evaluate_pop checks, with H for L; 0 <= Q <= MFG_FORECAST_MAX_RANKS, every
+ * rank in [0, repeats), emp32 and emp64 both given or both NULL, curves NULL exactly when they are (MFG_EINVAL); repeats <=
+ * MFG_FORECAST_MAX_REPEATS (MFG_EUNSUPPORTED); the workspace (MFG_EWORKSPACE).  Mixed precision reports into and is refused
+ * on the bound context's status word exactly as mfg_evaluate_pop. */
+#define MFG_FORECAST_MAX_RANKS 8
+#define MFG_FORECAST_MAX_REPEATS 1024
+size_t mfg_forecast_pop_workspace_bytes(int64_t N, int H, int d, int K, int repeats, int traj_given);
+int mfg_forecast_pop(const float* start32, int64_t N, int H, int d, int K, const double* theta, const double* shift,
+                     const double* alpha_scale, const uint64_t* seed, uint32_t first_step, int repeats, int precision,
+                     const int32_t* ranks, int Q, const float* emp32, const double* emp64, double* mean, double* std, float* quant,
+                     double* curves, float* pi_traj, void* workspace, size_t workspace_bytes, mfg_stream_t stream);
+
 /* Weights of the reward network of networks.py:46-81 as device pointers (layouts as for mfg_reward_net_forward). */
 typedef struct mfg_reward_net {
   int k1, f2, k2, n3, n4;
