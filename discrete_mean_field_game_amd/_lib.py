@@ -191,6 +191,15 @@ SIGNATURES['mfg_forecast_pop_workspace_bytes'] = (_sz, [_i64, _i32, _i32, _i32, 
 SIGNATURES['mfg_forecast_pop'] = (_i32, [_p, _i64, _i32, _i32, _i32, _p, _p, _p, _p, _u32, _i32, _i32, C.POINTER(C.c_int32), _i32,
                                          _p, _p, _p, _p, _p, _p, _p, _p, _sz, _p])
 
+# the backward-equation check.  given: P, K, M, T, d, metrics, steps, V, workspace, workspace_bytes, stream; pop: start32, N, H,
+# d, K, theta, shift, alpha_scale, seed, first_step, repeats, precision, metrics, steps, V, actions, pi_traj, workspace,
+# workspace_bytes, stream
+SIGNATURES['mfg_consistency_given_workspace_bytes'] = (_sz, [_i32, _i64, _i32, _i32])
+SIGNATURES['mfg_consistency_given'] = (_i32, [_p, _i32, _i64, _i32, _i32, _p, _p, _p, _p, _sz, _p])
+SIGNATURES['mfg_consistency_pop_workspace_bytes'] = (_sz, [_i64, _i32, _i32, _i32, _i32, _i32, _i32, _i32])
+SIGNATURES['mfg_consistency_pop'] = (_i32, [_p, _i64, _i32, _i32, _i32, _p, _p, _p, _p, _u32, _i32, _i32, _p, _p, _p, _p, _p, _p,
+                                            _sz, _p])
+
 _lib = None
 
 

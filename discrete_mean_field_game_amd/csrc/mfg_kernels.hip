@@ -25,6 +25,7 @@
 #include "mfg_core.h"
 #include "mfg_evaluate_pop.h"
 #include "mfg_forecast_pop.h"
+#include "mfg_consistency_pop.h"
 #include "mfg_irl_population.h"
 #include "mfg_population.h"
 
@@ -3397,6 +3398,99 @@ int mfg_forecast_pop(const float* start32, int64_t N, int H, int d, int K, const
   if (!emp32) return MFG_OK;
   launch_forecast_curves(traj, emp32, emp64, N, H, d, NR, K, per_step, curves, S(stream));
   return check_launch("forecast_pop curves");
+}
+
+// ---- backward-equation check (mfg_consistency_pop.h): the scan and the reduction of K groups; with the rollouts three launches ----
+size_t mfg_consistency_given_workspace_bytes(int K, int64_t M, int T, int steps_given) {
+  if (K < 1 || M < 1 || T < 1) return 0;
+  return consistency_given_workspace_bytes(K, M, T, steps_given != 0);
+}
+
+// the two launches both entries share: B = K M trajectories' actions -> steps (given, or `scratch`), V if asked for, metrics
+static int consistency_launches(const float* P, int K, int64_t M, int T, int d, double* metrics, double* steps, double* V,
+                                hipStream_t st) {
+  launch_consistency_backward(P, (int64_t)K * M, T, d, V, steps, num_cus(), st);
+  if (const int rc = check_launch("consistency backward"); rc != MFG_OK) return rc;
+  launch_consistency_reduce(steps, K, M * T, metrics, st);
+  return check_launch("consistency reduce");
+}
+
+int mfg_consistency_given(const float* P, int K, int64_t M, int T, int d, double* metrics, double* steps, double* V,
+                          void* workspace, size_t workspace_bytes, mfg_stream_t stream) {
+  REQUIRE(K >= 1 && K <= MFG_POP_MAX_K, "number of groups K outside [1, MFG_POP_MAX_K]");
+  REQUIRE(d >= 1, "d < 1");
+  if (d > WAVE) return fail(MFG_EUNSUPPORTED, "backward-equation check: d=%d > 64 (as for the populations)", d);
+  REQUIRE(T >= 1, "T < 1 (hours H < 2)");
+  REQUIRE(M >= 1, "no trajectories (M < 1)");
+  REQUIRE(M * (int64_t)T <= 0x7FFFFFFF, "M T too large");
+  REQUIRE(P && metrics && (steps || workspace), "null pointer");
+  const size_t need = consistency_given_workspace_bytes(K, M, T, steps != nullptr);
+  if (workspace_bytes < need)
+    return fail(MFG_EWORKSPACE, "backward-equation check workspace: need %lld bytes, have %lld", (long long)need,
+                (long long)workspace_bytes);
+  return consistency_launches(P, K, M, T, d, metrics, steps ? steps : reinterpret_cast<double*>(workspace), V, S(stream));
+}
+
+size_t mfg_consistency_pop_workspace_bytes(int64_t N, int H, int d, int K, int repeats, int steps_given, int actions_given,
+                                           int traj_given) {
+  if (N < 1 || H < 2 || d < 1 || K < 1 || repeats < 1) return 0;
+  return consistency_pop_workspace_bytes(N, H, d, K, repeats, steps_given != 0, actions_given != 0, traj_given != 0);
+}
+
+int mfg_consistency_pop(const float* start32, int64_t N, int H, int d, int K, const double* theta, const double* shift,
+                        const double* alpha_scale, const uint64_t* seed, uint32_t first_step, int repeats, int precision,
+                        double* metrics, double* steps, double* V, float* actions, float* pi_traj, void* workspace,
+                        size_t workspace_bytes, mfg_stream_t stream) {
+  REQUIRE(K >= 1 && K <= MFG_POP_MAX_K, "population size K outside [1, MFG_POP_MAX_K]");
+  REQUIRE(d >= 1, "d < 1");
+  if (d > WAVE) return fail(MFG_EUNSUPPORTED, "backward-equation check: d=%d > 64 (as for the populations)", d);
+  REQUIRE(H >= 2, "hours H < 2");
+  REQUIRE(N >= 1, "no start states (N < 1)");
+  REQUIRE(repeats >= 1, "repeats < 1");
+  REQUIRE(N * (int64_t)H <= 0x7FFFFFFF && N * (int64_t)repeats <= 0x7FFFFFFF &&
+              N * (int64_t)repeats * (H - 1) <= 0x7FFFFFFF,
+          "N H or N repeats (H - 1) too large");
+  REQUIRE(start32 && theta && shift && alpha_scale && seed && metrics && workspace, "null pointer");
+  CHECK_PRECISION();
+  REQUIRE((uint64_t)first_step + (uint64_t)(H - 1) <= 0xFFFFFFFFull, "Philox step counter would wrap");
+  const size_t need = consistency_pop_workspace_bytes(N, H, d, K, repeats, steps != nullptr, actions != nullptr, pi_traj != nullptr);
+  if (workspace_bytes < need)
+    return fail(MFG_EWORKSPACE, "backward-equation check workspace: need %lld bytes, have %lld", (long long)need,
+                (long long)workspace_bytes);
+  const int64_t NR = N * repeats;
+  const int T = H - 1;
+  PopArgs p = pop_args(K, NR, d, T, 0, seed, shift, alpha_scale, nullptr, nullptr, 0);
+  p.N = N;
+  p.L = 1;  // (member j starts at row j mod N of start32 [N, d], as in a forecast)
+  p.s_idx = eval_pop_idx_stride(NR);
+  p.idx = reinterpret_cast<int32_t*>(workspace);
+  p.s_P = NR * T * d * d;
+  char* at = reinterpret_cast<char*>(workspace) + (size_t)K * p.s_idx * 4;
+  double* per_step = steps;
+  if (!per_step) {
+    per_step = reinterpret_cast<double*>(at);
+    at += consistency_given_workspace_bytes(K, NR, T, false);
+  }
+  float* traj = pi_traj;
+  if (!traj) {
+    traj = reinterpret_cast<float*>(at);
+    at += ((size_t)K * NR * H * d * 4 + 7) / 8 * 8;
+  }
+  float* acts = actions ? actions : reinterpret_cast<float*>(at);
+  CoreArgs a{};
+  a.pi0 = start32;
+  a.num_start = N;
+  a.theta = theta;
+  a.gamma = 1.0;
+  a.B = NR;
+  a.d = d;
+  a.T = T;
+  a.reward_kind = MFG_REWARD_EXTERNAL;  // (states and actions only: no reward is formed)
+  a.first_step = first_step;
+  a.pi_traj = traj;
+  a.P_out = acts;
+  if (const int rc = launch_core(a, true, false, precision, S(stream), &p); rc != MFG_OK) return rc;
+  return consistency_launches(acts, K, NR, T, d, metrics, per_step, V, S(stream));
 }
 
 // ---- IRL forward learners (AC_IRL.train): the reward comes from the reward network, launched between the core kernel and the

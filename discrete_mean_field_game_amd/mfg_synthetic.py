@@ -19,6 +19,97 @@ from . import ops
 from .mfg_ac2 import _with_ctx, actor_critic as _base
 
 
+SWEEP_HEADER = 'Shift,theta_initial,theta_final,diff_mean,diff_std\n'   # mfg_synthetic.py:905
+SWEEP_FMT = '%.3f,%.3f,%.3f,%.3f,%.3f\n'                                 # :925
+SWEEP_FAILED = 900.0                                                     # diff_mean / diff_std of the `except` branch, :922-923
+
+
+def sweep_points(shift_range, theta_range):
+    """The sweep's points (shift, theta_initial) in the reference's loop order: shift outermost, theta innermost (:907-908)."""
+    return [(float(shift), float(theta)) for shift in shift_range for theta in theta_range]
+
+
+def sweep_table(points, theta_final, diff_mean, diff_std, failed):
+    """The [K, 5] table (shift, theta_initial, theta_final, diff_mean, diff_std) of a sweep; a learner marked in `failed`
+    gets the reference's 900, 900 (:919-923)."""
+    table = np.empty((len(points), 5))
+    table[:, 0:2] = np.asarray(points, dtype=np.float64).reshape(-1, 2)
+    table[:, 2] = theta_final
+    bad = np.asarray(failed, dtype=bool)
+    table[:, 3] = np.where(bad, SWEEP_FAILED, diff_mean)
+    table[:, 4] = np.where(bad, SWEEP_FAILED, diff_std)
+    return table
+
+
+def write_sweep_rows(outfile, table):
+    """Append the header and one line per point, as the reference's __main__ writes them (:904-905, :924-925)."""
+    with open(outfile, 'a') as f:
+        f.write(SWEEP_HEADER)
+        for row in table:
+            f.write(SWEEP_FMT % tuple(row))
+
+
+def resolve_start_table(d, pi0=None, path_to_dir=None):
+    """The start-state table [num_start, d] (fp64) in the order actor_critic (below) resolves it: `pi0`; else `path_to_dir`
+    or cwd/train_normalized with the `_reordered` file names; else what the base class falls back to."""
+    from .population import resolve_start_table as base_table
+    if pi0 is not None:
+        return base_table(d, pi0)
+    if path_to_dir is None and os.path.isdir(os.getcwd() + '/train_normalized'):
+        path_to_dir = os.getcwd() + '/train_normalized'
+    if path_to_dir is not None:
+        holder = type('_Table', (), {})()
+        holder.d = int(d)
+        actor_critic.init_pi0(holder, path_to_dir)
+        return holder.mat_pi0
+    return base_table(d)
+
+
+def check_sweep_args(metric, num_start, day_first, day_last, repeats):
+    """The argument rules of sweep that need no GPU (ValueError): metric 'l1' or 'jsd', the days inside the start table,
+    repeats >= 1."""
+    from .population import check_synthetic_eval
+    if metric not in ('l1', 'jsd'):
+        raise ValueError("metric must be 'jsd' (evaluate_synthetic_JSD, the reference's sweep) or 'l1' (evaluate_synthetic)")
+    return check_synthetic_eval('synthetic', num_start, day_first, day_last, repeats)
+
+
+def sweep(shift_range=np.arange(0, 0.04, 0.02), theta_range=np.arange(0, 5.0, 0.05), *, batch, alpha_scale=10000, d=21,
+          num_episodes=1000, gamma=1, constant=1, lr_critic=0.1, lr_actor=0.001, update_every='step', metric='jsd', day_first=1,
+          day_last=26, repeats=1, seed=0, eval_seed=0, pi0=None, path_to_dir=None, precision='mixed', outfile='synthetic.csv',
+          device=None):
+    """The reference's __main__ (mfg_synthetic.py:902-925) as one population: a learner per (shift, theta_initial) point, in
+    its loop order, learner k with seed `seed + k` and critic weights from np.random as actor_critic draws them;
+    train(num_episodes, isolate=True) for the reference's `try: train ... except: pass`; then ONE population.consistency
+    call at `eval_seed` over the start rows day_first .. day_last -- every point is scored on the same noise -- and the CSV
+    lines of :904-925 appended to `outfile`.  A learner that failed in training gets 900, 900.  Returns the [K, 5] table
+    (shift, theta_initial, theta_final, diff_mean, diff_std)."""
+    from . import population
+    points = sweep_points(shift_range, theta_range)
+    if not points:
+        raise ValueError('an empty sweep: no (shift, theta) points')
+    table_pi0 = resolve_start_table(d, pi0, path_to_dir)
+    day_first, day_last, repeats = check_sweep_args(metric, table_pi0.shape[0], day_first, day_last, repeats)
+    K = len(points)
+    par = np.asarray(points, dtype=np.float64).reshape(K, 2)
+    pop = population.ActorCriticPopulation(par[:, 1], par[:, 0], alpha_scale, d, batch=batch, seeds=int(seed) + np.arange(K),
+                                           pi0=table_pi0, update_every=update_every, reward='synthetic', precision=precision,
+                                           device=device)
+    pop.train(num_episodes, gamma=gamma, constant=constant, lr_critic=lr_critic, lr_actor=lr_actor, isolate=True)
+    theta_final = pop.thetas
+    failed = pop.learner_state == population.FAILED
+    live = np.flatnonzero(~failed)
+    mean, std = np.full(K, np.nan), np.full(K, np.nan)
+    if live.size:
+        res = population.consistency(theta_final[live], par[live, 0], alpha_scale, table_pi0[day_first - 1:day_last], d=d,
+                                     seed=eval_seed, hours=population.SYNTHETIC_HOURS, repeats=repeats, precision=precision,
+                                     device=pop.device)
+        mean[live], std[live] = (res.jsd_mean, res.jsd_std) if metric == 'jsd' else (res.l1_mean, res.l1_std)
+    table = sweep_table(points, theta_final, mean, std, failed)
+    write_sweep_rows(outfile, table)
+    return table
+
+
 class actor_critic(_base):
 
     def __init__(self, theta=10, shift=0, alpha_scale=100, d=21, **kw):

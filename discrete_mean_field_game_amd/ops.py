@@ -1031,6 +1031,93 @@ def forecast_pop(start32, thetas, shifts, alpha_scales, seeds, horizon, first_st
     return out
 
 
+def consistency_given(P, want_steps=True, want_V=True):
+    """The backward-equation check of K groups of given actions in two launches (mfg_consistency_given; evaluate_synthetic /
+    evaluate_synthetic_JSD, mfg_synthetic.py:741-899): P [K,M,T,d,d] fp32.  Returns a dict of device fp64 tensors: metrics
+    [K,4] = (l1_mean, l1_std, jsd_mean, jsd_std) over each group's M T hours (std: ddof = 0); steps [K,M,T,2] (l1, jsd per
+    hour) and V [K,M,T+1,d], each None unless asked for."""
+    _chk_f32(P, 'P')
+    if P.dim() != 5 or P.shape[3] != P.shape[4]:
+        raise ValueError('P: expected [K, M, T, d, d], got %s' % (tuple(P.shape),))
+    K, M, T, d, _ = P.shape
+    if min(K, M, T, d) < 1:
+        raise ValueError('P: an empty dimension in %s' % (tuple(P.shape),))
+    dev = P.device
+    out = {'metrics': torch.empty(K, 4, dtype=torch.float64, device=dev),
+           'steps': torch.empty(K, M, T, 2, dtype=torch.float64, device=dev) if want_steps else None,
+           'V': torch.empty(K, M, T + 1, d, dtype=torch.float64, device=dev) if want_V else None}
+    nbytes = int(L.lib().mfg_consistency_given_workspace_bytes(K, M, T, int(bool(want_steps))))
+    ws = torch.empty(max(nbytes // 8, 1), dtype=torch.float64, device=dev)
+    L.check(L.lib().mfg_consistency_given(P.data_ptr(), K, M, T, d, out['metrics'].data_ptr(), _ptr(out['steps']), _ptr(out['V']),
+                                          ws.data_ptr(), ws.numel() * ws.element_size(), _stream()), 'mfg_consistency_given')
+    return out
+
+
+def consistency_pop_workspace_bytes(N, hours, d, K, repeats, steps_given=False, actions_given=False, traj_given=False):
+    """mfg_consistency_pop_workspace_bytes: the scratch bytes of one consistency_pop call (needs the library, not a GPU)."""
+    return int(L.lib().mfg_consistency_pop_workspace_bytes(int(N), int(hours), int(d), int(K), int(repeats), int(bool(steps_given)),
+                                                           int(bool(actions_given)), int(bool(traj_given))))
+
+
+def check_consistency_args(start_shape, hours, repeats, precision, K=1, first_step=0):
+    """The argument rules of consistency_pop that need no GPU (ValueError): start32 [N, d] with N >= 1 and 1 <= d <= 64,
+    hours >= 2, repeats >= 1, 1 <= K <= POP_MAX_K, a known precision, a Philox step first_step + hours - 1 below 2^32.
+    Returns (N, d, hours, repeats)."""
+    if len(start_shape) != 2:
+        raise ValueError('start32: expected [N, d], got %s' % (tuple(start_shape),))
+    N, d = int(start_shape[0]), int(start_shape[1])
+    hours, repeats, K, first_step = int(hours), int(repeats), int(K), int(first_step)
+    if N < 1:
+        raise ValueError('start32: no start rows')
+    if not 1 <= d <= 64:
+        raise ValueError('d=%d: the backward-equation check covers 1 <= d <= 64 (as the populations do)' % d)
+    if hours < 2:
+        raise ValueError('hours=%d: the check needs at least one action matrix (hours >= 2)' % hours)
+    if repeats < 1:
+        raise ValueError('repeats=%d: at least one rollout per start row' % repeats)
+    if not 1 <= K <= L.POP_MAX_K:
+        raise ValueError('K=%d policies: between 1 and %d per call (MFG_POP_MAX_K)' % (K, L.POP_MAX_K))
+    if precision not in L.PRECISIONS:
+        raise ValueError("precision must be 'mixed' or 'f64'")
+    if first_step < 0 or first_step + hours - 1 > 0xFFFFFFFF:
+        raise ValueError('first_step=%d: the Philox step counter would wrap within %d hours' % (first_step, hours))
+    return N, d, hours, repeats
+
+
+def consistency_pop(start32, thetas, shifts, alpha_scales, seeds, hours, *, first_step=0, repeats=1, precision='mixed',
+                    want_steps=False, want_V=False, want_actions=False, want_traj=False, ws=None):
+    """The backward-equation check of K policies in three launches (mfg_consistency_pop): start32 [N,d] the start rows; thetas,
+    shifts, alpha_scales fp64 and seeds int64 (read as uint64) device arrays [K].  Learner k's member j (0 <= j < N repeats)
+    starts at start32[j mod N] under Philox (seeds[k], first_step + t, j) and has `hours` rows, i.e. hours - 1 action matrices:
+    generate_trajectory over the repeats-fold tiled start rows.  Returns a dict of device tensors: metrics [K,4] fp64 (l1_mean,
+    l1_std, jsd_mean, jsd_std over the policy's N repeats (hours - 1) values, ddof = 0) and, each None unless asked for, steps
+    [K, N repeats, hours-1, 2] fp64, V [K, N repeats, hours, d] fp64, actions [K, N repeats, hours-1, d, d] fp32 and traj
+    [K, N repeats, hours, d] fp32."""
+    _chk_f32(start32, 'start32')
+    K = thetas.numel()
+    N, d, H, repeats = check_consistency_args(start32.shape, hours, repeats, precision, K, first_step)
+    _chk_pop(K, 'thetas', thetas, torch.float64)
+    for name, t in (('shifts', shifts), ('alpha_scales', alpha_scales)):
+        _chk_pop(K, name, t, torch.float64)
+    _chk_pop(K, 'seeds', seeds, torch.int64)
+    dev = start32.device
+    NR, T = N * repeats, H - 1
+    out = {'metrics': torch.empty(K, 4, dtype=torch.float64, device=dev),
+           'steps': torch.empty(K, NR, T, 2, dtype=torch.float64, device=dev) if want_steps else None,
+           'V': torch.empty(K, NR, H, d, dtype=torch.float64, device=dev) if want_V else None,
+           'actions': torch.empty(K, NR, T, d, d, dtype=torch.float32, device=dev) if want_actions else None,
+           'traj': torch.empty(K, NR, H, d, dtype=torch.float32, device=dev) if want_traj else None}
+    if ws is None:
+        nbytes = consistency_pop_workspace_bytes(N, H, d, K, repeats, want_steps, want_actions, want_traj)
+        ws = torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=dev)
+    L.check(L.lib().mfg_consistency_pop(start32.data_ptr(), N, H, d, K, thetas.data_ptr(), shifts.data_ptr(),
+                                        alpha_scales.data_ptr(), seeds.data_ptr(), int(first_step), repeats,
+                                        L.PRECISIONS[precision], out['metrics'].data_ptr(), _ptr(out['steps']), _ptr(out['V']),
+                                        _ptr(out['actions']), _ptr(out['traj']), ws.data_ptr(), ws.numel() * ws.element_size(),
+                                        _stream()), 'mfg_consistency_pop')
+    return out
+
+
 def policy_logpdf(pi, P, thetas, shift, alpha_scale=1.0, alpha_floor=0.0, p_floor=0.0):
     """log q_k(P_n | pi_n) [N,K] of the product-Dirichlet policy under K thetas (ac_irl.py:270-289, :324-379)."""
     _chk_f32(pi, 'pi'); _chk_f32(P, 'P'); _chk_f64(thetas, 'thetas')

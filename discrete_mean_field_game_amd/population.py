@@ -457,6 +457,125 @@ def forecast(thetas, shifts, alpha_scales, pi0, horizon, *, d, seed=0, repeats=2
     return Forecast(cat('mean'), cat('std'), cat('quant'), probs, ranks, cat('curves'), repeats, cat('traj'))
 
 
+# --------------------------------------------------------------------------------------------- backward-equation check
+# The scoring half of the reference's synthetic sweep (evaluate_synthetic / evaluate_synthetic_JSD, mfg_synthetic.py:741-899,
+# once per learner in its __main__, :902-925) for K policies at once: one mfg_consistency_pop call rolls every policy from
+# every start row, runs the backward recursion over the actions and reduces both metrics on the device.
+CONSISTENCY_BUDGET = 1 << 30    # workspace bytes of one consistency_pop call of consistency() (more policies go in chunks)
+SYNTHETIC_HOURS = 16            # rows per trajectory of evaluate_synthetic (mfg_synthetic.py:759, :838)
+
+
+def consistency_chunks(K, bytes_per_policy, budget=None):
+    """[(first, count), ...]: the K policies in order, in chunks whose workspace (count x bytes_per_policy, an upper bound of
+    mfg_consistency_pop_workspace_bytes at that count) stays within `budget` (None: CONSISTENCY_BUDGET), at most POP_MAX_K per chunk.  ValueError when
+    one policy alone exceeds the budget.  Needs no GPU."""
+    K, per, budget = int(K), int(bytes_per_policy), int(CONSISTENCY_BUDGET if budget is None else budget)
+    if K < 1:
+        raise ValueError('no policies')
+    if per < 1:
+        raise ValueError('bytes_per_policy=%d' % per)
+    if per > budget:
+        raise ValueError('one policy needs %d bytes of workspace, the budget is %d: fewer start rows, repeats or hours'
+                         % (per, budget))
+    n = min(budget // per, L.POP_MAX_K)
+    return [(c0, min(n, K - c0)) for c0 in range(0, K, n)]
+
+
+class Consistency:
+    """The result of a backward-equation check (NumPy): l1_mean, l1_std, jsd_mean, jsd_std, each [K] -- mean and std (ddof = 0)
+    over the policy's N R (hours - 1) values of sum_ij |P_ij - value_ij| and of sum_i JSD(P_i, implied row i); steps
+    [K, N R, hours - 1, 2] (l1, jsd per trajectory and hour) when asked for, else None."""
+
+    def __init__(self, metrics, steps=None):
+        self.metrics = metrics
+        self.l1_mean, self.l1_std, self.jsd_mean, self.jsd_std = (metrics[:, q].copy() for q in range(4))
+        self.steps = steps
+
+
+def consistency_policies(start, thetas, shifts, alpha_scales, seeds, hours, first_step, repeats, precision, device, ctx,
+                         want_steps=False):
+    """One ops.consistency_pop call as NumPy arrays (metrics [K, 4], steps or None): `start` [N, d] fp64 rows; `thetas`,
+    `shifts`, `alpha_scales` fp64 and `seeds` int64 device tensors [K].  MfgError when a mixed-precision policy left the fp32
+    range (ctx: the bound context whose status word the launch reports into)."""
+    start32 = torch.as_tensor(np.ascontiguousarray(start, dtype=np.float32), device=device)
+    out = ops.consistency_pop(start32, thetas, shifts, alpha_scales, seeds, hours, first_step=first_step, repeats=repeats,
+                              precision=precision, want_steps=want_steps)
+    metrics = out['metrics'].cpu().numpy()
+    steps = out['steps'].cpu().numpy() if want_steps else None
+    if precision == 'mixed' and ctx.status(synchronize=True):
+        raise L.MfgError('a mixed-precision backward-equation check ran a policy with |theta| (1 + |shift|) > 86 (or theta not '
+                         'finite): its metrics are NaN; use precision=\'f64\'')
+    return metrics, steps
+
+
+def _consistency_start(pi0, d):
+    """The start rows [N, d] fp64 of a backward-equation check from `pi0` ((d,) or [N, >= d]).  ValueError otherwise."""
+    d = int(d)
+    if not 1 <= d <= 64:
+        raise ValueError('d=%d: the backward-equation check covers d <= 64 (as the populations do)' % d)
+    if pi0 is None:
+        raise ValueError('a backward-equation check needs start rows (pi0)')
+    start = np.asarray(pi0, dtype=np.float64)
+    if start.ndim == 1:
+        start = start[None]
+    if start.ndim != 2 or start.shape[0] < 1 or start.shape[1] < d:
+        raise ValueError('pi0: expected (d,) or [N, d] with d >= %d, got %s' % (d, start.shape))
+    return np.ascontiguousarray(start[:, :d])
+
+
+def consistency(thetas, shifts, alpha_scales, pi0, *, d, seed=0, hours=SYNTHETIC_HOURS, repeats=1, precision='mixed', device=None,
+                first_step=0, want_steps=False):
+    """The backward-equation check of K policies (thetas, shifts, alpha_scales: scalars or K values) from the start rows `pi0`
+    ((d,) or [N, d]): `repeats` rollouts of `hours` rows per start row and policy, V^n = r^n + P^n V^{n+1} over their actions
+    and the two consistency metrics, reduced on the device.  Every policy uses the same seed and the Philox steps first_step ..
+    first_step + hours - 2: common random numbers, and with first_step = 0 policy k's actions are those a fresh
+    mfg_synthetic.actor_critic(theta_k, shift_k, alpha_k, d, seed=seed, pi0=...) returns from generate_trajectory over the
+    repeats-fold tiled start rows.  (seed may also be K values, one per policy.)  Policies go in chunks whose workspace stays
+    within CONSISTENCY_BUDGET (consistency_chunks).  Returns a Consistency.  Runs on a context of its own: a diverged
+    mixed-precision policy raises MfgError and leaves the caller's status word alone."""
+    th = np.asarray(thetas, dtype=np.float64).reshape(-1)
+    K = th.shape[0]
+    if K < 1:
+        raise ValueError('no policies')
+    sh, al = broadcast('shifts', shifts, K), broadcast('alpha_scales', alpha_scales, K)
+    sd = broadcast('seed', seed, K, np.uint64).view(np.int64)
+    start = _consistency_start(pi0, d)
+    N, d, H, R = ops.check_consistency_args(start.shape, hours, repeats, precision, 1, first_step)
+    if not torch.cuda.is_available():
+        raise L.MfgError('consistency needs a ROCm GPU: the HIP hot path has no CPU fallback')
+    L.lib()
+    ops.init()
+    chunks = consistency_chunks(K, ops.consistency_pop_workspace_bytes(N, H, d, 1, R, want_steps, False, False))
+    dev = torch.device(device) if device is not None else torch.device('cuda', torch.cuda.current_device())
+    ctx = ops.Context(dev)
+    prev = ctx.bind_scoped()
+    try:
+        parts = []
+        for c0, n in chunks:
+            f = lambda a: torch.as_tensor(a[c0:c0 + n].copy(), device=dev)
+            parts.append(consistency_policies(start, f(th), f(sh), f(al), f(sd), H, int(first_step), R, precision, dev, ctx,
+                                              want_steps))
+    finally:
+        ctx.restore(prev)
+        ctx.close()
+    return Consistency(np.concatenate([p[0] for p in parts]), np.concatenate([p[1] for p in parts]) if want_steps else None)
+
+
+def check_synthetic_eval(reward, num_start, day_first, day_last, repeats=1):
+    """The argument rules of evaluate_synthetic / evaluate_synthetic_JSD of a population (ValueError; no GPU needed): the
+    synthetic reward, start rows day_first .. day_last inside the table of `num_start` rows, repeats >= 1.  Returns (day_first,
+    day_last, repeats) as ints."""
+    if reward != 'synthetic':
+        raise ValueError("evaluate_synthetic checks the backward equation of the synthetic reward: the population has "
+                         "reward=%r" % (reward,))
+    day_first, day_last, repeats = int(day_first), int(day_last), int(repeats)
+    if not 1 <= day_first <= day_last <= int(num_start):
+        raise ValueError('days %d .. %d outside the start table\'s rows 1 .. %d' % (day_first, day_last, num_start))
+    if repeats < 1:
+        raise ValueError('repeats=%d: at least one rollout per start row' % repeats)
+    return day_first, day_last, repeats
+
+
 class _Population:
     """What ActorCriticPopulation and AC_IRLPopulation share: the K learners' theta, w, shifts, alpha_scales and seeds (host
     and device copies), the start-state table, the Philox step counter and the instance's own ops.Context.  Subclasses say
@@ -773,6 +892,43 @@ class ActorCriticPopulation(_Population):
         learner(k).evaluate(thetas[k], shifts[k], alpha_scales[k], d, episode_length, ...) gives; repeats = R rolls R
         trajectories per test file.  MfgError (and no CSV line) when a mixed-precision policy left the fp32 range."""
         return self._evaluate(episode_length, indir, outfile, write_header, repeats)
+
+    @_with_ctx
+    def _evaluate_synthetic(self, day_first, day_last, repeats, column):
+        """The body of evaluate_synthetic (column 0: l1) / evaluate_synthetic_JSD (column 2: jsd)."""
+        start = self.mat_pi0[day_first - 1:day_last]
+        first_step = self._rng_step
+        self._rng_step += SYNTHETIC_HOURS - 1        # (a diverged launch has run: its step is spent, as in train())
+        live = self._healthy()                       # failed learners are not launched: NaN
+        sub = (lambda t: t) if len(live) == self.K else (lambda t: t[torch.as_tensor(live, device=self.device)].contiguous())
+        table = np.full((self.K, 4), np.nan)
+        try:
+            if live:
+                table[live] = consistency_policies(start, sub(self._theta), sub(self._shifts_dev), sub(self._alphas_dev),
+                                                   sub(self._seeds_dev), SYNTHETIC_HOURS, first_step, repeats, self.precision,
+                                                   self.device, self._ctx)[0]
+        except L.MfgError as e:
+            if e.code:                               # refused by the library before anything was launched
+                self._rng_step = first_step
+            raise
+        return table[:, column].copy(), table[:, column + 1].copy()
+
+    def evaluate_synthetic(self, day_first=1, day_last=26, *, repeats=1):
+        """mfg_synthetic.actor_critic.evaluate_synthetic (mfg_synthetic.py:741-812) for every learner's current policy in one
+        consistency_pop call: (mean [K], std [K]) over (start row, hour) of sum_ij |P_ij - value_ij|.  Start rows
+        mat_pi0[day_first-1:day_last]; learner k rolls with its own seed from the population's Philox step, which advances by
+        15 as each learner's own call would (restored when the library refuses the call).  With repeats=1 learner k gets what
+        learner(k).evaluate_synthetic(day_first, day_last) gives up to the summation order; repeats = R rolls R trajectories
+        per start row.  Failed learners are not launched: NaN.  ValueError for a population whose reward is not 'synthetic' or
+        days outside the table; MfgError when a mixed-precision policy left the fp32 range."""
+        day_first, day_last, repeats = check_synthetic_eval(self.reward, self.mat_pi0.shape[0], day_first, day_last, repeats)
+        return self._evaluate_synthetic(day_first, day_last, repeats, 0)
+
+    def evaluate_synthetic_JSD(self, day_first=1, day_last=26, *, repeats=1):
+        """evaluate_synthetic with the reference's second metric (mfg_synthetic.py:815-899): (mean [K], std [K]) over (start
+        row, hour) of sum_i JSD(P_i, value-implied row i)."""
+        day_first, day_last, repeats = check_synthetic_eval(self.reward, self.mat_pi0.shape[0], day_first, day_last, repeats)
+        return self._evaluate_synthetic(day_first, day_last, repeats, 2)
 
     def _new_learner(self, k):
         return actor_critic(float(self.thetas[k]), float(self.shifts[k]), float(self.alpha_scales[k]), self.d,

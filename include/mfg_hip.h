@@ -567,6 +567,42 @@ int mfg_forecast_pop(const float* start32, int64_t N, int H, int d, int K, const
                      const int32_t* ranks, int Q, const float* emp32, const double* emp64, double* mean, double* std, float* quant,
                      double* curves, float* pi_traj, void* workspace, size_t workspace_bytes, mfg_stream_t stream);
 
+/* Backward-equation check of K groups of trajectories, reduced on the device: the scoring of the reference's synthetic sweep
+ * (evaluate_synthetic / evaluate_synthetic_JSD, mfg_synthetic.py:741-899, called once per learner by its __main__, :902-925).
+ * mfg_consistency_given, TWO launches on given actions:
+ *   P [K,M,T,d,d] fp32: K groups of M trajectories of T row-stochastic action matrices.
+ *   launch 1: per trajectory the reverse-time scan V^n = r^n + P^n V^{n+1}, r^n_i = -1/2 ||P^n_i||^2, V^T = 0 (:768-774), and
+ *   per hour n  l1 = sum_ij |P_ij - value_ij| (:776-790)  and  jsd = sum_i JSD(P_i, implied row i) (:858-880), where implied
+ *   row i is V^n_j - V^n_i off the diagonal and 1 - (sum_j V^n_j - d V^n_i) on it; in the JSD every entry <= 0 of either
+ *   argument counts as 1e-100 and P, Q and M are renormalised (mfg_backward_value's formulas).  fp64 throughout, in an order
+ *   that depends on (d, T) only.
+ *   launch 2: metrics [K,4] fp64 = (l1_mean, l1_std, jsd_mean, jsd_std): mean and std (ddof = 0, np.mean / np.std at :800-801,
+ *   :887-888) over the group's M T values, two passes in a fixed order.  No floating-point atomics: group k's outputs depend
+ *   on group k's inputs only.
+ *   steps [K,M,T,2] fp64 (l1, jsd per hour) or NULL (then they stay in the workspace); V [K,M,T+1,d] fp64 or NULL (then V is
+ *   not written to memory at all).
+ *   workspace: mfg_consistency_given_workspace_bytes(K, M, T, steps != NULL) bytes (0 with steps: NULL is then allowed).
+ * mfg_consistency_pop, THREE launches, no host synchronisation: the actions are those of K policies' rollouts.
+ *   start32 [N,d], theta / shift / alpha_scale [K] fp64, seed [K] uint64, first_step, repeats R, precision: as for
+ *   mfg_forecast_pop -- learner k's member j (0 <= j < N R) starts at start32[j mod N] and is keyed by Philox (seed[k],
+ *   first_step + t, j): the actions and states of mfg_rollout over the R-fold tiled start rows (generate_trajectory,
+ *   mfg_ac2.py:566-592).  H >= 2 hours per member, T = H - 1 action matrices; M = N R.
+ *   metrics, steps, V: as above.  actions [K, N R, T, d, d] fp32 or NULL, pi_traj [K, N R, H, d] fp32 or NULL (then in the
+ *   workspace).  workspace: mfg_consistency_pop_workspace_bytes(N, H, d, K, repeats, steps != NULL, actions != NULL,
+ *   pi_traj != NULL) bytes; contents are scratch.
+ * Checked before anything is launched: no null pointer, 1 <= K <= MFG_POP_MAX_K, H >= 2 (T >= 1), N, M, repeats >= 1, the
+ * Philox step counter does not wrap (MFG_EINVAL); d <= 64 (MFG_EUNSUPPORTED); the workspace (MFG_EWORKSPACE).  Mixed precision
+ * reports into and is refused on the bound context's status word exactly as mfg_evaluate_pop. */
+size_t mfg_consistency_given_workspace_bytes(int K, int64_t M, int T, int steps_given);
+int mfg_consistency_given(const float* P, int K, int64_t M, int T, int d, double* metrics, double* steps, double* V,
+                          void* workspace, size_t workspace_bytes, mfg_stream_t stream);
+size_t mfg_consistency_pop_workspace_bytes(int64_t N, int H, int d, int K, int repeats, int steps_given, int actions_given,
+                                           int traj_given);
+int mfg_consistency_pop(const float* start32, int64_t N, int H, int d, int K, const double* theta, const double* shift,
+                        const double* alpha_scale, const uint64_t* seed, uint32_t first_step, int repeats, int precision,
+                        double* metrics, double* steps, double* V, float* actions, float* pi_traj, void* workspace,
+                        size_t workspace_bytes, mfg_stream_t stream);
+
 /* Weights of the reward network of networks.py:46-81 as device pointers (layouts as for mfg_reward_net_forward). */
 typedef struct mfg_reward_net {
   int k1, f2, k2, n3, n4;
