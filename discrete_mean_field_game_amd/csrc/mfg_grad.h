@@ -157,7 +157,14 @@ struct GradChunk {
 };
 
 // n0 = first sample of the chunk (wave uniform); (b0, s0) = its trajectory / step.  Sample n0 + j sits at trajectory
-// b0 + (s0 + j) / T, step (s0 + j) % T: small integers, so the division is an fp32 multiply (exact below 2^22).
+// b0 + (s0 + j) / T, step (s0 + j) % T: small integers, so the division is an fp32 multiply.  The multiply is exact for every
+// T < 2^22 and puts step T - 1 behind the boundary from T = 6 556 022 on (oracle/grad_index_ref.py restates it,
+// tests/test_grad_index_host.py checks every T): the host sends T >= 2^22 to the WIDE form, which counts the boundaries of a
+// long trajectory with a compare -- for T >= 64 a chunk of 64 samples crosses at most one.
+constexpr int MFG_GRAD_LONG_T = 1 << 22;
+__device__ __forceinline__ int grad_boundaries_wide(int sj, int T, float invT) {
+  return T >= GS_CH ? (int)(sj >= T) : (int)(((float)sj + 0.5f) * invT);
+}
 template <int D, bool WIDE>
 __device__ __forceinline__ void grad_chunk_load(GradChunk<D>& c, const GradArgs& a, const double* gp, const float* rp, int d,
                                                 int64_t n0, int64_t b0, int s0, int lane, float invT, float inv_d) {
@@ -172,8 +179,8 @@ __device__ __forceinline__ void grad_chunk_load(GradChunk<D>& c, const GradArgs&
   // (stride_b - T d floats, the T+1-th state of pi_traj): element e of the block sits at  base + e + q extra,  q = number of
   // trajectory boundaries in front of its sample -- 32-bit arithmetic on a wave-uniform 64-bit base (the (b, s) form cost
   // two 64-bit multiplies and three 64-bit shifts-and-adds per load: 330 of the kernel's 790 VALU instructions per chunk,
-  // and f64 VALU work does not overlap the f64 matrix instructions).  Wide strides (WIDE, chosen by the host: skipped part
-  // >= 2^23 floats) keep the general form.
+  // and f64 VALU work does not overlap the f64 matrix instructions).  Wide strides and long trajectories (WIDE, chosen by the
+  // host: skipped part >= 2^23 floats, or T >= MFG_GRAD_LONG_T) keep the general form.
   if constexpr (!WIDE) {
     const float* cb = a.pi + b0 * a.stride_b + (int64_t)s0 * d;
     const int extra = (int)(a.stride_b - (int64_t)a.T * d);
@@ -201,8 +208,8 @@ __device__ __forceinline__ void grad_chunk_load(GradChunk<D>& c, const GradArgs&
       int col = e - j * d;
       if (j > last) { j = last; col = 0; }
       const int sj = s0 + j;
-      const int q = (int)(((float)sj + 0.5f) * invT);
-      const int64_t off = (b0 + q) * a.stride_b + (int64_t)((sj - q * a.T) * d + col);
+      const int q = grad_boundaries_wide(sj, a.T, invT);
+      const int64_t off = (b0 + q) * a.stride_b + ((int64_t)(sj - q * a.T) * d + col);  // (T d need not fit 32 bits)
       c.pi[k] = a.pi[off];
     }
   }

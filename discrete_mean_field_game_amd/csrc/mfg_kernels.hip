@@ -9,6 +9,7 @@
 //   large d (d > 64): one wavefront per trajectory, lanes own columns, rows are streamed from HBM
 //       with coalesced loads; per-row quantities use wavefront reductions.
 #include <hip/hip_runtime.h>
+#include <limits.h>
 #include <stdarg.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -1648,6 +1649,10 @@ static int launch_grad(const float* pi, int64_t stride_b, const double* delta, c
                        const ApplyArgs* apply = nullptr, bool* applied = nullptr, bool add_reward = false,
                        const PopArgs* pop = nullptr) {
   if (applied) *applied = false;
+  // FIRST, before anything can be launched: the d <= 28 kernel keeps a chunk's step counter s0 + j (s0 < T, j < 64) in a
+  // 32-bit int (tests/test_gpu_batch_sums_layouts.py calls with such a T over buffers that hold nothing)
+  if (d <= MFG_GRAD_SMALL_MAX_D && T > INT_MAX - GS_CH)
+    return fail(MFG_EUNSUPPORTED, "batch sums, d <= %d: T = %d above 2^31 - 65", MFG_GRAD_SMALL_MAX_D, T);
   const int64_t FO = mfg_num_features(d) + 3;
   int chunk, nob;
   int64_t nsb;
@@ -1711,9 +1716,10 @@ static int launch_grad(const float* pi, int64_t stride_b, const double* delta, c
         if (applied) *applied = true;
       }
     }
-    const bool wide = stride_b - (int64_t)T * d >= (1 << 23);  // floats skipped between trajectories: 32-bit offsets inside a chunk?
-    if (pop) {  // (population: K learners side by side; `wide` never holds for the strides of a training episode)
-      if (wide) return fail(MFG_EUNSUPPORTED, "%s", "population: trajectory stride beyond the small gradient kernel");
+    // 32-bit offsets and the fp32 step division inside a chunk: skipped part below 2^23 floats, T below 2^22
+    const bool wide = stride_b - (int64_t)T * d >= (1 << 23) || T >= MFG_GRAD_LONG_T;
+    if (pop) {  // (population: K learners side by side; `wide` never holds for the strides and lengths of a training episode)
+      if (wide) return fail(MFG_EUNSUPPORTED, "%s", "population: trajectory stride or length beyond the small gradient kernel");
       launch_grad_mfma_small_pop(d == 21 || d == 15 ? d : 0, (unsigned)blocks, a, *pop, st);
       if (fuse) return check_launch("grad_mfma_small_pop");
       launch_reduce_partials_pop((unsigned)((FO + RP_OUT - 1) / RP_OUT), (const double*)a.partial, blocks, FO, G, rap, *pop, st);

@@ -419,7 +419,11 @@ int mfg_backward_value(const float* P, int64_t B, int T, int d, double* V, doubl
  * n = (b, s), pi_n = pi + b*stride_b + s*d (stride_b = (T+1)*d for a pi_traj, d for a plain [B,d] batch).
  * add_reward != 0: first delta_n <- delta_n + reward_n, written back -- the IRL step, where the rollout
  * (reward_kind = MFG_REWARD_EXTERNAL) leaves delta = gamma V(pi') - V(pi) and the reward network (ac_irl.py:683)
- * runs in between (:691).  Workspace as for mfg_td_pg_accumulate(B*T). */
+ * runs in between (:691).  Workspace as for mfg_td_pg_accumulate(B*T).
+ * Any stride_b >= T*d and any alignment of pi are served (float4 staging at d >= 64 needs a 16-byte aligned pi and
+ * stride_b % 4 == 0; otherwise the scalar staging path runs, same sums).  d <= 28: a skipped part stride_b - T*d of 2^23
+ * floats or more, or T >= 2^22, takes the kernel's 64-bit address form (slower, same sums); T <= 2^31 - 65, a longer
+ * trajectory is refused with MFG_EUNSUPPORTED (mfg_grad_apply and the batch sums of mfg_rollout likewise). */
 int mfg_grad_accumulate(const float* pi, int64_t stride_b, double* delta, const double* g, const float* reward, int64_t B,
                         int T, int d, int add_reward, double* G, int accumulate, void* workspace, size_t workspace_bytes,
                         mfg_stream_t stream);
@@ -467,7 +471,10 @@ int mfg_train_episodes(const float* mat_pi0, int64_t num_start, float* pi_io, fl
  *   workspace_bytes: ONE learner's slice, a multiple of 256 (the buffer holds K slices back to back).
  * Checked before anything is launched: 1 <= K <= MFG_POP_MAX_K, no null pointer, d <= 64 (MFG_EUNSUPPORTED beyond: one wave
  * per trajectory fills the machine there), an in-kernel reward_kind, the Philox step counter does not wrap (MFG_EINVAL);
- * the slice holds the update's partial rows (MFG_EWORKSPACE).  The sticky mixed-range status word (mfg_status) is per
+ * the slice holds the update's partial rows (MFG_EWORKSPACE).  Rollout mode, d <= 28: the population form of the batch sums
+ * has the 32-bit address form only (mfg_grad_accumulate), so an episode of T >= 2^22 steps is refused with MFG_EUNSUPPORTED --
+ * by the update, i.e. after the episode's rollout has been enqueued (mfg_train_rollouts_pop, mfg_train_rollouts_irl_pop).
+ * The sticky mixed-range status word (mfg_status) is per
  * device / context: one learner whose policy left the fp32 range blocks the population's next mixed-precision launch --
  * unless the bound context carries a population control block (mfg_ctx_set_pop_control), which books the condition to that
  * learner alone, retires it at the next episode boundary and lets the others run on. */

@@ -359,6 +359,89 @@ def test_matrix_core_values_equal_in_kernel_values(dev, d, B, T):
     assert np.max(np.abs(a['delta'].cpu().numpy() - want)) <= 1e-11 * np.max(np.abs(V))
 
 
+def _value_terms(x, w, d):
+    """V = x^T U x + b.x + c of the states x [n, d] for the packed weights w (fp64, NumPy), and the same form on magnitudes."""
+    Q = d * (d + 1) // 2
+    iu = np.triu_indices(d)
+    out = []
+    for xx, ww in ((x, w), (np.abs(x), np.abs(w))):
+        U = np.zeros((d, d))
+        U[iu] = ww[:Q]
+        out.append(((xx @ U) * xx).sum(1) + xx @ ww[Q:Q + d] + ww[Q + d])
+    return out[0], out[1]
+
+
+def _check_signed_values(dev, d, B, T, oracle_values):
+    """Deferred (matrix-core) TD errors against the in-kernel ones and against an fp64 reference, critic weights of both signs.
+    A value is a sum of n = d(d+1)/2 + d + 1 products: a priori |V - V_ref| <= n u (|x|^T |U| |x| + |b|.|x| + |c|) = n u Vmag,
+    u = 2^-53, so |delta - delta_ref| <= n u (gd Vmag' + Vmag) + 3 u (|r| + gd |V'| + |V|) + 2^-24 |r| (the last term: the fp32
+    reward hand-over documented in tests/test_gpu_score_regimes.py).  Returns the worst error / bound of both comparisons and
+    the worst cross-path error relative to 1e-12 max|delta|."""
+    from discrete_mean_field_game_amd import _lib as L
+    o = ops()
+    u = 2.0 ** -53
+    pi0 = start_states(B, d, dev, seed=4)
+    theta = torch.tensor([THETA], dtype=torch.float64, device=dev)
+    w = torch.as_tensor(np.random.RandomState(2 + d).randn(o.num_features(d)), device=dev)
+    nterm = o.num_features(d)
+    worst_cross = worst_ref = worst_12 = 0.0
+    for dpow in (False, True):
+        a = o.rollout(pi0, T, theta, SHIFT, SCALE, w=w, gamma=0.9, seed=3, td=True, discount_pow=dpow)           # deferred
+        b = o.rollout(pi0, T, theta, SHIFT, SCALE, w=w, gamma=0.9, seed=3, td=True, discount_pow=dpow,
+                      reward_kind=L.REWARD_EXTERNAL)                                                               # in-kernel
+        torch.cuda.synchronize()
+        assert torch.equal(a['pi_traj'], b['pi_traj']) and torch.equal(a['g'], b['g'])
+        x = a['pi_traj'].cpu().numpy().astype(np.float64).reshape(-1, d)
+        V, Vmag = _value_terms(x, w.cpu().numpy(), d)
+        if oracle_values:
+            V = O().calc_value(x, w.cpu().numpy())
+        V, Vmag = V.reshape(B, T + 1), Vmag.reshape(B, T + 1)
+        r = a['reward'].cpu().numpy().astype(np.float64)
+        gd = (0.9 ** np.arange(T) if dpow else np.full(T, 0.9))[None, :]
+        ref = r + gd * V[:, 1:] - V[:, :-1]
+        bound = (nterm * u * (gd * Vmag[:, 1:] + Vmag[:, :-1]) + 3 * u * (np.abs(r) + gd * np.abs(V[:, 1:]) + np.abs(V[:, :-1]))
+                 + 2.0 ** -24 * np.abs(r))
+        da = a['delta'].cpu().numpy()
+        db = b['delta'].cpu().numpy() + r
+        worst_cross = max(worst_cross, float(np.max(np.abs(da - db) / bound)))
+        worst_ref = max(worst_ref, float(np.max(np.abs(da - ref) / bound)), float(np.max(np.abs(db - ref) / bound)))
+        worst_12 = max(worst_12, float(np.max(np.abs(da - db)) / (1e-12 * np.max(np.abs(db)))))
+    print('values d = %d, %d states: error / a-priori bound %.3g (deferred vs in-kernel) %.3g (vs fp64 reference); '
+          'deferred vs in-kernel / (1e-12 max|delta|) %.3g' % (d, B * (T + 1), worst_cross, worst_ref, worst_12))
+    assert worst_cross <= 1.0 and worst_ref <= 1.0
+    assert worst_12 <= 1.0
+    return worst_cross, worst_ref, worst_12
+
+
+@pytest.mark.parametrize('B,T', [(1, 16), (43, 2)])
+@pytest.mark.parametrize('d', list(range(80, 513, 16)))
+def test_matrix_core_values_every_tile_count_signed_weights(dev, d, B, T):
+    """k_value_mfma at every multiple of 16 from 80 to 512 and k_value_mfma2 at every multiple of 64 (2 .. 8 pieces of 64, the 5, 6
+    and 7 of d = 320, 384, 448 among them), with w = randn: with weights of both signs the terms of a value cancel, which
+    w = rand >= 0 of test_matrix_core_values_equal_in_kernel_values cannot show.  17 states (one trajectory of 16 steps: one
+    16-state tile and one state) and 129 (one past a 128-state block, ragged against 16-state tiles).  Criteria: the a-priori
+    bound of _check_signed_values against the in-kernel delta and against the oracle, and the 1e-12 cross-path criterion of
+    the unsigned test."""
+    _check_signed_values(dev, d, B, T, oracle_values=True)
+
+
+@pytest.mark.parametrize('d', [80, 128])
+def test_matrix_core_values_several_passes_per_block(dev, d):
+    """More states than one pass of the launch holds -- k_value_mfma: 8 blocks per CU x 64 states, k_value_mfma2: 2 blocks per CU
+    x 128 states -- so the first blocks take a second, ragged pass (T = 2; the CU count from mfg_device_info)."""
+    import ctypes as C
+    from discrete_mean_field_game_amd import _lib as L
+    cu = C.c_int(0)
+    L.check(L.lib().mfg_device_info(C.byref(cu), None, 0), 'mfg_device_info')
+    one_pass = cu.value * (8 * 64 if d == 80 else 2 * 128)
+    T = 2
+    B = one_pass // (T + 1) + 30
+    while (B * (T + 1)) % 16 == 0:
+        B += 1
+    assert one_pass < B * (T + 1) < 2 * one_pass
+    _check_signed_values(dev, d, B, T, oracle_values=False)
+
+
 @pytest.mark.parametrize('d,B', [(21, 96000 + 7), (21, 192000 + 5), (21, 384000 + 50), (21, 983040), (15, 128000 + 1), (15, 512000 + 3)])
 def test_given_P_batched_store_kernel_equals_per_tile_kernel(dev, d, B):
     """Large batches take k_step_wave_batched (KB consecutive tiles per wave, outputs parked in LDS and written as one
