@@ -153,7 +153,8 @@ int launch_core_small(const CoreArgs& a, bool sample, bool td, bool fast, int nu
 // per matrix row (mfg_core_row3.hip).  core_row3_wanted: whether launch_core_small hands a launch of this shape to it.
 bool core_row3_wanted(const CoreArgs& a, bool sample, bool td, bool fast, int num_cus);
 int launch_core_row3(const CoreArgs& a, bool td, int num_cus, hipStream_t st);
-int core_mapping_set(int mode);  // 0 by batch size, 1 packed, 2 one trajectory per wave; returns the previous mode
+int core_mapping_set(int mode);  // 0 by batch size, 1 packed, 2 one trajectory per wave, 3 packed and never k_core_small_lean; returns the previous mode
+int core_mapping_get();
 int launch_core_large_f64(const CoreArgs& a, bool sample, bool td, int num_cus, hipStream_t st);
 int launch_core_large_mixed(const CoreArgs& a, bool sample, bool td, int num_cus, hipStream_t st);
 
@@ -533,11 +534,24 @@ __device__ __forceinline__ double value_wave(const float* pis, const double* __r
 // waves per SIMD (the three-wave cap spills 31 registers here); used while all tiles are resident at that occupancy.
 // STEP: 0 plain; 1 IRL env step with the previous step's partial rows (CoreArgs::step_rows); 2 an IRL episode's FIRST env step
 // (nothing to reduce; the start states are also written to pi_start_out)
-template <bool SAMPLE, bool TD, bool FAST, int D, bool SUMS = false, int STEP = 0>
+// LEAN (the training call's instantiation, k_core_small_lean below; mixed-precision sampling with TD at compile-time d): the
+// options a training rollout never varies are constants -- no P copy-out, the in-kernel mfg_ac2 reward, a constant bootstrap
+// factor, and pi_traj / reward_out / delta / g / w all present -- so their argument pointers are not kept (or reloaded from spilled
+// scalar registers) across the step loop and the per-step tests on them go.  The arithmetic is the general instantiation's, expression
+// by expression: the same bits (tests/test_gpu_core_lean.py).  The start mode, the deferred update, pi_next_out and the status word
+// stay run-time arguments.  core_lean_ok (below) is the launch-side statement of the same conditions.
+template <bool SAMPLE, bool TD, bool FAST, int D, bool SUMS = false, int STEP = 0, bool LEAN = false>
 #ifndef MFG_CORE_SMALL_WAVES_F64
 #define MFG_CORE_SMALL_WAVES_F64 3  // strict precision: 227 registers wanted; at 168 the third wave still pays (5.95 -> 5.80 ms at the bench shape)
 #endif
 __device__ __forceinline__ void core_small_body(const CoreArgs& a) {
+  static_assert(!LEAN || (SAMPLE && TD && FAST && D > 0 && !SUMS && STEP == 0), "LEAN: the training rollout only");
+#ifndef MFG_LEAN_ADDR
+#define MFG_LEAN_ADDR 0  // developer switch (A/B timing), LEAN only: 1 = the outputs of a tile through one scalar base per array and a
+                         // 32-bit lane offset instead of a 64-bit address per lane and array (151 instead of 157 VGPRs at d = 21).  Same
+                         // bits; 0.2-0.8 % per step, inside the spread of the runs: not kept (docs/HISTORY.md, profiles/lean_ab_d21.txt)
+#endif
+  constexpr bool LADDR = LEAN && MFG_LEAN_ADDR != 0;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   MFG_STAMP0(8)
   MFG_STAMPB(0)
@@ -545,7 +559,7 @@ __device__ __forceinline__ void core_small_body(const CoreArgs& a) {
   const int dd = d * d, dp = d | 1, T = a.T;
   const int G = WAVE / d, TB = WAVES * G;
   const int Q = d * (d + 1) / 2, F = Q + d + 1;
-  const bool want_v = TD && a.w != nullptr;
+  const bool want_v = TD && (LEAN || a.w != nullptr);
   // Value function: V = sum_{i<=k} U_ik pi_i pi_k + b.pi + c.  Lane (t, i) owns the terms of "its" entry i:
   //   generic: column i of the upper triangle, k <= i  -- 1 .. d terms per lane, the wave waits for the longest;
   //   CIRC (compile-time odd d, the reference's 21 and 15): the unordered pairs {i, i+m mod d}, m = 0 .. (d-1)/2 --
@@ -713,7 +727,16 @@ __device__ __forceinline__ void core_small_body(const CoreArgs& a) {
         pi_first = a.pi0[core_src_row(a, bn) * d + i];
       }
     }
-    if (valid && a.pi_traj) a.pi_traj[b * (int64_t)(T + 1) * d + i] = pi_i;
+    // (LADDR: bases of this tile's rows in the output arrays -- wave-uniform -- and the lane's offsets into them)
+    float* const trj_t = LADDR ? a.pi_traj + b0 * (int64_t)(T + 1) * d : nullptr;
+    float* const rew_t = LADDR ? a.reward_out + b0 * T : nullptr;
+    double* const del_t = LADDR ? a.delta + b0 * T : nullptr;
+    double* const g_t = LADDR ? a.g + b0 * T : nullptr;
+    const uint32_t trj_o = (uint32_t)(tlc * (T + 1) * d + i), out_o = (uint32_t)(tlc * T);
+    if constexpr (LADDR) {
+      if (valid) trj_t[trj_o] = pi_i;
+    } else
+    if (valid && (LEAN || a.pi_traj)) a.pi_traj[b * (int64_t)(T + 1) * d + i] = pi_i;
     if constexpr (STEP == 2) {
       if (valid && a.pi_start_out) a.pi_start_out[b * d + i] = pi_i;
     }
@@ -875,7 +898,7 @@ __device__ __forceinline__ void core_small_body(const CoreArgs& a) {
           float* inv_slot = reinterpret_cast<float*>(pis64 + 2 * (tlc * d + i) + 1);
           if (FAST) {
             const float inv32 = fast_rcp_f32_of_f64(Ssum);
-            if (a.P_out) {
+            if (!LEAN && a.P_out) {
               for (int j = 0; j < d; ++j) trow[j] *= inv32;
               *inv_slot = 1.0f;
             } else {
@@ -975,14 +998,14 @@ __device__ __forceinline__ void core_small_body(const CoreArgs& a) {
           s2 = fma(u, u, s2);
 #endif
         }
-        if (a.reward_kind == MFG_REWARD_MFG_AC2) rcol = fma(pid, s1, -s2);
-        if (a.reward_kind == MFG_REWARD_SYNTHETIC) rcol = s1;
+        if (LEAN || a.reward_kind == MFG_REWARD_MFG_AC2) rcol = fma(pid, s1, -s2);
+        if (!LEAN && a.reward_kind == MFG_REWARD_SYNTHETIC) rcol = s1;
         pi_n = (float)acc;
         if (valid) {
           pnv[i] = pi_n;
           if (CIRC) pnv[d + i] = pi_n;
         }
-        if (a.P_out && wv * G < nb) {
+        if (!LEAN && a.P_out && wv * G < nb) {
           // copy-out of THIS WAVE's trajectories into [B,T,d,d] (coalesced: a trajectory's matrix is contiguous on both
           // sides when the LDS tile is unpadded).  Wave local on purpose: the rows were written by this wave's own lanes, so
           // no block barrier is needed and the per-step barriers stay wave-local also when P is materialised (round 2
@@ -1034,7 +1057,7 @@ __device__ __forceinline__ void core_small_body(const CoreArgs& a) {
       // Per-trajectory sums of the lane terms (reward, score, value): every lane parks its terms in an LDS line, lane 0
       // of the trajectory adds up reward and value, lane 1 the score -- two LDS round trips per step instead of the six
       // dependent cross-lane exchanges (ds_bpermute) of a shuffle tree per quantity, in a fixed order.
-      const bool ext = a.reward_kind == MFG_REWARD_EXTERNAL;
+      const bool ext = !LEAN && a.reward_kind == MFG_REWARD_EXTERNAL;
       if (valid) {
         if (!ext) redq[i] = rcol;
         if (TD) redq[d + i] = gacc;
@@ -1070,7 +1093,7 @@ __device__ __forceinline__ void core_small_body(const CoreArgs& a) {
       if (par) {
         if (valid && i < 8) {
           const int q = i >> 1, pp = i & 1;
-          const bool need = q == 0 ? !ext : (q == 1 ? want_v : (q == 2 ? (TD && a.g != nullptr) : (SAMPLE && want_v && s == 0)));
+          const bool need = q == 0 ? !ext : (q == 1 ? want_v : (q == 2 ? (TD && (LEAN || a.g != nullptr)) : (SAMPLE && want_v && s == 0)));
           double x = 0.0;
           if (need) {
             const double* src = redq + (q == 0 ? 0 : (q == 1 ? 2 * d : (q == 2 ? d : 3 * d)));
@@ -1107,8 +1130,10 @@ __device__ __forceinline__ void core_small_body(const CoreArgs& a) {
           if (k < d) r0 += redq[k];
         }
         double r = r0 + r1;
-        if (a.reward_kind == MFG_REWARD_SYNTHETIC) r *= -0.5;
-        if (a.reward_out) a.reward_out[b * T + s] = (float)r;
+        if (!LEAN && a.reward_kind == MFG_REWARD_SYNTHETIC) r *= -0.5;
+        if constexpr (LADDR) rew_t[out_o + (uint32_t)s] = (float)r;
+        else
+        if (LEAN || a.reward_out) a.reward_out[b * T + s] = (float)r;
         if (want_v) {
           if (par) {
             v0 = totq[2];
@@ -1139,9 +1164,11 @@ __device__ __forceinline__ void core_small_body(const CoreArgs& a) {
             }
             v_cur = (u0 + u1) + wl[Q + d];
           }
-          const double gd = a.discount_pow ? discount : a.gamma;
+          const double gd = (!LEAN && a.discount_pow) ? discount : a.gamma;
           const double del = r + gd * v_next - v_cur;
-          if (a.delta) a.delta[b * T + s] = del;
+          if constexpr (LADDR) del_t[out_o + (uint32_t)s] = del;
+          else
+          if (LEAN || a.delta) a.delta[b * T + s] = del;
           if (SUMS) {
             scal[tlc * 3] = del;
             scal[tlc * 3 + 2] = (double)(float)r;  // the reward as the caller sees it (fp32 output)
@@ -1153,7 +1180,7 @@ __device__ __forceinline__ void core_small_body(const CoreArgs& a) {
 #ifdef MFG_ABL_TSUM
       if (false) {
 #else
-      if (TD && valid && i == gl && a.g) {
+      if (TD && valid && i == gl && (LEAN || a.g)) {
 #endif
         double g0 = 0.0, g1 = 0.0;
         if (par) {
@@ -1168,10 +1195,15 @@ __device__ __forceinline__ void core_small_body(const CoreArgs& a) {
           }
           if (k < d) g0 += redq[d + k];
         }
+        if constexpr (LADDR) g_t[out_o + (uint32_t)s] = g0 + g1;
+        else
         a.g[b * T + s] = g0 + g1;
         if (SUMS) scal[tlc * 3 + 1] = g0 + g1;
       }
-      if (valid && a.pi_traj) a.pi_traj[(b * (int64_t)(T + 1) + s + 1) * d + i] = pi_n;
+      if constexpr (LADDR) {
+        if (valid) trj_t[trj_o + (uint32_t)((s + 1) * d)] = pi_n;
+      } else
+      if (valid && (LEAN || a.pi_traj)) a.pi_traj[(b * (int64_t)(T + 1) + s + 1) * d + i] = pi_n;
       pi_i = pi_n;
       MFG_STAMP(5)
     }
@@ -1245,6 +1277,17 @@ __device__ __forceinline__ void core_small_body(const CoreArgs& a) {
 }
 template <bool SAMPLE, bool TD, bool FAST, int D, bool SUMS = false, int STEP = 0>
 __global__ __launch_bounds__(BLOCK, SUMS ? 2 : (FAST ? MFG_CORE_SMALL_WAVES : MFG_CORE_SMALL_WAVES_F64)) void k_core_small(CoreArgs a) { core_small_body<SAMPLE, TD, FAST, D, SUMS, STEP>(a); }
+// The training call's instantiation (LEAN above), a kernel of its own name: k_core_small<SAMPLE, TD, MIXED, D> keeps its symbol and
+// its code, so a build is compared with its parent kernel by kernel (tools/kernel_isa_diff.py).
+template <int D>
+__global__ __launch_bounds__(BLOCK, MFG_CORE_SMALL_WAVES) void k_core_small_lean(CoreArgs a) { core_small_body<true, true, true, D, false, 0, true>(a); }
+// Whether a packed-kernel launch is the one LEAN is compiled for (the caller has already settled sample / td / mixed precision and a
+// compile-time d): every condition the flag turned into a constant, checked on the arguments.
+inline bool core_lean_ok(const CoreArgs& a) {
+  return a.step_nrows == 0 && !a.part_rows && !a.P_out && !a.reward_in && a.reward_kind == MFG_REWARD_MFG_AC2 && !a.pi_alpha &&
+         !a.pi_next_in && !a.discount_pow && a.pi_traj && a.reward_out && a.delta && a.g && a.w &&
+         (!MFG_LEAN_ADDR || a.T < (1 << 20));  // (the variant's 32-bit lane offsets: a tile's rows of pi_traj stay below 2^31 floats)
+}
 
 inline size_t core_small_lds(int d, bool want_v, bool sample) {
   const int G = WAVE / d, TB = WAVES * G, dp = d | 1;

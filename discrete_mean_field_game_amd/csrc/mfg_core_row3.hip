@@ -486,9 +486,11 @@ __global__ __launch_bounds__(BLOCK, MFG_ROW3_WAVES) void k_core_row3(CoreArgs a)
 }
 
 // lane mapping of the d = 21 sampling launches (mfg_set_core_mapping, include/mfg_hip.h): 0 by batch size, 1 always the packed
-// kernel, 2 the one-trajectory-per-wave kernel wherever it supports the launch.  A measurement / test hook: both give the same bits.
+// kernel, 2 the one-trajectory-per-wave kernel wherever it supports the launch, 3 the packed kernel in its general instantiation
+// (never k_core_small_lean, mfg_core_small.hip).  A measurement / test hook: all give the same bits.
 static std::atomic<int> g_core_mapping{0};
-int core_mapping_set(int mode) { return g_core_mapping.exchange(mode < 0 || mode > 2 ? 0 : mode); }
+int core_mapping_set(int mode) { return g_core_mapping.exchange(mode < 0 || mode > 3 ? 0 : mode); }
+int core_mapping_get() { return g_core_mapping.load(); }
 
 bool core_row3_wanted(const CoreArgs& a, bool sample, bool td, bool fast, int num_cus) {
   // not the per-step SUMS variant (k_core_small<..., SUMS>: batch sums of 12- / 16-trajectory tiles on the matrix cores); the STEP

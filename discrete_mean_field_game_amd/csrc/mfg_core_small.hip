@@ -16,6 +16,13 @@ static void go(const CoreArgs& a, int num_cus, size_t lds, hipStream_t st) {
   hipLaunchKernelGGL((k_core_small<SAMPLE, TD, FAST, D, SUMS, STEP>), dim3(grid + (STEP == 1 ? core_step_red_blocks(a.d * (a.d + 1) / 2 + a.d + 1 + 3) : 0)), dim3(BLOCK), lds, st, a);
 }
 
+// the training call (k_core_small_lean, mfg_core.h): the same grid rule, asked for its own register count
+template <int D>
+static void go_lean(const CoreArgs& a, int num_cus, size_t lds, hipStream_t st) {
+  const int grid = core_small_grid<k_core_small_lean<D>>(a, lds, num_cus);
+  hipLaunchKernelGGL((k_core_small_lean<D>), dim3(grid), dim3(BLOCK), lds, st, a);
+}
+
 template <int D>
 static void dispatch(const CoreArgs& a, bool sample, bool td, bool fast, int num_cus, size_t lds, hipStream_t st) {
   if constexpr (D > 0) {
@@ -34,6 +41,12 @@ static void dispatch(const CoreArgs& a, bool sample, bool td, bool fast, int num
     if (sample && td && a.part_rows) {
       if (fast) go<true, true, true, D, true>(a, num_cus, lds, st);
       else go<true, true, false, D, true>(a, num_cus, lds, st);
+      return;
+    }
+    // a training rollout with nothing optional asked for: the instantiation with those options compiled out (same bits);
+    // every other launch takes the general kernel below (mapping mode 3 forces it: the test hook)
+    if (sample && td && fast && core_lean_ok(a) && core_mapping_get() != 3) {
+      go_lean<D>(a, num_cus, lds, st);
       return;
     }
   }

@@ -82,8 +82,11 @@ int mfg_abi_version(void);
  * wavefront with three / four lanes per matrix row, whose serial chain per wave is 1.65x / 2.2x shorter; the library takes the
  * second where the packed kernel leaves the SIMDs under-occupied (d = 21: <= 16 trajectories per CU = 4 096 on an MI355X;
  * d = 15: <= 16 per CU, <= 12 with MFG_ROLLOUT_WRITE_P, <= 4 for single-step launches -- measured).
- * mode: 0 by batch size (default), 1 always packed, 2 one trajectory per wave wherever it supports the launch.  Process-wide;
- * returns the previous mode.  A measurement / test hook (A/B timing, bit-identity tests): results never depend on it. */
+ * mode: 0 by batch size (default), 1 always packed, 2 one trajectory per wave wherever it supports the launch, 3 always packed and
+ * in the packed kernel's GENERAL instantiation: a training rollout that asks for nothing optional (in-kernel mfg_ac2 reward, all
+ * of pi_traj / reward / delta / g, no actions written out, constant bootstrap factor) otherwise runs an instantiation with those
+ * options compiled out (k_core_small_lean: fewer registers, no scratch, the same bits).  Process-wide; returns the previous mode.
+ * A measurement / test hook (A/B timing, bit-identity tests): results never depend on it. */
 int mfg_set_core_mapping(int mode);
 
 /* One-time per-device setup (fits the 12 KB h(z) = psi(softplus z) sigmoid z table used by the mixed-precision

@@ -143,7 +143,9 @@ def main():
         print('DIFF  %s: %s' % (name, why))
     only_b = sorted(set(isa_b) - set(isa_a))
     for name in only_b:
-        print('new   %s' % name)
+        m = meta_b.get(name, {})
+        print('new   %s (%d instructions, .vgpr_count %s, .sgpr_count %s, .private_segment_fixed_size %s)' % (
+            name, len(isa_b[name]), m.get('.vgpr_count'), m.get('.sgpr_count'), m.get('.private_segment_fixed_size')))
     for sym in args.histogram:
         ha, hb = (collections.Counter(i.split()[0] for i in isa.get(sym, [])) for isa in (isa_a, isa_b))
         print('\nopcode histogram of %s: %d -> %d instructions, .vgpr_count %s -> %s, .private_segment_fixed_size %s -> %s' % (
