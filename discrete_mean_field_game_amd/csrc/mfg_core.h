@@ -118,7 +118,7 @@ __device__ __forceinline__ void reduce_rows_apply_body(const double* __restrict_
   }
 }
 
-int set_error(int code, const char* msg);  // records mfg_last_error() (defined in mfg_kernels.hip)
+int set_error(int code, const char* msg);  // records mfg_last_error(): fail(code, "%s", msg) of mfg_host.h (mfg_kernels.hip)
 
 // IRL env step: reward network + the batch sums of the TD update over the same samples in one launch
 // (mfg_reward_net.hip; used by mfg_train_episode_irl)
@@ -164,7 +164,7 @@ __device__ __forceinline__ int64_t core_src_row(const CoreArgs& a, int64_t b) {
   return a.start_idx ? start_row(a.start_idx[b], a.num_start) : b;
 }
 
-// the start-state draw of k_draw_start (mfg_kernels.hip) and its population form (mfg_population.hip): idx[b] and / or the rows
+// the start-state draw of k_draw_start (mfg_launch_once.hip) and its population form (mfg_population.hip): idx[b] and / or the rows
 __device__ __forceinline__ void draw_start_body(const float* __restrict__ mat, int64_t num_start, int64_t B, int d, uint64_t seed,
                                                 uint32_t step, uint64_t traj_offset, int32_t* __restrict__ idx_out,
                                                 float* __restrict__ out) {
@@ -1211,7 +1211,7 @@ __device__ __forceinline__ void core_small_body(const CoreArgs& a) {
     if constexpr (SUMS && SAMPLE && TD && D > 0) {
       if (a.part_rows) {
         // batch sums of this tile's transitions (T == 1): sample = trajectory, state = pis (the step's start state).
-        // Operand layout and augmented vectors exactly as in k_grad_mfma_small (mfg_kernels.hip).
+        // Operand layout and augmented vectors exactly as in k_grad_mfma_small (mfg_grad.h).
         constexpr int FO = D * (D + 1) / 2 + D + 1 + 3;
         static_assert(WAVES * FO * 8 <= WAVES * (WAVE / D) * D * (D | 1) * 4, "the partial rows reuse the tile region");
         tile_sync();

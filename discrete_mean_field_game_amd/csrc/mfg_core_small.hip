@@ -37,7 +37,7 @@ static void dispatch(const CoreArgs& a, bool sample, bool td, bool fast, int num
       else go<true, true, false, D, false, 2>(a, num_cus, lds, st);
       return;
     }
-    // per-step updates: the variant that also leaves the tile's batch sums (launch_core_sums in mfg_kernels.hip)
+    // per-step updates: the variant that also leaves the tile's batch sums (core_sums_ok / reduce_core_sums in mfg_kernels.hip)
     if (sample && td && a.part_rows) {
       if (fast) go<true, true, true, D, true>(a, num_cus, lds, st);
       else go<true, true, false, D, true>(a, num_cus, lds, st);

@@ -1,6 +1,7 @@
-// Batch sums of the actor-critic update (a6 / a8) and their fixed-order row reduction: the kernels of mfg_kernels.hip that the
-// population launches (mfg_population.hip) run as well.  Each __global__ is a thin shell around a __device__ body, so both
-// translation units run the same code.  MFG_GRAD_BODIES_ONLY: without the non-template kernels (defined in mfg_kernels.hip).
+// Batch sums of the actor-critic update (a6 / a8) and their fixed-order row reduction: the bodies and template kernels of
+// mfg_batch_sums.hip that the population launches (mfg_population.hip, mfg_pop_resident.hip) run as well.  Each __global__ is a
+// thin shell around a __device__ body, so these translation units run the same code.  The non-template shells (k_grad_partial,
+// k_add_reward, k_reduce_partials) are in mfg_batch_sums.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -110,16 +111,6 @@ __device__ __forceinline__ void grad_partial_body(const GradArgs& a) {
     if (kind[u] >= 0) a.partial[(int64_t)blockIdx.x * FO + k] = acc[u];
   }
 }
-#ifndef MFG_GRAD_BODIES_ONLY
-__global__ __launch_bounds__(BLOCK) void k_grad_partial(GradArgs a) { grad_partial_body(a); }
-#endif
-
-#ifndef MFG_GRAD_BODIES_ONLY
-__global__ void k_add_reward(double* __restrict__ delta, const float* __restrict__ reward, int64_t N) {
-  for (int64_t n = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; n < N; n += (int64_t)gridDim.x * blockDim.x)
-    delta[n] += (double)reward[n];
-}
-#endif
 
 // Small d (d <= 28; compile-time for the reference's 21 and 15): ALL the batch sums of an update on the fp64 matrix cores.
 // Per sample n two augmented vectors of length d + 4 <= 32,
@@ -682,7 +673,3 @@ __device__ __forceinline__ void reduce_partials_body(const double* __restrict__ 
     }
   }
 }
-#ifndef MFG_GRAD_BODIES_ONLY
-__global__ __launch_bounds__(RP_SLICES* RP_OUT) void k_reduce_partials(const double* __restrict__ partial, int64_t nsb, int64_t FO,
-                                                                      int accumulate, double* __restrict__ G, ReduceApply ap) { reduce_partials_body(partial, nsb, FO, accumulate, G, ap); }
-#endif

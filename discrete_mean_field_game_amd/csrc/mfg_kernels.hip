@@ -1,13 +1,11 @@
-// HIP kernels + C ABI of the MFG hot path for MI355X (gfx950 / CDNA4, wave64).
+// Host side of the MFG hot path for MI355X (gfx950 / CDNA4, wave64): the C ABI and what its entry points share.
 // See include/mfg_hip.h for the contract and DESIGN.md for the layout / roofline notes.
 //
-// Two work decompositions:
-//   small d (d <= 64): G = 64/d trajectories packed per wavefront; the d x d action matrix of each
-//       trajectory is staged in LDS (per block tile).  HBM-bound step kernel: lane = (trajectory, column j).
-//       Compute-bound sampler / TD kernels: lane = (trajectory, row i) so that all per-row Dirichlet
-//       quantities (row sum of gamma variates, sum_j alpha_ij, ...) stay lane-local.
-//   large d (d > 64): one wavefront per trajectory, lanes own columns, rows are streamed from HBM
-//       with coalesced loads; per-row quantities use wavefront reductions.
+// Here: the error record, the context registry and the status word, the h(z) table, the RCCL loader, launch_core and the
+// training / evaluation drivers with their entry points.  The kernels live with their launch rules in translation units of
+// their own: mfg_core_*.hip (fused rollout), mfg_step.hip (given-P step), mfg_batch_sums.hip (batch sums, critic values),
+// mfg_launch_once.hip (elementwise and evaluation kernels), mfg_population*.hip / mfg_*_pop.hip (population forms),
+// mfg_reward_*.hip (reward network).  mfg_host.h declares what those units use from this one.
 #include <hip/hip_runtime.h>
 #include <limits.h>
 #include <stdarg.h>
@@ -29,38 +27,35 @@
 #include "mfg_consistency_pop.h"
 #include "mfg_irl_population.h"
 #include "mfg_population.h"
+#include "mfg_batch_sums.h"
+#include "mfg_host.h"
+#include "mfg_launch_once.h"
+#include "mfg_step.h"
 
 using namespace mfg;
 
 // ---------------------------------------------------------------------------------------------
-// error plumbing
+// error plumbing (declared in mfg_host.h)
 // ---------------------------------------------------------------------------------------------
 static thread_local char g_err[512] = "";
 
-static int fail(int code, const char* fmt, ...) {
+namespace mfg {
+int fail(int code, const char* fmt, ...) {
   va_list ap;
   va_start(ap, fmt);
   vsnprintf(g_err, sizeof(g_err), fmt, ap);
   va_end(ap);
   return code;
 }
-namespace mfg {
 int set_error(int code, const char* msg) { return fail(code, "%s", msg); }
-}  // namespace mfg
-static int check_launch(const char* what) {
+int check_launch(const char* what) {
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return fail(MFG_ELAUNCH, "%s: %s", what, hipGetErrorString(e));
   return MFG_OK;
 }
-#define REQUIRE(cond, msg) \
-  do {                     \
-    if (!(cond)) return fail(MFG_EINVAL, "%s", msg); \
-  } while (0)
-
-static inline hipStream_t S(mfg_stream_t s) { return (hipStream_t)s; }
 
 // CU count of the CURRENT device (cached per device: one context may drive several GPUs from one process)
-static int num_cus() {
+int num_cus() {
   static std::atomic<int> cus[64];
   int dev = 0;
   if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 256;
@@ -73,1721 +68,14 @@ static int num_cus() {
   return c;
 }
 
-
-// ---------------------------------------------------------------------------------------------
-// trivial kernels: gather, alpha, features, dirichlet_from_gamma, philox_raw, apply_update
-// ---------------------------------------------------------------------------------------------
-__global__ void k_gather_start(const float* __restrict__ mat, int64_t num_start, const int32_t* __restrict__ idx, int64_t B,
-                               int d, float* __restrict__ out) {
-  const int64_t n = B * d;
-  for (int64_t e = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; e < n; e += (int64_t)gridDim.x * blockDim.x) {
-    const int64_t b = e / d;
-    const int j = (int)(e - b * d);
-    out[e] = mat[start_row(idx[b], num_start) * d + j];
-  }
-}
-
-// a9: the start-state draw itself (start_draw_row, mfg_device.h) as a launch of its own: idx[b] and / or the gathered rows
-// (draw_start_body, mfg_core.h)
-__global__ void k_draw_start(const float* __restrict__ mat, int64_t num_start, int64_t B, int d, uint64_t seed, uint32_t step,
-                             uint64_t traj_offset, int32_t* __restrict__ idx_out, float* __restrict__ out) {
-  draw_start_body(mat, num_start, B, d, seed, step, traj_offset, idx_out, out);
-}
-
-__global__ void k_alpha(const float* __restrict__ pi, int64_t B, int d, const double* __restrict__ theta_p,
-                        double shift, double* __restrict__ alpha, double* __restrict__ deriv) {
-  const double theta = *theta_p;
-  const int64_t dd = (int64_t)d * d;
-  const int64_t n = B * dd;
-  for (int64_t e = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; e < n; e += (int64_t)gridDim.x * blockDim.x) {
-    const int64_t b = e / dd;
-    const int r = (int)(e - b * dd);
-    const int i = r / d, j = r - i * d;
-    const double x = (double)pi[b * d + j] - (double)pi[b * d + i] - shift;
-    double sp, sg;
-    softplus_sigmoid(theta * x, sp, sg);
-    if (alpha) alpha[e] = sp;
-    if (deriv) deriv[e] = x * sg;
-  }
-}
-
-__global__ void k_features(const float* __restrict__ pi, int64_t B, int d, double* __restrict__ phi) {
-  const int64_t dd = (int64_t)d * d;
-  const int64_t F = (int64_t)d * (d + 1) / 2 + d + 1;
-  const int64_t Q = (int64_t)d * (d + 1) / 2;
-  const int64_t n = B * dd;
-  for (int64_t e = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; e < n; e += (int64_t)gridDim.x * blockDim.x) {
-    const int64_t b = e / dd;
-    const int r = (int)(e - b * dd);
-    const int i = r / d, j = r - i * d;
-    const double pi_i = (double)pi[b * d + i], pi_j = (double)pi[b * d + j];
-    if (j >= i) phi[b * F + feat_idx(i, j, d)] = pi_i * pi_j;
-    if (i == 0) phi[b * F + Q + j] = pi_j;
-    if (r == 0) phi[b * F + Q + d] = 1.0;
-  }
-}
-
-__global__ void k_dirichlet_from_gamma(const float* __restrict__ y, int64_t rows, int d, float* __restrict__ P) {
-  // one wavefront per row of gamma variates
-  const int lane = threadIdx.x & (WAVE - 1);
-  const int64_t wave = (blockIdx.x * (int64_t)blockDim.x + threadIdx.x) / WAVE;
-  const int64_t nw = (int64_t)gridDim.x * blockDim.x / WAVE;
-  for (int64_t r = wave; r < rows; r += nw) {
-    double s = 0.0;
-    for (int j = lane; j < d; j += WAVE) {
-      float v = y[r * d + j];
-      if (v == 0.0f) v = ZERO_GAMMA_REPLACEMENT;
-      s += (double)v;
-    }
-    s = wave_sum(s);
-    const double inv = 1.0 / s;
-    for (int j = lane; j < d; j += WAVE) {
-      float v = y[r * d + j];
-      if (v == 0.0f) v = ZERO_GAMMA_REPLACEMENT;
-      P[r * d + j] = (float)((double)v * inv);
-    }
-  }
-}
-
-__global__ void k_philox_raw(uint64_t seed, uint32_t first, uint32_t c1, uint32_t c2, uint32_t c3, int64_t n,
-                             uint32_t* __restrict__ out) {
-  for (int64_t e = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; e < n; e += (int64_t)gridDim.x * blockDim.x) {
-    u32x4 c{first + (uint32_t)e, c1, c2, c3};
-    const u32x4 r = philox4x32_10(c, (uint32_t)seed, (uint32_t)(seed >> 32));
-    out[4 * e + 0] = r.x;
-    out[4 * e + 1] = r.y;
-    out[4 * e + 2] = r.z;
-    out[4 * e + 3] = r.w;
-  }
-}
-
-__global__ void k_apply_update(const double* __restrict__ G, int64_t F, double lr_c, double lr_a, double* __restrict__ w,
-                               double* __restrict__ theta, double* __restrict__ reward_acc) {
-  const double count = G[F + 2];
-  if (!(count > 0.0)) return;
-  const double inv = 1.0 / count;
-  if (reward_acc && blockIdx.x == 0 && threadIdx.x == 0) *reward_acc += G[F + 1] * inv;
-  for (int64_t k = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; k < F; k += (int64_t)gridDim.x * blockDim.x)
-    w[k] = updated_param(w[k], lr_c, G[k], inv);
-  if (blockIdx.x == 0 && threadIdx.x == 0) *theta = updated_param(*theta, lr_a, G[F], inv);
-}
-
-// the same update out of place: (w_out, theta_out) = (w_in, theta_in) + lr G / count -- the large-d form of the deferred
-// update of mfg_train_rollout_deferred (at d <= 64 the rollout kernel applies it while staging its weights)
-__global__ void k_apply_update_oop(const double* __restrict__ G, int64_t F, double lr_c, double lr_a, const double* __restrict__ w_in,
-                                   const double* __restrict__ theta_in, double* __restrict__ w_out, double* __restrict__ theta_out,
-                                   double* __restrict__ reward_acc) {
-  const double count = G[F + 2];
-  const bool on = count > 0.0;
-  const double inv = on ? 1.0 / count : 0.0;
-  if (on && reward_acc && blockIdx.x == 0 && threadIdx.x == 0) *reward_acc += G[F + 1] * inv;
-  for (int64_t k = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; k < F; k += (int64_t)gridDim.x * blockDim.x)
-    w_out[k] = on ? updated_param(w_in[k], lr_c, G[k], inv) : w_in[k];
-  if (blockIdx.x == 0 && threadIdx.x == 0) *theta_out = on ? updated_param(*theta_in, lr_a, G[F], inv) : *theta_in;
-}
-
-// ---------------------------------------------------------------------------------------------
-// a11: JSD, one wavefront per pair of rows
-// ---------------------------------------------------------------------------------------------
-__global__ void k_jsd(const float* __restrict__ p, const float* __restrict__ q, int64_t B, int d, double* __restrict__ out) {
-  const int lane = threadIdx.x & (WAVE - 1);
-  const int64_t wave = (blockIdx.x * (int64_t)blockDim.x + threadIdx.x) / WAVE;
-  const int64_t nw = (int64_t)gridDim.x * blockDim.x / WAVE;
-  for (int64_t b = wave; b < B; b += nw) {
-    // zeros -> 1e-100, M = (P+Q)/2 from the un-normalised vectors, entropy() renormalises P, Q and M
-    double sp = 0, sq = 0;
-    for (int j = lane; j < d; j += WAVE) {
-      double a = p[b * d + j], c = q[b * d + j];
-      if (a == 0.0) a = 1e-100;
-      if (c == 0.0) c = 1e-100;
-      sp += a;
-      sq += c;
-    }
-    sp = wave_sum(sp);
-    sq = wave_sum(sq);
-    const double sm = 0.5 * (sp + sq);
-    double acc = 0;
-    for (int j = lane; j < d; j += WAVE) {
-      double a = p[b * d + j], c = q[b * d + j];
-      if (a == 0.0) a = 1e-100;
-      if (c == 0.0) c = 1e-100;
-      const double m = 0.5 * (a + c) / sm;
-      const double pn = a / sp, qn = c / sq;
-      acc += pn * log(pn / m) + qn * log(qn / m);
-    }
-    acc = wave_sum(acc);
-    if (lane == 0) out[b] = 0.5 * acc;
-  }
-}
-
-// ---------------------------------------------------------------------------------------------
-// f1 (importance weights of the max-ent IRL loss, ac_irl.py:270-289 calc_pdf_action / :324-379 calc_z): log-density of
-// the product-Dirichlet policy, one wavefront per (sample n, policy k):
-//   log q_k(P_n | pi_n) = sum_i [ lgamma(sum_j a_ij) - sum_j lgamma(a_ij) + sum_j (a_ij - 1) ln P_ij ],
-//   a_ij = max(alpha_floor, alpha_scale * ln(1 + exp(theta_k (pi_j - pi_i - shift)))).
-// Log space replaces the reference's divide-by-normaliser trick (pdf / c before the products).  fp64 throughout.
-// ---------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(BLOCK) void k_policy_logpdf(const float* __restrict__ pi, const float* __restrict__ P, int64_t N,
-                                                         int d, const double* __restrict__ thetas, int K, double shift,
-                                                         double alpha_scale, double alpha_floor, double p_floor,
-                                                         double* __restrict__ out) {
-  const int lane = threadIdx.x & (WAVE - 1);
-  const int64_t wave = (blockIdx.x * (int64_t)blockDim.x + threadIdx.x) / WAVE;
-  const int64_t nw = (int64_t)gridDim.x * blockDim.x / WAVE;
-  const int dd = d * d;
-  for (int64_t u = wave; u < N * K; u += nw) {
-    const int64_t n = u / K;
-    const int k = (int)(u - n * K);
-    const double th = thetas[k];
-    const float* pn = pi + n * d;
-    const float* Pn = P + n * (int64_t)dd;
-    double acc = 0.0;
-    for (int e = lane; e < dd; e += WAVE) {
-      const int i = e / d, j = e - i * d;
-      double sp, sg;
-      softplus_sigmoid(th * ((double)pn[j] - (double)pn[i] - shift), sp, sg);
-      double al = alpha_scale * sp;
-      if (al < alpha_floor) al = alpha_floor;
-      double pv = (double)Pn[e];
-      if (pv < p_floor) pv = p_floor;
-      acc += (al - 1.0) * log(pv) - lgamma(al);
-    }
-    for (int i = lane; i < d; i += WAVE) {
-      double A = 0.0;
-      for (int j = 0; j < d; ++j) {
-        double sp, sg;
-        softplus_sigmoid(th * ((double)pn[j] - (double)pn[i] - shift), sp, sg);
-        double al = alpha_scale * sp;
-        if (al < alpha_floor) al = alpha_floor;
-        A += al;
-      }
-      acc += lgamma(A);
-    }
-    acc = wave_sum(acc);
-    if (lane == 0) out[u] = acc;
-  }
-}
-
-// ---------------------------------------------------------------------------------------------
-// f3: backward value recursion of mfg_synthetic (mfg_synthetic.py:768-774) and the two consistency metrics
-// of evaluate_synthetic (:776-790, sum_ij |P_ij - value_ij|) / evaluate_synthetic_JSD (:858-880, sum_i JSD(P_i,
-// implied row i) with entries <= 0 -> 1e-100).  One wavefront per trajectory, lane = row i, reverse-time scan
-// with V^{n+1} in LDS.  Evaluation-only: rows are read strided (L2 resident), fp64 throughout.
-// ---------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(BLOCK) void k_backward_value(const float* __restrict__ P, int64_t B, int T, int d,
-                                                          double* __restrict__ V, double* __restrict__ diff_l1,
-                                                          double* __restrict__ diff_jsd) {
-  extern __shared__ __attribute__((aligned(16))) double smd[];
-  const int tid = threadIdx.x, lane = tid & (WAVE - 1), wv = tid / WAVE;
-  double* vn1 = smd + wv * 2 * d;  // V^{n+1}
-  double* vn = vn1 + d;            // V^{n}
-  const int64_t nw = (int64_t)gridDim.x * WAVES;
-  for (int64_t b = (int64_t)blockIdx.x * WAVES + wv; b < B; b += nw) {
-    __builtin_amdgcn_wave_barrier();
-    for (int i = lane; i < d; i += WAVE) {
-      vn1[i] = 0.0;
-      V[(b * (T + 1) + T) * d + i] = 0.0;
-    }
-    __builtin_amdgcn_s_waitcnt(0xc07f);
-    __builtin_amdgcn_wave_barrier();
-    for (int n = T - 1; n >= 0; --n) {
-      const float* Pn = P + (b * T + n) * (int64_t)d * d;
-      double sumV = 0.0;
-      for (int i = lane; i < d; i += WAVE) {
-        const float* row = Pn + (int64_t)i * d;
-        double r2 = 0.0, acc = 0.0;
-        for (int j = 0; j < d; ++j) {
-          const double p = (double)row[j];
-          r2 = fma(p, p, r2);
-          acc = fma(p, vn1[j], acc);
-        }
-        const double v = fma(-0.5, r2, acc);
-        vn[i] = v;
-        V[(b * (T + 1) + n) * d + i] = v;
-        sumV += v;
-      }
-      sumV = wave_sum(sumV);
-      __builtin_amdgcn_s_waitcnt(0xc07f);
-      __builtin_amdgcn_wave_barrier();
-      double l1 = 0.0, js = 0.0;
-      for (int i = lane; i < d; i += WAVE) {
-        const float* row = Pn + (int64_t)i * d;
-        const double vi = vn[i];
-        const double diag = 1.0 - (sumV - (double)d * vi);
-        double sp = 0.0, sq = 0.0;
-        for (int j = 0; j < d; ++j) {
-          const double p = (double)row[j];
-          const double val = (j == i) ? diag : vn[j] - vi;
-          l1 += fabs(p - val);
-          sp += (p <= 0.0) ? 1e-100 : p;
-          sq += (val <= 0.0) ? 1e-100 : val;
-        }
-        if (diff_jsd) {
-          const double sm = 0.5 * (sp + sq);
-          double kl = 0.0;
-          for (int j = 0; j < d; ++j) {
-            double p = (double)row[j];
-            double q = (j == i) ? diag : vn[j] - vi;
-            if (p <= 0.0) p = 1e-100;
-            if (q <= 0.0) q = 1e-100;
-            const double m = 0.5 * (p + q) / sm;
-            const double pn = p / sp, qn = q / sq;
-            kl += pn * log(pn / m) + qn * log(qn / m);
-          }
-          js += 0.5 * kl;
-        }
-      }
-      l1 = wave_sum(l1);
-      if (diff_jsd) js = wave_sum(js);
-      if (lane == 0) {
-        diff_l1[b * T + n] = l1;
-        if (diff_jsd) diff_jsd[b * T + n] = js;
-      }
-      __builtin_amdgcn_wave_barrier();
-      for (int i = lane; i < d; i += WAVE) vn1[i] = vn[i];
-      __builtin_amdgcn_s_waitcnt(0xc07f);
-      __builtin_amdgcn_wave_barrier();
-    }
-  }
-}
-
-// ---------------------------------------------------------------------------------------------
-// a5: V(pi) = phi(pi).w, one wavefront per trajectory, lanes own columns c, rows i <= c.
-// w rows are contiguous in k for fixed i, so the loads are coalesced (L2 resident).
-// ---------------------------------------------------------------------------------------------
-__global__ void k_value(const float* __restrict__ pi, const double* __restrict__ w, int64_t B, int d,
-                        double* __restrict__ out) {
-  const int lane = threadIdx.x & (WAVE - 1);
-  const int64_t wave = (blockIdx.x * (int64_t)blockDim.x + threadIdx.x) / WAVE;
-  const int64_t nw = (int64_t)gridDim.x * blockDim.x / WAVE;
-  for (int64_t b = wave; b < B; b += nw) {
-    const double v = value_wave(pi + b * d, w, d, lane);
-    if (lane == 0) out[b] = v;
-  }
-}
-
-// ---------------------------------------------------------------------------------------------
-// a3+a4, small d: HBM-bound.  Block = 4 waves, tile = 4*G consecutive trajectories whose P slab
-// (contiguous in HBM) is copied flat with 16-byte loads into LDS; lane = (trajectory, column j).
-// Per element the lane does: cvt, p^2, and three fp64 FMAs
-//     pi'_j += p pi_i,   s1_j += pi_i p^2,   s2_j += pi_i^2 p^2        (reward_j = pi_j s1_j - s2_j)
-// with (pi_i, pi_i^2) staged once per tile as fp64 pairs in LDS (one broadcast 16-byte read per row).
-// D > 0: compile-time d (rows unrolled, immediate LDS offsets); D == 0: runtime d.
-// ---------------------------------------------------------------------------------------------
-// The P slab of the NEXT tile is prefetched into registers (PER 16-byte loads per thread, all in flight
-// together) while the current tile is consumed from LDS, so each block keeps ~a tile of HBM traffic in
-// flight at all times (the un-pipelined version spent 83 % of its wave cycles waiting: SQ_WAIT_ANY).
-#ifndef MFG_STEP_UNROLL
-#define MFG_STEP_UNROLL 3
-#endif
-// Streamed-once data: non-temporal loads (measured +5 % on the d=21 kernel, +8..12 % on the row kernels).
-// Depth-2 register prefetch was tried and lost (3.8-4.9 TB/s): the extra 24 VGPRs cost a block per CU.
-typedef float v4f_t __attribute__((ext_vector_type(4)));
-#define MFG_STREAM_LOAD(p) __builtin_nontemporal_load(p)
-#ifndef MFG_STEP_WAVES
-#define MFG_STEP_WAVES 7
-#endif
-template <int KIND, int D, int PER>
-__global__ __launch_bounds__(BLOCK, (PER <= 6 ? MFG_STEP_WAVES : 4)) void k_step_small(const float* __restrict__ pi, const float* __restrict__ P,
-                                                      int64_t B, int d_rt, float* __restrict__ pi_next,
-                                                      float* __restrict__ reward) {
-  extern __shared__ __attribute__((aligned(16))) float smem[];
-  const int d = D ? D : d_rt;
-  const int G = WAVE / d, TB = WAVES * G, dd = d * d;
-  float* tQ = smem;                  // [TB][d] pi (fp32; widened on the fly: VALU is idle here, LDS bytes are not)
-  float* tP = smem + ((TB * d + 3) & ~3);  // [TB][d][d], 16-byte aligned
-  const int tid = threadIdx.x, lane = tid & (WAVE - 1), wv = tid / WAVE;
-  const int t = lane / d, j = lane - t * d;
-  const int p2 = next_pow2(d);
-  const int64_t ntiles = (B + TB - 1) / TB;
-  v4f_t pre[PER];
-  float prepi = 0.0f;
-  // prefetch of tile TT into registers (a macro, not a lambda: capturing pre[] by reference sends it to scratch)
-#define MFG_STEP_PREFETCH(TT)                                                  \
-  {                                                                            \
-    const int64_t pb0 = (TT) * TB;                                             \
-    const int pnb = (int)((B - pb0) < TB ? (B - pb0) : TB);                    \
-    const int pn4 = (pnb * dd) >> 2;                                           \
-    const v4f_t* s4 = reinterpret_cast<const v4f_t*>(P + pb0 * dd);            \
-    _Pragma("unroll") for (int u = 0; u < PER; ++u) {                          \
-      const int k = tid + u * BLOCK;                                           \
-      pre[u] = (k < pn4) ? MFG_STREAM_LOAD(s4 + k) : (v4f_t)(0.0f);            \
-    }                                                                          \
-    prepi = (tid < pnb * d) ? pi[pb0 * d + tid] : 0.0f;                        \
-  }
-  if ((int64_t)blockIdx.x < ntiles) MFG_STEP_PREFETCH((int64_t)blockIdx.x)
-  for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-    const int64_t b0 = tile * TB;
-    const int nb = (int)((B - b0) < TB ? (B - b0) : TB);
-    const int n = nb * dd, n4 = n >> 2;
-    v4f_t* d4 = reinterpret_cast<v4f_t*>(tP);
-#pragma unroll
-    for (int u = 0; u < PER; ++u) {
-      const int k = tid + u * BLOCK;
-      if (k < n4) d4[k] = pre[u];
-    }
-    for (int k = (n4 << 2) + tid; k < n; k += BLOCK) tP[k] = P[b0 * dd + k];  // ragged last tile only
-    if (tid < nb * d) tQ[tid] = prepi;
-    __syncthreads();
-    if (tile + gridDim.x < ntiles) MFG_STEP_PREFETCH(tile + gridDim.x)
-    const int tl = wv * G + t;
-    const bool valid = (t < G) && (tl < nb);
-    const int tlc = valid ? tl : 0;
-    const float* colp = tP + tlc * dd + j;
-    const float* qv = tQ + tlc * d;
-    double acc = 0.0, s1 = 0.0, s2 = 0.0;
-    // rows in groups of col_group_rows(d) (mfg_device.h: three groups of seven at d = 21, the plain row order otherwise)
-    const int dr = D ? D : d, grp = col_group_rows(dr);
-    for (int g0 = 0; g0 < dr; g0 += grp) {
-      double pa = 0.0, p1 = 0.0, p2 = 0.0;
-#pragma unroll MFG_STEP_UNROLL
-      for (int i = g0; i < g0 + grp && i < (D ? D : d); ++i) {
-        const double p = (double)colp[i * d];
-        const double qx = (double)qv[i];
-        // u = pi_i P_ij is exact in fp64 (two fp32 factors), so acc += u equals the fma, and pi_i P_ij^2 = u p,
-        // pi_i^2 P_ij^2 = u^2 are formed inside the fmas with the same single rounding as before: 4 fp64 ops, not 5
-        const double u = p * qx;
-        pa += u;
-        if (KIND != MFG_REWARD_EXTERNAL) {
-          p1 = fma(u, p, p1);
-          if (KIND == MFG_REWARD_MFG_AC2) p2 = fma(u, u, p2);
-        }
-      }
-      acc = g0 ? acc + pa : pa;
-      s1 = g0 ? s1 + p1 : p1;
-      s2 = g0 ? s2 + p2 : p2;
-    }
-    double racc = 0.0;
-    if (KIND == MFG_REWARD_MFG_AC2) racc = fma((double)qv[j], s1, -s2);
-    if (KIND == MFG_REWARD_SYNTHETIC) racc = -0.5 * s1;
-    if (KIND != MFG_REWARD_EXTERNAL) racc = seg_sum(racc, j, d, p2);
-    if (valid) {
-      pi_next[(b0 + tl) * d + j] = (float)acc;
-      if (KIND != MFG_REWARD_EXTERNAL && j == 0) reward[b0 + tl] = (float)racc;
-    }
-    __syncthreads();
-  }
-}
-
-#undef MFG_STEP_PREFETCH
-
-// ---------------------------------------------------------------------------------------------
-// a3+a4, compile-time small d (21, 15), WAVE-PRIVATE tiles: each wavefront stages the contiguous slab of its own
-// G = 64/D trajectories (16-byte loads from the enclosing aligned window, the few bytes of the neighbours that come
-// along are never read back), so there is no block-wide barrier at all -- a wave waits only for its OWN prefetch --
-// and the per-trajectory reward sum goes through the wave's LDS region (dead after its column walk) instead of a
-// shuffle tree.  Same arithmetic and summation order as k_core_small's column pass.
-// ---------------------------------------------------------------------------------------------
-// Prefetch of tile TT (the G trajectories' slab, as 16-byte words of its enclosing aligned window) into pre[] / prepi.
-// MFG_WAVE_PREFETCH: B is a multiple of lcm(G, 4) (the launcher splits off the remainder), so every tile is full and
-// the slab is a whole number of 16-byte words: every word of a window lies inside it, the first PER-1 loads are
-// unconditional and issue back to back; the last one clamps its lane's word index to the window.  (With per-load lane
-// tests, partial register writes or a second code path for partial tiles the compiler serialised the loads with
-// s_waitcnt vmcnt(0), or waited for the prefetch right after issuing it in order to copy the whole pre[] tuple through
-// a phi -- 2x on the low-occupancy batched kernel.)
-#define MFG_WAVE_PREFETCH(TT)                                                             \
-  {                                                                                       \
-    const int64_t f0 = (TT) * (int64_t)(G * DD);                                          \
-    const int pn4 = (int)(((f0 & 3) + (int64_t)(G * DD) + 3) >> 2);                       \
-    const v4f_t* src = P4 + (f0 >> 2);                                                    \
-    _Pragma("unroll") for (int u = 0; u < PER; ++u) {                                     \
-      /* every load unconditional (no phi over pre[]): lanes past the window re-read its last word */ \
-      const int k = lane + u * WAVE;                                                      \
-      pre[u] = MFG_STREAM_LOAD(src + (((u + 1) * WAVE <= ((G * DD) >> 2)) ? k : (k < pn4 ? k : pn4 - 1))); \
-    }                                                                                     \
-    prepi = pi[(TT) * (int64_t)(G * D) + (lane < G * D ? lane : G * D - 1)];              \
-  }
-// MFG_WAVE_PREFETCH_RAG: any B (the tail launch): word addresses clamped to the slab, the 1..3 floats after its last
-// whole word are patched into LDS by MFG_WAVE_TAIL.
-#define MFG_WAVE_PREFETCH_RAG(TT)                                                             \
-  {                                                                                       \
-    const int64_t f0 = (TT) * (int64_t)(G * DD);                                          \
-    const int64_t a4 = f0 >> 2;                                                           \
-    const int png = (int)((B - (TT) * G) < G ? (B - (TT) * G) : G);                       \
-    const int pn4 = (int)(((f0 & 3) + (int64_t)png * DD + 3) >> 2);                       \
-    _Pragma("unroll") for (int u = 0; u < PER; ++u) {                                     \
-      const int k = lane + u * WAVE;                                                      \
-      pre[u] = (v4f_t)(0.0f);                                                             \
-      /* whole words only, address clamped to the slab: no partial register writes, so the PER loads issue back to  \
-         back; the 1..3 floats after the last whole word are patched into LDS by MFG_WAVE_TAIL */                    \
-      if (k < pn4) pre[u] = MFG_STREAM_LOAD(P4 + ((a4 + k) < total4 ? (a4 + k) : total4 - 1));                    \
-    }                                                                                     \
-    prepi = (lane < png * D) ? pi[(TT) * (int64_t)(G * D) + lane] : 0.0f;                 \
-  }
-// The 1..3 floats after the slab's last whole 16-byte word (B d^2 not a multiple of 4) belong to the LAST tile only: its
-// wave copies them into its LDS window after the vector staging (wave-uniform test, off the hot path).
-#define MFG_WAVE_TAIL(TT)                                                                  \
-  if ((TT) == ntiles - 1 && ((B * DD) & 3)) {                                              \
-    const int64_t w0 = total4 << 2;                                                        \
-    if (lane < (int)((B * DD) & 3)) wP[(int)(w0 - ((((TT) * (int64_t)(G * DD)) >> 2) << 2)) + lane] = P[w0 + lane]; \
-  }
-template <int KIND, int D, bool RAG>
-__global__ __launch_bounds__(BLOCK, MFG_STEP_WAVES) void k_step_wave(const float* __restrict__ pi, const float* __restrict__ P,
-                                                                      int64_t B, float* __restrict__ pi_next,
-                                                                      float* __restrict__ reward) {
-  constexpr int G = WAVE / D, DD = D * D;
-  constexpr int WF = ((G * DD + 6 + 3) / 4) * 4;        // floats of a wave's LDS window (16-byte multiple, + alignment slack)
-  constexpr int PER = (WF / 4 + WAVE - 1) / WAVE;       // 16-byte loads per lane per tile
-  __shared__ __attribute__((aligned(16))) float sP[WAVES][WF];
-  __shared__ float sQ[WAVES][G * D];
-  const int tid = threadIdx.x, lane = tid & (WAVE - 1);
-  const int wv = __builtin_amdgcn_readfirstlane(tid / WAVE);  // wave-uniform by construction: keeps the tile bookkeeping scalar
-  const int t = lane / D, j = lane - t * D;
-  float* wP = sP[wv];
-  float* wQ = sQ[wv];
-  const int64_t total4 = (B * DD) >> 2;                 // whole 16-byte words of the slab
-  const int64_t ntiles = (B + G - 1) / G;
-  const int64_t nwaves = (int64_t)gridDim.x * WAVES;
-  v4f_t pre[PER];
-  float prepi = 0.0f;
-  const v4f_t* P4 = reinterpret_cast<const v4f_t*>(P);
-  int64_t tile = (int64_t)blockIdx.x * WAVES + wv;
-  if (tile < ntiles) {
-    if (RAG) MFG_WAVE_PREFETCH_RAG(tile) else MFG_WAVE_PREFETCH(tile)
-  }
-  for (; tile < ntiles; tile += nwaves) {
-    const int ng = (int)((B - tile * G) < G ? (B - tile * G) : G);
-    const int off = (int)((tile * (int64_t)(G * DD)) & 3);   // position of the slab inside its aligned window
-    v4f_t* d4 = reinterpret_cast<v4f_t*>(wP);
-#pragma unroll
-    for (int u = 0; u < PER; ++u) {
-      const int k = lane + u * WAVE;
-      if (k < WF / 4) d4[k] = pre[u];
-    }
-    if (lane < G * D) wQ[lane] = prepi;
-    if (RAG) MFG_WAVE_TAIL(tile)
-    __builtin_amdgcn_s_waitcnt(0xc07f);
-    __builtin_amdgcn_wave_barrier();
-    if (tile + nwaves < ntiles) {
-      if (RAG) MFG_WAVE_PREFETCH_RAG(tile + nwaves) else MFG_WAVE_PREFETCH(tile + nwaves)
-    }
-    const bool valid = (t < G) && (t < ng);
-    const int tc = valid ? t : 0;
-    const float* colp = wP + off + tc * DD + j;
-    const float* qv = wQ + tc * D;
-    double acc = 0.0, s1 = 0.0, s2 = 0.0;
-    // rows in groups of col_group_rows(D) (mfg_device.h: three groups of seven at d = 21; one group = the plain row order at 15):
-    // THE loop of rounds 2-5 with the running sums folded into the totals at the end of a group (all sums start from 0: 0 + u,
-    // fma(u, p, 0) and 0 + P0 are exact -- the bits of col_walk_row)
-    constexpr int GR = col_group_rows(D);
-    double pa = 0.0, p1 = 0.0, p2 = 0.0;
-#ifndef MFG_COLWALK_STEP
-#define MFG_COLWALK_STEP 2  // developer switch: 2 seven rows per unrolled body (static folds), 3 MFG_STEP_UNROLL rows + a uniform test
-#endif
-    constexpr int UN = (MFG_COLWALK_STEP == 2 && GR < D) ? (D == 15 ? 8 : GR) : MFG_STEP_UNROLL;  // a whole number of groups per body
-#pragma unroll UN
-    for (int i = 0; i < D; ++i) {
-      const double p = (double)colp[i * D];
-      const double qx = (double)qv[i];
-      const double u = p * qx;
-      pa += u;
-      if (KIND != MFG_REWARD_EXTERNAL) {
-        p1 = fma(u, p, p1);
-        if (KIND == MFG_REWARD_MFG_AC2) p2 = fma(u, u, p2);
-      }
-      if (GR < D && col_group_end(i, D)) {
-        acc += pa;
-        s1 += p1;
-        s2 += p2;
-        pa = p1 = p2 = 0.0;
-      }
-    }
-    if (GR >= D) {
-      acc = pa;
-      s1 = p1;
-      s2 = p2;
-    }
-    double racc = 0.0;
-    if (KIND == MFG_REWARD_MFG_AC2) racc = fma((double)qv[j], s1, -s2);
-    if (KIND == MFG_REWARD_SYNTHETIC) racc = s1;
-    const int64_t b = tile * G + tc;
-    if (valid) pi_next[b * D + j] = (float)acc;
-    if (KIND != MFG_REWARD_EXTERNAL) {
-      // the wave's tile region is dead now: park the column terms there (8-byte aligned line per trajectory)
-      __builtin_amdgcn_s_waitcnt(0xc07f);
-      __builtin_amdgcn_wave_barrier();
-      double* line = reinterpret_cast<double*>(wP) + tc * (D + 1);
-      if (valid) line[j] = racc;
-      __builtin_amdgcn_s_waitcnt(0xc07f);
-      __builtin_amdgcn_wave_barrier();
-      if (valid && j == 0) {
-        double r0 = 0.0, r1 = 0.0;
-        int k = 0;
-#pragma unroll 4
-        for (; k + 1 < D; k += 2) {
-          r0 += line[k];
-          r1 += line[k + 1];
-        }
-        if (k < D) r0 += line[k];
-        double r = r0 + r1;
-        if (KIND == MFG_REWARD_SYNTHETIC) r *= -0.5;
-        reward[b] = (float)r;
-      }
-      __builtin_amdgcn_s_waitcnt(0xc07f);
-      __builtin_amdgcn_wave_barrier();
-    }
-  }
-}
-
-// ---------------------------------------------------------------------------------------------
-// a3+a4, d = 21 / 15, LARGE batches: k_step_wave with the OUTPUT side rebuilt.  tools/micro/step_lab.hip (round 2) showed
-// that the walk costs 4 % and the 4.5 % of bytes that are written cost 25 %: the same kernel without its stores streams at
-// 6.95 TB/s, with them at 5.5, and with the stores aimed at an L2-resident scratch again at 7.05 -- it is the trickle of
-// small writes reaching HBM in between the reads, not the store instructions.  So here a wave
-//   * takes KB CONSECUTIVE tiles (KB*G trajectories), parks their pi' / rewards in its own LDS stash and writes them out
-//     once per super tile as one contiguous burst of 16-byte stores (KB = 32 at d = 21: 8 KB of pi' per wave),
-//   * issues those stores at device scope (sc1: written through the L2 right away instead of trickling out of it line by
-//     line whenever the cache replaces one),
-//   * and the grid is sized to 8 waves per CU with an equal number of super tiles per wave (the batch costs 42 KB of LDS
-//     per block; more resident waves measured slower with the batched stores, fewer starve the read stream).
-// Same arithmetic, same summation order, bit-identical outputs.  Measured on the 983 040-transition slab: 5.5 -> 6.4 TB/s.
-// A ragged last super tile falls back to per-tile stores.
-// ---------------------------------------------------------------------------------------------
-// Device-scope (sc1) stores through the raw-buffer intrinsics (a plain C++ store cannot carry a scope; inline asm would
-// hide the store from the compiler's hazard / waitcnt bookkeeping).  The base must be wave-uniform.
-typedef unsigned int v4u_t __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t out_rsrc(void* base) {
-  return __builtin_amdgcn_make_buffer_rsrc(base, 0, 0x7fffffff, 0x27000);  // raw buffer, 32-bit dword format (gfx9 family)
-}
-__device__ __forceinline__ void store16_device_scope(__amdgpu_buffer_rsrc_t r, int byte_off, v4f_t v) {
-  __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(v4u_t, v), r, byte_off, 0, 16 /* sc1 */);
-}
-__device__ __forceinline__ void store4_device_scope(__amdgpu_buffer_rsrc_t r, int byte_off, float v) {
-  __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned int, v), r, byte_off, 0, 16 /* sc1 */);
-}
-template <int KIND, int D, int KB>
-__global__ __launch_bounds__(BLOCK, 2) void k_step_wave_batched(const float* __restrict__ pi, const float* __restrict__ P,
-                                                                 int64_t B, float* __restrict__ pi_next,
-                                                                 float* __restrict__ reward) {
-  constexpr int G = WAVE / D, DD = D * D;
-  constexpr int WF = ((G * DD + 6 + 3) / 4) * 4;
-  constexpr int PER = (WF / 4 + WAVE - 1) / WAVE;
-  constexpr int NO = KB * G * D, NR = KB * G;          // floats of pi' / rewards per super tile
-  constexpr bool REW = KIND != MFG_REWARD_EXTERNAL;
-  static_assert(NO % 4 == 0 && NR % 4 == 0, "a super tile's outputs must be whole 16-byte words");
-  __shared__ __attribute__((aligned(16))) float sP[WAVES][WF];
-  __shared__ float sQ[WAVES][G * D];
-  __shared__ __attribute__((aligned(16))) float sO[WAVES][NO];
-  __shared__ __attribute__((aligned(16))) float sR[WAVES][NR];
-  __shared__ double sL[WAVES][G * (D + 1)];  // per-trajectory line of the column terms of the reward
-  const int tid = threadIdx.x, lane = tid & (WAVE - 1);
-  const int wv = __builtin_amdgcn_readfirstlane(tid / WAVE);  // wave-uniform by construction: keeps the tile bookkeeping scalar
-  const int t = lane / D, j = lane - t * D;
-  const bool valid = t < G;  // every tile is full (B is a multiple of G)
-  const int tc = valid ? t : 0;
-  float* wP = sP[wv];
-  float* wQ = sQ[wv];
-  float* wO = sO[wv];
-  float* wR = sR[wv];
-  double* line = sL[wv] + tc * (D + 1);
-  const int64_t ntiles = (B + G - 1) / G;
-  const int64_t nsuper = (ntiles + KB - 1) / KB;
-  const int64_t nwaves = (int64_t)gridDim.x * WAVES;
-  v4f_t pre[PER];
-  float prepi = 0.0f;
-  const v4f_t* P4 = reinterpret_cast<const v4f_t*>(P);
-  int64_t sup = (int64_t)blockIdx.x * WAVES + wv;
-  if (sup * KB < ntiles) MFG_WAVE_PREFETCH(sup * KB)
-  for (; sup < nsuper; sup += nwaves) {
-    const bool full = (sup + 1) * (int64_t)(KB * G) <= B;  // every trajectory of the super tile exists: batched stores
-    int oo = lane, ro = 0;  // running stash offsets of the tile (no per-tile multiply)
-    int kk = 0;
-#pragma unroll 1
-    for (; kk < KB; ++kk, oo += G * D, ro += G) {
-      const int64_t tile = sup * KB + kk;
-      if (tile >= ntiles) break;  // wave-uniform (last super tile only)
-      const int off = (int)((tile * (int64_t)(G * DD)) & 3);
-      v4f_t* d4 = reinterpret_cast<v4f_t*>(wP);
-#pragma unroll
-      for (int u = 0; u < PER; ++u) {
-        const int k = lane + u * WAVE;
-        if (k < WF / 4) d4[k] = pre[u];
-      }
-      if (lane < G * D) wQ[lane] = prepi;
-      __builtin_amdgcn_s_waitcnt(0xc07f);
-      __builtin_amdgcn_wave_barrier();
-      {
-        const int64_t nxt = (kk + 1 < KB && tile + 1 < ntiles) ? tile + 1 : (sup + nwaves) * KB;
-        if (nxt < ntiles) MFG_WAVE_PREFETCH(nxt)
-      }
-      const float* colp = wP + off + tc * DD + j;
-      const float* qv = wQ + tc * D;
-      double acc = 0.0, s1 = 0.0, s2 = 0.0;
-      // The reward of the PREVIOUS tile is summed here, one line entry per row of this tile's walk, by every lane of
-      // the trajectory (broadcast reads; the VALU is idle anyway): the per-tile serial phase of k_step_wave -- two wave
-      // barriers and 21 dependent adds on one lane -- disappears into the walk.  Same order: even terms, odd terms.
-      double r0 = 0.0, r1 = 0.0;
-      // rows in groups of col_group_rows(D) (mfg_device.h: three groups of seven at d = 21; the plain row order at 15): the fully
-      // unrolled walk of round 2 with the running sums folded at the end of a group (see k_step_wave)
-      constexpr int GR = col_group_rows(D);
-      double pa = 0.0, p1 = 0.0, p2 = 0.0;
-#pragma unroll
-      for (int i = 0; i < D; ++i) {
-        const double p = (double)colp[i * D];
-        const double qx = (double)qv[i];
-        const double u = p * qx;
-        pa += u;
-        if (REW) {
-          p1 = fma(u, p, p1);
-          if (KIND == MFG_REWARD_MFG_AC2) p2 = fma(u, u, p2);
-          if (i & 1) r1 += line[i];
-          else r0 += line[i];
-        }
-        if (GR < D && col_group_end(i, D)) {
-          acc += pa;
-          s1 += p1;
-          s2 += p2;
-          pa = p1 = p2 = 0.0;
-        }
-      }
-      if (GR >= D) {
-        acc = pa;
-        s1 = p1;
-        s2 = p2;
-      }
-      double racc = 0.0;
-      if (KIND == MFG_REWARD_MFG_AC2) racc = fma((double)qv[j], s1, -s2);
-      if (KIND == MFG_REWARD_SYNTHETIC) racc = s1;
-      const int64_t b = tile * G + tc;
-      if (full) {
-        if (valid) wO[oo] = (float)acc;
-      } else if (valid) {
-        pi_next[b * D + j] = (float)acc;
-      }
-      if (REW) {
-        if (kk > 0 && valid) {  // the previous tile's reward (stash: every lane of the trajectory writes the same value,
-          double r = r0 + r1;   // so the sums above stay in the walk instead of sinking into a one-lane branch)
-          if (KIND == MFG_REWARD_SYNTHETIC) r *= -0.5;
-          if (full) wR[ro - G + tc] = (float)r;
-          else if (j == 0) reward[b - G] = (float)r;
-        }
-        __builtin_amdgcn_wave_barrier();  // every lane has read the line (LDS operations of a wave execute in order)
-        if (valid) line[j] = racc;
-        __builtin_amdgcn_wave_barrier();
-      }
-    }
-    if (REW && kk > 0) {
-      // the super tile's last reward: the one serial sum left
-      __builtin_amdgcn_s_waitcnt(0xc07f);
-      __builtin_amdgcn_wave_barrier();
-      if (valid && j == 0) {
-        double r0 = 0.0, r1 = 0.0;
-        int k = 0;
-#pragma unroll 4
-        for (; k + 1 < D; k += 2) {
-          r0 += line[k];
-          r1 += line[k + 1];
-        }
-        if (k < D) r0 += line[k];
-        double r = r0 + r1;
-        if (KIND == MFG_REWARD_SYNTHETIC) r *= -0.5;
-        if (full) wR[ro - G + tc] = (float)r;
-        else reward[(sup * KB + kk - 1) * G + tc] = (float)r;
-      }
-    }
-    if (full) {
-      __builtin_amdgcn_s_waitcnt(0xc07f);
-      __builtin_amdgcn_wave_barrier();
-      const __amdgpu_buffer_rsrc_t ob = out_rsrc(pi_next + sup * (int64_t)NO);
-      const v4f_t* s4 = reinterpret_cast<const v4f_t*>(wO);
-      for (int k = lane; k < NO / 4; k += WAVE) store16_device_scope(ob, k * 16, s4[k]);
-      if (REW) {
-        const __amdgpu_buffer_rsrc_t rb = out_rsrc(reward + sup * (int64_t)NR);
-        const v4f_t* sr4 = reinterpret_cast<const v4f_t*>(wR);
-        for (int k = lane; k < NR / 4; k += WAVE) store16_device_scope(rb, k * 16, sr4[k]);
-      }
-      __builtin_amdgcn_s_waitcnt(0xc07f);
-      __builtin_amdgcn_wave_barrier();
-    }
-  }
-}
-
-// Fallback for a P pointer that is not 16-byte aligned: scalar staging, no prefetch.
-template <int KIND>
-__global__ __launch_bounds__(BLOCK) void k_step_small_unaligned(const float* __restrict__ pi, const float* __restrict__ P,
-                                                                int64_t B, int d, float* __restrict__ pi_next,
-                                                                float* __restrict__ reward) {
-  extern __shared__ __attribute__((aligned(16))) float smem[];
-  const int G = WAVE / d, TB = WAVES * G, dd = d * d;
-  double2* tQ = reinterpret_cast<double2*>(smem);
-  float* tP = reinterpret_cast<float*>(tQ + TB * d);
-  const int tid = threadIdx.x, lane = tid & (WAVE - 1), wv = tid / WAVE;
-  const int t = lane / d, j = lane - t * d;
-  const int p2 = next_pow2(d);
-  const int64_t ntiles = (B + TB - 1) / TB;
-  for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-    const int64_t b0 = tile * TB;
-    const int nb = (int)((B - b0) < TB ? (B - b0) : TB);
-    for (int k = tid; k < nb * dd; k += BLOCK) tP[k] = P[b0 * dd + k];
-    for (int k = tid; k < nb * d; k += BLOCK) {
-      const double v = (double)pi[b0 * d + k];
-      tQ[k] = make_double2(v, v * v);
-    }
-    __syncthreads();
-    const int tl = wv * G + t;
-    const bool valid = (t < G) && (tl < nb);
-    const int tlc = valid ? tl : 0;
-    const float* colp = tP + tlc * dd + j;
-    const double2* qv = tQ + tlc * d;
-    double acc = 0.0, s1 = 0.0, s2 = 0.0;
-    const int grp = col_group_rows(d);  // (mfg_device.h: pi' of the aligned kernels bit for bit, also at d = 21)
-    for (int g0 = 0; g0 < d; g0 += grp) {
-      double pa = 0.0, p1 = 0.0, p2 = 0.0;
-      for (int i = g0; i < g0 + grp && i < d; ++i) {
-        const double p = (double)colp[i * d];
-        const double2 q = qv[i];
-        const double pp = p * p;
-        pa = fma(p, q.x, pa);
-        p1 = fma(q.x, pp, p1);
-        p2 = fma(q.y, pp, p2);
-      }
-      acc = g0 ? acc + pa : pa;
-      s1 = g0 ? s1 + p1 : p1;
-      s2 = g0 ? s2 + p2 : p2;
-    }
-    double racc = 0.0;
-    if (KIND == MFG_REWARD_MFG_AC2) racc = fma(qv[j].x, s1, -s2);
-    if (KIND == MFG_REWARD_SYNTHETIC) racc = -0.5 * s1;
-    if (KIND != MFG_REWARD_EXTERNAL) racc = seg_sum(racc, j, d, p2);
-    if (valid) {
-      pi_next[(b0 + tl) * d + j] = (float)acc;
-      if (KIND != MFG_REWARD_EXTERNAL && j == 0) reward[b0 + tl] = (float)racc;
-    }
-    __syncthreads();
-  }
-}
-
-// ---------------------------------------------------------------------------------------------
-// a3+a4, d = 4*LPR (d = 128: LPR = 32, d = 256: LPR = 64): one wavefront per trajectory, every lane issues
-// 16-byte loads and one wave instruction covers 64/LPR consecutive rows (1 KiB, fully coalesced).  8-byte
-// or half-populated loads reach only ~0.55x of this rate (the d = 128 case of k_step_large).  The lane
-// groups that hold the same columns of different rows are combined with xor-shuffles at the end.
-// ---------------------------------------------------------------------------------------------
-#ifndef MFG_ROWS_UNROLL
-#define MFG_ROWS_UNROLL 8   // row groups (1 KiB wave loads) per chunk; two chunks are in flight / in use per wave
-#endif
-#ifndef MFG_ROWS_BPC
-#define MFG_ROWS_BPC 2      // resident blocks per CU the grid is sized for (8 waves per CU)
-#endif
-#ifndef MFG_ROWS_KT
-#define MFG_ROWS_KT 8       // consecutive trajectories per wave whose outputs are written as one burst (large batches)
-#endif
-#ifndef MFG_ROWS_ABL_NOREW   // timing ablations (tools/variant.sh): drop the reward sums / the output stores
-#define MFG_ROWS_ABL_NOREW 0
-#endif
-#ifndef MFG_ROWS_ABL_NOSTORE
-#define MFG_ROWS_ABL_NOSTORE 0
-#endif
-#ifndef MFG_ROWS_ABL_NOMATH
-#define MFG_ROWS_ABL_NOMATH 0
-#endif
-// Round 2: a CONTINUOUS load stream per wave.  The first version loaded pi, staged it, and only then started the row
-// loads of a trajectory -- two serial memory latencies per trajectory during which the wave streamed nothing (12 % of
-// the time at d = 128, fitted from the d = 128 / 256 rates) -- and ran 32 waves per CU.  Now the rows are consumed in
-// chunks of U row groups from two register buffers (ping-pong): while one chunk is multiplied the next one is in flight,
-// and the chunk after a trajectory's last is the FIRST chunk of the wave's next trajectory, issued before the reduction /
-// stores of the current one; the next trajectory's state is prefetched into registers at the start of the current one.
-// 8 waves per CU (more resident waves measured slower: d = 256 6.5 TB/s at 32 waves/CU, 6.9-7.0 at 8), outputs stored at
-// device scope (sc1).  Per-lane summation order is unchanged (rows in increasing order) => bit-identical results.
-// KT > 1: a wave takes KT CONSECUTIVE trajectories (a super tile), parks their pi' / rewards in its LDS stash and writes
-// them as one contiguous burst (the d = 21 finding: it is the trickle of small writes between the reads that costs
-// bandwidth -- the 0.8 % of bytes written here cost 6 % at d = 128).  KT = 1 (small batches): direct stores.
-template <int KIND, int LPR, int KT>
-__global__ __launch_bounds__(BLOCK, 2) void k_step_rows(const float* __restrict__ pi, const float* __restrict__ P, int64_t B,
-                                                        float* __restrict__ pi_next, float* __restrict__ reward) {
-  constexpr int d = 4 * LPR, RPW = WAVE / LPR;
-  constexpr int U = MFG_ROWS_UNROLL;
-  constexpr int CPT = d / RPW / U;   // chunks per trajectory
-  constexpr int NQ = d / WAVE;       // state entries per lane
-  static_assert(CPT >= 2 && CPT % 2 == 0, "ping-pong needs an even number of chunks per trajectory");
-  static_assert(KT == 1 || KT % 4 == 0, "a super tile's rewards must be whole 16-byte words");
-  __shared__ double2 qs[WAVES][d];  // (pi_i, pi_i^2) fp64 per wave
-  __shared__ __attribute__((aligned(16))) float sO[WAVES][KT > 1 ? KT * d : 4];
-  __shared__ __attribute__((aligned(16))) float sR[WAVES][KT > 1 ? KT : 4];
-  const int tid = threadIdx.x, lane = tid & (WAVE - 1);
-  const int wv = __builtin_amdgcn_readfirstlane(tid / WAVE);
-  const int sub = lane / LPR, c4 = lane - sub * LPR;
-  double2* q = qs[wv];
-  float* wO = sO[wv];
-  float* wR = sR[wv];
-  const int64_t nw = (int64_t)gridDim.x * WAVES;
-  const int64_t nsup = (B + KT - 1) / KT;
-  int64_t sup = (int64_t)blockIdx.x * WAVES + wv;
-  if (sup >= nsup) return;
-  v4f_t va[U], vb[U];
-  float pnx[NQ];
-  // chunk c of trajectory bb -> register buffer BUF (U wave-wide 1 KiB loads)
-#define MFG_ROWS_ISSUE(BUF, bb, c)                                                                          \
-  {                                                                                                         \
-    const v4f_t* src = reinterpret_cast<const v4f_t*>(P + (bb) * (int64_t)d * d) + (c) * (U * WAVE) + lane; \
-    _Pragma("unroll") for (int u = 0; u < U; ++u) BUF[u] = MFG_STREAM_LOAD(src + u * WAVE);                 \
-  }
-#define MFG_ROWS_COMPUTE(BUF, c)                                    \
-  _Pragma("unroll") for (int u = 0; u < U; ++u) {                   \
-    if (MFG_ROWS_ABL_NOMATH) {                                      \
-      acc[0] += (double)(BUF[u].x + BUF[u].y + BUF[u].z + BUF[u].w); \
-      continue;                                                     \
-    }                                                               \
-    const double2 qq = q[((c) * U + u) * RPW + sub];                \
-    const float pv[4] = {BUF[u].x, BUF[u].y, BUF[u].z, BUF[u].w};   \
-    _Pragma("unroll") for (int k = 0; k < 4; ++k) {                 \
-      const double p = (double)pv[k];                               \
-      acc[k] = fma(p, qq.x, acc[k]);                                \
-      if (KIND != MFG_REWARD_EXTERNAL && !MFG_ROWS_ABL_NOREW) {     \
-        const double pp = p * p;                                    \
-        s1[k] = fma(qq.x, pp, s1[k]);                               \
-        if (KIND == MFG_REWARD_MFG_AC2) s2 = fma(qq.y, pp, s2);     \
-      }                                                             \
-    }                                                               \
-  }
-  // prologue: state of the first trajectory, its first chunk
-  {
-    const int64_t b0 = sup * KT;
-#pragma unroll
-    for (int m = 0; m < NQ; ++m) pnx[m] = pi[b0 * d + lane + m * WAVE];
-    MFG_ROWS_ISSUE(va, b0, 0)
-  }
-  for (; sup < nsup; sup += nw) {
-    const bool full = KT > 1 && (sup + 1) * KT <= B;  // every trajectory of the super tile exists: batched stores
-#pragma unroll 1
-    for (int kk = 0; kk < KT; ++kk) {
-      const int64_t b = sup * KT + kk;
-      if (b >= B) break;  // wave-uniform (last super tile only)
-      // the wave's next trajectory (B = none: the very last chunk issue re-reads this trajectory's chunk 0)
-      const int64_t bn = (kk + 1 < KT && b + 1 < B) ? b + 1 : ((sup + nw) * KT < B ? (sup + nw) * KT : B);
-      __builtin_amdgcn_wave_barrier();
-#pragma unroll
-      for (int m = 0; m < NQ; ++m) {
-        const double v = (double)pnx[m];
-        q[lane + m * WAVE] = make_double2(v, v * v);
-      }
-      __builtin_amdgcn_s_waitcnt(0xc07f);
-      __builtin_amdgcn_wave_barrier();
-      if (bn < B) {
-#pragma unroll
-        for (int m = 0; m < NQ; ++m) pnx[m] = pi[bn * d + lane + m * WAVE];
-      }
-      double acc[4] = {0.0, 0.0, 0.0, 0.0}, s1[4] = {0.0, 0.0, 0.0, 0.0}, s2 = 0.0;
-#pragma unroll 1
-      for (int c = 0; c < CPT; c += 2) {
-        MFG_ROWS_ISSUE(vb, b, c + 1)
-        MFG_ROWS_COMPUTE(va, c)
-        {
-          // always issued (no phi over the register buffer): the chunk after the wave's very last one re-reads chunk 0
-          const bool more = c + 2 < CPT;
-          const int64_t nb = more ? b : (bn < B ? bn : b);
-          const int nc = more ? c + 2 : 0;
-          MFG_ROWS_ISSUE(va, nb, nc)
-        }
-        MFG_ROWS_COMPUTE(vb, c + 1)
-      }
-#pragma unroll
-      for (int off = LPR; off < WAVE; off <<= 1) {
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-          acc[k] += __shfl_xor(acc[k], off, WAVE);
-          if (KIND != MFG_REWARD_EXTERNAL) s1[k] += __shfl_xor(s1[k], off, WAVE);
-        }
-      }
-      if (sub == 0 && (!MFG_ROWS_ABL_NOSTORE || acc[0] == 123.456)) {
-        const v4f_t ov = {(float)acc[0], (float)acc[1], (float)acc[2], (float)acc[3]};
-        if (full) reinterpret_cast<v4f_t*>(wO + kk * d)[c4] = ov;
-        else store16_device_scope(out_rsrc(pi_next + b * d), c4 * 16, ov);
-      }
-      if (KIND != MFG_REWARD_EXTERNAL) {
-        double racc = 0.0;
-        if (sub == 0) {
-#pragma unroll
-          for (int k = 0; k < 4; ++k) racc += (KIND == MFG_REWARD_MFG_AC2) ? q[4 * c4 + k].x * s1[k] : s1[k];
-        }
-        if (KIND == MFG_REWARD_MFG_AC2) racc -= s2;
-        racc = wave_sum(racc);
-        if (KIND == MFG_REWARD_SYNTHETIC) racc *= -0.5;
-        if (lane == 0 && (!MFG_ROWS_ABL_NOSTORE || racc == 123.456)) {
-          if (full) wR[kk] = (float)racc;
-          else store4_device_scope(out_rsrc(reward + b), 0, (float)racc);
-        }
-      }
-    }
-    if (full) {
-      __builtin_amdgcn_s_waitcnt(0xc07f);
-      __builtin_amdgcn_wave_barrier();
-      const __amdgpu_buffer_rsrc_t ob = out_rsrc(pi_next + sup * (int64_t)(KT * d));
-      const v4f_t* s4 = reinterpret_cast<const v4f_t*>(wO);
-#pragma unroll
-      for (int k = lane; k < KT * d / 4; k += WAVE) store16_device_scope(ob, k * 16, s4[k]);
-      if (KIND != MFG_REWARD_EXTERNAL && lane < KT / 4)
-        store16_device_scope(out_rsrc(reward + sup * (int64_t)KT), lane * 16, reinterpret_cast<const v4f_t*>(wR)[lane]);
-      __builtin_amdgcn_s_waitcnt(0xc07f);
-      __builtin_amdgcn_wave_barrier();
-    }
-  }
-#undef MFG_ROWS_ISSUE
-#undef MFG_ROWS_COMPUTE
-}
-
-// ---------------------------------------------------------------------------------------------
-// a3+a4, large d: one wavefront per trajectory; lane owns VEC consecutive columns in each of R
-// 64*VEC-wide column chunks; rows stream from HBM with coalesced VEC*4-byte loads per lane.
-// ---------------------------------------------------------------------------------------------
-template <int VEC>
-struct VecT;
-template <>
-struct VecT<1> {
-  using type = float;
-};
-template <>
-struct VecT<2> {
-  using type = float2;
-};
-template <>
-struct VecT<4> {
-  using type = float4;
-};
-
-template <int VEC, int R, int KIND>
-__global__ __launch_bounds__(BLOCK) void k_step_large(const float* __restrict__ pi, const float* __restrict__ P,
-                                                      int64_t B, int d, float* __restrict__ pi_next,
-                                                      float* __restrict__ reward) {
-  extern __shared__ __attribute__((aligned(16))) float smem[];
-  using V = typename VecT<VEC>::type;
-  const int tid = threadIdx.x, lane = tid & (WAVE - 1), wv = tid / WAVE;
-  float* pis = smem + wv * d;
-  const int64_t nw = (int64_t)gridDim.x * WAVES;
-  for (int64_t b = (int64_t)blockIdx.x * WAVES + wv; b < B; b += nw) {
-    for (int c = lane; c < d; c += WAVE) pis[c] = pi[b * d + c];
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_s_waitcnt(0xc07f);  // lgkmcnt(0): LDS writes of this wave landed
-    double pc[R][VEC], acc[R][VEC], s1[R][VEC];
-    int col[R];
-#pragma unroll
-    for (int m = 0; m < R; ++m) {
-      col[m] = (m * WAVE + lane) * VEC;
-#pragma unroll
-      for (int v = 0; v < VEC; ++v) {
-        pc[m][v] = (col[m] + v < d) ? (double)pis[col[m] + v] : 0.0;
-        acc[m][v] = 0.0;
-        s1[m][v] = 0.0;
-      }
-    }
-    double s2 = 0.0;  // sum_i pi_i^2 sum_(own columns) p^2
-    const float* Pb = P + b * (int64_t)d * d;
-#pragma unroll 4
-    for (int i = 0; i < d; ++i) {
-      const double pii = (double)pis[i];
-      const double pii2 = pii * pii;
-      const float* row = Pb + (int64_t)i * d;
-#pragma unroll
-      for (int m = 0; m < R; ++m) {
-        if (col[m] < d) {  // VEC divides d on the vector paths, so a chunk is fully in or out
-          float pv[VEC];
-          *reinterpret_cast<V*>(pv) = *reinterpret_cast<const V*>(row + col[m]);
-#pragma unroll
-          for (int v = 0; v < VEC; ++v) {
-            const double p = (double)pv[v];
-            acc[m][v] = fma(p, pii, acc[m][v]);
-            if (KIND != MFG_REWARD_EXTERNAL) {
-              const double pp = p * p;
-              s1[m][v] = fma(pii, pp, s1[m][v]);
-              if (KIND == MFG_REWARD_MFG_AC2) s2 = fma(pii2, pp, s2);
-            }
-          }
-        }
-      }
-    }
-#pragma unroll
-    for (int m = 0; m < R; ++m) {
-      if (col[m] < d) {
-        float pv[VEC];
-#pragma unroll
-        for (int v = 0; v < VEC; ++v) pv[v] = (float)acc[m][v];
-        *reinterpret_cast<V*>(pi_next + b * d + col[m]) = *reinterpret_cast<V*>(pv);
-      }
-    }
-    if (KIND != MFG_REWARD_EXTERNAL) {
-      double racc = 0.0;
-#pragma unroll
-      for (int m = 0; m < R; ++m)
-#pragma unroll
-        for (int v = 0; v < VEC; ++v) racc += (KIND == MFG_REWARD_MFG_AC2) ? pc[m][v] * s1[m][v] : s1[m][v];
-      if (KIND == MFG_REWARD_MFG_AC2) racc -= s2;
-      racc = wave_sum(racc);
-      if (KIND == MFG_REWARD_SYNTHETIC) racc *= -0.5;
-      if (lane == 0) reward[b] = (float)racc;
-    }
-    __builtin_amdgcn_wave_barrier();
-  }
-}
-
-#include "mfg_grad.h"
-
-// ---------------------------------------------------------------------------------------------
-// Round 3: register-blocked form of k_grad_mfma for d = 128 / 256 (C3, C5).  k_grad_mfma gives a wave an arbitrary run of
-// tiles, fetches BOTH operands of every matrix instruction from LDS and tests `i < nmine` (a scalar branch, i.e. a basic
-// block boundary) in front of each: nothing overlaps, 190-220 cycles per instruction against the ~70 the matrix core needs,
-// whatever the tile count per wave or the number of sample slices (variants measured: no better).  Here a wave owns
-// RECTANGLES of tiles given at compile time as (rows NA, columns NB, tile mask) -- one K step of 4 samples fetches NA + NB
-// operands for up to NA NB instructions, no branch in the K loop, and the fetches of a step issue under the matrix
-// instructions of the step before.  The upper triangle is cut so that EVERY wave has the same number of tiles (the
-// instruction stream of a SIMD is the bound; 64 x 64 "super tiles" s = 0 .. d/64-1 on the diagonal, (r, c) off it):
-//   d = 256, 136 tiles = 8 waves x 17 (grid.y = 2 blocks of 4 waves):
-//     y = 0: (0,1) + one tile of diagonal 1 | (0,2) + one | (0,3) + one | diagonal 0 (10 tiles) + the first two rows of diagonal 1 (7)
-//     y = 1: (1,2) + one tile of diagonal 3 | (1,3) + one | (2,3) + one | diagonal 2 + the first two rows of diagonal 3
-//   d = 128, 36 tiles = 4 waves x 9: half of (0,1) (2 x 4 tiles) + tile (3,3) of a diagonal | ... | diagonal 0 less (3,3) | diagonal 1 less (3,3)
-// Staging, split-K over grid.x, partial rows, side sums and the row reduction are those of k_grad_mfma.
-// ---------------------------------------------------------------------------------------------
-constexpr unsigned GM2_RECT44 = 0xFFFFu, GM2_DIAG44 = 0x8CEFu, GM2_DIAG44M = 0x0CEFu, GM2_TRAP24 = 0xEFu, GM2_RECT24 = 0xFFu,
-                   GM2_ONE = 1u;
-__host__ __device__ constexpr int gm2_count(unsigned m) { return m == 0 ? 0 : (int)(m & 1u) + gm2_count(m >> 1); }
-
-// one rectangle over one staged chunk
-template <int D, int NA, int NB, unsigned MASK>
-__device__ __forceinline__ void gm2_step(const float* __restrict__ abase, const float* __restrict__ bbase, int off, double dk,
-                                         v4d_t* acc) {
-  double av[NA], bv[NB];
-#pragma unroll
-  for (int i = 0; i < NA; ++i) av[i] = dk * (double)abase[off + (i << 4)];  // A[row li][k] = delta_k pi_k[16 (ra + i) + li]
-#pragma unroll
-  for (int j = 0; j < NB; ++j) bv[j] = (double)bbase[off + (j << 4)];       // B[k][col li] = pi_k[16 (cb + j) + li]
-  int t = 0;
-#pragma unroll
-  for (int i = 0; i < NA; ++i) {
-#pragma unroll
-    for (int j = 0; j < NB; ++j) {
-      if ((MASK >> (i * NB + j)) & 1u) {
-        acc[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(av[i], bv[j], acc[t], 0, 0, 0);
-        ++t;
-      }
-    }
-  }
-}
-template <int D, int NA0, int NB0, unsigned M0, int NA1, int NB1, unsigned M1>
-__device__ __forceinline__ void gm2_chunk(const float* __restrict__ sp, const double* __restrict__ dl, int lk, int li,
-                                          const int* ra, const int* cb, v4d_t* acc) {
-  constexpr int pitch = D + 16;
-  const float* lb = sp + lk * pitch + li;
-  const float *a0 = lb + (ra[0] << 4), *b0 = lb + (cb[0] << 4), *a1 = lb + (ra[1] << 4), *b1 = lb + (cb[1] << 4);
-#pragma unroll 2
-  for (int ks = 0; ks < GM_KC / 4; ++ks) {  // (fully unrolled the compiler hoists all 8 steps' operands: 444 spilled registers)
-    const double dk = dl[ks * 4 + lk];
-    gm2_step<D, NA0, NB0, M0>(a0, b0, ks * 4 * pitch, dk, acc);
-    if constexpr (M1 != 0) gm2_step<D, NA1, NB1, M1>(a1, b1, ks * 4 * pitch, dk, acc + gm2_count(M0));
-  }
-}
-template <int D, int NA, int NB, unsigned MASK>
-__device__ __forceinline__ void gm2_store(double* __restrict__ out, int lk, int li, int ra, int cb, const v4d_t* acc) {
-  int t = 0;
-#pragma unroll
-  for (int i = 0; i < NA; ++i) {
-#pragma unroll
-    for (int j = 0; j < NB; ++j) {
-      if ((MASK >> (i * NB + j)) & 1u) {
-#pragma unroll
-        for (int v = 0; v < 4; ++v) {  // D[i][j] of a tile: lane holds rows 4 v + lane / 16, column lane % 16
-          const int gi = ((ra + i) << 4) + 4 * v + lk, gj = ((cb + j) << 4) + li;
-          if (gi <= gj) out[feat_idx(gi, gj, D)] = acc[t][v];
-        }
-        ++t;
-      }
-    }
-  }
-}
-
-template <int D>
-struct Gm2Geom {
-  static constexpr int NY = D == 256 ? 2 : 1, ACCN = D == 256 ? 17 : 9;
-};
-template <int NA_, int NB_, unsigned MASK_>
-struct Gm2Rect {
-  static constexpr int NA = NA_, NB = NB_;
-  static constexpr unsigned MASK = MASK_;
-};
-template <int D>
-__global__ __launch_bounds__(BLOCK, 2) void k_grad_mfma2(GradArgs a) {
-  static_assert(D == 128 || D == 256, "tile maps exist for d = 128 and 256");
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-  constexpr int d = D, pitch = D + 16;
-  constexpr int Q = d * (d + 1) / 2, F = Q + d + 1, FO = F + 3;
-  constexpr int ACCN = Gm2Geom<D>::ACCN;
-  double* dl = reinterpret_cast<double*>(smem_raw);       // [KC] delta
-  double* red = dl + GM_KC;                               // [4][BLOCK] scalar reduction scratch
-  float* sp = reinterpret_cast<float*>(red + 4 * BLOCK);  // [KC][pitch] pi rows
-  const int tid = threadIdx.x, lane = tid & (WAVE - 1);
-  const int wv = __builtin_amdgcn_readfirstlane(tid / WAVE), y = (int)blockIdx.y;
-  // this wave's two rectangles (tile coordinates of their corners); the last wave of a block owns the diagonal pieces
-  const bool diag = D == 256 ? wv == 3 : wv >= 2;
-  int ra[2] = {0, 0}, cb[2] = {0, 0};
-  if (D == 256) {
-    const int sd = 2 * y;  // this block's diagonal super tiles: sd (whole), sd + 1 (split)
-    if (diag) {
-      ra[0] = cb[0] = 4 * sd;
-      ra[1] = cb[1] = 4 * sd + 4;
-    } else {
-      const int sr = y == 0 ? 0 : (wv == 2 ? 2 : 1), sc = y == 0 ? wv + 1 : (wv == 0 ? 2 : 3);
-      ra[0] = 4 * sr;
-      cb[0] = 4 * sc;
-      ra[1] = 4 * sd + 4 + (wv == 2 ? 3 : 2);  // tiles (2,2) (2,3) (3,3) of super tile sd + 1
-      cb[1] = 4 * sd + 4 + (wv == 0 ? 2 : 3);
-    }
-  } else {
-    if (diag) ra[0] = cb[0] = 4 * (wv - 2);
-    else {
-      ra[0] = 2 * wv;
-      cb[0] = 4;
-      ra[1] = cb[1] = 4 * wv + 3;  // tile (3,3) of diagonal super tile wv
-    }
-  }
-  const bool side = blockIdx.y == 0;  // also owns the linear and scalar sums
-  double lin = 0.0, s_d = 0.0, s_dg = 0.0, s_r = 0.0, s_n = 0.0;  // (d <= BLOCK: one linear column per thread)
-  const int li = lane & 15, lk = lane >> 4;
-  const double invT = 1.0 / (double)a.T;
-  // register prefetch of a chunk: thread -> (row q0 + rpp u, float4 column c4)
-  constexpr int dq = d >> 2, rpp = BLOCK / dq, NPF = GM_KC / rpp;
-  static_assert(BLOCK % dq == 0 && GM_KC % rpp == 0, "whole rows per staging pass");
-  const int q0 = tid / dq, c4 = tid - q0 * dq;
-  double* out = a.partial + (int64_t)blockIdx.x * FO;
-  // The whole sample loop is instantiated once per ROLE and the role is chosen outside it: with the role test inside the
-  // loop the two instantiations' accumulators are merged at every iteration (two full sets live: 254 spilled registers
-  // at d = 256).  Both instantiations execute the same barriers.
-  auto run = [&](auto r0, auto r1) __attribute__((always_inline)) {
-    using R0 = decltype(r0);
-    using R1 = decltype(r1);
-    v4d_t acc[ACCN];
-#pragma unroll
-    for (int i = 0; i < ACCN; ++i) acc[i] = (v4d_t)(0.0);
-    float4 pf[NPF];
-    double pf_de = 0.0, pf_dg = 0.0, pf_rr = 0.0;
-    bool pf_on = false;
-    auto fetch = [&](int64_t n0_) __attribute__((always_inline)) {
-      const int cn_ = (int)((a.N - n0_) < GM_KC ? (a.N - n0_) : GM_KC);
-#pragma unroll
-      for (int u = 0; u < NPF; ++u) {
-        const int q = q0 + u * rpp;
-        pf[u] = make_float4(0.f, 0.f, 0.f, 0.f);  // rows past the end are zero: they add nothing
-        if (q < cn_) {
-          const int64_t n = n0_ + q;
-          const int64_t b = (int64_t)(((double)n + 0.5) * invT);
-          pf[u] = *reinterpret_cast<const float4*>(a.pi + b * a.stride_b + (n - b * a.T) * d + 4 * c4);
-        }
-      }
-      pf_de = 0.0, pf_dg = 0.0, pf_rr = 0.0, pf_on = false;
-      if (tid < cn_) {
-        const int64_t n = n0_ + tid;
-        pf_de = a.delta[n];
-        pf_rr = a.reward ? (double)a.reward[n] : 0.0;
-        if (a.g) pf_dg = a.g[n];
-        pf_on = true;
-      }
-    };
-    if ((int64_t)blockIdx.x * GM_KC < a.N) fetch((int64_t)blockIdx.x * GM_KC);
-    for (int64_t n0 = (int64_t)blockIdx.x * GM_KC; n0 < a.N; n0 += (int64_t)gridDim.x * GM_KC) {
-      __syncthreads();
-#pragma unroll
-      for (int u = 0; u < NPF; ++u) *reinterpret_cast<float4*>(sp + (q0 + u * rpp) * pitch + 4 * c4) = pf[u];
-      if (tid < GM_KC) {
-        if (side && pf_on) {
-          s_d += pf_de;
-          if (a.g) s_dg = fma(pf_de, pf_dg, s_dg);
-          s_r += pf_rr;
-          s_n += 1.0;
-        }
-        dl[tid] = pf_de;
-      }
-      __syncthreads();
-      const int64_t nn = n0 + (int64_t)gridDim.x * GM_KC;
-      if (nn < a.N) fetch(nn);
-      gm2_chunk<D, R0::NA, R0::NB, R0::MASK, R1::NA, R1::NB, R1::MASK>(sp, dl, lk, li, ra, cb, acc);
-      if (side && tid < d) {
-        double t = lin;
-#pragma unroll 8
-        for (int q = 0; q < GM_KC; ++q) t = fma(dl[q], (double)sp[q * pitch + tid], t);
-        lin = t;
-      }
-    }
-    gm2_store<D, R0::NA, R0::NB, R0::MASK>(out, lk, li, ra[0], cb[0], acc);
-    if constexpr (R1::MASK != 0) gm2_store<D, R1::NA, R1::NB, R1::MASK>(out, lk, li, ra[1], cb[1], acc + gm2_count(R0::MASK));
-  };
-  if (D == 256) {
-    if (diag) run(Gm2Rect<4, 4, GM2_DIAG44>{}, Gm2Rect<2, 4, GM2_TRAP24>{});
-    else run(Gm2Rect<4, 4, GM2_RECT44>{}, Gm2Rect<1, 1, GM2_ONE>{});
-  } else {
-    if (diag) run(Gm2Rect<4, 4, GM2_DIAG44M>{}, Gm2Rect<1, 1, 0u>{});
-    else run(Gm2Rect<2, 4, GM2_RECT24>{}, Gm2Rect<1, 1, GM2_ONE>{});
-  }
-  if (side) {
-    if (tid < d) out[Q + tid] = lin;
-    __syncthreads();
-    red[tid] = s_d;
-    red[BLOCK + tid] = s_dg;
-    red[2 * BLOCK + tid] = s_r;
-    red[3 * BLOCK + tid] = s_n;
-    __syncthreads();
-    if (tid < 4) {
-      double t = 0.0;
-      for (int q = 0; q < GM_KC; ++q) t += red[tid * BLOCK + q];  // only threads < KC hold scalar partials
-      out[Q + d + tid] = t;
-    }
-  }
-}
-
-// ---------------------------------------------------------------------------------------------
-// Critic values of a whole rollout on the fp64 matrix cores (d a multiple of 16, 64 <= d <= 512): the second GEMM-shaped
-// piece of the path.  V_n = x_n^T U x_n + b.x_n + c for the N = B (T+1) states a rollout left in pi_traj, i.e. the
-// diagonal of X U X^T: a wave owns 16 states (A operand: X[16 x 4] slices from its LDS copy of the rows), sweeps the
-// column tiles of the upper triangle U (B operand straight from the L2-resident weight vector, row k of U is contiguous in
-// c), and folds each finished 16 x 16 tile Y = X U into  v_n += sum_c (Y_nc + b_c) x_nc.  The 16 lanes that hold one state
-// are one DPP row, so the final sum is four DPP steps.  Inside the wave-per-trajectory rollout kernel the same values
-// cost a latency-bound triangular loop per state (10 % of the d = 128 training rollout); here they are ~2 nt (nt + 1)
-// matrix instructions per 16 states.  Followed by k_td_delta (delta = r + gamma V' - V).
-// ---------------------------------------------------------------------------------------------
-// Round 2b: the B operand comes from LDS.  Before, every lane fetched its U element from the L2-resident weight vector
-// with 64-bit index arithmetic and a select in front of every matrix instruction (~15 VALU + 1 dependent L2 load per
-// MFMA, the whole of U re-read by every wave for its 16 states): 3-6x the matrix-core time.  Now the block's four waves
-// (64 states) share each 64-row x 16-column piece of U: it is fetched once per block (zero-filled below the diagonal),
-// double-buffered in LDS -- the loads of piece n+1 are issued before the matrix instructions of piece n and committed
-// after them -- and a matrix instruction costs two LDS reads and a convert.
-constexpr int VM_CH = 64;  // rows of U per staged piece
-__global__ __launch_bounds__(BLOCK) void k_value_mfma(const float* __restrict__ pi, int64_t stride_b, int64_t N, int TP1, int d,
-                                                      const double* __restrict__ w, double* __restrict__ V) {
-  extern __shared__ __attribute__((aligned(16))) float smx[];
-  const int tid = threadIdx.x, lane = tid & (WAVE - 1);
-  const int wv = __builtin_amdgcn_readfirstlane(tid / WAVE);
-  const int li = lane & 15, lk = lane >> 4;
-  const int nt = d >> 4, pitch = d + 4;  // +4 floats: the 16 state rows of an A operand fall on distinct banks
-  const int Q = d * (d + 1) / 2;
-  float* xs = smx + (size_t)wv * 16 * pitch;
-  double* Bs = reinterpret_cast<double*>(smx + (size_t)WAVES * 16 * pitch);  // [2][VM_CH][16]
-  const double invT = 1.0 / (double)TP1;
-  const int64_t ngroups = (N + 15) / 16;
-  const int64_t npass = (ngroups + WAVES - 1) / WAVES;
-  // staging role of this thread: column sc of the tile, rows sr, sr + 16, sr + 32, sr + 48 of the piece
-  const int sc = tid & 15, sr = tid >> 4;
-  double stg[4];
-#define MFG_VM_LOAD(jt_, ch_)                                                              \
-  _Pragma("unroll") for (int q = 0; q < 4; ++q) {                                          \
-    const int k = VM_CH * (ch_) + sr + 16 * q, c = 16 * (jt_) + sc;                        \
-    stg[q] = (k <= c) ? w[k * d - (k * (k - 1)) / 2 + (c - k)] : 0.0;                      \
-  }
-#define MFG_VM_COMMIT(buf_)                                                                \
-  _Pragma("unroll") for (int q = 0; q < 4; ++q) Bs[((buf_) * VM_CH + sr + 16 * q) * 16 + sc] = stg[q];
-  for (int64_t pass = blockIdx.x; pass < npass; pass += gridDim.x) {
-    const int64_t n0 = (pass * WAVES + wv) * 16;
-    __syncthreads();  // the previous pass is done with Bs
-    // stage the 16 state rows (fp32, float4 copies: d is a multiple of 16 and rows are 16-byte aligned when stride_b % 4 == 0)
-    for (int e = lane; e < 16 * (d >> 2); e += WAVE) {
-      const int q = e / (d >> 2), c4 = e - q * (d >> 2);
-      const int64_t n = n0 + q;
-      float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (n < N) {
-        const int64_t b = (int64_t)(((double)n + 0.5) * invT);
-        v = *reinterpret_cast<const float4*>(pi + b * stride_b + (n - b * TP1) * (int64_t)d + 4 * c4);
-      }
-      *reinterpret_cast<float4*>(xs + q * pitch + 4 * c4) = v;
-    }
-    MFG_VM_LOAD(0, 0)
-    MFG_VM_COMMIT(0)
-    __syncthreads();
-    int buf = 0;
-    double vs[4] = {0.0, 0.0, 0.0, 0.0};
-    for (int jt = 0; jt < nt; ++jt) {
-      const int c = (jt << 4) + li;  // this lane's column of the tile
-      v4d_t acc = (v4d_t)(0.0);
-      const int nch = (16 * (jt + 1) + VM_CH - 1) / VM_CH;
-      for (int ch = 0; ch < nch; ++ch) {
-        // the next piece of the sweep: issue its loads now, commit them after this piece's matrix instructions
-        const bool last_ch = ch + 1 == nch;
-        const bool has_next = !last_ch || jt + 1 < nt;
-        const int njt = last_ch ? jt + 1 : jt, nc = last_ch ? 0 : ch + 1;
-        if (has_next) MFG_VM_LOAD(njt, nc)
-        int ksteps = 4 * (jt + 1) - (VM_CH / 4) * ch;  // rows 0 .. 16 jt + 15 of U, four at a time
-        if (ksteps > VM_CH / 4) ksteps = VM_CH / 4;
-        const float* xa = xs + li * pitch + VM_CH * ch + lk;
-        const double* bb = Bs + (buf * VM_CH + lk) * 16 + li;
-#pragma unroll 4
-        for (int ks = 0; ks < ksteps; ++ks)
-          acc = __builtin_amdgcn_mfma_f64_16x16x4f64((double)xa[4 * ks], bb[64 * ks], acc, 0, 0, 0);  // A[i = li][k], B[k][j = li]
-        if (has_next) MFG_VM_COMMIT(buf ^ 1)
-        __syncthreads();
-        buf ^= 1;
-      }
-      const double bc = w[Q + c];
-#pragma unroll
-      for (int v = 0; v < 4; ++v) vs[v] = fma(acc[v] + bc, (double)xs[(4 * v + lk) * pitch + c], vs[v]);  // D[i = 4v + lk][j = li]
-    }
-#pragma unroll
-    for (int v = 0; v < 4; ++v) {
-      double t = vs[v];
-      t += dpp_mov_f64<0xB1, 0xF>(t);
-      t += dpp_mov_f64<0x4E, 0xF>(t);
-      t += dpp_mov_f64<0x141, 0xF>(t);
-      t += dpp_mov_f64<0x140, 0xF>(t);
-      const int64_t n = n0 + 4 * v + lk;
-      if (li == 0 && n < N) V[n] = t + w[Q + d];
-    }
-  }
-#undef MFG_VM_LOAD
-#undef MFG_VM_COMMIT
-}
-
-// ---------------------------------------------------------------------------------------------
-// Round 3: GEMM-tiled form of k_value_mfma for d a multiple of 64 (C3, C5).  k_value_mfma keeps the FULL rows of a wave's
-// 16 states in LDS (66 KB per block at d = 256: one block per CU, one wave per SIMD), one accumulator tile per wave (every
-// matrix instruction waits for the one before) and a block barrier every 16 instructions: 226 cycles per instruction
-// against ~70.  Here a block owns 128 states and walks the upper triangle of U in 64 x 64 pieces (column block cb, row
-// chunk kc <= cb): a piece of U (fp64, zero below the diagonal) and the matching 128 x 64 slab of states (fp32) are staged
-// -- fetched into registers under the previous piece's matrix instructions, committed behind them -- and a wave runs
-// 2 state groups x 4 column tiles = 8 independent accumulators over the 16 K steps of the piece: 2 + 4 operand reads
-// for 8 matrix instructions, 128 instructions between barriers, two blocks per CU.  After a column block's last piece the
-// finished tiles Y = X U are folded into  v_n += sum_c (Y_nc + b_c) x_nc  (x: 32 LDS reads per lane per 64
-// columns, read back from the slab of the diagonal piece).  The all-zero tiles of a diagonal piece are skipped.
-// ---------------------------------------------------------------------------------------------
-constexpr int VM2_MB = 128, VM2_KC = 64, VM2_XP = VM2_KC + 2;  // states per block, rows per piece, pitch of the state slab
-                                                               // (2 mod 32: the 32 lanes of a half wave hit 32 banks)
-__global__ __launch_bounds__(BLOCK, 2) void k_value_mfma2(const float* __restrict__ pi, int64_t stride_b, int64_t N, int TP1, int d,
-                                                           const double* __restrict__ w, double* __restrict__ V) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-  double* Us = reinterpret_cast<double*>(smem_raw);                   // [KC][64]
-  float* Xs = reinterpret_cast<float*>(Us + VM2_KC * 64);             // [MB][XP]
-  const int tid = threadIdx.x, lane = tid & (WAVE - 1);
-  const int wv = __builtin_amdgcn_readfirstlane(tid / WAVE);
-  const int li = lane & 15, lk = lane >> 4;
-  const int ncb = d >> 6, Q = d * (d + 1) / 2;
-  const double invT = 1.0 / (double)TP1;
-  const int64_t npass = (N + VM2_MB - 1) / VM2_MB;
-  // staging roles.  U piece: thread -> row ur = tid / 4, sixteen columns from uc = 16 (tid % 4) (the row of U is contiguous in
-  // the packed weight vector); state slab: thread -> state xr + 16 u (u < 8), float4 column xc.
-  const int ur = tid >> 2, uc = (tid & 3) << 4;
-  const int xr = tid >> 4, xc = (tid & 15) << 2;
-  double ustg[16];
-  float4 xstg[8];
-  for (int64_t pass = blockIdx.x; pass < npass; pass += gridDim.x) {
-    const int64_t n0 = pass * VM2_MB;
-    // row pointers of this thread's staged states (clamped; rows past N are never written out)
-    const float* xrow[8];
-#pragma unroll
-    for (int u = 0; u < 8; ++u) {
-      int64_t n = n0 + xr + 16 * u;
-      if (n >= N) n = N - 1;
-      const int64_t b = (int64_t)(((double)n + 0.5) * invT);
-      xrow[u] = pi + b * stride_b + (n - b * TP1) * (int64_t)d;
-    }
-    auto fetch = [&](int cbk, int kc) __attribute__((always_inline)) {
-      const int k = VM2_KC * kc + ur, c0 = 64 * cbk + uc;
-      const double* wr = w + ((int64_t)k * d - ((int64_t)k * (k - 1)) / 2 - k);  // U[k][c] = wr[c] for c >= k
-#pragma unroll
-      for (int q = 0; q < 16; ++q) ustg[q] = (c0 + q >= k) ? wr[c0 + q] : 0.0;
-#pragma unroll
-      for (int u = 0; u < 8; ++u) xstg[u] = *reinterpret_cast<const float4*>(xrow[u] + VM2_KC * kc + xc);
-    };
-    auto commit = [&]() __attribute__((always_inline)) {
-#pragma unroll
-      for (int q = 0; q < 16; q += 2) *reinterpret_cast<double2*>(Us + ur * 64 + uc + q) = make_double2(ustg[q], ustg[q + 1]);
-#pragma unroll
-      for (int u = 0; u < 8; ++u) {
-        float* dst = Xs + (xr + 16 * u) * VM2_XP + xc;  // (pitch 66: 8-byte aligned only)
-        *reinterpret_cast<float2*>(dst) = make_float2(xstg[u].x, xstg[u].y);
-        *reinterpret_cast<float2*>(dst + 2) = make_float2(xstg[u].z, xstg[u].w);
-      }
-    };
-    double vs[2][4] = {{0.0, 0.0, 0.0, 0.0}, {0.0, 0.0, 0.0, 0.0}};
-    fetch(0, 0);
-    for (int cbk = 0; cbk < ncb; ++cbk) {
-      v4d_t acc[2][4];
-#pragma unroll
-      for (int sg = 0; sg < 2; ++sg)
-#pragma unroll
-        for (int cg = 0; cg < 4; ++cg) acc[sg][cg] = (v4d_t)(0.0);
-      for (int kc = 0; kc <= cbk; ++kc) {
-        __syncthreads();  // the previous piece's matrix instructions are done with Us / Xs
-        commit();
-        __syncthreads();
-        // the next piece of the sweep (its loads land under this piece's matrix instructions)
-        const bool last_kc = kc == cbk;
-        if (!last_kc || cbk + 1 < ncb) fetch(last_kc ? cbk + 1 : cbk, last_kc ? 0 : kc + 1);
-        const float* xa = Xs + (wv * 32 + li) * VM2_XP + lk;
-        const double* ub = Us + lk * 64 + li;
-        if (!last_kc) {
-#pragma unroll 2
-          for (int ks = 0; ks < VM2_KC / 4; ++ks) {
-            const double a0 = (double)xa[4 * ks], a1 = (double)xa[16 * VM2_XP + 4 * ks];  // A[state li][k]
-#pragma unroll
-            for (int cg = 0; cg < 4; ++cg) {
-              const double bv = ub[4 * ks * 64 + 16 * cg];  // B[k][col li]
-              acc[0][cg] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, bv, acc[0][cg], 0, 0, 0);
-              acc[1][cg] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, bv, acc[1][cg], 0, 0, 0);
-            }
-          }
-        } else {
-          // the piece on the diagonal: rows 16 p .. 16 p + 15 of it are zero left of column tile p -- skip those tiles
-#pragma unroll
-          for (int pq = 0; pq < 4; ++pq) {
-#pragma unroll 2
-            for (int ks = 4 * pq; ks < 4 * pq + 4; ++ks) {
-              const double a0 = (double)xa[4 * ks], a1 = (double)xa[16 * VM2_XP + 4 * ks];
-#pragma unroll
-              for (int cg = pq; cg < 4; ++cg) {
-                const double bv = ub[4 * ks * 64 + 16 * cg];
-                acc[0][cg] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, bv, acc[0][cg], 0, 0, 0);
-                acc[1][cg] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, bv, acc[1][cg], 0, 0, 0);
-              }
-            }
-          }
-        }
-      }
-      // fold the finished 32 x 64 block of Y: D[i = 4 v + lk][j = li] of tile (sg, cg).  The state slab of the diagonal
-      // piece (still in LDS: the next commit waits behind the barrier) holds exactly the columns of this block.
-#pragma unroll
-      for (int cg = 0; cg < 4; ++cg) {
-        const double bc = w[Q + 64 * cbk + 16 * cg + li];
-#pragma unroll
-        for (int sg = 0; sg < 2; ++sg) {
-#pragma unroll
-          for (int v = 0; v < 4; ++v) {
-            const double x = (double)Xs[(wv * 32 + sg * 16 + 4 * v + lk) * VM2_XP + 16 * cg + li];
-            vs[sg][v] = fma(acc[sg][cg][v] + bc, x, vs[sg][v]);
-          }
-        }
-      }
-    }
-#pragma unroll
-    for (int sg = 0; sg < 2; ++sg) {
-#pragma unroll
-      for (int v = 0; v < 4; ++v) {
-        double t = vs[sg][v];
-        t += dpp_mov_f64<0xB1, 0xF>(t);
-        t += dpp_mov_f64<0x4E, 0xF>(t);
-        t += dpp_mov_f64<0x141, 0xF>(t);
-        t += dpp_mov_f64<0x140, 0xF>(t);
-        const int64_t n = n0 + wv * 32 + sg * 16 + 4 * v + lk;
-        if (li == 0 && n < N) V[n] = t + w[Q + d];
-      }
-    }
-  }
-}
-
-// delta[b, s] = r[b, s] + gd(s) V[b, s+1] - V[b, s],  gd = gamma (mfg_ac2.py:505) or the running gamma^s (ac_irl.py:691);
-// reward == NULL: the IRL form without the reward (added by the gradient kernel once the network has run).
-__global__ void k_td_delta(const double* __restrict__ V, const float* __restrict__ reward, int64_t B, int T, double gamma,
-                           int discount_pow, double* __restrict__ delta) {
-  const int64_t n_tot = B * T;
-  for (int64_t n = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; n < n_tot; n += (int64_t)gridDim.x * blockDim.x) {
-    const int64_t b = n / T;
-    const int s = (int)(n - b * T);
-    double gd = gamma;
-    if (discount_pow) {
-      gd = 1.0;
-      for (int q = 0; q < s; ++q) gd *= gamma;  // the running product of the in-kernel form, same rounding
-    }
-    const double r = reward ? (double)reward[n] : 0.0;
-    delta[n] = r + gd * V[b * (T + 1) + s + 1] - V[b * (T + 1) + s];
-  }
-}
-
-
-// The row reduction + update of the IRL env step as a launch of its own (after an episode's LAST step; the other steps' reductions
-// ride in the next step kernel, k_core_small<.., STEP>): a wave per column, rows_column_sum -- the same order, the same bits.
-__global__ __launch_bounds__(BLOCK) void k_reduce_rows_apply(const double* __restrict__ rows, int nrows, int64_t FO, double* __restrict__ G,
-                                                            double lr_c, double lr_a, double count, double* __restrict__ w,
-                                                            const double* theta_in, double* theta_out,
-                                                            double* __restrict__ reward_acc) {
-  reduce_rows_apply_body(rows, nrows, FO, G, lr_c, lr_a, count, w, theta_in, theta_out, reward_acc);
-}
-
-// ---------------------------------------------------------------------------------------------
-// host side: launch helpers
-// ---------------------------------------------------------------------------------------------
-static int grid_for(int64_t work_items, int per_block, int blocks_per_cu) {
+int grid_for(int64_t work_items, int per_block, int blocks_per_cu) {
   int64_t g = (work_items + per_block - 1) / per_block;
   const int64_t cap = (int64_t)num_cus() * blocks_per_cu;
   if (g > cap) g = cap;
   if (g < 1) g = 1;
   return (int)g;
 }
-
-constexpr size_t MFG_WS_CONTROL_BYTES = 64;  // control block at the START of the workspace (completion counter), kept zero:
-                                              // a fixed place, whatever N a call is made with; partial rows follow it
-constexpr int MFG_GRAD_FUSE_MAX_ROWS = 32;   // in-kernel finalisation up to this many partial rows
-
-struct ApplyArgs {
-  double lr_c, lr_a;
-  double *w, *theta, *reward_acc;
-};
-// the update as a launch of its own (where no kernel applied it while it formed G)
-static void launch_apply_update(const double* G, int d, double lr_c, double lr_a, double* w, double* theta, double* reward_acc,
-                                hipStream_t st) {
-  const int64_t F = mfg_num_features(d);
-  hipLaunchKernelGGL(k_apply_update, dim3((unsigned)((F + 255) / 256)), dim3(256), 0, st, G, F, lr_c, lr_a, w, theta, reward_acc);
-}
-
-// Large-d rollouts evaluate the critic values of all states in one matrix-core pass after the rollout (k_value_mfma): room
-// for V[B (T+1)] <= 2 N doubles behind the partial rows of the gradient sums.
-static bool value_batch_ok(int d) { return d > WAVE && d % 16 == 0 && d <= MFG_MAX_D; }
-static size_t value_buffer_bytes(int64_t N, int d) { return value_batch_ok(d) ? (size_t)(2 * N) * 8 : 0; }
-
-static void grad_geometry(int64_t N, int d, int* chunk, int64_t* nsb, int* nob) {
-  const int64_t FO = mfg_num_features(d) + 3;
-  int ch = 8192 / d;
-  if (ch > 64) ch = 64;
-  if (ch < 8) ch = 8;
-  *chunk = ch;
-  int64_t sb = (N + ch - 1) / ch;
-#ifndef MFG_GRAD_WS_MB
-#define MFG_GRAD_WS_MB 72  // partial rows of the batch sums: 256 rows at d = 256 (one per CU; 32 MB until round 3)
-#endif
-  int64_t cap = (int64_t)((long long)MFG_GRAD_WS_MB << 20) / (FO * 8);
-  if (cap > 1024) cap = 1024;
-  if (cap < 16) cap = 16;
-  if (sb > cap) sb = cap;
-  if (sb < 1) sb = 1;
-  *nsb = sb;
-  *nob = (int)((FO + GR_OUT_PER_BLOCK - 1) / GR_OUT_PER_BLOCK);
-}
-
-// `apply` (optional): also perform the parameter update; *applied tells whether it was done in-kernel.
-static int launch_grad(const float* pi, int64_t stride_b, const double* delta, const double* g, const float* reward,
-                       int64_t N, int T, int d, double* G, int accumulate, void* ws, size_t ws_bytes, hipStream_t st,
-                       const ApplyArgs* apply = nullptr, bool* applied = nullptr, bool add_reward = false,
-                       const PopArgs* pop = nullptr) {
-  if (applied) *applied = false;
-  // FIRST, before anything can be launched: the d <= 28 kernel keeps a chunk's step counter s0 + j (s0 < T, j < 64) in a
-  // 32-bit int (tests/test_gpu_batch_sums_layouts.py calls with such a T over buffers that hold nothing)
-  if (d <= MFG_GRAD_SMALL_MAX_D && T > INT_MAX - GS_CH)
-    return fail(MFG_EUNSUPPORTED, "batch sums, d <= %d: T = %d above 2^31 - 65", MFG_GRAD_SMALL_MAX_D, T);
-  const int64_t FO = mfg_num_features(d) + 3;
-  int chunk, nob;
-  int64_t nsb;
-  grad_geometry(N, d, &chunk, &nsb, &nob);
-  const size_t need = (size_t)(nsb * FO * 8) + MFG_WS_CONTROL_BYTES;  // (the value buffer, if any, lies behind)
-  if (ws_bytes < need) return fail(MFG_EWORKSPACE, "%s: need %lld bytes, have %lld", "workspace", (long long)need,
-                                   (long long)ws_bytes);
-  // the parameter update, when asked for, rides in the kernel that finishes the sums (fixed-order; needs accumulate == 0
-  // so that the sample count is the host-known N)
-  ReduceApply rap{};
-  if (apply && !accumulate) {
-    rap.on = 1;
-    rap.lr_c = apply->lr_c;
-    rap.lr_a = apply->lr_a;
-    rap.count = (double)N;
-    rap.w = apply->w;
-    rap.theta = apply->theta;
-    rap.reward_acc = apply->reward_acc;
-  }
-  GradArgs a{};
-  a.pi = pi;
-  a.stride_b = stride_b;
-  a.delta = delta;
-  a.g = g;
-  a.reward = reward;
-  a.N = N;
-  a.T = T;
-  a.d = d;
-  a.chunk = chunk;
-  a.nsb = nsb;
-  a.partial = reinterpret_cast<double*>((char*)ws + MFG_WS_CONTROL_BYTES);
-  // (the small-d kernel folds delta += reward into its own load: every sample is read by exactly one wave there; the
-  //  other kernels read a sample from several blocks, so the update is a separate elementwise launch first)
-  const bool small = d <= MFG_GRAD_SMALL_MAX_D;
-  if (add_reward && !small)
-    hipLaunchKernelGGL(k_add_reward, dim3(grid_for(N, 256, 8)), dim3(256), 0, st, const_cast<double*>(delta), reward, N);
-  if (small) {
-    a.add_reward = add_reward ? 1 : 0;
-    // one partial row per block; nsb rows fit the workspace by construction (grad_geometry).  A wave works through chunks of
-    // 64 samples: one chunk per wave while the batch is small, then more chunks per wave (two blocks per CU at most)
-    const int64_t NC = (N + GS_CH - 1) / GS_CH;  // chunks of 64 samples, one wave each at a time
-    int64_t blocks = (NC + WAVES - 1) / WAVES;
-    const int64_t cap = (int64_t)num_cus() * MFG_GS_BPC;
-    if (blocks > cap) blocks = cap;
-    if (blocks > nsb) blocks = nsb;
-    if (blocks < 1) blocks = 1;
-    a.nsb = blocks;
-    // few rows (small batches, per-step updates): the last block to finish sums them (and applies the update) itself
-    const bool fuse = blocks <= MFG_GRAD_FUSE_MAX_ROWS;
-    if (fuse) {
-      a.counter = reinterpret_cast<unsigned*>(ws);
-      a.G = G;
-      a.accumulate = accumulate;
-      if (apply) {
-        a.apply = 1;
-        a.lr_c = apply->lr_c;
-        a.lr_a = apply->lr_a;
-        a.w = apply->w;
-        a.theta = apply->theta;
-        a.reward_acc = apply->reward_acc;
-        if (applied) *applied = true;
-      }
-    }
-    // 32-bit offsets and the fp32 step division inside a chunk: skipped part below 2^23 floats, T below 2^22
-    const bool wide = stride_b - (int64_t)T * d >= (1 << 23) || T >= MFG_GRAD_LONG_T;
-    if (pop) {  // (population: K learners side by side; `wide` never holds for the strides and lengths of a training episode)
-      if (wide) return fail(MFG_EUNSUPPORTED, "%s", "population: trajectory stride or length beyond the small gradient kernel");
-      launch_grad_mfma_small_pop(d == 21 || d == 15 ? d : 0, (unsigned)blocks, a, *pop, st);
-      if (fuse) return check_launch("grad_mfma_small_pop");
-      launch_reduce_partials_pop((unsigned)((FO + RP_OUT - 1) / RP_OUT), (const double*)a.partial, blocks, FO, G, rap, *pop, st);
-      if (applied && rap.on) *applied = true;
-      return check_launch("grad_mfma_small_pop");
-    }
-    if (wide) hipLaunchKernelGGL((k_grad_mfma_small<0, true>), dim3((unsigned)blocks), dim3(BLOCK), 0, st, a);
-    else if (d == 21) hipLaunchKernelGGL((k_grad_mfma_small<21>), dim3((unsigned)blocks), dim3(BLOCK), 0, st, a);
-    else if (d == 15) hipLaunchKernelGGL((k_grad_mfma_small<15>), dim3((unsigned)blocks), dim3(BLOCK), 0, st, a);
-    else hipLaunchKernelGGL((k_grad_mfma_small<0>), dim3((unsigned)blocks), dim3(BLOCK), 0, st, a);
-    if (fuse) return check_launch("grad_mfma_small");
-    hipLaunchKernelGGL(k_reduce_partials, dim3((unsigned)((FO + RP_OUT - 1) / RP_OUT)), dim3(RP_SLICES * RP_OUT), 0, st,
-                       (const double*)a.partial, blocks, FO, accumulate, G, rap);
-    if (applied && rap.on) *applied = true;
-    return check_launch("grad_mfma_small");
-  }
-  if (d % 16 == 0 && d >= 64 && d <= 4 * BLOCK) {
-    const int nt = d / 16, ntiles = nt * (nt + 1) / 2;
-    const int ny = (ntiles + WAVES * GM_TPW - 1) / (WAVES * GM_TPW);
-    const int tpw = (ntiles + ny * WAVES - 1) / (ny * WAVES);
-    a.chunk = (BLOCK % (d / 4) == 0 && (((uintptr_t)pi & 15) == 0) && (stride_b % 4 == 0)) ? 1 : 0;  // float4 staging
-    const size_t lds_m = (size_t)GM_KC * 8 + (size_t)4 * BLOCK * 8 + (size_t)GM_KC * (d + 16) * 4;
-    const int npf = a.chunk ? d / 32 : 0;
-    if (pop) {
-      if (npf != 0 && npf != 2) return fail(MFG_EUNSUPPORTED, "%s", "population: d > 64");
-      launch_grad_mfma_pop(npf, (unsigned)nsb, (unsigned)ny, lds_m, a, tpw, *pop, st);
-      launch_reduce_partials_pop((unsigned)((FO + RP_OUT - 1) / RP_OUT), (const double*)a.partial, nsb, FO, G, rap, *pop, st);
-      if (applied && rap.on) *applied = true;
-      return check_launch("grad_mfma_pop");
-    }
-#ifndef MFG_GRAD_MFMA_OLD
-    if (a.chunk && (d == 128 || d == 256)) {
-      // two resident blocks per CU (two waves per SIMD: the second hides the first one's staging and barriers)
-#ifndef MFG_GM2_BPC128
-#define MFG_GM2_BPC128 3  // 166 registers: three blocks per CU fit (measured 253 -> 236 us at C3)
-#endif
-      const int64_t want = d == 256 ? (int64_t)num_cus() * 2 / Gm2Geom<256>::NY : (int64_t)num_cus() * MFG_GM2_BPC128 / Gm2Geom<128>::NY;
-      if (nsb > want) nsb = want;
-      a.nsb = nsb;
-      if (d == 256) hipLaunchKernelGGL((k_grad_mfma2<256>), dim3((unsigned)nsb, (unsigned)Gm2Geom<256>::NY), dim3(BLOCK), lds_m, st, a);
-      else hipLaunchKernelGGL((k_grad_mfma2<128>), dim3((unsigned)nsb, (unsigned)Gm2Geom<128>::NY), dim3(BLOCK), lds_m, st, a);
-    } else
-#endif
-    switch (npf) {
-      case 2: hipLaunchKernelGGL((k_grad_mfma<2>), dim3((unsigned)nsb, (unsigned)ny), dim3(BLOCK), lds_m, st, a, tpw); break;
-      case 4: hipLaunchKernelGGL((k_grad_mfma<4>), dim3((unsigned)nsb, (unsigned)ny), dim3(BLOCK), lds_m, st, a, tpw); break;
-      case 8: hipLaunchKernelGGL((k_grad_mfma<8>), dim3((unsigned)nsb, (unsigned)ny), dim3(BLOCK), lds_m, st, a, tpw); break;
-      case 16: hipLaunchKernelGGL((k_grad_mfma<16>), dim3((unsigned)nsb, (unsigned)ny), dim3(BLOCK), lds_m, st, a, tpw); break;
-      default: hipLaunchKernelGGL((k_grad_mfma<0>), dim3((unsigned)nsb, (unsigned)ny), dim3(BLOCK), lds_m, st, a, tpw); break;
-    }
-    hipLaunchKernelGGL(k_reduce_partials, dim3((unsigned)((FO + RP_OUT - 1) / RP_OUT)), dim3(RP_SLICES * RP_OUT), 0, st,
-                       (const double*)a.partial, nsb, FO, accumulate, G, rap);
-    if (applied && rap.on) *applied = true;
-    return check_launch("grad_mfma");
-  }
-  const size_t lds = (size_t)chunk * 3 * 8 + (size_t)chunk * d * 4;
-  if (pop) {
-    launch_grad_partial_pop((unsigned)nsb, (unsigned)nob, lds, a, *pop, st);
-    launch_reduce_partials_pop((unsigned)((FO + RP_OUT - 1) / RP_OUT), (const double*)a.partial, nsb, FO, G, rap, *pop, st);
-    if (applied && rap.on) *applied = true;
-    return check_launch("grad_partial_pop");
-  }
-  hipLaunchKernelGGL(k_grad_partial, dim3((unsigned)nsb, (unsigned)nob), dim3(BLOCK), lds, st, a);
-  hipLaunchKernelGGL(k_reduce_partials, dim3((unsigned)((FO + RP_OUT - 1) / RP_OUT)), dim3(RP_SLICES * RP_OUT), 0, st,
-                     (const double*)a.partial, nsb, FO, accumulate, G, rap);
-  if (applied && rap.on) *applied = true;
-  return check_launch("grad_reduce");
-}
+}  // namespace mfg
 
 // ---- h(z) table (mfg_device.h): module-resident, fitted once per device in fp64 -------------------------
 __device__ float4 g_htab[HTAB_N];
@@ -1987,8 +275,7 @@ static int reduce_core_sums(int d, int64_t B, double* G, int accumulate, void* w
                                rap, *pop, st);
     return check_launch("core_sums_pop");
   }
-  hipLaunchKernelGGL(k_reduce_partials, dim3((unsigned)((FO + RP_OUT - 1) / RP_OUT)), dim3(RP_SLICES * RP_OUT), 0, st,
-                     (const double*)((char*)ws + MFG_WS_CONTROL_BYTES), nt, FO, accumulate, G, rap);
+  launch_reduce_partials((const double*)((char*)ws + MFG_WS_CONTROL_BYTES), nt, FO, accumulate, G, rap, st);
   return check_launch("core_sums");
 }
 
@@ -2159,21 +446,6 @@ size_t mfg_workspace_bytes(int64_t N, int d) {
   return (size_t)(nsb * (mfg_num_features(d) + 3) * 8) + MFG_WS_CONTROL_BYTES + value_buffer_bytes(N, d);
 }
 
-#define CHECK_BD()                                        \
-  REQUIRE(B >= 0, "B < 0");                               \
-  REQUIRE(d >= 1, "d < 1");                               \
-  if (d > MFG_MAX_D) return fail(MFG_EUNSUPPORTED, "%s: d=%lld > %lld", "shape", (long long)d, (long long)MFG_MAX_D); \
-  if (B == 0) return MFG_OK;
-
-int mfg_gather_start(const float* mat_pi0, int64_t num_start, const int32_t* idx, int64_t B, int d, float* pi0,
-                     mfg_stream_t stream) {
-  CHECK_BD();
-  REQUIRE(mat_pi0 && idx && pi0 && num_start > 0, "null pointer / empty table");
-  hipLaunchKernelGGL(k_gather_start, dim3(grid_for(B * d, 256, 8)), dim3(256), 0, S(stream), mat_pi0, num_start, idx, B,
-                     d, pi0);
-  return check_launch("gather_start");
-}
-
 int mfg_draw_start(const float* mat_pi0, int64_t num_start, int64_t B, int d, uint64_t seed, uint32_t step, uint64_t traj_offset,
                    int32_t* idx, float* pi0, mfg_stream_t stream) {
   CHECK_BD();
@@ -2181,49 +453,8 @@ int mfg_draw_start(const float* mat_pi0, int64_t num_start, int64_t B, int d, ui
   REQUIRE(idx || pi0, "nothing to write");
   REQUIRE(!pi0 || mat_pi0, "null start-state table");
   REQUIRE(traj_ids_ok(traj_offset, B), "trajectory ids traj_offset + B exceed 2^48 (MFG_TRAJ_ID_LIMIT)");
-  hipLaunchKernelGGL(k_draw_start, dim3(grid_for(pi0 ? B * d : B, 256, 8)), dim3(256), 0, S(stream), mat_pi0, num_start, B, d,
-                     seed, step, traj_offset, idx, pi0);
+  launch_draw_start(mat_pi0, num_start, B, d, seed, step, traj_offset, idx, pi0, S(stream));
   return check_launch("draw_start");
-}
-
-int mfg_alpha(const float* pi, int64_t B, int d, const double* theta, double shift, double* alpha, double* alpha_deriv,
-              mfg_stream_t stream) {
-  CHECK_BD();
-  REQUIRE(pi && theta && (alpha || alpha_deriv), "null pointer");
-  hipLaunchKernelGGL(k_alpha, dim3(grid_for(B * d * d, 256, 8)), dim3(256), 0, S(stream), pi, B, d, theta, shift, alpha,
-                     alpha_deriv);
-  return check_launch("alpha");
-}
-
-int mfg_dirichlet_from_gamma(const float* y, int64_t B, int d, float* P, mfg_stream_t stream) {
-  CHECK_BD();
-  REQUIRE(y && P, "null pointer");
-  hipLaunchKernelGGL(k_dirichlet_from_gamma, dim3(grid_for(B * d, WAVES, 8)), dim3(BLOCK), 0, S(stream), y, B * d, d, P);
-  return check_launch("dirichlet_from_gamma");
-}
-
-int mfg_philox_raw(uint64_t seed, uint32_t first_ctr, uint32_t c1, uint32_t c2, uint32_t c3, int64_t n, uint32_t* out,
-                   mfg_stream_t stream) {
-  REQUIRE(n >= 0 && (out || n == 0), "null pointer");
-  if (n == 0) return MFG_OK;
-  hipLaunchKernelGGL(k_philox_raw, dim3(grid_for(n, 256, 8)), dim3(256), 0, S(stream), seed, first_ctr, c1, c2, c3, n, out);
-  return check_launch("philox_raw");
-}
-
-// developer knob (tools/step_probe.py): MFG_STEP_BATCH = 0 | 8 | 16 | 32 forces the tiles per super tile of the d = 21 / 15
-// given-P kernel (0 = per-tile stores); unset / anything else = chosen from the batch size
-static int step_batch_override() {
-#ifdef MFG_DEV_KNOBS  // developer builds only (tools/variant.sh ... "-DMFG_DEV_KNOBS"): the shipped library reads no environment
-  static const int v = [] {
-    const char* e = getenv("MFG_STEP_BATCH");
-    if (!e || !*e) return -1;
-    const int k = atoi(e);
-    return (k == 0 || k == 8 || k == 16 || k == 32) ? k : -1;
-  }();
-  return v;
-#else
-  return -1;
-#endif
 }
 
 int mfg_step_given_P(const float* pi, const float* P, int64_t B, int d, int reward_kind, float* pi_next, float* reward,
@@ -2232,217 +463,7 @@ int mfg_step_given_P(const float* pi, const float* P, int64_t B, int d, int rewa
   REQUIRE(pi && P && pi_next, "null pointer");
   REQUIRE(reward_kind >= 0 && reward_kind <= 2, "bad reward_kind");
   if (!reward) reward_kind = MFG_REWARD_EXTERNAL;
-  hipStream_t st = S(stream);
-  if (d <= WAVE) {
-    const int G = WAVE / d, TB = WAVES * G;
-    const size_t lds_pre = (size_t)TB * d * d * 4 + (size_t)((TB * d + 3) & ~3) * 4;   // prefetching kernel (fp32 pi)
-    const size_t lds_una = (size_t)TB * d * d * 4 + (size_t)TB * d * 16;               // unaligned fallback (fp64 pi, pi^2)
-    const size_t lds = (((uintptr_t)P & 15) == 0) ? lds_pre : lds_una;
-    int bpc = (int)((160 * 1024) / (lds + 64));
-    if (bpc > 8) bpc = 8;
-    if (bpc < 1) bpc = 1;
-    const int grid = grid_for(B, TB, bpc);
-    const bool aligned = (((uintptr_t)P & 15) == 0);
-    const int per = (int)(((int64_t)TB * d * d / 4 + BLOCK - 1) / BLOCK);  // 16-byte loads per thread per tile
-#define STEP_SMALL(K, DD, PP) \
-  hipLaunchKernelGGL((k_step_small<K, DD, PP>), dim3(grid), dim3(BLOCK), lds, st, pi, P, B, d, pi_next, reward)
-#define STEP_SMALL_D(DD, PP)                 \
-  switch (reward_kind) {                     \
-    case 0: STEP_SMALL(0, DD, PP); break;    \
-    case 1: STEP_SMALL(1, DD, PP); break;    \
-    default: STEP_SMALL(2, DD, PP); break;   \
-  }
-    if (!aligned) {
-      switch (reward_kind) {
-        case 0: hipLaunchKernelGGL((k_step_small_unaligned<0>), dim3(grid), dim3(BLOCK), lds, st, pi, P, B, d, pi_next, reward); break;
-        case 1: hipLaunchKernelGGL((k_step_small_unaligned<1>), dim3(grid), dim3(BLOCK), lds, st, pi, P, B, d, pi_next, reward); break;
-        default: hipLaunchKernelGGL((k_step_small_unaligned<2>), dim3(grid), dim3(BLOCK), lds, st, pi, P, B, d, pi_next, reward); break;
-      }
-    } else if (d == 21 || d == 15) {
-#ifdef MFG_STEP_BLOCK_TILES
-      if (d == 21) { STEP_SMALL_D(21, 6) } else { STEP_SMALL_D(15, 4) }
-#else
-      // The main launch covers B4 = B - B mod lcm(G, 4) trajectories (full tiles only and a whole number of 16-byte words
-      // of P, so its prefetch needs no partial-tile / end-of-slab handling); the remaining < 12 trajectories go through
-      // the ragged-capable instantiation.
-      const int G = WAVE / d;
-      const int64_t unit = (G % 4 == 0) ? G : (G % 2 == 0 ? 2 * G : 4 * G);
-      const int64_t B4 = B - B % unit;
-#define STEP_WAVE(K, DD, RAG, GRID, PI, PP, NB, PN, RW) \
-  hipLaunchKernelGGL((k_step_wave<K, DD, RAG>), dim3(GRID), dim3(BLOCK), 0, st, PI, PP, NB, PN, RW)
-#define STEP_WAVE_K(DD, RAG, GRID, PI, PP, NB, PN, RW)                    \
-  switch (reward_kind) {                                                   \
-    case 0: STEP_WAVE(0, DD, RAG, GRID, PI, PP, NB, PN, RW); break;        \
-    case 1: STEP_WAVE(1, DD, RAG, GRID, PI, PP, NB, PN, RW); break;        \
-    default: STEP_WAVE(2, DD, RAG, GRID, PI, PP, NB, PN, RW); break;       \
-  }
-      if (B4 > 0) {
-        // Large batches: consecutive-tile super tiles with batched device-scope stores (k_step_wave_batched), as soon as
-        // every one of the 8 waves per CU gets >= 2 super tiles; KB = tiles per super tile, the largest that qualifies.
-        const int64_t ntiles = (B4 + G - 1) / G;
-        const int64_t nw_target = (int64_t)num_cus() * 2 * WAVES;
-        int kb = 0;
-        for (int cand : {32, 16, 8}) {  // >= 2 super tiles per wave, and the last round >= 90 % full
-          const int64_t ns = (ntiles + cand - 1) / cand, rr = (ns + nw_target - 1) / nw_target;
-          if (!kb && rr >= 2 && 10 * ns >= 9 * rr * nw_target) kb = cand;
-        }
-        const int forced = step_batch_override();  // developer knob: MFG_STEP_BATCH = 0 (never) | 8 | 16 | 32
-        if (forced >= 0) kb = forced;
-        const bool out16 = (((uintptr_t)pi_next & 15) == 0) && (((uintptr_t)reward & 15) == 0);
-        if (kb && out16) {
-          const int64_t nsuper = (ntiles + kb - 1) / kb;
-          const int64_t rounds = (nsuper + nw_target - 1) / nw_target;
-          const int64_t nwv = (nsuper + rounds - 1) / rounds;
-          const int gb = (int)((nwv + WAVES - 1) / WAVES);
-#define STEP_WAVE_B(K, DD, KB) \
-  hipLaunchKernelGGL((k_step_wave_batched<K, DD, KB>), dim3(gb), dim3(BLOCK), 0, st, pi, P, B4, pi_next, reward)
-#define STEP_WAVE_BK(DD, KB)                    \
-  switch (reward_kind) {                        \
-    case 0: STEP_WAVE_B(0, DD, KB); break;      \
-    case 1: STEP_WAVE_B(1, DD, KB); break;      \
-    default: STEP_WAVE_B(2, DD, KB); break;     \
-  }
-          if (d == 21) {
-            if (kb == 32) { STEP_WAVE_BK(21, 32) } else if (kb == 16) { STEP_WAVE_BK(21, 16) } else { STEP_WAVE_BK(21, 8) }
-          } else {
-            if (kb == 32) { STEP_WAVE_BK(15, 32) } else if (kb == 16) { STEP_WAVE_BK(15, 16) } else { STEP_WAVE_BK(15, 8) }
-          }
-#undef STEP_WAVE_BK
-#undef STEP_WAVE_B
-        } else {
-          const int gw = grid_for(B4, G * WAVES, MFG_STEP_WAVES);
-          if (d == 21) { STEP_WAVE_K(21, false, gw, pi, P, B4, pi_next, reward) }
-          else { STEP_WAVE_K(15, false, gw, pi, P, B4, pi_next, reward) }
-        }
-      }
-      if (B > B4) {
-        const float* pi_t = pi + B4 * d;
-        const float* P_t = P + B4 * d * d;   // 16-byte aligned: B4 is a multiple of 4
-        float* pn_t = pi_next + B4 * d;
-        float* rw_t = reward ? reward + B4 : nullptr;
-        const int64_t Bt = B - B4;
-        if (d == 21) { STEP_WAVE_K(21, true, 1, pi_t, P_t, Bt, pn_t, rw_t) }
-        else { STEP_WAVE_K(15, true, 1, pi_t, P_t, Bt, pn_t, rw_t) }
-      }
-#undef STEP_WAVE_K
-#undef STEP_WAVE
-#endif
-    }
-    else if (per <= 4) { STEP_SMALL_D(0, 4) }
-    else if (per <= 8) { STEP_SMALL_D(0, 8) }
-    else { STEP_SMALL_D(0, 16) }
-#undef STEP_SMALL_D
-#undef STEP_SMALL
-  } else {
-    const size_t lds = (size_t)WAVES * d * 4;
-    const int grid = grid_for(B, WAVES, (d == 128 || d == 256) ? MFG_ROWS_BPC : 8);
-    const bool a16 = (((uintptr_t)P & 15) == 0) && (((uintptr_t)pi_next & 15) == 0);
-    int vec = 1;
-    if (a16 && d % 4 == 0) vec = 4;
-    else if (a16 && d % 2 == 0) vec = 2;
-    // keep at most 2 chunks per lane on the vector paths, fall back to narrower vectors otherwise
-    int R = (d + WAVE * vec - 1) / (WAVE * vec);
-#define STEP_ROWS(L, KT, GRID)                                                                                                \
-  switch (reward_kind) {                                                                                                       \
-    case 0: hipLaunchKernelGGL((k_step_rows<0, L, KT>), dim3(GRID), dim3(BLOCK), 0, st, pi, P, B, pi_next, reward); break;     \
-    case 1: hipLaunchKernelGGL((k_step_rows<1, L, KT>), dim3(GRID), dim3(BLOCK), 0, st, pi, P, B, pi_next, reward); break;     \
-    default: hipLaunchKernelGGL((k_step_rows<2, L, KT>), dim3(GRID), dim3(BLOCK), 0, st, pi, P, B, pi_next, reward); break;    \
-  }
-    if (a16 && (d == 128 || d == 256)) {
-      // super tiles of MFG_ROWS_KT consecutive trajectories (batched output bursts) once every resident wave gets one
-      const bool out16 = (((uintptr_t)pi_next & 15) == 0) && (((uintptr_t)reward & 15) == 0);
-      const int64_t nw_target = (int64_t)num_cus() * MFG_ROWS_BPC * WAVES;
-      // ... and the last round is >= 90 % full (a half-empty round of 8-trajectory units costs more than the bursts save:
-      // 20 000 trajectories ran at 0.70 of peak as 2 500 super tiles over two rounds, 0.78 one trajectory at a time)
-      int kt = 1;
-      if (out16) {
-        const int64_t ns8 = (B + MFG_ROWS_KT - 1) / MFG_ROWS_KT, rr8 = (ns8 + nw_target - 1) / nw_target;
-        if (ns8 >= nw_target && 10 * ns8 >= 9 * rr8 * nw_target) kt = MFG_ROWS_KT;
-      }
-      const int64_t nsup = (B + kt - 1) / kt;
-      const int64_t rounds = (nsup + nw_target - 1) / nw_target;
-      const int gr = (int)(((nsup + rounds - 1) / rounds + WAVES - 1) / WAVES);
-      if (d == 128) {
-        if (kt > 1) { STEP_ROWS(32, MFG_ROWS_KT, gr) } else { STEP_ROWS(32, 1, gr) }
-      } else {
-        if (kt > 1) { STEP_ROWS(64, MFG_ROWS_KT, gr) } else { STEP_ROWS(64, 1, gr) }
-      }
-      return check_launch("step_given_P");
-    }
-#undef STEP_ROWS
-#define STEP_LARGE(V, RR, K) \
-  hipLaunchKernelGGL((k_step_large<V, RR, K>), dim3(grid), dim3(BLOCK), lds, st, pi, P, B, d, pi_next, reward)
-#define STEP_LARGE_K(V, RR)                      \
-  switch (reward_kind) {                         \
-    case 0: STEP_LARGE(V, RR, 0); break;         \
-    case 1: STEP_LARGE(V, RR, 1); break;         \
-    default: STEP_LARGE(V, RR, 2); break;        \
-  }
-    if (vec == 4 && R == 1) { STEP_LARGE_K(4, 1) }
-    else if (vec == 4 && R == 2) { STEP_LARGE_K(4, 2) }
-    else if (vec == 2 && R == 1) { STEP_LARGE_K(2, 1) }
-    else if (vec == 2 && R == 2) { STEP_LARGE_K(2, 2) }
-    else if (vec == 2 && R == 3) { STEP_LARGE_K(2, 3) }
-    else if (vec == 2 && R == 4) { STEP_LARGE_K(2, 4) }
-    else {
-      R = (d + WAVE - 1) / WAVE;
-      switch (R) {
-        case 2: STEP_LARGE_K(1, 2) break;
-        case 3: STEP_LARGE_K(1, 3) break;
-        case 4: STEP_LARGE_K(1, 4) break;
-        case 5: STEP_LARGE_K(1, 5) break;
-        case 6: STEP_LARGE_K(1, 6) break;
-        case 7: STEP_LARGE_K(1, 7) break;
-        case 8: STEP_LARGE_K(1, 8) break;
-        default: return fail(MFG_EUNSUPPORTED, "%s: d=%lld > %lld", "step", (long long)d, (long long)MFG_MAX_D);
-      }
-    }
-#undef STEP_LARGE_K
-#undef STEP_LARGE
-  }
-  return check_launch("step_given_P");
-}
-
-int mfg_value(const float* pi, const double* w, int64_t B, int d, double* value, mfg_stream_t stream) {
-  CHECK_BD();
-  REQUIRE(pi && w && value, "null pointer");
-  hipLaunchKernelGGL(k_value, dim3(grid_for(B, WAVES, 8)), dim3(BLOCK), 0, S(stream), pi, w, B, d, value);
-  return check_launch("value");
-}
-
-int mfg_features(const float* pi, int64_t B, int d, double* phi, mfg_stream_t stream) {
-  CHECK_BD();
-  REQUIRE(pi && phi, "null pointer");
-  hipLaunchKernelGGL(k_features, dim3(grid_for(B * d * d, 256, 8)), dim3(256), 0, S(stream), pi, B, d, phi);
-  return check_launch("features");
-}
-
-int mfg_backward_value(const float* P, int64_t B, int T, int d, double* V, double* diff_l1, double* diff_jsd,
-                       mfg_stream_t stream) {
-  CHECK_BD();
-  REQUIRE(T >= 1, "T < 1");
-  REQUIRE(P && V && diff_l1, "null pointer");
-  hipLaunchKernelGGL(k_backward_value, dim3(grid_for(B, WAVES, 8)), dim3(BLOCK), (size_t)WAVES * 2 * d * 8, S(stream), P,
-                     B, T, d, V, diff_l1, diff_jsd);
-  return check_launch("backward_value");
-}
-
-int mfg_jsd(const float* p, const float* q, int64_t B, int d, double* out, mfg_stream_t stream) {
-  REQUIRE(B >= 0 && d >= 1, "bad shape");
-  if (B == 0) return MFG_OK;
-  REQUIRE(p && q && out, "null pointer");
-  hipLaunchKernelGGL(k_jsd, dim3(grid_for(B, WAVES, 8)), dim3(BLOCK), 0, S(stream), p, q, B, d, out);
-  return check_launch("jsd");
-}
-
-int mfg_policy_logpdf(const float* pi, const float* P, int64_t N, int d, const double* thetas, int K, double shift,
-                      double alpha_scale, double alpha_floor, double p_floor, double* out, mfg_stream_t stream) {
-  const int64_t B = N;
-  CHECK_BD();
-  REQUIRE(pi && P && thetas && out && K >= 1, "null pointer / K < 1");
-  hipLaunchKernelGGL(k_policy_logpdf, dim3(grid_for(N * K, WAVES, 8)), dim3(BLOCK), 0, S(stream), pi, P, N, d, thetas, K,
-                     shift, alpha_scale, alpha_floor, p_floor, out);
-  return check_launch("policy_logpdf");
+  return launch_step_given_P(pi, P, B, d, reward_kind, pi_next, reward, S(stream));
 }
 
 #define CHECK_PRECISION() REQUIRE(precision == MFG_PRECISION_F64 || precision == MFG_PRECISION_MIXED, "bad precision")
@@ -2524,35 +545,6 @@ int mfg_apply_update(const double* G, int d, double lr_critic, double lr_actor, 
   return check_launch("apply_update");
 }
 
-// After a TD rollout that skipped the in-kernel values (large d): V of all B (T+1) states, then delta.
-static int launch_values_and_delta(const float* pi_traj, int64_t B, int T, int d, const double* w, const float* reward,
-                                   double gamma, int discount_pow, double* delta, void* ws, size_t ws_bytes, hipStream_t st) {
-  const int64_t N = B * T, NV = B * (int64_t)(T + 1);
-  int chunk, nob;
-  int64_t nsb;
-  grad_geometry(N, d, &chunk, &nsb, &nob);
-  const size_t off = (size_t)(nsb * (mfg_num_features(d) + 3) * 8) + MFG_WS_CONTROL_BYTES;
-  if (!ws || ws_bytes < off + (size_t)NV * 8)
-    return fail(MFG_EWORKSPACE, "%s: need %lld bytes, have %lld", "values", (long long)(off + (size_t)NV * 8), (long long)ws_bytes);
-  double* V = reinterpret_cast<double*>((char*)ws + off);
-  const size_t lds = (size_t)WAVES * 16 * (d + 4) * 4 + (size_t)2 * VM_CH * 16 * 8;  // state rows + two pieces of U
-  int64_t groups = (NV + 15) / 16;
-  int64_t blocks = (groups + WAVES - 1) / WAVES;
-  const int64_t cap = (int64_t)num_cus() * 8;
-  if (blocks > cap) blocks = cap;
-#ifndef MFG_VALUE_MFMA_OLD
-  if (d % 64 == 0) {
-    const size_t lds2 = (size_t)VM2_KC * 64 * 8 + (size_t)VM2_MB * VM2_XP * 4;
-    int64_t blocks2 = (NV + VM2_MB - 1) / VM2_MB;
-    if (blocks2 > (int64_t)num_cus() * 2) blocks2 = (int64_t)num_cus() * 2;
-    hipLaunchKernelGGL(k_value_mfma2, dim3((unsigned)blocks2), dim3(BLOCK), lds2, st, pi_traj, (int64_t)(T + 1) * d, NV, T + 1, d, w, V);
-  } else
-#endif
-  hipLaunchKernelGGL(k_value_mfma, dim3((unsigned)blocks), dim3(BLOCK), lds, st, pi_traj, (int64_t)(T + 1) * d, NV, T + 1, d, w, V);
-  hipLaunchKernelGGL(k_td_delta, dim3(grid_for(N, 256, 8)), dim3(256), 0, st, (const double*)V, reward, B, T, gamma, discount_pow,
-                     delta);
-  return check_launch("values");
-}
 // whether a TD rollout can defer its values to k_value_mfma
 static bool defer_values(int d, int64_t B, int T, const float* pi_traj, const void* ws, size_t ws_bytes) {
   if (!value_batch_ok(d) || !pi_traj || !ws || (((uintptr_t)pi_traj & 15) != 0)) return false;
@@ -2665,9 +657,7 @@ static int train_rollout_impl(const float* mat_pi0, int64_t num_start, const int
       a.w_out = du->w_out;
     } else {
       // wave-per-trajectory kernels read the weights from memory throughout: apply the update out of place first
-      const int64_t F = mfg_num_features(d);
-      hipLaunchKernelGGL(k_apply_update_oop, dim3((unsigned)((F + 255) / 256)), dim3(256), 0, st, du->G, F, du->lr_c, du->lr_a,
-                         (const double*)w, (const double*)theta, du->w_out, du->theta_out, du->reward_acc);
+      launch_apply_update_oop(du->G, d, du->lr_c, du->lr_a, w, theta, du->w_out, du->theta_out, du->reward_acc, st);
       theta = du->theta_out;
       w = du->w_out;
     }
@@ -3060,8 +1050,7 @@ int mfg_train_episodes(const float* mat_pi0, int64_t num_start, float* pi_io, fl
   REQUIRE((uint64_t)first_step + (uint64_t)episodes * (uint64_t)T <= 0xFFFFFFFFull, "Philox step counter would wrap");
   for (int64_t k = 0; k < episodes; ++k) {
     const uint32_t step0 = first_step + (uint32_t)(k * T);
-    hipLaunchKernelGGL(k_draw_start, dim3(grid_for(B * d, 256, 8)), dim3(256), 0, S(stream), mat_pi0, num_start, B, d, seed, step0,
-                       traj_offset, (int32_t*)nullptr, pi_io);
+    launch_draw_start(mat_pi0, num_start, B, d, seed, step0, traj_offset, nullptr, pi_io, S(stream));
     double sc, sa;
     lr_schedule(first_episode + k, constant, &sc, &sa);
     const int rc = train_episode_impl(pi_io, pi_scratch, B, d, T, theta, shift, alpha_scale, w, gamma, reward_kind, seed, step0,
@@ -3569,15 +1558,6 @@ static IrlStepWs irl_step_ws(void* workspace, int64_t B, int d) {
   return l;
 }
 
-// the row reduction + update that closes a step-mode episode (population: learner k's theta_in at k pop->s_theta_b bytes)
-static void launch_reduce_rows_apply(const double* rows, int nrows, int64_t FO, double* G, double lr_c, double lr_a, double count,
-                                     double* w, const double* theta_in, double* theta_out, double* reward_acc, hipStream_t st,
-                                     const PopArgs* pop) {
-  if (pop) launch_reduce_rows_apply_pop(rows, nrows, FO, G, count, w, theta_in, theta_out, reward_acc, *pop, st);
-  else hipLaunchKernelGGL(k_reduce_rows_apply, dim3((unsigned)((FO + WAVES - 1) / WAVES)), dim3(BLOCK), 0, st, rows, nrows, FO,
-                          G, lr_c, lr_a, count, w, theta_in, theta_out, reward_acc);
-}
-
 // One step-mode episode, two launches per env step where the matrix-core reward-network kernel serves (d = 21 / 15, n_fc3 <= 16;
 // the caller asked reward_net_sums_td_ready / reward_net_pop_ready and checked the room for irl_step_ws):
 //   step kernel (STEP variant): sampling + transition + score with theta formed from the PREVIOUS step's partial rows by
@@ -3692,8 +1672,7 @@ static int train_episode_irl_3launch(const float* mat_pi0, int64_t num_start, fl
   float* nxt = pi_scratch;
   double discount = 1.0;
   if (mat_pi0) {
-    hipLaunchKernelGGL(k_draw_start, dim3(grid_for(B * d, 256, 8)), dim3(256), 0, st, mat_pi0, num_start, B, d, seed, first_step,
-                       traj_offset, (int32_t*)nullptr, pi_io);
+    launch_draw_start(mat_pi0, num_start, B, d, seed, first_step, traj_offset, nullptr, pi_io, st);
     const int rc = check_launch("draw_start");
     if (rc != MFG_OK) return rc;
   }
@@ -3738,8 +1717,7 @@ static int train_episode_irl_3launch(const float* mat_pi0, int64_t num_start, fl
       rap.w = w;
       rap.theta = theta;
       rap.reward_acc = reward_acc;
-      hipLaunchKernelGGL(k_reduce_partials, dim3((unsigned)((FO + RP_OUT - 1) / RP_OUT)), dim3(RP_SLICES * RP_OUT), 0, st,
-                         (const double*)sm.part_rows, (int64_t)rows, FO, 0, G, rap);
+      launch_reduce_partials(sm.part_rows, rows, FO, 0, G, rap, st);
       applied = true;
       rc = check_launch("irl_sums");
     } else {

@@ -18,7 +18,6 @@
 // that this kernel also stores to could be fetched through the scalar data cache, which does not see the kernel's own vector
 // stores.  States and partial rows are written and re-read with per-lane (vector) accesses on both sides of a barrier.
 #include "mfg_core.h"
-#define MFG_GRAD_BODIES_ONLY
 #include "mfg_grad.h"
 #include "mfg_population.h"
 

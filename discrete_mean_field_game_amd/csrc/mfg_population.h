@@ -5,7 +5,7 @@
 // argument block to learner k (pointers moved by k x their per-learner stride, the per-learner scalars read from device arrays
 // [K]) and then runs the body of the single kernel unchanged, so the summation trees and the Philox keys (trajectory ids
 // traj_offset .. traj_offset + Bk - 1 under the learner's seed) are those of a single-learner call: the same bits.  The
-// kernels are in mfg_population.hip and mfg_evaluate_pop.hip, the episode loops in mfg_kernels.hip.
+// kernels are in mfg_population.hip, mfg_population_ctl.hip and mfg_evaluate_pop.hip, the episode loops in mfg_kernels.hip.
 //
 // Retiring learners (mfg_ctx_set_pop_control, include/mfg_hip.h): with a control block every training launch carries the learners'
 // activity state [K] (PopArgs::state) and runs the _ctl form of each wrapper, which returns before the single kernel's body when
@@ -100,10 +100,11 @@ __device__ __forceinline__ CoreArgs pop_core_args(const CoreArgs& a, const PopAr
   return b;
 }
 
-// launchers (mfg_population.hip, mfg_evaluate_pop.hip); grids as the single launches of one learner, times K.  launch_core_pop:
+// launchers (mfg_population.hip, mfg_population_ctl.hip, mfg_evaluate_pop.hip); grids as the single launches of one learner, times K.  launch_core_pop:
 // training (sampling + TD); the variant follows the arguments as in launch_core_small: part_rows -> SUMS, step_nrows > 0 ->
 // STEP 1, < 0 -> STEP 2.  launch_eval_rollout_pop: sampling without TD (mfg_evaluate_pop.h).
 int launch_core_pop(const CoreArgs& a, const PopArgs& p, bool fast, int num_cus, hipStream_t st);
+int launch_core_pop_ctl(const CoreArgs& a, const PopArgs& p, bool fast, int num_cus, hipStream_t st);  // (its p.state half: mfg_population_ctl.hip)
 int launch_eval_rollout_pop(const CoreArgs& a, const PopArgs& p, bool fast, int num_cus, hipStream_t st);
 void launch_draw_start_pop(int grid, const float* mat, int64_t num_start, int64_t B, int d, uint32_t step, uint64_t traj_offset,
                            float* out, const PopArgs& p, hipStream_t st);

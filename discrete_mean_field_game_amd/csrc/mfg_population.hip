@@ -9,74 +9,18 @@
 // nothing for the test (measured: in the shared form it cost the step-mode episodes up to 7 %).  The pairs are written out and
 // not folded into one inlined function with a compile-time flag: passing the argument blocks through such a function changed
 // the register allocation and the schedule of the plain forms (tools/kernel_isa_diff.py; docs/HISTORY.md has the table).
+// The packed core kernel's pair is written out in mfg_population_core.h; its _ctl half is instantiated by mfg_population_ctl.hip,
+// a translation unit of its own (the two halves compile side by side).
 #include "mfg_core.h"
-#define MFG_GRAD_BODIES_ONLY
 #include "mfg_grad.h"
 #include "mfg_population.h"
+#include "mfg_population_core.h"
 
 namespace mfg {
 
-// ---- packed core kernel: sampling, transition, value, TD error, score of learner blockIdx.y; SUMS: the tile's batch-sum rows;
-//      STEP 1 / 2: an IRL env step (external reward, P materialised) ----
-#define MFG_CORE_POP_BOUNDS __launch_bounds__(BLOCK, SUMS ? 2 : (FAST ? MFG_CORE_SMALL_WAVES : MFG_CORE_SMALL_WAVES_F64))
-template <bool FAST, int D, bool SUMS, int STEP>
-__global__ MFG_CORE_POP_BOUNDS void k_core_pop(CoreArgs a, PopArgs p) {
-  core_small_body<true, true, FAST, D, SUMS, STEP>(pop_core_args<SUMS, STEP>(a, p, blockIdx.y));
-}
-template <bool FAST, int D, bool SUMS, int STEP>
-__global__ MFG_CORE_POP_BOUNDS void k_core_pop_ctl(CoreArgs a, PopArgs p) {
-  if (pop_retired(p, blockIdx.y)) return;
-  core_small_body<true, true, FAST, D, SUMS, STEP>(pop_core_args<SUMS, STEP, true>(a, p, blockIdx.y));
-}
-#undef MFG_CORE_POP_BOUNDS
-
-template <bool FAST, int D, bool SUMS, int STEP>
-static void go_pop(const CoreArgs& a, const PopArgs& p, int num_cus, size_t lds, hipStream_t st) {
-  const int red = STEP == 1 ? core_step_red_blocks(a.d * (a.d + 1) / 2 + a.d + 1 + 3) : 0;
-  if (p.state) {
-    const int grid = core_small_grid<k_core_pop_ctl<FAST, D, SUMS, STEP>>(a, lds, num_cus) + red;
-    hipLaunchKernelGGL((k_core_pop_ctl<FAST, D, SUMS, STEP>), dim3((unsigned)grid, (unsigned)p.K), dim3(BLOCK), lds, st, a, p);
-  } else {
-    const int grid = core_small_grid<k_core_pop<FAST, D, SUMS, STEP>>(a, lds, num_cus) + red;
-    hipLaunchKernelGGL((k_core_pop<FAST, D, SUMS, STEP>), dim3((unsigned)grid, (unsigned)p.K), dim3(BLOCK), lds, st, a, p);
-  }
-}
-
-// (as dispatch<D> in mfg_core_small.hip, sampling + TD only)
-template <int D>
-static void dispatch_pop(const CoreArgs& a, const PopArgs& p, bool fast, int num_cus, size_t lds, hipStream_t st) {
-  if constexpr (D > 0) {
-    if (a.step_nrows > 0) {
-      if (fast) go_pop<true, D, false, 1>(a, p, num_cus, lds, st);
-      else go_pop<false, D, false, 1>(a, p, num_cus, lds, st);
-      return;
-    }
-    if (a.step_nrows < 0) {
-      if (fast) go_pop<true, D, false, 2>(a, p, num_cus, lds, st);
-      else go_pop<false, D, false, 2>(a, p, num_cus, lds, st);
-      return;
-    }
-    if (a.part_rows) {
-      if (fast) go_pop<true, D, true, 0>(a, p, num_cus, lds, st);
-      else go_pop<false, D, true, 0>(a, p, num_cus, lds, st);
-      return;
-    }
-  }
-  if (fast) go_pop<true, D, false, 0>(a, p, num_cus, lds, st);
-  else go_pop<false, D, false, 0>(a, p, num_cus, lds, st);
-}
-
-// Always the packed lane mapping: k_core_row3 is for batches that under-fill the machine, a population fills it (both
-// mappings give the same bits).  Training launches only (sampling + TD).
+// ---- packed core kernel (mfg_population_core.h): the plain forms here, the _ctl forms in mfg_population_ctl.hip ----
 int launch_core_pop(const CoreArgs& a, const PopArgs& p, bool fast, int num_cus, hipStream_t st) {
-  const int d = a.d;
-  if (d > WAVE) return MFG_EUNSUPPORTED;
-  const size_t lds = core_small_lds(d, a.w != nullptr, true);
-  if (d == 21) dispatch_pop<21>(a, p, fast, num_cus, lds, st);
-  else if (d == 15) dispatch_pop<15>(a, p, fast, num_cus, lds, st);
-  else if (!a.part_rows && a.step_nrows == 0) dispatch_pop<0>(a, p, fast, num_cus, lds, st);
-  else return MFG_EUNSUPPORTED;  // (SUMS rows and the STEP variants: compile-time d only)
-  return MFG_OK;
+  return p.state ? launch_core_pop_ctl(a, p, fast, num_cus, st) : launch_core_pop_forms<false>(a, p, fast, num_cus, st);
 }
 
 // ---- start-state draw (a9) of learner blockIdx.y ----

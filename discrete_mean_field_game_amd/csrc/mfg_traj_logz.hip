@@ -4,7 +4,7 @@
 // leaves commented out).  The reference multiplies 15 d Dirichlet densities in linear space over a hand-picked normaliser
 // c = 2e11, which overflows; here everything stays in log space and in fp64:
 //     log_z[k, row] = ln n_pol - logsumexp_p( sum_t ln q_{theta[k,p]}(a_t; s_t) - log_start ).
-// ln q is the formula of k_policy_logpdf (mfg_kernels.hip) with its alpha_floor / p_floor clamps and its device helpers.
+// ln q is the formula of k_policy_logpdf (mfg_launch_once.hip) with its alpha_floor / p_floor clamps and its device helpers.
 //
 // One launch, no host read: block (x = listed row, y = learner), one wavefront per policy (a loop when there are more
 // policies than waves).  The per-policy sums of a round meet in LDS and one thread folds them into a running logsumexp in

@@ -1,4 +1,4 @@
-"""-m gpu: the launch-once kernels of csrc/mfg_kernels.hip (k_value, k_features, k_alpha, k_jsd, k_policy_logpdf,
+"""-m gpu: the launch-once kernels of csrc/mfg_launch_once.hip (k_value, k_features, k_alpha, k_jsd, k_policy_logpdf,
 k_backward_value, k_dirichlet_from_gamma, k_gather_start, k_draw_start, k_philox_raw, k_apply_update) past the grid cap and
 past the 64-lane width, against the NumPy oracles.
 

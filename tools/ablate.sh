@@ -5,16 +5,12 @@
 R=$(cd "$(dirname "$0")/.." && pwd); C=$R/discrete_mean_field_game_amd/csrc; V=${MFG_VARIANT_DIR:-$C/variants}
 ABL="PHILOX BM SETUP TRY HTAB LNY EPI COLREW V COLT TSUM"
 if [ "$1" = build ]; then
-  mkdir -p $V
   for a in $ABL; do
-    ( ( /opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -ffp-contract=on -Wno-pass-failed -fno-slp-vectorize -mllvm -amdgpu-sched-strategy=iterative-ilp -DMFG_ABL_$a -c -o $V/abl_$a.o $C/mfg_core_small.hip 2>/dev/null ||
-        /opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -ffp-contract=on -Wno-pass-failed -fno-slp-vectorize -DMFG_ABL_$a -c -o $V/abl_$a.o $C/mfg_core_small.hip ) &&
-      /opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -ffp-contract=on -Wno-pass-failed -fno-slp-vectorize -DMFG_ABL_$a -c -o $V/abll_$a.o $C/mfg_core_large_mixed.hip &&
-      /opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -ffp-contract=on -Wno-pass-failed -fno-slp-vectorize -mllvm -amdgpu-sched-strategy=iterative-ilp -DMFG_ABL_$a -c -o $V/ablli_$a.o $C/mfg_core_large_mixed_ilp.hip &&
-      /opt/rocm/bin/hipcc -shared -fPIC --offload-arch=gfx950 -o $V/libabl_$a.so $C/mfg_kernels.o $V/abl_$a.o $C/mfg_core_row3.o $C/mfg_core_large_f64.o $V/abll_$a.o $V/ablli_$a.o $C/mfg_reward_net.o $C/mfg_reward_train.o ) &
-    if (( $(jobs -r | wc -l) >= 5 )); then wait -n; fi
+    # the three mixed-precision sampling units carry the switch.  Where the iterative-ILP scheduler fails on an ablated body,
+    # the second call builds what is still missing without it (ILP= empties that flag group of csrc/Makefile).
+    M="make -C $C -j${MFG_JOBS:-16} O=$V/abl_$a.obj OUT=$V/libabl_$a.so EXTRA_mfg_core_small=-DMFG_ABL_$a EXTRA_mfg_core_large_mixed=-DMFG_ABL_$a EXTRA_mfg_core_large_mixed_ilp=-DMFG_ABL_$a"
+    $M >/dev/null 2>&1 || $M ILP= >/dev/null
   done
-  wait
   ls $V
 else
   S=${2:-21,65536,15}

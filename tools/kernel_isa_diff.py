@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Compare the gfx950 kernels of two builds of libmfg_hip.so, kernel by kernel (CPU only).
 
-For every kernel symbol of build A: its instruction listing (addresses and encodings stripped) and its
+For every kernel symbol of build A: its instruction listing (addresses, encodings and trailing padding stripped) and its
 .vgpr_count / .sgpr_count / .private_segment_fixed_size against the kernel of the same name in build B.
 
     python tools/kernel_isa_diff.py A/libmfg_hip.so B/libmfg_hip.so [--verbose]
@@ -68,6 +68,12 @@ def listing(co):
         ins = re.sub(r'<[^>]*>', '<>', ins)  # branch targets name labels / offsets of this build
         if ins:
             funcs[cur].append(ins)
+    # What follows a function's last instruction is layout, not the kernel: the s_nop padding up to the next function (or,
+    # behind the last function of a code object, the section's closing run of them) and objdump's '...' for skipped zeros.
+    # Which kernel comes last depends on the translation unit it is compiled in.
+    for ins in funcs.values():
+        while ins and ins[-1] in ('s_nop 0', '...'):
+            ins.pop()
     return funcs
 
 

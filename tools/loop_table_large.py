@@ -88,8 +88,8 @@ def klass(op):
 
 def listing():
     asm = os.path.join(tempfile.mkdtemp(), 'k.s')
-    cmd = ['/opt/rocm/bin/hipcc', '-O3', '-std=c++17', '-fPIC', '--offload-arch=gfx950', '-ffp-contract=on', '-Wno-unused-function',
-           '-Wno-pass-failed', '-fno-slp-vectorize', '-mllvm', '-amdgpu-sched-strategy=iterative-ilp', '-S', '--cuda-device-only', '-o', asm,
+    cmd = ['/opt/rocm/bin/hipcc'] + subprocess.check_output(['make', '-s', '-C', CSRC, 'flags', 'U=mfg_core_large_mixed_ilp'], text=True).split() + [  # (csrc/Makefile owns the flags)
+           '-S', '--cuda-device-only', '-o', asm,
            os.path.join(CSRC, 'mfg_core_large_mixed_ilp.hip')]
     subprocess.run(cmd, check=True, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
     return open(asm).read().split('\n')

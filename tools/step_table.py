@@ -57,8 +57,8 @@ def klass(op):
 
 
 def compile_asm(out, extra):
-    cmd = ['/opt/rocm/bin/hipcc', '-O3', '-std=c++17', '-fPIC', '--offload-arch=gfx950', '-ffp-contract=on', '-Wno-unused-function',
-           '-Wno-pass-failed', '-fno-slp-vectorize', '-mllvm', '-amdgpu-sched-strategy=iterative-ilp', '-S', '--cuda-device-only'] + extra + [
+    cmd = ['/opt/rocm/bin/hipcc'] + subprocess.check_output(['make', '-s', '-C', CSRC, 'flags', 'U=mfg_core_small'], text=True).split() + [  # (csrc/Makefile owns the flags)
+           '-S', '--cuda-device-only'] + extra + [
            '-o', out, os.path.join(CSRC, 'mfg_core_small.hip')]
     subprocess.run(cmd, check=True, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
     return open(out).read().split('\n')
