@@ -25,6 +25,9 @@ ECOMM = -6                      # MFG_ECOMM: the call aborted its RCCL communica
 RN_TRAIN_MAX_TRAJ = 64          # MFG_RN_TRAIN_MAX_TRAJ
 FORECAST_MAX_RANKS = 8          # MFG_FORECAST_MAX_RANKS: order statistics of one mfg_forecast_pop call
 FORECAST_MAX_REPEATS = 1024     # MFG_FORECAST_MAX_REPEATS: members per start state of one mfg_forecast_pop call
+DIST_MAX_BINS = 1024            # MFG_DIST_MAX_BINS: histogram bins of one mfg_row_distribution call
+DIST_MAX_GRID = 4096            # MFG_DIST_MAX_GRID: KDE grid points of one mfg_row_distribution call
+DIST_NONFINITE, DIST_NO_KDE = 1, 2      # MFG_DIST_NONFINITE / MFG_DIST_NO_KDE: bits of a row's status
 PRECISIONS = {'f64': PRECISION_F64, 'mixed': PRECISION_MIXED, 0: 0, 1: 1}
 
 
@@ -199,6 +202,15 @@ SIGNATURES['mfg_consistency_given'] = (_i32, [_p, _i32, _i64, _i32, _i32, _p, _p
 SIGNATURES['mfg_consistency_pop_workspace_bytes'] = (_sz, [_i64, _i32, _i32, _i32, _i32, _i32, _i32, _i32])
 SIGNATURES['mfg_consistency_pop'] = (_i32, [_p, _i64, _i32, _i32, _i32, _p, _p, _p, _p, _u32, _i32, _i32, _p, _p, _p, _p, _p, _p,
                                             _sz, _p])
+
+# the distribution summary of R rows: values, R, N, stride, bins, use_range, lo, hi, G, x_lo, x_hi, moments, counts, edges,
+# density, status, workspace, workspace_bytes, stream; the mean action matrices: action, s_action, K, N, d, mean, workspace,
+# workspace_bytes, stream
+SIGNATURES['mfg_row_distribution_workspace_bytes'] = (_sz, [_i32, _i64, _i32, _i32])
+SIGNATURES['mfg_row_distribution'] = (_i32, [_p, _i32, _i64, _i64, _i32, _i32, _f64, _f64, _i32, _f64, _f64, _p, _p, _p, _p, _p, _p,
+                                             _sz, _p])
+SIGNATURES['mfg_action_mean_pop_workspace_bytes'] = (_sz, [_i32, _i64, _i32])
+SIGNATURES['mfg_action_mean_pop'] = (_i32, [_p, _i64, _i32, _i64, _i32, _p, _p, _sz, _p])
 
 _lib = None
 

@@ -507,7 +507,7 @@ class AC_IRL(actor_critic):
         Ps = Ps.cpu().numpy().astype(np.float64)
         return [[(pis[b, t], Ps[b, t]) for t in range(T)] for b in range(n)]
 
-    def _generate_device(self, n, mat_dev=None):
+    def _generate_device(self, n, mat_dev=None, theta=None):
         """generate_trajectories without the host copy: (pi_traj [n,16,d], P [n,15,d,d]) device tensors straight from
         mfg_rollout(WRITE_P).  Start states drawn on the device like train()'s (mfg_draw_start keyed by seed / step /
         trajectory id): every rank of a multi-GPU job generates the identical D_samp without sharing a host RNG stream."""
@@ -515,8 +515,8 @@ class AC_IRL(actor_critic):
         T = EPISODE_STEPS
         off = self._gen_offset(n)
         _, pi0 = ops.draw_start(mat_dev, n, self.seed, self._rng_step, off)
-        r = ops.rollout(pi0, T, self._theta, self.shift, self.alpha_scale, seed=self.seed, first_step=self._rng_step,
-                        traj_offset=off, td=False, write_P=True, precision=self.precision)
+        r = ops.rollout(pi0, T, self._theta if theta is None else theta, self.shift, self.alpha_scale, seed=self.seed,
+                        first_step=self._rng_step, traj_offset=off, td=False, write_P=True, precision=self.precision)
         self._rng_step += T
         return r['pi_traj'], r['P']
 
@@ -841,6 +841,71 @@ class AC_IRL(actor_critic):
         if self.verbose:
             print('Avg reward demo train %f | Avg reward demo test %f | Avg reward gen %f' % (train_avg, test_avg, gen_avg))
         return train_avg, test_avg, gen_avg
+
+    def _given_theta(self, theta):
+        """`theta` (None: the current one) as a [1] fp64 device array, for a generation only."""
+        return None if theta is None else torch.as_tensor([float(theta)], dtype=torch.float64, device=self.device)
+
+    @_with_ctx
+    def reward_distribution(self, *, theta=None, num_bins=20, xmin=-0.1, xmax=0.4, num_points=200, hist_range=None,
+                            want_rewards=False):
+        """The numbers of plot_reward_distribution (ac_irl.py:1046-1123), reduced on the device: the reward of every transition
+        of list_demonstrations, of list_demonstrations_test, of len(list_demonstrations) trajectories generated from mat_pi0
+        and of as many from mat_pi0_test; per set np.histogram with `num_bins` bins, the moments and gaussian_kde on
+        linspace(xmin, xmax, num_points); and the three JSDs the reference prints.  Returns a reward_dist.RewardDistribution
+        without the leading K (moments [4,6], counts [4,bins], ...): what learner k of an AC_IRLPopulation gives, bit for bit.
+        hist_range, want_rewards and the sets' status: as AC_IRLPopulation.reward_distribution.  theta=None generates under
+        the current policy; a given theta is used for the two generations only (the reference assigns self.theta =
+        theta_good; here theta stays).  D_samp is not touched; the reward-call counter advances by one per forward, the Philox
+        step by 15 and the trajectory counter by len(list_demonstrations) per generation.  rng='philox' only."""
+        from . import reward_dist
+        if self.rng != 'philox':
+            raise ValueError("reward_distribution needs rng='philox' (the trajectories are generated on the device)")
+        if not ops.reward_net_supported(self.reward_net):
+            raise ValueError('reward_distribution: the reward network is outside the range of the HIP forward kernel')
+        self._resync_stores()
+        if getattr(self, '_demo_ragged', False) or not len(self._demo_store):
+            raise ValueError('reward_distribution needs demonstrations of %d (state, action) pairs each' % EPISODE_STEPS)
+        T, d = EPISODE_STEPS, self.d
+        num_demos = len(self._demo_store)
+        ops.check_row_distribution_args(1, num_demos * T, num_demos * T, num_bins, hist_range, num_points, xmin, xmax)
+        th = self._given_theta(theta)
+        inputs = [self._demo_store.gather_flat(), None]
+        test = [pair for traj in self.list_demonstrations_test for pair in traj]
+        if test:
+            inputs[1] = self._pairs_to_tensors(test)
+        test_table = torch.as_tensor(np.ascontiguousarray(self.mat_pi0_test, dtype=np.float32), device=self.device)
+        for table in (self._mat_pi0_dev, test_table):
+            st, ac = self._generate_device(num_demos, table, th)
+            inputs.append((st[:, :T].reshape(num_demos * T, d).contiguous(), ac.reshape(num_demos * T, d, d)))
+        rewards = []
+        self._reward_sample_offset = 0
+        for inp in inputs:
+            rewards.append(None if inp is None else self.reward(*inp).reshape(1, -1))
+        return reward_dist.squeeze(reward_dist.summarise(rewards, 1, self.device, num_bins, xmin, xmax, num_points, hist_range,
+                                                         want_rewards))
+
+    @_with_ctx
+    def action_heatmap(self, *, theta=None):
+        """The numbers of plot_action_heatmap (ac_irl.py:1276-1289): (demo_avg, gen_avg, diff), each [d,d] fp64 -- the mean
+        demonstrated action matrix, the mean action over len(list_demonstrations) freshly generated trajectories and their
+        absolute difference; the means are formed on the device (mfg_action_mean_pop with K = 1).  theta: as for
+        reward_distribution.  The Philox step advances by 15, the trajectory counter by len(list_demonstrations).
+        rng='philox' only."""
+        if self.rng != 'philox':
+            raise ValueError("action_heatmap needs rng='philox' (the trajectories are generated on the device)")
+        self._resync_stores()
+        if getattr(self, '_demo_ragged', False) or not len(self._demo_store):
+            raise ValueError('action_heatmap needs demonstrations of %d (state, action) pairs each' % EPISODE_STEPS)
+        T, d = EPISODE_STEPS, self.d
+        num_demos = len(self._demo_store)
+        _, da = self._demo_store.gather_flat()
+        _, ac = self._generate_device(num_demos, None, self._given_theta(theta))
+        both = torch.empty(2, d, d, dtype=torch.float64, device=self.device)
+        ops.action_mean_pop(da, out=both[:1])
+        ops.action_mean_pop(ac.reshape(num_demos * T, d, d), out=both[1:])
+        host = both.cpu().numpy()
+        return host[0], host[1], np.abs(host[0] - host[1])
 
     @_with_ctx
     def evaluate(self, theta=8.86349, shift=0.5, alpha_scale=1e4, d=15, episode_length=16, indir='test_normalized_round2',

@@ -461,12 +461,13 @@ class AC_IRLPopulation(_Population):
         active = self._healthy() if learners is None else [int(k) for k in learners if self._act.state[int(k)] != 2]
         self._train_rewards(active, 1)
 
-    def _forward(self, st, ac, active, keys):
-        """One population forward of the learners `active` under `keys` (shared [N, ...] or per-learner [K, N, ...] inputs)."""
+    def _forward(self, st, ac, active, keys, out=None):
+        """One population forward of the learners `active` under `keys` (shared [N, ...] or per-learner [K, N, ...] inputs);
+        out: an fp32 [K, N] tensor to fill (rows of other learners are left as they are)."""
         if self._fw_scratch is None:
             self._fw_scratch = torch.empty(2 * self.K, dtype=torch.float64, device=self.device)
-        return ops.reward_net_forward_pop(self._net_struct, True, self.K, st, ac, active, keys, net_stride=self._net_stride,
-                                          scratch=self._fw_scratch, geom=self._geom)
+        return ops.reward_net_forward_pop(self._net_struct, True, self.K, st, ac, active, keys, out=out,
+                                          net_stride=self._net_stride, scratch=self._fw_scratch, geom=self._geom)
 
     def _reward_averages(self, active):
         """AC_IRL._eval_reward_averages of the learners `active`: one population forward over the demonstrations, one over
@@ -571,10 +572,106 @@ class AC_IRLPopulation(_Population):
                 print('learner %d: Avg reward demo train %f | Avg reward demo test %f | Avg reward gen %f' % ((k,) + tuple(out[k])))
         return out
 
-    def _generate(self, n):
-        """AC_IRL._generate_device(n) of every learner (its seed, theta, shift, alpha_scale; shared Philox step and
-        trajectory ids): K draw + rollout launch pairs.  Returns (pi_traj [K,n,16,d], P [K,n,15,d,d])."""
+    def _given_thetas(self, thetas):
+        """`thetas` ([K] or a scalar; None: the learners' own) as a [K] fp64 device array, for a generation only."""
+        if thetas is None:
+            return None
+        return torch.as_tensor(broadcast('thetas', thetas, self.K), device=self.device)
+
+    def _nan_rows(self, active, *shape):
+        """An fp32 device tensor [K, *shape]: NaN in the rows of the learners outside `active`."""
+        t = torch.empty(self.K, *shape, dtype=torch.float32, device=self.device)
+        if len(active) < self.K:
+            t.fill_(float('nan'))
+        return t
+
+    @_with_ctx
+    def reward_distribution(self, *, thetas=None, pi0_test=None, num_bins=20, xmin=-0.1, xmax=0.4, num_points=200,
+                            hist_range=None, want_rewards=False):
+        """The numbers of plot_reward_distribution (ac_irl.py:1046-1123) for every learner, reduced on the device: the reward of
+        every transition of the training demonstrations, of the test demonstrations (constructor argument
+        demonstrations_test), of len(demonstrations) trajectories generated from the train start table and of as many from the
+        start table `pi0_test` [n, d]; per set the histogram (np.histogram with `num_bins` bins), the moments and the Gaussian
+        KDE on linspace(xmin, xmax, num_points); and the three JSDs between the histograms.  Returns a
+        reward_dist.RewardDistribution (leading K).  Four population forwards (the demonstrations shared by all learners),
+        four mfg_row_distribution launches, ONE host read (a second for the rewards with want_rewards).
+        hist_range=None gives every set its own min..max as plt.hist does -- the JSDs then compare histograms over different
+        supports, as the reference's do; (lo, hi) gives all sets that range, values outside it are dropped.
+        thetas=None generates under the learners' current policies; a [K] array (or scalar) is used for the two generations
+        only: unlike the reference, which assigns self.theta = theta_good, no learner's theta is changed.  D_samp is not
+        touched.  The counters advance as the calls the method stands for: the reward-call counters by one per forward (four,
+        three or two: a missing set has none) in the order of `sets`, the Philox step by 15 and the trajectory counter by
+        len(demonstrations) per generation.  Without demonstrations_test / pi0_test the set is NaN with status -1, and so are
+        its JSDs.  Failed learners generate nothing and give NaN rows (status _lib.DIST_NONFINITE)."""
+        from . import reward_dist
+        if not self.per_learner_net:
+            raise ValueError('reward_distribution needs one reward network per learner')
+        if self._demo_np is None:
+            raise ValueError('reward_distribution needs demonstrations (constructor argument demonstrations=...)')
         K, T, d = self.K, EPISODE_STEPS, self.d
+        num_demos = len(self._demo_store)
+        ops.check_row_distribution_args(K, num_demos * T, num_demos * T, num_bins, hist_range, num_points, xmin, xmax)
+        th = self._given_thetas(thetas)
+        test_table = None
+        if pi0_test is not None:
+            test_table = torch.as_tensor(np.ascontiguousarray(np.asarray(pi0_test, dtype=np.float64)[:, :d], dtype=np.float32),
+                                         device=self.device)
+        active = self._healthy()
+        inputs = [self._demo_store.gather_flat(), None, None, None]
+        if self._test_np is not None:
+            if self._test_dev is None:
+                self._test_dev = (torch.from_numpy(self._test_np[0]).reshape(-1, d).contiguous().to(self.device),
+                                  torch.from_numpy(self._test_np[1]).reshape(-1, d, d).contiguous().to(self.device))
+            inputs[1] = self._test_dev
+        for s, table in ((2, self._mat_pi0_dev), (3, test_table)):
+            if table is None:
+                continue
+            st, ac = self._generate(num_demos, mat_dev=table, theta=th)
+            inputs[s] = (st[:, :, :T].reshape(K, num_demos * T, d).contiguous(), ac.reshape(K, num_demos * T, d, d))
+        rewards = [None] * 4
+        for s, inp in enumerate(inputs):
+            if inp is None:
+                continue
+            st, ac = inp
+            rewards[s] = self._nan_rows(active, st.shape[-2])
+            if active:
+                self._calls_k[active] += 1
+                keys = [philox_call_key(self.seeds[k], RN_SEED_OFFSET, self._calls_k[k]) for k in active]
+                self._forward(st, ac, active, keys, out=rewards[s])
+        return reward_dist.summarise(rewards, K, self.device, num_bins, xmin, xmax, num_points, hist_range, want_rewards)
+
+    @_with_ctx
+    def action_heatmap(self, *, thetas=None):
+        """The numbers of plot_action_heatmap (ac_irl.py:1276-1289) for every learner: (demo_avg [d,d], gen_avg [K,d,d], diff
+        [K,d,d]) -- the mean demonstrated action matrix, each learner's mean action over len(demonstrations) freshly generated
+        trajectories, and |demo_avg - gen_avg|, fp64 means formed on the device (mfg_action_mean_pop, K = 1 for the
+        demonstrations), one host read.  thetas: as for reward_distribution (used for the generation only).  The Philox step
+        advances by 15 and the trajectory counter by len(demonstrations); D_samp is not touched; failed learners give NaN
+        rows."""
+        if self._demo_np is None:
+            raise ValueError('action_heatmap needs demonstrations (constructor argument demonstrations=...)')
+        K, T, d = self.K, EPISODE_STEPS, self.d
+        num_demos = len(self._demo_store)
+        active = self._healthy()
+        _, da = self._demo_store.gather_flat()
+        _, ac = self._generate(num_demos, theta=self._given_thetas(thetas))
+        both = torch.empty(K + 1, d, d, dtype=torch.float64, device=self.device)
+        ops.action_mean_pop(da, out=both[:1])
+        ops.action_mean_pop(ac.reshape(K, num_demos * T, d, d), out=both[1:])
+        host = both.cpu().numpy()
+        demo_avg, gen_avg = host[0], host[1:].copy()
+        failed = [k for k in range(K) if k not in active]
+        gen_avg[failed] = np.nan
+        return demo_avg, gen_avg, np.abs(demo_avg[None] - gen_avg)
+
+    def _generate(self, n, mat_dev=None, theta=None):
+        """AC_IRL._generate_device(n) of every learner (its seed, theta, shift, alpha_scale; shared Philox step and
+        trajectory ids): K draw + rollout launch pairs.  Returns (pi_traj [K,n,16,d], P [K,n,15,d,d]).  mat_dev: another
+        start table [num_start, d] fp32 on the device (default: the train table); theta: another [K] fp64 device array of
+        policies to roll (default: the learners' own)."""
+        K, T, d = self.K, EPISODE_STEPS, self.d
+        mat_dev = self._mat_pi0_dev if mat_dev is None else mat_dev
+        theta = self._theta if theta is None else theta
         off = self._gen_traj_counter
         self._gen_traj_counter = off + n
         live = self._healthy()                     # (a failed learner rolls nothing: its rows stay zero and are never read)
@@ -583,8 +680,8 @@ class AC_IRLPopulation(_Population):
         actions = new(K, n, T, d, d, dtype=torch.float32, device=self.device)
         for k in live:
             seed = int(self.seeds[k])
-            _, pi0 = ops.draw_start(self._mat_pi0_dev, n, seed, self._rng_step, off)
-            ops.rollout(pi0, T, self._theta[k:k + 1], float(self.shifts[k]), float(self.alpha_scales[k]), seed=seed,
+            _, pi0 = ops.draw_start(mat_dev, n, seed, self._rng_step, off)
+            ops.rollout(pi0, T, theta[k:k + 1], float(self.shifts[k]), float(self.alpha_scales[k]), seed=seed,
                         first_step=self._rng_step, traj_offset=off, td=False, write_P=True, precision=self.precision,
                         out={'pi_traj': states[k], 'P': actions[k]})
         self._rng_step += T

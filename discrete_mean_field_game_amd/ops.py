@@ -1031,6 +1031,120 @@ def forecast_pop(start32, thetas, shifts, alpha_scales, seeds, horizon, first_st
     return out
 
 
+def hist_edges(first, last, bins):
+    """The bin edges of mfg_row_distribution, i.e. of np.histogram(x, bins, range=(first, last)), restated in plain Python
+    floats: first - 0.5, last + 0.5 when the two are equal; step = (last - first) / bins; edge_i = fl(fl(i step) + first) for
+    i < bins (two roundings) and edge_bins = last.  Returns a NumPy fp64 array [bins + 1]."""
+    import numpy as np
+    first, last, bins = float(first), float(last), int(bins)
+    if first == last:
+        first, last = first - 0.5, last + 0.5
+    step = (last - first) / bins
+    out = []
+    for i in range(bins):
+        m = float(i) * step
+        out.append(m + first)
+    out.append(last)
+    return np.array(out, dtype=np.float64)
+
+
+def check_row_distribution_args(R, N, stride, bins, hist_range, G, x_lo, x_hi, dtype=torch.float32, is_cuda=True):
+    """The argument rules of row_distribution that need no GPU (ValueError): R >= 1 rows of 1 <= N < 2^31 values `stride` >= N
+    apart, fp32 on the device; 1 <= bins <= DIST_MAX_BINS; hist_range None or finite (lo, hi) with lo < hi; 0 <= G <=
+    DIST_MAX_GRID grid points between finite x_lo and x_hi.  Returns (use_range, lo, hi)."""
+    import math
+    if dtype != torch.float32 or not is_cuda:
+        raise ValueError('values must be a contiguous float32 CUDA tensor')
+    R, N, stride, bins, G = int(R), int(N), int(stride), int(bins), int(G)
+    if R < 1:
+        raise ValueError('R=%d: at least one row' % R)
+    if not 1 <= N < 2 ** 31:
+        raise ValueError('N=%d outside [1, 2^31)' % N)
+    if stride < N:
+        raise ValueError('stride=%d < N=%d' % (stride, N))
+    if not 1 <= bins <= L.DIST_MAX_BINS:
+        raise ValueError('bins=%d outside [1, %d] (MFG_DIST_MAX_BINS)' % (bins, L.DIST_MAX_BINS))
+    if not 0 <= G <= L.DIST_MAX_GRID:
+        raise ValueError('G=%d grid points outside [0, %d] (MFG_DIST_MAX_GRID)' % (G, L.DIST_MAX_GRID))
+    if G and not (math.isfinite(float(x_lo)) and math.isfinite(float(x_hi))):
+        raise ValueError('KDE grid: finite x_lo and x_hi needed')
+    if hist_range is None:
+        return 0, 0.0, 0.0
+    lo, hi = (float(v) for v in hist_range)
+    if not (math.isfinite(lo) and math.isfinite(hi)) or lo >= hi:
+        raise ValueError('hist_range=(%r, %r): finite lo < hi needed' % (lo, hi))
+    return 1, lo, hi
+
+
+def row_distribution(values, N=None, bins=20, hist_range=None, G=0, x_lo=0.0, x_hi=1.0, out=None):
+    """The distribution summary of the rows of `values` [R, stride] fp32 in one launch (mfg_row_distribution; plt.hist and
+    gaussian_kde of plot_reward_distribution, ac_irl.py:1087-1119): the first N values of every row (default: all).  Returns
+    a dict of device tensors: moments [R,6] fp64 (kept, min, max, mean, variance with ddof 1, KDE bandwidth variance), counts
+    [R,bins] int64 and edges [R,bins+1] fp64 (np.histogram on the fp64 copy; hist_range=(lo, hi): a common range), density
+    [R,G] fp64 (gaussian_kde on linspace(x_lo, x_hi, G); None with G = 0) and status [R] int32 (DIST_NONFINITE: NaN row,
+    DIST_NO_KDE: NaN density).  out: the same dict with tensors to fill instead."""
+    if values.dim() != 2:
+        raise ValueError('values: expected [R, stride], got %s' % (tuple(values.shape),))
+    R, stride = values.shape
+    N = stride if N is None else int(N)
+    use_range, lo, hi = check_row_distribution_args(R, N, stride, bins, hist_range, G, x_lo, x_hi, values.dtype, values.is_cuda)
+    _chk_f32(values, 'values')
+    bins, G = int(bins), int(G)
+    dev = values.device
+    if out is None:
+        out = {'moments': torch.empty(R, 6, dtype=torch.float64, device=dev),
+               'counts': torch.empty(R, bins, dtype=torch.int64, device=dev),
+               'edges': torch.empty(R, bins + 1, dtype=torch.float64, device=dev),
+               'density': torch.empty(R, G, dtype=torch.float64, device=dev) if G else None,
+               'status': torch.empty(R, dtype=torch.int32, device=dev)}
+    else:
+        for name, shape, dt in (('moments', (R, 6), torch.float64), ('counts', (R, bins), torch.int64),
+                                ('edges', (R, bins + 1), torch.float64), ('density', (R, G), torch.float64),
+                                ('status', (R,), torch.int32)):
+            t = out.get(name)
+            if name == 'density' and not G:
+                continue
+            if t is None or tuple(t.shape) != shape or t.dtype != dt or not t.is_cuda or not t.is_contiguous():
+                raise ValueError('out[%r]: expected a contiguous %s device tensor %s' % (name, dt, shape))
+    nbytes = int(L.lib().mfg_row_distribution_workspace_bytes(R, N, bins, G))
+    ws = torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=dev) if nbytes else None
+    L.check(L.lib().mfg_row_distribution(values.data_ptr(), R, N, stride, bins, use_range, lo, hi, G, float(x_lo), float(x_hi),
+                                         out['moments'].data_ptr(), out['counts'].data_ptr(), out['edges'].data_ptr(),
+                                         _ptr(out['density']) if G else None, out['status'].data_ptr(), _ptr(ws), nbytes,
+                                         _stream()), 'mfg_row_distribution')
+    return out
+
+
+def action_mean_pop(action, K=None, out=None):
+    """The mean action matrix of K learners in two launches (mfg_action_mean_pop; np.mean(actions, axis=0) of
+    plot_action_heatmap, ac_irl.py:1276-1289): action [K,N,d,d] fp32, or [N,d,d] shared by K learners (default K = 1).
+    Returns mean [K,d,d] fp64 on the device."""
+    _chk_f32(action, 'action')
+    shared = action.dim() == 3
+    if shared:
+        K = 1 if K is None else int(K)
+        N, d = action.shape[0], action.shape[1]
+    else:
+        if action.dim() != 4 or (K is not None and int(K) != action.shape[0]):
+            raise ValueError('action: expected [N, d, d] or [K, N, d, d], got %s' % (tuple(action.shape),))
+        K, N, d = action.shape[:3]
+    if action.shape[-1] != d or min(K, N, d) < 1:
+        raise ValueError('action: square matrices and no empty dimension expected, got %s' % (tuple(action.shape),))
+    if d > 64:
+        raise ValueError('d=%d: the mean action covers d <= 64' % d)
+    dev = action.device
+    if out is None:
+        out = torch.empty(K, d, d, dtype=torch.float64, device=dev)
+    elif tuple(out.shape) != (K, d, d):
+        raise ValueError('out: expected [%d, %d, %d]' % (K, d, d))
+    _chk_f64(out, 'out')
+    nbytes = int(L.lib().mfg_action_mean_pop_workspace_bytes(K, N, d))
+    ws = torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=dev)
+    L.check(L.lib().mfg_action_mean_pop(action.data_ptr(), 0 if shared else N * d * d, K, N, d, out.data_ptr(), ws.data_ptr(),
+                                        ws.numel() * ws.element_size(), _stream()), 'mfg_action_mean_pop')
+    return out
+
+
 def consistency_given(P, want_steps=True, want_V=True):
     """The backward-equation check of K groups of given actions in two launches (mfg_consistency_given; evaluate_synthetic /
     evaluate_synthetic_JSD, mfg_synthetic.py:741-899): P [K,M,T,d,d] fp32.  Returns a dict of device fp64 tensors: metrics

@@ -577,6 +577,51 @@ int mfg_forecast_pop(const float* start32, int64_t N, int H, int d, int K, const
                      const int32_t* ranks, int Q, const float* emp32, const double* emp64, double* mean, double* std, float* quant,
                      double* curves, float* pi_traj, void* workspace, size_t workspace_bytes, mfg_stream_t stream);
 
+/* Distribution summary of R rows of N fp32 values in ONE launch, one workgroup per row: what plot_reward_distribution and
+ * its two siblings (ac_irl.py:1046-1263) take from plt.hist (np.histogram, :1116-1119) and gaussian_kde (:1087-1100) for each
+ * of their reward sets.  Row r is values[r stride .. r stride + N), stride >= N; everything below is on x = (double)values.
+ *   moments [R,6] fp64: number of values the histogram kept (N without a range), min, max, mean (a fixed-order sum),
+ *   variance (ddof = 1, two passes: sum (x - mean)^2 / (N - 1)), KDE bandwidth variance c = variance N^(-2/5) (gaussian_kde's
+ *   Scott factor squared).  Mean and variance are over all N values; the range only affects the histogram.
+ *   counts [R,bins] int64, edges [R,bins+1] fp64: those of np.histogram(x, bins) on the fp64 array, with use_range those of
+ *   np.histogram(x, bins, range=(lo, hi)): first = min, last = max (lo, hi with a range); first - 0.5, last + 0.5 if they are
+ *   equal; step = (last - first) / bins; edge_i = fl(fl(i step) + first) for i < bins (two roundings), edge_bins = last.  A
+ *   value is counted in bin i when edge_i <= x < edge_(i+1), the last bin closed on the right; values outside a given range
+ *   are dropped.  The index is NumPy's guess ((x - first) / (last - first)) bins, truncated, corrected against the exact edges.
+ *   density [R,G] fp64 (NULL allowed iff G == 0): scipy.stats.gaussian_kde(x)(grid) on grid = linspace(x_lo, x_hi, G), i.e.
+ *   density_g = sum_n exp(-(g - x_n)^2 / (2c)) / (N sqrt(2 pi c)), fp64, the terms added in ascending n.
+ *   status [R] int32 bit flags: MFG_DIST_NONFINITE: the row holds a non-finite value -- its moments, edges and density are NaN
+ *   and its counts zero, every other row is as without it; MFG_DIST_NO_KDE: N < 2 or variance == 0 (gaussian_kde raises
+ *   there) -- the density is NaN, the rest of the row stands.
+ * Row r's outputs depend on row r alone and are the same bits whatever R is; no floating-point atomics.
+ * workspace: mfg_row_distribution_workspace_bytes(R, N, bins, G) bytes (at present 0: NULL is then allowed).
+ * Checked before anything is launched: no null pointer, R >= 1, 1 <= N < 2^31, stride >= N, 1 <= bins <= MFG_DIST_MAX_BINS,
+ * 0 <= G <= MFG_DIST_MAX_GRID, finite lo < hi with use_range, finite x_lo, x_hi with G > 0 (MFG_EINVAL); the workspace
+ * (MFG_EWORKSPACE).  No allocation, no synchronisation; runs on `stream`. */
+#define MFG_DIST_MAX_BINS 1024
+#define MFG_DIST_MAX_GRID 4096
+#define MFG_DIST_NONFINITE 1
+#define MFG_DIST_NO_KDE 2
+size_t mfg_row_distribution_workspace_bytes(int R, int64_t N, int bins, int G);
+int mfg_row_distribution(const float* values, int R, int64_t N, int64_t stride, int bins, int use_range, double lo, double hi,
+                         int G, double x_lo, double x_hi, double* moments, int64_t* counts, double* edges, double* density,
+                         int32_t* status, void* workspace, size_t workspace_bytes, mfg_stream_t stream);
+
+/* Mean action matrix of K learners in TWO launches: np.mean(np.asarray(actions), axis=0) of plot_action_heatmap
+ * (ac_irl.py:1276-1289), for every learner at once.
+ *   action: learner k's N matrices [N,d,d] fp32 start at action + k s_action; s_action = 0: one input shared by all K.
+ *   mean [K,d,d] fp64.
+ *   launch 1, grid (chunks, K): thread e mod 256 owns matrix element e (consecutive threads, consecutive floats) and adds its
+ *   chunk of n in ascending n in fp64 into partials [K,chunks,d d] in the workspace; launch 2 adds a learner's partials (16
+ *   runs of chunks, each in chunk order, the run totals in run order) and divides by N.  The number of chunks depends on N
+ *   alone, so learner k's mean is the same bits whatever K is.  The input is read once (K N d d 4 bytes).
+ *   workspace: mfg_action_mean_pop_workspace_bytes(K, N, d) bytes; contents are scratch.
+ * Checked before anything is launched: no null pointer, 1 <= K <= MFG_POP_MAX_K, N >= 1, d >= 1, s_action = 0 or >= N d d
+ * (MFG_EINVAL); d <= 64 (MFG_EUNSUPPORTED); the workspace (MFG_EWORKSPACE). */
+size_t mfg_action_mean_pop_workspace_bytes(int K, int64_t N, int d);
+int mfg_action_mean_pop(const float* action, int64_t s_action, int K, int64_t N, int d, double* mean, void* workspace,
+                        size_t workspace_bytes, mfg_stream_t stream);
+
 /* Backward-equation check of K groups of trajectories, reduced on the device: the scoring of the reference's synthetic sweep
  * (evaluate_synthetic / evaluate_synthetic_JSD, mfg_synthetic.py:741-899, called once per learner by its __main__, :902-925).
  * mfg_consistency_given, TWO launches on given actions:
