@@ -25,6 +25,7 @@ ECOMM = -6                      # MFG_ECOMM: the call aborted its RCCL communica
 RN_TRAIN_MAX_TRAJ = 64          # MFG_RN_TRAIN_MAX_TRAJ
 FORECAST_MAX_RANKS = 8          # MFG_FORECAST_MAX_RANKS: order statistics of one mfg_forecast_pop call
 FORECAST_MAX_REPEATS = 1024     # MFG_FORECAST_MAX_REPEATS: members per start state of one mfg_forecast_pop call
+FORECAST_SCORE_TILE = 64        # MFG_FORECAST_SCORE_TILE: members per tile of mfg_forecast_score's energy pass
 DIST_MAX_BINS = 1024            # MFG_DIST_MAX_BINS: histogram bins of one mfg_row_distribution call
 DIST_MAX_GRID = 4096            # MFG_DIST_MAX_GRID: KDE grid points of one mfg_row_distribution call
 DIST_NONFINITE, DIST_NO_KDE = 1, 2      # MFG_DIST_NONFINITE / MFG_DIST_NO_KDE: bits of a row's status
@@ -193,6 +194,11 @@ SIGNATURES['mfg_evaluate_pop'] = (_i32, [_p, _p, _i64, _i32, _i32, _i32, _p, _p,
 SIGNATURES['mfg_forecast_pop_workspace_bytes'] = (_sz, [_i64, _i32, _i32, _i32, _i32, _i32])
 SIGNATURES['mfg_forecast_pop'] = (_i32, [_p, _i64, _i32, _i32, _i32, _p, _p, _p, _p, _u32, _i32, _i32, C.POINTER(C.c_int32), _i32,
                                          _p, _p, _p, _p, _p, _p, _p, _p, _sz, _p])
+
+# the proper scores of given members: traj, N, H, d, K, repeats, emp32, emp64, crps, less, equal, energy, summary, workspace,
+# workspace_bytes, stream
+SIGNATURES['mfg_forecast_score_workspace_bytes'] = (_sz, [_i64, _i32, _i32, _i32, _i32])
+SIGNATURES['mfg_forecast_score'] = (_i32, [_p, _i64, _i32, _i32, _i32, _i32, _p, _p, _p, _p, _p, _p, _p, _p, _sz, _p])
 
 # the backward-equation check.  given: P, K, M, T, d, metrics, steps, V, workspace, workspace_bytes, stream; pop: start32, N, H,
 # d, K, theta, shift, alpha_scale, seed, first_step, repeats, precision, metrics, steps, V, actions, pi_traj, workspace,

@@ -838,6 +838,36 @@ class actor_critic:
         return population.Forecast(pick(got['mean']), pick(got['std']), pick(got['quant']), probs, ranks, pick(got['curves']),
                                    repeats, pick(got['traj']))
 
+    @_with_ctx
+    def forecast_score(self, pi0, total_hours, repeats=256, *, emp, want_energy=True):
+        """The proper scores of forecast()'s ensemble against the held-out rows `emp` [N, >= total_hours, >= d] (CRPS per topic,
+        the energy score per histogram, the observation's rank counts; mfg_forecast_score, K = 1): the members forecast()
+        rolls from the same state (pi0 (d,) or [N, d]; None: row 0 of each emp matrix), scored on the device.  Advances
+        _rng_step by total_hours - 1, as forecast() does.  Returns a population.ForecastScore of NumPy arrays without the
+        leading K: crps, less, equal [N, H, d], energy [N, H] (None without want_energy), summary [H, 2]."""
+        from . import population
+        check_forecast_rng(self.rng)
+        start, emp, H = population._score_inputs(None if pi0 is None else _as_np(pi0), None if emp is None else _as_np(emp),
+                                                 self.d, total_hours)
+        ops.check_forecast_args(start.shape, H, repeats, (), self.precision)
+        first_step = self._rng_step
+        self._rng_step += H - 1
+        dev = self.device
+        one = lambda v: torch.as_tensor(np.array([float(v)], dtype=np.float64), device=dev)
+        seeds = torch.as_tensor(np.array([self.seed & 0xFFFFFFFFFFFFFFFF], dtype=np.uint64).view(np.int64), device=dev)
+        self._flush_pending()
+        try:
+            got = population.forecast_score_policies(start, emp, self._theta.reshape(1).contiguous(), one(self.shift),
+                                                     one(self.alpha_scale), seeds, H, first_step, int(repeats), self.precision,
+                                                     dev, self._ctx, want_energy)
+        except L.MfgError as e:
+            if e.code:                               # refused by the library before anything was launched
+                self._rng_step = first_step
+            raise
+        pick = lambda a: None if a is None else a[0]
+        return population.ForecastScore(pick(got['crps']), pick(got['less']), pick(got['equal']), pick(got['energy']),
+                                        pick(got['summary']), repeats)
+
     _EVAL_HEADER = ('theta,shift,alpha_scale,mean_l1_final,std_l1_final,mean_l1_mean,std_l1_mean,'
                     'mean_JSD_final,std_JSD_final,mean_JSD_mean,std_JSD_mean\n')
     _EVAL_FMT = '%f,%f,%f,%.3e,%.3e,%.3e,%.3e,%.3e,%.3e,%.3e,%.3e\n'    # one CSV line: theta, shift, alpha_scale, the 8 metrics

@@ -1031,6 +1031,67 @@ def forecast_pop(start32, thetas, shifts, alpha_scales, seeds, horizon, first_st
     return out
 
 
+def forecast_score_workspace_bytes(N, horizon, d, K, repeats):
+    """mfg_forecast_score_workspace_bytes: the scratch bytes of one forecast_score call (needs the library, no GPU)."""
+    return int(L.lib().mfg_forecast_score_workspace_bytes(int(N), int(horizon), int(d), int(K), int(repeats)))
+
+
+def forecast_score_workspace(N, horizon, d, K, repeats, device):
+    """The scratch buffer of one forecast_score call (whole doubles)."""
+    return torch.empty((forecast_score_workspace_bytes(N, horizon, d, K, repeats) + 7) // 8, dtype=torch.float64, device=device)
+
+
+def check_forecast_score_args(traj_shape, emp32_shape, emp64_shape, N, repeats):
+    """The argument rules of forecast_score that need no GPU (ValueError): traj [K, N repeats, H, d] with 1 <= K <= POP_MAX_K,
+    N >= 1, H >= 2, 1 <= d <= 64, 1 <= repeats <= FORECAST_MAX_REPEATS; emp32 and emp64 [N, H, d].  Returns (K, N, H, d,
+    repeats)."""
+    N, repeats = int(N), int(repeats)
+    if N < 1:
+        raise ValueError('N=%d: at least one start state' % N)
+    if repeats < 1:
+        raise ValueError('repeats=%d: an ensemble has at least one member' % repeats)
+    if repeats > L.FORECAST_MAX_REPEATS:
+        raise ValueError('repeats=%d: at most %d members per start state (MFG_FORECAST_MAX_REPEATS)' % (repeats, L.FORECAST_MAX_REPEATS))
+    if len(traj_shape) != 4 or int(traj_shape[1]) != N * repeats:
+        raise ValueError('traj: expected [K, N repeats = %d, H, d], got %s' % (N * repeats, tuple(traj_shape)))
+    K, H, d = int(traj_shape[0]), int(traj_shape[2]), int(traj_shape[3])
+    if not 1 <= K <= L.POP_MAX_K:
+        raise ValueError('traj: %d policies outside [1, %d]' % (K, L.POP_MAX_K))
+    if H < 2:
+        raise ValueError('traj: H=%d rows per member, a forecast has at least 2' % H)
+    if not 1 <= d <= 64:
+        raise ValueError('d=%d: the forecast scores cover d <= 64 (as the ensemble forecast does)' % d)
+    if tuple(emp32_shape) != (N, H, d) or tuple(emp64_shape) != (N, H, d):
+        raise ValueError('emp32 / emp64: expected two [%d, %d, %d] tensors, got %s and %s'
+                         % (N, H, d, tuple(emp32_shape), tuple(emp64_shape)))
+    return K, N, H, d, repeats
+
+
+def forecast_score(traj, emp32, emp64, N, repeats, want_energy=True, ws=None):
+    """The proper scores of given ensemble members in at most two launches (mfg_forecast_score): traj [K, N repeats, H, d] fp32
+    as forecast_pop(want_traj=True) returns it (member r of start row n is row r N + n), emp32 / emp64 [N, H, d] the held-out
+    rows.  Returns a dict of device tensors: crps [K,N,H,d] fp64; less, equal [K,N,H,d] int32 (members below / equal to the
+    fp32 observation; -1 in a cell with a non-finite value, whose scores are NaN); energy [K,N,H] fp64 (None without
+    want_energy, which skips the O(repeats^2 d) pass); summary [K,H,2] fp64 (mean crps over (n, c), mean energy over n or NaN)."""
+    for name, t in (('traj', traj), ('emp32', emp32)):
+        _chk_f32(t, name)
+    _chk_f64(emp64, 'emp64')
+    K, N, H, d, repeats = check_forecast_score_args(traj.shape, emp32.shape, emp64.shape, N, repeats)
+    dev = traj.device
+    out = {'crps': torch.empty(K, N, H, d, dtype=torch.float64, device=dev),
+           'less': torch.empty(K, N, H, d, dtype=torch.int32, device=dev),
+           'equal': torch.empty(K, N, H, d, dtype=torch.int32, device=dev),
+           'energy': torch.empty(K, N, H, dtype=torch.float64, device=dev) if want_energy else None,
+           'summary': torch.empty(K, H, 2, dtype=torch.float64, device=dev)}
+    if ws is None:
+        ws = forecast_score_workspace(N, H, d, K, repeats, dev)
+    L.check(L.lib().mfg_forecast_score(traj.data_ptr(), N, H, d, K, repeats, emp32.data_ptr(), emp64.data_ptr(),
+                                       out['crps'].data_ptr(), out['less'].data_ptr(), out['equal'].data_ptr(),
+                                       _ptr(out['energy']), out['summary'].data_ptr(), ws.data_ptr(),
+                                       ws.numel() * ws.element_size(), _stream()), 'mfg_forecast_score')
+    return out
+
+
 def hist_edges(first, last, bins):
     """The bin edges of mfg_row_distribution, i.e. of np.histogram(x, bins, range=(first, last)), restated in plain Python
     floats: first - 0.5, last + 0.5 when the two are equal; step = (last - first) / bins; edge_i = fl(fl(i step) + first) for

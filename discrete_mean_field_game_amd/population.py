@@ -457,6 +457,174 @@ def forecast(thetas, shifts, alpha_scales, pi0, horizon, *, d, seed=0, repeats=2
     return Forecast(cat('mean'), cat('std'), cat('quant'), probs, ranks, cat('curves'), repeats, cat('traj'))
 
 
+# ------------------------------------------------------------------------------------------------ scoring the forecast
+# Whether the ensemble is any good: the proper scoring rules of a forecast distribution against the held-out rows (Gneiting &
+# Raftery, JASA 2007) -- CRPS per topic, the energy score per histogram, and the rank of the observation among the members
+# (PIT, band coverage) -- on the device (mfg_forecast_score), the members never leaving it.  The reference has no such scorer:
+# its forecast is one sample path, scored by L1 / JSD (evaluate, mfg_ac2.py:595-670; the VAR baseline, var.py:330-416).
+SCORE_HEADER = 'theta,shift,alpha_scale,crps_mean,crps_final,energy_mean,energy_final\n'
+SCORE_FMT = '%f,%f,%f,%.6e,%.6e,%.6e,%.6e\n'
+
+
+class ForecastScore:
+    """The scores of a forecast (NumPy): crps [K, N, H, d]; less, equal [K, N, H, d] int32, the members below / equal to the
+    fp32 observation (-1 where the cell holds a non-finite value or the learner failed); energy [K, N, H] or None; summary
+    [K, H, 2], the mean CRPS over start rows and topics and the mean energy score over start rows, per hour.  A single-policy
+    score (actor_critic.forecast_score) drops the leading K."""
+
+    def __init__(self, crps, less, equal, energy, summary, repeats):
+        self.crps, self.less, self.equal, self.energy, self.summary = crps, less, equal, energy, summary
+        self.repeats = int(repeats)
+
+    def learner(self, k):
+        """Row k as a ForecastScore of its own."""
+        pick = lambda a: None if a is None else a[k]
+        return ForecastScore(pick(self.crps), pick(self.less), pick(self.equal), pick(self.energy), pick(self.summary),
+                             self.repeats)
+
+
+def pit(less, equal, repeats):
+    """The probability integral transform of the observation among `repeats` members, ties split evenly:
+    (less + equal / 2) / repeats.  Uniform on [0, 1] for a calibrated forecast.  Needs no GPU."""
+    R = int(repeats)
+    if R < 1:
+        raise ValueError('repeats=%d: an ensemble has at least one member' % R)
+    return (np.asarray(less, dtype=np.float64) + np.asarray(equal, dtype=np.float64) / 2.0) / R
+
+
+def covered(less, equal, lo_rank, hi_rank):
+    """Whether the observation lies inside the band of the ascending order statistics lo_rank .. hi_rank (0-based, as
+    forecast_ranks names them): x_(lo) <= y <= x_(hi), i.e. (less + equal > lo_rank) & (less <= hi_rank).  Needs no GPU."""
+    less, equal = np.asarray(less, dtype=np.int64), np.asarray(equal, dtype=np.int64)
+    return (less + equal > int(lo_rank)) & (less <= int(hi_rank))
+
+
+def forecast_score_bytes(N, horizon, d, repeats):
+    """Device bytes one policy takes in a forecast_score chunk: its members, the forecast's and the score's workspaces and
+    outputs (the byte counts of the library; needs no GPU)."""
+    N, H, d, R = int(N), int(horizon), int(d), int(repeats)
+    lib = L.lib()
+    outputs = N * H * d * (8 + 8 + 8 + 4 + 4) + N * H * 8 + H * 2 * 8
+    return (N * R * H * d * 4 + int(lib.mfg_forecast_pop_workspace_bytes(N, H, d, 1, R, 1))
+            + int(lib.mfg_forecast_score_workspace_bytes(N, H, d, 1, R)) + outputs)
+
+
+def forecast_score_policies(start, emp, thetas, shifts, alpha_scales, seeds, horizon, first_step, repeats, precision, device, ctx,
+                            want_energy=True):
+    """One ops.forecast_pop call for the members and one ops.forecast_score call on them, as NumPy arrays (crps, less, equal,
+    energy, summary): `start` [N, d], `emp` [N, H, d] fp64 rows; `thetas`, `shifts`, `alpha_scales` fp64 and `seeds` int64
+    device tensors [K].  Only the scores come to the host.  MfgError when a mixed-precision policy left the fp32 range."""
+    start32 = torch.as_tensor(np.ascontiguousarray(start, dtype=np.float32), device=device)
+    emp64 = torch.as_tensor(np.ascontiguousarray(emp, dtype=np.float64), device=device)
+    emp32 = torch.as_tensor(np.ascontiguousarray(emp, dtype=np.float64).astype(np.float32), device=device)
+    traj = ops.forecast_pop(start32, thetas, shifts, alpha_scales, seeds, horizon, first_step=first_step, repeats=repeats,
+                            precision=precision, want_traj=True)['traj']
+    out = ops.forecast_score(traj, emp32, emp64, start32.shape[0], repeats, want_energy=want_energy)
+    host = {k: None if v is None else v.cpu().numpy() for k, v in out.items()}
+    if precision == 'mixed' and ctx.status(synchronize=True):
+        raise L.MfgError('a mixed-precision forecast ran a policy with |theta| (1 + |shift|) > 86 (or theta not finite): '
+                         'its rows are NaN; use precision=\'f64\'')
+    return host
+
+
+def _score_inputs(pi0, emp, d, horizon):
+    """(start, emp, horizon) of a forecast_score: `emp` is needed, `horizon` defaults to its rows.  ValueError otherwise."""
+    if emp is None:
+        raise ValueError('a forecast is scored against held-out rows: emp is needed')
+    if horizon is None:
+        e = np.asarray(emp)
+        if e.ndim not in (2, 3):
+            raise ValueError('emp: expected [N, H, >= d] or [H, >= d], got %s' % (e.shape,))
+        horizon = e.shape[-2]
+    start, emp = _forecast_inputs(pi0, emp, d, horizon)
+    return start, emp, int(horizon)
+
+
+def forecast_score(thetas, shifts, alpha_scales, emp, *, d, pi0=None, horizon=None, seed=0, repeats=256, precision='mixed',
+                   device=None, first_step=0, want_energy=True, budget=None):
+    """The proper scores of the ensemble forecast of K policies against the held-out rows `emp` [N, >= horizon, >= d]
+    (horizon None: all its rows): the members are those of forecast() for the same arguments (start rows pi0, or row 0 of each
+    emp matrix; common random numbers), scored on the device without coming to the host.  Policies go in chunks whose members,
+    workspaces and outputs stay within `budget` bytes (None: CONSISTENCY_BUDGET; consistency_chunks) -- chunking changes no bit.
+    want_energy=False skips the O(repeats^2 d) energy score.  Returns a ForecastScore.  Runs on a context of its own: a diverged
+    mixed-precision policy raises MfgError and leaves the caller's status word alone."""
+    if precision not in ('mixed', 'f64'):
+        raise ValueError("precision must be 'mixed' or 'f64'")
+    th = np.asarray(thetas, dtype=np.float64).reshape(-1)
+    K = th.shape[0]
+    if K < 1:
+        raise ValueError('no policies')
+    sh, al = broadcast('shifts', shifts, K), broadcast('alpha_scales', alpha_scales, K)
+    sd = broadcast('seed', seed, K, np.uint64).view(np.int64)
+    start, emp, H = _score_inputs(pi0, emp, d, horizon)
+    ops.check_forecast_args(start.shape, H, repeats, (), precision)
+    N, R = start.shape[0], int(repeats)
+    chunks = consistency_chunks(K, forecast_score_bytes(N, H, int(d), R), budget)
+    if not torch.cuda.is_available():
+        raise L.MfgError('forecast_score needs a ROCm GPU: the HIP hot path has no CPU fallback')
+    ops.init()
+    dev = torch.device(device) if device is not None else torch.device('cuda', torch.cuda.current_device())
+    ctx = ops.Context(dev)
+    prev = ctx.bind_scoped()
+    try:
+        parts = []
+        for c0, n in chunks:
+            f = lambda a: torch.as_tensor(a[c0:c0 + n].copy(), device=dev)
+            parts.append(forecast_score_policies(start, emp, f(th), f(sh), f(al), f(sd), H, int(first_step), R, precision, dev,
+                                                 ctx, want_energy))
+    finally:
+        ctx.restore(prev)
+        ctx.close()
+    cat = lambda key: None if parts[0][key] is None else np.concatenate([p[key] for p in parts])
+    return ForecastScore(cat('crps'), cat('less'), cat('equal'), cat('energy'), cat('summary'), R)
+
+
+def score_columns(summary):
+    """[K, 4] = (crps_mean, crps_final, energy_mean, energy_final) from a ForecastScore.summary [K, H, 2]: the means over the
+    hours 1 .. H - 1 (hour 0 is the start row, which every member shares) and the last hour."""
+    summary = np.asarray(summary, dtype=np.float64)
+    return np.stack([summary[:, 1:, 0].mean(axis=1), summary[:, -1, 0], summary[:, 1:, 1].mean(axis=1), summary[:, -1, 1]], axis=1)
+
+
+def best_score_points(points, table):
+    """Per column of `table` [len(points), 4] the value and the point of the LAST minimum in grid order (best_points' `<=`),
+    starting from [inf, 0, 0, 0]; a NaN never wins."""
+    best = [[float('inf'), 0, 0, 0] for _ in range(4)]
+    for (theta, shift, alpha_scale), res in zip(points, table):
+        for idx in range(4):
+            if res[idx] <= best[idx][0]:
+                best[idx] = [float(res[idx]), theta, shift, alpha_scale]
+    return best
+
+
+def gridsearch_score(theta_range, shift_range, alpha_range, indir, outfile, *, d=21, seed=0, episode_length=16, repeats=64,
+                     precision='mixed', device=None):
+    """gridsearch with proper scores: every grid point's ensemble forecast (`repeats` members per test file of cwd/indir, from
+    the file's row 0, common random numbers) is scored against the file's first `episode_length` rows by forecast_score.
+    Appends one CSV line per point in the reference's theta-major order (SCORE_FMT; SCORE_HEADER first when the file is new or
+    empty): the mean CRPS and energy score over hours 1 .. L - 1 and at hour L - 1, over all test files (and topics).  Returns,
+    per column, [value, theta, shift, alpha_scale] of the last minimum in grid order.  gridsearch itself is unchanged."""
+    if precision not in ('mixed', 'f64'):
+        raise ValueError("precision must be 'mixed' or 'f64'")
+    if not 1 <= int(repeats) <= L.FORECAST_MAX_REPEATS:
+        raise ValueError('repeats=%d outside [1, %d]' % (repeats, L.FORECAST_MAX_REPEATS))
+    emp = load_empirical(indir, int(d), int(episode_length))
+    points = grid_points(theta_range, shift_range, alpha_range)
+    if not points:
+        return best_score_points(points, [])
+    par = np.array(points, dtype=np.float64).reshape(-1, 3)
+    score = forecast_score(par[:, 0].copy(), par[:, 1].copy(), par[:, 2].copy(), emp, d=int(d), horizon=int(episode_length),
+                           seed=seed, repeats=int(repeats), precision=precision, device=device)
+    table = score_columns(score.summary)
+    header = not os.path.exists(outfile) or os.path.getsize(outfile) == 0
+    with open(outfile, 'a') as f:
+        if header:
+            f.write(SCORE_HEADER)
+        for point, res in zip(points, table):
+            f.write(SCORE_FMT % (tuple(point) + tuple(res)))
+    return best_score_points(points, table)
+
+
 # --------------------------------------------------------------------------------------------- backward-equation check
 # The scoring half of the reference's synthetic sweep (evaluate_synthetic / evaluate_synthetic_JSD, mfg_synthetic.py:741-899,
 # once per learner in its __main__, :902-925) for K policies at once: one mfg_consistency_pop call rolls every policy from
@@ -803,6 +971,42 @@ class _Population:
                 self._rng_step = first_step
             raise
         return Forecast(res['mean'], res['std'], res['quant'], probs, ranks, res['curves'], R, res['traj'])
+
+    @_with_ctx
+    def forecast_score(self, pi0=None, indir=None, horizon=16, repeats=256, *, emp=None, want_energy=True):
+        """The proper scores (a ForecastScore with a leading K) of every learner's ensemble forecast against held-out rows: the
+        first `horizon` rows of each file of cwd/indir, or `emp` [N, >= horizon, >= d].  The members are those forecast() rolls
+        from the same state (start rows `pi0`, or row 0 of each held-out matrix; learner k's own seed, the population's Philox
+        step) and stay on the device.  Advances the Philox step by horizon - 1, as forecast() does (restored when the library
+        refuses the call).  Failed learners are not launched: NaN rows, counts -1.  MfgError when a mixed-precision policy left
+        the fp32 range."""
+        if (indir is None) == (emp is None):
+            raise ValueError('a forecast is scored against held-out rows: give indir or emp (not both)')
+        if indir is not None:
+            emp = load_empirical(indir, self.d, int(horizon))
+        start, emp, H = _score_inputs(pi0, emp, self.d, horizon)
+        ops.check_forecast_args(start.shape, H, repeats, (), self.precision)
+        R, N = int(repeats), start.shape[0]
+        first_step = self._rng_step
+        self._rng_step += H - 1                      # (a diverged launch has run: its step is spent, as in train())
+        live = self._healthy()
+        sub = (lambda t: t) if len(live) == self.K else (lambda t: t[torch.as_tensor(live, device=self.device)].contiguous())
+        res = {'crps': np.full((self.K, N, H, self.d), np.nan), 'less': np.full((self.K, N, H, self.d), -1, dtype=np.int32),
+               'equal': np.full((self.K, N, H, self.d), -1, dtype=np.int32),
+               'energy': np.full((self.K, N, H), np.nan) if want_energy else None, 'summary': np.full((self.K, H, 2), np.nan)}
+        try:
+            if live:
+                got = forecast_score_policies(start, emp, sub(self._theta), sub(self._shifts_dev), sub(self._alphas_dev),
+                                              sub(self._seeds_dev), H, first_step, R, self.precision, self.device, self._ctx,
+                                              want_energy)
+                for key, a in res.items():
+                    if a is not None:
+                        a[live] = got[key]
+        except L.MfgError as e:
+            if e.code:                               # refused by the library before anything was launched
+                self._rng_step = first_step
+            raise
+        return ForecastScore(res['crps'], res['less'], res['equal'], res['energy'], res['summary'], R)
 
     def learner(self, k):
         """An actor_critic holding learner k's parameters, table and Philox position (for evaluate / generate_trajectory

@@ -577,6 +577,42 @@ int mfg_forecast_pop(const float* start32, int64_t N, int H, int d, int K, const
                      const int32_t* ranks, int Q, const float* emp32, const double* emp64, double* mean, double* std, float* quant,
                      double* curves, float* pi_traj, void* workspace, size_t workspace_bytes, mfg_stream_t stream);
 
+/* Proper scores of an ensemble forecast: CRPS per topic, the energy score per histogram and the rank of the observation among
+ * the members (Gneiting & Raftery, Strictly Proper Scoring Rules, Prediction, and Estimation, JASA 2007; kernel forms, beta = 1).
+ * This goes beyond the reference, whose only quality numbers are the L1 / JSD tables of ONE sample path (evaluate,
+ * mfg_ac2.py:595-670; the VAR baseline, var.py:330-416), and beyond mfg_forecast_pop, whose curves score single members too:
+ * here the forecast DISTRIBUTION is scored.  The entry scores GIVEN members (no rollouts) in at most TWO launches, no host
+ * synchronisation, no allocation, on `stream`.
+ *   traj [K, N R, H, d] fp32: the members as mfg_forecast_pop writes pi_traj (R = repeats): member r of start row n is row
+ *   r N + n.  emp32, emp64 [N,H,d]: the held-out rows y.  For cell (k, n, l) with members x_r and observation y:
+ *   crps [K,N,H,d] fp64: 1/R sum_r |x_rc - y_c| - 1/(2 R^2) sum_{r,s} |x_rc - x_sc|, y from emp64, members widened to fp64.
+ *     Order: lane r mod 64 of the column's wave adds |x_r - y| over r, r + 64, ... in member order, the 64 lane values go
+ *     through an xor butterfly (offsets 32, 16, ..., 1); the double sum is 2 sum_i (2 i - R + 1) x_(i) over the ascending
+ *     column (0-based), lane i mod 64 adding entries i, i + 64, ..., then the butterfly; crps = first / R - second / R^2.
+ *   less, equal [K,N,H,d] int32: #{r : x_rc < y32_c} and #{r : x_rc == y32_c}, fp32 comparisons against emp32: exact.
+ *   energy [K,N,H] fp64 or NULL (then the O(R^2 d) pass is skipped): 1/R sum_r ||x_r - y||_2 - 1/(2 R^2) sum_{r,s} ||x_r - x_s||_2,
+ *     differences, squares and sqrt in fp64, the d squares of a norm added in column order (fused multiply-add).  Order: the
+ *     members go in tiles of MFG_FORECAST_SCORE_TILE; every unordered pair r < s is taken once, by the thread (wave w, lane j)
+ *     with r mod TILE = w (mod 4) and s mod TILE = j; a thread adds its norms to one fp64 partial in the order (tile of r,
+ *     tile of s, r) ascending; the 64 lane partials go through the butterfly, the four wave totals are added in wave order and
+ *     doubled by the formula: energy = first / R - (sum_{r<s}) / R^2.  The first sum: lane r mod 64 of wave 0 adds
+ *     ||x_r - y|| over r, r + 64, ..., then the butterfly.
+ *   summary [K,H,2] fp64: per policy and hour the mean of crps over (n, c) and of energy over n (NaN without energy): a cell's
+ *     d CRPS values are added in column order, lane n mod 64 adds the cells n, n + 64, ..., then the butterfly -- an order that
+ *     does not depend on K.
+ *   A cell that holds a non-finite member or observation gets NaN scores and -1 counts (and its hour's summary is NaN); every
+ *   other cell is as without it.  Policy k's outputs depend on policy k alone: the same bits whatever K is and run to run
+ *   (no floating-point atomics).  With R = 1: crps = |x - y|, energy = ||x - y||.  When every member equals y and emp64 is
+ *   fp32-representable, crps and energy are exactly 0, less 0 and equal R (hour 0 of a forecast).
+ *   workspace: mfg_forecast_score_workspace_bytes(N, H, d, K, repeats) bytes, 8-byte aligned; contents are scratch.
+ * Checked before anything is launched: no null pointer but energy, 1 <= K <= MFG_POP_MAX_K, N, d, repeats >= 1, H >= 2,
+ * N H < 2^31 (MFG_EINVAL); d <= 64, repeats <= MFG_FORECAST_MAX_REPEATS (MFG_EUNSUPPORTED); the workspace (MFG_EWORKSPACE). */
+#define MFG_FORECAST_SCORE_TILE 64
+size_t mfg_forecast_score_workspace_bytes(int64_t N, int H, int d, int K, int repeats);
+int mfg_forecast_score(const float* traj, int64_t N, int H, int d, int K, int repeats, const float* emp32, const double* emp64,
+                       double* crps, int32_t* less, int32_t* equal, double* energy, double* summary, void* workspace,
+                       size_t workspace_bytes, mfg_stream_t stream);
+
 /* Distribution summary of R rows of N fp32 values in ONE launch, one workgroup per row: what plot_reward_distribution and
  * its two siblings (ac_irl.py:1046-1263) take from plt.hist (np.histogram, :1116-1119) and gaussian_kde (:1087-1100) for each
  * of their reward sets.  Row r is values[r stride .. r stride + N), stride >= N; everything below is on x = (double)values.
