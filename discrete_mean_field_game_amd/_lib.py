@@ -26,6 +26,7 @@ RN_TRAIN_MAX_TRAJ = 64          # MFG_RN_TRAIN_MAX_TRAJ
 FORECAST_MAX_RANKS = 8          # MFG_FORECAST_MAX_RANKS: order statistics of one mfg_forecast_pop call
 FORECAST_MAX_REPEATS = 1024     # MFG_FORECAST_MAX_REPEATS: members per start state of one mfg_forecast_pop call
 FORECAST_SCORE_TILE = 64        # MFG_FORECAST_SCORE_TILE: members per tile of mfg_forecast_score's energy pass
+AGENTS_MAX = 1 << 24            # MFG_AGENTS_MAX: agents of one finite-population member
 DIST_MAX_BINS = 1024            # MFG_DIST_MAX_BINS: histogram bins of one mfg_row_distribution call
 DIST_MAX_GRID = 4096            # MFG_DIST_MAX_GRID: KDE grid points of one mfg_row_distribution call
 DIST_NONFINITE, DIST_NO_KDE = 1, 2      # MFG_DIST_NONFINITE / MFG_DIST_NO_KDE: bits of a row's status
@@ -199,6 +200,13 @@ SIGNATURES['mfg_forecast_pop'] = (_i32, [_p, _i64, _i32, _i32, _i32, _p, _p, _p,
 # workspace_bytes, stream
 SIGNATURES['mfg_forecast_score_workspace_bytes'] = (_sz, [_i64, _i32, _i32, _i32, _i32])
 SIGNATURES['mfg_forecast_score'] = (_i32, [_p, _i64, _i32, _i32, _i32, _i32, _p, _p, _p, _p, _p, _p, _p, _p, _sz, _p])
+
+# finite-population members.  step: counts, P, B, d, K, agents, seed, step, traj_offset, counts_next, pi_next, moves, stream;
+# forecast: mfg_forecast_pop's arguments with counts0 for start32, `agents` behind K, counts_traj and actions behind pi_traj
+SIGNATURES['mfg_agents_step_pop'] = (_i32, [_p, _p, _i64, _i32, _i32, _i32, _p, _u32, _u64, _p, _p, _p, _p])
+SIGNATURES['mfg_forecast_agents_pop_workspace_bytes'] = (_sz, [_i64, _i32, _i32, _i32, _i32, _i32, _i32])
+SIGNATURES['mfg_forecast_agents_pop'] = (_i32, [_p, _i64, _i32, _i32, _i32, _i32, _p, _p, _p, _p, _u32, _i32, _i32,
+                                                C.POINTER(C.c_int32), _i32, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _sz, _p])
 
 # the backward-equation check.  given: P, K, M, T, d, metrics, steps, V, workspace, workspace_bytes, stream; pop: start32, N, H,
 # d, K, theta, shift, alpha_scale, seed, first_step, repeats, precision, metrics, steps, V, actions, pi_traj, workspace,

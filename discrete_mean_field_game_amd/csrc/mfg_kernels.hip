@@ -24,6 +24,7 @@
 #include "mfg_core.h"
 #include "mfg_evaluate_pop.h"
 #include "mfg_forecast_pop.h"
+#include "mfg_agents.h"
 #include "mfg_consistency_pop.h"
 #include "mfg_irl_population.h"
 #include "mfg_population.h"
@@ -1393,6 +1394,126 @@ int mfg_forecast_pop(const float* start32, int64_t N, int H, int d, int K, const
   if (!emp32) return MFG_OK;
   launch_forecast_curves(traj, emp32, emp64, N, H, d, NR, K, per_step, curves, S(stream));
   return check_launch("forecast_pop curves");
+}
+
+// ---- finite-population forecast (mfg_agents.h): the sampling kernel and k_agents_step in turn, then the forecast's reductions ----
+size_t mfg_forecast_agents_pop_workspace_bytes(int64_t N, int H, int d, int K, int repeats, int traj_given, int counts_given) {
+  if (N < 1 || H < 1 || d < 1 || K < 1 || repeats < 1) return 0;
+  return forecast_agents_workspace_bytes(N, H, d, K, repeats, traj_given != 0, counts_given != 0);
+}
+
+int mfg_forecast_agents_pop(const int32_t* counts0, int64_t N, int H, int d, int K, int agents, const double* theta,
+                            const double* shift, const double* alpha_scale, const uint64_t* seed, uint32_t first_step, int repeats,
+                            int precision, const int32_t* ranks, int Q, const float* emp32, const double* emp64, double* mean,
+                            double* std, float* quant, double* curves, float* pi_traj, int32_t* counts_traj, float* actions,
+                            void* workspace, size_t workspace_bytes, mfg_stream_t stream) {
+  REQUIRE(K >= 1 && K <= MFG_POP_MAX_K, "population size K outside [1, MFG_POP_MAX_K]");
+  REQUIRE(d >= 1, "d < 1");
+  if (d > WAVE) return fail(MFG_EUNSUPPORTED, "finite-population forecast: d=%d > 64 (as for the populations)", d);
+  REQUIRE(H >= 2, "horizon H < 2");
+  REQUIRE(N >= 1, "no start states (N < 1)");
+  REQUIRE(repeats >= 1, "repeats < 1");
+  REQUIRE(agents >= 1 && agents <= MFG_AGENTS_MAX, "agents outside [1, MFG_AGENTS_MAX]");
+  REQUIRE(N * (int64_t)H <= 0x7FFFFFFF && N * (int64_t)repeats <= 0x7FFFFFFF, "N H or N repeats too large");
+  REQUIRE(counts0 && theta && shift && alpha_scale && seed && mean && std && workspace, "null pointer");
+  CHECK_PRECISION();
+  REQUIRE((uint64_t)first_step + (uint64_t)(H - 1) <= 0xFFFFFFFFull, "Philox step counter would wrap");
+  REQUIRE(Q >= 0 && Q <= MFG_FORECAST_MAX_RANKS, "number of ranks Q outside [0, MFG_FORECAST_MAX_RANKS]");
+  REQUIRE(Q == 0 || (ranks && quant), "ranks / quant: null pointer with Q > 0");
+  ForecastRanks fr{};
+  for (int q = 0; q < Q; ++q) {
+    REQUIRE(ranks[q] >= 0 && ranks[q] < repeats, "a rank outside [0, repeats)");
+    fr.r[q] = ranks[q];
+  }
+  REQUIRE((emp32 != nullptr) == (emp64 != nullptr), "emp32 and emp64: both or neither");
+  REQUIRE((curves != nullptr) == (emp32 != nullptr), "curves is given exactly when emp32 / emp64 are");
+  if (repeats > MFG_FORECAST_MAX_REPEATS)
+    return fail(MFG_EUNSUPPORTED, "finite-population forecast: repeats=%d > MFG_FORECAST_MAX_REPEATS=%d", repeats,
+                MFG_FORECAST_MAX_REPEATS);
+  const size_t need = forecast_agents_workspace_bytes(N, H, d, K, repeats, pi_traj != nullptr, counts_traj != nullptr);
+  if (workspace_bytes < need)
+    return fail(MFG_EWORKSPACE, "finite-population forecast workspace: need %lld bytes, have %lld", (long long)need,
+                (long long)workspace_bytes);
+  REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 7) == 0, "workspace not 8-byte aligned");
+  const int64_t NR = N * repeats;
+  PopArgs p = pop_args(K, NR, d, 1, 0, seed, shift, alpha_scale, nullptr, nullptr, 0);
+  p.N = NR;  // (member j reads row j of its learner's current rows: the start-index table is the identity)
+  p.L = 1;
+  p.s_idx = eval_pop_idx_stride(NR);
+  p.idx = reinterpret_cast<int32_t*>(workspace);
+  p.s_pi0 = NR * d;
+  p.s_P = NR * d * d;
+  char* at = reinterpret_cast<char*>(workspace) + (size_t)K * p.s_idx * 4;
+  double* per_step = reinterpret_cast<double*>(at);
+  at += (size_t)K * H * NR * 2 * 8;
+  float* cur = reinterpret_cast<float*>(at);
+  at += agents_pad8((size_t)K * NR * d * 4);
+  float* P_step = reinterpret_cast<float*>(at);
+  at += agents_pad8((size_t)K * NR * d * d * 4);
+  float* traj = pi_traj;
+  if (!traj) {
+    traj = reinterpret_cast<float*>(at);
+    at += agents_pad8((size_t)K * NR * H * d * 4);
+  }
+  int32_t* ctraj = counts_traj ? counts_traj : reinterpret_cast<int32_t*>(at);
+  // The sticky status word is examined ONCE, here, before anything is launched (launch_core's rule: a range report of an
+  // earlier mixed-precision launch refuses a mixed-precision call).  The H - 1 sampling launches below then go ahead whatever
+  // the device reports meanwhile, as the one launch of mfg_forecast_pop does: a policy that leaves the range in this call has
+  // unspecified actions (each of its members fails or stays a histogram of its agents), the other policies are complete,
+  // the call returns MFG_OK and the NEXT call is refused -- whatever the host's timing.
+  {
+    const StatusWord sw = status_word();
+    if (!sw.host) return fail(MFG_ELAUNCH, "%s", "status word allocation failed");
+    const unsigned bits = g_status_check_deferred ? 0u : *(volatile unsigned*)sw.host;
+    const unsigned blocking = precision == MFG_PRECISION_MIXED ? bits : (bits & ~(unsigned)MFG_STATUS_MIXED_RANGE);
+    if (blocking) return status_error(blocking);
+  }
+  struct DeferGuard {
+    const bool was = g_status_check_deferred;
+    DeferGuard() { g_status_check_deferred = true; }
+    ~DeferGuard() { g_status_check_deferred = was; }
+  } defer_guard;
+  launch_agents_init(counts0, N, NR, H, d, K, agents, ctraj, traj, cur, S(stream));
+  int rc = check_launch("forecast_agents_pop init");
+  if (rc != MFG_OK) return rc;
+  CoreArgs a{};
+  a.pi0 = cur;
+  a.num_start = NR;
+  a.theta = theta;
+  a.gamma = 1.0;
+  a.B = NR;
+  a.d = d;
+  a.T = 1;
+  a.reward_kind = MFG_REWARD_EXTERNAL;  // (actions only: no reward is formed)
+  a.P_out = P_step;
+  AgentsArgs g{};
+  g.cs_k = g.ns_k = g.ps_k = NR * H * d;
+  g.cs_m = g.ns_m = g.ps_m = (int64_t)H * d;
+  g.P = P_step;
+  g.pi_cur = cur;
+  g.as_k = NR * (int64_t)(H - 1) * d * d;
+  g.as_m = (int64_t)(H - 1) * d * d;
+  g.seed = seed;
+  g.B = NR;
+  g.d = d;
+  g.agents = agents;
+  for (int t = 0; t < H - 1; ++t) {
+    a.first_step = first_step + (uint32_t)t;
+    if ((rc = launch_core(a, true, false, precision, S(stream), &p)) != MFG_OK) return rc;
+    g.counts = ctraj + (int64_t)t * d;
+    g.counts_next = ctraj + (int64_t)(t + 1) * d;
+    g.pi_next = traj + (int64_t)(t + 1) * d;
+    g.P_copy = actions ? actions + (int64_t)t * d * d : nullptr;
+    g.step = a.first_step;
+    launch_agents_step(g, K, S(stream));
+    if ((rc = check_launch("forecast_agents_pop step")) != MFG_OK) return rc;
+  }
+  rc = launch_forecast_reduce(traj, N, H, d, K, repeats, fr, Q, mean, std, quant, S(stream));
+  if (rc != MFG_OK) return fail(rc, "%s", "forecast reduce: LDS request beyond the budget");
+  if ((rc = check_launch("forecast_agents_pop reduce")) != MFG_OK) return rc;
+  if (!emp32) return MFG_OK;
+  launch_forecast_curves(traj, emp32, emp64, N, H, d, NR, K, per_step, curves, S(stream));
+  return check_launch("forecast_agents_pop curves");
 }
 
 // ---- backward-equation check (mfg_consistency_pop.h): the scan and the reduction of K groups; with the rollouts three launches ----

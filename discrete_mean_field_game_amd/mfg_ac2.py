@@ -868,6 +868,61 @@ class actor_critic:
         return population.ForecastScore(pick(got['crps']), pick(got['less']), pick(got['equal']), pick(got['energy']),
                                         pick(got['summary']), repeats)
 
+    def _one_policy(self, steps, run):
+        """run(theta, shift, alpha_scale, seeds [1] device tensors, first_step) with _rng_step advanced by `steps` (restored
+        when the library refuses the call)."""
+        first_step = self._rng_step
+        self._rng_step += steps
+        dev = self.device
+        one = lambda v: torch.as_tensor(np.array([float(v)], dtype=np.float64), device=dev)
+        seeds = torch.as_tensor(np.array([self.seed & 0xFFFFFFFFFFFFFFFF], dtype=np.uint64).view(np.int64), device=dev)
+        self._flush_pending()
+        try:
+            return run(self._theta.reshape(1).contiguous(), one(self.shift), one(self.alpha_scale), seeds, first_step)
+        except L.MfgError as e:
+            if e.code:                               # refused by the library before anything was launched
+                self._rng_step = first_step
+            raise
+
+    @_with_ctx
+    def forecast_agents(self, pi0, total_hours, repeats=256, probs=(0.05, 0.5, 0.95), *, agents, emp=None, want_traj=False,
+                        want_counts=False):
+        """forecast() for a population of `agents` agents per member (mfg_forecast_agents_pop, K = 1): every member starts from
+        the counts population.apportion(pi0 row, agents), draws its action as forecast()'s member does from its own histogram
+        row and then moves each agent by a draw from the action's row of the agent's topic -- the sampling noise of order
+        1 / sqrt(agents) that the mean-field rows leave out.  Seed, Philox steps, member ids and _rng_step as forecast().
+        Returns a population.Forecast without the leading K; want_counts adds its counts [N repeats, H, d] int32."""
+        from . import population
+        check_forecast_rng(self.rng)
+        as_tensor = isinstance(pi0, torch.Tensor)
+        ranks = population.forecast_ranks(probs, repeats)
+        start, emp = population._forecast_inputs(_as_np(pi0), None if emp is None else _as_np(emp), self.d, total_hours)
+        agents = ops.check_forecast_agents_args(start.shape, agents, total_hours, repeats, ranks, self.precision)[-1]
+        population.apportion(start, agents)
+        H = int(total_hours)
+        got = self._one_policy(H - 1, lambda th, sh, al, sd, first_step: population.forecast_agents_policies(
+            start, emp, agents, th, sh, al, sd, H, first_step, int(repeats), ranks, self.precision, self.device, self._ctx,
+            want_traj, want_counts))
+        pick = lambda a: None if a is None else (torch.as_tensor(a[0], device=self.device) if as_tensor else a[0])
+        return population.Forecast(pick(got['mean']), pick(got['std']), pick(got['quant']), probs, ranks, pick(got['curves']),
+                                   repeats, pick(got['traj']), counts=pick(got['counts']))
+
+    @_with_ctx
+    def forecast_agents_score(self, pi0, total_hours, repeats=256, *, agents, emp, want_energy=True):
+        """forecast_score() of forecast_agents()'s members (`agents` agents each), scored on the device by the same
+        mfg_forecast_score.  Returns a population.ForecastScore without the leading K."""
+        from . import population
+        check_forecast_rng(self.rng)
+        start, emp, H = population._score_inputs(None if pi0 is None else _as_np(pi0), None if emp is None else _as_np(emp),
+                                                 self.d, total_hours)
+        agents = ops.check_forecast_agents_args(start.shape, agents, H, repeats, (), self.precision)[-1]
+        population.apportion(start, agents)
+        got = self._one_policy(H - 1, lambda th, sh, al, sd, first_step: population.forecast_agents_score_policies(
+            start, emp, agents, th, sh, al, sd, H, first_step, int(repeats), self.precision, self.device, self._ctx, want_energy))
+        pick = lambda a: None if a is None else a[0]
+        return population.ForecastScore(pick(got['crps']), pick(got['less']), pick(got['equal']), pick(got['energy']),
+                                        pick(got['summary']), repeats)
+
     _EVAL_HEADER = ('theta,shift,alpha_scale,mean_l1_final,std_l1_final,mean_l1_mean,std_l1_mean,'
                     'mean_JSD_final,std_JSD_final,mean_JSD_mean,std_JSD_mean\n')
     _EVAL_FMT = '%f,%f,%f,%.3e,%.3e,%.3e,%.3e,%.3e,%.3e,%.3e,%.3e\n'    # one CSV line: theta, shift, alpha_scale, the 8 metrics

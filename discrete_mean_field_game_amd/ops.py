@@ -1031,6 +1031,107 @@ def forecast_pop(start32, thetas, shifts, alpha_scales, seeds, horizon, first_st
     return out
 
 
+def _chk_i32(t, name):
+    if not (t.is_cuda and t.dtype == torch.int32 and t.is_contiguous()):
+        raise ValueError('%s must be a contiguous int32 CUDA tensor' % name)
+    return t
+
+
+def check_agents(agents):
+    """`agents` as an int in [1, AGENTS_MAX] (ValueError otherwise)."""
+    if isinstance(agents, bool) or int(agents) != agents:
+        raise ValueError('agents=%r: a whole number of agents' % (agents,))
+    agents = int(agents)
+    if not 1 <= agents <= L.AGENTS_MAX:
+        raise ValueError('agents=%d outside [1, %d] (MFG_AGENTS_MAX)' % (agents, L.AGENTS_MAX))
+    return agents
+
+
+def agents_step_pop(counts, P, agents, seeds, step=0, traj_offset=0, want_pi=True, want_moves=False):
+    """One resampling step of finite-population members in one launch (mfg_agents_step_pop): counts [K,B,d] int32 (each row
+    summing to `agents`), P [K,B,d,d] fp32 the members' actions, seeds int64 (read as uint64) device array [K].  Every agent of
+    topic i of member (k, b) -- Philox (seeds[k], step, member id traj_offset + b) -- moves to a topic drawn from P[k,b,i,:].
+    Returns (counts_next [K,B,d] int32, pi_next [K,B,d] fp32 = counts_next / agents or None, moves [K,B,d,d] int32 or None);
+    a member with an unusable row (a sum that is not finite or <= 0 under agents, a count outside [0, agents]) gets -1 / NaN."""
+    _chk_i32(counts, 'counts'); _chk_f32(P, 'P')
+    if counts.dim() != 3:
+        raise ValueError('counts: expected [K, B, d], got %s' % (tuple(counts.shape),))
+    K, B, d = counts.shape
+    if tuple(P.shape) != (K, B, d, d):
+        raise ValueError('P: expected [%d, %d, %d, %d], got %s' % (K, B, d, d, tuple(P.shape)))
+    if not 1 <= d <= 64:
+        raise ValueError('d=%d: finite populations cover d <= 64 (as the populations do)' % d)
+    agents = check_agents(agents)
+    _chk_pop(K, 'seeds', seeds, torch.int64)
+    dev = counts.device
+    counts_next = torch.empty_like(counts)
+    pi_next = torch.empty(K, B, d, dtype=torch.float32, device=dev) if want_pi else None
+    moves = torch.empty(K, B, d, d, dtype=torch.int32, device=dev) if want_moves else None
+    L.check(L.lib().mfg_agents_step_pop(counts.data_ptr(), P.data_ptr(), B, d, K, agents, seeds.data_ptr(), int(step),
+                                        int(traj_offset), counts_next.data_ptr(), _ptr(pi_next), _ptr(moves), _stream()),
+            'mfg_agents_step_pop')
+    return counts_next, pi_next, moves
+
+
+def forecast_agents_pop_workspace(N, horizon, d, K, repeats, traj_given, counts_given, device):
+    """The scratch buffer of one forecast_agents_pop call (mfg_forecast_agents_pop_workspace_bytes; whole doubles)."""
+    nbytes = int(L.lib().mfg_forecast_agents_pop_workspace_bytes(int(N), int(horizon), int(d), int(K), int(repeats),
+                                                                 int(bool(traj_given)), int(bool(counts_given))))
+    return torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=device)
+
+
+def check_forecast_agents_args(counts_shape, agents, horizon, repeats, ranks, precision, emp32_shape=None, emp64_shape=None):
+    """The argument rules of forecast_agents_pop that need no GPU (ValueError): those of check_forecast_args with counts0
+    [N, d] for start32, 1 <= d <= 64, and agents a whole number in [1, AGENTS_MAX].  Returns (N, d, horizon, repeats, ranks as a
+    list of ints, agents)."""
+    N, d, horizon, repeats, ranks = check_forecast_args(counts_shape, horizon, repeats, ranks, precision, emp32_shape, emp64_shape)
+    if not 1 <= d <= 64:
+        raise ValueError('d=%d: finite populations cover d <= 64 (as the populations do)' % d)
+    return N, d, horizon, repeats, ranks, check_agents(agents)
+
+
+def forecast_agents_pop(counts0, agents, thetas, shifts, alpha_scales, seeds, horizon, first_step=0, repeats=1, ranks=(),
+                        precision='mixed', emp32=None, emp64=None, want_traj=False, want_counts=False, want_actions=False, ws=None):
+    """forecast_pop with finite-population members (mfg_forecast_agents_pop): counts0 [N,d] int32 the start counts, each row
+    summing to `agents`.  Member j of learner k draws its action as forecast_pop's member j does -- from the histogram row of its
+    counts, under Philox (seeds[k], first_step + t, j) -- and then moves each of its agents by a draw from the action's row of
+    the agent's topic.  Returns forecast_pop's dict (mean, std, quant, curves, traj) with counts [K, N repeats, horizon, d] int32
+    (want_counts) and actions [K, N repeats, horizon - 1, d, d] fp32 (want_actions), None otherwise."""
+    import ctypes as C
+    _chk_i32(counts0, 'counts0')
+    if emp32 is not None:
+        _chk_f32(emp32, 'emp32')
+    if emp64 is not None:
+        _chk_f64(emp64, 'emp64')
+    N, d, H, repeats, ranks, agents = check_forecast_agents_args(
+        counts0.shape, agents, horizon, repeats, ranks, precision, None if emp32 is None else emp32.shape,
+        None if emp64 is None else emp64.shape)
+    K = thetas.numel()
+    _chk_pop(K, 'thetas', thetas, torch.float64)
+    for name, t in (('shifts', shifts), ('alpha_scales', alpha_scales)):
+        _chk_pop(K, name, t, torch.float64)
+    _chk_pop(K, 'seeds', seeds, torch.int64)
+    dev = counts0.device
+    Q, NR = len(ranks), N * repeats
+    out = {'mean': torch.empty(K, N, H, d, dtype=torch.float64, device=dev),
+           'std': torch.empty(K, N, H, d, dtype=torch.float64, device=dev),
+           'quant': torch.empty(K, N, H, Q, d, dtype=torch.float32, device=dev) if Q else None,
+           'curves': torch.empty(K, H, 4, dtype=torch.float64, device=dev) if emp32 is not None else None,
+           'traj': torch.empty(K, NR, H, d, dtype=torch.float32, device=dev) if want_traj else None,
+           'counts': torch.empty(K, NR, H, d, dtype=torch.int32, device=dev) if want_counts else None,
+           'actions': torch.empty(K, NR, H - 1, d, d, dtype=torch.float32, device=dev) if want_actions else None}
+    if ws is None:
+        ws = forecast_agents_pop_workspace(N, H, d, K, repeats, want_traj, want_counts, dev)
+    rk = (C.c_int32 * max(Q, 1))(*ranks)
+    L.check(L.lib().mfg_forecast_agents_pop(counts0.data_ptr(), N, H, d, K, agents, thetas.data_ptr(), shifts.data_ptr(),
+                                            alpha_scales.data_ptr(), seeds.data_ptr(), int(first_step), repeats,
+                                            L.PRECISIONS[precision], rk, Q, _ptr(emp32), _ptr(emp64), out['mean'].data_ptr(),
+                                            out['std'].data_ptr(), _ptr(out['quant']), _ptr(out['curves']), _ptr(out['traj']),
+                                            _ptr(out['counts']), _ptr(out['actions']), ws.data_ptr(),
+                                            ws.numel() * ws.element_size(), _stream()), 'mfg_forecast_agents_pop')
+    return out
+
+
 def forecast_score_workspace_bytes(N, horizon, d, K, repeats):
     """mfg_forecast_score_workspace_bytes: the scratch bytes of one forecast_score call (needs the library, no GPU)."""
     return int(L.lib().mfg_forecast_score_workspace_bytes(int(N), int(horizon), int(d), int(K), int(repeats)))

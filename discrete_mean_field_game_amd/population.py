@@ -349,17 +349,19 @@ class Forecast:
     """The result of a forecast (NumPy): mean, std [K, N, H, d] over the ensemble of each start state; quantiles
     [K, N, H, Q, d], the order statistics of ranks[q] = floor(probs[q] (R - 1)); curves [K, H, 4] = (l1_mean, l1_std, jsd_mean,
     jsd_std) per hour against the held-out rows, or None without them; traj [K, N R, H, d], the members, only when asked for.
-    A single-policy forecast (actor_critic.forecast) drops the leading K."""
+    A single-policy forecast (actor_critic.forecast) drops the leading K.  counts [K, N R, H, d] int32: the members' agent
+    counts, from a finite-population forecast (forecast_agents) that was asked for them; None otherwise."""
 
-    def __init__(self, mean, std, quantiles, probs, ranks, curves, repeats, traj=None):
+    def __init__(self, mean, std, quantiles, probs, ranks, curves, repeats, traj=None, counts=None):
         self.mean, self.std, self.quantiles, self.curves, self.traj = mean, std, quantiles, curves, traj
         self.probs, self.ranks, self.repeats = tuple(probs), tuple(ranks), int(repeats)
+        self.counts = counts
 
     def learner(self, k):
         """Row k as a Forecast of its own."""
         pick = lambda a: None if a is None else a[k]
         return Forecast(pick(self.mean), pick(self.std), pick(self.quantiles), self.probs, self.ranks, pick(self.curves),
-                        self.repeats, pick(self.traj))
+                        self.repeats, pick(self.traj), pick(self.counts))
 
 
 def forecast_policies(start, emp, thetas, shifts, alpha_scales, seeds, horizon, first_step, repeats, ranks, precision, device, ctx,
@@ -623,6 +625,171 @@ def gridsearch_score(theta_range, shift_range, alpha_range, indir, outfile, *, d
         for point, res in zip(points, table):
             f.write(SCORE_FMT % (tuple(point) + tuple(res)))
     return best_score_points(points, table)
+
+
+# ------------------------------------------------------------------------------------------ finite-population forecasts
+# The members above follow pi' = P^T pi, the dynamics of infinitely many agents, and their only noise is the Dirichlet draw of P.
+# Here a member is ONE population of `agents` agents (mfg_forecast_agents_pop): every agent of topic i picks its next topic from
+# row P[i,:], so the histogram carries the sampling noise of order 1 / sqrt(agents) on top.  The same reductions and scores
+# apply, which makes `agents` a parameter one can fit with them -- and the N-player check of the mean-field model: how large a
+# population must be before the mean-field forecast holds.  The reference has no such path.
+def apportion(pi, agents):
+    """The start counts of a population of `agents` agents on the histogram rows `pi` ((d,) or [N, d]): int32, every row
+    summing to `agents` (largest-remainder rounding).  With x = (double)(float)pi and s the sequential sum of a row in column
+    order, q_i = x_i agents / s and c_i = floor(q_i); the agents - sum c_i left over go to the largest fractional parts q_i - c_i,
+    ties to the lower index.  A row whose agents pi is integral (pi fp32-representable) is reproduced exactly.  NumPy, needs no
+    GPU.  ValueError for agents outside [1, AGENTS_MAX], a negative or non-finite entry or a row that sums to 0."""
+    agents = ops.check_agents(agents)
+    x = np.asarray(pi, dtype=np.float64).astype(np.float32).astype(np.float64)
+    if x.ndim not in (1, 2) or x.shape[-1] < 1:
+        raise ValueError('pi: expected (d,) or [N, d], got %s' % (x.shape,))
+    rows = x.reshape(-1, x.shape[-1])
+    if not np.all(np.isfinite(rows)) or np.any(rows < 0):
+        raise ValueError('pi: a histogram row holds a negative or non-finite entry')
+    s = np.cumsum(rows, axis=1)[:, -1:]                  # (cumsum adds in column order)
+    if np.any(s <= 0):
+        raise ValueError('pi: a histogram row sums to 0')
+    q = rows * float(agents) / s
+    c = np.floor(q)
+    counts = c.astype(np.int64)
+    for r in range(rows.shape[0]):
+        left = agents - int(counts[r].sum())
+        frac = q[r] - c[r]
+        # the q_i add up to agents within agents d 2^-51 < 1 (three roundings per term, d - 1 in s; agents <= 2^24, d < 2^27), and
+        # sum floor(q_i) is a whole number not above that sum: never more than agents, and fewer than d short of it
+        assert 0 <= left <= rows.shape[1], (left, agents)
+        if left > 0:
+            counts[r, np.argsort(-frac, kind='stable')[:left]] += 1
+    return counts.astype(np.int32).reshape(x.shape)
+
+
+def _agents_emp(emp, device):
+    if emp is None:
+        return None, None
+    e64 = np.ascontiguousarray(emp, dtype=np.float64)
+    return torch.as_tensor(e64.astype(np.float32), device=device), torch.as_tensor(e64, device=device)
+
+
+def forecast_agents_policies(start, emp, agents, thetas, shifts, alpha_scales, seeds, horizon, first_step, repeats, ranks, precision,
+                             device, ctx, want_traj=False, want_counts=False):
+    """forecast_policies with finite-population members: one ops.forecast_agents_pop call from the counts apportion(start,
+    agents), as NumPy arrays (mean, std, quant, curves, traj, counts)."""
+    counts0 = torch.as_tensor(apportion(start, agents), device=device)
+    emp32, emp64 = _agents_emp(emp, device)
+    out = ops.forecast_agents_pop(counts0, agents, thetas, shifts, alpha_scales, seeds, horizon, first_step=first_step,
+                                  repeats=repeats, ranks=ranks, precision=precision, emp32=emp32, emp64=emp64,
+                                  want_traj=want_traj, want_counts=want_counts)
+    host = {k: None if v is None else v.cpu().numpy() for k, v in out.items() if k != 'actions'}
+    if precision == 'mixed' and ctx.status(synchronize=True):
+        raise L.MfgError('a mixed-precision forecast ran a policy with |theta| (1 + |shift|) > 86 (or theta not finite): '
+                         'the rows of its members are unspecified; use precision=\'f64\'')
+    if host['quant'] is None:
+        K, N = host['mean'].shape[:2]
+        host['quant'] = np.zeros((K, N, int(horizon), 0, host['mean'].shape[-1]), dtype=np.float32)
+    return host
+
+
+def forecast_agents(thetas, shifts, alpha_scales, pi0, horizon, *, d, agents, seed=0, repeats=256, probs=FORECAST_PROBS, emp=None,
+                    precision='mixed', device=None, first_step=0, want_traj=False, want_counts=False):
+    """forecast() for populations of `agents` agents (one value for the call, 1 <= agents <= AGENTS_MAX): every member starts
+    from the counts apportion(pi0 row, agents), draws its action as forecast()'s member does from its own histogram row (the
+    same seed, Philox steps and member ids: common random numbers across policies) and then moves each agent by a draw from the
+    action's row of the agent's topic.  As agents grows the members approach forecast()'s.  Returns a Forecast whose rows are
+    the histogram rows counts / agents; want_counts adds Forecast.counts [K, N repeats, horizon, d] int32.  Chunks, context and
+    errors as forecast()."""
+    if precision not in ('mixed', 'f64'):
+        raise ValueError("precision must be 'mixed' or 'f64'")
+    th = np.asarray(thetas, dtype=np.float64).reshape(-1)
+    K = th.shape[0]
+    if K < 1:
+        raise ValueError('no policies')
+    sh, al = broadcast('shifts', shifts, K), broadcast('alpha_scales', alpha_scales, K)
+    sd = broadcast('seed', seed, K, np.uint64).view(np.int64)
+    ranks = forecast_ranks(probs, repeats)
+    start, emp = _forecast_inputs(pi0, emp, d, horizon)
+    agents = ops.check_forecast_agents_args(start.shape, agents, horizon, repeats, ranks, precision)[-1]
+    apportion(start, agents)                             # (its ValueErrors ahead of the GPU)
+    if not torch.cuda.is_available():
+        raise L.MfgError('forecast_agents needs a ROCm GPU: the HIP hot path has no CPU fallback')
+    L.lib()
+    ops.init()
+    dev = torch.device(device) if device is not None else torch.device('cuda', torch.cuda.current_device())
+    ctx = ops.Context(dev)
+    prev = ctx.bind_scoped()
+    try:
+        parts = []
+        for c0 in range(0, K, FORECAST_CHUNK):
+            n = min(FORECAST_CHUNK, K - c0)
+            f = lambda a: torch.as_tensor(a[c0:c0 + n].copy(), device=dev)
+            parts.append(forecast_agents_policies(start, emp, agents, f(th), f(sh), f(al), f(sd), int(horizon), int(first_step),
+                                                  int(repeats), ranks, precision, dev, ctx, want_traj, want_counts))
+    finally:
+        ctx.restore(prev)
+        ctx.close()
+    cat = lambda key: None if parts[0][key] is None else np.concatenate([p[key] for p in parts])
+    return Forecast(cat('mean'), cat('std'), cat('quant'), probs, ranks, cat('curves'), repeats, cat('traj'), counts=cat('counts'))
+
+
+def forecast_agents_score_bytes(N, horizon, d, repeats):
+    """forecast_score_bytes with the finite-population forecast's workspace (the members given, the counts in the workspace)."""
+    N, H, d, R = int(N), int(horizon), int(d), int(repeats)
+    lib = L.lib()
+    outputs = N * H * d * (8 + 8 + 8 + 4 + 4) + N * H * 8 + H * 2 * 8
+    return (N * R * H * d * 4 + int(lib.mfg_forecast_agents_pop_workspace_bytes(N, H, d, 1, R, 1, 0))
+            + int(lib.mfg_forecast_score_workspace_bytes(N, H, d, 1, R)) + outputs)
+
+
+def forecast_agents_score_policies(start, emp, agents, thetas, shifts, alpha_scales, seeds, horizon, first_step, repeats, precision,
+                                   device, ctx, want_energy=True):
+    """forecast_score_policies with finite-population members: one ops.forecast_agents_pop call for the members and one
+    ops.forecast_score call on them; only the scores come to the host."""
+    counts0 = torch.as_tensor(apportion(start, agents), device=device)
+    emp32, emp64 = _agents_emp(emp, device)
+    traj = ops.forecast_agents_pop(counts0, agents, thetas, shifts, alpha_scales, seeds, horizon, first_step=first_step,
+                                   repeats=repeats, precision=precision, want_traj=True)['traj']
+    out = ops.forecast_score(traj, emp32, emp64, counts0.shape[0], repeats, want_energy=want_energy)
+    host = {k: None if v is None else v.cpu().numpy() for k, v in out.items()}
+    if precision == 'mixed' and ctx.status(synchronize=True):
+        raise L.MfgError('a mixed-precision forecast ran a policy with |theta| (1 + |shift|) > 86 (or theta not finite): '
+                         'the rows of its members are unspecified; use precision=\'f64\'')
+    return host
+
+
+def forecast_agents_score(thetas, shifts, alpha_scales, emp, *, d, agents, pi0=None, horizon=None, seed=0, repeats=256,
+                          precision='mixed', device=None, first_step=0, want_energy=True, budget=None):
+    """forecast_score() of forecast_agents()'s members: the proper scores of the finite-population ensemble of K policies
+    against the held-out rows `emp`, scored by the same ops.forecast_score without the members coming to the host.  Chunks under
+    `budget` as forecast_score (chunking changes no bit).  Returns a ForecastScore."""
+    if precision not in ('mixed', 'f64'):
+        raise ValueError("precision must be 'mixed' or 'f64'")
+    th = np.asarray(thetas, dtype=np.float64).reshape(-1)
+    K = th.shape[0]
+    if K < 1:
+        raise ValueError('no policies')
+    sh, al = broadcast('shifts', shifts, K), broadcast('alpha_scales', alpha_scales, K)
+    sd = broadcast('seed', seed, K, np.uint64).view(np.int64)
+    start, emp, H = _score_inputs(pi0, emp, d, horizon)
+    agents = ops.check_forecast_agents_args(start.shape, agents, H, repeats, (), precision)[-1]
+    apportion(start, agents)
+    N, R = start.shape[0], int(repeats)
+    chunks = consistency_chunks(K, forecast_agents_score_bytes(N, H, int(d), R), budget)
+    if not torch.cuda.is_available():
+        raise L.MfgError('forecast_agents_score needs a ROCm GPU: the HIP hot path has no CPU fallback')
+    ops.init()
+    dev = torch.device(device) if device is not None else torch.device('cuda', torch.cuda.current_device())
+    ctx = ops.Context(dev)
+    prev = ctx.bind_scoped()
+    try:
+        parts = []
+        for c0, n in chunks:
+            f = lambda a: torch.as_tensor(a[c0:c0 + n].copy(), device=dev)
+            parts.append(forecast_agents_score_policies(start, emp, agents, f(th), f(sh), f(al), f(sd), H, int(first_step), R,
+                                                        precision, dev, ctx, want_energy))
+    finally:
+        ctx.restore(prev)
+        ctx.close()
+    cat = lambda key: None if parts[0][key] is None else np.concatenate([p[key] for p in parts])
+    return ForecastScore(cat('crps'), cat('less'), cat('equal'), cat('energy'), cat('summary'), R)
 
 
 # --------------------------------------------------------------------------------------------- backward-equation check
@@ -1006,6 +1173,67 @@ class _Population:
             if e.code:                               # refused by the library before anything was launched
                 self._rng_step = first_step
             raise
+        return ForecastScore(res['crps'], res['less'], res['equal'], res['energy'], res['summary'], R)
+
+    def _run_live(self, res, steps, run):
+        """res[key][live learners] = run(sub)[key] with the Philox step advanced by `steps` (restored when the library refuses
+        the call); failed learners keep the fill of `res`."""
+        first_step = self._rng_step
+        self._rng_step += steps                      # (a diverged launch has run: its step is spent, as in train())
+        live = self._healthy()
+        sub = (lambda t: t) if len(live) == self.K else (lambda t: t[torch.as_tensor(live, device=self.device)].contiguous())
+        try:
+            if live:
+                got = run(sub, first_step)
+                for key, a in res.items():
+                    if a is not None:
+                        a[live] = got[key]
+        except L.MfgError as e:
+            if e.code:                               # refused by the library before anything was launched
+                self._rng_step = first_step
+            raise
+        return res
+
+    @_with_ctx
+    def forecast_agents(self, pi0=None, indir=None, horizon=16, repeats=256, probs=FORECAST_PROBS, *, agents, want_traj=False,
+                        want_counts=False):
+        """forecast() with finite-population members of `agents` agents each (population.forecast_agents at the learners'
+        parameters, seeds and Philox step): a Forecast with a leading K, with want_counts its counts.  Start rows, held-out rows,
+        the Philox step, failed learners (NaN rows, counts -1) and errors as forecast()."""
+        emp = load_empirical(indir, self.d, int(horizon)) if indir is not None else None
+        ranks = forecast_ranks(probs, repeats)
+        start, emp = _forecast_inputs(pi0, emp, self.d, horizon)
+        agents = ops.check_forecast_agents_args(start.shape, agents, horizon, repeats, ranks, self.precision)[-1]
+        apportion(start, agents)
+        H, R, N, Q = int(horizon), int(repeats), start.shape[0], len(ranks)
+        res = {'mean': np.full((self.K, N, H, self.d), np.nan), 'std': np.full((self.K, N, H, self.d), np.nan),
+               'quant': np.full((self.K, N, H, Q, self.d), np.nan, dtype=np.float32),
+               'curves': None if emp is None else np.full((self.K, H, 4), np.nan),
+               'traj': np.full((self.K, N * R, H, self.d), np.nan, dtype=np.float32) if want_traj else None,
+               'counts': np.full((self.K, N * R, H, self.d), -1, dtype=np.int32) if want_counts else None}
+        self._run_live(res, H - 1, lambda sub, first_step: forecast_agents_policies(
+            start, emp, agents, sub(self._theta), sub(self._shifts_dev), sub(self._alphas_dev), sub(self._seeds_dev), H, first_step,
+            R, ranks, self.precision, self.device, self._ctx, want_traj, want_counts))
+        return Forecast(res['mean'], res['std'], res['quant'], probs, ranks, res['curves'], R, res['traj'], counts=res['counts'])
+
+    @_with_ctx
+    def forecast_agents_score(self, pi0=None, indir=None, horizon=16, repeats=256, *, agents, emp=None, want_energy=True):
+        """forecast_score() of forecast_agents()'s members (`agents` agents each): a ForecastScore with a leading K.  Held-out
+        rows, start rows, the Philox step, failed learners and errors as forecast_score()."""
+        if (indir is None) == (emp is None):
+            raise ValueError('a forecast is scored against held-out rows: give indir or emp (not both)')
+        if indir is not None:
+            emp = load_empirical(indir, self.d, int(horizon))
+        start, emp, H = _score_inputs(pi0, emp, self.d, horizon)
+        agents = ops.check_forecast_agents_args(start.shape, agents, H, repeats, (), self.precision)[-1]
+        apportion(start, agents)
+        R, N = int(repeats), start.shape[0]
+        res = {'crps': np.full((self.K, N, H, self.d), np.nan), 'less': np.full((self.K, N, H, self.d), -1, dtype=np.int32),
+               'equal': np.full((self.K, N, H, self.d), -1, dtype=np.int32),
+               'energy': np.full((self.K, N, H), np.nan) if want_energy else None, 'summary': np.full((self.K, H, 2), np.nan)}
+        self._run_live(res, H - 1, lambda sub, first_step: forecast_agents_score_policies(
+            start, emp, agents, sub(self._theta), sub(self._shifts_dev), sub(self._alphas_dev), sub(self._seeds_dev), H, first_step,
+            R, self.precision, self.device, self._ctx, want_energy))
         return ForecastScore(res['crps'], res['less'], res['equal'], res['energy'], res['summary'], R)
 
     def learner(self, k):

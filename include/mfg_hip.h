@@ -613,6 +613,58 @@ int mfg_forecast_score(const float* traj, int64_t N, int H, int d, int K, int re
                        double* crps, int32_t* less, int32_t* equal, double* energy, double* summary, void* workspace,
                        size_t workspace_bytes, mfg_stream_t stream);
 
+/* Finite populations: a member is ONE population of A agents (1 <= A <= MFG_AGENTS_MAX) instead of the mean-field limit
+ * pi' = P^T pi that every other entry rolls.  Its state is counts [d] int32 (d <= 64) summing to A; each agent of topic i draws
+ * its next topic from row P[i,:] of the member's action, so the histogram carries sampling noise of order 1 / sqrt(A) on top of
+ * the policy's -- the N-player game whose limit the mean-field forecast is.  The reference has no such path.  Everything is
+ * integer but the thresholds, which are defined operation by operation: the results are the same bits on every run and layout.
+ *   Histogram row: pi_i = (float)((double)counts_i / (double)A).
+ *   One step of the member with global id j under seed s at Philox step `step`, given its action P [d,d] fp32:
+ *   1. thresholds: S_ic = the sequential sum of (double)P[i,0..c] in column order (adds only), t_ic = floor(S_ic / S_i,d-1 2^32)
+ *      as a 64-bit integer, clamped to [0, 2^32]; t_i,d-1 = 2^32 exactly.
+ *   2. agent a (0 <= a < counts_i) of topic i reads word a mod 4 (x, y, z, w) of philox4x32_10 with counter
+ *      c0 = 0x80000000 | (i << 22) | (a >> 2), c1 = step, c2 = (uint32)j, c3 = (j >> 32) & 0xFFFF and key (s low, s high):
+ *      draw block 0, a c0 range above the action element ids (< 2^18) and never the start draw's 0xFFFFFFFF.
+ *   3. the agent moves to the first column c with word < t_ic (64-bit comparison: t = 2^32 accepts 0xFFFFFFFF, t = 0 nothing);
+ *      moves[i,c] counts these moves and counts'_c = sum_i moves[i,c], which sum to A again.
+ *   4. a row with counts_i > 0 whose S_i,d-1 is not finite or <= 0, or a count outside [0, A], fails the member: its counts' and
+ *      moves are -1 and its histogram row is NaN; every other member is as without it.
+ *
+ * mfg_agents_step_pop: the given-P building block (the counterpart of mfg_step_given_P) in ONE launch, no workspace, no
+ * allocation, no synchronisation, on `stream`.
+ *   counts [K,B,d] int32, P [K,B,d,d] fp32; member b of group k has id traj_offset + b and seed seed[k] (a device array [K]).
+ *   counts_next [K,B,d] int32 (may be `counts`); pi_next [K,B,d] fp32 or NULL; moves [K,B,d,d] int32 or NULL.
+ *   Group k's outputs depend on group k alone.
+ * Checked before launch: no null pointer but pi_next / moves, 1 <= K <= MFG_POP_MAX_K, 0 <= B < 2^31, d >= 1, 1 <= agents <=
+ * MFG_AGENTS_MAX, traj_offset + B <= MFG_TRAJ_ID_LIMIT (MFG_EINVAL); d <= 64 (MFG_EUNSUPPORTED).
+ *
+ * mfg_forecast_agents_pop: mfg_forecast_pop with finite-population members.  Its arguments are mfg_forecast_pop's with
+ * counts0 [N,d] int32 (the start counts, each row summing to `agents`) for start32, `agents`, and two more outputs that may be
+ * NULL: counts_traj [K, N R, H, d] int32 and actions [K, N R, H-1, d, d] fp32.  Member j of learner k (start row j mod N) at
+ * step t forms pi from its counts, draws P from that row exactly as mfg_forecast_pop's members do -- Philox keys (seed[k],
+ * first_step + t, j): actions[k,j,t] is mfg_sample_dirichlet's row j on pi_traj[k,:,t] -- and resamples its agents as above
+ * with step = first_step + t.  pi_traj rows are the histogram rows of counts_traj; a member that fails at step t has NaN rows
+ * and -1 counts from row t + 1 on (its later actions are drawn from its last valid row).  mean, std, quant and curves are
+ * mfg_forecast_pop's, by the same kernels on pi_traj.  Launches: one for row 0, then the sampling kernel over all K N R members
+ * and the agents kernel per step -- 2 (H - 1) whatever K is -- and the one or two reductions.
+ *   workspace: mfg_forecast_agents_pop_workspace_bytes(N, H, d, K, repeats, pi_traj != NULL, counts_traj != NULL) bytes, 8-byte
+ *   aligned; contents are scratch.
+ * Checked before anything is launched: everything mfg_forecast_pop checks, 1 <= agents <= MFG_AGENTS_MAX (MFG_EINVAL).  Mixed
+ * precision reports into and is refused on the bound context's status word exactly as mfg_forecast_pop: the word is read once,
+ * before the first launch; a policy that leaves the range INSIDE the call does not stop it -- its actions are unspecified, so
+ * each of its members fails or stays a histogram of its agents, every other policy's outputs are complete, the call returns
+ * MFG_OK and the next mixed-precision call is refused. */
+#define MFG_AGENTS_MAX (1 << 24)
+int mfg_agents_step_pop(const int32_t* counts, const float* P, int64_t B, int d, int K, int agents, const uint64_t* seed,
+                        uint32_t step, uint64_t traj_offset, int32_t* counts_next, float* pi_next, int32_t* moves,
+                        mfg_stream_t stream);
+size_t mfg_forecast_agents_pop_workspace_bytes(int64_t N, int H, int d, int K, int repeats, int traj_given, int counts_given);
+int mfg_forecast_agents_pop(const int32_t* counts0, int64_t N, int H, int d, int K, int agents, const double* theta,
+                            const double* shift, const double* alpha_scale, const uint64_t* seed, uint32_t first_step, int repeats,
+                            int precision, const int32_t* ranks, int Q, const float* emp32, const double* emp64, double* mean,
+                            double* std, float* quant, double* curves, float* pi_traj, int32_t* counts_traj, float* actions,
+                            void* workspace, size_t workspace_bytes, mfg_stream_t stream);
+
 /* Distribution summary of R rows of N fp32 values in ONE launch, one workgroup per row: what plot_reward_distribution and
  * its two siblings (ac_irl.py:1046-1263) take from plt.hist (np.histogram, :1116-1119) and gaussian_kde (:1087-1100) for each
  * of their reward sets.  Row r is values[r stride .. r stride + N), stride >= N; everything below is on x = (double)values.
