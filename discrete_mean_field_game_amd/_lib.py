@@ -187,7 +187,22 @@ class PopControlStruct(C.Structure):
 
 SIGNATURES['mfg_ctx_set_pop_control'] = (_i32, [_p, C.POINTER(PopControlStruct)])
 
-SIGNATURES['mfg_evaluate_pop_workspace_bytes'] = (_sz, [_i64, _i32, _i32, _i32, _i32, _i32])
+POP_VALIDATE_COLUMNS = 10       # MFG_POP_VALIDATE_COLUMNS: columns of a validation curve row
+
+
+class PopValidateStruct(C.Structure):
+    """mfg_pop_validate_t of include/mfg_hip.h: the held-out checks a population training call runs every `period` episodes."""
+    _fields_ = ([(n, C.c_void_p) for n in ('emp32', 'emp64', 'curve', 'checks', 'best_value', 'best_check', 'since_best',
+                                           'best_theta', 'best_w', 'workspace')]
+                + [('workspace_bytes', C.c_size_t), ('N', C.c_int64)]
+                + [(n, C.c_int32) for n in ('L', 'repeats', 'period', 'column', 'with_score', 'patience', 'max_checks', 'K')]
+                + [('first_step', C.c_uint32)])
+
+
+SIGNATURES['mfg_ctx_set_pop_validate'] = (_i32, [_p, C.POINTER(PopValidateStruct)])
+SIGNATURES['mfg_pop_validate_workspace_bytes'] = (_sz, [_i64, _i32, _i32, _i32, _i32, _i32])
+
+SIGNATURES['mfg_evaluate_pop_workspace_bytes'] =(_sz, [_i64, _i32, _i32, _i32, _i32, _i32])
 SIGNATURES['mfg_evaluate_pop'] = (_i32, [_p, _p, _i64, _i32, _i32, _i32, _p, _p, _p, _p, _u32, _i32, _i32, _p, _p, _p, _sz, _p])
 
 # the ensemble forecast: start32, N, H, d, K, theta, shift, alpha_scale, seed, first_step, repeats, precision, ranks (host), Q,

@@ -54,7 +54,9 @@ __device__ __forceinline__ void eval_step_l1_jsd(const float* __restrict__ gp, c
   jsd = 0.5 * wave_sum(acc);
 }
 
+// state: NULL, or the [K] activity states of a control block (a validation check, mfg_pop_validate.h): learner k's block returns
+// at once when state[k] != 0
 void launch_eval_metrics_pop(const float* pi_traj, const float* emp32, const double* emp64, int64_t N, int L, int d, int64_t NR,
-                             int K, double* per_traj, double* metrics, hipStream_t st);
+                             int K, double* per_traj, double* metrics, hipStream_t st, const int32_t* state = nullptr);
 
 }  // namespace mfg

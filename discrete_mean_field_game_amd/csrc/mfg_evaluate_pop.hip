@@ -11,6 +11,9 @@ namespace mfg {
 template <bool FAST, int D>
 __global__ __launch_bounds__(BLOCK, FAST ? MFG_CORE_SMALL_WAVES : 2) void k_eval_rollout_pop(CoreArgs a, PopArgs p) {
   const int k = blockIdx.y;
+  // a check inside a training call with a control block (mfg_pop_validate.h): a retired learner's blocks return at once
+  // (block-uniform, ahead of every barrier); mfg_evaluate_pop itself passes no states
+  if (p.state && pop_retired(p, k)) return;
   const int d = D ? D : a.d;
   const int TB = WAVES * (WAVE / d);
   int32_t* idx = p.idx + p.s_idx * k;
@@ -25,6 +28,7 @@ __global__ __launch_bounds__(BLOCK, FAST ? MFG_CORE_SMALL_WAVES : 2) void k_eval
   __syncthreads();
   CoreArgs c = pop_core_args<false, 0>(a, p, k);
   c.start_idx = idx;
+  if (p.state) c.status = p.status + k;  // (as the _ctl training forms: an out-of-range theta is booked to the learner)
   core_small_body<true, false, FAST, D, false, 0>(c);
 }
 
@@ -58,10 +62,12 @@ int launch_eval_rollout_pop(const CoreArgs& a, const PopArgs& p, bool fast, int 
 // the second pass of the standard deviation.  Wave totals are combined in wave order: a fixed summation order.
 __global__ __launch_bounds__(BLOCK) void k_eval_metrics_pop(const float* __restrict__ gen_all, const float* __restrict__ emp32,
                                                             const double* __restrict__ emp64, int64_t N, int L, int d, int64_t NR,
-                                                            double* __restrict__ per_traj_all, double* __restrict__ metrics) {
+                                                            double* __restrict__ per_traj_all, double* __restrict__ metrics,
+                                                            const int32_t* __restrict__ state) {
   __shared__ double part[WAVES][4];
   __shared__ double mean_s[4];
   const int k = blockIdx.x;
+  if (state && state[k] != 0) return;  // (a retired learner of a validation check: its row of metrics is left alone)
   const int lane = threadIdx.x & (WAVE - 1), wv = threadIdx.x / WAVE;
   const float* gen = gen_all + (int64_t)k * NR * L * d;
   double* per_traj = per_traj_all + (int64_t)k * NR * 4;
@@ -115,9 +121,9 @@ __global__ __launch_bounds__(BLOCK) void k_eval_metrics_pop(const float* __restr
 }
 
 void launch_eval_metrics_pop(const float* pi_traj, const float* emp32, const double* emp64, int64_t N, int L, int d, int64_t NR,
-                             int K, double* per_traj, double* metrics, hipStream_t st) {
+                             int K, double* per_traj, double* metrics, hipStream_t st, const int32_t* state) {
   hipLaunchKernelGGL(k_eval_metrics_pop, dim3((unsigned)K), dim3(BLOCK), 0, st, pi_traj, emp32, emp64, N, L, d, NR, per_traj,
-                     metrics);
+                     metrics, state);
 }
 
 }  // namespace mfg

@@ -62,9 +62,10 @@ inline size_t score_lds_bytes(int d, int repeats, bool want_energy) {
 // workspace of mfg_forecast_score: cell_crps [K, N, H] fp64
 inline size_t forecast_score_workspace_bytes(int64_t N, int H, int K) { return (size_t)K * (size_t)N * (size_t)H * 8; }
 
-// MFG_ELAUNCH (nothing launched) if the LDS request of the shape were to exceed the budget
+// MFG_ELAUNCH (nothing launched) if the LDS request of the shape were to exceed the budget.  state: NULL, or the [K] activity
+// states of a control block (a validation check, mfg_pop_validate.h): policy k's blocks return at once when state[k] != 0
 int launch_forecast_score(const float* traj, int64_t N, int H, int d, int K, int repeats, const float* emp32, const double* emp64,
                           double* crps, int32_t* less, int32_t* equal, double* energy, double* summary, double* cell_crps,
-                          hipStream_t st);
+                          hipStream_t st, const int32_t* state = nullptr);
 
 }  // namespace mfg

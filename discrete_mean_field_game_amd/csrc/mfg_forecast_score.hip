@@ -36,6 +36,7 @@ struct ForecastScoreArgs {
   int32_t *less, *equal;
   double* energy;       // [K, N, H] or NULL
   double* cell_crps;    // [K, N, H]
+  const int32_t* state; // [K] activity states of a control block (a validation check), or NULL: policy k is skipped when != 0
 };
 
 // norms of the pairs (row a of tile ta, member j of tile tb) this thread owns, added to acc in ascending a; `diag`: ta == tb,
@@ -74,6 +75,7 @@ __global__ __launch_bounds__(FS_BLOCK) void k_forecast_score(ForecastScoreArgs a
   __shared__ float s_y32[FS_MAX_D];
   __shared__ int s_less[FS_MAX_D], s_equal[FS_MAX_D];
   const int k = blockIdx.y;
+  if (a.state && a.state[k] != 0) return;  // (a retired learner of a validation check; block-uniform, ahead of every barrier)
   const int64_t cell = blockIdx.x;
   const int64_t n = cell / a.H;
   const int l = (int)(cell - n * a.H);
@@ -217,8 +219,10 @@ __global__ __launch_bounds__(FS_BLOCK) void k_forecast_score(ForecastScoreArgs a
 // ---- launch 2: summary[k, l] = (mean of crps over (n, c), mean of energy over n), block (l, k), one wave ----
 __global__ __launch_bounds__(FS_WAVE) void k_forecast_score_summary(const double* __restrict__ cell_crps,
                                                                     const double* __restrict__ energy, int64_t N, int H, int d,
-                                                                    double* __restrict__ summary) {
+                                                                    double* __restrict__ summary,
+                                                                    const int32_t* __restrict__ state) {
   const int l = blockIdx.x, k = blockIdx.y, lane = threadIdx.x;
+  if (state && state[k] != 0) return;
   double s = 0.0, e = 0.0;
   for (int64_t n = lane; n < N; n += FS_WAVE) {
     const int64_t o = ((int64_t)k * N + n) * H + l;
@@ -236,8 +240,9 @@ __global__ __launch_bounds__(FS_WAVE) void k_forecast_score_summary(const double
 
 int launch_forecast_score(const float* traj, int64_t N, int H, int d, int K, int repeats, const float* emp32, const double* emp64,
                           double* crps, int32_t* less, int32_t* equal, double* energy, double* summary, double* cell_crps,
-                          hipStream_t st) {
+                          hipStream_t st, const int32_t* state) {
   ForecastScoreArgs a{};
+  a.state = state;
   a.traj = traj;
   a.emp32 = emp32;
   a.emp64 = emp64;
@@ -256,7 +261,7 @@ int launch_forecast_score(const float* traj, int64_t N, int H, int d, int K, int
   if (a.C < 1 || lds > FS_COL_BUDGET) return MFG_ELAUNCH;  // (never within MFG_FORECAST_MAX_REPEATS and d <= 64)
   hipLaunchKernelGGL(k_forecast_score, dim3((unsigned)(N * H), (unsigned)K), dim3(FS_BLOCK), lds, st, a);
   hipLaunchKernelGGL(k_forecast_score_summary, dim3((unsigned)H, (unsigned)K), dim3(FS_WAVE), 0, st, cell_crps, energy, N, H, d,
-                     summary);
+                     summary, state);
   return MFG_OK;
 }
 

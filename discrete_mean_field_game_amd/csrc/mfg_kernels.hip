@@ -28,6 +28,7 @@
 #include "mfg_consistency_pop.h"
 #include "mfg_irl_population.h"
 #include "mfg_population.h"
+#include "mfg_pop_validate.h"
 #include "mfg_batch_sums.h"
 #include "mfg_host.h"
 #include "mfg_launch_once.h"
@@ -130,6 +131,8 @@ struct mfg_ctx {
   void* comm = nullptr;  // adopted RCCL communicator (mfg_ctx_adopt_comm), destroyed with the context
   bool has_ctl = false;  // population control block (mfg_ctx_set_pop_control): the population training calls carry it
   mfg_pop_control_t ctl{};
+  bool has_val = false;  // population validation block (mfg_ctx_set_pop_validate): held-out checks inside those calls
+  mfg_pop_validate_t val{};
 };
 // The binding is per THREAD, the object's lifetime is not: a context may be destroyed by another thread than the one(s) it is
 // bound on (a garbage collector drops the last reference wherever it runs).  Every live context is therefore registered with
@@ -406,6 +409,42 @@ int mfg_ctx_set_pop_control(mfg_ctx_t* ctx, const mfg_pop_control_t* block) {
   REQUIRE(block->K >= 1 && block->K <= MFG_POP_MAX_K, "population control block: K outside [1, MFG_POP_MAX_K]");
   ctx->ctl = *block;
   ctx->has_ctl = true;
+  return MFG_OK;
+}
+
+static bool pop_validate_complete(const mfg_pop_validate_t& v) {
+  return v.emp32 && v.emp64 && v.curve && v.checks && v.best_value && v.best_check && v.since_best && v.best_theta && v.best_w &&
+         v.workspace;
+}
+
+int mfg_ctx_set_pop_validate(mfg_ctx_t* ctx, const mfg_pop_validate_t* block) {
+  REQUIRE(ctx && ctx_is_live(ctx), "null or destroyed context");
+  if (!block) {
+    ctx->has_val = false;
+    ctx->val = mfg_pop_validate_t{};
+    return MFG_OK;
+  }
+  const mfg_pop_validate_t& v = *block;
+  REQUIRE(pop_validate_complete(v), "population validation block: null pointer");
+  REQUIRE((reinterpret_cast<uintptr_t>(v.workspace) & 7) == 0, "population validation block: workspace not 8-byte aligned");
+  REQUIRE(v.K >= 1 && v.K <= MFG_POP_MAX_K, "population validation block: K outside [1, MFG_POP_MAX_K]");
+  REQUIRE(v.period >= 1, "population validation block: period < 1");
+  REQUIRE(v.max_checks >= 1, "population validation block: max_checks < 1");
+  REQUIRE(v.patience >= 0, "population validation block: patience < 0");
+  REQUIRE(v.with_score == 0 || v.with_score == 1, "population validation block: with_score is not 0 / 1");
+  REQUIRE(v.column >= 0 && v.column < MFG_POP_VALIDATE_COLUMNS, "population validation block: column outside [0, 10)");
+  REQUIRE(v.column < 8 || v.with_score, "population validation block: columns 8 / 9 (crps, energy) need with_score");
+  REQUIRE(v.N >= 1, "population validation block: no held-out trajectories (N < 1)");
+  REQUIRE(v.L >= 2, "population validation block: episode_length L < 2");
+  REQUIRE(v.repeats >= 1, "population validation block: repeats < 1");
+  REQUIRE(v.N * (int64_t)v.L <= 0x7FFFFFFF && v.N * (int64_t)v.repeats <= 0x7FFFFFFF,
+          "population validation block: N L or N repeats too large");
+  REQUIRE((uint64_t)v.first_step + (uint64_t)(v.L - 1) <= 0xFFFFFFFFull, "population validation block: Philox step counter would wrap");
+  if (v.with_score && v.repeats > MFG_FORECAST_MAX_REPEATS)
+    return fail(MFG_EUNSUPPORTED, "population validation block: repeats=%d > MFG_FORECAST_MAX_REPEATS=%d with with_score", v.repeats,
+                MFG_FORECAST_MAX_REPEATS);
+  ctx->val = v;
+  ctx->has_val = true;
   return MFG_OK;
 }
 
@@ -1125,6 +1164,61 @@ struct PopControl {
   }
 };
 
+static int evaluate_pop_launches(const float* emp32, const double* emp64, int64_t N, int L, int d, int K, const double* theta,
+                                 const double* shift, const double* alpha_scale, const uint64_t* seed, uint32_t first_step,
+                                 int repeats, int precision, double* metrics, float* pi_traj, void* workspace,
+                                 const int32_t* state, unsigned* status, const float** traj_out, hipStream_t st);
+
+// The validation block a population training call runs under -- that of the bound context, none without one
+// (mfg_ctx_set_pop_validate, mfg_pop_validate.h).  begin() checks the block against the call before ANYTHING is launched (so ahead
+// of PopControl::begin); check(k, p) enqueues the held-out check behind episode k's closing update and retire step when one
+// is due: the launches of mfg_evaluate_pop on the call's current theta, with with_score those of mfg_forecast_score on the
+// members just rolled out, and k_pop_validate_select.  p carries the control block's states after PopControl::begin.  Without a
+// block neither does anything.
+struct PopValidate {
+  const mfg_pop_validate_t* v = nullptr;
+  PopValidateLayout lay{};
+  const double *theta = nullptr, *w = nullptr;
+  int d = 0, precision = 0;
+  hipStream_t st = nullptr;
+
+  int begin(int K, int d_, const double* theta_, const double* w_, int precision_, hipStream_t st_) {
+    const mfg_ctx* c = bound_ctx();
+    if (!c || !c->has_val) return MFG_OK;
+    REQUIRE(pop_validate_complete(c->val), "population validation block: null pointer");
+    REQUIRE(c->val.K == K, "population validation block: set for another population size K");
+    REQUIRE(c->val.patience == 0 || c->has_ctl,
+            "population validation block: patience > 0 needs a population control block (mfg_ctx_set_pop_control)");
+    lay = pop_validate_layout(c->val.N, c->val.L, d_, K, c->val.repeats, c->val.with_score != 0);
+    if (c->val.workspace_bytes < lay.bytes)
+      return fail(MFG_EWORKSPACE, "population validation workspace: need %lld bytes, have %lld", (long long)lay.bytes,
+                  (long long)c->val.workspace_bytes);
+    v = &c->val;
+    theta = theta_, w = w_, d = d_, precision = precision_, st = st_;
+    return MFG_OK;
+  }
+  int check(int64_t k, const PopArgs& p) const {
+    if (!v || (k + 1) % v->period != 0) return MFG_OK;
+    char* ws = reinterpret_cast<char*>(v->workspace);
+    double* metrics = reinterpret_cast<double*>(ws + lay.metrics);
+    const float* traj = nullptr;
+    int rc = evaluate_pop_launches(v->emp32, v->emp64, v->N, v->L, d, p.K, theta, p.shift, p.alpha_scale, p.seed, v->first_step,
+                                   v->repeats, precision, metrics, nullptr, ws, p.state, p.status, &traj, st);
+    if (rc != MFG_OK) return rc;
+    double* summary = nullptr;
+    if (v->with_score) {
+      summary = reinterpret_cast<double*>(ws + lay.summary);
+      rc = launch_forecast_score(traj, v->N, v->L, d, p.K, v->repeats, v->emp32, v->emp64, reinterpret_cast<double*>(ws + lay.crps),
+                                 reinterpret_cast<int32_t*>(ws + lay.less), reinterpret_cast<int32_t*>(ws + lay.equal),
+                                 reinterpret_cast<double*>(ws + lay.energy), summary,
+                                 reinterpret_cast<double*>(ws + lay.score_ws), st, p.state);
+      if (rc != MFG_OK) return fail(rc, "%s", "population validation: score LDS request beyond the budget");
+    }
+    launch_pop_validate_select(*v, const_cast<int32_t*>(p.state), metrics, summary, theta, w, p.F, st);
+    return check_launch("pop_validate");
+  }
+};
+
 // the argument block of a population call (the call sets the strides that depend on its flow: s_pi0, s_gpi, s_n, s_P)
 static PopArgs pop_args(int K, int64_t B, int d, int64_t T, int64_t episodes, const uint64_t* seed, const double* shift,
                         const double* alpha_scale, const double* lr_critic, const double* lr_actor, size_t workspace_bytes) {
@@ -1161,6 +1255,8 @@ int mfg_train_episodes_pop(const float* mat_pi0, int64_t num_start, float* pi_io
   PopArgs p = pop_args(K, B, d, 1, episodes, seed, shift, alpha_scale, lr_critic, lr_actor, workspace_bytes);
   p.s_pi0 = p.s_gpi = B * d;  // (the env step reads and the batch sums read the learner's current states)
   p.s_n = B;
+  PopValidate pv;
+  if (const int rc = pv.begin(K, d, theta, w, precision, S(stream)); rc != MFG_OK) return rc;
   PopControl pc;
   if (const int rc = pc.begin(p, theta, w, shift, precision == MFG_PRECISION_MIXED, S(stream)); rc != MFG_OK) return rc;
   for (int64_t k = 0; k < episodes; ++k) {
@@ -1172,6 +1268,7 @@ int mfg_train_episodes_pop(const float* mat_pi0, int64_t num_start, float* pi_io
                                       workspace_bytes, S(stream), &p);
     if (rc != MFG_OK) return rc;
     pc.retire();
+    if (const int rv = pv.check(k, p); rv != MFG_OK) return rv;
   }
   return MFG_OK;
 }
@@ -1199,6 +1296,9 @@ int mfg_train_episodes_pop_resident(const float* mat_pi0, int64_t num_start, flo
   if (const mfg_ctx* c = bound_ctx(); c && c->has_ctl)
     return fail(MFG_EUNSUPPORTED, "%s", "resident population: the bound context carries a population control block "
                                         "(mfg_train_episodes_pop retires learners)");
+  if (const mfg_ctx* c = bound_ctx(); c && c->has_val)
+    return fail(MFG_EUNSUPPORTED, "%s", "resident population: the bound context carries a population validation block "
+                                        "(mfg_train_episodes_pop runs the held-out checks)");
   const size_t need = pop_workspace_need(d, B, true);
   if (workspace_bytes < need)
     return fail(MFG_EWORKSPACE, "population workspace: need %lld bytes per learner, have %lld", (long long)need,
@@ -1268,6 +1368,10 @@ int mfg_train_rollouts_pop(const float* mat_pi0, int64_t num_start, int64_t B, i
   p.s_pi0 = 0;  // (the shared start-state table: the rows are drawn in the kernel)
   p.s_gpi = p.s_traj;
   p.s_n = B * T;
+  PopValidate pv;
+  if (const int rc = pv.begin(K, d, theta, w, (flags & MFG_ROLLOUT_F64) ? MFG_PRECISION_F64 : MFG_PRECISION_MIXED, S(stream));
+      rc != MFG_OK)
+    return rc;
   PopControl pc;
   if (const int rc = pc.begin(p, theta, w, shift, !(flags & MFG_ROLLOUT_F64), S(stream)); rc != MFG_OK) return rc;
   for (int64_t k = 0; k < episodes; ++k) {
@@ -1278,6 +1382,7 @@ int mfg_train_rollouts_pop(const float* mat_pi0, int64_t num_start, int64_t B, i
                                       workspace_bytes, S(stream), nullptr, &p);
     if (rc != MFG_OK) return rc;
     pc.retire();
+    if (const int rv = pv.check(k, p); rv != MFG_OK) return rv;
   }
   return MFG_OK;
 }
@@ -1286,6 +1391,40 @@ int mfg_train_rollouts_pop(const float* mat_pi0, int64_t num_start, int64_t B, i
 size_t mfg_evaluate_pop_workspace_bytes(int64_t N, int L, int d, int K, int repeats, int traj_given) {
   if (N < 1 || L < 1 || d < 1 || K < 1 || repeats < 1) return 0;
   return eval_pop_workspace_bytes(N, L, d, K, repeats, traj_given != 0);
+}
+
+// the two launches of mfg_evaluate_pop on checked arguments; state / status: NULL, or those of a control block (a validation
+// check inside a training call: retired learners are skipped, range reports go to the learner).  *traj_out: where the members are.
+static int evaluate_pop_launches(const float* emp32, const double* emp64, int64_t N, int L, int d, int K, const double* theta,
+                                 const double* shift, const double* alpha_scale, const uint64_t* seed, uint32_t first_step,
+                                 int repeats, int precision, double* metrics, float* pi_traj, void* workspace,
+                                 const int32_t* state, unsigned* status, const float** traj_out, hipStream_t st) {
+  const int64_t NR = N * repeats;
+  PopArgs p = pop_args(K, NR, d, L - 1, 0, seed, shift, alpha_scale, nullptr, nullptr, 0);
+  p.N = N;
+  p.L = L;
+  p.s_idx = eval_pop_idx_stride(NR);
+  p.idx = reinterpret_cast<int32_t*>(workspace);
+  p.state = state;
+  p.status = status;
+  double* per_traj = reinterpret_cast<double*>(reinterpret_cast<char*>(workspace) + (size_t)K * p.s_idx * 4);
+  float* traj = pi_traj ? pi_traj : reinterpret_cast<float*>(per_traj + (size_t)K * NR * 4);
+  if (traj_out) *traj_out = traj;
+  CoreArgs a{};
+  a.pi0 = emp32;  // viewed as [N L, d]; row (j mod N) L is the start state of trajectory j
+  a.num_start = N * L;
+  a.theta = theta;
+  a.gamma = 1.0;
+  a.B = NR;
+  a.d = d;
+  a.T = L - 1;
+  a.reward_kind = MFG_REWARD_EXTERNAL;  // (states only: no reward is formed)
+  a.first_step = first_step;
+  a.pi_traj = traj;
+  const int rc = launch_core(a, true, false, precision, st, &p);
+  if (rc != MFG_OK) return rc;
+  launch_eval_metrics_pop(traj, emp32, emp64, N, L, d, NR, K, per_traj, metrics, st, state);
+  return check_launch("evaluate_pop metrics");
 }
 
 int mfg_evaluate_pop(const float* emp32, const double* emp64, int64_t N, int L, int d, int K, const double* theta,
@@ -1306,29 +1445,8 @@ int mfg_evaluate_pop(const float* emp32, const double* emp64, int64_t N, int L, 
   if (workspace_bytes < need)
     return fail(MFG_EWORKSPACE, "population evaluation workspace: need %lld bytes, have %lld", (long long)need,
                 (long long)workspace_bytes);
-  const int64_t NR = N * repeats;
-  PopArgs p = pop_args(K, NR, d, L - 1, 0, seed, shift, alpha_scale, nullptr, nullptr, 0);
-  p.N = N;
-  p.L = L;
-  p.s_idx = eval_pop_idx_stride(NR);
-  p.idx = reinterpret_cast<int32_t*>(workspace);
-  double* per_traj = reinterpret_cast<double*>(reinterpret_cast<char*>(workspace) + (size_t)K * p.s_idx * 4);
-  float* traj = pi_traj ? pi_traj : reinterpret_cast<float*>(per_traj + (size_t)K * NR * 4);
-  CoreArgs a{};
-  a.pi0 = emp32;  // viewed as [N L, d]; row (j mod N) L is the start state of trajectory j
-  a.num_start = N * L;
-  a.theta = theta;
-  a.gamma = 1.0;
-  a.B = NR;
-  a.d = d;
-  a.T = L - 1;
-  a.reward_kind = MFG_REWARD_EXTERNAL;  // (states only: no reward is formed)
-  a.first_step = first_step;
-  a.pi_traj = traj;
-  const int rc = launch_core(a, true, false, precision, S(stream), &p);
-  if (rc != MFG_OK) return rc;
-  launch_eval_metrics_pop(traj, emp32, emp64, N, L, d, NR, K, per_traj, metrics, S(stream));
-  return check_launch("evaluate_pop metrics");
+  return evaluate_pop_launches(emp32, emp64, N, L, d, K, theta, shift, alpha_scale, seed, first_step, repeats, precision, metrics,
+                               pi_traj, workspace, nullptr, nullptr, nullptr, S(stream));
 }
 
 // ---- ensemble forecast (mfg_forecast_pop.h): R rollouts per start state of K policies, reduced in at most three launches ------
@@ -1901,6 +2019,8 @@ int mfg_train_episodes_irl_pop(const float* mat_pi0, int64_t num_start, float* p
   rp.s_action = B * d * d;
   rp.s_n = B;
   rp.s_w = p.F;
+  PopValidate pv;
+  if (const int rc = pv.begin(K, d, theta, w, precision, S(stream)); rc != MFG_OK) return rc;
   PopControl pc;
   if (const int rc = pc.begin(p, theta, w, shift, precision == MFG_PRECISION_MIXED, S(stream)); rc != MFG_OK) return rc;
   rp.state = p.state;
@@ -1912,6 +2032,7 @@ int mfg_train_episodes_irl_pop(const float* mat_pi0, int64_t num_start, float* p
                                           reward_acc ? reward_acc + e : nullptr, workspace, workspace_bytes, S(stream), &p, &rp);
     if (rc != MFG_OK) return rc;
     pc.retire();
+    if (const int rv = pv.check(e, p); rv != MFG_OK) return rv;
   }
   return MFG_OK;
 }
@@ -1941,6 +2062,10 @@ int mfg_train_rollouts_irl_pop(const float* mat_pi0, int64_t num_start, int64_t 
   rp.s_state = B * (T + 1) * d;
   rp.s_action = B * T * d * d;
   rp.s_n = B * T;
+  PopValidate pv;
+  if (const int rc = pv.begin(K, d, theta, w, (flags & MFG_ROLLOUT_F64) ? MFG_PRECISION_F64 : MFG_PRECISION_MIXED, S(stream));
+      rc != MFG_OK)
+    return rc;
   PopControl pc;
   if (const int rc = pc.begin(p, theta, w, shift, !(flags & MFG_ROLLOUT_F64), S(stream)); rc != MFG_OK) return rc;
   rp.state = p.state;
@@ -1954,6 +2079,7 @@ int mfg_train_rollouts_irl_pop(const float* mat_pi0, int64_t num_start, int64_t 
                                       workspace_bytes, S(stream), nullptr, &p, &ext);
     if (rc != MFG_OK) return rc;
     pc.retire();
+    if (const int rv = pv.check(e, p); rv != MFG_OK) return rv;
   }
   return MFG_OK;
 }

@@ -285,7 +285,7 @@ class AC_IRLPopulation(_Population):
     # ------------------------------------------------------------------ training
     @_with_ctx
     def train(self, num_episodes, gamma=1, constant=False, lr_critic=0.1, lr_actor=0.001, *, first_episode=0, stop_criteria=-1,
-              isolate=False):
+              isolate=False, validate=None):
         """`num_episodes` episodes of every learner: AC_IRL.train(num_episodes, stop_criteria[k], ...) under each learner's
         reward network (episodes numbered first_episode + 1 ... in the learning-rate schedule, as there).  lr_critic /
         lr_actor: scalars or [K].  Returns a NumPy array [K, num_episodes] of the per-episode returns as AC_IRL.train books
@@ -296,7 +296,9 @@ class AC_IRLPopulation(_Population):
         num_episodes all the same: a later call of learner k corresponds to an AC_IRL whose _rng_step and _reward_calls were
         set to the population's values.  isolate=True: a learner that diverges is frozen instead of raising for everybody
         (ActorCriticPopulation.train).  isolate=False with a criterion (or after an uncleared failure): the diverged learner is
-        frozen all the same, the context's status word stays 0, the others finish the call, and train() raises afterwards."""
+        frozen all the same, the context's status word stays 0, the others finish the call, and train() raises afterwards.
+        validate (a population.Validation; None: nothing changes): held-out checks on the device every validate.period
+        episodes, as ActorCriticPopulation.train; the results land on self.validation."""
         T = self.episode_steps
 
         def run(b, lrc, lra, acc):
@@ -315,7 +317,7 @@ class AC_IRLPopulation(_Population):
                                            self._net_struct, self.per_learner_net, self._rn_seeds_dev, calls, b['G'],
                                            b['ws'], b['run'], **common)
                 self._calls_k += int(num_episodes)
-        out = self._train(num_episodes, lr_critic, lr_actor, run, stop_criteria, isolate)
+        out = self._train(num_episodes, lr_critic, lr_actor, run, stop_criteria, isolate, validate)
         if out.shape[1]:
             for k, t in enumerate(self.thetas):         # AC_IRL.train records the policy (list_policies FIFO)
                 if self._act.state[k] != 2:            # (a failed learner has no policy to record)

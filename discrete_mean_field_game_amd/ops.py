@@ -140,6 +140,43 @@ class Context:
                                  stop_criteria.data_ptr(), K)
         L.check(L.lib().mfg_ctx_set_pop_control(self._ptr, C.byref(blk)), 'mfg_ctx_set_pop_control')
 
+    def set_pop_validate(self, emp32=None, emp64=None, *, period=1, column=3, with_score=False, patience=0, first_step=0,
+                         repeats=1, curve=None, checks=None, best_value=None, best_check=None, since_best=None,
+                         best_theta=None, best_w=None, workspace=None, workspace_bytes=None):
+        """mfg_ctx_set_pop_validate: bind a population validation block to this context; every population training call made
+        with the context bound then runs a held-out check every `period` episodes (include/mfg_hip.h).  emp32 / emp64 [N,L,d]:
+        the held-out rows; curve [K, max_checks, 10], best_value / best_theta [K], best_w [K,F] float64 and checks /
+        best_check / since_best [K] int32 device tensors, initialised by the caller (checks, since_best 0; best_value +inf;
+        best_check -1); workspace: pop_validate_workspace (workspace_bytes: what the block announces, default the tensor's
+        size).  No arguments: clear it.  The caller keeps the tensors alive while the block is set."""
+        import ctypes as C
+        if emp32 is None:
+            L.check(L.lib().mfg_ctx_set_pop_validate(self._ptr, None), 'mfg_ctx_set_pop_validate')
+            return
+        _chk_f32(emp32, 'emp32'); _chk_f64(emp64, 'emp64')
+        if emp32.dim() != 3 or tuple(emp64.shape) != tuple(emp32.shape):
+            raise ValueError('emp32 / emp64: expected two [N, L, d] tensors of the same shape, got %s and %s'
+                             % (tuple(emp32.shape), tuple(emp64.shape)))
+        N, Lr, _d = emp32.shape
+        if curve is None or curve.dim() != 3 or curve.shape[2] != L.POP_VALIDATE_COLUMNS:
+            raise ValueError('set_pop_validate: curve must be a [K, max_checks, %d] tensor' % L.POP_VALIDATE_COLUMNS)
+        K, max_checks = int(curve.shape[0]), int(curve.shape[1])
+        for name, t, dt, nd in (('curve', curve, torch.float64, 3), ('checks', checks, torch.int32, 1),
+                                ('best_value', best_value, torch.float64, 1), ('best_check', best_check, torch.int32, 1),
+                                ('since_best', since_best, torch.int32, 1), ('best_theta', best_theta, torch.float64, 1),
+                                ('best_w', best_w, torch.float64, 2)):
+            if t is None or t.dtype != dt or t.dim() != nd or t.shape[0] != K or not t.is_contiguous() or not t.is_cuda:
+                raise ValueError('set_pop_validate: %s must be a contiguous %s device tensor with %d rows' % (name, dt, K))
+        if workspace is None or not workspace.is_cuda or not workspace.is_contiguous():
+            raise ValueError('set_pop_validate: workspace must be a contiguous device tensor')
+        if workspace_bytes is None:
+            workspace_bytes = workspace.numel() * workspace.element_size()
+        blk = L.PopValidateStruct(emp32.data_ptr(), emp64.data_ptr(), curve.data_ptr(), checks.data_ptr(), best_value.data_ptr(),
+                                  best_check.data_ptr(), since_best.data_ptr(), best_theta.data_ptr(), best_w.data_ptr(),
+                                  workspace.data_ptr(), int(workspace_bytes), int(N), int(Lr), int(repeats), int(period),
+                                  int(column), int(with_score), int(patience), max_checks, K, int(first_step))
+        L.check(L.lib().mfg_ctx_set_pop_validate(self._ptr, C.byref(blk)), 'mfg_ctx_set_pop_validate')
+
     def close(self):
         if self._ptr is not None:
             try:
@@ -919,6 +956,17 @@ def jsd(p, q):
 def evaluate_pop_workspace(N, L_rows, d, K, repeats, traj_given, device):
     """The scratch buffer of one evaluate_pop call (mfg_evaluate_pop_workspace_bytes, rounded up to whole doubles)."""
     nbytes = int(L.lib().mfg_evaluate_pop_workspace_bytes(int(N), int(L_rows), int(d), int(K), int(repeats), int(bool(traj_given))))
+    return torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=device)
+
+
+def pop_validate_workspace_bytes(N, L_rows, d, K, repeats, with_score=False):
+    """Bytes of scratch a validation block needs (mfg_pop_validate_workspace_bytes; host only, 0 for a degenerate shape)."""
+    return int(L.lib().mfg_pop_validate_workspace_bytes(int(N), int(L_rows), int(d), int(K), int(repeats), int(bool(with_score))))
+
+
+def pop_validate_workspace(N, L_rows, d, K, repeats, with_score, device):
+    """The scratch buffer of a validation block (Context.set_pop_validate), rounded up to whole doubles."""
+    nbytes = pop_validate_workspace_bytes(N, L_rows, d, K, repeats, with_score)
     return torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=device)
 
 

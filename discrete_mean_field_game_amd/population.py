@@ -232,6 +232,75 @@ def load_empirical(indir, d, episode_length):
     return np.array(emp)
 
 
+# ---------------------------------------------------------------------------------------- validation inside train()
+# The held-out checks of a population training call (mfg_ctx_set_pop_validate, include/mfg_hip.h): every `period` episodes the
+# call itself enqueues the evaluate_pop launches on the learners' current theta (and the forecast-score launches), keeps the
+# curve row and the best iterate on the device and -- with patience -- stops a learner whose metric no longer improves.
+# The columns of a curve row: the CSV's eight (actor_critic._EVAL_HEADER) and the two hour means of the proper scores.
+VALIDATION_COLUMNS = tuple(actor_critic._EVAL_HEADER.strip().split(',')[3:]) + ('crps', 'energy')
+
+
+def validation_column(metric):
+    """Index of `metric` in VALIDATION_COLUMNS: a column's name, or for the four means its short form ('JSD_mean' is
+    'mean_JSD_mean', the names of the table evaluate() returns).  ValueError for anything else."""
+    if metric in VALIDATION_COLUMNS:
+        return VALIDATION_COLUMNS.index(metric)
+    if isinstance(metric, str) and 'mean_' + metric in VALIDATION_COLUMNS:
+        return VALIDATION_COLUMNS.index('mean_' + metric)
+    raise ValueError('metric=%r: expected one of %s (or l1_final, l1_mean, JSD_final, JSD_mean for the means)'
+                     % (metric, ', '.join(VALIDATION_COLUMNS)))
+
+
+class Validation:
+    """What train(..., validate=Validation(...)) checks on held-out days, on the device, every `period` episodes.
+    emp [N, L, d] (NumPy; the held-out rows) or indir (read by load_empirical with episode_length, at the first call: its d is
+    the population's) -- exactly one of them; repeats: rollouts per held-out file; metric: the column of VALIDATION_COLUMNS the
+    best iterate is selected by (smaller is better; 'crps' / 'energy' need score=True); patience > 0: a learner whose metric
+    has not improved in `patience` consecutive checks stops (learner_state STOPPED); score=True: also the proper scores of
+    the members (columns 'crps', 'energy').  Every argument is checked here, on the host."""
+
+    def __init__(self, emp=None, indir=None, period=1, repeats=1, metric='JSD_mean', patience=0, score=False, episode_length=16):
+        if (emp is None) == (indir is None):
+            raise ValueError('Validation: give exactly one of emp (an [N, L, d] array) and indir (a directory of held-out files)')
+        for name, v, lo in (('period', period, 1), ('repeats', repeats, 1), ('patience', patience, 0),
+                            ('episode_length', episode_length, 2)):
+            if int(v) != v or int(v) < lo:
+                raise ValueError('Validation: %s=%r, expected an integer >= %d' % (name, v, lo))
+        self.column = validation_column(metric)
+        self.score = bool(score)
+        if self.column >= 8 and not self.score:
+            raise ValueError('Validation: metric=%r needs score=True' % (metric,))
+        if self.score and int(repeats) > L.FORECAST_MAX_REPEATS:
+            raise ValueError('Validation: repeats=%d > %d with score=True' % (repeats, L.FORECAST_MAX_REPEATS))
+        if emp is not None:
+            emp = np.array(emp, dtype=np.float64)
+            if emp.ndim != 3 or emp.shape[0] < 1 or emp.shape[1] < 2 or not 1 <= emp.shape[2] <= 64:
+                raise ValueError('Validation: emp must be [N >= 1, L >= 2, 1 <= d <= 64], got %s' % (emp.shape,))
+        self.emp, self.indir = emp, indir
+        self.metric, self.period, self.repeats, self.patience = metric, int(period), int(repeats), int(patience)
+        self.episode_length = int(episode_length)
+
+    def rows(self, d):
+        """The held-out rows [N, L, d] fp64 for a population of dimension d (ValueError when emp has another d)."""
+        if self.emp is None:
+            self.emp = load_empirical(self.indir, d, self.episode_length)
+        if self.emp.shape[2] != d:
+            raise ValueError('Validation: emp has d=%d, the population d=%d' % (self.emp.shape[2], d))
+        return self.emp
+
+
+class ValidationTrace:
+    """The held-out checks of one train(..., validate=...) call (NumPy): curve [K, C, 10] (VALIDATION_COLUMNS; NaN past
+    checks[k]), checks [K], episodes [C] (the call-episode number after which check c ran, 1-based), and the best iterate per
+    learner: best_value, best_check (-1: none), best_episode (0: none), best_theta, best_w."""
+
+    def __init__(self, curve, checks, period, best_value, best_check, best_theta, best_w, column):
+        self.curve, self.checks, self.column = curve, checks, column
+        self.episodes = (np.arange(curve.shape[1]) + 1) * int(period)
+        self.best_value, self.best_check, self.best_theta, self.best_w = best_value, best_check, best_theta, best_w
+        self.best_episode = np.where(best_check >= 0, (best_check + 1) * int(period), 0)
+
+
 def evaluate_policies(emp, thetas, shifts, alpha_scales, seeds, first_step, repeats, precision, device, ctx):
     """The eight metrics [K, 8] (NumPy) of K policies on the test rows `emp` [N, L, d]: one ops.evaluate_pop call.  `thetas`,
     `shifts`, `alpha_scales` fp64 and `seeds` int64 device tensors [K].  MfgError when a mixed-precision policy left the
@@ -952,6 +1021,8 @@ class _Population:
         # per-learner activity (the population control block): host mirrors, read back with train()'s one synchronisation
         self._act = LearnerActivity(K)
         self._ctl = None     # the block's device tensors, made by the first train() call that needs one
+        self.validation = None     # the ValidationTrace of the last train(..., validate=...) call
+        self._val_dev = None       # its snapshots (best_theta, best_w) on the device, for restore_best
 
     # ------------------------------------------------------------------ state
     @property
@@ -1010,7 +1081,73 @@ class _Population:
         return self._bufs
 
     # ------------------------------------------------------------------ training
-    def _train(self, num_episodes, lr_critic, lr_actor, run, stop_criteria=-1, isolate=False):
+    def _validated(self, validate, num_episodes, run):
+        """`run` wrapped in the validation block of `validate` for one train() call: reserves the checks' Philox steps
+        (first_step = the counter, which moves on by L - 1 BEFORE the first training episode), makes the block's device arrays
+        -- curve sized to exactly num_episodes // period rows --, binds the block around run() and leaves the results on
+        self.validation (finish(), called once the call's one synchronisation has happened)."""
+        K, dev, F = self.K, self.device, ops.num_features(self.d)
+        emp = validate.rows(self.d)
+        N, Lr, _ = emp.shape
+        C = int(num_episodes) // validate.period
+        first_step = self._rng_step
+        if first_step + Lr - 1 + int(num_episodes) * self.episode_steps > 0xFFFFFFFF:
+            raise ValueError('validate: the Philox step counter would wrap')
+        self._rng_step += Lr - 1
+        v = {'curve': torch.full((K, max(C, 1), L.POP_VALIDATE_COLUMNS), float('nan'), dtype=torch.float64, device=dev),
+             'ints': torch.zeros(3, K, dtype=torch.int32, device=dev),       # checks | best_check | since_best
+             'best_value': torch.full((K,), float('inf'), dtype=torch.float64, device=dev),
+             'best_theta': torch.full((K,), float('nan'), dtype=torch.float64, device=dev),
+             'best_w': torch.full((K, F), float('nan'), dtype=torch.float64, device=dev)}
+        v['ints'][1].fill_(-1)
+
+        def bound_run(*args):
+            if C == 0:                               # (no check falls into this call: nothing to bind)
+                return run(*args)
+            emp64 = torch.as_tensor(emp, dtype=torch.float64, device=dev)
+            emp32 = torch.as_tensor(emp.astype(np.float32), device=dev)
+            ws = ops.pop_validate_workspace(N, Lr, self.d, K, validate.repeats, validate.score, dev)
+            self._ctx.set_pop_validate(emp32, emp64, period=validate.period, column=validate.column, with_score=validate.score,
+                                       patience=validate.patience, first_step=first_step, repeats=validate.repeats,
+                                       curve=v['curve'], checks=v['ints'][0], best_value=v['best_value'],
+                                       best_check=v['ints'][1], since_best=v['ints'][2], best_theta=v['best_theta'],
+                                       best_w=v['best_w'], workspace=ws)
+            try:
+                return run(*args)
+            except L.MfgError as e:
+                if e.code:                           # refused by the library before anything was launched
+                    self._rng_step = first_step
+                raise
+            finally:
+                self._ctx.set_pop_validate()
+
+        def finish():
+            ints = v['ints'].cpu().numpy()
+            self._val_dev = (v['best_theta'], v['best_w'])
+            self.validation = ValidationTrace(v['curve'][:, :C].cpu().numpy(), ints[0].copy(), validate.period,
+                                              v['best_value'].cpu().numpy(), ints[1].copy(), v['best_theta'].cpu().numpy(),
+                                              v['best_w'].cpu().numpy(), validate.column)
+        return bound_run, finish
+
+    def restore_best(self, k=None):
+        """Copy the best held-out iterate of the last train(..., validate=...) call -- theta and w as they were at the check
+        validation.best_check -- back into learner k (None: every learner that recorded one).  ValueError for a learner
+        without one (k given), or when no validated call has run."""
+        if self.validation is None:
+            raise ValueError('restore_best: no train(..., validate=...) call has run')
+        have = self.validation.best_check >= 0
+        if k is not None:
+            if not 0 <= int(k) < self.K:
+                raise IndexError('learner %d of %d' % (k, self.K))
+            if not have[int(k)]:
+                raise ValueError('restore_best: learner %d has no recorded best iterate' % int(k))
+            have = np.arange(self.K) == int(k)
+        sel = torch.as_tensor(np.flatnonzero(have), device=self.device)
+        best_theta, best_w = self._val_dev
+        self._theta[sel] = best_theta[sel]
+        self._w[sel] = best_w[sel]
+
+    def _train(self, num_episodes, lr_critic, lr_actor, run, stop_criteria=-1, isolate=False, validate=None):
         """The frame of train(): checks, learning rates as device arrays [K], run(buffers, lrc, lra, acc) -- the native calls
         -- and the Philox step; returns acc [K, num_episodes] as a NumPy array.  MfgError when a mixed-precision launch left the
         fp32 range.  A stop criterion, isolate=True or a learner that failed earlier: the call runs under the population's
@@ -1023,6 +1160,13 @@ class _Population:
         lra = torch.as_tensor(broadcast('lr_actor', lr_actor, K), device=self.device)
         stop = stop_criteria_array(stop_criteria, K)
         control = needs_control(stop, isolate, self._act.state)
+        finish = None
+        if validate is not None:
+            if not isinstance(validate, Validation):
+                raise TypeError('validate: expected a population.Validation or None')
+            control = control or validate.patience > 0     # (the patience stop moves the control block's states)
+            if num_episodes > 0:
+                run, finish = self._validated(validate, num_episodes, run)
         if not control:
             # (no learner has failed here, or the call would be a controlled one: everybody is active for the whole call)
             self._act.state[:] = ACTIVE
@@ -1034,6 +1178,8 @@ class _Population:
             run(self._buffers(), lrc, lra, acc)
             self._rng_step += num_episodes * self.episode_steps
             out = acc.cpu().numpy()
+            if finish:
+                finish()
             if self.precision == 'mixed' and self._ctx.status(synchronize=True):
                 raise L.MfgError('a mixed-precision sampling launch of this population ran with |theta| (1 + |shift|) > 86 '
                                  '(or theta not finite): its outputs are NaN; use precision=\'f64\', then clear_status()')
@@ -1057,6 +1203,8 @@ class _Population:
             self._ctx.set_pop_control()
         self._rng_step += num_episodes * self.episode_steps
         out = acc.cpu().numpy()
+        if finish:
+            finish()
         ints = c['ints'].cpu().numpy()
         self._act.state, self._act.status, self._act.episodes = ints[0].copy(), ints[1].copy(), ints[2].copy()
         if self.precision == 'mixed' and self._ctx.status(synchronize=False):
@@ -1276,7 +1424,7 @@ class ActorCriticPopulation(_Population):
 
     @_with_ctx
     def train(self, num_episodes, gamma=1, constant=0, lr_critic=0.1, lr_actor=0.001, *, first_episode=0, stop_criteria=-1,
-              isolate=False):
+              isolate=False, validate=None):
         """`num_episodes` episodes of every learner (mfg_ac2.py:448-539; update per env step or per episode as chosen at
         construction).  lr_critic / lr_actor: scalars or [K].  Returns a NumPy array [K, num_episodes] of what
         actor_critic.train books per episode (step mode: the sum of the T updates' mean rewards; rollout mode: the one
@@ -1291,14 +1439,22 @@ class ActorCriticPopulation(_Population):
         cleared -- differs from the plain call in how a diverging learner is reported: it is booked to its own word and
         frozen, the context's status word stays 0, the other learners finish the call, and train() then raises MfgError
         naming the failed learners.  Later calls are not refused; they skip those learners (and raise again when
-        isolate=False) until clear_status()."""
+        isolate=False) until clear_status().
+        validate (a Validation; None: nothing changes): every validate.period episodes the call checks every active learner on
+        the held-out rows ON THE DEVICE -- the launches of evaluate() on its current theta, with score=True those of
+        forecast_score() -- with no host round trip: the curve, the best iterate and (patience > 0) the stop are kept by the
+        device and land on self.validation (a ValidationTrace); restore_best() puts the best iterate back.  Every check uses
+        the same Philox steps (common random numbers along the curve): first_step = the counter at the call, which moves on
+        by L - 1 before the first training episode.  The per-step launches run such a call (resident=True refuses it)."""
         T = self.episode_steps
+        if validate is not None and self.resident is True:
+            raise ValueError('resident=True: a validated call runs the per-step launches; use resident=None or False')
         resident = False
         if self.update_every == 'step':
             control = needs_control(stop_criteria_array(stop_criteria, self.K), isolate, self._act.state)
             # (the rule was measured in mixed precision; strict precision keeps the per-step launches unless forced)
             rule = self.precision == 'mixed' and resident_rule(self.K, self.d, self.batch)
-            resident = use_resident(self.resident, rule, control)
+            resident = validate is None and use_resident(self.resident, rule, control)
         step_call = ops.train_episodes_pop_resident if resident else ops.train_episodes_pop
 
         def run(b, lrc, lra, acc):
@@ -1312,7 +1468,7 @@ class ActorCriticPopulation(_Population):
                                        self._shifts_dev, self._alphas_dev, self._w, gamma, b['G'], b['ws'], b['run'], lrc, lra,
                                        self._seeds_dev, reward_kind=self.reward_kind, first_step=self._rng_step,
                                        reward_acc=acc, precision=self.precision)
-        return self._train(num_episodes, lr_critic, lr_actor, run, stop_criteria, isolate)
+        return self._train(num_episodes, lr_critic, lr_actor, run, stop_criteria, isolate, validate)
 
     @_with_ctx
     def evaluate(self, episode_length=16, indir='test_normalized_round2', outfile='eval_mfg_round2/test_eval_fixed_reward.csv',

@@ -613,6 +613,75 @@ int mfg_forecast_score(const float* traj, int64_t N, int H, int d, int K, int re
                        double* crps, int32_t* less, int32_t* equal, double* energy, double* summary, void* workspace,
                        size_t workspace_bytes, mfg_stream_t stream);
 
+/* Population validation block: held-out checks INSIDE a population training call, so that a held-out learning curve, the best
+ * iterate and "stop when the held-out metric stops improving" need no host round trip between episodes (the reference
+ * evaluates only the iterate a training ends on, mfg_ac2.py:595-670).  Like the control block above it is bound to a context
+ * by a setter that takes no stream, and the four population training calls (mfg_train_episodes_pop, mfg_train_rollouts_pop,
+ * mfg_train_episodes_irl_pop, mfg_train_rollouts_irl_pop) act on it.  By value:
+ *   N, L, repeats      as for mfg_evaluate_pop (N held-out files of L rows, R = repeats rollouts per file)
+ *   period >= 1        a check runs after the closing update of the call's episode k (0-based) whenever (k + 1) % period == 0 --
+ *                      with a control block also bound, after that episode's retire step
+ *   column             in [0, 10): the curve column the best iterate is selected by (smaller is better); 8, 9 need with_score
+ *   with_score         0 / 1: also score the members just rolled out (mfg_forecast_score with the energy score)
+ *   patience >= 0      > 0: a learner whose `column` has not improved in `patience` consecutive checks is stopped (state 1, as the
+ *                      early stop); needs a control block bound when a call is made
+ *   first_step         the Philox step of EVERY check's rollouts (steps first_step .. first_step + L - 2): common random numbers
+ *                      along the curve, so two checks differ by theta alone
+ *   max_checks >= 1    rows of `curve` per learner
+ *   K                  the population size
+ *   workspace_bytes    >= mfg_pop_validate_workspace_bytes(N, L, d, K, repeats, with_score) for the d of the call
+ * Device arrays, owned and initialised by the caller:
+ *   emp32, emp64 [N,L,d]      the held-out rows (fp32 for the rollouts, the JSD and the ranks; fp64 for L1, CRPS, energy)
+ *   curve [K, max_checks, 10] fp64: row c of learner k is its c-th check.  Columns 0-7: the eight metrics of mfg_evaluate_pop in
+ *                             the CSV's column order, bit for bit what that call returns for the learner's theta at the check (the
+ *                             same kernels, the call's shift / alpha_scale / seed arrays and precision).  Column 8 (9): the mean over
+ *                             the hours l = 1 .. L-1 of summary[k,l,0] (summary[k,l,1]) of mfg_forecast_score on the check's
+ *                             members -- CRPS (energy score) --, added in hour order in fp64 by one lane and divided by L - 1;
+ *                             NaN without with_score
+ *   checks [K] int32          += 1 per check the learner took part in (the caller zeroes it); a row is written only while
+ *                             checks[k] < max_checks, the best tracking below goes on past that
+ *   best_value [K] fp64       the smallest finite value of `column` so far (the caller sets +inf)
+ *   best_check [K] int32      the check it was seen at (the caller sets -1); the EARLIEST minimum wins (strict <)
+ *   since_best [K] int32      checks since then (the caller zeroes it)
+ *   best_theta [K], best_w [K,F] fp64: theta[k] and w[k,:] as they were at that check
+ *   workspace                 scratch (the members, the metrics and the scores of one check), 8-byte aligned
+ * A check is three groups of launches on the call's stream, no host read, no allocation: the two launches of mfg_evaluate_pop,
+ * with with_score the two of mfg_forecast_score, and k_pop_validate_select (one wave per learner).  A learner that is not active
+ * at the check (state[k] != 0 under a control block) is skipped entirely: its blocks of every launch return at once and none of
+ * its arrays is touched.  Mixed precision: a check reports into and is refused on the status word exactly as mfg_evaluate_pop;
+ * under a control block it books to the learner, as the training launches do.  Without a block the calls issue exactly the
+ * launches they always did.
+ * Checked when the block is set: MFG_EINVAL for a null context or pointer, period < 1, max_checks < 1, patience < 0, column
+ * outside [0, 10) or >= 8 without with_score, with_score not 0 / 1, K outside [1, MFG_POP_MAX_K], N < 1, L < 2, repeats < 1, N L
+ * or N repeats >= 2^31, first_step + L - 1 wrapping; MFG_EUNSUPPORTED for repeats > MFG_FORECAST_MAX_REPEATS with with_score.
+ * Checked again before a call launches anything: MFG_EINVAL when K differs from the call's K or patience > 0 without a control
+ * block; MFG_EWORKSPACE when workspace_bytes is below mfg_pop_validate_workspace_bytes for the call's d.
+ * mfg_train_episodes_pop_resident refuses a bound validation block with MFG_EUNSUPPORTED, as it refuses a control block.
+ * mfg_pop_validate_workspace_bytes is 0 for a degenerate shape, never below mfg_evaluate_pop_workspace_bytes(N, L, d, K,
+ * repeats, 0) otherwise, and larger with with_score. */
+typedef struct mfg_pop_validate {
+  const float* emp32;
+  const double* emp64;
+  double* curve;
+  int32_t* checks;
+  double* best_value;
+  int32_t* best_check;
+  int32_t* since_best;
+  double* best_theta;
+  double* best_w;
+  void* workspace;
+  size_t workspace_bytes;
+  int64_t N;
+  int32_t L, repeats;
+  int32_t period, column;
+  int32_t with_score, patience;
+  int32_t max_checks, K;
+  uint32_t first_step;
+} mfg_pop_validate_t;
+#define MFG_POP_VALIDATE_COLUMNS 10
+int mfg_ctx_set_pop_validate(mfg_ctx_t* ctx, const mfg_pop_validate_t* block);
+size_t mfg_pop_validate_workspace_bytes(int64_t N, int L, int d, int K, int repeats, int with_score);
+
 /* Finite populations: a member is ONE population of A agents (1 <= A <= MFG_AGENTS_MAX) instead of the mean-field limit
  * pi' = P^T pi that every other entry rolls.  Its state is counts [d] int32 (d <= 64) summing to A; each agent of topic i draws
  * its next topic from row P[i,:] of the member's action, so the histogram carries sampling noise of order 1 / sqrt(A) on top of
