@@ -202,6 +202,18 @@ class PopValidateStruct(C.Structure):
 SIGNATURES['mfg_ctx_set_pop_validate'] = (_i32, [_p, C.POINTER(PopValidateStruct)])
 SIGNATURES['mfg_pop_validate_workspace_bytes'] = (_sz, [_i64, _i32, _i32, _i32, _i32, _i32])
 
+
+class PopEvolveStruct(C.Structure):
+    """mfg_pop_evolve_t of include/mfg_hip.h: the exploit / explore steps a population training call runs behind its checks."""
+    _fields_ = ([(n, C.c_void_p) for n in ('lr_critic', 'lr_actor', 'order', 'active', 'rank', 'parent', 'lr_log')]
+                + [('seed', C.c_uint64)]
+                + [(n, C.c_double) for n in ('factor_down', 'factor_up', 'lr_critic_min', 'lr_critic_max', 'lr_actor_min',
+                                             'lr_actor_max')]
+                + [(n, C.c_int32) for n in ('every', 'n_top', 'n_bottom', 'perturb', 'max_steps', 'K')])
+
+
+SIGNATURES['mfg_ctx_set_pop_evolve'] = (_i32, [_p, C.POINTER(PopEvolveStruct)])
+
 SIGNATURES['mfg_evaluate_pop_workspace_bytes'] =(_sz, [_i64, _i32, _i32, _i32, _i32, _i32])
 SIGNATURES['mfg_evaluate_pop'] = (_i32, [_p, _p, _i64, _i32, _i32, _i32, _p, _p, _p, _p, _u32, _i32, _i32, _p, _p, _p, _sz, _p])
 

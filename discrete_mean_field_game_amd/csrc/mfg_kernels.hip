@@ -28,6 +28,7 @@
 #include "mfg_consistency_pop.h"
 #include "mfg_irl_population.h"
 #include "mfg_population.h"
+#include "mfg_pop_evolve.h"
 #include "mfg_pop_validate.h"
 #include "mfg_batch_sums.h"
 #include "mfg_host.h"
@@ -133,6 +134,8 @@ struct mfg_ctx {
   mfg_pop_control_t ctl{};
   bool has_val = false;  // population validation block (mfg_ctx_set_pop_validate): held-out checks inside those calls
   mfg_pop_validate_t val{};
+  bool has_evo = false;  // population evolve block (mfg_ctx_set_pop_evolve): exploit / explore steps behind those checks
+  mfg_pop_evolve_t evo{};
 };
 // The binding is per THREAD, the object's lifetime is not: a context may be destroyed by another thread than the one(s) it is
 // bound on (a garbage collector drops the last reference wherever it runs).  Every live context is therefore registered with
@@ -445,6 +448,36 @@ int mfg_ctx_set_pop_validate(mfg_ctx_t* ctx, const mfg_pop_validate_t* block) {
                 MFG_FORECAST_MAX_REPEATS);
   ctx->val = v;
   ctx->has_val = true;
+  return MFG_OK;
+}
+
+static bool pop_evolve_complete(const mfg_pop_evolve_t& e) {
+  return e.lr_critic && e.lr_actor && e.order && e.active && e.rank && e.parent && e.lr_log;
+}
+
+int mfg_ctx_set_pop_evolve(mfg_ctx_t* ctx, const mfg_pop_evolve_t* block) {
+  REQUIRE(ctx && ctx_is_live(ctx), "null or destroyed context");
+  if (!block) {
+    ctx->has_evo = false;
+    ctx->evo = mfg_pop_evolve_t{};
+    return MFG_OK;
+  }
+  const mfg_pop_evolve_t& e = *block;
+  REQUIRE(pop_evolve_complete(e), "population evolve block: null pointer");
+  REQUIRE(e.K >= 1 && e.K <= MFG_POP_MAX_K, "population evolve block: K outside [1, MFG_POP_MAX_K]");
+  REQUIRE(e.every >= 1, "population evolve block: every < 1");
+  REQUIRE(e.n_top >= 1 && e.n_bottom >= 1, "population evolve block: n_top < 1 or n_bottom < 1");
+  REQUIRE((int64_t)e.n_top + (int64_t)e.n_bottom <= e.K, "population evolve block: n_top + n_bottom > K");
+  REQUIRE(e.max_steps >= 1, "population evolve block: max_steps < 1");
+  REQUIRE(std::isfinite(e.factor_down) && e.factor_down > 0.0 && std::isfinite(e.factor_up) && e.factor_up > 0.0,
+          "population evolve block: a factor is not finite or <= 0");
+  REQUIRE(std::isfinite(e.lr_critic_max) && e.lr_critic_min > 0.0 && e.lr_critic_min <= e.lr_critic_max,
+          "population evolve block: lr_critic bounds need 0 < min <= max, finite");
+  REQUIRE(std::isfinite(e.lr_actor_max) && e.lr_actor_min > 0.0 && e.lr_actor_min <= e.lr_actor_max,
+          "population evolve block: lr_actor bounds need 0 < min <= max, finite");
+  REQUIRE(e.perturb >= 0 && e.perturb <= 3, "population evolve block: perturb outside [0, 3]");
+  ctx->evo = e;
+  ctx->has_evo = true;
   return MFG_OK;
 }
 
@@ -1219,6 +1252,52 @@ struct PopValidate {
   }
 };
 
+// The evolve block a forward population training call runs under -- that of the bound context, none without one
+// (mfg_ctx_set_pop_evolve, mfg_pop_evolve.h).  begin() checks the block against the call and its validation block before ANYTHING
+// is launched (after PopValidate::begin, ahead of PopControl::begin); step(k, p) enqueues the two launches of a step behind
+// pv.check(k, p) when the check that just ran is an `every`-th one.  Without a block neither does anything.
+struct PopEvolve {
+  const mfg_pop_evolve_t* e = nullptr;
+  const PopValidate* pv = nullptr;
+  double *theta = nullptr, *w = nullptr;
+  hipStream_t st = nullptr;
+
+  int begin(const PopValidate& pv_, int K, int64_t episodes, double* theta_, double* w_, const double* lr_critic,
+            const double* lr_actor, hipStream_t st_) {
+    const mfg_ctx* c = bound_ctx();
+    if (!c || !c->has_evo) return MFG_OK;
+    REQUIRE(pop_evolve_complete(c->evo), "population evolve block: null pointer");
+    REQUIRE(c->evo.K == K, "population evolve block: set for another population size K");
+    REQUIRE(pv_.v, "population evolve block: needs a population validation block (mfg_ctx_set_pop_validate)");
+    REQUIRE(c->evo.lr_critic == lr_critic && c->evo.lr_actor == lr_actor,
+            "population evolve block: lr_critic / lr_actor are not the call's arrays");
+    REQUIRE((episodes / pv_.v->period) / c->evo.every <= c->evo.max_steps,
+            "population evolve block: max_steps < (episodes / period) / every");
+    e = &c->evo;
+    pv = &pv_;
+    theta = theta_, w = w_, st = st_;
+    return MFG_OK;
+  }
+  int step(int64_t k, const PopArgs& p) const {
+    if (!e || (k + 1) % pv->v->period != 0) return MFG_OK;
+    const int64_t checks = (k + 1) / pv->v->period;  // (the check that just ran is number checks - 1 of the call)
+    if (checks % e->every != 0) return MFG_OK;
+    char* ws = reinterpret_cast<char*>(pv->v->workspace);
+    PopEvolveArgs a{};
+    a.state = p.state;
+    const mfg_ctx* c = bound_ctx();
+    a.theta_prev = (p.state && c && c->has_ctl) ? c->ctl.theta_prev : nullptr;
+    a.metrics = reinterpret_cast<const double*>(ws + pv->lay.metrics);
+    a.summary = pv->v->with_score ? reinterpret_cast<const double*>(ws + pv->lay.summary) : nullptr;
+    a.theta = theta;
+    a.w = w;
+    a.F = p.F;
+    a.step = (int32_t)(checks / e->every - 1);
+    launch_pop_evolve(*e, *pv->v, a, st);
+    return check_launch("pop_evolve");
+  }
+};
+
 // the argument block of a population call (the call sets the strides that depend on its flow: s_pi0, s_gpi, s_n, s_P)
 static PopArgs pop_args(int K, int64_t B, int d, int64_t T, int64_t episodes, const uint64_t* seed, const double* shift,
                         const double* alpha_scale, const double* lr_critic, const double* lr_actor, size_t workspace_bytes) {
@@ -1257,6 +1336,8 @@ int mfg_train_episodes_pop(const float* mat_pi0, int64_t num_start, float* pi_io
   p.s_n = B;
   PopValidate pv;
   if (const int rc = pv.begin(K, d, theta, w, precision, S(stream)); rc != MFG_OK) return rc;
+  PopEvolve pe;
+  if (const int rc = pe.begin(pv, K, episodes, theta, w, lr_critic, lr_actor, S(stream)); rc != MFG_OK) return rc;
   PopControl pc;
   if (const int rc = pc.begin(p, theta, w, shift, precision == MFG_PRECISION_MIXED, S(stream)); rc != MFG_OK) return rc;
   for (int64_t k = 0; k < episodes; ++k) {
@@ -1269,6 +1350,7 @@ int mfg_train_episodes_pop(const float* mat_pi0, int64_t num_start, float* pi_io
     if (rc != MFG_OK) return rc;
     pc.retire();
     if (const int rv = pv.check(k, p); rv != MFG_OK) return rv;
+    if (const int rv = pe.step(k, p); rv != MFG_OK) return rv;
   }
   return MFG_OK;
 }
@@ -1299,6 +1381,10 @@ int mfg_train_episodes_pop_resident(const float* mat_pi0, int64_t num_start, flo
   if (const mfg_ctx* c = bound_ctx(); c && c->has_val)
     return fail(MFG_EUNSUPPORTED, "%s", "resident population: the bound context carries a population validation block "
                                         "(mfg_train_episodes_pop runs the held-out checks)");
+  if (const mfg_ctx* c = bound_ctx(); c && c->has_evo)
+    return fail(MFG_EUNSUPPORTED, "%s", "resident population: the bound context carries a population evolve block (the "
+                                        "resident kernel reads its learning rates once per launch; mfg_train_episodes_pop "
+                                        "runs the exploit / explore steps)");
   const size_t need = pop_workspace_need(d, B, true);
   if (workspace_bytes < need)
     return fail(MFG_EWORKSPACE, "population workspace: need %lld bytes per learner, have %lld", (long long)need,
@@ -1372,6 +1458,8 @@ int mfg_train_rollouts_pop(const float* mat_pi0, int64_t num_start, int64_t B, i
   if (const int rc = pv.begin(K, d, theta, w, (flags & MFG_ROLLOUT_F64) ? MFG_PRECISION_F64 : MFG_PRECISION_MIXED, S(stream));
       rc != MFG_OK)
     return rc;
+  PopEvolve pe;
+  if (const int rc = pe.begin(pv, K, episodes, theta, w, lr_critic, lr_actor, S(stream)); rc != MFG_OK) return rc;
   PopControl pc;
   if (const int rc = pc.begin(p, theta, w, shift, !(flags & MFG_ROLLOUT_F64), S(stream)); rc != MFG_OK) return rc;
   for (int64_t k = 0; k < episodes; ++k) {
@@ -1383,6 +1471,7 @@ int mfg_train_rollouts_pop(const float* mat_pi0, int64_t num_start, int64_t B, i
     if (rc != MFG_OK) return rc;
     pc.retire();
     if (const int rv = pv.check(k, p); rv != MFG_OK) return rv;
+    if (const int rv = pe.step(k, p); rv != MFG_OK) return rv;
   }
   return MFG_OK;
 }
@@ -1748,6 +1837,12 @@ int mfg_consistency_pop(const float* start32, int64_t N, int H, int d, int K, co
                 "reward network (d = 21 / 15, 5 / 2 / 3, n_fc3 <= 16, 8-byte aligned fc3_w of every learner)",           \
                 d, net->k1, net->f2, net->k2, net->n3, net->n4)
 
+// the IRL population calls refuse a bound evolve block (mfg_ctx_set_pop_evolve) before anything is launched
+#define REFUSE_POP_EVOLVE()                                                                                              \
+  if (const mfg_ctx* c_evo = bound_ctx(); c_evo && c_evo->has_evo)                                                       \
+  return fail(MFG_EUNSUPPORTED, "%s", "IRL population: the bound context carries a population evolve block; IRL learners " \
+                                      "may carry different reward networks, which an exploit would have to copy too")
+
 // a population with a geometry table (geom_host / geom_dev given; rn_pop_nets_struct, mfg_irl_population.h): its checks, then
 // the launches are set up with the row base and the table's maxima
 #define IRL_POP_NETS()                                                                                                   \
@@ -2006,6 +2101,7 @@ int mfg_train_episodes_irl_pop(const float* mat_pi0, int64_t num_start, float* p
   REQUIRE(rn_call0 && pi_out && pi_scratch, "null pointer");
   IRL_POP_NETS();
   CHECK_IRL_POP();
+  REFUSE_POP_EVOLVE();
   CHECK_PRECISION();
   const size_t need = irl_step_ws(workspace, B, d).bytes;
   if (workspace_bytes < need)
@@ -2049,6 +2145,7 @@ int mfg_train_rollouts_irl_pop(const float* mat_pi0, int64_t num_start, int64_t 
   REQUIRE(rn_call0 && pi_traj, "null pointer");
   IRL_POP_NETS();
   CHECK_IRL_POP();
+  REFUSE_POP_EVOLVE();
   const size_t need = pop_workspace_need(d, B * T, false);
   if (workspace_bytes < need)
     return fail(MFG_EWORKSPACE, "IRL population workspace: need %lld bytes per learner, have %lld", (long long)need,

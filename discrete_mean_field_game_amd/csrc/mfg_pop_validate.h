@@ -42,6 +42,25 @@ inline PopValidateLayout pop_validate_layout(int64_t N, int L, int d, int K, int
   return o;
 }
 
+// Learner k's ten-column row of a check, r[0 .. 9]: the eight metrics, and the hour means of the score summary added in hour
+// order in fp64 (NaN without a summary).  ONE definition for k_pop_validate_select, which writes the row, and for the evolve
+// step (mfg_pop_evolve.h), which ranks the learners by one of its columns: the same bits in both.
+__device__ __forceinline__ void pop_validate_row(const mfg_pop_validate_t& v, const double* __restrict__ metrics,
+                                                 const double* __restrict__ summary, int k, double* r) {
+#pragma unroll
+  for (int q = 0; q < 8; ++q) r[q] = metrics[(int64_t)k * 8 + q];
+  r[8] = r[9] = NAN;
+  if (summary) {
+    double s0 = 0.0, s1 = 0.0;
+    for (int l = 1; l < v.L; ++l) {  // (hour 0 is the start row: every member equals the observation there)
+      s0 += summary[((int64_t)k * v.L + l) * 2];
+      s1 += summary[((int64_t)k * v.L + l) * 2 + 1];
+    }
+    r[8] = s0 / (double)(v.L - 1);
+    r[9] = s1 / (double)(v.L - 1);
+  }
+}
+
 // state: the control block's [K] activity states, or NULL (every learner is active; patience is then 0).  metrics [K,8];
 // summary [K,L,2] or NULL (columns 8, 9 are NaN); theta [K], w [K,F]: the call's parameters at the check.
 void launch_pop_validate_select(const mfg_pop_validate_t& v, int32_t* state, const double* metrics, const double* summary,

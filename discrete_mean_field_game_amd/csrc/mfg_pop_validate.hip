@@ -19,18 +19,7 @@ __global__ __launch_bounds__(PV_WAVE) void k_pop_validate_select(mfg_pop_validat
   double val = NAN;
   if (lane == 0) {
     double r[PV_COLS];
-#pragma unroll
-    for (int q = 0; q < 8; ++q) r[q] = metrics[(int64_t)k * 8 + q];
-    r[8] = r[9] = NAN;
-    if (summary) {
-      double s0 = 0.0, s1 = 0.0;
-      for (int l = 1; l < v.L; ++l) {  // (hour 0 is the start row: every member equals the observation there)
-        s0 += summary[((int64_t)k * v.L + l) * 2];
-        s1 += summary[((int64_t)k * v.L + l) * 2 + 1];
-      }
-      r[8] = s0 / (double)(v.L - 1);
-      r[9] = s1 / (double)(v.L - 1);
-    }
+    pop_validate_row(v, metrics, summary, k, r);
     if (row >= 0 && row < v.max_checks) {
       double* out = v.curve + ((int64_t)k * v.max_checks + row) * PV_COLS;
 #pragma unroll

@@ -177,6 +177,36 @@ class Context:
                                   int(column), int(with_score), int(patience), max_checks, K, int(first_step))
         L.check(L.lib().mfg_ctx_set_pop_validate(self._ptr, C.byref(blk)), 'mfg_ctx_set_pop_validate')
 
+    def set_pop_evolve(self, lr_critic=None, lr_actor=None, *, every=1, n_top=1, n_bottom=1, perturb=3, factors=(0.8, 1.25),
+                       lr_critic_bounds=(1e-6, 10.0), lr_actor_bounds=(1e-8, 1.0), seed=0, order=None, active=None, rank=None,
+                       parent=None, lr_log=None, K=None):
+        """mfg_ctx_set_pop_evolve: bind a population evolve block to this context; the forward population training calls made
+        with the context (and a validation block) bound then run an exploit / explore step behind every `every`-th held-out
+        check (include/mfg_hip.h).  lr_critic / lr_actor [K] float64: the SAME device tensors the training call is given (a
+        step writes them); order [K], active [1] int32 scratch; rank, parent [K, max_steps] int32 (the caller sets -1) and
+        lr_log [K, max_steps, 2] float64 (NaN) logs.  perturb: bit 0 critic, bit 1 actor.  K: what the block announces
+        (default the tensors').  No arguments: clear it.  The caller keeps the tensors alive while the block is set."""
+        import ctypes as C
+        if lr_critic is None:
+            L.check(L.lib().mfg_ctx_set_pop_evolve(self._ptr, None), 'mfg_ctx_set_pop_evolve')
+            return
+        n = int(lr_critic.shape[0])
+        if rank is None or rank.dim() != 2:
+            raise ValueError('set_pop_evolve: rank must be a [K, max_steps] tensor')
+        max_steps = int(rank.shape[1])
+        for name, t, dt, shape in (('lr_critic', lr_critic, torch.float64, (n,)), ('lr_actor', lr_actor, torch.float64, (n,)),
+                                   ('order', order, torch.int32, (n,)), ('active', active, torch.int32, (1,)),
+                                   ('rank', rank, torch.int32, (n, max_steps)), ('parent', parent, torch.int32, (n, max_steps)),
+                                   ('lr_log', lr_log, torch.float64, (n, max_steps, 2))):
+            if t is None or t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous() or not t.is_cuda:
+                raise ValueError('set_pop_evolve: %s must be a contiguous %s device tensor %s' % (name, dt, list(shape)))
+        blk = L.PopEvolveStruct(lr_critic.data_ptr(), lr_actor.data_ptr(), order.data_ptr(), active.data_ptr(), rank.data_ptr(),
+                                parent.data_ptr(), lr_log.data_ptr(), int(seed) & 0xFFFFFFFFFFFFFFFF, float(factors[0]),
+                                float(factors[1]), float(lr_critic_bounds[0]), float(lr_critic_bounds[1]),
+                                float(lr_actor_bounds[0]), float(lr_actor_bounds[1]), int(every), int(n_top), int(n_bottom),
+                                int(perturb), max_steps, n if K is None else int(K))
+        L.check(L.lib().mfg_ctx_set_pop_evolve(self._ptr, C.byref(blk)), 'mfg_ctx_set_pop_evolve')
+
     def close(self):
         if self._ptr is not None:
             try:

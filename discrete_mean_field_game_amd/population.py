@@ -28,6 +28,11 @@ not raise and does not touch the context's status word: `learner_state` (0 activ
 `learner_status` tell what happened, failed learners are skipped (NaN rows) by everything after training, and
 clear_status(k) revives one.  The Philox step (and an IRL population's reward-call counters) advance by the whole call for
 every learner, stopped or not.
+
+Population-based training on the device: train(..., validate=Validation(...), evolve=Evolution(...)) runs an exploit / explore
+step behind every evolve.every-th held-out check (mfg_ctx_set_pop_evolve, include/mfg_hip.h): the worst active learners take
+over theta, w and the best iterate of a random one of the best and go on with perturbed learning rates, ranked, copied and
+perturbed by two small kernels inside the call; `evolution` (an EvolutionTrace) tells what happened.
 """
 from __future__ import annotations
 
@@ -299,6 +304,89 @@ class ValidationTrace:
         self.episodes = (np.arange(curve.shape[1]) + 1) * int(period)
         self.best_value, self.best_check, self.best_theta, self.best_w = best_value, best_check, best_theta, best_w
         self.best_episode = np.where(best_check >= 0, (best_check + 1) * int(period), 0)
+
+
+# -------------------------------------------------------------------------- population-based training inside train()
+# The exploit / explore steps of a population training call (mfg_ctx_set_pop_evolve, include/mfg_hip.h; Jaderberg et al. 2017,
+# truncation selection): behind every `every`-th held-out check the worst learners take over theta, w and the best iterate of
+# one of the best and go on with perturbed learning rates -- ranked, copied and perturbed on the device.
+PERTURB_BITS = {'lr_critic': 1, 'lr_actor': 2}
+
+
+def _evolve_count(name, v, K):
+    """`v` as a number of learners out of K: an integer count as it is, a fraction f in (0, 1) as max(1, floor(f K))."""
+    if isinstance(v, (int, np.integer)) and not isinstance(v, bool):
+        return int(v)
+    return max(1, int(np.floor(float(v) * K)))
+
+
+class Evolution:
+    """What train(..., validate=V, evolve=Evolution(...)) does behind every `every`-th check of V: the `bottom` worst active
+    learners (by V's metric) are replaced by copies of random members of the `top` best and continue with the donor's learning
+    rates times factors[0] or factors[1] (a fair coin per rate), clamped to the bounds.  top / bottom: fractions in (0, 1)
+    (max(1, floor(f K)) learners) or integer counts >= 1; perturb: the rates that are perturbed, a subset of ('lr_critic',
+    'lr_actor') -- the others are copied from the donor; seed: key of the donor and coin draws.  Every argument is checked
+    here, on the host; counts(K) raises ValueError when top + bottom exceed the population."""
+
+    def __init__(self, every=1, top=0.25, bottom=0.25, factors=(0.8, 1.25), perturb=('lr_critic', 'lr_actor'),
+                 lr_critic_bounds=(1e-6, 10.0), lr_actor_bounds=(1e-8, 1.0), seed=0):
+        if isinstance(every, bool) or int(every) != every or int(every) < 1:
+            raise ValueError('Evolution: every=%r, expected an integer >= 1' % (every,))
+        for name, v in (('top', top), ('bottom', bottom)):
+            if isinstance(v, bool):
+                raise ValueError('Evolution: %s=%r' % (name, v))
+            if isinstance(v, (int, np.integer)):
+                if v < 1:
+                    raise ValueError('Evolution: %s=%r, a count is >= 1' % (name, v))
+            elif not 0.0 < float(v) < 1.0:           # (a NaN fails both comparisons)
+                raise ValueError('Evolution: %s=%r, a fraction lies in (0, 1)' % (name, v))
+        factors = tuple(float(f) for f in factors)
+        if len(factors) != 2 or not all(np.isfinite(f) and f > 0 for f in factors):
+            raise ValueError('Evolution: factors=%r, expected two finite factors > 0' % (factors,))
+        if isinstance(perturb, str):
+            perturb = (perturb,)
+        perturb = tuple(perturb)
+        if any(n not in PERTURB_BITS for n in perturb) or len(set(perturb)) != len(perturb):
+            raise ValueError("Evolution: perturb=%r, expected a subset of ('lr_critic', 'lr_actor')" % (perturb,))
+        bounds = []
+        for name, b in (('lr_critic_bounds', lr_critic_bounds), ('lr_actor_bounds', lr_actor_bounds)):
+            b = tuple(float(x) for x in b)
+            if len(b) != 2 or not (0.0 < b[0] <= b[1] and np.isfinite(b[1])):
+                raise ValueError('Evolution: %s=%r, expected 0 < min <= max, finite' % (name, b))
+            bounds.append(b)
+        if isinstance(seed, bool) or int(seed) != seed or not 0 <= int(seed) < 2 ** 64:
+            raise ValueError('Evolution: seed=%r, expected an integer in [0, 2^64)' % (seed,))
+        self.every, self.top, self.bottom, self.factors, self.perturb = int(every), top, bottom, factors, perturb
+        self.lr_critic_bounds, self.lr_actor_bounds, self.seed = bounds[0], bounds[1], int(seed)
+        self.perturb_bits = sum(PERTURB_BITS[n] for n in perturb)
+
+    def counts(self, K):
+        """(n_top, n_bottom) for a population of K learners; ValueError when they exceed it."""
+        n_top, n_bottom = _evolve_count('top', self.top, K), _evolve_count('bottom', self.bottom, K)
+        if n_top + n_bottom > int(K):
+            raise ValueError('Evolution: top=%d + bottom=%d learners exceed the population (K=%d)' % (n_top, n_bottom, K))
+        return n_top, n_bottom
+
+
+class EvolutionTrace:
+    """The exploit / explore steps of one train(..., evolve=...) call (NumPy): rank [K, S] (learner k's rank among the active
+    learners at step s, 0 the best; -1: not active), parent [K, S] (the learner whose parameters k continued with: itself, or
+    its donor; -1: not active), lr [K, S, 2] (critic, actor rate after the step; NaN: not active), and lr_critic, lr_actor [K],
+    the rates the call ended on -- ready to pass to the next train()."""
+
+    def __init__(self, rank, parent, lr, lr_critic, lr_actor, every):
+        self.rank, self.parent, self.lr, self.lr_critic, self.lr_actor, self.every = rank, parent, lr, lr_critic, lr_actor, int(every)
+
+    def lineage(self, k):
+        """[S + 1] learners: entry S is k, entry s < S the learner that held, before step s, the parameters learner k went on
+        with (a step at which the holder was not active changes nothing)."""
+        S = self.parent.shape[1]
+        out = np.empty(S + 1, dtype=np.int64)
+        out[S] = int(k)
+        for s in range(S - 1, -1, -1):
+            p = int(self.parent[out[s + 1], s])
+            out[s] = p if p >= 0 else out[s + 1]
+        return out
 
 
 def evaluate_policies(emp, thetas, shifts, alpha_scales, seeds, first_step, repeats, precision, device, ctx):
@@ -1023,6 +1111,7 @@ class _Population:
         self._ctl = None     # the block's device tensors, made by the first train() call that needs one
         self.validation = None     # the ValidationTrace of the last train(..., validate=...) call
         self._val_dev = None       # its snapshots (best_theta, best_w) on the device, for restore_best
+        self.evolution = None      # the EvolutionTrace of the last train(..., evolve=...) call
 
     # ------------------------------------------------------------------ state
     @property
@@ -1129,6 +1218,37 @@ class _Population:
                                               v['best_w'].cpu().numpy(), validate.column)
         return bound_run, finish
 
+    def _evolved(self, evolve, validate, num_episodes, run):
+        """`run` wrapped in the evolve block of `evolve` for one train() call: makes the logs -- sized to exactly
+        (num_episodes // period) // every steps --, binds the block to the call's own learning-rate tensors around run() and
+        leaves the results on self.evolution (finish(), called once the call's one synchronisation has happened)."""
+        K, dev = self.K, self.device
+        n_top, n_bottom = evolve.counts(K)
+        S = (int(num_episodes) // validate.period) // evolve.every
+        e = {'ints': torch.full((2, K, max(S, 1)), -1, dtype=torch.int32, device=dev),          # rank | parent
+             'lr_log': torch.full((K, max(S, 1), 2), float('nan'), dtype=torch.float64, device=dev),
+             'scratch': torch.zeros(K + 1, dtype=torch.int32, device=dev)}                      # order | active
+        rates = []
+
+        def bound_run(b, lrc, lra, acc):
+            rates[:] = [lrc, lra]
+            if S == 0:                               # (no step falls into this call: nothing to bind)
+                return run(b, lrc, lra, acc)
+            self._ctx.set_pop_evolve(lrc, lra, every=evolve.every, n_top=n_top, n_bottom=n_bottom, perturb=evolve.perturb_bits,
+                                     factors=evolve.factors, lr_critic_bounds=evolve.lr_critic_bounds,
+                                     lr_actor_bounds=evolve.lr_actor_bounds, seed=evolve.seed, order=e['scratch'][:K],
+                                     active=e['scratch'][K:], rank=e['ints'][0], parent=e['ints'][1], lr_log=e['lr_log'])
+            try:
+                return run(b, lrc, lra, acc)
+            finally:
+                self._ctx.set_pop_evolve()
+
+        def finish():
+            ints = e['ints'][:, :, :S].cpu().numpy()
+            self.evolution = EvolutionTrace(ints[0].copy(), ints[1].copy(), e['lr_log'][:, :S].cpu().numpy(),
+                                            rates[0].cpu().numpy(), rates[1].cpu().numpy(), evolve.every)
+        return bound_run, finish
+
     def restore_best(self, k=None):
         """Copy the best held-out iterate of the last train(..., validate=...) call -- theta and w as they were at the check
         validation.best_check -- back into learner k (None: every learner that recorded one).  ValueError for a learner
@@ -1147,7 +1267,7 @@ class _Population:
         self._theta[sel] = best_theta[sel]
         self._w[sel] = best_w[sel]
 
-    def _train(self, num_episodes, lr_critic, lr_actor, run, stop_criteria=-1, isolate=False, validate=None):
+    def _train(self, num_episodes, lr_critic, lr_actor, run, stop_criteria=-1, isolate=False, validate=None, evolve=None):
         """The frame of train(): checks, learning rates as device arrays [K], run(buffers, lrc, lra, acc) -- the native calls
         -- and the Philox step; returns acc [K, num_episodes] as a NumPy array.  MfgError when a mixed-precision launch left the
         fp32 range.  A stop criterion, isolate=True or a learner that failed earlier: the call runs under the population's
@@ -1161,12 +1281,21 @@ class _Population:
         stop = stop_criteria_array(stop_criteria, K)
         control = needs_control(stop, isolate, self._act.state)
         finish = None
+        if evolve is not None:
+            if not isinstance(evolve, Evolution):
+                raise TypeError('evolve: expected a population.Evolution or None')
+            if validate is None:
+                raise ValueError('evolve: the exploit / explore steps follow held-out checks; give validate= too')
+            evolve.counts(K)
         if validate is not None:
             if not isinstance(validate, Validation):
                 raise TypeError('validate: expected a population.Validation or None')
             control = control or validate.patience > 0     # (the patience stop moves the control block's states)
             if num_episodes > 0:
-                run, finish = self._validated(validate, num_episodes, run)
+                if evolve is not None:
+                    run, finish_evolve = self._evolved(evolve, validate, num_episodes, run)
+                run, finish_validate = self._validated(validate, num_episodes, run)
+                finish = finish_validate if evolve is None else (lambda: (finish_validate(), finish_evolve()))
         if not control:
             # (no learner has failed here, or the call would be a controlled one: everybody is active for the whole call)
             self._act.state[:] = ACTIVE
@@ -1424,7 +1553,7 @@ class ActorCriticPopulation(_Population):
 
     @_with_ctx
     def train(self, num_episodes, gamma=1, constant=0, lr_critic=0.1, lr_actor=0.001, *, first_episode=0, stop_criteria=-1,
-              isolate=False, validate=None):
+              isolate=False, validate=None, evolve=None):
         """`num_episodes` episodes of every learner (mfg_ac2.py:448-539; update per env step or per episode as chosen at
         construction).  lr_critic / lr_actor: scalars or [K].  Returns a NumPy array [K, num_episodes] of what
         actor_critic.train books per episode (step mode: the sum of the T updates' mean rewards; rollout mode: the one
@@ -1445,8 +1574,17 @@ class ActorCriticPopulation(_Population):
         forecast_score() -- with no host round trip: the curve, the best iterate and (patience > 0) the stop are kept by the
         device and land on self.validation (a ValidationTrace); restore_best() puts the best iterate back.  Every check uses
         the same Philox steps (common random numbers along the curve): first_step = the counter at the call, which moves on
-        by L - 1 before the first training episode.  The per-step launches run such a call (resident=True refuses it)."""
+        by L - 1 before the first training episode.  The per-step launches run such a call (resident=True refuses it).
+        evolve (an Evolution; needs validate): population-based training ON THE DEVICE -- behind every evolve.every-th check
+        the worst active learners (by validate's metric) take over theta, w and the best iterate of a random one of the best
+        and go on with perturbed learning rates, with no host round trip (mfg_ctx_set_pop_evolve).  The steps land on
+        self.evolution (an EvolutionTrace); its lr_critic / lr_actor are the rates to pass to the next call.  A learner keeps
+        its own seed, shift and alpha_scale.  ValueError without validate= or with resident=True."""
         T = self.episode_steps
+        if evolve is not None and validate is None:
+            raise ValueError('evolve: the exploit / explore steps follow held-out checks; give validate= too')
+        if evolve is not None and self.resident is True:
+            raise ValueError('resident=True: an evolved call runs the per-step launches; use resident=None or False')
         if validate is not None and self.resident is True:
             raise ValueError('resident=True: a validated call runs the per-step launches; use resident=None or False')
         resident = False
@@ -1468,7 +1606,7 @@ class ActorCriticPopulation(_Population):
                                        self._shifts_dev, self._alphas_dev, self._w, gamma, b['G'], b['ws'], b['run'], lrc, lra,
                                        self._seeds_dev, reward_kind=self.reward_kind, first_step=self._rng_step,
                                        reward_acc=acc, precision=self.precision)
-        return self._train(num_episodes, lr_critic, lr_actor, run, stop_criteria, isolate, validate)
+        return self._train(num_episodes, lr_critic, lr_actor, run, stop_criteria, isolate, validate, evolve)
 
     @_with_ctx
     def evaluate(self, episode_length=16, indir='test_normalized_round2', outfile='eval_mfg_round2/test_eval_fixed_reward.csv',

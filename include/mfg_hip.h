@@ -682,6 +682,74 @@ typedef struct mfg_pop_validate {
 int mfg_ctx_set_pop_validate(mfg_ctx_t* ctx, const mfg_pop_validate_t* block);
 size_t mfg_pop_validate_workspace_bytes(int64_t N, int L, int d, int K, int repeats, int with_score);
 
+/* Population evolve block: population-based training (Jaderberg et al. 2017, truncation selection) on the device.  After a
+ * held-out check of the validation block above, the worst learners take over the parameters of one of the best (exploit) and
+ * go on with perturbed learning rates (explore), with no host round trip: the K values never leave the device.  Like the two
+ * blocks above it is bound to a context by a setter that takes no stream; the two forward population calls
+ * (mfg_train_episodes_pop, mfg_train_rollouts_pop) act on it, on the stream they are given.  It needs a validation block bound
+ * at the call.  By value:
+ *   every >= 1         a step runs behind k_pop_validate_select of the call's validation check c (0-based) whenever
+ *                      (c + 1) % every == 0; its index is s = (c + 1) / every - 1
+ *   n_top, n_bottom    >= 1, n_top + n_bottom <= K: the donors are the n_top best, the receivers the n_bottom worst learners
+ *   perturb            bit 0: the critic rate is perturbed, bit 1: the actor rate; a rate whose bit is clear is copied
+ *   factor_down, factor_up   finite, > 0 (e.g. 0.8, 1.25)
+ *   lr_critic_min <= lr_critic_max, lr_actor_min <= lr_actor_max, every bound > 0: the clamp of a perturbed rate
+ *   seed               key of the step's Philox draws
+ *   max_steps >= 1     steps the logs hold per learner; a call needs (episodes / period) / every <= max_steps
+ *   K                  the population size
+ * Device arrays, owned by the caller:
+ *   lr_critic, lr_actor [K] fp64   the SAME arrays the training call is given: a step writes them between two episodes, and the
+ *                                  launches of the following episodes read the new rates
+ *   order [K] int32                scratch: order[r] = the active learner of rank r at the last step
+ *   active [1] int32               scratch: the number A of active learners at the last step
+ *   rank, parent [K, max_steps] int32   logs (the caller sets -1)
+ *   lr_log [K, max_steps, 2] fp64  log: (critic, actor) rate after the step (the caller sets NaN)
+ * A step.  Learner k's value is column `column` of the validation block's row of that check, formed from the check's metrics /
+ * summary in the validation workspace by the device function k_pop_validate_select forms it with.  The active learners are all
+ * learners without a control block, and those with state[k] == 0 (after the check's patience stop) under one.  They are ordered
+ * ascending by the key (value not finite, value, k), in which a non-finite value counts as +inf: a strict total order; ties go
+ * to the smaller index, non-finite values come last in index order.  rank[k, s] is learner k's position in that order,
+ * order[rank] = k, active[0] = A.  A learner that is not active is skipped entirely: none of its arrays is touched, its log
+ * entries stay -1 / NaN.
+ * Learners are replaced only when A >= n_top + n_bottom and the learner of rank n_top - 1 has a finite value (every donor's
+ * value is then finite); otherwise the step only logs.  When they are, every active learner k with rank >= A - n_bottom draws
+ * the Philox4x32-10 block of counter (0xFFFFFFFE, s, k, 0) under the key (seed low, seed high) -- element id 0xFFFFFFFE lies
+ * outside the action draws and the start draw's 0xFFFFFFFF -- for the words x0 .. x3, and
+ *   donor = order[floor(x0 n_top / 2^32)]      (the integer form of mfg_draw_start)
+ *   exploit: theta[k], w[k,:] and the validation block's best_value, best_check, since_best, best_theta, best_w[k,:] become the
+ *            donor's (the best iterate of the lineage); with a control block theta_prev[k] = theta[donor], so that the next
+ *            retire step compares the new theta with the donor's and not with the replaced learner's
+ *   explore: lr_critic[k] = min(max(lr_critic[donor] f, lr_critic_min), lr_critic_max) in fp64 with f = factor_up when
+ *            x1 >> 31 is 1, else factor_down; lr_actor[k] by the same rule with x2 >> 31 and the actor bounds; a rate whose
+ *            perturb bit is clear becomes the donor's unchanged
+ *   parent[k, s] = donor.  The learner keeps its own seed, shift and alpha_scale.
+ * Every other active learner gets parent[k, s] = k.  lr_log[k, s, :] holds every active learner's rates after the step.
+ * Donor and receiver ranks are disjoint, a receiver writes only its own rows and reads only a donor's: no race, no fence.
+ * A step is two launches on the call's stream (k_pop_evolve_rank, k_pop_evolve_apply), no atomics, no host read, no allocation.
+ * Without a block the calls issue exactly the launches they always did.
+ * Checked when the block is set: MFG_EINVAL for a null context or pointer, every / n_top / n_bottom < 1, n_top + n_bottom > K, K
+ * outside [1, MFG_POP_MAX_K], max_steps < 1, a factor that is not finite or <= 0, a bound pair with min > max or min <= 0 (or
+ * not finite), perturb outside [0, 3].  Checked again before a call launches anything: MFG_EINVAL when K differs from the call's
+ * K, when no validation block is bound, when lr_critic / lr_actor are not the call's pointers, or when max_steps <
+ * (episodes / period) / every.  mfg_train_episodes_pop_resident, mfg_train_episodes_irl_pop and mfg_train_rollouts_irl_pop
+ * refuse a bound block with MFG_EUNSUPPORTED: the resident kernel reads its rates once per launch, and IRL learners may carry
+ * different reward networks, which an exploit would have to copy too. */
+typedef struct mfg_pop_evolve {
+  double* lr_critic;
+  double* lr_actor;
+  int32_t* order;
+  int32_t* active;
+  int32_t* rank;
+  int32_t* parent;
+  double* lr_log;
+  uint64_t seed;
+  double factor_down, factor_up;
+  double lr_critic_min, lr_critic_max, lr_actor_min, lr_actor_max;
+  int32_t every, n_top, n_bottom, perturb;
+  int32_t max_steps, K;
+} mfg_pop_evolve_t;
+int mfg_ctx_set_pop_evolve(mfg_ctx_t* ctx, const mfg_pop_evolve_t* block);
+
 /* Finite populations: a member is ONE population of A agents (1 <= A <= MFG_AGENTS_MAX) instead of the mean-field limit
  * pi' = P^T pi that every other entry rolls.  Its state is counts [d] int32 (d <= 64) summing to A; each agent of topic i draws
  * its next topic from row P[i,:] of the member's action, so the histogram carries sampling noise of order 1 / sqrt(A) on top of
