@@ -95,10 +95,12 @@ struct CoreArgs {
 __host__ __device__ constexpr int core_step_red_blocks(int FO) { return (FO + WAVES - 1) / WAVES; }
 
 // The row reduction + update that closes an IRL episode of per-step updates (k_reduce_rows_apply and its population form): a
-// wave per column k of the [nrows][FO] rows, rows_column_sum -- G, w, theta (theta_in -> theta_out), the return.
+// wave per column k of the [nrows][FO] rows, rows_column_sum -- G, w, theta (theta_in -> theta_out), the return.  slots: NULL,
+// or the two theta slots of the control block (IrlStepWs), which the wave of column F leaves zero.
 __device__ __forceinline__ void reduce_rows_apply_body(const double* __restrict__ rows, int nrows, int64_t FO, double* __restrict__ G,
                                                        double lr_c, double lr_a, double count, double* __restrict__ w,
-                                                       const double* theta_in, double* theta_out, double* __restrict__ reward_acc) {
+                                                       const double* theta_in, double* theta_out, double* __restrict__ reward_acc,
+                                                       double* slots) {
   const int lane = threadIdx.x & (WAVE - 1), wv = threadIdx.x / WAVE;
   const int64_t k = (int64_t)blockIdx.x * WAVES + wv, F = FO - 3;
   if (k >= FO) return;
@@ -113,8 +115,12 @@ __device__ __forceinline__ void reduce_rows_apply_body(const double* __restrict_
     const double inv = 1.0 / count;
     G[k] = gk;
     if (k < F) w[k] = updated_param(old_val, lr_c, gk, inv);
-    else if (k == F) *theta_out = updated_param(old_val, lr_a, gk, inv);
-    else if (k == F + 1 && reward_acc) *reward_acc = old_val + gk * inv;
+    else if (k == F) {
+      *theta_out = updated_param(old_val, lr_a, gk, inv);
+      // the two theta slots of the workspace's control block (theta_in may be one of them: this lane, the only one that
+      // reads it, has read it above): zero again, as every call leaves the control block
+      if (slots) slots[0] = slots[1] = 0.0;
+    } else if (k == F + 1 && reward_acc) *reward_acc = old_val + gk * inv;
   }
 }
 

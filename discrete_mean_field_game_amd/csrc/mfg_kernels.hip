@@ -1987,7 +1987,7 @@ static int train_episode_irl_step(const float* mat_pi0, int64_t num_start, float
     nxt = t;
   }
   if (pop) pop->s_theta_b = s_th_in;
-  launch_reduce_rows_apply(ws.rows, nrows, FO, G, lr_critic, lr_actor, (double)B, w, th_in, theta, reward_acc, st, pop);
+  launch_reduce_rows_apply(ws.rows, nrows, FO, G, lr_critic, lr_actor, (double)B, w, th_in, theta, reward_acc, ws.theta_slot, st, pop);
   if (cur != pi_io && hipMemcpyAsync(pi_io, cur, (size_t)B * d * sizeof(float) * (pop ? pop->K : 1), hipMemcpyDeviceToDevice,
                                      st) != hipSuccess)
     return fail(MFG_ELAUNCH, "%s", "train_episode_irl: final state copy failed");

@@ -311,8 +311,8 @@ __global__ void k_value(const float* __restrict__ pi, const double* __restrict__
 __global__ __launch_bounds__(BLOCK) void k_reduce_rows_apply(const double* __restrict__ rows, int nrows, int64_t FO, double* __restrict__ G,
                                                             double lr_c, double lr_a, double count, double* __restrict__ w,
                                                             const double* theta_in, double* theta_out,
-                                                            double* __restrict__ reward_acc) {
-  reduce_rows_apply_body(rows, nrows, FO, G, lr_c, lr_a, count, w, theta_in, theta_out, reward_acc);
+                                                            double* __restrict__ reward_acc, double* slots) {
+  reduce_rows_apply_body(rows, nrows, FO, G, lr_c, lr_a, count, w, theta_in, theta_out, reward_acc, slots);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -341,11 +341,11 @@ void launch_draw_start(const float* mat, int64_t num_start, int64_t B, int d, ui
 }
 
 void launch_reduce_rows_apply(const double* rows, int nrows, int64_t FO, double* G, double lr_c, double lr_a, double count,
-                              double* w, const double* theta_in, double* theta_out, double* reward_acc, hipStream_t st,
-                              const PopArgs* pop) {
-  if (pop) launch_reduce_rows_apply_pop(rows, nrows, FO, G, count, w, theta_in, theta_out, reward_acc, *pop, st);
+                              double* w, const double* theta_in, double* theta_out, double* reward_acc, double* slots,
+                              hipStream_t st, const PopArgs* pop) {
+  if (pop) launch_reduce_rows_apply_pop(rows, nrows, FO, G, count, w, theta_in, theta_out, reward_acc, slots, *pop, st);
   else hipLaunchKernelGGL(k_reduce_rows_apply, dim3((unsigned)((FO + WAVES - 1) / WAVES)), dim3(BLOCK), 0, st, rows, nrows, FO,
-                          G, lr_c, lr_a, count, w, theta_in, theta_out, reward_acc);
+                          G, lr_c, lr_a, count, w, theta_in, theta_out, reward_acc, slots);
 }
 
 }  // namespace mfg

@@ -116,7 +116,8 @@ void launch_reduce_partials_pop(unsigned nob, const double* partial, int64_t nsb
                                 const PopArgs& p, hipStream_t st);
 // the row reduction + update that closes a step-mode IRL episode: learner k's theta in at theta_in + k p.s_theta_b bytes
 void launch_reduce_rows_apply_pop(const double* rows, int nrows, int64_t FO, double* G, double count, double* w,
-                                  const double* theta_in, double* theta_out, double* reward_acc, const PopArgs& p, hipStream_t st);
+                                  const double* theta_in, double* theta_out, double* reward_acc, double* slots, const PopArgs& p,
+                                  hipStream_t st);
 
 // The resident form of the step-mode episodes (mfg_pop_resident.hip, mfg_train_episodes_pop_resident): what one launch of
 // k_pop_resident needs beyond CoreArgs (shape, gamma, reward_kind, traj_offset, htab, status, reward / delta / g and the rows

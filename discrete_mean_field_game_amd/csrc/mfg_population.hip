@@ -155,27 +155,30 @@ void launch_reduce_partials_pop(unsigned nob, const double* partial, int64_t nsb
 __global__ __launch_bounds__(BLOCK) void k_reduce_rows_apply_pop(const double* __restrict__ rows, int nrows, int64_t FO,
                                                                  double* __restrict__ G, double count, double* __restrict__ w,
                                                                  const double* theta_in, double* theta_out,
-                                                                 double* __restrict__ reward_acc, PopArgs p) {
+                                                                 double* __restrict__ reward_acc, double* slots, PopArgs p) {
   const int k = blockIdx.y;
   reduce_rows_apply_body(pop_bytes(rows, p.s_ws, k), nrows, FO, G + FO * k, p.lr_c[k] * p.sc, p.lr_a[k] * p.sa, count,
-                         w + p.F * k, pop_bytes(theta_in, p.s_theta_b, k), theta_out + k, pop_at(reward_acc, p.s_acc, k));
+                         w + p.F * k, pop_bytes(theta_in, p.s_theta_b, k), theta_out + k, pop_at(reward_acc, p.s_acc, k),
+                         pop_bytes(slots, p.s_ws, k));
 }
 __global__ __launch_bounds__(BLOCK) void k_reduce_rows_apply_pop_ctl(const double* __restrict__ rows, int nrows, int64_t FO,
                                                                      double* __restrict__ G, double count,
                                                                      double* __restrict__ w, const double* theta_in,
                                                                      double* theta_out, double* __restrict__ reward_acc,
-                                                                     PopArgs p) {
+                                                                     double* slots, PopArgs p) {
   const int k = blockIdx.y;
   if (pop_retired(p, k)) return;
   reduce_rows_apply_body(pop_bytes(rows, p.s_ws, k), nrows, FO, G + FO * k, p.lr_c[k] * p.sc, p.lr_a[k] * p.sa, count,
-                         w + p.F * k, pop_bytes(theta_in, p.s_theta_b, k), theta_out + k, pop_at(reward_acc, p.s_acc, k));
+                         w + p.F * k, pop_bytes(theta_in, p.s_theta_b, k), theta_out + k, pop_at(reward_acc, p.s_acc, k),
+                         pop_bytes(slots, p.s_ws, k));
 }
 
 void launch_reduce_rows_apply_pop(const double* rows, int nrows, int64_t FO, double* G, double count, double* w,
-                                  const double* theta_in, double* theta_out, double* reward_acc, const PopArgs& p, hipStream_t st) {
+                                  const double* theta_in, double* theta_out, double* reward_acc, double* slots, const PopArgs& p,
+                                  hipStream_t st) {
   hipLaunchKernelGGL(p.state ? k_reduce_rows_apply_pop_ctl : k_reduce_rows_apply_pop,
                      dim3((unsigned)((FO + WAVES - 1) / WAVES), (unsigned)p.K), dim3(BLOCK), 0, st, rows, nrows, FO, G, count, w,
-                     theta_in, theta_out, reward_acc, p);
+                     theta_in, theta_out, reward_acc, slots, p);
 }
 
 // ---- the learners' activity states between two episodes (mfg_population.h): one wave, learner blockIdx.x ----

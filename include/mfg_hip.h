@@ -176,7 +176,10 @@ int64_t mfg_num_features(int d);
 /* Bytes of scratch the gradient reductions need for N transitions of dimension d.  The first 64 bytes are a control
  * block (completion counter of the in-kernel finalisation): zero the workspace ONCE after allocating it
  * (hipMemset); every call leaves the control block zero again, so one workspace sized for the largest N serves
- * calls with any smaller N.  A workspace must not be shared by calls that can
+ * calls with any smaller N.  Everything behind the control block is scratch: no call reads a word there that it has not
+ * written itself, so what an earlier call left behind never shows in a result.  The population forms take K such workspaces
+ * back to back (slices of workspace_bytes each): every slice has a control block of its own, [k workspace_bytes,
+ * k workspace_bytes + 64), zero before the call and left zero.  A workspace must not be shared by calls that can
  * run concurrently on different streams. */
 size_t mfg_workspace_bytes(int64_t N, int d);
 
@@ -240,7 +243,8 @@ int mfg_score(const float* pi_alpha, const float* P, int64_t B, int d, const dou
 
 /* a5-a8 on given transitions: delta[b] = r + gamma_or_discount V(pi') - V(pi), g[b] as mfg_score,
  * and the batch sums G = [ sum_b delta_b phi(pi_b) (F) | sum_b delta_b g_b | sum_b r_b | B ] (fp64,
- * F+3 entries; accumulate != 0 adds onto the existing contents of G).  (mfg_ac2.py:501-522) */
+ * F+3 entries; accumulate != 0 adds onto the existing contents of G).  (mfg_ac2.py:501-522)
+ * workspace: mfg_workspace_bytes(B, d) bytes; its control block is zero on entry and on return, the rest is scratch. */
 int mfg_td_pg_accumulate(const float* pi, const float* pi_next, const float* P, const float* reward,
                          const double* w, const double* theta, double shift, double gamma_or_discount,
                          int64_t B, int d, int precision, double* delta, double* g, double* G, int accumulate,
@@ -260,7 +264,8 @@ int mfg_apply_update(const double* G, int d, double lr_critic, double lr_actor, 
  *   transitions when MFG_ROLLOUT_TD.  first_step offsets the RNG step counter.
  *   reward_kind = MFG_REWARD_EXTERNAL (the IRL step: the reward network needs the sampled action first,
  *   ac_irl.py:679-691): `reward` is not touched, delta = gamma V(pi') - V(pi) WITHOUT the reward, G must be NULL;
- *   finish with mfg_grad_accumulate(add_reward = 1) once the rewards exist. */
+ *   finish with mfg_grad_accumulate(add_reward = 1) once the rewards exist.
+ *   workspace as for mfg_td_pg_accumulate(B*T) when G is given; may be NULL otherwise. */
 int mfg_rollout(const float* pi0, int64_t B, int d, int T, const double* theta, double shift,
                 double alpha_scale, const double* w, double gamma, int reward_kind, uint64_t seed,
                 uint32_t first_step, uint64_t traj_offset, int flags, float* pi_traj, float* pi_last,
@@ -275,7 +280,8 @@ int mfg_rollout(const float* pi0, int64_t B, int d, int T, const double* theta, 
  * launches.  Without MFG_TRAIN_APPLY G is complete on return: multi-GPU jobs all-reduce it and call mfg_apply_update.
  * Outputs as for mfg_rollout (pi_traj, reward, delta, g are required; pi_last may be NULL).
  * idx == NULL: the start rows are DRAWN inside the rollout kernel (mfg_draw_start with step = first_step) -- batched runs
- * need no host RNG, no index upload and, with several ranks, no broadcast in front of an episode. */
+ * need no host RNG, no index upload and, with several ranks, no broadcast in front of an episode.
+ * workspace as for mfg_td_pg_accumulate(B*T). */
 #define MFG_TRAIN_APPLY 16
 int mfg_train_rollout(const float* mat_pi0, int64_t num_start, const int32_t* idx, int64_t B, int d, int T, double* theta,
                       double shift, double alpha_scale, double* w, double gamma, int reward_kind, uint64_t seed,
@@ -290,7 +296,7 @@ int mfg_train_rollout(const float* mat_pi0, int64_t num_start, const int32_t* id
  * (mfg_ac2.py:511-522; pass the 1-indexed episode number for ac_irl.py:697-708), mean reward of the update added to
  * reward_acc[k] (may be NULL).  flags as for mfg_train_rollout (MFG_TRAIN_APPLY implied).  Single GPU: between two
  * episodes of a multi-GPU job sits an all-reduce, which stays with the caller (mfg_train_rollout per episode).
- * The output buffers hold the LAST episode's values on return. */
+ * The output buffers hold the LAST episode's values on return.  workspace as for mfg_td_pg_accumulate(B*T). */
 int mfg_train_rollouts(const float* mat_pi0, int64_t num_start, int64_t B, int d, int T, int64_t episodes, int64_t first_episode,
                        int constant, double* theta, double shift, double alpha_scale, double* w, double gamma, int reward_kind,
                        uint64_t seed, uint32_t first_step, uint64_t traj_offset, int flags, double lr_critic, double lr_actor,
@@ -307,7 +313,7 @@ int mfg_train_rollouts(const float* mat_pi0, int64_t num_start, int64_t B, int d
  * outputs must be OTHER buffers than theta / w (blocks that start later still read the old values): callers ping-pong
  * two parameter sets.  Then as mfg_train_rollout without MFG_TRAIN_APPLY: G holds this rank's sums of the new update on
  * return (G may alias G_pending: it is written by a later launch).  A rank's cycle is rollout -> sums -> all-reduce, and
- * mfg_apply_update only once, after the last episode. */
+ * mfg_apply_update only once, after the last episode.  workspace as for mfg_td_pg_accumulate(B*T). */
 int mfg_train_rollout_deferred(const float* mat_pi0, int64_t num_start, const int32_t* idx, int64_t B, int d, int T,
                                const double* theta, const double* w, const double* G_pending, double lr_critic_pending,
                                double lr_actor_pending, double* reward_acc_pending, double* theta_out, double* w_out, double shift,
@@ -402,7 +408,7 @@ int mfg_reward_net_adam(float* params, float* adam_m, float* adam_v, const float
  * (fp64 until the maximum is gone: |ln z| ~ 1e4 with a spread of tens, so an fp32 ln z is off by 5e-4 before it reaches expf).
  * Everything else -- arguments, checks, per-sample coefficients, the fp64 batch sum, regulariser, Adam, MFG_RN_TRAIN_GRAD_ONLY
  * -- is mfg_reward_net_train_step's, which is this call with gen_log_z = NULL (then, or with n_gen = 0, the same launches
- * and the same bits).  A +inf entry (a generated P with an exact zero under p_floor = 0) poisons the update with NaN as it would
+ * and the same bits); workspace as for mfg_reward_net_train_step.  A +inf entry (a generated P with an exact zero under p_floor = 0) poisons the update with NaN as it would
  * in the reference; nothing hides it. */
 int mfg_reward_net_train_step_z(float* params, float* adam_m, float* adam_v, int d, int k1, int f2, int k2, int n3, int n4,
                                 const float* demo_state, const float* demo_action, const int32_t* demo_rows_host, int n_demo,
@@ -433,7 +439,7 @@ int mfg_grad_accumulate(const float* pi, int64_t stride_b, double* delta, const 
 
 /* mfg_grad_accumulate (accumulate = 0) followed by mfg_apply_update, with the update applied inside the kernel that
  * finishes the sums (single GPU; mfg_ac2.py:511-522 / ac_irl.py:697-708 for the batch): the IRL step
- * rollout(EXTERNAL) -> reward net -> this call is three launches. */
+ * rollout(EXTERNAL) -> reward net -> this call is three launches.  Workspace as for mfg_grad_accumulate. */
 int mfg_grad_apply(const float* pi, int64_t stride_b, double* delta, const double* g, const float* reward, int64_t B, int T,
                    int d, int add_reward, double* G, double lr_critic, double lr_actor, double* w, double* theta,
                    double* reward_acc, void* workspace, size_t workspace_bytes, mfg_stream_t stream);
@@ -454,7 +460,8 @@ int mfg_train_episode(float* pi_io, float* pi_scratch, int64_t B, int d, int T, 
 
 /* a9, the episode loop with the reference's per-step updates (mfg_ac2.py:460-526): `episodes` x [start states drawn on the
  * device into pi_io (mfg_draw_start, step = first_step + k T) | mfg_train_episode], learning rates per episode as in
- * mfg_train_rollouts, reward_acc[k] += mean reward of every step's update of episode k (may be NULL).  Single GPU. */
+ * mfg_train_rollouts, reward_acc[k] += mean reward of every step's update of episode k (may be NULL).  Single GPU.
+ * pi_scratch and workspace as for mfg_train_episode. */
 int mfg_train_episodes(const float* mat_pi0, int64_t num_start, float* pi_io, float* pi_scratch, int64_t B, int d, int T,
                        int64_t episodes, int64_t first_episode, int constant, double* theta, double shift, double alpha_scale,
                        double* w, double gamma, int reward_kind, uint64_t seed, uint32_t first_step, uint64_t traj_offset,
@@ -471,7 +478,9 @@ int mfg_train_episodes(const float* mat_pi0, int64_t num_start, float* pi_io, fl
  *   Learner-major arrays: theta [K], w [K,F], G [K,F+3], reward_acc [K,episodes] (may be NULL); step mode pi_io /
  *   pi_scratch [K,Bk,d], reward / delta / g [K,Bk]; rollout mode pi_traj [K,Bk,T+1,d], pi_last [K,Bk,d] (may be NULL),
  *   reward / delta / g [K,Bk,T].  mat_pi0 [num_start,d] is shared.
- *   workspace_bytes: ONE learner's slice, a multiple of 256 (the buffer holds K slices back to back).
+ *   workspace_bytes: ONE learner's slice, a multiple of 256 (the buffer holds K slices back to back).  Every slice is a
+ *   workspace of mfg_workspace_bytes: its control block, bytes [k workspace_bytes, k workspace_bytes + 64) of the buffer, is
+ *   zero on entry and on return (a retired learner's too), the rest of the slice is scratch.
  * Checked before anything is launched: 1 <= K <= MFG_POP_MAX_K, no null pointer, d <= 64 (MFG_EUNSUPPORTED beyond: one wave
  * per trajectory fills the machine there), an in-kernel reward_kind, the Philox step counter does not wrap (MFG_EINVAL);
  * the slice holds the update's partial rows (MFG_EWORKSPACE).  Rollout mode, d <= 28: the population form of the batch sums
@@ -482,7 +491,8 @@ int mfg_train_episodes(const float* mat_pi0, int64_t num_start, float* pi_io, fl
  * unless the bound context carries a population control block (mfg_ctx_set_pop_control), which books the condition to that
  * learner alone, retires it at the next episode boundary and lets the others run on. */
 #define MFG_POP_MAX_K 65535
-/* step mode (update_every = 'step', mfg_ac2.py:478-526): mfg_train_episodes for K learners */
+/* step mode (update_every = 'step', mfg_ac2.py:478-526): mfg_train_episodes for K learners; workspace: K slices, each with
+ * its control block zero (above); pi_scratch is scratch */
 int mfg_train_episodes_pop(const float* mat_pi0, int64_t num_start, float* pi_io, float* pi_scratch, int64_t B, int K, int d, int T,
                            int64_t episodes, int64_t first_episode, int constant, double* theta, const double* shift,
                            const double* alpha_scale, double* w, double gamma, int reward_kind, const uint64_t* seed,
@@ -514,7 +524,7 @@ int mfg_train_episodes_pop_resident(const float* mat_pi0, int64_t num_start, flo
                                     const double* lr_critic, const double* lr_actor, float* reward, double* delta, double* g,
                                     double* G, double* reward_acc, void* workspace, size_t workspace_bytes, mfg_stream_t stream);
 /* rollout mode (one update per episode, mfg_ac2.py:460-526): mfg_train_rollouts for K learners (flags: MFG_ROLLOUT_F64 /
- * MFG_ROLLOUT_DISCOUNT_POW) */
+ * MFG_ROLLOUT_DISCOUNT_POW); workspace: K slices, each with its control block zero (above) */
 int mfg_train_rollouts_pop(const float* mat_pi0, int64_t num_start, int64_t B, int K, int d, int T, int64_t episodes,
                            int64_t first_episode, int constant, double* theta, const double* shift, const double* alpha_scale,
                            double* w, double gamma, int reward_kind, const uint64_t* seed, uint32_t first_step,
@@ -861,7 +871,8 @@ int mfg_action_mean_pop(const float* action, int64_t s_action, int K, int64_t N,
  *   on group k's inputs only.
  *   steps [K,M,T,2] fp64 (l1, jsd per hour) or NULL (then they stay in the workspace); V [K,M,T+1,d] fp64 or NULL (then V is
  *   not written to memory at all).
- *   workspace: mfg_consistency_given_workspace_bytes(K, M, T, steps != NULL) bytes (0 with steps: NULL is then allowed).
+ *   workspace: mfg_consistency_given_workspace_bytes(K, M, T, steps != NULL) bytes (0 with steps: NULL is then allowed);
+ *   contents are scratch.
  * mfg_consistency_pop, THREE launches, no host synchronisation: the actions are those of K policies' rollouts.
  *   start32 [N,d], theta / shift / alpha_scale [K] fp64, seed [K] uint64, first_step, repeats R, precision: as for
  *   mfg_forecast_pop -- learner k's member j (0 <= j < N R) starts at start32[j mod N] and is keyed by Philox (seed[k],
@@ -904,7 +915,8 @@ typedef struct mfg_reward_net {
  * sample counter rn_sample_offset + b -- the keys the host class would have passed to T separate
  * mfg_reward_net_forward calls numbered rn_call0 + 1 ... .  pi_io [B,d]: start states in, final states out; pi_scratch
  * [B,d]; P [B,d,d], reward / delta / g [B] hold the last step's values on return; G [F+3]; workspace as for
- * mfg_td_pg_accumulate(B).  Philox steps first_step .. first_step+T-1 for the actions. */
+ * mfg_td_pg_accumulate(B) (the two-launch flow keeps theta between two env steps in the control block; the row reduction that
+ * closes the episode leaves it zero again).  Philox steps first_step .. first_step+T-1 for the actions. */
 int mfg_train_episode_irl(float* pi_io, float* pi_scratch, int64_t B, int d, int T, double* theta, double shift,
                           double alpha_scale, double* w, double gamma, uint64_t seed, uint32_t first_step,
                           uint64_t traj_offset, int precision, double lr_critic, double lr_actor,
@@ -914,7 +926,8 @@ int mfg_train_episode_irl(float* pi_io, float* pi_scratch, int64_t B, int d, int
 
 /* The same episode with the start states DRAWN from the table mat_pi0 [num_start,d] (the draw of mfg_draw_start at
  * step = first_step, trajectory ids traj_offset + b; ac_irl.py:655) -- inside the first step kernel where the two-launch flow
- * serves, by a launch of its own otherwise.  pi_out [B,d]: final states (output only); the rest as above. */
+ * serves, by a launch of its own otherwise.  pi_out [B,d]: final states (output only); the rest as above: pi_scratch and
+ * workspace as for mfg_train_episode_irl. */
 int mfg_train_episode_irl_draw(const float* mat_pi0, int64_t num_start, float* pi_out, float* pi_scratch, int64_t B, int d, int T,
                                double* theta, double shift, double alpha_scale, double* w, double gamma, uint64_t seed,
                                uint32_t first_step, uint64_t traj_offset, int precision, double lr_critic, double lr_actor,
@@ -993,7 +1006,8 @@ typedef struct mfg_rn_geom { int32_t n3, n4; float keep_prob; int32_t l1l2; } mf
  * (d = 21 / 15, k1 = 5, f2 = 2, k2 = 3, n_fc3 <= 16, n_fc4 <= 32, every learner's fc3_w 8-byte aligned); MFG_EWORKSPACE when
  * one learner's slice (workspace_bytes, a multiple of 256) cannot hold the control block and the partial rows of the update:
  * 64 + min(ceil(Bk / 16), 256) (F + 4) 8 bytes in step mode, those of the gradient kernels over Bk T samples in rollout mode. */
-/* step mode (AC_IRL.train, ac_irl.py:634-732; with a table: for the K points of gridsearch.py:8-31) */
+/* step mode (AC_IRL.train, ac_irl.py:634-732; with a table: for the K points of gridsearch.py:8-31); workspace: K slices, each
+ * with its control block zero on entry and on return, the rest scratch, as for mfg_train_episodes_pop; pi_scratch is scratch */
 int mfg_train_episodes_irl_pop(const float* mat_pi0, int64_t num_start, float* pi_out, float* pi_scratch, int64_t B, int K, int d,
                                int T, int64_t episodes, int64_t first_episode, int constant, double* theta, const double* shift,
                                const double* alpha_scale, double* w, double gamma, const uint64_t* seed, uint32_t first_step,
@@ -1002,7 +1016,8 @@ int mfg_train_episodes_irl_pop(const float* mat_pi0, int64_t num_start, float* p
                                const mfg_rn_geom_t* geom_host, const mfg_rn_geom_t* geom_dev, const uint64_t* rn_seed,
                                const uint64_t* rn_call0, float* P, float* reward, double* delta, double* g, double* G,
                                double* reward_acc, void* workspace, size_t workspace_bytes, mfg_stream_t stream);
-/* rollout mode (one update per episode); flags: MFG_ROLLOUT_DISCOUNT_POW | MFG_ROLLOUT_F64 */
+/* rollout mode (one update per episode); flags: MFG_ROLLOUT_DISCOUNT_POW | MFG_ROLLOUT_F64; workspace: K slices, each with its
+ * control block zero on entry and on return, the rest scratch, as for mfg_train_rollouts_pop */
 int mfg_train_rollouts_irl_pop(const float* mat_pi0, int64_t num_start, int64_t B, int K, int d, int T, int64_t episodes,
                                int64_t first_episode, int constant, double* theta, const double* shift, const double* alpha_scale,
                                double* w, double gamma, const uint64_t* seed, uint32_t first_step, uint64_t traj_offset, int flags,
@@ -1052,7 +1067,7 @@ typedef struct mfg_rn_train_plan {
  * the arguments n3, n4, keep_prob and l1l2 are not read.
  * plan_host [n_updates n_active] (its lr_t fields written first) is uploaded ONCE into plan_dev (device, >= n_updates n_active
  * sizeof(mfg_rn_train_plan_t) bytes) and the stream is drained once before the first launch.  workspace: n_active slices, each
- * mfg_reward_net_train_workspace_bytes(geometry, N) rounded up to 256 bytes.
+ * mfg_reward_net_train_workspace_bytes(geometry, N) rounded up to 256 bytes; contents are scratch (plan_dev likewise).
  * Checked before anything is launched: MFG_EINVAL for null pointers, bad counts, param_stride < NP, a learner id out of
  * range or twice in one update, a store row negative or >= its capacity, adam_step < 1; MFG_EUNSUPPORTED outside
  * d = 15 / 21, k1 = 5, f2 = 2, k2 = 3, n_fc3 <= 16, n_fc4 <= 32, or for a batch beyond the single step's limits (n_demo, n_gen
@@ -1069,7 +1084,8 @@ int mfg_reward_net_train_steps_pop(float* params, float* adam_m, float* adam_v, 
 /* mfg_reward_net_train_steps_pop with importance weights (ac_irl.py:404-406, see mfg_reward_net_train_step_z): gen_log_z is a
  * device fp64 array [K, gen_capacity], learner k's ln z at gen_log_z + k gen_capacity, indexed by the plan entries' gen_rows
  * (already checked against gen_capacity).  Update u, slot s is exactly mfg_reward_net_train_step_z for that learner -- the same
- * bits, with or without a geometry table.  gen_log_z = NULL: mfg_reward_net_train_steps_pop. */
+ * bits, with or without a geometry table.  gen_log_z = NULL: mfg_reward_net_train_steps_pop; workspace as for
+ * mfg_reward_net_train_steps_pop. */
 int mfg_reward_net_train_steps_pop_z(float* params, float* adam_m, float* adam_v, int64_t param_stride, int K, int d, int k1, int f2,
                                      int k2, int n3, int n4, const mfg_rn_geom_t* geom_host, const mfg_rn_geom_t* geom_dev,
                                      const float* demo_state, const float* demo_action, int64_t demo_capacity,

@@ -17,6 +17,18 @@ so a launch that runs ahead of its producer computes a well-defined wrong answer
   independent_side_stream()  the side stream both run on: one on which a null-stream kernel was measured to complete while a
                   sleep is pending (streams share a few hardware queues; a shared queue would hide a launch on stream 0).
 No row hands a call a buffer smaller than it needs, and no decoy is garbage: nothing here can fault.
+
+The table also knows each workspace's CONTRACT, in the words of include/mfg_hip.h (tests/test_stale_workspace_host.py holds the
+two against each other): Row.work lists, per work buffer in the order of the builder's ws() calls, (entry point, parameter, kind)
+  CTL      a workspace from mfg_workspace_bytes: bytes [0, 64), the control block, are zero before and after every call
+  SLICES   K such slices back to back (the population forms): [k slice, k slice + 64) of every slice
+  SCRATCH  "contents are scratch": nothing is promised, nothing may be assumed
+and ws(..., zero=) hands the byte ranges over.  Bufs(dev, salt) zeroes the whole buffer as before.  Bufs(dev, salt, fill=byte)
+is the POISONED mode of tests/test_gpu_stale_workspace.py: every work buffer is a guard_bands.Guarded of exactly nbytes whose
+bytes outside the declared ranges are `byte`.  Bufs(dev, salt, donor=earlier_bufs) is the DONOR mode: ws() returns the leading
+nbytes of the buffer the earlier Bufs used for the same ws() call, contents untouched.  A declared range that was not a
+declared range of the call before (a slice boundary that lay in a neighbour's rows) is the caller's to zero: the procedures do
+that, and only that, with Bufs.zero_new_ranges before they issue the call.
 """
 import contextlib
 import ctypes as C
@@ -24,6 +36,8 @@ import time
 
 import numpy as np
 import torch
+
+import guard_bands
 
 NAN = float('nan')
 THETA, SHIFT, SCALE, GAMMA = 8.86349, 0.16, 12000.0, 0.9
@@ -79,11 +93,35 @@ def p(t):
     return None if t is None else t.data_ptr()
 
 
-class Bufs:
-    """The buffers of one call.  salt = 0: the true data; 1: the decoy."""
+# ---- the workspace contracts of include/mfg_hip.h (Row.work kinds and the `zero` ranges of Bufs.ws)
+CONTROL_BYTES = 64                        # MFG_WS_CONTROL_BYTES
+CTL, SLICES, SCRATCH_KIND = 'control', 'slices', 'scratch'
+CONTROL = ((0, CONTROL_BYTES),)
+SCRATCH = ()
 
-    def __init__(self, dev, salt):
-        self.dev, self.salt = dev, salt
+
+def slices(K, slice_bytes):
+    """The control blocks of K slices back to back."""
+    return tuple((k * slice_bytes, k * slice_bytes + CONTROL_BYTES) for k in range(K))
+
+
+def kind_of(zero, nbytes):
+    if not zero:
+        return SCRATCH_KIND
+    if tuple(zero) == CONTROL:
+        return CTL
+    assert nbytes % len(zero) == 0 and tuple(zero) == slices(len(zero), nbytes // len(zero)), zero
+    return SLICES
+
+
+class Bufs:
+    """The buffers of one call.  salt = 0: the true data; 1: the decoy.  fill / donor: see the module's docstring."""
+
+    def __init__(self, dev, salt, fill=None, donor=None):
+        assert fill is None or donor is None
+        self.dev, self.salt, self.fill, self.donor = dev, salt, fill, donor
+        self.guarded = []     # poisoned / donor mode: the Guarded behind work[i]
+        self.zero = []        # the declared zero ranges of work[i]: ((first byte, end byte), ...)
         self.inputs = {}      # inputs and in/out buffers (what a producer has to write before the call)
         self.written = []     # names of the in/out buffers: compared after the call
         self.outs = {}        # name -> (tensor, fill)
@@ -110,13 +148,53 @@ class Bufs:
         self.outs[name] = (t, fill)
         return t
 
-    def ws(self, nbytes, dtype=U8, shape=None):
-        """A zeroed workspace of exactly the advertised bytes; its contents are scratch and not compared."""
+    def ws(self, nbytes, dtype=U8, shape=None, zero=SCRATCH):
+        """A workspace of exactly the advertised bytes; its contents are not compared.  zero: the byte ranges the header
+        requires to be zero (CTL, slices(K, slice_bytes), SCRATCH).  Plain mode: all of it zeroed.  Poisoned mode: a Guarded,
+        `fill` everywhere outside `zero`.  Donor mode: the head of the donor's buffer, untouched."""
         item = torch.empty(0, dtype=dtype).element_size()
         assert nbytes % item == 0
-        t = torch.zeros(nbytes // item, dtype=dtype, device=self.dev)
+        assert all(0 <= lo < hi <= nbytes for lo, hi in zero), (zero, nbytes)
+        if self.fill is None and self.donor is None:
+            t = torch.zeros(nbytes // item, dtype=dtype, device=self.dev)
+        else:
+            if self.donor is not None:
+                i = len(self.work)
+                g = self.donor.guarded[i]
+                assert g.nbytes >= nbytes, 'the donor\'s buffer %d holds %d bytes, the call needs %d' % (i, g.nbytes, nbytes)
+                raw = g.raw[g.start:g.start + nbytes]
+            else:
+                g = guard_bands.Guarded(nbytes, U8, self.dev, fill=self.fill)
+                raw = g.t
+                for lo, hi in zero:
+                    raw[lo:hi] = 0
+            self.guarded.append(g)
+            t = raw.view(dtype)
         self.work.append(t)
+        self.zero.append(tuple(zero))
         return t if shape is None else t.view(shape)
+
+    def zero_new_ranges(self, before):
+        """The caller's side of reusing a buffer: zero every declared range of work[i] that was not a declared range
+        (before[i]) of the call that used the buffer last -- a slice's control block that lay in a neighbour's old rows.
+        Nothing else of a reused buffer is ever touched."""
+        for t, zero, old in zip(self.work, self.zero, before):
+            raw = t.view(-1).view(U8)
+            for lo, hi in zero:
+                if (lo, hi) not in old:
+                    raw[lo:hi] = 0
+
+    def stale_ranges(self):
+        """Names of the declared zero ranges that are not all zero (after a call: assertion (b) of the stale-workspace tests)."""
+        bad = []
+        for i, (t, zero) in enumerate(zip(self.work, self.zero)):
+            raw = t.view(-1).view(U8)
+            bad += ['work[%d] bytes [%d, %d)' % (i, lo, hi) for lo, hi in zero if bool(raw[lo:hi].any())]
+        return bad
+
+    def check_bands(self):
+        for i, g in enumerate(self.guarded):
+            g.check('work[%d]' % i)
 
     # ---- valid data by seed
     def simplex(self, shape, seed):
@@ -178,8 +256,10 @@ class Bufs:
 
 
 class Row:
-    def __init__(self, name, entries, build):
+    def __init__(self, name, entries, build, work=()):
         self.name, self.entries, self.build = name, tuple(entries), build
+        self.work = tuple(work)          # (entry point, parameter, kind) per work buffer, in the order of the builder's ws() calls
+        assert all(e in self.entries and k in (CTL, SLICES, SCRATCH_KIND) for e, _, k in self.work), name
         self.drains = any(e in DRAINS for e in self.entries)
 
     def __repr__(self):
@@ -187,13 +267,31 @@ class Row:
 
 
 ROWS = []
+_SINK = [ROWS]
 
 
-def row(name, *entries):
+def row(name, *entries, work=()):
     def deco(build):
-        ROWS.append(Row(name, entries, build))
+        _SINK[0].append(Row(name, entries, build, work))
         return build
     return deco
+
+
+@contextlib.contextmanager
+def extra_rows():
+    """Rows made by the factories below inside this block go to the list it yields, not into ROWS: other shapes of a family."""
+    out = []
+    _SINK[0] = out
+    try:
+        yield out
+    finally:
+        _SINK[0] = ROWS
+
+
+def _w(entry, *kinds):
+    """Row.work of an entry point whose work buffers are all called `workspace` but for a leading pi_scratch (SCRATCH_KIND first)."""
+    return tuple((entry, 'pi_scratch' if k == SCRATCH_KIND and len(kinds) > 1 and i == 0 else 'workspace', k)
+                 for i, k in enumerate(kinds))
 
 
 def wsb(N, d):
@@ -236,14 +334,14 @@ def _rollout_outs(a, B, d, T, lead=()):
 
 
 def _rollout_td(d, B, T):
-    @row('rollout-td-G-d%d-B%d-T%d' % (d, B, T), 'mfg_rollout')
+    @row('rollout-td-G-d%d-B%d-T%d' % (d, B, T), 'mfg_rollout', work=_w('mfg_rollout', CTL))
     def build(a):
         L = _L()
         F = _ops().num_features(d)
         pi0, th, w = a.inp('pi0', a.simplex((B, d), 4)), a.theta(), a.w(d)
         traj, last, r, delta, g = _rollout_outs(a, B, d, T)
         G, n = a.out('G', (F + 3,), F64), wsb(B * T, d)
-        ws = a.ws(n)
+        ws = a.ws(n, zero=CONTROL)
         return lambda: call('mfg_rollout', p(pi0), B, d, T, p(th), SHIFT, SCALE, p(w), GAMMA, L.REWARD_MFG_AC2, 99, 5, 1000,
                             L.ROLLOUT_TD, p(traj), p(last), p(r), p(delta), p(g), None, p(G), 0, p(ws), n)
 
@@ -253,7 +351,7 @@ _rollout_td(128, 6, 2)      # k_core_large, k_value_mfma2, k_td_delta, k_grad_mf
 _rollout_td(100, 5, 2)      # the generic forms
 
 
-@row('rollout-external+grad_accumulate-d21', 'mfg_rollout', 'mfg_grad_accumulate')
+@row('rollout-external+grad_accumulate-d21', 'mfg_rollout', 'mfg_grad_accumulate', work=_w('mfg_grad_accumulate', CTL))
 def _rollout_external(a):
     """The IRL step by hand: rollout without a reward, then the batch sums with the reward added to delta."""
     L = _L()
@@ -264,7 +362,7 @@ def _rollout_external(a):
     traj, last = a.out('pi_traj', (B, T + 1, d)), a.out('pi_last', (B, d))
     delta, g, G = a.out('delta', (B, T), F64), a.out('g', (B, T), F64), a.out('G', (F + 3,), F64)
     n = wsb(B * T, d)
-    ws = a.ws(n)
+    ws = a.ws(n, zero=CONTROL)
 
     def issue():
         call('mfg_rollout', p(pi0), B, d, T, p(th), SHIFT, SCALE, p(w), GAMMA, L.REWARD_EXTERNAL, 99, 5, 1000, L.ROLLOUT_TD,
@@ -280,47 +378,51 @@ def _sum_N(d):
     return 65 if d == 21 else 37          # d = 21: one chunk of 64 samples + 1
 
 
-def _td_pg_accumulate(d, accumulate):
-    @row('td_pg_accumulate-d%d-acc%d' % (d, accumulate), 'mfg_td_pg_accumulate')
-    def build(a):
-        N = _sum_N(d)
+def _nm(N):
+    return '' if N is None else '-N%d' % N
+
+
+def _td_pg_accumulate(d, accumulate, N=None):
+    @row('td_pg_accumulate-d%d-acc%d%s' % (d, accumulate, _nm(N)), 'mfg_td_pg_accumulate', work=_w('mfg_td_pg_accumulate', CTL))
+    def build(a, N=N):
+        N = N or _sum_N(d)
         F = _ops().num_features(d)
         pi, pin, P = a.inp('pi', a.simplex((N, d), 7)), a.inp('pi_next', a.simplex((N, d), 8)), a.inp('P', a.simplex((N, d, d), 9))
         reward, w, th = a.inp('reward', a.randn64((N,), 10).float()), a.w(d), a.theta()
         delta, g = a.out('delta', (N,), F64), a.out('g', (N,), F64)
         G = a.io('G', a.randn64((F + 3,), 11)) if accumulate else a.out('G', (F + 3,), F64)
         n = wsb(N, d)
-        ws = a.ws(n)
+        ws = a.ws(n, zero=CONTROL)
         return lambda: call('mfg_td_pg_accumulate', p(pi), p(pin), p(P), p(reward), p(w), p(th), SHIFT, GAMMA, N, d,
                             _L().PRECISION_MIXED, p(delta), p(g), p(G), accumulate, p(ws), n)
 
 
-def _grad_accumulate(d, accumulate):
-    @row('grad_accumulate-d%d-acc%d' % (d, accumulate), 'mfg_grad_accumulate')
-    def build(a):
+def _grad_accumulate(d, accumulate, N=None):
+    @row('grad_accumulate-d%d-acc%d%s' % (d, accumulate, _nm(N)), 'mfg_grad_accumulate', work=_w('mfg_grad_accumulate', CTL))
+    def build(a, N=N):
         """accumulate = 1 also runs add_reward = 1: delta is then updated in place."""
-        N = _sum_N(d)
+        N = N or _sum_N(d)
         F = _ops().num_features(d)
         pi, g, reward = a.inp('pi', a.simplex((N, d), 12)), a.inp('g', a.randn64((N,), 13)), a.inp('reward', a.randn64((N,), 14).float())
         delta = a.io_or_inp('delta', a.randn64((N,), 15), bool(accumulate))
         G = a.io('G', a.randn64((F + 3,), 16)) if accumulate else a.out('G', (F + 3,), F64)
         n = wsb(N, d)
-        ws = a.ws(n)
+        ws = a.ws(n, zero=CONTROL)
         return lambda: call('mfg_grad_accumulate', p(pi), d, p(delta), p(g), p(reward), N, 1, d, accumulate, p(G), accumulate,
                             p(ws), n)
 
 
-def _grad_apply(d, add_reward):
-    @row('grad_apply-d%d-add_reward%d' % (d, add_reward), 'mfg_grad_apply')
-    def build(a):
+def _grad_apply(d, add_reward, N=None):
+    @row('grad_apply-d%d-add_reward%d%s' % (d, add_reward, _nm(N)), 'mfg_grad_apply', work=_w('mfg_grad_apply', CTL))
+    def build(a, N=N):
         """mfg_grad_apply has no `accumulate`: its two forms are add_reward = 0 / 1 (delta then updated in place)."""
-        N = _sum_N(d)
+        N = N or _sum_N(d)
         F = _ops().num_features(d)
         pi, g, reward = a.inp('pi', a.simplex((N, d), 17)), a.inp('g', a.randn64((N,), 18)), a.inp('reward', a.randn64((N,), 19).float())
         delta = a.io_or_inp('delta', a.randn64((N,), 20), bool(add_reward))
         w, th, acc = a.w(d, True), a.io('theta', a.f64(THETA)), a.io('reward_acc', a.f64(-3.25))
         G, n = a.out('G', (F + 3,), F64), wsb(N, d)
-        ws = a.ws(n)
+        ws = a.ws(n, zero=CONTROL)
         return lambda: call('mfg_grad_apply', p(pi), d, p(delta), p(g), p(reward), N, 1, d, add_reward, p(G), LR_C, LR_A, p(w),
                             p(th), p(acc), p(ws), n)
 
@@ -350,7 +452,7 @@ def _apply_update(a):
 # mfg_train_rollout (MFG_TRAIN_APPLY), mfg_train_rollout_deferred, mfg_train_rollouts
 # ---------------------------------------------------------------------------------------------------
 def _train_rollout(with_idx):
-    @row('train_rollout-apply-%s' % ('idx' if with_idx else 'drawn'), 'mfg_train_rollout')
+    @row('train_rollout-apply-%s' % ('idx' if with_idx else 'drawn'), 'mfg_train_rollout', work=_w('mfg_train_rollout', CTL))
     def build(a):
         L = _L()
         d, B, T = 21, 13, 3
@@ -360,7 +462,7 @@ def _train_rollout(with_idx):
         th, w, acc = a.io('theta', a.f64(THETA)), a.w(d, True), a.io('reward_acc', a.f64(-3.25))
         traj, last, r, delta, g = _rollout_outs(a, B, d, T)
         G, n = a.out('G', (F + 3,), F64), wsb(B * T, d)
-        ws = a.ws(n)
+        ws = a.ws(n, zero=CONTROL)
         return lambda: call('mfg_train_rollout', p(mat), NUM_START, p(idx), B, d, T, p(th), SHIFT, SCALE, p(w), GAMMA,
                             L.REWARD_MFG_AC2, 7, 3, 100, L.TRAIN_APPLY, LR_C, LR_A, p(traj), p(last), p(r), p(delta), p(g), p(G),
                             p(acc), p(ws), n)
@@ -370,8 +472,12 @@ _train_rollout(True)
 _train_rollout(False)
 
 
+_DEFERRED = {21: (13, 3), 128: (5, 2)}      # the table's shapes per d: their rows keep the names without a shape suffix
+
+
 def _train_rollout_deferred(d, B, T):
-    @row('train_rollout_deferred-x2-d%d' % d, 'mfg_train_rollout_deferred')
+    @row('train_rollout_deferred-x2-d%d%s' % (d, '' if (B, T) == _DEFERRED[d] else '-B%d-T%d' % (B, T)),
+         'mfg_train_rollout_deferred', work=_w('mfg_train_rollout_deferred', CTL))
     def build(a):
         """Two chained calls that ping-pong the parameter sets: (theta, w) -> (theta_alt, w_alt) -> (theta, w), the second
         applying the sums the first left in G (d > 64: the out-of-place update launch and its device-to-device copies)."""
@@ -383,7 +489,7 @@ def _train_rollout_deferred(d, B, T):
         th2, w2 = a.out('theta_alt', (1,), F64), a.out('w_alt', (F,), F64)
         traj, last, r, delta, g = _rollout_outs(a, B, d, T)
         G, n = a.out('G', (F + 3,), F64), wsb(B * T, d)
-        ws = a.ws(n)
+        ws = a.ws(n, zero=CONTROL)
 
         def one(t_in, w_in, pend, t_out, w_out, step):
             call('mfg_train_rollout_deferred', p(mat), NUM_START, None, B, d, T, p(t_in), p(w_in), p(pend), LR_C, LR_A, p(acc),
@@ -401,13 +507,17 @@ _train_rollout_deferred(128, 5, 2)
 
 
 def _episode_bufs(a, B, d, lead=()):
-    """pi_scratch is scratch by contract, like the workspace: zeroed, not compared."""
+    """pi_scratch is scratch by contract (no range of it is declared zero): not compared."""
     return (a.ws(int(np.prod(lead + (B, d))) * 4, F32, lead + (B, d)), a.out('reward', lead + (B,)), a.out('delta', lead + (B,), F64),
             a.out('g', lead + (B,), F64))
 
 
+_EPISODE = {21: (13, 3), 47: (9, 2)}         # the table's shapes per d, as _DEFERRED
+
+
 def _train_episode(d, B, T):
-    @row('train_episode-d%d-T%d' % (d, T), 'mfg_train_episode')
+    @row('train_episode-d%d-T%d%s' % (d, T, '' if (B, T) == _EPISODE.get(d) else '-B%d' % B), 'mfg_train_episode',
+         work=_w('mfg_train_episode', SCRATCH_KIND, CTL))
     def build(a):
         L = _L()
         F = _ops().num_features(d)
@@ -415,7 +525,7 @@ def _train_episode(d, B, T):
         th, w, acc = a.io('theta', a.f64(THETA)), a.w(d, True), a.io('reward_acc', a.f64(-3.25))
         scratch, r, delta, g = _episode_bufs(a, B, d)
         G, n = a.out('G', (F + 3,), F64), wsb(B, d)
-        ws = a.ws(n)
+        ws = a.ws(n, zero=CONTROL)
         return lambda: call('mfg_train_episode', p(pi), p(scratch), B, d, T, p(th), SHIFT, SCALE, p(w), GAMMA, L.REWARD_MFG_AC2,
                             7, 3, 100, L.PRECISION_MIXED, LR_C, LR_A, p(r), p(delta), p(g), p(G), p(acc), p(ws), n)
 
@@ -426,33 +536,46 @@ _train_episode(47, 9, 2)        # the two-kernel path
 EPISODES = 3
 
 
-@row('train_episodes-x3', 'mfg_train_episodes')
-def _train_episodes(a):
-    L = _L()
-    d, B, T = 21, 13, 3
-    F = _ops().num_features(d)
-    mat, pi = a.inp('mat_pi0', a.simplex((NUM_START, d), 27)), a.out('pi_io', (B, d))
-    th, w, acc = a.io('theta', a.f64(THETA)), a.w(d, True), a.io('reward_acc', a.f64(0.0, 0.0, 0.0) + a.salt)
-    scratch, r, delta, g = _episode_bufs(a, B, d)
-    G, n = a.out('G', (F + 3,), F64), wsb(B, d)
-    ws = a.ws(n)
-    return lambda: call('mfg_train_episodes', p(mat), NUM_START, p(pi), p(scratch), B, d, T, EPISODES, 0, 0, p(th), SHIFT, SCALE,
-                        p(w), GAMMA, L.REWARD_MFG_AC2, 7, 3, 100, L.PRECISION_MIXED, LR_C, LR_A, p(r), p(delta), p(g), p(G), p(acc),
-                        p(ws), n)
+def _bt(B, T, B0=13, T0=3):
+    return '' if (B, T) == (B0, T0) else '-B%d-T%d' % (B, T)
 
 
-@row('train_rollouts-x3', 'mfg_train_rollouts')
-def _train_rollouts(a):
-    L = _L()
-    d, B, T = 21, 13, 3
-    F = _ops().num_features(d)
-    mat = a.inp('mat_pi0', a.simplex((NUM_START, d), 28))
-    th, w, acc = a.io('theta', a.f64(THETA)), a.w(d, True), a.io('reward_acc', a.f64(0.0, 0.0, 0.0) + a.salt)
-    traj, last, r, delta, g = _rollout_outs(a, B, d, T)
-    G, n = a.out('G', (F + 3,), F64), wsb(B * T, d)
-    ws = a.ws(n)
-    return lambda: call('mfg_train_rollouts', p(mat), NUM_START, B, d, T, EPISODES, 0, 0, p(th), SHIFT, SCALE, p(w), GAMMA,
-                        L.REWARD_MFG_AC2, 7, 3, 100, 0, LR_C, LR_A, p(traj), p(last), p(r), p(delta), p(g), p(G), p(acc), p(ws), n)
+def _train_episodes(B=13, T=3):
+    @row('train_episodes-x3' + _bt(B, T), 'mfg_train_episodes', work=_w('mfg_train_episodes', SCRATCH_KIND, CTL))
+    def build(a):
+        L = _L()
+        d = 21
+        F = _ops().num_features(d)
+        mat, pi = a.inp('mat_pi0', a.simplex((NUM_START, d), 27)), a.out('pi_io', (B, d))
+        th, w, acc = a.io('theta', a.f64(THETA)), a.w(d, True), a.io('reward_acc', a.f64(0.0, 0.0, 0.0) + a.salt)
+        scratch, r, delta, g = _episode_bufs(a, B, d)
+        G, n = a.out('G', (F + 3,), F64), wsb(B, d)
+        ws = a.ws(n, zero=CONTROL)
+        return lambda: call('mfg_train_episodes', p(mat), NUM_START, p(pi), p(scratch), B, d, T, EPISODES, 0, 0, p(th), SHIFT,
+                            SCALE, p(w), GAMMA, L.REWARD_MFG_AC2, 7, 3, 100, L.PRECISION_MIXED, LR_C, LR_A, p(r), p(delta), p(g),
+                            p(G), p(acc), p(ws), n)
+
+
+_train_episodes()
+
+
+def _train_rollouts(B=13, T=3):
+    @row('train_rollouts-x3' + _bt(B, T), 'mfg_train_rollouts', work=_w('mfg_train_rollouts', CTL))
+    def build(a):
+        L = _L()
+        d = 21
+        F = _ops().num_features(d)
+        mat = a.inp('mat_pi0', a.simplex((NUM_START, d), 28))
+        th, w, acc = a.io('theta', a.f64(THETA)), a.w(d, True), a.io('reward_acc', a.f64(0.0, 0.0, 0.0) + a.salt)
+        traj, last, r, delta, g = _rollout_outs(a, B, d, T)
+        G, n = a.out('G', (F + 3,), F64), wsb(B * T, d)
+        ws = a.ws(n, zero=CONTROL)
+        return lambda: call('mfg_train_rollouts', p(mat), NUM_START, B, d, T, EPISODES, 0, 0, p(th), SHIFT, SCALE, p(w), GAMMA,
+                            L.REWARD_MFG_AC2, 7, 3, 100, 0, LR_C, LR_A, p(traj), p(last), p(r), p(delta), p(g), p(G), p(acc), p(ws),
+                            n)
+
+
+_train_rollouts()
 
 
 # ---------------------------------------------------------------------------------------------------
@@ -461,8 +584,12 @@ def _train_rollouts(a):
 POP = dict(K=3, B=13, T=2, E=2, d=21)
 
 
-def _pop_common(a, seed):
-    K, B, T, E, d = (POP[k] for k in 'KBTEd')
+def _pop_name(shape):
+    return '' if shape is POP else '-B%d-T%d' % (shape['B'], shape['T'])
+
+
+def _pop_common(a, seed, shape=POP, scratch=False):
+    K, B, T, E, d = (shape[k] for k in 'KBTEd')
     F = _ops().num_features(d)
     sb = _ops().pop_workspace_slice(B, d, T)
     mat = a.inp('mat_pi0', a.simplex((NUM_START, d), seed))
@@ -472,16 +599,19 @@ def _pop_common(a, seed):
     w, G = a.w(d, True, (K,)), a.out('G', (K, F + 3), F64)
     acc = a.io('reward_acc', torch.zeros(K, E, dtype=F64, device=a.dev) + a.salt)
     lrc, lra = a.inp('lr_critic', a.f64(*np.linspace(0.05, 0.15, K))), a.inp('lr_actor', a.f64(*np.linspace(5e-4, 2e-3, K)))
-    ws = a.ws(K * sb, F64, (K, sb // 8))
+    ws = a.ws(K * sb, F64, (K, sb // 8), zero=SCRATCH if scratch else slices(K, sb))
     return mat, th, sh, al, sd, w, G, acc, lrc, lra, ws, sb
 
 
-def _pop_step(entry, control=False):
-    @row(entry[4:] + ('-control' if control else ''), entry)
+def _pop_step(entry, control=False, shape=POP):
+    # (the resident form's header comment calls its workspace scratch: nothing of it is declared)
+    kind = SCRATCH_KIND if entry.endswith('_resident') else SLICES
+
+    @row(entry[4:] + ('-control' if control else '') + _pop_name(shape), entry, work=((entry, 'workspace', kind), (entry, 'pi_scratch', SCRATCH_KIND)))
     def build(a):
         L = _L()
-        K, B, T, E, d = (POP[k] for k in 'KBTEd')
-        mat, th, sh, al, sd, w, G, acc, lrc, lra, ws, sb = _pop_common(a, 29)
+        K, B, T, E, d = (shape[k] for k in 'KBTEd')
+        mat, th, sh, al, sd, w, G, acc, lrc, lra, ws, sb = _pop_common(a, 29, shape, kind == SCRATCH_KIND)
         pi = a.out('pi_io', (K, B, d))
         scratch, r, delta, g = _episode_bufs(a, B, d, (K,))
         args = (p(mat), NUM_START, p(pi), p(scratch), B, K, d, T, E, 0, 0, p(th), p(sh), p(al), p(w), GAMMA, L.REWARD_MFG_AC2, p(sd),
@@ -514,15 +644,72 @@ _pop_step('mfg_train_episodes_pop', control=True)
 _pop_step('mfg_train_episodes_pop_resident')
 
 
-@row('train_rollouts_pop', 'mfg_train_rollouts_pop')
-def _pop_rollouts(a):
-    L = _L()
-    K, B, T, E, d = (POP[k] for k in 'KBTEd')
-    mat, th, sh, al, sd, w, G, acc, lrc, lra, ws, sb = _pop_common(a, 30)
-    traj, last, r, delta, g = _rollout_outs(a, B, d, T, (K,))
-    return lambda: call('mfg_train_rollouts_pop', p(mat), NUM_START, B, K, d, T, E, 0, 0, p(th), p(sh), p(al), p(w), GAMMA,
-                        L.REWARD_MFG_AC2, p(sd), 3, 100, 0, p(lrc), p(lra), p(traj), p(last), p(r), p(delta), p(g), p(G), p(acc),
-                        p(ws), sb)
+def _pop_rollouts(shape=POP):
+    @row('train_rollouts_pop' + _pop_name(shape), 'mfg_train_rollouts_pop', work=_w('mfg_train_rollouts_pop', SLICES))
+    def build(a):
+        L = _L()
+        K, B, T, E, d = (shape[k] for k in 'KBTEd')
+        mat, th, sh, al, sd, w, G, acc, lrc, lra, ws, sb = _pop_common(a, 30, shape)
+        traj, last, r, delta, g = _rollout_outs(a, B, d, T, (K,))
+        return lambda: call('mfg_train_rollouts_pop', p(mat), NUM_START, B, K, d, T, E, 0, 0, p(th), p(sh), p(al), p(w), GAMMA,
+                            L.REWARD_MFG_AC2, p(sd), 3, 100, 0, p(lrc), p(lra), p(traj), p(last), p(r), p(delta), p(g), p(G), p(acc),
+                            p(ws), sb)
+
+
+_pop_rollouts()
+
+VAL = dict(N=2, L=4, R=3)        # a held-out check: N files of L rows, R rollouts per file
+
+
+def _pop_validated(shape=POP, VN=VAL['N']):
+    """mfg_train_episodes_pop under a validation block (with the scores) and an evolve block: E = 2 episodes, period 1, so TWO
+    checks run in one call, each followed by an exploit / explore step.  The blocks' work buffers reach the library through
+    the structs of mfg_ctx_set_pop_validate / mfg_ctx_set_pop_evolve, not through a parameter: the validation workspace and
+    the evolve block's order / active arrays, all three scratch in the header's words."""
+    entry = 'mfg_train_episodes_pop'
+
+    @row('train_episodes_pop-validate-evolve' + _pop_name(shape) + ('' if VN == VAL['N'] else '-VN%d' % VN), entry,
+         work=((entry, 'workspace', SLICES), (entry, 'pi_scratch', SCRATCH_KIND), (entry, 'validate.workspace', SCRATCH_KIND),
+               (entry, 'evolve.order', SCRATCH_KIND), (entry, 'evolve.active', SCRATCH_KIND)))
+    def build(a):
+        L, ops = _L(), _ops()
+        K, B, T, E, d = (shape[k] for k in 'KBTEd')
+        F = ops.num_features(d)
+        mat, th, sh, al, sd, w, G, acc, lrc, lra, ws, sb = _pop_common(a, 78, shape)
+        a.written += ['lr_critic', 'lr_actor']                      # (an evolve step rewrites the rates between two episodes)
+        pi = a.out('pi_io', (K, B, d))
+        scratch, r, delta, g = _episode_bufs(a, B, d, (K,))
+        emp = a.simplex((VN, VAL['L'], d), 79)
+        emp32, emp64 = a.inp('emp32', emp), a.inp('emp64', emp.double())
+        i32 = lambda v: torch.full((K,), v, dtype=I32, device=a.dev)
+        val = dict(curve=a.out('val_curve', (K, E, 10), F64), checks=a.io('val_checks', i32(0)),
+                   best_value=a.io('val_best_value', torch.full((K,), float('inf'), dtype=F64, device=a.dev)),
+                   best_check=a.io('val_best_check', i32(-1)), since_best=a.io('val_since_best', i32(0)),
+                   best_theta=a.out('val_best_theta', (K,), F64), best_w=a.out('val_best_w', (K, F), F64))
+        nv = ops.pop_validate_workspace_bytes(VN, VAL['L'], d, K, VAL['R'], True)
+        vws = a.ws(nv)
+        evo = dict(order=a.ws(4 * K, I32), active=a.ws(4, I32), rank=a.out('evo_rank', (K, E), I32, keep=-1),
+                   parent=a.out('evo_parent', (K, E), I32, keep=-1), lr_log=a.out('evo_lr_log', (K, E, 2), F64))
+        ctx = ops.Context(a.dev)
+        a.keep.append(ctx)
+        args = (p(mat), NUM_START, p(pi), p(scratch), B, K, d, T, E, 0, 0, p(th), p(sh), p(al), p(w), GAMMA, L.REWARD_MFG_AC2, p(sd),
+                3, 100, L.PRECISION_MIXED, p(lrc), p(lra), p(r), p(delta), p(g), p(G), p(acc), p(ws), sb)
+
+        def issue():
+            before = ctx.bind_scoped()
+            try:
+                ctx.set_pop_validate(emp32, emp64, period=1, column=8, with_score=True, first_step=7, repeats=VAL['R'],
+                                     workspace=vws, workspace_bytes=nv, **val)
+                ctx.set_pop_evolve(lrc, lra, n_top=1, n_bottom=1, seed=0x5EED, **evo)
+                call(entry, *args)
+            finally:
+                ctx.set_pop_evolve()
+                ctx.set_pop_validate()
+                ctx.restore(before)
+        return issue
+
+
+_pop_validated()
 
 
 # ---------------------------------------------------------------------------------------------------
@@ -561,13 +748,17 @@ _reward_net_forward(24, 'runs')      # n_fc3 > 16: the run-mapped kernel
 IRL = dict(d=21, B=13, T=2, n3=8, n4=4)
 
 
-def _irl_episode(draw):
-    @row('train_episode_irl' + ('_draw' if draw else ''), 'mfg_train_episode_irl' + ('_draw' if draw else ''))
+def _irl_episode(draw, B=IRL['B'], T=IRL['T'], n3=IRL['n3']):
+    """n3 <= 16: the two-launch env step (k_reward_net_mfma<.., SUMS>); above: three launches, the run-mapped network kernel."""
+    entry = 'mfg_train_episode_irl' + ('_draw' if draw else '')
+
+    @row(entry[4:] + _bt(B, T, IRL['B'], IRL['T']) + ('' if n3 == IRL['n3'] else '-n3_%d' % n3), entry,
+         work=_w(entry, SCRATCH_KIND, CTL))
     def build(a):
         L = _L()
-        d, B, T = IRL['d'], IRL['B'], IRL['T']
+        d = IRL['d']
         F = _ops().num_features(d)
-        st = _net(a, d, IRL['n3'], IRL['n4'])
+        st = _net(a, d, n3, IRL['n4'])
         if draw:
             mat, pi = a.inp('mat_pi0', a.simplex((NUM_START, d), 33)), a.out('pi_out', (B, d))
         else:
@@ -575,7 +766,7 @@ def _irl_episode(draw):
         th, w, acc = a.io('theta', a.f64(THETA)), a.w(d, True), a.io('reward_acc', a.f64(-3.25))
         scratch, r, delta, g = _episode_bufs(a, B, d)
         P, G, n = a.out('P', (B, d, d)), a.out('G', (F + 3,), F64), wsb(B, d)
-        ws = a.ws(n)
+        ws = a.ws(n, zero=CONTROL)
         rest = (p(pi), p(scratch), B, d, T, p(th), SHIFT, SCALE, p(w), GAMMA, 7, 3, 100, L.PRECISION_MIXED, LR_C, LR_A, C.byref(st),
                 0x5EED, 4, 100, p(P), p(r), p(delta), p(g), p(G), p(acc), p(ws), n)
         if draw:
@@ -587,31 +778,36 @@ _irl_episode(False)
 _irl_episode(True)
 
 
-@row('train_rollout_irl', 'mfg_train_rollout_irl')
-def _irl_rollout(a):
-    L = _L()
-    d, B, T = IRL['d'], IRL['B'], IRL['T']
-    F = _ops().num_features(d)
-    st = _net(a, d, IRL['n3'], IRL['n4'])
-    mat = a.inp('mat_pi0', a.simplex((NUM_START, d), 34))
-    th, w, acc = a.io('theta', a.f64(THETA)), a.w(d, True), a.io('reward_acc', a.f64(-3.25))
-    traj, last, r, delta, g = _rollout_outs(a, B, d, T)
-    P, G, n = a.out('P', (B, T, d, d)), a.out('G', (F + 3,), F64), wsb(B * T, d)
-    ws = a.ws(n)
-    return lambda: call('mfg_train_rollout_irl', p(mat), NUM_START, None, B, d, T, p(th), SHIFT, SCALE, p(w), GAMMA, 7, 3, 100,
-                        L.TRAIN_APPLY | L.ROLLOUT_DISCOUNT_POW, LR_C, LR_A, C.byref(st), 0xABCDEF, 100 * T, p(traj), p(last), p(P),
-                        p(r), p(delta), p(g), p(G), p(acc), p(ws), n)
-
-
-def _irl_pop(step):
-    entry = 'mfg_train_episodes_irl_pop' if step else 'mfg_train_rollouts_irl_pop'
-
-    @row(entry[4:], entry)
+def _irl_rollout(B=IRL['B'], T=IRL['T']):
+    @row('train_rollout_irl' + _bt(B, T, IRL['B'], IRL['T']), 'mfg_train_rollout_irl', work=_w('mfg_train_rollout_irl', CTL))
     def build(a):
         L = _L()
-        K, B, T, E, d = (POP[k] for k in 'KBTEd')
+        d = IRL['d']
+        F = _ops().num_features(d)
+        st = _net(a, d, IRL['n3'], IRL['n4'])
+        mat = a.inp('mat_pi0', a.simplex((NUM_START, d), 34))
+        th, w, acc = a.io('theta', a.f64(THETA)), a.w(d, True), a.io('reward_acc', a.f64(-3.25))
+        traj, last, r, delta, g = _rollout_outs(a, B, d, T)
+        P, G, n = a.out('P', (B, T, d, d)), a.out('G', (F + 3,), F64), wsb(B * T, d)
+        ws = a.ws(n, zero=CONTROL)
+        return lambda: call('mfg_train_rollout_irl', p(mat), NUM_START, None, B, d, T, p(th), SHIFT, SCALE, p(w), GAMMA, 7, 3, 100,
+                            L.TRAIN_APPLY | L.ROLLOUT_DISCOUNT_POW, LR_C, LR_A, C.byref(st), 0xABCDEF, 100 * T, p(traj), p(last),
+                            p(P), p(r), p(delta), p(g), p(G), p(acc), p(ws), n)
+
+
+_irl_rollout()
+
+
+def _irl_pop(step, shape=POP):
+    entry = 'mfg_train_episodes_irl_pop' if step else 'mfg_train_rollouts_irl_pop'
+    work = ((entry, 'workspace', SLICES),) + (((entry, 'pi_scratch', SCRATCH_KIND),) if step else ())
+
+    @row(entry[4:] + _pop_name(shape), entry, work=work)
+    def build(a):
+        L = _L()
+        K, B, T, E, d = (shape[k] for k in 'KBTEd')
         st = _net(a, d, IRL['n3'], IRL['n4'], K=K)               # per-learner networks, stacked tensors
-        mat, th, sh, al, sd, w, G, acc, lrc, lra, ws, sb = _pop_common(a, 35)
+        mat, th, sh, al, sd, w, G, acc, lrc, lra, ws, sb = _pop_common(a, 35, shape)
         rn_seed = a.inp('rn_seed', torch.arange(K, dtype=I64, device=a.dev) + 0x5EED + a.salt)
         rn_call0 = a.inp('rn_call0', torch.arange(K, dtype=I64, device=a.dev) * 3 + a.salt)
         head = (p(th), p(sh), p(al), p(w), GAMMA, p(sd), 3, 100)
@@ -652,7 +848,7 @@ def _rn_state(a, lead=()):
 def _rn_train_step(z):
     entry = 'mfg_reward_net_train_step' + ('_z' if z else '')
 
-    @row(entry[4:], entry)
+    @row(entry[4:], entry, work=_w(entry, SCRATCH_KIND))
     def build(a):
         nd, ng, T = RN['nd'], RN['ng'], RN['T']
         NP, prm, m, v, demo, gen = _rn_state(a)
@@ -683,7 +879,7 @@ def _rn_adam(a):
 # ---------------------------------------------------------------------------------------------------
 # evaluation, forecast, scores, finite populations, consistency, distributions
 # ---------------------------------------------------------------------------------------------------
-@row('evaluate_pop', 'mfg_evaluate_pop')
+@row('evaluate_pop', 'mfg_evaluate_pop', work=_w('mfg_evaluate_pop', SCRATCH_KIND))
 def _evaluate_pop(a):
     d, K, R, N, Lr = 21, 3, 3, 5, 6
     emp = a.simplex((N, Lr, d), 48)
@@ -703,7 +899,7 @@ def _host_ranks(a, ranks, other):
     return arr
 
 
-@row('forecast_pop-R3', 'mfg_forecast_pop')
+@row('forecast_pop-R3', 'mfg_forecast_pop', work=_w('mfg_forecast_pop', SCRATCH_KIND))
 def _forecast_pop(a):
     d, K, N, H, R = 21, 2, 2, 4, 3
     emp = a.simplex((N, H, d), 49)
@@ -718,7 +914,7 @@ def _forecast_pop(a):
                         p(e32), p(e64), p(mean), p(std), p(quant), p(curves), None, p(ws), n)
 
 
-@row('forecast_score-R65-energy', 'mfg_forecast_score')
+@row('forecast_score-R65-energy', 'mfg_forecast_score', work=_w('mfg_forecast_score', SCRATCH_KIND))
 def _forecast_score(a):
     d, K, N, H, R = 15, 2, 2, 3, 65
     emp = a.simplex((N, H, d), 50)
@@ -750,7 +946,7 @@ def _agents_step(a):
     return lambda: call('mfg_agents_step_pop', p(counts), p(P), B, d, K, AGENTS, p(sd), 5, 1000, p(cn), p(pn), p(mv))
 
 
-@row('forecast_agents_pop-H4', 'mfg_forecast_agents_pop')
+@row('forecast_agents_pop-H4', 'mfg_forecast_agents_pop', work=_w('mfg_forecast_agents_pop', SCRATCH_KIND))
 def _forecast_agents(a):
     d, K, N, H, R = 21, 2, 2, 4, 3
     emp = a.simplex((N, H, d), 54)
@@ -767,7 +963,7 @@ def _forecast_agents(a):
                         p(ws), n)
 
 
-@row('consistency_given', 'mfg_consistency_given')
+@row('consistency_given', 'mfg_consistency_given', work=_w('mfg_consistency_given', SCRATCH_KIND))
 def _consistency_given(a):
     """Without `steps` the per-hour values live in the workspace, which the second launch reads."""
     K, M, T, d = 2, 3, 2, 7
@@ -777,7 +973,7 @@ def _consistency_given(a):
     return lambda: call('mfg_consistency_given', p(P), K, M, T, d, p(metrics), None, None, p(ws), n)
 
 
-@row('consistency_pop', 'mfg_consistency_pop')
+@row('consistency_pop', 'mfg_consistency_pop', work=_w('mfg_consistency_pop', SCRATCH_KIND))
 def _consistency_pop(a):
     d, K, N, H, R = 15, 2, 3, 3, 2
     s32 = a.inp('start32', a.simplex((N, d), 56))
@@ -802,7 +998,7 @@ def _row_distribution(a):
                         p(density), p(status), p(ws), n)
 
 
-@row('action_mean_pop', 'mfg_action_mean_pop')
+@row('action_mean_pop', 'mfg_action_mean_pop', work=_w('mfg_action_mean_pop', SCRATCH_KIND))
 def _action_mean(a):
     K, N, d = 2, 37, 21
     act, mean = a.inp('action', a.simplex((K, N, d, d), 58)), a.out('mean', (K, d, d), F64)
@@ -900,7 +1096,7 @@ def _philox_raw(a):
 # ---------------------------------------------------------------------------------------------------
 # the documented drainers: a host array goes into device scratch and the stream is drained before the first launch
 # ---------------------------------------------------------------------------------------------------
-@row('reward_net_forward_pop', 'mfg_reward_net_forward_pop')
+@row('reward_net_forward_pop', 'mfg_reward_net_forward_pop', work=(('mfg_reward_net_forward_pop', 'scratch', SCRATCH_KIND),))
 def _forward_pop(a):
     d, K, N = 21, 3, 37
     st = _net(a, d, 8, 4, K=K)
@@ -912,7 +1108,7 @@ def _forward_pop(a):
 def _train_steps_pop(z):
     entry = 'mfg_reward_net_train_steps_pop' + ('_z' if z else '')
 
-    @row(entry[4:], entry)
+    @row(entry[4:], entry, work=((entry, 'workspace', SCRATCH_KIND), (entry, 'plan_dev', SCRATCH_KIND)))
     def build(a):
         ops = _ops()
         nd, ng, T, rows = RN['nd'], RN['ng'], RN['T'], RN['rows']
@@ -941,7 +1137,7 @@ _train_steps_pop(False)
 _train_steps_pop(True)
 
 
-@row('traj_log_z_pop', 'mfg_traj_log_z_pop')
+@row('traj_log_z_pop', 'mfg_traj_log_z_pop', work=(('mfg_traj_log_z_pop', 'scratch', SCRATCH_KIND),))
 def _traj_log_z(a):
     K, cap, T, d = 2, 6, 3, 15
     state, action = a.inp('state', a.simplex((cap, T, d), 76)), a.inp('action', a.simplex((cap, T, d, d), 77))

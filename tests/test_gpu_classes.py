@@ -671,6 +671,34 @@ def test_irl_episode_with_drawn_start_states_equals_draw_then_episode(dev, d, B,
     assert outs[1][0][0] != 8.64 and outs[1][2][F + 2] == B
 
 
+@pytest.mark.parametrize('T,n3,draw', [(2, 8, False), (3, 8, True), (1, 8, False), (2, 24, False)])
+def test_irl_episode_leaves_the_control_block_zero(dev, T, n3, draw):
+    """include/mfg_hip.h: every call leaves the workspace's control block (its first 64 bytes) zero again.  The two-launch env
+    step (n_fc3 = 8) keeps theta between two steps in bytes 16 .. 31 of that block (odd / even steps: T = 2 and 3 fill one slot
+    and both); the row reduction that closes the episode has to zero them.  T = 1 and the three-launch flow (n_fc3 = 24) never
+    write them.  The episode itself is compared elsewhere; here only the block, and that theta moved."""
+    from discrete_mean_field_game_amd import ops
+    from discrete_mean_field_game_amd.networks import RewardNet
+    ops.init()
+    d, B = 21, 37
+    rs = np.random.RandomState(T * 100 + n3)
+    torch.manual_seed(n3)
+    mat = torch.as_tensor(rs.dirichlet(np.ones(d), size=11).astype(np.float32), device=dev)
+    net = RewardNet(d=d, reg='dropout_l1l2', n_fc3=n3, n_fc4=8).to(dev)
+    F = ops.num_features(d)
+    th = torch.tensor([8.64], dtype=torch.float64, device=dev)
+    w = torch.as_tensor(rs.rand(F) * 0.1, device=dev)
+    G = torch.zeros(F + 3, dtype=torch.float64, device=dev)
+    ws = ops.workspace(B, d, dev)
+    bufs = dict(ops.episode_buffers(B, d, dev), P=torch.empty(B, d, d, dtype=torch.float32, device=dev))
+    pi = torch.full((B, d), float('nan'), dtype=torch.float32, device=dev) if draw else ops.draw_start(mat, B, 7, 40, 5)[1]
+    ops.train_episode_irl(pi, T, th, 0.1, 1e4, w, 0.95, 0.1, 0.001, net, G, ws, bufs, seed=7, first_step=40, traj_offset=5,
+                          rn_seed=99, rn_call0=3, rn_sample_offset=5, **(dict(mat_pi0=mat) if draw else {}))
+    torch.cuda.synchronize()
+    assert float(th[0]) != 8.64 and float(G[F + 2]) == B
+    assert not ws.view(torch.uint8)[:64].any(), ws[:8].tolist()
+
+
 def test_training_step_is_hip_graph_capturable(dev):
     """The C ABI launches on the caller's stream and never allocates or synchronises (after mfg_init), so a whole
     update (fused TD rollout + gradient kernels + parameter update) can be captured into a HIP graph and replayed;
