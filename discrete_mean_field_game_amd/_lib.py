@@ -253,6 +253,17 @@ SIGNATURES['mfg_row_distribution'] = (_i32, [_p, _i32, _i64, _i64, _i32, _i32, _
 SIGNATURES['mfg_action_mean_pop_workspace_bytes'] = (_sz, [_i32, _i64, _i32])
 SIGNATURES['mfg_action_mean_pop'] = (_i32, [_p, _i64, _i32, _i64, _i32, _p, _p, _sz, _p])
 
+
+class RnInputGradStruct(C.Structure):
+    """mfg_rn_input_grad_t of include/mfg_hip.h: the reward input-gradient block that rides on mfg_reward_net_forward_pop."""
+    _fields_ = ([(n, C.c_void_p) for n in ('grad_state', 'grad_action', 'mean_state', 'mean_action', 'workspace')]
+                + [('workspace_bytes', C.c_size_t), ('N', C.c_int64)]
+                + [(n, C.c_int32) for n in ('K', 'd', 'reserved')])
+
+
+SIGNATURES['mfg_rn_input_grad_workspace_bytes'] = (_sz, [_i32, _i64, _i32])
+SIGNATURES['mfg_ctx_set_rn_input_grad'] = (_i32, [_p, C.POINTER(RnInputGradStruct)])
+
 _lib = None
 
 

@@ -907,6 +907,69 @@ class AC_IRL(actor_critic):
         host = both.cpu().numpy()
         return host[0], host[1], np.abs(host[0] - host[1])
 
+    def _check_pop_forward(self, what):
+        """The methods that go through mfg_reward_net_forward_pop with K = 1 need its geometry."""
+        if self.rng != 'philox':
+            raise ValueError("%s needs rng='philox' (the trajectories are generated on the device)" % what)
+        try:
+            ops.irl_pop_net_geometries([self.reward_net])
+        except ValueError as e:
+            raise ValueError('%s: %s' % (what, e)) from None
+
+    @_with_ctx
+    def reward_sensitivity(self, *, theta=None, dropout=False, want_samples=False):
+        """AC_IRLPopulation.reward_sensitivity for this learner: the mean of d r / d pi and d r / d P (and of gradient x input)
+        over the four sets of reward_distribution, through the same C ABI with K = 1 -- a reward_dist.RewardSensitivity
+        without the leading K, what learner k of a population gives, bit for bit.  The counters advance as reward_distribution
+        advances them; theta: for the two generations only.  rng='philox' only."""
+        from . import reward_dist
+        self._check_pop_forward('reward_sensitivity')
+        self._resync_stores()
+        if getattr(self, '_demo_ragged', False) or not len(self._demo_store):
+            raise ValueError('reward_sensitivity needs demonstrations of %d (state, action) pairs each' % EPISODE_STEPS)
+        T, d = EPISODE_STEPS, self.d
+        num_demos = len(self._demo_store)
+        th = self._given_theta(theta)
+        inputs = [self._demo_store.gather_flat(), None]
+        test = [pair for traj in self.list_demonstrations_test for pair in traj]
+        if test:
+            inputs[1] = self._pairs_to_tensors(test)
+        test_table = torch.as_tensor(np.ascontiguousarray(self.mat_pi0_test, dtype=np.float32), device=self.device)
+        for table in (self._mat_pi0_dev, test_table):
+            st, ac = self._generate_device(num_demos, table, th)
+            inputs.append((st[:, :T].reshape(num_demos * T, d).contiguous(), ac.reshape(num_demos * T, d, d)))
+        self._reward_sample_offset = 0
+        struct = ops.reward_net_struct(self.reward_net, dropout=None if dropout else False)
+
+        def run(s, st, ac, reward, bufs):
+            self._reward_calls += 1
+            key = philox_call_key(self.seed, RN_SEED_OFFSET, self._reward_calls)
+            ops.reward_input_grad_pop(struct, True, 1, st, ac, [0], [key], out=reward, want=tuple(bufs), bufs=bufs)
+        return reward_dist.sensitivity(inputs, 1, d, [0], self.device, run, want_samples).learner(0)
+
+    @_with_ctx
+    def reward_heatmap(self, *, theta=8.64, states=None, actions=None):
+        """The numbers of plot_reward_heatmap (ac_irl.py:1378-1443): (rewards [3,3] fp32, states [3,d], actions [3,d,d]) --
+        AC_IRLPopulation.reward_heatmap for this learner, bit for bit.  Unlike the reference, self.theta is not assigned.
+        rng='philox' only."""
+        from . import reward_dist
+        self._check_pop_forward('reward_heatmap')
+        d = self.d
+        protos = reward_dist.heatmap_states(self.mat_pi0, d)
+        if states is None:
+            states = protos
+        if actions is None:
+            table = torch.as_tensor(protos[1:2].copy(), device=self.device)
+            _, ac = self._generate_device(1, table, self._given_theta(theta))
+            actions = reward_dist.heatmap_actions(ac[0:1, 0].cpu().numpy())
+        st9, ac9, states, actions = reward_dist.heatmap_pairs(states, actions, 1, d)
+        # one mfg_reward_net_forward_pop with K = 1, keyed as reward() keys its calls (dropout as the network has it)
+        self._reward_calls += 1
+        key = philox_call_key(self.seed, RN_SEED_OFFSET, self._reward_calls)
+        r = ops.reward_net_forward_pop(ops.reward_net_struct(self.reward_net), True, 1, torch.as_tensor(st9[0], device=self.device),
+                                       torch.as_tensor(ac9[0], device=self.device), [0], [key])
+        return r.cpu().numpy().reshape(3, 3), states, actions[0]
+
     @_with_ctx
     def evaluate(self, theta=8.86349, shift=0.5, alpha_scale=1e4, d=15, episode_length=16, indir='test_normalized_round2',
                  outfile='eval_mfg_round2/validation.csv', write_header=0):

@@ -29,6 +29,7 @@
 #include "mfg_irl_population.h"
 #include "mfg_population.h"
 #include "mfg_pop_evolve.h"
+#include "mfg_reward_grad.h"
 #include "mfg_pop_validate.h"
 #include "mfg_batch_sums.h"
 #include "mfg_host.h"
@@ -136,6 +137,8 @@ struct mfg_ctx {
   mfg_pop_validate_t val{};
   bool has_evo = false;  // population evolve block (mfg_ctx_set_pop_evolve): exploit / explore steps behind those checks
   mfg_pop_evolve_t evo{};
+  bool has_rig = false;  // reward input-gradient block (mfg_ctx_set_rn_input_grad): rides on mfg_reward_net_forward_pop
+  mfg_rn_input_grad_t rig{};
 };
 // The binding is per THREAD, the object's lifetime is not: a context may be destroyed by another thread than the one(s) it is
 // bound on (a garbage collector drops the last reference wherever it runs).  Every live context is therefore registered with
@@ -478,6 +481,23 @@ int mfg_ctx_set_pop_evolve(mfg_ctx_t* ctx, const mfg_pop_evolve_t* block) {
   REQUIRE(e.perturb >= 0 && e.perturb <= 3, "population evolve block: perturb outside [0, 3]");
   ctx->evo = e;
   ctx->has_evo = true;
+  return MFG_OK;
+}
+
+int mfg_ctx_set_rn_input_grad(mfg_ctx_t* ctx, const mfg_rn_input_grad_t* block) {
+  REQUIRE(ctx && ctx_is_live(ctx), "null or destroyed context");
+  if (!block) {
+    ctx->has_rig = false;
+    ctx->rig = mfg_rn_input_grad_t{};
+    return MFG_OK;
+  }
+  const mfg_rn_input_grad_t& b = *block;
+  REQUIRE(b.grad_state || b.grad_action || b.mean_state || b.mean_action, "reward input-gradient block: all four outputs are NULL");
+  REQUIRE(b.K >= 1 && b.K <= MFG_POP_MAX_K, "reward input-gradient block: K outside [1, MFG_POP_MAX_K]");
+  REQUIRE(b.N >= 1, "reward input-gradient block: no samples (N < 1)");
+  REQUIRE((reinterpret_cast<uintptr_t>(b.workspace) & 7) == 0, "reward input-gradient block: workspace not 8-byte aligned");
+  ctx->rig = b;
+  ctx->has_rig = true;
   return MFG_OK;
 }
 
@@ -844,6 +864,13 @@ int mfg_train_rollout_deferred(const float* mat_pi0, int64_t num_start, const in
 // instance serves the job); the library has no link-time dependency on it and reports MFG_EUNSUPPORTED where it is absent.
 // ---------------------------------------------------------------------------------------------
 }  // extern "C" (the helpers below have C++ linkage)
+namespace mfg {
+// (mfg_reward_grad.h) the reward input-gradient block mfg_reward_net_forward_pop runs under: that of the bound context
+const mfg_rn_input_grad_t* bound_rn_input_grad() {
+  const mfg_ctx* c = bound_ctx();
+  return (c && c->has_rig) ? &c->rig : nullptr;
+}
+}  // namespace mfg
 namespace {
 struct RcclApi {
   int (*GetUniqueId)(void*) = nullptr;

@@ -18,6 +18,7 @@
 #include "../../include/mfg_hip.h"
 #include "mfg_core.h"
 #include "mfg_irl_population.h"
+#include "mfg_reward_grad.h"
 #include "mfg_rn_common.h"
 
 namespace mfg {
@@ -1503,6 +1504,13 @@ extern "C" int mfg_reward_net_forward_pop(const float* state, const float* actio
     return set_error(MFG_EUNSUPPORTED, "reward_net_forward_pop: not the matrix-core reward network (d = 21 / 15, 5 / 2 / 3, "
                                        "n_fc3 <= 16, 8-byte aligned fc3_w of every learner)");
   if (scratch_bytes < (size_t)n * 16) return set_error(MFG_EWORKSPACE, "reward_net_forward_pop: scratch holds fewer than 16 n bytes");
+  // a reward input-gradient block of the bound context (mfg_ctx_set_rn_input_grad) rides on this call: checked here, before
+  // anything is launched; its launches go behind the reward launch
+  const mfg_rn_input_grad_t* rig = bound_rn_input_grad();
+  if (rig) {
+    const int rc = rn_input_grad_check(*rig, K, N, d);
+    if (rc != MFG_OK) return rc;
+  }
   if (n == 0 || N == 0) return MFG_OK;
   // keys [n] uint64 | learners [n] int32, uploaded once; the host copy dies with this frame, so the stream is drained first
   std::vector<unsigned char> up((size_t)n * 12);
@@ -1522,7 +1530,16 @@ extern "C" int mfg_reward_net_forward_pop(const float* state, const float* actio
   rp.learner = (const int32_t*)((const char*)scratch + (size_t)n * 8);
   rp.n_y = n;
   rp.geom = geom_dev;
-  return reward_net_forward_sums(state, action, N, d, *net, 0, sample_offset, reward, nullptr, nullptr, st, 0, &rp);
+  const int rc = reward_net_forward_sums(state, action, N, d, *net, 0, sample_offset, reward, nullptr, nullptr, st, 0, &rp);
+  if (rc != MFG_OK || !rig) return rc;
+  RnGradCall gc{};
+  gc.state = state; gc.action = action;
+  gc.s_state = s_state; gc.s_action = s_action; gc.N = N;
+  gc.d = d; gc.K = K; gc.n = n;
+  gc.net = *net;
+  gc.per_learner_net = rp.per_learner_net; gc.s_net = rp.s_net; gc.geom = geom_dev;
+  gc.key = rp.key; gc.learner = rp.learner; gc.sample_offset = sample_offset;
+  return launch_rn_input_grad(*rig, gc, st);
 }
 
 #ifdef MFG_RN_STAMPS

@@ -666,6 +666,140 @@ class AC_IRLPopulation(_Population):
         gen_avg[failed] = np.nan
         return demo_avg, gen_avg, np.abs(demo_avg[None] - gen_avg)
 
+    def _sub_population(self, first, count, dropout):
+        """(net struct, geometry table) of the learners [first, first + count) as a population of their own: the struct's
+        pointers moved to row `first` of the flat buffer, the table's rows sliced.  dropout=False: keep_prob = 1 in a COPY
+        of the struct / the table (no learner's network changes)."""
+        import ctypes as C
+        st = L.RewardNetStruct.from_buffer_copy(self._net_struct)
+        shift = 4 * self._net_stride * first
+        for field, _ in NET_TENSORS:
+            setattr(st, field, getattr(st, field) + shift)
+        geom = self._geom
+        if geom is not None:
+            host, dev = geom
+            host = host[first:first + count].copy()
+            if not dropout:
+                host['keep_prob'] = 1.0
+                dev = torch.from_numpy(host.view(np.uint8).copy()).to(self.device)
+            else:
+                dev = dev[16 * first:16 * (first + count)]
+            geom = (host, dev)
+        elif not dropout:
+            st.keep_prob = 1.0
+        return st, geom
+
+    def _forward_input_grad(self, st, ac, active, keys, reward, bufs, dropout, budget, cache):
+        """_forward with a reward input-gradient block bound (ops.reward_input_grad_pop), the learners in chunks whose
+        workspace stays within `budget` bytes (population.consistency_chunks; None: its default).  cache: a dict that lives
+        as long as one reward_sensitivity call -- the chunks' structs / tables and ONE workspace, grown to the largest need."""
+        from .population import consistency_chunks
+        K, d = self.K, self.d
+        N = int(st.shape[-2])
+        if self._fw_scratch is None:
+            self._fw_scratch = torch.empty(2 * K, dtype=torch.float64, device=self.device)
+        key_of = dict(zip(active, keys))
+        for first, count in consistency_chunks(K, ops.rn_input_grad_workspace_bytes(1, N, d), budget):
+            mine = [k for k in active if first <= k < first + count]
+            if not mine:
+                continue
+            if (first, count) not in cache:
+                cache[first, count] = self._sub_population(first, count, dropout)
+            struct, geom = cache[first, count]
+            need = ops.rn_input_grad_workspace_bytes(count, N, d)
+            if cache.get('ws') is None or cache['ws'].numel() * 8 < need:
+                cache['ws'] = torch.empty((need + 7) // 8, dtype=torch.float64, device=self.device)
+            cut = (lambda t: t) if st.dim() == 2 else (lambda t: t[first:first + count])
+            ops.reward_input_grad_pop(struct, True, count, cut(st), cut(ac), [k - first for k in mine], [key_of[k] for k in mine],
+                                      out=reward[first:first + count], net_stride=self._net_stride, scratch=self._fw_scratch,
+                                      geom=geom, want=tuple(bufs), bufs={n: t[first:first + count] for n, t in bufs.items()},
+                                      workspace=cache['ws'])
+
+    @_with_ctx
+    def reward_sensitivity(self, *, thetas=None, pi0_test=None, dropout=False, want_samples=False, budget=None):
+        """What the learned rewards reward, locally: the derivative of every learner's reward with respect to its inputs, d r /
+        d pi [d] and d r / d P [d,d], on every transition of the four sets of reward_distribution (training demonstrations,
+        test demonstrations, len(demonstrations) trajectories generated from the train start table and as many from
+        `pi0_test`), averaged per set on the device, next to the mean of gradient x input.  Returns a
+        reward_dist.RewardSensitivity (leading K).  The same two generations and one population forward per set as
+        reward_distribution, each forward with a reward input-gradient block bound (include/mfg_hip.h,
+        mfg_ctx_set_rn_input_grad); ONE host read for the means.
+        dropout=False evaluates every network with keep_prob = 1 (through a copy of the geometry table / the struct: no
+        learner's network changes); dropout=True with the learners' own keep_prob under the calls' keys.  Either way the
+        Philox step, the trajectory counter and the reward-call counters advance exactly as reward_distribution advances them
+        for the same sets.  thetas: for the two generations only, no theta changes; D_samp is not touched.  want_samples: the
+        per-sample gradients too.  budget: bytes of workspace of one call; more learners go in chunks (None:
+        population.CONSISTENCY_BUDGET).  A missing set is NaN with status -1; failed learners give NaN rows."""
+        from . import reward_dist
+        if not self.per_learner_net:
+            raise ValueError('reward_sensitivity needs one reward network per learner')
+        if self._demo_np is None:
+            raise ValueError('reward_sensitivity needs demonstrations (constructor argument demonstrations=...)')
+        from .population import consistency_chunks
+        K, T, d = self.K, EPISODE_STEPS, self.d
+        num_demos = len(self._demo_store)
+        th = self._given_thetas(thetas)
+        test_table = None
+        if pi0_test is not None:
+            test_table = torch.as_tensor(np.ascontiguousarray(np.asarray(pi0_test, dtype=np.float64)[:, :d], dtype=np.float32),
+                                         device=self.device)
+        active = self._healthy()
+        inputs = [self._demo_store.gather_flat(), None, None, None]
+        if self._test_np is not None:
+            if self._test_dev is None:
+                self._test_dev = (torch.from_numpy(self._test_np[0]).reshape(-1, d).contiguous().to(self.device),
+                                  torch.from_numpy(self._test_np[1]).reshape(-1, d, d).contiguous().to(self.device))
+            inputs[1] = self._test_dev
+        for n in {num_demos * T} | ({int(inputs[1][0].shape[0])} if inputs[1] is not None else set()):
+            consistency_chunks(K, ops.rn_input_grad_workspace_bytes(1, n, d), budget)     # (refused before anything runs)
+        for s, table in ((2, self._mat_pi0_dev), (3, test_table)):
+            if table is None:
+                continue
+            st, ac = self._generate(num_demos, mat_dev=table, theta=th)
+            inputs[s] = (st[:, :, :T].reshape(K, num_demos * T, d).contiguous(), ac.reshape(K, num_demos * T, d, d))
+
+        cache = {}
+
+        def run(s, st, ac, reward, bufs):
+            self._calls_k[active] += 1
+            keys = [philox_call_key(self.seeds[k], RN_SEED_OFFSET, self._calls_k[k]) for k in active]
+            self._forward_input_grad(st, ac, active, keys, reward, bufs, dropout, budget, cache)
+        return reward_dist.sensitivity(inputs, K, d, active, self.device, run, want_samples)
+
+    @_with_ctx
+    def reward_heatmap(self, *, theta=8.64, states=None, actions=None):
+        """The numbers of plot_reward_heatmap (ac_irl.py:1378-1443) for every learner: the reward of three prototype states x
+        three prototype actions.  Returns (rewards [K,3,3] fp32, rewards[k,i,j] = r_k(state i, action j); states [3,d];
+        actions [K,3,d,d]).  Default states: the first row of the start table; weight 2^(d-i) on topic i, normalised in fp32;
+        uniform.  Default actions: action 1 of learner k is the first action of ONE trajectory generated from the one-row
+        start table [state 2] under (theta, shift_k, alpha_scale_k) -- mass moves to more popular topics; the Philox step
+        advances by 15 and the trajectory counter by 1 --, action 2 is uniform, action 3 is action 1 with every row reversed.
+        The nine pairs of every learner go through ONE population forward, dropout as the learner's network has it (the
+        reference's quirk); the reward-call counters advance by one.  Unlike the reference, no learner's theta is assigned.
+        states [3,d] / actions [3,d,d] or [K,3,d,d]: given ones; given actions skip the generation.  Failed learners: NaN."""
+        from . import reward_dist
+        if not self.per_learner_net:
+            raise ValueError('reward_heatmap needs one reward network per learner')
+        K, d = self.K, self.d
+        active = self._healthy()
+        protos = reward_dist.heatmap_states(self.mat_pi0, d)
+        if states is None:
+            states = protos
+        if actions is None:
+            table = torch.as_tensor(protos[1:2].copy(), device=self.device)
+            _, ac = self._generate(1, mat_dev=table, theta=self._given_thetas(theta))
+            actions = reward_dist.heatmap_actions(ac[:, 0, 0].cpu().numpy())
+        st9, ac9, states, actions = reward_dist.heatmap_pairs(states, actions, K, d)
+        out = self._nan_rows(active, 9)
+        if active:
+            self._calls_k[active] += 1
+            keys = [philox_call_key(self.seeds[k], RN_SEED_OFFSET, self._calls_k[k]) for k in active]
+            self._forward(torch.as_tensor(st9, device=self.device), torch.as_tensor(ac9, device=self.device), active, keys, out=out)
+        failed = [k for k in range(K) if k not in active]
+        actions = actions.copy()
+        actions[failed] = np.nan
+        return out.cpu().numpy().reshape(K, 3, 3), states, actions
+
     def _generate(self, n, mat_dev=None, theta=None):
         """AC_IRL._generate_device(n) of every learner (its seed, theta, shift, alpha_scale; shared Philox step and
         trajectory ids): K draw + rollout launch pairs.  Returns (pi_traj [K,n,16,d], P [K,n,15,d,d]).  mat_dev: another

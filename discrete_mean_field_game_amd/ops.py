@@ -917,6 +917,128 @@ def reward_net_forward_pop(net_struct, per_learner_net, K, state, action, learne
     return out
 
 
+RN_INPUT_GRAD_OUTPUTS = ('grad_state', 'grad_action', 'mean_state', 'mean_action')
+
+
+def check_reward_input_grad_args(K, state_shape, action_shape, learners, n_keys, want):
+    """The argument check of reward_input_grad_pop (needs no GPU): returns (shared, N, d).  state [N,d] / action [N,d,d] shared by
+    every learner, or [K,N,d] / [K,N,d,d]; d = 15 / 21; distinct learners in [0, K), one key each; `want` a non-empty subset of
+    RN_INPUT_GRAD_OUTPUTS."""
+    if not 1 <= int(K) <= L.POP_MAX_K:
+        raise ValueError('population size %d outside [1, %d]' % (K, L.POP_MAX_K))
+    state_shape, action_shape = tuple(state_shape), tuple(action_shape)
+    shared = len(state_shape) == 2
+    if shared:
+        N, d = state_shape
+        if action_shape != (N, d, d):
+            raise ValueError('action: expected [%d, %d, %d], got %s' % (N, d, d, list(action_shape)))
+    else:
+        if len(state_shape) != 3 or state_shape[0] != K:
+            raise ValueError('state: expected [N, d] or [%d, N, d], got %s' % (K, list(state_shape)))
+        _, N, d = state_shape
+        if action_shape != (K, N, d, d):
+            raise ValueError('action: expected [%d, %d, %d, %d], got %s' % (K, N, d, d, list(action_shape)))
+    if d not in IRL_POP_D:
+        raise ValueError('d=%d: the reward input gradient covers d = 15 / 21 (the matrix-core reward-network geometry)' % d)
+    if N < 1:
+        raise ValueError('no samples (N < 1)')
+    if N >= 1 << 31:
+        raise ValueError('N=%d >= 2^31' % N)
+    ids = [int(k) for k in learners]
+    if any(not 0 <= k < K for k in ids):
+        raise ValueError('learner id outside [0, %d)' % K)
+    if len(set(ids)) != len(ids):
+        raise ValueError('a learner twice in the list')
+    if n_keys != len(ids):
+        raise ValueError('one key per listed learner')
+    want = tuple(want)
+    if not want or any(w not in RN_INPUT_GRAD_OUTPUTS for w in want) or len(set(want)) != len(want):
+        raise ValueError('want: a non-empty subset of %s, got %s' % (RN_INPUT_GRAD_OUTPUTS, want))
+    return shared, int(N), int(d)
+
+
+def rn_input_grad_workspace_bytes(K, N, d):
+    """mfg_rn_input_grad_workspace_bytes: bytes of the workspace of a reward input-gradient block."""
+    return int(L.lib().mfg_rn_input_grad_workspace_bytes(int(K), int(N), int(d)))
+
+
+def _rn_input_grad_shape(name, K, N, d):
+    return {'grad_state': (K, N, d), 'grad_action': (K, N, d, d), 'mean_state': (K, 2, d), 'mean_action': (K, 2, d, d)}[name]
+
+
+def reward_input_grad_pop(net_struct, per_learner_net, K, state, action, learners, keys, out=None, net_stride=0, scratch=None,
+                          geom=None, want_samples=False, *, want=None, bufs=None, workspace=None, workspace_bytes=None,
+                          ctx=None):
+    """reward_net_forward_pop with a reward input-gradient block (mfg_rn_input_grad_t) bound for this call only: the rewards
+    and, for the listed learners, d r / d state and d r / d action on every sample and their means (include/mfg_hip.h).  The
+    arguments of reward_net_forward_pop; per-learner inputs [K,N,d] / [K,N,d,d] may be views whose learner stride is larger
+    than needed.  Returns a dict: reward [K,N] f32, mean_state [K,2,d] / mean_action [K,2,d,d] f64 ([k,0] the mean gradient,
+    [k,1] the mean of gradient x input) and, with want_samples, grad_state [K,N,d] / grad_action [K,N,d,d] f32.  Rows of
+    learners not in the list are left alone (fresh outputs: NaN).  want: the outputs of the block instead (a subset of
+    RN_INPUT_GRAD_OUTPUTS); bufs: tensors to write into, by name; workspace (device tensor) / workspace_bytes: what the block
+    announces; ctx: the Context that carries the block (default: the bound one, or one made for the call)."""
+    import ctypes as C
+    import numpy as np
+    if want is None:
+        want = ('mean_state', 'mean_action') + (('grad_state', 'grad_action') if want_samples else ())
+    lr = np.ascontiguousarray(learners, dtype=np.int32).reshape(-1)
+    ky = np.array([int(k) & 0xFFFFFFFFFFFFFFFF for k in keys], dtype=np.uint64).reshape(-1)
+    shared, N, d = check_reward_input_grad_args(K, state.shape, action.shape, lr.tolist(), ky.size, want)
+    for name, t in (('state', state), ('action', action)):
+        inner = t if shared else t[0]
+        if not (t.is_cuda and t.dtype == torch.float32 and inner.is_contiguous()):
+            raise ValueError('%s must be a float32 CUDA tensor, contiguous within a learner' % name)
+    s_state = 0 if shared else int(state.stride(0))
+    s_action = 0 if shared else int(action.stride(0))
+    if not shared and K > 1 and (s_state < N * d or s_action < N * d * d):
+        raise ValueError('per-learner inputs overlap')
+    if K == 1 and not shared:
+        s_state, s_action = N * d, N * d * d
+    dev = state.device
+    if out is None:
+        out = torch.empty(K, N, dtype=torch.float32, device=dev)
+    elif tuple(out.shape) != (K, N):
+        raise ValueError('out: expected [%d, %d]' % (K, N))
+    _chk_f32(out, 'out')
+    if scratch is None:
+        scratch = torch.empty(max(2 * lr.size, 2), dtype=torch.float64, device=dev)
+    res = {'reward': out}
+    for name in want:
+        shape, dt = _rn_input_grad_shape(name, K, N, d), (torch.float32 if name.startswith('grad') else torch.float64)
+        t = bufs.get(name) if bufs else None
+        if t is None:
+            t = torch.full(shape, float('nan'), dtype=dt, device=dev)
+        elif tuple(t.shape) != shape or t.dtype != dt or not t.is_cuda or not t.is_contiguous():
+            raise ValueError('%s: expected a contiguous %s device tensor %s' % (name, dt, list(shape)))
+        res[name] = t
+    if workspace is None:
+        workspace = torch.empty(max(rn_input_grad_workspace_bytes(K, N, d) // 8, 1), dtype=torch.float64, device=dev)
+    if workspace_bytes is None:
+        workspace_bytes = workspace.numel() * workspace.element_size()
+    blk = L.RnInputGradStruct(_ptr(res.get('grad_state')), _ptr(res.get('grad_action')), _ptr(res.get('mean_state')),
+                              _ptr(res.get('mean_action')), workspace.data_ptr(), int(workspace_bytes), N, int(K), d, 0)
+    lib = L.lib()
+    tmp = None
+    if ctx is None and lib.mfg_ctx_current() is None:
+        ctx = tmp = Context(dev)
+    prev = ctx.bind_scoped() if ctx is not None else Context.KEEP
+    ptr = lib.mfg_ctx_current()
+    try:
+        L.check(lib.mfg_ctx_set_rn_input_grad(ptr, C.byref(blk)), 'mfg_ctx_set_rn_input_grad')
+        try:
+            L.check(lib.mfg_reward_net_forward_pop(
+                state.data_ptr(), action.data_ptr(), s_state, s_action, N, d, C.byref(net_struct), int(bool(per_learner_net)),
+                int(net_stride), *_geom_ptrs(geom, K), int(K), lr.ctypes.data, ky.ctypes.data, int(lr.size), 0, out.data_ptr(),
+                scratch.data_ptr(), scratch.numel() * scratch.element_size(), _stream()), 'mfg_reward_net_forward_pop')
+        finally:
+            lib.mfg_ctx_set_rn_input_grad(ptr, None)
+    finally:
+        Context.restore(prev)
+        if tmp is not None:
+            tmp.close()
+    return res
+
+
 RN_TRAIN_PLAN = None     # numpy dtype of mfg_rn_train_plan_t (L.RnTrainPlan)
 
 

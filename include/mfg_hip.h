@@ -1044,6 +1044,47 @@ int mfg_reward_net_forward_pop(const float* state, const float* action, int64_t 
                                const int32_t* learners_host, const uint64_t* keys_host, int n, uint64_t sample_offset,
                                float* reward, void* scratch, size_t scratch_bytes, mfg_stream_t stream);
 
+/* Input gradients of the reward network ("reward sensitivities": what the learned reward rewards, locally, on given
+ * transitions).  A block bound to the context (mfg_ctx_set_rn_input_grad; NULL unbinds; no device work, no stream) rides on
+ * mfg_reward_net_forward_pop: with the context bound, that call enqueues, behind its reward launch and on its stream, the
+ * gradient launch and the two launches of the means, for the learners of ITS list with their weights, geometry-table rows and
+ * keys.  Every other call ignores the block; without one mfg_reward_net_forward_pop issues the launches it always did, and
+ * with one its `reward` is bit for bit what it is without.
+ *   Per sample n of learner k, for r = tanh(.) as mfg_reward_net_forward documents it (networks.py:46-81):
+ *     grad_state [K,N,d] fp32    d r / d state, the state as it enters FC4 (the concatenation of networks.py:72)
+ *     grad_action [K,N,d,d] fp32 d r / d action, the [d,d] image that enters the first convolution
+ *   A ReLU passes the derivative where its pre-activation is > 0 and blocks it at 0.  With keep_prob < 1 the masks are the
+ *   forward's own -- key keys_host[s], counter (unit, 3 | 4, sample_offset + n, 0) -- and a kept unit carries 1 / keep_prob
+ *   in the backward pass as well.  fp32 like the forward; the sample's forward is recomputed by the gradient kernel (one
+ *   256-thread block per (sample, list slot), every activation in LDS), so `reward` does not depend on it.
+ *   Means over n, fp64:
+ *     mean_state [K,2,d], mean_action [K,2,d,d]:  [k,0] = mean of the gradient, [k,1] = mean of gradient x input, each product
+ *     formed in fp64 from the two fp32 values (exact).
+ *   No floating-point atomics: chunk c of mfg_action_mean_pop's chunking of N is added in ascending n by one thread per
+ *   element, a learner's chunk totals are added in chunk order by one thread per element and divided by N -- an order that
+ *   depends on N alone, not on K, the list, or which outputs are requested; the means are the same bits with and without
+ *   the per-sample arrays.
+ *   Any of the four outputs may be NULL (not all); rows of learners not in the list are left alone in all four.  A per-sample
+ *   array that is NULL lives in `workspace` (mfg_rn_input_grad_workspace_bytes(K, N, d) bytes, 8-byte aligned, contents
+ *   scratch: the per-sample arrays [K,N,d + d d] fp32 and the chunk totals [K,chunks,2,d + d d] fp64).
+ * Checked when the block is set: MFG_EINVAL for a null or destroyed context, all four outputs NULL, K outside
+ * [1, MFG_POP_MAX_K], N < 1, a workspace that is not 8-byte aligned.  Checked again before the call launches anything (nothing
+ * is written on refusal): MFG_EINVAL when K, N or d differ from the call's; MFG_EUNSUPPORTED for N >= 2^31; MFG_EWORKSPACE
+ * when workspace is NULL or workspace_bytes is too small.  The geometry is the call's (d = 15 / 21, k1 = 5, f2 = 2, k2 = 3,
+ * n_fc3 <= 16, n_fc4 <= 32, the optional table included). */
+typedef struct mfg_rn_input_grad {
+  float* grad_state;    /* [K, N, d]     d r / d state,  per sample; may be NULL */
+  float* grad_action;   /* [K, N, d, d]  d r / d action, per sample; may be NULL */
+  double* mean_state;   /* [K, 2, d]     may be NULL */
+  double* mean_action;  /* [K, 2, d, d]  may be NULL */
+  void* workspace;
+  size_t workspace_bytes;
+  int64_t N;
+  int32_t K, d, reserved;
+} mfg_rn_input_grad_t;
+size_t mfg_rn_input_grad_workspace_bytes(int K, int64_t N, int d);
+int mfg_ctx_set_rn_input_grad(mfg_ctx_t* ctx, const mfg_rn_input_grad_t* block);
+
 /* One entry of the plan of mfg_reward_net_train_steps_pop: one update_reward of one learner. */
 typedef struct mfg_rn_train_plan {
   int32_t learner;    /* in [0, K), once per update */
