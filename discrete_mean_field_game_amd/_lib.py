@@ -264,6 +264,28 @@ class RnInputGradStruct(C.Structure):
 SIGNATURES['mfg_rn_input_grad_workspace_bytes'] = (_sz, [_i32, _i64, _i32])
 SIGNATURES['mfg_ctx_set_rn_input_grad'] = (_i32, [_p, C.POINTER(RnInputGradStruct)])
 
+VAR_MAX_REGRESSORS = 512        # MFG_VAR_MAX_REGRESSORS: 1 + lag d of one model of mfg_var_fit_pop
+VAR_MAX_D, VAR_MAX_HOURS, VAR_MAX_DAYS = 64, 64, 64     # its limits on d, Hd and the training / test days of one model
+VAR_NONFINITE, VAR_PIVOT = 1, 2                         # MFG_VAR_NONFINITE / MFG_VAR_PIVOT: bits of a model's status
+
+
+class VarModelStruct(C.Structure):
+    """mfg_var_model_t of include/mfg_hip.h: one model of mfg_var_fit_pop (32 bytes)."""
+    _fields_ = ([(n, C.c_int32) for n in ('lag', 'origin', 'n_train', 'n_test')]
+                + [('ridge', C.c_double), ('ws_offset', C.c_int64)])
+
+
+class VarFitStruct(C.Structure):
+    """mfg_var_fit_t of include/mfg_hip.h: the descriptor of one mfg_var_fit_pop call; the stream is a member."""
+    _fields_ = ([(n, C.c_void_p) for n in ('days', 'models_host', 'models', 'train_idx', 'test_idx', 'coef', 'sse', 'insample',
+                                           'future', 'per_day', 'metrics', 'status', 'workspace')]
+                + [('workspace_bytes', C.c_size_t), ('stream', C.c_void_p)]
+                + [(n, C.c_int32) for n in ('D', 'Hd', 'd', 'K', 'train_stride', 'test_stride', 'M', 'S_max')])
+
+
+SIGNATURES['mfg_var_fit_workspace_bytes'] = (_sz, [_i32, C.POINTER(VarModelStruct), _i32])
+SIGNATURES['mfg_var_fit_pop'] = (_i32, [C.POINTER(VarFitStruct)])
+
 _lib = None
 
 

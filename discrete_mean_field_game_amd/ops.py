@@ -1594,6 +1594,154 @@ def consistency_pop(start32, thetas, shifts, alpha_scales, seeds, hours, *, firs
     return out
 
 
+def check_var_fit_args(days_shape, lags, ridges, train_n, test_n, origins, train_stride=None, test_stride=None):
+    """The argument rules of var_fit_pop that need no GPU (ValueError), the limits of mfg_var_fit_pop: days [D, Hd, d] with
+    1 <= Hd <= 64 and 1 <= d <= 64; per model a lag >= 1 with m = 1 + lag d <= VAR_MAX_REGRESSORS, 1 to 64 training and 0 to 64
+    test days (within the index tables' strides when given), n = n_train Hd - lag >= 1, origin 0 or 1 and with origin 1
+    lag <= n_train Hd + 1, a ridge that is finite and > 0.  Returns (K, D, Hd, d, M, S_max): M the largest m, S_max the largest
+    n_test Hd."""
+    import math
+    if len(days_shape) != 3:
+        raise ValueError('days: expected [D, Hd, d], got %s' % (tuple(days_shape),))
+    D, Hd, d = (int(s) for s in days_shape)
+    if D < 1:
+        raise ValueError('days: no day')
+    if not 1 <= Hd <= L.VAR_MAX_HOURS:
+        raise ValueError('Hd=%d: a day has 1 to %d rows' % (Hd, L.VAR_MAX_HOURS))
+    if not 1 <= d <= L.VAR_MAX_D:
+        raise ValueError('d=%d: the VAR population covers 1 <= d <= %d' % (d, L.VAR_MAX_D))
+    cols = [list(lags), list(ridges), list(train_n), list(test_n), list(origins)]
+    K = len(cols[0])
+    if K < 1:
+        raise ValueError('no models')
+    if K > L.POP_MAX_K:
+        raise ValueError('%d models: at most %d in one call (MFG_POP_MAX_K)' % (K, L.POP_MAX_K))
+    if any(len(c) != K for c in cols):
+        raise ValueError('lags, ridges, train_n, test_n and origins must have one entry per model (%d)' % K)
+    M = S_max = 0
+    for k, (p, lam, ntr, nte, org) in enumerate(zip(*cols)):
+        p, ntr, nte, lam = int(p), int(ntr), int(nte), float(lam)
+        if p < 1:
+            raise ValueError('model %d: lag=%d < 1' % (k, p))
+        if 1 + p * d > L.VAR_MAX_REGRESSORS:
+            raise ValueError('model %d: 1 + lag d = %d regressors, at most %d (MFG_VAR_MAX_REGRESSORS)'
+                             % (k, 1 + p * d, L.VAR_MAX_REGRESSORS))
+        if not 1 <= ntr <= L.VAR_MAX_DAYS or (train_stride is not None and ntr > train_stride):
+            raise ValueError('model %d: %d training days, a model has 1 to %d (and train_idx holds them)' % (k, ntr, L.VAR_MAX_DAYS))
+        if not 0 <= nte <= L.VAR_MAX_DAYS or (test_stride is not None and nte > test_stride):
+            raise ValueError('model %d: %d test days, a model has 0 to %d (and test_idx holds them)' % (k, nte, L.VAR_MAX_DAYS))
+        if ntr * Hd - p < 1:
+            raise ValueError('model %d: lag=%d leaves no row to fit of %d training rows' % (k, p, ntr * Hd))
+        if org not in (0, 1):
+            raise ValueError('model %d: origin=%r, 0 (the end of the training series) or 1 (rolling)' % (k, org))
+        if int(org) == 1 and p > ntr * Hd + 1:
+            raise ValueError('model %d: a rolling origin needs lag <= training rows + 1' % k)
+        if not (lam > 0.0 and math.isfinite(lam)):
+            raise ValueError('model %d: ridge=%r must be finite and > 0' % (k, lam))
+        M, S_max = max(M, 1 + p * d), max(S_max, nte * Hd)
+    return K, D, Hd, d, M, S_max
+
+
+def var_models(lags, ridges, train_n, test_n, origins, d):
+    """The host table of mfg_var_fit_pop: (an array of K _lib.VarModelStruct with ws_offset laid out by
+    mfg_var_fit_workspace_bytes, the workspace bytes of the call).  Needs the library, no GPU."""
+    K = len(lags)
+    table = (L.VarModelStruct * K)()
+    for k in range(K):
+        table[k].lag, table[k].origin, table[k].n_train, table[k].n_test = int(lags[k]), int(origins[k]), int(train_n[k]), int(test_n[k])
+        table[k].ridge = float(ridges[k])
+    nbytes = int(L.lib().mfg_var_fit_workspace_bytes(K, table, int(d)))
+    if nbytes == 0:
+        raise ValueError('var_models: a lag outside [1, (MFG_VAR_MAX_REGRESSORS - 1) / d] or d outside [1, 64]')
+    return table, nbytes
+
+
+def var_models_device(table, device):
+    """The device copy of a var_models table (a uint8 tensor of 32 K bytes)."""
+    import ctypes as C
+    import numpy as np
+    raw = np.frombuffer(C.string_at(C.addressof(table), C.sizeof(table)), dtype=np.uint8).copy()
+    return torch.as_tensor(raw).to(device)
+
+
+VAR_OUTPUTS = ('coef', 'sse', 'insample', 'future', 'per_day', 'metrics', 'status')
+
+
+def var_fit_shapes(K, d, M, S_max, test_stride):
+    """name -> (shape, dtype) of the outputs of var_fit_pop."""
+    f64 = torch.float64
+    return {'coef': ((K, M, d), f64), 'sse': ((K, d), f64), 'insample': ((K, 2), f64), 'future': ((K, S_max, d), f64),
+            'per_day': ((K, test_stride, 4), f64), 'metrics': ((K, 8), f64), 'status': ((K,), torch.int32)}
+
+
+def var_fit_pop(days, lags, ridges, train_idx, train_n, test_idx, test_n, origins, *, want_future=True, want_per_day=True,
+                out=None, workspace=None, models=None, M=None, S_max=None):
+    """K vector autoregressions fitted, forecast and scored in the three launches of one call (mfg_var_fit_pop; the definitions
+    are in include/mfg_hip.h).  days [D, Hd, d] fp64 on the device; lags, ridges, train_n, test_n, origins: K host values each
+    (sequences or CPU tensors); train_idx [K, >= max train_n] and test_idx [K, >= max test_n] int32 device tensors of day indices
+    (test_idx may be None when no model has a test day).  The fit is RIDGE regression of order lag (no information criterion
+    picks a smaller order).  Returns a dict of device tensors: coef [K, M, d], sse [K, d], insample [K, 2], future [K, S_max, d]
+    (None without want_future), per_day [K, test_stride, 4] (None without want_per_day), metrics [K, 8], status [K] int32.
+    out / workspace / models: preallocated outputs (a dict by name), the scratch buffer and the (host table, device copy,
+    bytes) of var_models / var_models_device -- then the call allocates nothing.  M / S_max: rows of coef / future per model
+    when more than this call's models need (a chunk of a larger population)."""
+    import ctypes as C
+    M_want, S_want = M, S_max
+    _chk_f64(days, 'days')
+    as_list = lambda x: x.tolist() if hasattr(x, 'tolist') else list(x)
+    lags, ridges, train_n, test_n, origins = (as_list(x) for x in (lags, ridges, train_n, test_n, origins))
+    train_idx = _chk_i32(train_idx, 'train_idx')
+    if train_idx.dim() != 2:
+        raise ValueError('train_idx: expected [K, days], got %s' % (tuple(train_idx.shape),))
+    test_stride = 0
+    if test_idx is not None:
+        test_idx = _chk_i32(test_idx, 'test_idx')
+        if test_idx.dim() != 2:
+            raise ValueError('test_idx: expected [K, days], got %s' % (tuple(test_idx.shape),))
+        test_stride = int(test_idx.shape[1])
+    K, D, Hd, d, M, S_max = check_var_fit_args(days.shape, lags, ridges, train_n, test_n, origins, int(train_idx.shape[1]),
+                                               test_stride)
+    if int(train_idx.shape[0]) != K or (test_idx is not None and int(test_idx.shape[0]) != K):
+        raise ValueError('train_idx / test_idx: one row per model (%d)' % K)
+    if M_want is not None:
+        if not M <= int(M_want) <= L.VAR_MAX_REGRESSORS:
+            raise ValueError('M=%d: the models need %d rows, at most %d' % (M_want, M, L.VAR_MAX_REGRESSORS))
+        M = int(M_want)
+    if S_want is not None:
+        if int(S_want) < S_max:
+            raise ValueError('S_max=%d: the models forecast up to %d rows' % (S_want, S_max))
+        S_max = int(S_want)
+    dev = days.device
+    if models is None:
+        table, nbytes = var_models(lags, ridges, train_n, test_n, origins, d)
+        models = (table, var_models_device(table, dev), nbytes)
+    table, table_dev, nbytes = models
+    if workspace is None:
+        workspace = torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=dev)
+    shapes = var_fit_shapes(K, d, M, S_max, test_stride)
+    res = {}
+    for name in VAR_OUTPUTS:
+        if (name == 'future' and not want_future) or (name == 'per_day' and not want_per_day):
+            res[name] = None
+        elif out is not None and name in out:
+            t = out[name]
+            if tuple(t.shape) != shapes[name][0] or t.dtype != shapes[name][1] or not t.is_cuda or not t.is_contiguous():
+                raise ValueError('out[%r]: expected a contiguous %s %s device tensor' % (name, shapes[name][0], shapes[name][1]))
+            res[name] = t
+        else:
+            res[name] = torch.empty(shapes[name][0], dtype=shapes[name][1], device=dev)
+    fit = L.VarFitStruct()
+    fit.days, fit.models_host, fit.models = days.data_ptr(), C.addressof(table), table_dev.data_ptr()
+    fit.train_idx, fit.test_idx = train_idx.data_ptr(), _ptr(test_idx)
+    for name in VAR_OUTPUTS:
+        setattr(fit, name, _ptr(res[name]))
+    fit.workspace, fit.workspace_bytes = workspace.data_ptr(), workspace.numel() * workspace.element_size()
+    fit.stream = _stream()
+    fit.D, fit.Hd, fit.d, fit.K, fit.train_stride, fit.test_stride, fit.M, fit.S_max = D, Hd, d, K, int(train_idx.shape[1]), test_stride, M, S_max
+    L.check(L.lib().mfg_var_fit_pop(C.byref(fit)), 'mfg_var_fit_pop')
+    return res
+
+
 def policy_logpdf(pi, P, thetas, shift, alpha_scale=1.0, alpha_floor=0.0, p_floor=0.0):
     """log q_k(P_n | pi_n) [N,K] of the product-Dirichlet policy under K thetas (ac_irl.py:270-289, :324-379)."""
     _chk_f32(pi, 'pi'); _chk_f32(P, 'P'); _chk_f64(thetas, 'thetas')

@@ -1170,6 +1170,81 @@ int mfg_traj_log_z_pop(const float* state, const float* action, int64_t capacity
  * (mfg_ac2.py:546-563).  fp64 out. */
 int mfg_jsd(const float* p, const float* q, int64_t B, int d, double* out, mfg_stream_t stream);
 
+/* The VAR baseline as a population (the reference's var.py: train, forecast, validation, evaluate_train, evaluate_test and the
+ * 100 fits of cross_validation, :102-162, :195-416): K independent vector autoregressions, each with its own lag, ridge and
+ * days, fitted, forecast and scored in the three launches of one call.  fp64 throughout.
+ *   days [D, Hd, d] fp64: a table of day matrices.  Model k (models[k]) has a lag p >= 1, a ridge lambda > 0, an ordered list of
+ *   n_train training days train_idx[k train_stride + 0 ..] and of n_test >= 0 test days test_idx[k test_stride + 0 ..] (indices
+ *   into the table), and an origin, 0 or 1.
+ *   Series and regressors: Y is the training days concatenated in list order (lags run across day boundaries, var.py:129-141);
+ *   T = n_train Hd, n = T - p, m = 1 + p d; for t = p .. T-1, z_t = [1, y_{t-1}, ..., y_{t-p}]: regressor 0 is the constant,
+ *   regressor 1 + (l-1) d + j is topic j at lag l.
+ *   coef [K, M, d]: B = (Z'Z + lambda I)^-1 Z'Y in rows < m, zeros in rows >= m.  This is RIDGE regression, not the reference's
+ *   minimum-norm least squares (statsmodels): rows that sum to 1 make Z'Z singular for every shape, and lambda > 0 is what
+ *   factors by Cholesky; B tends to the minimum-norm solution as lambda -> 0.  No information criterion selects the order
+ *   (the residual covariance is exactly singular): the model of lag p has order p.
+ *   sse [K, d]: sum over t of the squared residual per topic.  insample [K, 2]: the mean over t of ||y_t - B'z_t||_1 and of
+ *   JSD(y_t, B'z_t) (evaluate_train part 2, var.py:229-241).  JSD as var.py:175-192: entries <= 0 become 1e-100, then
+ *   1/2 (KL(P||M) + KL(Q||M)), M = (P + Q)/2, every argument renormalised as scipy.stats.entropy does.
+ *   future [K, S_max, d] or NULL: the forecast of S = n_test Hd rows, zeros in rows >= S.  Origin 0 (var.py:258-327): one path
+ *   fed by the last p training rows and then by its own outputs.  Origin 1 (rolling): for test day j the history is the
+ *   training series, then test days 0 .. j-1, then hour 0 of day j; hours 1 .. Hd-1 are forecast from it and hour 0 of the
+ *   output is the observed row, bit for bit.  Row s is compared with row s of the concatenated test days:
+ *   per_day [K, test_stride, 4] or NULL: (l1_final, l1_mean, JSD_final, JSD_mean) per test day -- hour Hd-1 and the mean over the
+ *   Hd hours (evaluate_test, var.py:342-383); zeros in rows >= n_test.  metrics [K, 8]: mean and standard deviation (ddof 0) over
+ *   the test days of each of the four, in that order; NaN without a test day.
+ *   status [K] int32: bit 0 (MFG_VAR_NONFINITE) a non-finite value in the rows the model reads, or a day index outside [0, D);
+ *   bit 1 (MFG_VAR_PIVOT) a non-positive or non-finite Cholesky pivot (reported only without bit 0).  A model whose status is
+ *   not 0 returns NaN in all its float outputs; no other model is affected.
+ *   Order: G = Z'Z + lambda I and Z'Y are formed element by element, t ascending, fused multiply-add; a right-looking Cholesky
+ *   in 16-wide panels (the d right-hand sides ride along as d more rows; the trailing update subtracts a panel's 16 products in
+ *   column order), the back substitution panel by panel from the last; a dot product B'z is 16 strided partial sums (terms
+ *   i, i + 16, ... ascending) added in partial order; every mean is added in row, hour or day order by one thread.  So each
+ *   summation order is a function of the model's own shapes, there are no floating-point atomics, and a model's outputs are
+ *   the same bits whether it runs alone or among others, in any position.
+ *   models_host / models: the same K records on the host (read by the checks and for the launch geometry) and on the device
+ *   (read by the kernels).  ws_offset is the model's byte offset into the workspace: mfg_var_fit_workspace_bytes fills it in
+ *   the host records (each model gets 64 bytes + (m + d) m doubles, rounded up to 256 bytes) and returns the total, 0 for K < 1,
+ *   a null table or a record outside the limits.  The workspace is 8-byte aligned; its contents are scratch.
+ *   Everything is enqueued on fit->stream; the call neither allocates nor synchronises.
+ * Checked before anything is launched (MFG_EINVAL): a null struct or pointer (future and per_day may be null, the index tables
+ * when their stride is 0), 1 <= K <= MFG_POP_MAX_K, D >= 1, 1 <= Hd <= 64, 1 <= d <= 64; per model 1 <= n_train <= 64 and
+ * <= train_stride, 0 <= n_test <= 64 and <= test_stride, lag >= 1, m <= MFG_VAR_MAX_REGRESSORS and <= M, n >= 1, origin 0
+ * or 1 and with origin 1 lag <= T + 1, lambda finite and > 0, n_test Hd <= S_max when future is given, ws_offset as
+ * mfg_var_fit_workspace_bytes lays it out; MFG_EWORKSPACE when workspace_bytes is below that call's total. */
+#define MFG_VAR_MAX_REGRESSORS 512
+#define MFG_VAR_NONFINITE 1
+#define MFG_VAR_PIVOT 2
+typedef struct mfg_var_model {
+  int32_t lag, origin;
+  int32_t n_train, n_test;
+  double ridge;
+  int64_t ws_offset;
+} mfg_var_model_t; /* 32 bytes */
+typedef struct mfg_var_fit {
+  const double* days;
+  const mfg_var_model_t* models_host;
+  const mfg_var_model_t* models;
+  const int32_t* train_idx;
+  const int32_t* test_idx;
+  double* coef;
+  double* sse;
+  double* insample;
+  double* future;
+  double* per_day;
+  double* metrics;
+  int32_t* status;
+  void* workspace;
+  size_t workspace_bytes;
+  mfg_stream_t stream;
+  int32_t D, Hd;
+  int32_t d, K;
+  int32_t train_stride, test_stride;
+  int32_t M, S_max;
+} mfg_var_fit_t;
+size_t mfg_var_fit_workspace_bytes(int K, mfg_var_model_t* models_host, int d);
+int mfg_var_fit_pop(const mfg_var_fit_t* fit);
+
 #ifdef __cplusplus
 }
 #endif
