@@ -286,6 +286,30 @@ class VarFitStruct(C.Structure):
 SIGNATURES['mfg_var_fit_workspace_bytes'] = (_sz, [_i32, C.POINTER(VarModelStruct), _i32])
 SIGNATURES['mfg_var_fit_pop'] = (_i32, [C.POINTER(VarFitStruct)])
 
+RNN_MAX_D, RNN_MAX_HIDDEN, RNN_MAX_HOURS, RNN_MAX_DAYS = 64, 64, 64, 64     # the limits of one model of mfg_rnn_fit_pop
+RNN_MAX_EPOCHS = 65535                                  # MFG_RNN_MAX_EPOCHS
+RNN_ADAM, RNN_SGD = 0, 1                                # MFG_RNN_ADAM / MFG_RNN_SGD
+RNN_NONFINITE, RNN_DIVERGED = 1, 2                      # MFG_RNN_NONFINITE / MFG_RNN_DIVERGED: bits of a model's status
+
+
+class RnnModelStruct(C.Structure):
+    """mfg_rnn_model_t of include/mfg_hip.h: one model of mfg_rnn_fit_pop (56 bytes)."""
+    _fields_ = ([(n, C.c_int32) for n in ('hidden', 'epochs', 'n_train', 'n_val', 'n_test', 'reserved')]
+                + [(n, C.c_double) for n in ('lr', 'wd', 'clip')] + [('ws_offset', C.c_int64)])
+
+
+class RnnFitStruct(C.Structure):
+    """mfg_rnn_fit_t of include/mfg_hip.h: the descriptor of one mfg_rnn_fit_pop call; the stream is a member."""
+    _fields_ = ([(n, C.c_void_p) for n in ('days', 'models_host', 'models', 'train_idx', 'val_idx', 'test_idx', 'w0', 'weights',
+                                           'loss', 'val', 'best_epoch', 'future', 'per_day', 'metrics', 'status', 'workspace')]
+                + [('workspace_bytes', C.c_size_t), ('stream', C.c_void_p)]
+                + [(n, C.c_int32) for n in ('D', 'Hd', 'd', 'K', 'train_stride', 'val_stride', 'test_stride', 'W_max', 'E_max',
+                                            'C_max', 'optimizer', 'eval_every')])
+
+
+SIGNATURES['mfg_rnn_fit_workspace_bytes'] = (_sz, [_i32, C.POINTER(RnnModelStruct), _i32, _i32])
+SIGNATURES['mfg_rnn_fit_pop'] = (_i32, [C.POINTER(RnnFitStruct)])
+
 _lib = None
 
 

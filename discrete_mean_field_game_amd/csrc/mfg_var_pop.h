@@ -27,6 +27,33 @@ constexpr size_t VAR_HEAD_BYTES = 64;
 
 inline size_t var_model_bytes(int m, int d) { return (VAR_HEAD_BYTES + (size_t)(m + d) * (size_t)m * 8 + 255) / 256 * 256; }
 
+// ---- device functions shared with the RNN baseline (mfg_rnn_pop.hip): the day clamp and the L1 / JSD of one row
+// a day index is clamped into the table before it addresses anything: k_var_forecast reports the model, nothing is read outside
+__device__ __forceinline__ int var_day(int idx, int D) { return idx < 0 ? 0 : (idx >= D ? D - 1 : idx); }
+
+__device__ __forceinline__ double var_wave_sum(double x) {
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) x += __shfl_xor(x, off);
+  return x;
+}
+
+// one wave (k_var_forecast: wave 0; the RNN kernels: a row per wave): ||yo - yh||_1 and JSD(yo, yh) of one row (var.py:175-192), every sum an xor butterfly over the 64 lanes
+__device__ __forceinline__ void var_row_metrics(const double* yo, const double* yh, int d, double& l1, double& jsd) {
+  const int j = threadIdx.x & 63;
+  const bool on = j < d;
+  const double P = on ? yo[j] : 0.0, Q = on ? yh[j] : 0.0;
+  l1 = var_wave_sum(on ? fabs(P - Q) : 0.0);
+  const double Pf = on ? (P <= 0.0 ? 1e-100 : P) : 0.0, Qf = on ? (Q <= 0.0 ? 1e-100 : Q) : 0.0;
+  const double Mf = 0.5 * (Pf + Qf);
+  const double sP = var_wave_sum(Pf), sQ = var_wave_sum(Qf), sM = var_wave_sum(Mf);
+  double term = 0.0;
+  if (on) {
+    const double pk = Pf / sP, qk = Qf / sQ, mk = Mf / sM;
+    term = pk * log(pk / mk) + qk * log(qk / mk);
+  }
+  jsd = 0.5 * var_wave_sum(term);
+}
+
 // m_max: the largest regressor count of the K models (sizes the tile grid of k_var_gram)
 void launch_var_fit(const mfg_var_fit_t& f, int m_max, hipStream_t st);
 

@@ -32,9 +32,6 @@ __device__ __forceinline__ VarModel var_model(const mfg_var_fit_t& f, const mfg_
   return v;
 }
 
-// a day index is clamped into the table before it addresses anything: k_var_forecast reports the model, nothing is read outside
-__device__ __forceinline__ int var_day(int idx, int D) { return idx < 0 ? 0 : (idx >= D ? D - 1 : idx); }
-
 // row r of the model's extended series: the training days in list order, then the test days
 __device__ __forceinline__ const double* var_row(const mfg_var_fit_t& f, const VarModel& v, int r) {
   const int32_t* list = r < v.T ? v.tr : v.te;
@@ -175,12 +172,6 @@ __global__ __launch_bounds__(VAR_SOLVE_THREADS) void k_var_solve(mfg_var_fit_t f
   if (tid == 0) *reinterpret_cast<int32_t*>(v.slice) = fail;
 }
 
-__device__ __forceinline__ double var_wave_sum(double x) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) x += __shfl_xor(x, off);
-  return x;
-}
-
 // yh[j] = sum_i coef[i][j] z[i] for j < d: thread (q, j) adds the terms i = q, q + 16, ... in ascending order, thread (0, j) the 16
 // partial sums in order.  Ends behind a barrier.
 __device__ __forceinline__ void var_dot(const double* __restrict__ coef, const double* z, int m, int d,
@@ -198,23 +189,6 @@ __device__ __forceinline__ void var_dot(const double* __restrict__ coef, const d
     yh[j] = s;
   }
   __syncthreads();
-}
-
-// wave 0: ||yo - yh||_1 and JSD(yo, yh) of one row (var.py:175-192), every sum an xor butterfly over the 64 lanes
-__device__ __forceinline__ void var_row_metrics(const double* yo, const double* yh, int d, double& l1, double& jsd) {
-  const int j = threadIdx.x & 63;
-  const bool on = j < d;
-  const double P = on ? yo[j] : 0.0, Q = on ? yh[j] : 0.0;
-  l1 = var_wave_sum(on ? fabs(P - Q) : 0.0);
-  const double Pf = on ? (P <= 0.0 ? 1e-100 : P) : 0.0, Qf = on ? (Q <= 0.0 ? 1e-100 : Q) : 0.0;
-  const double Mf = 0.5 * (Pf + Qf);
-  const double sP = var_wave_sum(Pf), sQ = var_wave_sum(Qf), sM = var_wave_sum(Mf);
-  double term = 0.0;
-  if (on) {
-    const double pk = Pf / sP, qk = Qf / sQ, mk = Mf / sM;
-    term = pk * log(pk / mk) + qk * log(qk / mk);
-  }
-  jsd = 0.5 * var_wave_sum(term);
 }
 
 // ---- one workgroup, model blockIdx.x

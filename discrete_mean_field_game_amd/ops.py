@@ -1742,6 +1742,177 @@ def var_fit_pop(days, lags, ridges, train_idx, train_n, test_idx, test_n, origin
     return res
 
 
+RNN_OPTIMIZERS = {'adam': L.RNN_ADAM, 'sgd': L.RNN_SGD}
+
+
+def rnn_weight_count(H, d):
+    """W(H, d) = 4H (d + H + 1) + d (H + 1): the packed weights Wx [4H, d] | Wh [4H, H] | b [4H] | Wo [d, H] | bo [d]."""
+    return 4 * H * (d + H + 1) + d * (H + 1)
+
+
+def rnn_check_count(epochs, n_val, eval_every):
+    """The held-out checks of a model: after every eval_every-th epoch and after the last; none without validation days."""
+    return -(-int(epochs) // int(eval_every)) if n_val > 0 else 0
+
+
+def check_rnn_fit_args(days_shape, hidden, epochs, lrs, wds, clips, train_n, val_n, test_n, optimizer='adam', eval_every=1,
+                       train_stride=None, val_stride=None, test_stride=None):
+    """The argument rules of rnn_fit_pop that need no GPU (ValueError), the limits of mfg_rnn_fit_pop: days [D, Hd, d] with
+    2 <= Hd <= 64 and 2 <= d <= 64; per model a hidden size that is a multiple of 4 in [4, 64], 1 to 65 535 epochs, 1 to 64
+    training and 0 to 64 validation / test days (within the index tables' strides when given), lr finite and > 0, wd and clip
+    finite and >= 0; optimizer 'adam' or 'sgd', eval_every >= 1.  Returns (K, D, Hd, d, W_max, E_max, C_max): the largest
+    weight count, epochs and number of held-out checks."""
+    import math
+    if len(days_shape) != 3:
+        raise ValueError('days: expected [D, Hd, d], got %s' % (tuple(days_shape),))
+    D, Hd, d = (int(s) for s in days_shape)
+    if D < 1:
+        raise ValueError('days: no day')
+    if not 2 <= Hd <= L.RNN_MAX_HOURS:
+        raise ValueError('Hd=%d: a day has 2 to %d rows' % (Hd, L.RNN_MAX_HOURS))
+    if not 2 <= d <= L.RNN_MAX_D:
+        raise ValueError('d=%d: the RNN population covers 2 <= d <= %d' % (d, L.RNN_MAX_D))
+    if optimizer not in RNN_OPTIMIZERS:
+        raise ValueError("optimizer=%r: 'adam' or 'sgd'" % (optimizer,))
+    if isinstance(eval_every, bool) or int(eval_every) != eval_every or eval_every < 1:
+        raise ValueError('eval_every=%r: a whole number >= 1' % (eval_every,))
+    cols = [list(c) for c in (hidden, epochs, lrs, wds, clips, train_n, val_n, test_n)]
+    K = len(cols[0])
+    if K < 1:
+        raise ValueError('no models')
+    if K > L.POP_MAX_K:
+        raise ValueError('%d models: at most %d in one call (MFG_POP_MAX_K)' % (K, L.POP_MAX_K))
+    if any(len(c) != K for c in cols):
+        raise ValueError('hidden, epochs, lrs, wds, clips, train_n, val_n and test_n must have one entry per model (%d)' % K)
+    W_max = E_max = C_max = 0
+    for k, (H, E, lr, wd, clip, ntr, nva, nte) in enumerate(zip(*cols)):
+        H, E, ntr, nva, nte = int(H), int(E), int(ntr), int(nva), int(nte)
+        lr, wd, clip = float(lr), float(wd), float(clip)
+        if not 4 <= H <= L.RNN_MAX_HIDDEN or H % 4:
+            raise ValueError('model %d: hidden=%d, a multiple of 4 in [4, %d]' % (k, H, L.RNN_MAX_HIDDEN))
+        if not 1 <= E <= L.RNN_MAX_EPOCHS:
+            raise ValueError('model %d: epochs=%d outside [1, %d]' % (k, E, L.RNN_MAX_EPOCHS))
+        if not 1 <= ntr <= L.RNN_MAX_DAYS or (train_stride is not None and ntr > train_stride):
+            raise ValueError('model %d: %d training days, a model has 1 to %d (and train_idx holds them)' % (k, ntr, L.RNN_MAX_DAYS))
+        if not 0 <= nva <= L.RNN_MAX_DAYS or (val_stride is not None and nva > val_stride):
+            raise ValueError('model %d: %d validation days, a model has 0 to %d (and val_idx holds them)' % (k, nva, L.RNN_MAX_DAYS))
+        if not 0 <= nte <= L.RNN_MAX_DAYS or (test_stride is not None and nte > test_stride):
+            raise ValueError('model %d: %d test days, a model has 0 to %d (and test_idx holds them)' % (k, nte, L.RNN_MAX_DAYS))
+        if not (lr > 0.0 and math.isfinite(lr)):
+            raise ValueError('model %d: lr=%r must be finite and > 0' % (k, lr))
+        if not (wd >= 0.0 and math.isfinite(wd)):
+            raise ValueError('model %d: wd=%r must be finite and >= 0' % (k, wd))
+        if not (clip >= 0.0 and math.isfinite(clip)):
+            raise ValueError('model %d: clip=%r must be finite and >= 0' % (k, clip))
+        W_max, E_max = max(W_max, rnn_weight_count(H, d)), max(E_max, E)
+        C_max = max(C_max, rnn_check_count(E, nva, eval_every))
+    return K, D, Hd, d, W_max, E_max, C_max
+
+
+def rnn_models(hidden, epochs, lrs, wds, clips, train_n, val_n, test_n, d, Hd):
+    """The host table of mfg_rnn_fit_pop: (an array of K _lib.RnnModelStruct with ws_offset laid out by
+    mfg_rnn_fit_workspace_bytes, the workspace bytes of the call).  Needs the library, no GPU."""
+    K = len(hidden)
+    table = (L.RnnModelStruct * K)()
+    for k in range(K):
+        t = table[k]
+        t.hidden, t.epochs, t.n_train, t.n_val, t.n_test = int(hidden[k]), int(epochs[k]), int(train_n[k]), int(val_n[k]), int(test_n[k])
+        t.lr, t.wd, t.clip = float(lrs[k]), float(wds[k]), float(clips[k])
+    nbytes = int(L.lib().mfg_rnn_fit_workspace_bytes(K, table, int(d), int(Hd)))
+    if nbytes == 0:
+        raise ValueError('rnn_models: a record, d or Hd outside the limits of mfg_rnn_fit_pop')
+    return table, nbytes
+
+
+def rnn_models_device(table, device):
+    """The device copy of an rnn_models table (a uint8 tensor of 56 K bytes)."""
+    return var_models_device(table, device)
+
+
+RNN_OUTPUTS = ('weights', 'loss', 'val', 'best_epoch', 'future', 'per_day', 'metrics', 'status')
+
+
+def rnn_fit_shapes(K, Hd, d, W_max, E_max, C_max, test_stride):
+    """name -> (shape, dtype) of the outputs of rnn_fit_pop."""
+    f64 = torch.float64
+    return {'weights': ((K, W_max), f64), 'loss': ((K, E_max), f64), 'val': ((K, C_max), f64), 'best_epoch': ((K,), torch.int32),
+            'future': ((K, test_stride, Hd, d), f64), 'per_day': ((K, test_stride, 4), f64), 'metrics': ((K, 8), f64),
+            'status': ((K,), torch.int32)}
+
+
+def rnn_fit_pop(days, w0, hidden, epochs, lrs, wds, clips, train_idx, train_n, val_idx=None, val_n=None, test_idx=None, test_n=None,
+                *, optimizer='adam', eval_every=1, out=None, workspace=None, models=None, E_max=None, C_max=None):
+    """K one-layer LSTMs with a softmax head trained, selected on held-out days, forecast and scored in the two launches of one
+    call (mfg_rnn_fit_pop; the model and every definition are in include/mfg_hip.h).  days [D, Hd, d] fp64 on the device;
+    w0 [K, W_max] fp64 on the device, the packed initial weights of each model in the first W(H, d) entries of its row;
+    hidden, epochs, lrs, wds, clips, train_n, val_n, test_n: K host values each; train_idx [K, >= max train_n], val_idx and
+    test_idx int32 device tensors of day indices (None: no model has such a day).  Returns a dict of device tensors: weights
+    [K, W_max] (the selected iterate), loss [K, E_max], val [K, C_max], best_epoch [K] int32, future [K, test_stride, Hd, d],
+    per_day [K, test_stride, 4], metrics [K, 8], status [K] int32.  out / workspace / models: preallocated outputs (a dict by
+    name), the scratch buffer and the (host table, device copy, bytes) of rnn_models / rnn_models_device -- then the call
+    allocates nothing.  E_max / C_max: columns of loss / val when more than this call's models need (a chunk of a larger
+    population)."""
+    import ctypes as C
+    _chk_f64(days, 'days')
+    _chk_f64(w0, 'w0')
+    as_list = lambda x: x.tolist() if hasattr(x, 'tolist') else list(x)
+    K0 = len(as_list(hidden))
+    val_n = [0] * K0 if val_n is None else val_n
+    test_n = [0] * K0 if test_n is None else test_n
+    hidden, epochs, lrs, wds, clips, train_n, val_n, test_n = (as_list(x) for x in (hidden, epochs, lrs, wds, clips, train_n, val_n, test_n))
+    strides = []
+    for name, t in (('train_idx', train_idx), ('val_idx', val_idx), ('test_idx', test_idx)):
+        if t is None:
+            if name == 'train_idx':
+                raise ValueError('train_idx: every model has training days')
+            strides.append(0)
+            continue
+        _chk_i32(t, name)
+        if t.dim() != 2 or int(t.shape[0]) != K0:
+            raise ValueError('%s: expected [K = %d, days], got %s' % (name, K0, tuple(t.shape)))
+        strides.append(int(t.shape[1]))
+    K, D, Hd, d, W_max, E_need, C_need = check_rnn_fit_args(days.shape, hidden, epochs, lrs, wds, clips, train_n, val_n, test_n,
+                                                            optimizer, eval_every, *strides)
+    if w0.dim() != 2 or int(w0.shape[0]) != K or int(w0.shape[1]) < W_max:
+        raise ValueError('w0: expected [K = %d, >= %d], got %s' % (K, W_max, tuple(w0.shape)))
+    W_max = int(w0.shape[1])
+    if E_max is not None and int(E_max) < E_need:
+        raise ValueError('E_max=%d: the models train up to %d epochs' % (E_max, E_need))
+    if C_max is not None and int(C_max) < C_need:
+        raise ValueError('C_max=%d: the models make up to %d checks' % (C_max, C_need))
+    E_max, C_max = int(E_need if E_max is None else E_max), int(C_need if C_max is None else C_max)
+    dev = days.device
+    if models is None:
+        table, nbytes = rnn_models(hidden, epochs, lrs, wds, clips, train_n, val_n, test_n, d, Hd)
+        models = (table, rnn_models_device(table, dev), nbytes)
+    table, table_dev, nbytes = models
+    if workspace is None:
+        workspace = torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=dev)
+    shapes = rnn_fit_shapes(K, Hd, d, W_max, E_max, C_max, strides[2])
+    res = {}
+    for name in RNN_OUTPUTS:
+        if out is not None and name in out:
+            t = out[name]
+            if tuple(t.shape) != shapes[name][0] or t.dtype != shapes[name][1] or not t.is_cuda or not t.is_contiguous():
+                raise ValueError('out[%r]: expected a contiguous %s %s device tensor' % (name, shapes[name][0], shapes[name][1]))
+            res[name] = t
+        else:
+            res[name] = torch.empty(shapes[name][0], dtype=shapes[name][1], device=dev)
+    fit = L.RnnFitStruct()
+    fit.days, fit.models_host, fit.models = days.data_ptr(), C.addressof(table), table_dev.data_ptr()
+    fit.train_idx, fit.val_idx, fit.test_idx, fit.w0 = train_idx.data_ptr(), _ptr(val_idx), _ptr(test_idx), w0.data_ptr()
+    for name in RNN_OUTPUTS:
+        setattr(fit, name, res[name].data_ptr() if res[name].numel() else None)
+    fit.workspace, fit.workspace_bytes = workspace.data_ptr(), workspace.numel() * workspace.element_size()
+    fit.stream = _stream()
+    fit.D, fit.Hd, fit.d, fit.K = D, Hd, d, K
+    fit.train_stride, fit.val_stride, fit.test_stride = strides
+    fit.W_max, fit.E_max, fit.C_max = W_max, E_max, C_max
+    fit.optimizer, fit.eval_every = RNN_OPTIMIZERS[optimizer], int(eval_every)
+    L.check(L.lib().mfg_rnn_fit_pop(C.byref(fit)), 'mfg_rnn_fit_pop')
+    return res
+
+
 def policy_logpdf(pi, P, thetas, shift, alpha_scale=1.0, alpha_floor=0.0, p_floor=0.0):
     """log q_k(P_n | pi_n) [N,K] of the product-Dirichlet policy under K thetas (ac_irl.py:270-289, :324-379)."""
     _chk_f32(pi, 'pi'); _chk_f32(P, 'P'); _chk_f64(thetas, 'thetas')

@@ -1245,6 +1245,98 @@ typedef struct mfg_var_fit {
 size_t mfg_var_fit_workspace_bytes(int K, mfg_var_model_t* models_host, int d);
 int mfg_var_fit_pop(const mfg_var_fit_t* fit);
 
+/* The RNN baseline as a population: the third arm of the paper's comparison.  The reference only prepares the network's
+ * training file (process.py:4-22), reads its predictions back for a figure (read_rnn, mfg_ac2.py:757-761) and hard-codes its
+ * scores (plots.py:29-30); the network itself is not in the reference, so the model below is this project's definition.
+ * K independent models, each with its own hidden size, learning rate, weight decay, clip, epochs and day lists, trained,
+ * selected on held-out days, forecast and scored in the two launches of one call.  fp64 throughout.
+ *   days [D, Hd, d] fp64: a table of day matrices, as for mfg_var_fit_pop.  Model k (models[k]) lists n_train training days
+ *   train_idx[k train_stride + 0 ..], n_val >= 0 validation days (val_idx, val_stride) and n_test >= 0 test days (test_idx,
+ *   test_stride).  A day is one sequence: nothing crosses a day boundary.
+ *   The model: one LSTM layer of hidden size H and a softmax head.  Weights are packed as
+ *     Wx [4H, d] | Wh [4H, H] | b [4H] | Wo [d, H] | bo [d],    W(H, d) = 4H (d + H + 1) + d (H + 1) values,
+ *   gate order i, f, g, o (torch.nn.LSTMCell's; one gate bias).  a = Wx x + Wh h + b; c' = s(a_f) c + s(a_i) tanh(a_g);
+ *   h' = s(a_o) tanh(c'); yhat = softmax(Wo h' + bo); s the logistic function; h = c = 0 at hour 0 of every day.
+ *   Loss (teacher forced): L = 1/(n_train (Hd-1)) sum_n sum_{t=0..Hd-2} -sum_j y[n,t+1,j] log yhat[n,t,j] + wd/2 ||w||^2,
+ *   the network fed the observed rows y[n,t].  The whole training set is one batch: an epoch is one gradient of L (the
+ *   weight-decay term included) and one update.  If clip > 0 and ||g||_2 > clip, g is scaled by clip / ||g||_2.  optimizer
+ *   MFG_RNN_ADAM: m = b1 m + (1-b1) g, v = b2 v + (1-b2) g^2, w -= lr / (1 - b1^e) m / (sqrt(v) / sqrt(1 - b2^e) + 1e-8),
+ *   b1 = 0.9, b2 = 0.999, e the epoch from 1 (torch.optim.Adam's form; b^e by repeated multiplication); MFG_RNN_SGD: w -= lr g.
+ *   w0 [K, W_max]: the initial weights (first W(H, d) values of a row).  There is no device random number in this call.
+ *   loss [K, E_max]: L at the weights BEFORE the update of each epoch; NaN beyond the model's epochs.
+ *   Forecast (the definition of origin 1 of mfg_var_fit_pop): a day starts from its observed hour 0 with zero state and the
+ *   model's own output is fed back for Hd - 1 hours.  Per day (l1_final, l1_mean, JSD_final, JSD_mean) against the observed
+ *   day, hour Hd-1 and the mean over the Hd hours (hour 0 contributes 0), L1 and JSD as for mfg_var_fit_pop.
+ *   Selection: after every eval_every-th epoch and after the last one the validation days are forecast and the mean over
+ *   them of JSD_mean goes to val [K, C_max] (NaN beyond the model's own checks); the weights with the lowest value are kept,
+ *   ties go to the earlier check, its epoch to best_epoch [K].  weights [K, W_max] (zeros beyond W(H, d)) are that iterate's;
+ *   without validation days they are the last iterate's, best_epoch = epochs and val is all NaN.
+ *   future [K, test_stride, Hd, d]: the forecast of the test days from `weights`, hour 0 the observed row, zeros in days
+ *   >= n_test.  per_day [K, test_stride, 4], zeros in rows >= n_test.  metrics [K, 8]: mean and standard deviation (ddof 0)
+ *   over the test days of each of the four, the columns of mfg_var_fit_pop; NaN without a test day.
+ *   status [K] int32: bit 0 (MFG_RNN_NONFINITE) a non-finite value in a row the model reads (training, validation or test
+ *   day) or in its w0, or a day index outside [0, D) -- the index is clamped before it addresses anything; bit 1
+ *   (MFG_RNN_DIVERGED) a non-finite loss or gradient norm in some epoch, reported when bit 0 is clear.  Such a model returns
+ *   NaN in every float output and best_epoch 0; no other model is affected.
+ *   Order: every dot product is added in ascending index order with fused multiply-add (a gate: the bias, the d inputs, the H
+ *   hidden values; the backward product with Wh': four partial sums, one per gate block, added in gate order); a gradient
+ *   entry is added over hours ascending, days ascending within an hour; sums over the weights (||w||^2, ||g||^2) and over the
+ *   (hour, day) losses are 1024 strided partial sums, folded by an xor butterfly within each group of 64 and then added in
+ *   group order.  So each summation order is a function of the model's own (d, H, n_train, n_val, n_test, Hd), there are no
+ *   floating-point atomics, and a model's outputs are the same bits alone, among others, in any position.
+ *   models_host / models: the same K records on the host (for the checks) and on the device (for the kernels).  ws_offset is
+ *   the model's byte offset into the workspace; mfg_rnn_fit_workspace_bytes fills it in the host records and returns the
+ *   total, 0 for K < 1, a null table or a record outside the limits.  The workspace is 8-byte aligned, its contents scratch.
+ *   Everything is enqueued on fit->stream; the call neither allocates nor synchronises nor reads back.
+ * Checked before anything is launched (MFG_EINVAL): a null struct or pointer (an index table may be null when its stride is
+ * 0; future and per_day when test_stride is 0; val when C_max is 0), 1 <= K <= MFG_POP_MAX_K, D >= 1, 2 <= Hd <= 64,
+ * 2 <= d <= 64, optimizer MFG_RNN_ADAM or MFG_RNN_SGD, eval_every >= 1; per model H a multiple of 4 in [4, 64],
+ * 1 <= n_train <= 64 and <= train_stride, 0 <= n_val <= 64 and <= val_stride, 0 <= n_test <= 64 and <= test_stride,
+ * 1 <= epochs <= 65535 and <= E_max, its checks <= C_max, W(H, d) <= W_max, lr finite and > 0, wd and clip finite and >= 0,
+ * ws_offset as mfg_rnn_fit_workspace_bytes lays it out; MFG_EWORKSPACE when workspace_bytes is below that call's total. */
+#define MFG_RNN_ADAM 0
+#define MFG_RNN_SGD 1
+#define MFG_RNN_NONFINITE 1
+#define MFG_RNN_DIVERGED 2
+#define MFG_RNN_MAX_EPOCHS 65535
+typedef struct mfg_rnn_model {
+  int32_t hidden, epochs;
+  int32_t n_train, n_val;
+  int32_t n_test, reserved;
+  double lr;
+  double wd;
+  double clip;
+  int64_t ws_offset;
+} mfg_rnn_model_t; /* 56 bytes */
+typedef struct mfg_rnn_fit {
+  const double* days;
+  const mfg_rnn_model_t* models_host;
+  const mfg_rnn_model_t* models;
+  const int32_t* train_idx;
+  const int32_t* val_idx;
+  const int32_t* test_idx;
+  const double* w0;
+  double* weights;
+  double* loss;
+  double* val;
+  int32_t* best_epoch;
+  double* future;
+  double* per_day;
+  double* metrics;
+  int32_t* status;
+  void* workspace;
+  size_t workspace_bytes;
+  mfg_stream_t stream;
+  int32_t D, Hd;
+  int32_t d, K;
+  int32_t train_stride, val_stride;
+  int32_t test_stride, W_max;
+  int32_t E_max, C_max;
+  int32_t optimizer, eval_every;
+} mfg_rnn_fit_t;
+size_t mfg_rnn_fit_workspace_bytes(int K, mfg_rnn_model_t* models_host, int d, int Hd);
+int mfg_rnn_fit_pop(const mfg_rnn_fit_t* fit);
+
 #ifdef __cplusplus
 }
 #endif
