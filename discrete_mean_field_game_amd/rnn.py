@@ -55,23 +55,33 @@ def check_population_args(days, hidden, lrs, epochs, train_days, val_days, test_
     tr = _day_lists('train_days', train_days, K, days.shape[0], False)
     va = _day_lists('val_days', val_days, K, days.shape[0], True)
     te = _day_lists('test_days', test_days, K, days.shape[0], True)
-    shape = ops.check_rnn_fit_args(days.shape, hidden, epochs, lrs, wds, clips, [t.size for t in tr], [t.size for t in va],
-                                   [t.size for t in te], optimizer, eval_every)
-    return days, hidden, lrs, epochs, wds, clips, tr, va, te, shape
+    n_tr, n_va, n_te = ([t.size for t in lists] for lists in (tr, va, te))
+    W_max = E_max = C_max = 0
+    for c0 in range(0, K, L.POP_MAX_K):      # (per-model rules and the limit of one call; fit_population's chunks are never larger)
+        s = slice(c0, c0 + L.POP_MAX_K)
+        _, D, Hd, d, Wc, Ec, Cc = ops.check_rnn_fit_args(days.shape, hidden[s], epochs[s], lrs[s], wds[s], clips[s], n_tr[s], n_va[s],
+                                                         n_te[s], optimizer, eval_every)
+        W_max, E_max, C_max = max(W_max, Wc), max(E_max, Ec), max(C_max, Cc)
+    return days, hidden, lrs, epochs, wds, clips, tr, va, te, (K, D, Hd, d, W_max, E_max, C_max)
 
 
 def model_bytes(hidden, epochs, train_n, val_n, test_n, d, Hd, eval_every=1):
-    """An upper bound of the device bytes one model of a fit_population chunk needs: the largest workspace slice
+    """An upper bound of the device bytes one model of a fit_population chunk needs (hidden, epochs, train_n, val_n, test_n:
+    arrays or lists of K values, laid out POP_MAX_K models at a time): the largest workspace slice
     (mfg_rnn_fit_workspace_bytes lays the slices out; needs the library, no GPU), its initial weights and its outputs."""
     from . import ops
     K = len(hidden)
     ones = np.ones(K)
-    table, total = ops.rnn_models(hidden, epochs, ones, 0 * ones, 0 * ones, train_n, val_n, test_n, d, Hd)
-    offs = [table[k].ws_offset for k in range(K)] + [total]
+    largest = 0
+    for c0 in range(0, K, L.POP_MAX_K):      # (the layout of ONE call, which takes at most POP_MAX_K models)
+        s = slice(c0, c0 + L.POP_MAX_K)
+        table, total = ops.rnn_models(hidden[s], epochs[s], ones[s], 0 * ones[s], 0 * ones[s], train_n[s], val_n[s], test_n[s], d, Hd)
+        offs = [table[k].ws_offset for k in range(len(table))] + [total]
+        largest = max(largest, max(b - a for a, b in zip(offs, offs[1:])))
     W_max = max(ops.rnn_weight_count(int(H), d) for H in hidden)
     C_max = max(ops.rnn_check_count(int(E), int(nv), eval_every) for E, nv in zip(epochs, val_n))
     outputs = 8 * (W_max + int(max(epochs)) + C_max + int(max(test_n)) * (Hd * d + 4) + 8) + 8
-    return max(b - a for a, b in zip(offs, offs[1:])) + 8 * W_max + outputs
+    return largest + 8 * W_max + outputs
 
 
 class RnnFits:

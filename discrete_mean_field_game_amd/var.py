@@ -84,8 +84,13 @@ def check_population_args(days, lags, ridges, train_days, test_days, origin):
     orgs = np.array([ORIGINS[o] for o in orgs], dtype=np.int32)
     tr = _day_lists('train_days', train_days, K, days.shape[0], False)
     te = _day_lists('test_days', test_days, K, days.shape[0], True)
-    shape = ops.check_var_fit_args(days.shape, lags, ridges, [t.size for t in tr], [t.size for t in te], orgs)
-    return days, lags, ridges, tr, te, orgs, shape
+    n_tr, n_te = [t.size for t in tr], [t.size for t in te]
+    M = S_max = 0
+    for c0 in range(0, K, L.POP_MAX_K):      # (per-model rules and the limit of one call; fit_population's chunks are never larger)
+        s = slice(c0, c0 + L.POP_MAX_K)
+        _, D, Hd, d, Mc, Sc = ops.check_var_fit_args(days.shape, lags[s], ridges[s], n_tr[s], n_te[s], orgs[s])
+        M, S_max = max(M, Mc), max(S_max, Sc)
+    return days, lags, ridges, tr, te, orgs, (K, D, Hd, d, M, S_max)
 
 
 class VarFits:

@@ -710,7 +710,9 @@ size_t mfg_pop_validate_workspace_bytes(int64_t N, int L, int d, int K, int repe
  * Device arrays, owned by the caller:
  *   lr_critic, lr_actor [K] fp64   the SAME arrays the training call is given: a step writes them between two episodes, and the
  *                                  launches of the following episodes read the new rates
- *   order [K] int32                scratch: order[r] = the active learner of rank r at the last step
+ *   order [K] int32                scratch: order[r] = the active learner of rank r at the last step.  A step writes the slots
+ *                                  r < A and reads only those back, as learner indices (the donors): what the caller leaves in
+ *                                  the array is never read
  *   active [1] int32               scratch: the number A of active learners at the last step
  *   rank, parent [K, max_steps] int32   logs (the caller sets -1)
  *   lr_log [K, max_steps, 2] fp64  log: (critic, actor) rate after the step (the caller sets NaN)

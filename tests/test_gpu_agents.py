@@ -187,6 +187,41 @@ def _np_curves(emp, traj):
     return np.stack([l1.mean(0), l1.std(0), jsd.mean(0), jsd.std(0)], axis=1)
 
 
+def _check_taken_apart(dev, out, emp, counts0, agents, policies, ranks, R, precision, first=FIRST):
+    """A finite-population forecast with its members, counts and actions (the dict of ops.forecast_agents_pop), taken apart:
+    every action is sample_dirichlet's on the member's state, every step the restatement's (tests/agents_ref.py), the members
+    the rounded quotients of the counts, the reductions those of the mean-field forecast on these members."""
+    from discrete_mean_field_game_amd import ops
+    th, sh, al, sd = policies
+    K, N, d = len(th), emp.shape[0], emp.shape[2]
+    traj, counts, actions = out['traj'].cpu().numpy(), out['counts'].cpu().numpy(), out['actions'].cpu().numpy()
+    assert traj.shape == (K, N * R, H, d) and counts.shape == traj.shape and actions.shape == (K, N * R, H - 1, d, d)
+    assert np.array_equal(counts[:, :, 0], np.broadcast_to(np.tile(counts0, (R, 1)), (K, N * R, d)))
+    assert np.all(counts.sum(axis=-1) == agents) and counts.min() >= 0
+    assert np.array_equal(traj, (counts.astype(np.float64) / float(agents)).astype(np.float32))       # the rounded quotient
+    for k in range(K):
+        theta = torch.tensor([th[k]], dtype=F64, device=dev)
+        for t in range(H - 1):
+            P = ops.sample_dirichlet(out['traj'][k, :, t].contiguous(), theta, float(sh[k]), float(al[k]), int(sd[k]),
+                                     step=first + t, traj_offset=0, precision=precision)
+            assert torch.equal(out['actions'][k, :, t], P), (k, t)
+            want = ref.step_pop(counts[k:k + 1, :, t], actions[k:k + 1, :, t], agents, [int(sd[k])], first + t)[0]
+            assert np.array_equal(counts[k:k + 1, :, t + 1], want), (k, t)
+    # the reductions: those of the mean-field forecast, on these members (tolerances of tests/test_gpu_forecast_pop.py)
+    tol = 2.0 * R * 2.0 ** -53
+    mean, std, quant, curves = (out[key].cpu().numpy() for key in ('mean', 'std', 'quant', 'curves'))
+    for k in range(K):
+        m = traj[k].reshape(R, N, H, d).transpose(1, 0, 2, 3)        # member r of start state n is trajectory r N + n
+        assert np.array_equal(quant[k], np.sort(m, axis=1)[:, list(ranks)].transpose(0, 2, 1, 3)), k
+        m64 = m.astype(np.float64)
+        err_mean = np.max(np.abs(mean[k] - m64.mean(axis=1)))
+        err_std = np.max(np.abs(std[k] - m64.std(axis=1)) - tol * np.abs(m64.std(axis=1)))
+        print('learner %d: mean error %.3e (tol %.3e), std excess %.3e (abs tol %.3e)' % (k, err_mean, tol, err_std, 2.0 ** -60))
+        assert err_mean <= tol and err_std <= 2.0 ** -60, k
+        assert np.array_equal(mean[k][:, 0], traj[k, :N, 0].astype(np.float64)) and not std[k][:, 0].any()
+        np.testing.assert_allclose(curves[k], _np_curves(emp, traj[k]), rtol=1e-12, atol=1e-15, err_msg='learner %d' % k)
+
+
 @pytest.mark.parametrize('precision', ['mixed', 'f64'])
 @pytest.mark.parametrize('agents', [1, 5, 1000])
 @pytest.mark.parametrize('d', [15, 21, 4])
@@ -202,32 +237,8 @@ def test_forecast_taken_apart(dev, d, agents, precision):
                                   repeats=R, ranks=ranks, precision=precision,
                                   emp32=torch.as_tensor(emp.astype(np.float32), device=dev), emp64=torch.as_tensor(emp.copy(), device=dev),
                                   want_traj=True, want_counts=True, want_actions=True)
-    traj, counts, actions = out['traj'].cpu().numpy(), out['counts'].cpu().numpy(), out['actions'].cpu().numpy()
-    assert traj.shape == (K, N * R, H, d) and counts.shape == traj.shape and actions.shape == (K, N * R, H - 1, d, d)
-    assert np.array_equal(counts[:, :, 0], np.broadcast_to(np.tile(counts0, (R, 1)), (K, N * R, d)))
-    assert np.all(counts.sum(axis=-1) == agents) and counts.min() >= 0
-    assert np.array_equal(traj, (counts.astype(np.float64) / float(agents)).astype(np.float32))       # the rounded quotient
-    for k in range(K):
-        theta = torch.tensor([th[k]], dtype=F64, device=dev)
-        for t in range(H - 1):
-            P = ops.sample_dirichlet(out['traj'][k, :, t].contiguous(), theta, float(sh[k]), float(al[k]), int(sd[k]),
-                                     step=FIRST + t, traj_offset=0, precision=precision)
-            assert torch.equal(out['actions'][k, :, t], P), (k, t)
-            want = ref.step_pop(counts[k:k + 1, :, t], actions[k:k + 1, :, t], agents, [int(sd[k])], FIRST + t)[0]
-            assert np.array_equal(counts[k:k + 1, :, t + 1], want), (k, t)
-    # the reductions: those of the mean-field forecast, on these members (tolerances of tests/test_gpu_forecast_pop.py)
-    tol = 2.0 * R * 2.0 ** -53
-    mean, std, quant, curves = (out[key].cpu().numpy() for key in ('mean', 'std', 'quant', 'curves'))
-    for k in range(K):
-        m = traj[k].reshape(R, N, H, d).transpose(1, 0, 2, 3)        # member r of start state n is trajectory r N + n
-        assert np.array_equal(quant[k], np.sort(m, axis=1)[:, list(ranks)].transpose(0, 2, 1, 3)), k
-        m64 = m.astype(np.float64)
-        err_mean = np.max(np.abs(mean[k] - m64.mean(axis=1)))
-        err_std = np.max(np.abs(std[k] - m64.std(axis=1)) - tol * np.abs(m64.std(axis=1)))
-        print('learner %d: mean error %.3e (tol %.3e), std excess %.3e (abs tol %.3e)' % (k, err_mean, tol, err_std, 2.0 ** -60))
-        assert err_mean <= tol and err_std <= 2.0 ** -60, k
-        assert np.array_equal(mean[k][:, 0], traj[k, :N, 0].astype(np.float64)) and not std[k][:, 0].any()
-        np.testing.assert_allclose(curves[k], _np_curves(emp, traj[k]), rtol=1e-12, atol=1e-15, err_msg='learner %d' % k)
+    _check_taken_apart(dev, out, emp, counts0, agents, (th, sh, al, sd), ranks, R, precision)
+    mean, std = out['mean'].cpu().numpy(), out['std'].cpu().numpy()
     # nothing but the moments asked for: the same moments
     bare = ops.forecast_agents_pop(torch.as_tensor(counts0, device=dev), agents, *_dev_args(dev, th, sh, al, sd), H, first_step=FIRST,
                                    repeats=R, precision=precision)

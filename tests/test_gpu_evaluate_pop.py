@@ -71,6 +71,12 @@ def _np_metrics(emp, traj):
     return np.array(out)
 
 
+def _assert_metrics(metrics_k, emp, traj_k, what):
+    """One policy's eight metrics against the restatement on its own trajectories."""
+    assert np.all(np.isfinite(metrics_k)), what
+    np.testing.assert_allclose(metrics_k, _np_metrics(emp, traj_k), rtol=1e-12, atol=1e-15, err_msg=what)
+
+
 # (d, precision, K, R): N R = 5 or 15 trajectories, never a multiple of a block's 12 (d = 21), 16 (15), 36 (7) or 4 (64)
 CASES = [(21, 'mixed', 37, 1), (21, 'f64', 3, 3), (15, 'mixed', 3, 3), (15, 'f64', 1, 1), (7, 'mixed', 3, 1), (7, 'f64', 3, 3),
          (64, 'mixed', 1, 3), (64, 'f64', 3, 1)]
@@ -98,9 +104,7 @@ def test_metrics_match_numpy_restatement(dev, d, precision, K, R):
     metrics, traj = _run(dev, emp, th, sh, al, sd, 5, R, precision)
     metrics, traj = metrics.cpu().numpy(), traj.cpu().numpy()
     for k in range(K):
-        want = _np_metrics(emp, traj[k])
-        assert np.all(np.isfinite(metrics[k]))
-        np.testing.assert_allclose(metrics[k], want, rtol=1e-12, atol=1e-15, err_msg='learner %d' % k)
+        _assert_metrics(metrics[k], emp, traj[k], 'learner %d' % k)
 
 
 def test_deterministic_and_independent_of_K(dev):

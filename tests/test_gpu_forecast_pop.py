@@ -198,6 +198,12 @@ def _np_curves(emp, traj):
     return np.stack([l1.mean(0), l1.std(0), jsd.mean(0), jsd.std(0)], axis=1)
 
 
+def _assert_curves(curves_k, emp, traj_k, what):
+    """One policy's error curves against the restatement on its own members."""
+    assert np.all(np.isfinite(curves_k)), what
+    np.testing.assert_allclose(curves_k, _np_curves(emp, traj_k), rtol=1e-12, atol=1e-15, err_msg=what)
+
+
 @pytest.mark.parametrize('d,precision,K,N,R', [(21, 'mixed', 3, 5, 3), (15, 'f64', 1, 5, 1), (7, 'mixed', 3, 2, 33), (64, 'f64', 1, 1, 5)])
 def test_curves_match_numpy_and_evaluate_pop(dev, d, precision, K, N, R):
     from discrete_mean_field_game_amd import ops
@@ -205,9 +211,7 @@ def test_curves_match_numpy_and_evaluate_pop(dev, d, precision, K, N, R):
     emp = f['emp']
     assert f['curves'].shape == (K, H, 4)
     for k in range(K):
-        want = _np_curves(emp, f['traj'][k])
-        assert np.all(np.isfinite(f['curves'][k]))
-        np.testing.assert_allclose(f['curves'][k], want, rtol=1e-12, atol=1e-15, err_msg='learner %d' % k)
+        _assert_curves(f['curves'][k], emp, f['traj'][k], 'learner %d' % k)
     # the same quantities through the existing call: its final-row columns are step H - 1, its mean-row means the mean over l
     e32, e64 = torch.as_tensor(emp.astype(np.float32), device=dev), torch.as_tensor(emp.copy(), device=dev)
     metrics, traj = ops.evaluate_pop(e32, e64, *_dev_args(dev, *f['policies']), first_step=f['first_step'], repeats=R,

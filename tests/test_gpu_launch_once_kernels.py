@@ -248,6 +248,15 @@ def _logpdf_cases():
     return out
 
 
+def _assert_logpdf(got, pi, P, thetas, setting, case, what):
+    """got [N, K] against the oracle under setting = (shift, alpha_scale, alpha_floor, p_floor): 1e-10 relative with floor 1."""
+    want = _O().policy_logpdf(pi, P, thetas, *setting)
+    err = float(np.max(np.abs(got - want) / np.maximum(np.abs(want), 1.0)))
+    _report('k_policy_logpdf', case, what, err, 1e-10)
+    assert not np.isnan(got).any()
+    assert err < 1e-10
+
+
 @pytest.mark.parametrize('case,K', _logpdf_cases())
 def test_policy_logpdf(dev, caps, case, K):
     """The three (alpha_scale, alpha_floor, p_floor) settings and the bound of test_policy_logpdf_vs_oracle: 1e-10 relative with
@@ -262,12 +271,7 @@ def test_policy_logpdf(dev, caps, case, K):
         out = _nan((N, K), dev)
         _call('mfg_policy_logpdf', pid.data_ptr(), Pd.data_ptr(), N, d, thd.data_ptr(), K, 0.05, scale, floor, pfloor,
               out.data_ptr())
-        got = out.cpu().numpy()
-        want = _O().policy_logpdf(pi, P, thetas, 0.05, scale, floor, pfloor)
-        err = float(np.max(np.abs(got - want) / np.maximum(np.abs(want), 1.0)))
-        _report('k_policy_logpdf', case, 'K=%d s=%g' % (K, scale), err, 1e-10)
-        assert not np.isnan(got).any()
-        assert err < 1e-10
+        _assert_logpdf(out.cpu().numpy(), pi, P, thetas, (0.05, scale, floor, pfloor), case, 'K=%d s=%g' % (K, scale))
 
 
 # ---------------------------------------------------------------------------------------------------

@@ -86,19 +86,25 @@ def test_every_model_of_the_mixed_calls_is_healthy(mixed):
         assert all(np.isfinite(g.out[n]).all() for n in ('coef', 'sse', 'insample', 'future', 'per_day', 'metrics'))
 
 
+def backward_error(days, train, p, lam, B, n):
+    """(eta, bound): the normwise backward error of the coefficients B [m, d] of a model of lag p, ridge lam fitted on n rows of
+    the training days `train`, in longdouble, and its bound 4 m (m + n) u."""
+    m = B.shape[0]
+    G, C = R.gram(R.series(days, train), p, lam)
+    B, G, C = B.astype(np.longdouble), G.astype(np.longdouble), C.astype(np.longdouble)
+    fro = lambda a: np.sqrt(np.sum(a * a))
+    return float(fro(G @ B - C) / (fro(G) * fro(B) + fro(C))), 4 * m * (m + n) * U
+
+
 @pytest.mark.parametrize('lam', R.RIDGES)
 @pytest.mark.parametrize('case', R.CASES, ids=R.case_id)
 def test_solve_backward_error(mixed, case, lam):
     d, p, n_train = case
     m, n = 1 + p * d, n_train * R.HD - p
     g, k = models_of(mixed, case, lam, 0)[0]
-    G, C = R.gram(R.series(g.days, g.specs[k][2]), p, lam)
-    B = g.out['coef'][k, :m].astype(np.longdouble)
-    G, C = G.astype(np.longdouble), C.astype(np.longdouble)
-    fro = lambda a: np.sqrt(np.sum(a * a))
-    eta = float(fro(G @ B - C) / (fro(G) * fro(B) + fro(C)))
-    print('eta %s lambda=%g: %.3e (bound %.3e)' % (R.case_id(case), lam, eta, 4 * m * (m + n) * U))
-    assert eta <= 4 * m * (m + n) * U
+    eta, bound = backward_error(g.days, g.specs[k][2], p, lam, g.out['coef'][k, :m], n)
+    print('eta %s lambda=%g: %.3e (bound %.3e)' % (R.case_id(case), lam, eta, bound))
+    assert eta <= bound
 
 
 @pytest.mark.parametrize('case', R.CASES, ids=R.case_id)
