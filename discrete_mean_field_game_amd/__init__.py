@@ -5,7 +5,7 @@ Hot path: hand-written HIP kernels behind the C ABI of include/mfg_hip.h (csrc/)
 """
 from . import _lib  # noqa: F401
 
-__all__ = ['_lib', 'population', 'ActorCriticPopulation', 'irl_population', 'AC_IRLPopulation']
+__all__ = ['_lib', 'population', 'ActorCriticPopulation', 'irl_population', 'AC_IRLPopulation', 'demos']
 
 
 def __getattr__(name):
@@ -18,5 +18,8 @@ def __getattr__(name):
         import importlib
         irl_population = importlib.import_module(__name__ + '.irl_population')
         return irl_population if name == 'irl_population' else irl_population.AC_IRLPopulation
+    if name == 'demos':
+        import importlib
+        return importlib.import_module(__name__ + '.demos')
     raise AttributeError('module %r has no attribute %r' % (__name__, name))
 __version__ = '0.1.0'

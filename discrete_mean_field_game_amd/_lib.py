@@ -310,6 +310,26 @@ class RnnFitStruct(C.Structure):
 SIGNATURES['mfg_rnn_fit_workspace_bytes'] = (_sz, [_i32, C.POINTER(RnnModelStruct), _i32, _i32])
 SIGNATURES['mfg_rnn_fit_pop'] = (_i32, [C.POINTER(RnnFitStruct)])
 
+DEMOS_MAX_C, DEMOS_MAX_WIDTH = 4096, 64         # MFG_DEMOS_MAX_C; the width limit of mfg_demos_from_logs (as the populations' d)
+DEMOS_CHUNK = 8192                              # MFG_DEMOS_CHUNK: agents of one day that one workgroup of the counting pass owns
+DEMOS_ORDERS = {'first_hour': 0, 'total': 1, 'given': 2}        # MFG_DEMOS_ORDER_*
+DEMOS_EMPTY_ROWS = {'uniform': 0, 'identity': 1}                # MFG_DEMOS_EMPTY_*
+DEMOS_LDS_UPDATES = {'plain': 0, 'combine': 1}                  # MFG_DEMOS_LDS_*
+DEMOS_BAD_VALUE, DEMOS_EMPTY_HOUR, DEMOS_FAILED = 1, 2, 4       # bits of a day's status
+
+
+class DemosStruct(C.Structure):
+    """mfg_demos_t of include/mfg_hip.h: the descriptor of one mfg_demos_from_logs call; the stream is a member."""
+    _fields_ = ([(n, C.c_void_p) for n in ('topic', 'order_given', 'state', 'action', 'counts', 'moves', 'order', 'present', 'left',
+                                           'entered', 'status', 'workspace')]
+                + [('workspace_bytes', C.c_size_t), ('stream', C.c_void_p), ('U', C.c_int64)]
+                + [(n, C.c_int32) for n in ('N', 'H', 'C', 'd', 'width', 'order_mode', 'empty_row', 'order_given_rows', 'lds_update',
+                                            'groups')])
+
+
+SIGNATURES['mfg_demos_workspace_bytes'] = (_sz, [_i32, _i32, _i32, _i32])
+SIGNATURES['mfg_demos_from_logs'] = (_i32, [C.POINTER(DemosStruct)])
+
 _lib = None
 
 

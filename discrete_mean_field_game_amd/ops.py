@@ -2005,3 +2005,157 @@ def backward_value(P_seq, want_jsd=True):
     L.check(L.lib().mfg_backward_value(P_seq.data_ptr(), B, T, d, V.data_ptr(), l1.data_ptr(), _ptr(js), _stream()),
             'mfg_backward_value')
     return V, l1, js
+
+
+DEMOS_OUTPUTS = ('state', 'action', 'counts', 'moves', 'order', 'present', 'left', 'entered', 'status')
+DEMOS_REQUIRED = ('order', 'status')
+
+
+def check_demos_args(topic_shape, C, d, width=None, order='first_hour', order_given_shape=None, empty_row='uniform',
+                     lds_update='plain'):
+    """The argument rules of demos_from_logs that need no GPU (ValueError), the limits of mfg_demos_from_logs: topic [N, H, U]
+    with N >= 1, H >= 2, 1 <= U <= 2^31 - 1; 1 <= C <= 4096; 1 <= d <= width <= min(C, 64) (width None: d); order one of
+    'first_hour', 'total', 'given', the last with a table [N, C] or [1, C]; empty_row 'uniform' or 'identity'.  Returns
+    (N, H, U, C, d, width)."""
+    if len(topic_shape) != 3:
+        raise ValueError('topic: expected [N, H, U] (day, hour, agent), got %s' % (tuple(topic_shape),))
+    N, H, U = (int(s) for s in topic_shape)
+    C, d = int(C), int(d)
+    width = d if width is None else int(width)
+    if N < 1 or H < 2:
+        raise ValueError('topic [%d, %d, %d]: at least one day and two hours' % (N, H, U))
+    if not 1 <= U <= 2 ** 31 - 1:
+        raise ValueError('U=%d agents outside [1, 2^31 - 1]' % U)
+    if not 1 <= C <= L.DEMOS_MAX_C:
+        raise ValueError('C=%d categories outside [1, %d] (MFG_DEMOS_MAX_C)' % (C, L.DEMOS_MAX_C))
+    if not 1 <= d <= width <= C:
+        raise ValueError('d=%d, width=%d, C=%d: 1 <= d <= width <= C' % (d, width, C))
+    if width > L.DEMOS_MAX_WIDTH:
+        raise ValueError('width=%d: demonstrations cover width <= %d (as the populations do)' % (width, L.DEMOS_MAX_WIDTH))
+    if order not in L.DEMOS_ORDERS:
+        raise ValueError('order=%r: one of %s' % (order, sorted(L.DEMOS_ORDERS)))
+    if empty_row not in L.DEMOS_EMPTY_ROWS:
+        raise ValueError('empty_row=%r: one of %s' % (empty_row, sorted(L.DEMOS_EMPTY_ROWS)))
+    if lds_update not in L.DEMOS_LDS_UPDATES:
+        raise ValueError('lds_update=%r: one of %s' % (lds_update, sorted(L.DEMOS_LDS_UPDATES)))
+    if order == 'given':
+        if order_given_shape is None or tuple(order_given_shape) not in ((N, C), (1, C)):
+            raise ValueError('order=\'given\' needs order_given [%d, %d] or [1, %d], got %s'
+                             % (N, C, C, None if order_given_shape is None else tuple(order_given_shape)))
+    elif order_given_shape is not None:
+        raise ValueError('order_given is read with order=\'given\' only')
+    return N, H, U, C, d, width
+
+
+def demos_shapes(N, H, C, d, width):
+    """name -> (shape, dtype) of the outputs of demos_from_logs."""
+    f32, i32 = torch.float32, torch.int32
+    return {'state': ((N, H, d), f32), 'action': ((N, H - 1, d, d), f32), 'counts': ((N, H, width), i32),
+            'moves': ((N, H - 1, width, width), i32), 'order': ((N, C), i32), 'present': ((N, H), i32),
+            'left': ((N, H - 1, width), i32), 'entered': ((N, H - 1, width), i32), 'status': ((N,), i32)}
+
+
+def demos_workspace_bytes(N, H, C, width):
+    """mfg_demos_workspace_bytes: needs the library, no GPU."""
+    nbytes = int(L.lib().mfg_demos_workspace_bytes(int(N), int(H), int(C), int(width)))
+    if nbytes == 0:
+        raise ValueError('demos_workspace_bytes: N=%d, H=%d, C=%d, width=%d outside the limits of mfg_demos_from_logs' % (N, H, C, width))
+    return nbytes
+
+
+def _demos_outputs(shapes, names, out, want, dev):
+    res = {}
+    for name in names:
+        if want is not None and name not in want and name not in DEMOS_REQUIRED:
+            res[name] = None
+        elif out is not None and name in out:
+            t = out[name]
+            if tuple(t.shape) != shapes[name][0] or t.dtype != shapes[name][1] or not t.is_cuda or not t.is_contiguous():
+                raise ValueError('out[%r]: expected a contiguous %s %s device tensor' % (name, shapes[name][0], shapes[name][1]))
+            res[name] = t
+        else:
+            res[name] = torch.empty(shapes[name][0], dtype=shapes[name][1], device=dev)
+    return res
+
+
+def demos_from_logs(topic, C, d, *, width=None, order='first_hour', order_given=None, empty_row='uniform', out=None,
+                    workspace=None, want=None, lds_update='plain', groups=0):
+    """States and actions counted from an agent log (mfg_demos_from_logs; the definitions are in include/mfg_hip.h).  topic
+    [N, H, U] int32 on the device: the category in [0, C) of agent u at hour h of day n, negative when absent.  Categories are
+    ranked per day by the first hour's popularity ('first_hour', the reference's reorder), once for all days ('total') or by
+    order_given (int32 device tensor [N, C] or [1, C] of ranks, -1 drops); the top `width` (default d) are the recorded set, the
+    top d the model's topics.  Returns a dict of device tensors: state [N, H, d] and action [N, H-1, d, d] fp32, counts
+    [N, H, width], moves [N, H-1, width, width], order [N, C], present [N, H], left and entered [N, H-1, width], status [N]
+    int32.  want: the names to compute (None: all; order and status always) -- the others are None.  out / workspace:
+    preallocated outputs (a dict by name) and the scratch buffer (demos_workspace_bytes) -- then the call allocates nothing.
+    lds_update ('plain' / 'combine') and groups (workgroups of the counting pass per day, 0: from the device) change no output."""
+    import ctypes as C_
+    _chk_i32(topic, 'topic')
+    if order_given is not None:
+        _chk_i32(order_given, 'order_given')
+    N, H, U, C, d, width = check_demos_args(topic.shape, C, d, width, order, None if order_given is None else order_given.shape,
+                                            empty_row, lds_update)
+    if want is not None and not set(want) <= set(DEMOS_OUTPUTS):
+        raise ValueError('want: unknown outputs %s' % sorted(set(want) - set(DEMOS_OUTPUTS)))
+    dev = topic.device
+    nbytes = demos_workspace_bytes(N, H, C, width)
+    if workspace is None:
+        workspace = torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=dev)
+    res = _demos_outputs(demos_shapes(N, H, C, d, width), DEMOS_OUTPUTS, out, want, dev)
+    f = L.DemosStruct()
+    f.topic, f.order_given = topic.data_ptr(), _ptr(order_given)
+    for name in DEMOS_OUTPUTS:
+        setattr(f, name, _ptr(res[name]))
+    f.workspace, f.workspace_bytes, f.stream = workspace.data_ptr(), workspace.numel() * workspace.element_size(), _stream()
+    f.U, f.N, f.H, f.C, f.d, f.width = U, N, H, C, d, width
+    f.order_mode, f.empty_row, f.lds_update = L.DEMOS_ORDERS[order], L.DEMOS_EMPTY_ROWS[empty_row], L.DEMOS_LDS_UPDATES[lds_update]
+    f.order_given_rows = 0 if order_given is None else int(order_given.shape[0])
+    f.groups = int(groups)
+    L.check(L.lib().mfg_demos_from_logs(C_.byref(f)), 'mfg_demos_from_logs')
+    return res
+
+
+DEMOS_MOVES_OUTPUTS = ('state', 'action', 'present', 'left', 'entered', 'status')
+
+
+def check_demos_moves_args(counts_shape, moves_shape, d=None, empty_row='uniform'):
+    """The argument rules of demos_from_moves that need no GPU: counts [N, H, width], moves [N, H-1, width, width], H >= 2,
+    1 <= d <= width <= 64 (d None: width).  Returns (N, H, d, width)."""
+    if len(counts_shape) != 3:
+        raise ValueError('counts: expected [N, H, width], got %s' % (tuple(counts_shape),))
+    N, H, width = (int(s) for s in counts_shape)
+    if N < 1 or H < 2:
+        raise ValueError('counts [%d, %d, %d]: at least one day and two hours' % (N, H, width))
+    if tuple(moves_shape) != (N, H - 1, width, width):
+        raise ValueError('moves: expected [%d, %d, %d, %d], got %s' % (N, H - 1, width, width, tuple(moves_shape)))
+    d = width if d is None else int(d)
+    if not 1 <= d <= width:
+        raise ValueError('d=%d, width=%d: 1 <= d <= width' % (d, width))
+    if width > L.DEMOS_MAX_WIDTH:
+        raise ValueError('width=%d: demonstrations cover width <= %d (as the populations do)' % (width, L.DEMOS_MAX_WIDTH))
+    if empty_row not in L.DEMOS_EMPTY_ROWS:
+        raise ValueError('empty_row=%r: one of %s' % (empty_row, sorted(L.DEMOS_EMPTY_ROWS)))
+    return N, H, d, width
+
+
+def demos_from_moves(counts, moves, d=None, *, empty_row='uniform', out=None, want=None):
+    """The second mode of mfg_demos_from_logs: states and actions from integer tables that exist already -- counts [N, H, width]
+    and moves [N, H-1, width, width] int32 on the device, e.g. (counts, counts_next) stacked and the moves of
+    agents_step_pop(..., want_moves=True) with every member a day of H = 2.  Returns state, action, present, left, entered and
+    status as demos_from_logs does (counts and moves are the inputs); an hour with a negative entry (a failed member) gives NaN
+    rows and status bit _lib.DEMOS_FAILED."""
+    import ctypes as C_
+    _chk_i32(counts, 'counts'); _chk_i32(moves, 'moves')
+    N, H, d, width = check_demos_moves_args(counts.shape, moves.shape, d, empty_row)
+    if want is not None and not set(want) <= set(DEMOS_MOVES_OUTPUTS):
+        raise ValueError('want: unknown outputs %s' % sorted(set(want) - set(DEMOS_MOVES_OUTPUTS)))
+    shapes = demos_shapes(N, H, width, d, width)
+    res = _demos_outputs(shapes, DEMOS_MOVES_OUTPUTS, out, want, counts.device)
+    f = L.DemosStruct()
+    for name in DEMOS_MOVES_OUTPUTS:
+        setattr(f, name, _ptr(res[name]))
+    f.counts, f.moves, f.stream = counts.data_ptr(), moves.data_ptr(), _stream()
+    f.N, f.H, f.C, f.d, f.width, f.empty_row = N, H, width, d, width, L.DEMOS_EMPTY_ROWS[empty_row]
+    L.check(L.lib().mfg_demos_from_logs(C_.byref(f)), 'mfg_demos_from_logs')
+    res.update(counts=counts, moves=moves)
+    return res

@@ -1339,6 +1339,92 @@ typedef struct mfg_rnn_fit {
 size_t mfg_rnn_fit_workspace_bytes(int K, mfg_rnn_model_t* models_host, int d, int Hd);
 int mfg_rnn_fit_pop(const mfg_rnn_fit_t* fit);
 
+/* Demonstrations from agent logs: the states pi [d] and actions P [d,d] that AC_IRL, the forward learners and the baselines
+ * start from, counted on the device from a log that says which of C categories each of U agents was in at each hour.  The
+ * reference reads them from files of a recorder that is not part of it and patches them up in three routines (reorder,
+ * mfg_ac2.py:58-81; normalize, :116-137; convert_action, ac_irl.py:116-157); the definitions below are this project's own and
+ * restate those routines where they are cited.  Integer work: every output is the same bits on every run and layout.
+ *   topic [N, H, U] int32 (day, hour, agent; agent fastest).  A value in [0, C) is a raw category, a negative value an agent
+ *   that is absent that hour, a value >= C counts as absent and sets bit 0 of the day's status.
+ *   1. raw[n,h,c]: the agents of day n in category c at hour h.
+ *   2. rank[n,c].  MFG_DEMOS_ORDER_FIRST_HOUR (reorder): per day by decreasing raw[n,0,c], ties by ascending c.
+ *      MFG_DEMOS_ORDER_TOTAL: one ranking for all days by decreasing sum_{n,h} raw, the same tie rule.  MFG_DEMOS_ORDER_GIVEN:
+ *      order_given [order_given_rows, C] int32 (rows = N, or 1 for all days) holds the ranks; -1 drops a category, a value outside
+ *      [-1, C) drops it and sets status bit 0 (of every day that row serves); duplicate ranks are not checked.  An agent in a
+ *      category that is dropped or of rank >= width is absent for that hour.
+ *   3. counts[n,h,i], i < width: the agents at rank i.  present[n,h] = sum_i counts.
+ *   4. moves[n,h,i,j], h < H-1: the agents at rank i at hour h and rank j at hour h+1, both < width.  row_total[n,h,i] = sum_j.
+ *   5. state[n,h,i] = (float)((double)counts / (double)present), i < d (with width > d the row sums to less than 1, as normalize
+ *      followed by the [0:d] slice of init_pi0).  present = 0: the row is NaN and status bit 1 is set.
+ *   6. action[n,h,i,j] = (float)((double)moves / (double)row_total), i, j < d.  row_total = 0 and counts = 0: every entry
+ *      (float)(1 / (double)d) with MFG_DEMOS_EMPTY_UNIFORM (convert_action), 1 on the diagonal with MFG_DEMOS_EMPTY_IDENTITY
+ *      (what the recorder wrote); row_total = 0 and counts > 0 (every agent of the row left the recorded set): identity under
+ *      either setting (convert_action tests state == 0 and leaves such a row alone).
+ *   7. left[n,h,i] = counts[n,h,i] - row_total[n,h,i] and entered[n,h,j] = counts[n,h+1,j] - sum_i moves[n,h,i,j], both over
+ *      width and >= 0; a closed population has 0 in both.
+ *   Shapes: state [N,H,d], action [N,H-1,d,d] fp32; counts [N,H,width], moves [N,H-1,width,width], present [N,H], left and
+ *   entered [N,H-1,width], order [N,C] (rank -> raw category, -1 where no category has the rank), status [N] int32.  order and
+ *   status are required, every other output may be NULL and changes no other output.
+ *   Second mode, topic = NULL: counts and moves are INPUTS (the int32 arrays of mfg_agents_step_pop, width = d) and only steps
+ *   5 to 7 run; order is not written, order_mode / C / U are ignored.  An hour with a negative count or move (the failed-member
+ *   mark of mfg_agents_step_pop) sets status bit 2: its state and action are NaN, its present, left and entered -1, and so is
+ *   entered of the hour before an hour with a negative count.
+ *   status: bit 0 MFG_DEMOS_BAD_VALUE, bit 1 MFG_DEMOS_EMPTY_HOUR, bit 2 MFG_DEMOS_FAILED; one word per day, a day's bits and
+ *   outputs do not depend on any other day (but through MFG_DEMOS_ORDER_TOTAL's ranking).
+ *   Launches, all on demos->stream: the workspace and status are zeroed (memset nodes), the category histogram the ranking
+ *   needs (none for a given order), the ranking (a workgroup per day), the counting pass (a workgroup walks the hours of its
+ *   chunks of MFG_DEMOS_CHUNK agents of one day; tiles in LDS, one global integer atomic per non-zero cell and hour of a
+ *   workgroup), the finishing pass (a workgroup per day and hour).  Nothing is allocated or synchronised; the call can be captured.
+ *   workspace: mfg_demos_workspace_bytes(N, H, C, width) bytes (0 for arguments outside the limits; the second mode needs none
+ *   and takes NULL), 8-byte aligned; contents are scratch and are zeroed inside the call.
+ *   groups: the workgroups of the counting pass per day, each taking every groups-th chunk; 0 (the default) spreads two
+ *   workgroups per compute unit over the days.  No output depends on it.
+ *   lds_update: MFG_DEMOS_LDS_PLAIN (0, the default: one LDS atomic per lane) or MFG_DEMOS_LDS_COMBINE (lanes of a wave that hit
+ *   the same cell are combined before the LDS atomic, two rounds, then one atomic per lane that is left).  The same bits; the
+ *   plain form measured faster on both logs of tools/demos_probe.py (profiles/demos_from_logs.txt), the other is kept for
+ *   logs that are more contended than those.
+ * Checked before anything is launched (MFG_EINVAL): a null descriptor, order or status; N < 1, H < 2; with a log U < 1 or
+ * U > 2^31 - 1, C < 1 or C > MFG_DEMOS_MAX_C, width > C, an unknown order_mode, MFG_DEMOS_ORDER_GIVEN without a table or with
+ * order_given_rows not 1 or N, a null or misaligned workspace; without a log null counts or moves; d < 1 or d > width; an
+ * unknown empty_row or lds_update, groups < 0; workspace_bytes below the query's value (the message names the bytes needed); N H times
+ * the chunks of a day above 2^31 - 1.  MFG_EUNSUPPORTED: width > 64. */
+#define MFG_DEMOS_MAX_C 4096
+#define MFG_DEMOS_CHUNK 8192
+#define MFG_DEMOS_ORDER_FIRST_HOUR 0
+#define MFG_DEMOS_ORDER_TOTAL 1
+#define MFG_DEMOS_ORDER_GIVEN 2
+#define MFG_DEMOS_EMPTY_UNIFORM 0
+#define MFG_DEMOS_EMPTY_IDENTITY 1
+#define MFG_DEMOS_LDS_PLAIN 0
+#define MFG_DEMOS_LDS_COMBINE 1
+#define MFG_DEMOS_BAD_VALUE 1
+#define MFG_DEMOS_EMPTY_HOUR 2
+#define MFG_DEMOS_FAILED 4
+typedef struct mfg_demos {
+  const int32_t* topic;
+  const int32_t* order_given;
+  float* state;
+  float* action;
+  int32_t* counts;
+  int32_t* moves;
+  int32_t* order;
+  int32_t* present;
+  int32_t* left;
+  int32_t* entered;
+  int32_t* status;
+  void* workspace;
+  size_t workspace_bytes;
+  mfg_stream_t stream;
+  int64_t U;
+  int32_t N, H;
+  int32_t C, d;
+  int32_t width, order_mode;
+  int32_t empty_row, order_given_rows;
+  int32_t lds_update, groups;
+} mfg_demos_t;
+size_t mfg_demos_workspace_bytes(int N, int H, int C, int width);
+int mfg_demos_from_logs(const mfg_demos_t* demos);
+
 #ifdef __cplusplus
 }
 #endif
