@@ -330,6 +330,32 @@ class DemosStruct(C.Structure):
 SIGNATURES['mfg_demos_workspace_bytes'] = (_sz, [_i32, _i32, _i32, _i32])
 SIGNATURES['mfg_demos_from_logs'] = (_i32, [C.POINTER(DemosStruct)])
 
+DEMOS_BOOT_MAX_R = 1024                         # MFG_DEMOS_BOOT_MAX_R
+DEMOS_BOOT_TAG = 0xB007                         # MFG_DEMOS_BOOT_TAG: the low 16 bits of the fourth counter word of a weight's draw
+DEMOS_UNITS = {'agent_day': 0, 'agent': 1}      # MFG_DEMOS_UNIT_*
+DEMOS_BOOT_TABLE = (1580030168, 3160060337, 3950075421, 4213413783, 4279248373, 4292415291, 4294609777, 4294923276, 4294962463,
+                    4294966817, 4294967252, 4294967292)       # MFG_DEMOS_BOOT_TABLE: floor(2^32 CDF of Poisson(1))
+
+
+class DemosBootStruct(C.Structure):
+    """mfg_demos_boot_t of include/mfg_hip.h: the descriptor of one mfg_demos_bootstrap call; the stream is a member."""
+    _fields_ = ([(n, C.c_void_p) for n in ('topic', 'rank', 'state', 'action', 'counts', 'moves', 'present', 'left', 'entered',
+                                           'status', 'workspace')]
+                + [('workspace_bytes', C.c_size_t), ('stream', C.c_void_p), ('U', C.c_int64), ('seed', C.c_uint64),
+                   ('day_offset', C.c_int64)]
+                + [(n, C.c_int32) for n in ('N', 'H', 'C', 'd', 'width', 'R', 'rank_rows', 'unit', 'empty_row', 'groups')])
+
+
+class ReplicateBandsStruct(C.Structure):
+    """mfg_replicate_bands_t of include/mfg_hip.h."""
+    _fields_ = ([(n, C.c_void_p) for n in ('x', 'mean', 'std', 'quant', 'stream')]
+                + [('cells', C.c_int64), ('R', C.c_int32), ('Q', C.c_int32), ('ranks', C.c_int32 * FORECAST_MAX_RANKS)])
+
+
+SIGNATURES['mfg_demos_bootstrap_workspace_bytes'] = (_sz, [_i32, _i32, _i32, _i32, _i32])
+SIGNATURES['mfg_demos_bootstrap'] = (_i32, [C.POINTER(DemosBootStruct)])
+SIGNATURES['mfg_replicate_bands'] = (_i32, [C.POINTER(ReplicateBandsStruct)])
+
 _lib = None
 
 

@@ -66,6 +66,44 @@ inline DemosTiles demos_tiles(int H, int C, int width) {
   return t;
 }
 
+// The chunk's values of one hour: slot s of a thread.  VEC (U a multiple of 4, the log 16-byte aligned): eight 16-byte loads,
+// slot s is agent (s / 4) 1 024 + 4 tid + s % 4 of the chunk; else 32 coalesced 4-byte loads, slot s is agent 256 s + tid.
+// Agents past U read as -1: absent.
+template <bool VEC>
+__device__ __forceinline__ void demos_load(const int32_t* __restrict__ row, int64_t left, int32_t (&v)[DEMOS_SLOTS]) {
+  const int tid = threadIdx.x;
+  if (VEC) {
+#pragma unroll
+    for (int r = 0; r < DEMOS_SLOTS / 4; ++r) {
+      const int off = r * (DEMOS_THREADS * 4) + tid * 4;
+      int4 q = make_int4(-1, -1, -1, -1);
+      if (off < left) q = *reinterpret_cast<const int4*>(row + off);
+      v[4 * r] = q.x, v[4 * r + 1] = q.y, v[4 * r + 2] = q.z, v[4 * r + 3] = q.w;
+    }
+  } else {
+#pragma unroll
+    for (int s = 0; s < DEMOS_SLOTS; ++s) {
+      const int off = s * DEMOS_THREADS + tid;
+      v[s] = off < left ? row[off] : -1;
+    }
+  }
+}
+
+// ranks of one hour of a chunk, packed four to a register; true when a value >= C was seen
+template <bool VEC>
+__device__ __forceinline__ bool demos_ranks(const int32_t* __restrict__ row, int64_t left, const uint8_t* rk, int C, int width,
+                                            int32_t (&cur)[DEMOS_SLOTS]) {
+  demos_load<VEC>(row, left, cur);
+  bool bad = false;
+#pragma unroll
+  for (int s = 0; s < DEMOS_SLOTS; ++s) {
+    const int v = cur[s];
+    bad = bad || v >= C;
+    cur[s] = (v >= 0 && v < C) ? rk[v] : width;                          // `width`: absent
+  }
+  return bad;
+}
+
 void launch_demos(const mfg_demos_t& f, hipStream_t st);
 
 }  // namespace mfg

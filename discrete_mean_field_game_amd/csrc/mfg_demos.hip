@@ -28,29 +28,6 @@ __device__ __forceinline__ void demos_add(int32_t* tile, int key, bool on) {
   if (on) atomicAdd(&tile[key], 1);
 }
 
-// The chunk's values of one hour: slot s of a thread.  VEC (U a multiple of 4, the log 16-byte aligned): eight 16-byte loads,
-// slot s is agent (s / 4) 1 024 + 4 tid + s % 4 of the chunk; else 32 coalesced 4-byte loads, slot s is agent 256 s + tid.
-// Agents past U read as -1: absent.
-template <bool VEC>
-__device__ __forceinline__ void demos_load(const int32_t* __restrict__ row, int64_t left, int32_t (&v)[DEMOS_SLOTS]) {
-  const int tid = threadIdx.x;
-  if (VEC) {
-#pragma unroll
-    for (int r = 0; r < DEMOS_SLOTS / 4; ++r) {
-      const int off = r * (DEMOS_THREADS * 4) + tid * 4;
-      int4 q = make_int4(-1, -1, -1, -1);
-      if (off < left) q = *reinterpret_cast<const int4*>(row + off);
-      v[4 * r] = q.x, v[4 * r + 1] = q.y, v[4 * r + 2] = q.z, v[4 * r + 3] = q.w;
-    }
-  } else {
-#pragma unroll
-    for (int s = 0; s < DEMOS_SLOTS; ++s) {
-      const int off = s * DEMOS_THREADS + tid;
-      v[s] = off < left ? row[off] : -1;
-    }
-  }
-}
-
 template <bool VEC, bool COMBINE>
 __global__ __launch_bounds__(DEMOS_THREADS) void k_demos_keys(mfg_demos_t f, DemosWs w, int chunks, int all_hours) {
   extern __shared__ int32_t lds[];
@@ -100,21 +77,6 @@ __global__ __launch_bounds__(DEMOS_RANK_THREADS) void k_demos_rank(mfg_demos_t f
     for (int o = 0; o < C; ++o) r += (key[o] > k || (key[o] == k && o < c)) ? 1 : 0;
     for (int64_t m = n; m < n + days; ++m) w.rank[m * C + c] = r, f.order[m * C + r] = c;
   }
-}
-
-// ranks of one hour of a chunk, packed four to a register; true when a value >= C was seen
-template <bool VEC>
-__device__ __forceinline__ bool demos_ranks(const int32_t* __restrict__ row, int64_t left, const uint8_t* rk, int C, int width,
-                                            int32_t (&cur)[DEMOS_SLOTS]) {
-  demos_load<VEC>(row, left, cur);
-  bool bad = false;
-#pragma unroll
-  for (int s = 0; s < DEMOS_SLOTS; ++s) {
-    const int v = cur[s];
-    bad = bad || v >= C;
-    cur[s] = (v >= 0 && v < C) ? rk[v] : width;                          // `width`: absent
-  }
-  return bad;
 }
 
 // A workgroup owns the chunks g, g + groups, ... of one day.  The hours go in blocks of `hb` transitions whose tiles sit in LDS

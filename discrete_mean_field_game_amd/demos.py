@@ -193,3 +193,140 @@ def from_agents_step(counts, counts_next, moves, *, empty_row='uniform'):
     K, B, d = counts.shape
     both = torch.stack([counts.reshape(K * B, d), counts_next.reshape(K * B, d)], dim=1).contiguous()
     return from_moves(both, moves.reshape(K * B, 1, d, d).contiguous(), d, empty_row=empty_row)
+
+
+BOOT_ARRAYS = ('state', 'action', 'counts', 'moves', 'present', 'left', 'entered', 'status')
+
+
+class BootstrapDemonstrations:
+    """R Poisson-bootstrap replicates of the demonstrations of one log (bootstrap): `sample`, the Demonstrations of the log
+    itself, and the arrays of mfg_demos_bootstrap as NumPy with a leading R -- state [R,N,H,d], action [R,N,H-1,d,d], counts,
+    moves, present, left, entered, status [R,N].  Every replicate shares the sample's ranking (`sample.order`)."""
+
+    def __init__(self, sample, arrays, seed=0, unit='agent_day'):
+        self.sample, self.seed, self.unit = sample, int(seed), unit
+        self.d, self.width, self.empty_row, self.N, self.H = sample.d, sample.width, sample.empty_row, sample.N, sample.H
+        for name in BOOT_ARRAYS:
+            setattr(self, name, np.asarray(arrays[name]))
+        self.R = self.state.shape[0]
+        if self.state.shape != (self.R, self.N, self.H, self.d) or self.status.shape != (self.R, self.N):
+            raise ValueError('state %s / status %s: expected [R, %d, %d, %d] and [R, %d]'
+                             % (self.state.shape, self.status.shape, self.N, self.H, self.d, self.N))
+
+    def _r(self, r):
+        if not 0 <= int(r) < self.R:
+            raise ValueError('replicate %d outside [0, %d)' % (r, self.R))
+        return int(r)
+
+    def replicate(self, r):
+        """Replicate r as a Demonstrations (order: the sample's), for every consumer of one."""
+        r = self._r(r)
+        arrays = {name: getattr(self, name)[r] for name in BOOT_ARRAYS}
+        arrays['order'] = self.sample.order
+        return Demonstrations(arrays, self.d, self.width, self.empty_row)
+
+    def emp(self, days=None):
+        """[R, days, H, d] fp64: every replicate's day table."""
+        return self.state[:, self.sample._days(days)].astype(np.float64)
+
+    def days_table(self):
+        """[R N, H, d] fp64: the days of all replicates as one table, replicate r's day n at row r N + n (day_index), so that
+        var.fit_population / rnn.fit_population fit K = R models in one call, model r on replicate r's days."""
+        return self.state.reshape(self.R * self.N, self.H, self.d).astype(np.float64)
+
+    def day_index(self, r, days=None):
+        """The rows of days_table() that hold the given days of replicate r."""
+        return np.asarray([self._r(r) * self.N + n for n in self.sample._days(days)], np.int64)
+
+    def bands(self, ranks=(), device=None):
+        """Per cell over the R replicates, on the device (ops.replicate_bands): a dict name -> (mean fp64, std fp64 with ddof 0,
+        quant [Q, ...] fp32) for 'state' [N,H,d] and 'action' [N,H-1,d,d].  quant[q] is the replicate value of 0-based rank
+        ranks[q]; a cell that is NaN in any replicate is NaN."""
+        import torch
+        from . import ops
+        dev = _device(device)
+        out = {}
+        for name in ('state', 'action'):
+            res = ops.replicate_bands(torch.as_tensor(np.ascontiguousarray(getattr(self, name)), device=dev), ranks)
+            out[name] = tuple(t.cpu().numpy() for t in res)
+        return out
+
+    def interval_ranks(self, level=0.9):
+        """The two 0-based ranks of the percentile interval of the given level: floor(a (R - 1)) and ceil((1 - a) (R - 1)),
+        a = (1 - level) / 2."""
+        if not 0.0 < level < 1.0:
+            raise ValueError('level=%r outside (0, 1)' % (level,))
+        a = (1.0 - level) / 2.0
+        return int(np.floor(a * (self.R - 1))), int(np.ceil((1.0 - a) * (self.R - 1)))
+
+    def interval(self, level=0.9, device=None):
+        """The percentile interval over the replicates: a dict name -> (low, high) fp32 for 'state' and 'action'."""
+        b = self.bands(self.interval_ranks(level), device)
+        return {name: (q[0], q[1]) for name, (_, _, q) in b.items()}
+
+
+def bootstrap_day_bytes(H, U, d, width, replicates, layout='nhu'):
+    """Device bytes one day costs a chunk of bootstrap: the log (twice when it is transposed) and the R-fold integer tables,
+    once as outputs and once in the workspace, and the R-fold fp32 outputs."""
+    tables = H * width + (H - 1) * width * width
+    return H * U * 4 * (2 if layout == 'nuh' else 1) + replicates * 4 * (2 * tables + H * d + (H - 1) * d * d + H + 2 * (H - 1) * width)
+
+
+def bootstrap(topic, d, replicates, *, seed=0, unit='agent_day', categories=None, width=None, order='first_hour', order_given=None,
+              empty_row='uniform', layout='nhu', device=None, budget=None):
+    """The demonstrations of a log with `replicates` Poisson-bootstrap replicates of them: the recorded agents resampled on the
+    device, every agent with its whole trajectory (ops.demos_bootstrap, C ABI mfg_demos_bootstrap).  topic, d, categories,
+    width, order, order_given, empty_row, layout, device as from_logs: the log is counted once as it is (the sample and its
+    ranking), then once with R weighted tallies under that ranking.  unit='agent_day': an agent index is another person each
+    day; 'agent': agent u is one person, who carries one weight through all days.  The days go in chunks whose log and R-fold
+    tables stay within `budget` bytes (None: BUDGET); chunking changes no bit; order='total' needs one chunk.  Returns a
+    BootstrapDemonstrations."""
+    import torch
+    from . import ops
+    from .population import consistency_chunks
+    is_tensor = isinstance(topic, torch.Tensor)
+    if not is_tensor:
+        topic = np.asarray(topic)
+    if categories is None:
+        if (topic.numel() if is_tensor else topic.size) == 0:
+            raise ValueError('topic is empty')
+        categories = int(topic.max()) + 1
+    N, H, U, C, d, width = check_from_logs_args(tuple(topic.shape), d, categories, width, order, empty_row, layout)
+    R = int(replicates)
+    ops.check_demos_boot_args((N, H, U), (1, C), C, d, R, width, unit, 0, empty_row)
+    g = None
+    if order == 'given':
+        if order_given is None:
+            raise ValueError('order=\'given\' needs order_given')
+        g = order_given.detach().cpu().numpy() if isinstance(order_given, torch.Tensor) else np.asarray(order_given)
+        g = g.reshape(1, -1) if g.ndim == 1 else g
+        if g.ndim != 2 or g.shape not in ((N, C), (1, C)):
+            raise ValueError('order_given: expected [%d, %d], [1, %d] or [%d], got %s' % (N, C, C, C, g.shape))
+    elif order_given is not None:
+        raise ValueError('order_given is read with order=\'given\' only')
+    dev = topic.device if is_tensor and topic.is_cuda and device is None else _device(device)
+    limit = BUDGET if budget is None else budget
+    chunks = consistency_chunks(N, bootstrap_day_bytes(H, U, d, width, R, layout), limit)
+    if order == 'total' and len(chunks) > 1:
+        raise ValueError('order=\'total\' ranks over all %d days at once: %d bytes, the budget is %d'
+                         % (N, N * bootstrap_day_bytes(H, U, d, width, R, layout), limit))
+    parts, boots = [], []
+    for first, count in chunks:
+        part = _to_device_i32(topic[first:first + count], dev)
+        if layout == 'nuh':
+            part = part.permute(0, 2, 1).contiguous()
+        table = None
+        if order == 'given':
+            table = _to_device_i32(g if g.shape[0] == 1 else g[first:first + count], dev)
+        res = ops.demos_from_logs(part, C, d, width=width, order=order, order_given=table, empty_row=empty_row)
+        if order == 'given':
+            rank = table
+        else:                                   # order [count, C]: rank -> category, every category ranked; inverted
+            rank = torch.empty_like(res['order'])
+            rank.scatter_(1, res['order'].long(), torch.arange(C, dtype=torch.int32, device=dev).expand(count, C).contiguous())
+        boot = ops.demos_bootstrap(part, rank, C, d, R, seed, width=width, unit=unit, day_offset=first, empty_row=empty_row)
+        parts.append({name: res[name].cpu().numpy() for name in ARRAYS})
+        boots.append({name: boot[name].cpu().numpy() for name in BOOT_ARRAYS})
+        del part, res, boot
+    sample = Demonstrations({name: np.concatenate([p[name] for p in parts]) for name in ARRAYS}, d, width, empty_row)
+    return BootstrapDemonstrations(sample, {name: np.concatenate([b[name] for b in boots], axis=1) for name in BOOT_ARRAYS}, seed, unit)

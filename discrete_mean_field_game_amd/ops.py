@@ -2159,3 +2159,118 @@ def demos_from_moves(counts, moves, d=None, *, empty_row='uniform', out=None, wa
     L.check(L.lib().mfg_demos_from_logs(C_.byref(f)), 'mfg_demos_from_logs')
     res.update(counts=counts, moves=moves)
     return res
+
+
+DEMOS_BOOT_OUTPUTS = ('state', 'action', 'counts', 'moves', 'present', 'left', 'entered', 'status')
+
+
+def check_demos_boot_args(topic_shape, rank_shape, C, d, R, width=None, unit='agent_day', day_offset=0, empty_row='uniform',
+                          groups=0):
+    """The argument rules of demos_bootstrap that need no GPU (ValueError), the limits of mfg_demos_bootstrap: those of
+    demos_from_logs with a given order (rank [N, C] or [1, C]), 1 <= R <= 1024, 12 U <= 2^31 - 1 (a weighted cell must fit
+    int32), unit 'agent_day' or 'agent', day_offset + n in [0, 2^48).  Returns (N, H, U, C, d, width)."""
+    if rank_shape is None:
+        raise ValueError('rank: the ranking of the recorded sample is required, [N, C] or [1, C]')
+    N, H, U, C, d, width = check_demos_args(topic_shape, C, d, width, 'given', tuple(rank_shape), empty_row)
+    R = int(R)
+    if not 1 <= R <= L.DEMOS_BOOT_MAX_R:
+        raise ValueError('R=%d replicates outside [1, %d] (MFG_DEMOS_BOOT_MAX_R)' % (R, L.DEMOS_BOOT_MAX_R))
+    if 12 * U > 2 ** 31 - 1:
+        raise ValueError('U=%d agents: a cell weighted up to 12 times must fit int32, 12 U <= 2^31 - 1' % U)
+    if R * N * H > 2 ** 31 - 1:
+        raise ValueError('R N H = %d > 2^31 - 1' % (R * N * H))
+    if unit not in L.DEMOS_UNITS:
+        raise ValueError('unit=%r: one of %s' % (unit, sorted(L.DEMOS_UNITS)))
+    if unit == 'agent_day' and not 0 <= int(day_offset) <= 2 ** 48 - N:
+        raise ValueError('day_offset=%d: day_offset + n must lie in [0, 2^48)' % day_offset)
+    if int(groups) < 0:
+        raise ValueError('groups=%d < 0' % groups)
+    return N, H, U, C, d, width
+
+
+def demos_boot_shapes(R, N, H, d, width):
+    """name -> (shape, dtype) of the outputs of demos_bootstrap: those of demos_from_logs (but order) with a leading R."""
+    return {n: ((R,) + s, t) for n, (s, t) in demos_shapes(N, H, 1, d, width).items() if n != 'order'}
+
+
+def demos_bootstrap_workspace_bytes(R, N, H, C, width):
+    """mfg_demos_bootstrap_workspace_bytes: needs the library, no GPU."""
+    nbytes = int(L.lib().mfg_demos_bootstrap_workspace_bytes(int(R), int(N), int(H), int(C), int(width)))
+    if nbytes == 0:
+        raise ValueError('demos_bootstrap_workspace_bytes: R=%d, N=%d, H=%d, C=%d, width=%d outside the limits of '
+                         'mfg_demos_bootstrap' % (R, N, H, C, width))
+    return nbytes
+
+
+def demos_bootstrap(topic, rank, C, d, R, seed=0, *, width=None, unit='agent_day', day_offset=0, empty_row='uniform', groups=0,
+                    out=None, workspace=None, want=None):
+    """R Poisson-bootstrap replicates of the demonstrations of a log (mfg_demos_bootstrap; the definitions are in
+    include/mfg_hip.h): topic [N, H, U] int32 as demos_from_logs, rank [N, C] or [1, C] int32 the ranks of the categories (the
+    recorded sample's, -1 drops).  In replicate r agent u of day n counts w ~ Poisson(1) times at every hour, w from the
+    counter-based generator under `seed`; unit 'agent_day' draws per (day_offset + n, u), 'agent' per u for all days.  Returns a
+    dict of device tensors with a leading R: state, action, counts, moves, present, left, entered, status [R, N].  want / out /
+    workspace as demos_from_logs; groups changes no output."""
+    import ctypes as C_
+    _chk_i32(topic, 'topic')
+    if rank is not None:
+        _chk_i32(rank, 'rank')
+    N, H, U, C, d, width = check_demos_boot_args(topic.shape, None if rank is None else rank.shape, C, d, R, width, unit, day_offset,
+                                                 empty_row, groups)
+    R = int(R)
+    if want is not None and not set(want) <= set(DEMOS_BOOT_OUTPUTS):
+        raise ValueError('want: unknown outputs %s' % sorted(set(want) - set(DEMOS_BOOT_OUTPUTS)))
+    dev = topic.device
+    nbytes = demos_bootstrap_workspace_bytes(R, N, H, C, width)
+    if workspace is None:
+        workspace = torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=dev)
+    res = _demos_outputs(demos_boot_shapes(R, N, H, d, width), DEMOS_BOOT_OUTPUTS, out, want, dev)
+    f = L.DemosBootStruct()
+    f.topic, f.rank = topic.data_ptr(), rank.data_ptr()
+    for name in DEMOS_BOOT_OUTPUTS:
+        setattr(f, name, _ptr(res[name]))
+    f.workspace, f.workspace_bytes, f.stream = workspace.data_ptr(), workspace.numel() * workspace.element_size(), _stream()
+    f.U, f.seed, f.day_offset = U, int(seed) & (2 ** 64 - 1), int(day_offset)
+    f.N, f.H, f.C, f.d, f.width, f.R = N, H, C, d, width, R
+    f.rank_rows, f.unit, f.empty_row, f.groups = int(rank.shape[0]), L.DEMOS_UNITS[unit], L.DEMOS_EMPTY_ROWS[empty_row], int(groups)
+    L.check(L.lib().mfg_demos_bootstrap(C_.byref(f)), 'mfg_demos_bootstrap')
+    return res
+
+
+def check_replicate_bands_args(x_shape, ranks):
+    """The argument rules of replicate_bands that need no GPU: x [R, ...] with 1 <= R <= 1024, at most FORECAST_MAX_RANKS
+    ranks, each in [0, R).  Returns (R, cells, ranks)."""
+    if len(x_shape) < 1:
+        raise ValueError('x: expected [R, ...]')
+    R = int(x_shape[0])
+    if not 1 <= R <= L.DEMOS_BOOT_MAX_R:
+        raise ValueError('R=%d replicates outside [1, %d]' % (R, L.DEMOS_BOOT_MAX_R))
+    ranks = [int(q) for q in ranks]
+    if len(ranks) > L.FORECAST_MAX_RANKS:
+        raise ValueError('%d ranks: at most %d order statistics per call (MFG_FORECAST_MAX_RANKS)' % (len(ranks), L.FORECAST_MAX_RANKS))
+    if any(not 0 <= q < R for q in ranks):
+        raise ValueError('ranks %s outside [0, %d)' % (ranks, R))
+    cells = 1
+    for s in x_shape[1:]:
+        cells *= int(s)
+    return R, cells, ranks
+
+
+def replicate_bands(x, ranks=()):
+    """Bands over the leading axis of x [R, ...] fp32 on the device (mfg_replicate_bands): (mean [...] fp64, std [...] fp64 with
+    ddof 0, quant [Q, ...] fp32) per cell over its R values.  mean and std are sums in the order r = 0 .. R - 1 in fp64, every
+    operation rounded on its own; quant[q] is the element of 0-based rank ranks[q] (not an interpolation; ranks may repeat and
+    need not be sorted).  A cell with a NaN in any replicate is NaN in all three."""
+    import ctypes as C_
+    _chk_f32(x, 'x')
+    R, cells, ranks = check_replicate_bands_args(tuple(x.shape), ranks)
+    rest = tuple(x.shape[1:])
+    mean = torch.empty(rest, dtype=torch.float64, device=x.device)
+    std = torch.empty(rest, dtype=torch.float64, device=x.device)
+    quant = torch.empty((len(ranks),) + rest, dtype=torch.float32, device=x.device)
+    b = L.ReplicateBandsStruct()
+    b.x, b.mean, b.std, b.quant, b.stream = x.data_ptr(), mean.data_ptr(), std.data_ptr(), quant.data_ptr() if ranks else None, _stream()
+    b.cells, b.R, b.Q = cells, R, len(ranks)
+    for q, rank in enumerate(ranks):
+        b.ranks[q] = rank
+    L.check(L.lib().mfg_replicate_bands(C_.byref(b)), 'mfg_replicate_bands')
+    return mean, std, quant

@@ -1425,6 +1425,100 @@ typedef struct mfg_demos {
 size_t mfg_demos_workspace_bytes(int N, int H, int C, int width);
 int mfg_demos_from_logs(const mfg_demos_t* demos);
 
+/* Bootstrap replicates of the demonstrations: the agents of a log resampled on the device.  A state of mfg_demos_from_logs is a
+ * proportion over the U recorded agents and an action row a proportion over the agents of one topic at one hour; this call
+ * says how far those move when the recorded agents are drawn again.  It is the Poisson bootstrap over the sampling unit, the
+ * agent with its whole trajectory: in replicate r every agent counts w times, w ~ Poisson(1) independent per agent and
+ * replicate and the same at every hour.  Nothing is gathered: the log is streamed, with R weighted tallies instead of one.
+ * (The exact multinomial bootstrap fixes sum w = U; here the weighted `present` varies by about 1 / sqrt(U) between replicates.)
+ *   topic [N, H, U] int32 as mfg_demos_from_logs.  rank [rank_rows, C] int32, rank_rows 1 or N: the ranks, with the meaning of
+ *   MFG_DEMOS_ORDER_GIVEN (-1 drops a category, a value outside [-1, C) drops it and sets status bit 0).  The ranking is always
+ *   given and shared by the replicates -- the ranking of the recorded sample (mfg_demos_from_logs' `order`, inverted) --, so
+ *   that topic i is the same category in every replicate and a cell's R values can be compared; a ranking per replicate would
+ *   mix the noise of the labels into every cell and is not offered.
+ *   Weights, word by word.  Replicate r, day n, agent u:
+ *     (x0, x1, x2, x3) = Philox4x32-10(counter = (u, day_key low 32 bits, r >> 2, MFG_DEMOS_BOOT_TAG | (day_key >> 32) << 16),
+ *                                      key = (seed low 32 bits, seed high 32 bits))
+ *     day_key = day_offset + n with MFG_DEMOS_UNIT_AGENT_DAY (an agent index is another person each day; day_offset lets the
+ *     days be sent in chunks without changing a bit), day_key = 0 with MFG_DEMOS_UNIT_AGENT (agent u is one person who carries
+ *     one weight through all days; day_offset is ignored).  day_key must lie in [0, 2^48).
+ *     w = #{k < 12 : x[r & 3] >= T[k]},  T[k] = floor(2^32 sum_{j <= k} e^-1 / j!) = MFG_DEMOS_BOOT_TABLE, so 0 <= w <= 12: the
+ *     tail beyond 12, of mass < 2^-32, is folded into 12.  MFG_DEMOS_BOOT_TAG in the low 16 bits of the fourth counter word
+ *     separates these draws from every other use of the generator (the samplers put bits 32..47 of a trajectory id there).
+ *   Outputs, replicate r: steps 3 to 7 of mfg_demos_from_logs with every agent of day n counted w times -- counts
+ *   [R,N,H,width], moves [R,N,H-1,width,width], present [R,N,H], left and entered [R,N,H-1,width] int32, state [R,N,H,d], action
+ *   [R,N,H-1,d,d] fp32, status [R,N].  Steps 5 to 7 are the second mode of mfg_demos_from_logs over the R N "days" r N + n, by
+ *   the same kernel.  status bits as there: bit 0 for a value >= C in the day's log or a bad rank, in every replicate of the day
+ *   whatever the weights; bit 1 for a replicate whose weighted present is 0 at some hour (NaN rows, as an empty hour).
+ *   status is required; every other output may be NULL and changes no other output.  Integer work: no output depends on
+ *   groups, on how replicates are blocked or on the chunking of agents or days.
+ *   Launches, all on boot->stream: memsets (the flags, counts and moves -- the caller's arrays when given, else the
+ *   workspace's --, status), the counting pass (a workgroup walks its chunks of MFG_DEMOS_CHUNK agents of one day for four
+ *   replicates -- one Philox block -- or one where four sets of tiles do not fit in LDS; one LDS atomic of w per agent, hour
+ *   and replicate with w > 0; one global integer atomic per non-zero cell), the finishing pass, and one pass that adds bit 0.
+ *   Nothing is allocated or synchronised; the call can be captured.
+ *   workspace: mfg_demos_bootstrap_workspace_bytes(R, N, H, C, width) bytes (0 for arguments outside the limits), 8-byte
+ *   aligned; contents are scratch and are zeroed inside the call.
+ *   groups: the workgroups of the counting pass per day and replicate block; 0 spreads two per compute unit.
+ * Checked before anything is launched (MFG_EINVAL): a null descriptor, topic, status or rank table; rank_rows not 1 or N;
+ * N < 1, H < 2; R outside [1, MFG_DEMOS_BOOT_MAX_R]; R N H > 2^31 - 1; U < 1 or 12 U > 2^31 - 1 (a weighted cell must fit
+ * int32); C < 1 or C > MFG_DEMOS_MAX_C; width > C; d < 1 or d > width; an unknown unit or empty_row; groups < 0; day_key outside
+ * [0, 2^48); a null or misaligned workspace or workspace_bytes below the query's value.  MFG_EUNSUPPORTED: width > 64. */
+#define MFG_DEMOS_BOOT_MAX_R 1024
+#define MFG_DEMOS_BOOT_TAG 0xB007u
+#define MFG_DEMOS_UNIT_AGENT_DAY 0
+#define MFG_DEMOS_UNIT_AGENT 1
+#define MFG_DEMOS_BOOT_TABLE                                                                                      \
+  { 1580030168u, 3160060337u, 3950075421u, 4213413783u, 4279248373u, 4292415291u, 4294609777u, 4294923276u, 4294962463u, \
+    4294966817u, 4294967252u, 4294967292u }
+typedef struct mfg_demos_boot {
+  const int32_t* topic;
+  const int32_t* rank;
+  float* state;
+  float* action;
+  int32_t* counts;
+  int32_t* moves;
+  int32_t* present;
+  int32_t* left;
+  int32_t* entered;
+  int32_t* status;
+  void* workspace;
+  size_t workspace_bytes;
+  mfg_stream_t stream;
+  int64_t U;
+  uint64_t seed;
+  int64_t day_offset;
+  int32_t N, H;
+  int32_t C, d;
+  int32_t width, R;
+  int32_t rank_rows, unit;
+  int32_t empty_row, groups;
+} mfg_demos_boot_t;
+size_t mfg_demos_bootstrap_workspace_bytes(int R, int N, int H, int C, int width);
+int mfg_demos_bootstrap(const mfg_demos_boot_t* boot);
+
+/* Bands over replicates: x [R, cells] fp32 (member r of cell c at x[r cells + c]; e.g. the state or action of
+ * mfg_demos_bootstrap flattened), per cell over its R values
+ *   mean [cells], std [cells] fp64: s = x[0] + x[1] + ... in the order r = 0 .. R - 1 in fp64, mean = s / R; then
+ *   q = sum_r (x[r] - mean)^2 in the same order, every operation rounded on its own, std = sqrt(q / R) (ddof 0);
+ *   quant [Q, cells] fp32: the order statistic of 0-based rank ranks[q] among the R values -- an element, not an interpolation
+ *   (the convention of mfg_forecast_pop); ranks may repeat and need not be sorted.
+ * A cell with a NaN in any replicate is NaN in all three.  mean, std and quant may each be NULL (quant only with Q = 0).  One
+ * launch on bands->stream (a workgroup per 16 cells, their R values in LDS); nothing is allocated or synchronised.
+ * MFG_EINVAL: a null descriptor or x, R outside [1, MFG_DEMOS_BOOT_MAX_R], cells < 0, Q outside [0, MFG_FORECAST_MAX_RANKS],
+ * Q > 0 without quant, a rank outside [0, R). */
+typedef struct mfg_replicate_bands {
+  const float* x;
+  double* mean;
+  double* std;
+  float* quant;
+  mfg_stream_t stream;
+  int64_t cells;
+  int32_t R, Q;
+  int32_t ranks[MFG_FORECAST_MAX_RANKS];
+} mfg_replicate_bands_t;
+int mfg_replicate_bands(const mfg_replicate_bands_t* bands);
+
 #ifdef __cplusplus
 }
 #endif
