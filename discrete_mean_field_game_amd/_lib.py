@@ -356,6 +356,21 @@ SIGNATURES['mfg_demos_bootstrap_workspace_bytes'] = (_sz, [_i32, _i32, _i32, _i3
 SIGNATURES['mfg_demos_bootstrap'] = (_i32, [C.POINTER(DemosBootStruct)])
 SIGNATURES['mfg_replicate_bands'] = (_i32, [C.POINTER(ReplicateBandsStruct)])
 
+MOVES_LOGLIK_MAX_D = 64                         # the d limit of mfg_moves_loglik_pop
+MOVES_LOGLIK_BAD_DATA, MOVES_LOGLIK_ZERO_ALPHA, MOVES_LOGLIK_BAD_POLICY, MOVES_LOGLIK_BAD_SET = 1, 2, 4, 8     # bits of status[k, n]
+
+
+class MovesLoglikStruct(C.Structure):
+    """mfg_moves_loglik_t of include/mfg_hip.h: the descriptor of one mfg_moves_loglik_pop call; the stream is a member."""
+    _fields_ = ([(n, C.c_void_p) for n in ('state', 'moves', 'set_index', 'theta', 'shift', 'alpha_scale', 'll', 'll_day', 'grad',
+                                           'grad_day', 'status', 'workspace')]
+                + [('workspace_bytes', C.c_size_t), ('stream', C.c_void_p), ('state_stride', C.c_int64), ('moves_stride', C.c_int64)]
+                + [(n, C.c_int32) for n in ('N', 'H', 'd', 'width', 'sets', 'policies')])
+
+
+SIGNATURES['mfg_moves_loglik_workspace_bytes'] = (_sz, [_i32, _i32, _i32, _i32, _i32])
+SIGNATURES['mfg_moves_loglik_pop'] = (_i32, [C.POINTER(MovesLoglikStruct)])
+
 _lib = None
 
 

@@ -2274,3 +2274,98 @@ def replicate_bands(x, ranks=()):
         b.ranks[q] = rank
     L.check(L.lib().mfg_replicate_bands(C_.byref(b)), 'mfg_replicate_bands')
     return mean, std, quant
+
+
+MOVES_LOGLIK_OUTPUTS = ('ll', 'll_day', 'grad', 'grad_day', 'status')
+
+
+def check_moves_loglik_args(state_shape, moves_shape, K, d, set_index_len=None):
+    """The argument rules of moves_loglik_pop that need no GPU (ValueError), the limits of mfg_moves_loglik_pop: state [N, H, d]
+    with moves [N, H-1, width, width], or both with a leading S (the data sets); 1 <= d <= 64, d <= width, H >= 2,
+    1 <= K <= POP_MAX_K, set_index of K entries.  Returns (S, N, H, d, width)."""
+    state_shape, moves_shape = tuple(int(s) for s in state_shape), tuple(int(s) for s in moves_shape)
+    if len(state_shape) not in (3, 4) or len(moves_shape) != len(state_shape) + 1:
+        raise ValueError('state %s / moves %s: expected [N, H, d] with [N, H-1, width, width], or both with a leading S'
+                         % (state_shape, moves_shape))
+    if len(state_shape) == 3:
+        state_shape, moves_shape = (1,) + state_shape, (1,) + moves_shape
+    S, N, H, ds = state_shape
+    d, width, K = int(d), moves_shape[-1], int(K)
+    if not 1 <= d <= L.MOVES_LOGLIK_MAX_D:
+        raise ValueError('d=%d outside [1, %d]' % (d, L.MOVES_LOGLIK_MAX_D))
+    if S < 1 or N < 1 or H < 2:
+        raise ValueError('S=%d, N=%d, H=%d: at least one data set, one day and two hours' % (S, N, H))
+    if ds != d:
+        raise ValueError('state %s: the last axis is the policy\'s input, d=%d' % (state_shape, d))
+    if moves_shape != (S, N, H - 1, width, width):
+        raise ValueError('moves %s: expected %s' % (moves_shape, (S, N, H - 1, width, width)))
+    if d > width:
+        raise ValueError('d=%d > width=%d' % (d, width))
+    if not 1 <= K <= L.POP_MAX_K:
+        raise ValueError('K=%d policies: at least 1, at most %d in one call' % (K, L.POP_MAX_K))
+    if N * (H - 1) > 2 ** 31 - 1:
+        raise ValueError('N (H - 1) = %d > 2^31 - 1' % (N * (H - 1)))
+    if set_index_len is not None and int(set_index_len) != K:
+        raise ValueError('set_index: %d entries for K=%d policies' % (set_index_len, K))
+    return S, N, H, d, width
+
+
+def moves_loglik_workspace_bytes(K, S, N, H, d):
+    """mfg_moves_loglik_workspace_bytes: needs the library, no GPU."""
+    nbytes = int(L.lib().mfg_moves_loglik_workspace_bytes(int(K), int(S), int(N), int(H), int(d)))
+    if nbytes == 0:
+        raise ValueError('moves_loglik_workspace_bytes: K=%d, S=%d, N=%d, H=%d, d=%d outside the limits of mfg_moves_loglik_pop'
+                         % (K, S, N, H, d))
+    return nbytes
+
+
+def moves_loglik_shapes(K, N, H):
+    """name -> (shape, dtype) of the outputs of moves_loglik_pop."""
+    return {'ll': ((K, N, H - 1), torch.float64), 'll_day': ((K, N), torch.float64), 'grad': ((K, N, H - 1, 3), torch.float64),
+            'grad_day': ((K, N, 3), torch.float64), 'status': ((K, N), torch.int32)}
+
+
+def moves_loglik_pop(state, moves, thetas, shifts, alpha_scales, d, set_index=None, grad=True, *, out=None, workspace=None):
+    """The Dirichlet-multinomial log-likelihood of counted moves under K policies (mfg_moves_loglik_pop; the definitions are in
+    include/mfg_hip.h): state [N, H, d] fp32 and moves [N, H-1, width, width] int32 (one data set), or [S, N, H, d] and
+    [S, N, H-1, width, width] with set_index [K] int32, the data set of each policy (None: all 0; an entry outside [0, S) is
+    marked on the device, status bit 3, and reads nothing).  thetas, shifts, alpha_scales [K] fp64 device tensors.  Returns a
+    dict of device tensors: ll [K, N, H-1], ll_day [K, N], grad [K, N, H-1, 3], grad_day [K, N, 3] in the order (theta, shift,
+    ln alpha_scale) -- both None with grad=False --, status [K, N] int32.  out: a dict of tensors to write into; workspace: a
+    device buffer of at least moves_loglik_workspace_bytes bytes.  Nothing is synchronised."""
+    import ctypes as C_
+    _chk_f32(state, 'state')
+    _chk_i32(moves, 'moves')
+    for name, t in (('thetas', thetas), ('shifts', shifts), ('alpha_scales', alpha_scales)):
+        _chk_f64(t, name)
+    K = int(thetas.numel())
+    if shifts.numel() != K or alpha_scales.numel() != K:
+        raise ValueError('thetas, shifts, alpha_scales: %d, %d, %d entries' % (K, shifts.numel(), alpha_scales.numel()))
+    if set_index is not None:
+        _chk_i32(set_index, 'set_index')
+    S, N, H, d, width = check_moves_loglik_args(state.shape, moves.shape, K, d, None if set_index is None else set_index.numel())
+    dev = state.device
+    nbytes = moves_loglik_workspace_bytes(K, S, N, H, d)
+    if workspace is None:
+        workspace = torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=dev)
+    res = {}
+    for name, (shape, dtype) in moves_loglik_shapes(K, N, H).items():
+        if not grad and name in ('grad', 'grad_day'):
+            res[name] = None
+            continue
+        t = None if out is None else out.get(name)
+        if t is None:
+            t = torch.empty(shape, dtype=dtype, device=dev)
+        elif not (t.is_cuda and t.dtype == dtype and t.is_contiguous() and tuple(t.shape) == shape):
+            raise ValueError('out[%r]: expected a contiguous %s CUDA tensor of shape %s' % (name, dtype, shape))
+        res[name] = t
+    f = L.MovesLoglikStruct()
+    f.state, f.moves, f.set_index = state.data_ptr(), moves.data_ptr(), _ptr(set_index)
+    f.theta, f.shift, f.alpha_scale = thetas.data_ptr(), shifts.data_ptr(), alpha_scales.data_ptr()
+    for name in MOVES_LOGLIK_OUTPUTS:
+        setattr(f, name, _ptr(res[name]))
+    f.workspace, f.workspace_bytes, f.stream = workspace.data_ptr(), workspace.numel() * workspace.element_size(), _stream()
+    f.state_stride, f.moves_stride = N * H * d, N * (H - 1) * width * width
+    f.N, f.H, f.d, f.width, f.sets, f.policies = N, H, d, width, S, K
+    L.check(L.lib().mfg_moves_loglik_pop(C_.byref(f)), 'mfg_moves_loglik_pop')
+    return res

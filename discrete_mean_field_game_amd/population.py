@@ -1146,6 +1146,13 @@ class _Population:
         """The learners that have not failed, in order."""
         return self._act.healthy()
 
+    def loglik(self, demos, days=None):
+        """The Dirichlet-multinomial log-likelihood of the moves of `demos` (a demos.Demonstrations; days: None for all) under
+        the K learners' current policies (theta_k, shift_k, alpha_scale_k), in one call: a likelihood.LogLik with ll [K, N, H-1],
+        ll_day [K, N], grad_day [K, N, 3], status [K, N] and total(days)."""
+        from . import likelihood
+        return likelihood.loglik(demos, self._theta.reshape(-1), self.shifts, self.alpha_scales, days, device=self.device)
+
     def _buffers(self):
         K, B, d, T = self.K, self.batch, self.d, self.episode_steps
         if self._bufs is None:

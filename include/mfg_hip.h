@@ -1519,6 +1519,73 @@ typedef struct mfg_replicate_bands {
 } mfg_replicate_bands_t;
 int mfg_replicate_bands(const mfg_replicate_bands_t* bands);
 
+/* The Dirichlet-multinomial (Polya) likelihood of the counted moves under each of a population of policies: how probable the
+ * integer moves of mfg_demos_from_logs / mfg_demos_bootstrap / mfg_agents_step_pop are under (theta, shift, alpha_scale), in
+ * closed form -- no sampling, no floor; a zero count is an ordinary outcome, and a row of 3 agents weighs less than a row of
+ * 300 000.  Under the policy row i of the action is Dirichlet(a_i.) and the n_i agents of topic i each draw from that row.
+ *   Data.  `sets` data sets, data set s at state + s state_stride and moves + s moves_stride (in elements; not read when
+ *   sets = 1): state [N, H, d] fp32, the policy's input as the forward learners see it; moves [N, H-1, width, width] int32, of
+ *   which only the corner i, j < d is read (d <= width).  set_index [policies] int32 says which data set policy k is held
+ *   against; NULL: all 0.  (sets = 1: a grid search; sets = R with set_index[k] = k: one policy per bootstrap replicate.)
+ *   Policy k: theta[k], shift[k], alpha_scale[k], three device fp64 arrays.
+ *   Value.  Policy k, day n, transition h, row i, m_j = moves[n,h,i,j] and pi = state[n,h,.], j < d:
+ *     n_i = sum_{j<d} m_j               (the agents that stay inside the d topics: the likelihood is conditional on that)
+ *     x_j = (double)pi_j - (double)pi_i - shift,   a_j = alpha_scale * log1p(exp(theta * x_j))   (as mfg_policy_logpdf, no floor)
+ *     A   = a_0 + ... + a_{d-1}, summed in column order
+ *     T(a, m) = ln Gamma(a + m) - ln Gamma(a) = sum_{t<m} ln(a + t);  T(a, 0) = 0 exactly for every a >= 0, T(0, m > 0) = -inf
+ *     ll_row = lgamma(n_i + 1) - sum_j lgamma(m_j + 1) + sum_j T(a_j, m_j) - T(A, n_i);  a row with n_i = 0 contributes exactly 0
+ *     ll [policies, N, H-1]:  ll[k,n,h] = sum_i ll_row, in the order i = 0 .. d - 1 in fp64, every addition rounded on its own
+ *     ll_day [policies, N]:   ll[k,n,0] + ... + ll[k,n,H-2], in that order in fp64, every addition rounded on its own
+ *   Gradient.  D(a, m) = psi(a + m) - psi(a) = sum_{t<m} 1 / (a + t), D(a, 0) = 0:
+ *     d ll_row / d p = sum_j D(a_j, m_j) da_j/dp - D(A, n_i) sum_j da_j/dp,   with s_j = e^(theta x_j) / (1 + e^(theta x_j)):
+ *     da_j/dtheta = alpha_scale s_j x_j,   da_j/dshift = -alpha_scale s_j theta,   da_j/dln(alpha_scale) = a_j
+ *     grad [policies, N, H-1, 3] and grad_day [policies, N, 3] in the order (theta, shift, ln alpha_scale), summed as the
+ *     value is.  Both NULL: no gradient is formed.
+ *   T and D are evaluated without the difference of two ln Gamma or two digamma values (at a ~ 1e5 and a handful of agents that
+ *   difference loses ten digits): the first terms as the finite sums themselves -- all of them for m <= 8, else those that bring
+ *   a to 16 --, the remaining terms from the two ends' asymptotic series combined through log1p(m / a).
+ *   Failures are marked, not raised.  status [policies, N] int32, the OR over the day's transitions of
+ *     bit 0 (1): a negative move in the corner (the failed-member mark of mfg_agents_step_pop) or a non-finite entry of
+ *                state[n,h,0..d-1]: the value and gradient of that transition and of the day are NaN;
+ *     bit 1 (2): some a_j = 0 with m_j > 0: the value is -inf, the gradient NaN;
+ *     bit 2 (4): theta, shift or alpha_scale not finite, or alpha_scale <= 0: everything of that policy is NaN;
+ *     bit 3 (8): set_index[k] outside [0, sets): marked on the device, nothing is read, everything of that policy is NaN.
+ *   (theta x_j above 709 overflows the softplus as in mfg_policy_logpdf: NaN, no bit.)  Every NaN written is the canonical one.
+ *   Independence: the outputs of policy k are the same bits alone, among any other policies, in any order and however the
+ *   policies are split over calls.
+ *   Launches, all on loglik->stream: one pass over the rows of the data (the multinomial coefficients, which no policy
+ *   changes), the cell pass (a lane per policy and row, 64 / d policies to a wavefront), the pass over the days.
+ *   Nothing is allocated or synchronised; the call can be captured.
+ *   workspace: mfg_moves_loglik_workspace_bytes(policies, sets, N, H, d) bytes (0 for arguments outside the limits), 8-byte
+ *   aligned; contents are scratch, and every word the call reads it has written first.
+ * Checked before anything is launched.  MFG_EINVAL: a null descriptor, state, moves, parameter array, ll, ll_day or status;
+ * exactly one of grad / grad_day; policies outside [1, MFG_POP_MAX_K]; N < 1; H < 2; d outside [1, 64]; d > width; sets < 1;
+ * N (H - 1) > 2^31 - 1 or more rows than one launch covers; with sets > 1 a stride below one data set; a null or misaligned
+ * workspace.  MFG_EWORKSPACE: workspace_bytes below the query's value. */
+typedef struct mfg_moves_loglik {
+  const float* state;
+  const int32_t* moves;
+  const int32_t* set_index;
+  const double* theta;
+  const double* shift;
+  const double* alpha_scale;
+  double* ll;
+  double* ll_day;
+  double* grad;
+  double* grad_day;
+  int32_t* status;
+  void* workspace;
+  size_t workspace_bytes;
+  mfg_stream_t stream;
+  int64_t state_stride;
+  int64_t moves_stride;
+  int32_t N, H;
+  int32_t d, width;
+  int32_t sets, policies;
+} mfg_moves_loglik_t;
+size_t mfg_moves_loglik_workspace_bytes(int policies, int sets, int N, int H, int d);
+int mfg_moves_loglik_pop(const mfg_moves_loglik_t* loglik);
+
 #ifdef __cplusplus
 }
 #endif
